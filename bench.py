@@ -25,13 +25,20 @@ selected workload (N times the users and ratings) AND, next to it, the north sta
 experiment as the sub-record `strong_10Mx1M` (configs[3]: the SAME device-generated 10M x 1M x 200
 matrix at every N, N = 1 included; --no-strong skips it).
 
-Timing: W warm-up steps, then untimed steps until >= 50 ms have gone by since start-up (`prewarm_ms`:
-the clocks ramp for the first ~20 ms after an idle period), then R blocks of EXACTLY K steps, each
-bracketed by barrier + synchronize; `ms_per_step` / `value` are the MEDIAN block (min / max beside it).
+Timing: W warm-up steps and P = 256 more untimed steps (`--prewarm-steps`: a fresh chain needs ~250 steps
+to reach its steady rate), then ONE block of exactly K timed steps bracketed by barrier + synchronize
+(`ms_per_step` = block / K).  Same arguments, same inputs and the same W + P + K steps on the timed chain,
+so what it leaves behind is the same from run to run.  `--prewarm-ms T` adds untimed steps until T ms have
+gone by (speed-dependent), `--repeats R` times R blocks of K steps (0: as many as fill `--window-s`) and
+reports the MEDIAN block (min / max beside it).
 
-Prints ONE JSON line (rank 0) with `roofline` (the dominant kernel = the per-column sampler, timed
-with HIP events on its own stream inside the library) and `cpu_baseline` (oracle/cpu_baseline.py: the
-oracle's OpenMP build on this box's host cores, in a process of its own).
+A plain run prints ONE JSON line (rank 0): the headline, `roofline` (the dominant kernel = the
+per-column sampler, timed with HIP events on its own stream inside the library during the timed steps)
+and `handover`.  `--dump-outputs DIR` writes what the timed path computed in its last step as
+DIR/<name>.npy (float64).  `--full` adds what takes runs of its own: `parity` (a chain through the same
+pipeline against the oracle's), `strong_10Mx1M`, `bpmf_exe`, `configs` (the other single-GPU
+configurations, one child run each) and `cpu_baseline` (oracle/cpu_baseline.py: the oracle's OpenMP
+build on the host cores, in a process of its own).
 """
 import argparse
 import glob
@@ -344,6 +351,28 @@ def timed_blocks(step_block, fence, steps, dist_max, min_blocks=5, max_blocks=40
             return times
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs DIR: every array as DIR/<name>.npy in float64, DUMP_BUDGET_BYTES in all.  An array above its equal share of
+    the budget is stored as a fixed, seeded sample of its rows (ascending; the same rows for the same shape), so that two builds
+    run with the same arguments can be compared output for output.  Returns {name: [shape written, rows sampled or None]}."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        sampled = None
+        if a.nbytes > share and a.shape[0] > 0:
+            n = max(1, share // (a.nbytes // a.shape[0]))
+            rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=n, replace=False))
+            a, sampled = a[rows], int(n)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+        out[name] = [list(a.shape), sampled]
+    return out
+
+
 METRIC = "user+item column samples/sec per Gibbs iter; test RMSE vs reference"
 
 
@@ -505,7 +534,8 @@ class Ranks:
 
     def init(self):
         import torch
-        torch.cuda.set_device(self.local_rank)
+        if not self.shared_gpu:                         # (shared GPU: gloo needs no device; run() opens it after the preflight)
+            torch.cuda.set_device(self.local_rank)
         if self.dist:
             import torch.distributed as dist
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29531")
@@ -761,8 +791,8 @@ def config_leg(name, what, steps, warmup, limit_s):
     """One entry of the line's `configs` object: ms_per_step / value / dtype / kernels / per-side launch times / roofline /
     parity of workload `name`, measured by a child run of this script through the same `step_block` and `timed_blocks`."""
     t0 = time.perf_counter()
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", str(warmup),
-           "--no-strong", "--no-bpmf-exe", "--no-configs", "--cpu-parity-only", "--window-s", "2.0"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", str(steps), "--warmup", str(warmup), "--full",
+           "--no-strong", "--no-bpmf-exe", "--no-configs", "--cpu-parity-only", "--repeats", "0", "--window-s", "2.0"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
@@ -846,8 +876,8 @@ def self_launch(n):
     """`bench.py --gpus N` without a launcher: start the N ranks (one process per GPU) and relay their exit code."""
     import socket
     shared = os.environ.get("BPMF_BENCH_SHARED_GPU") == "1"
-    have = visible_devices()
-    if have < n and not shared:
+    have = None if shared else visible_devices()         # (the shared-GPU set-up: this process does not open the device at all)
+    if not shared and have < n:
         raise SystemExit("bench.py: --gpus %d asked for, %d HIP device(s) visible: refusing to report fewer ranks as %d GPUs "
                          "(one rank per GPU; a launcher may set WORLD_SIZE / RANK / LOCAL_RANK instead)" % (n, have, n))
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -903,11 +933,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--K", type=int, default=None, help="shorthand: ML-1M shape with this K (32, 64, 128)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed blocks of --steps steps (0 = auto: as many as fill --window-s of timed time, at least 5)")
+    ap.add_argument("--full", action="store_true", help="also the records that take runs of their own: parity chain, strong_10Mx1M, bpmf_exe, "
+                                                         "configs, cpu_baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks of --steps steps, the median block is reported (0 = auto: as many as fill "
+                                                           "--window-s of timed time, at least 5)")
     ap.add_argument("--window-s", type=float, default=2.5, help="timed time the blocks must add up to when --repeats is 0 (the median block is reported)")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (the other single-GPU BASELINE configurations, one child run each)")
     ap.add_argument("--cpu-parity-only", action="store_true", help="the CPU leg runs the oracle's parity chain only (no timing sweep): what the `configs` children use")
-    ap.add_argument("--prewarm-ms", type=float, default=50.0, help="untimed steps until this much time has passed (0: the W warm-up steps only)")
+    ap.add_argument("--prewarm-steps", type=int, default=256, help="untimed steps after the W warm-up steps (a fixed count: the timed chain "
+                                                                   "does not depend on the speed)")
+    ap.add_argument("--prewarm-ms", type=float, default=0.0, help="then untimed steps until this much time has passed since the warm-up began "
+                                                                "(the timed chain then depends on the speed)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the `parity` object (the -i N -b B chain through the timed pipeline against the oracle's chain)")
     ap.add_argument("--no-bpmf-exe", action="store_true", help="skip the bpmf_exe sub-record (the `bpmf` executable on the same matrices)")
@@ -970,10 +1007,16 @@ def run(args, wl, R, wd):
     from bpmf_amd.sys import Sys
 
     world, rank, local_rank = R.world, R.rank, R.local_rank
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a HIP device (bpmf_amd has no CPU fallback)")
-    if torch.cuda.device_count() <= local_rank:
-        raise SystemExit("bench.py: rank %d wants device %d, %d visible" % (rank, local_rank, torch.cuda.device_count()))
+
+    def open_device():
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a HIP device (bpmf_amd has no CPU fallback)")
+        if torch.cuda.device_count() <= local_rank:
+            raise SystemExit("bench.py: rank %d wants device %d, %d visible" % (rank, local_rank, torch.cuda.device_count()))
+    # The shared-GPU test set-up (BPMF_BENCH_SHARED_GPU=1: every rank on device 0, gloo for the launcher's collectives) opens the
+    # device only after the preflight ladder, so that N ranks and their N preflight children never hold the one GPU all at once.
+    if not R.shared_gpu:
+        open_device()
     wd.stage("process group", max(wd.default, 300.0))
     R.init()
     comm = None
@@ -987,6 +1030,9 @@ def run(args, wl, R, wd):
             R.finish()
             raise SystemExit(2)
         wd.extra["exchange_config"] = exchange_config
+    if R.shared_gpu:
+        open_device()
+        torch.cuda.set_device(local_rank)
     wd.stage("matrices + engine + communicator", max(wd.default, 300.0))
 
     mult = world if (world > 1 or force_dist) else 1
@@ -1068,13 +1114,15 @@ def run(args, wl, R, wd):
             users.predict_finish()
 
     wd.stage("warm-up")
-    # warm-up: W steps, then by TIME -- a 20-step timed region straight after start-up otherwise sits
-    # on the clock ramp (round 1: 0.122 ms per step measured by the driver against 0.102 steady state)
+    # warm-up: W steps, then P more untimed steps on the same chain -- a fresh pair of sides needs ~250 steps to reach its steady
+    # rate even on a warm GPU (ML-1M shape: 0.116 ms per step in the first 20, 0.100 from ~240 on), and a 20-step timed region
+    # straight after start-up also sits on the clock ramp (round 1: 0.122 against 0.102).  P is a fixed count, so the timed chain
+    # runs the same W + P + K steps on every run; --prewarm-ms T adds untimed steps until T ms have gone by (speed-dependent).
     t_warm = time.perf_counter()
-    if args.warmup > 0:
-        step_block(args.warmup)
+    if args.warmup + args.prewarm_steps > 0:
+        step_block(args.warmup + args.prewarm_steps)
     fence()
-    extra = 0
+    extra = args.prewarm_steps
     while dist_max(time.perf_counter() - t_warm) < args.prewarm_ms * 1e-3:
         step_block(max(1, min(args.steps, 50))); extra += max(1, min(args.steps, 50))
         fence()
@@ -1087,6 +1135,13 @@ def run(args, wl, R, wd):
         times = timed_blocks(step_block, fence, args.steps, dist_max, window_s=args.window_s)
     fence()
     dt = float(np.median(times))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: both factor matrices, the test set's running average
+        # prediction and the step's RMSE pair (before the extra predict below, which is not part of a step)
+        dumped = dump_outputs(args.dump_outputs, {"U": users.items(), "V": movies.items(),
+                                                  "test_pred_avg": eng.test_get(movies.test)[0] if movies.test is not None else np.zeros(0),
+                                                  "rmse": np.array([movies.rmse, movies.rmse_avg])})
 
     # roofline of the dominant kernel (the sampler), per launch, this rank's shard
     nnz_m = movies.local_nnz; nnz_u = users.local_nnz
@@ -1224,7 +1279,10 @@ def run(args, wl, R, wd):
         # true iff the oracle has been diffed against dumps of the real reference build (oracle/build_ref.sh +
         # tests/test_oracle_vs_ref.py, which leaves the marker); false: "parity unpinned" 
         "oracle_pinned": os.path.exists(os.path.join(ROOT, "oracle", "_ref", "PINNED")),
+        "full": bool(args.full),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if args.ablate is not None:
         out["ablate"] = args.ablate
         out["invalid"] = "BPMF_HIP_ABLATE=%d: phases of the sampler were skipped, the samples are wrong; a profiling run, not a throughput" % args.ablate
@@ -1238,6 +1296,8 @@ def run(args, wl, R, wd):
     gpu_chain, parity_cfg, parity_skip = None, ((20, 5) if K <= 32 else (6, 2)), None
     if world != 1:
         parity_skip = "N > 1: the chain parity of the sharded path is tests/test_gpu_multirank.py's; this object is the N = 1 record's"
+    elif not args.full:
+        parity_skip = "not run (a plain run times the headline only; bench.py --full runs the chain against the oracle's)"
     elif args.no_parity or args.no_cpu_baseline:
         parity_skip = "skipped (--no-parity / --no-cpu-baseline: no oracle chain to compare with)"
     elif args.ablate is not None:
@@ -1261,7 +1321,7 @@ def run(args, wl, R, wd):
         pass
     del movies, users
 
-    if not args.no_strong and wl == "ml1m":
+    if args.full and not args.no_strong and wl == "ml1m":
         wd.stage("strong_10Mx1M record", wd.default + 120)
         try:
             out["strong_10Mx1M"] = strong_10Mx1M(R, args.strong_steps, args.strong_scale)
@@ -1273,13 +1333,13 @@ def run(args, wl, R, wd):
                     print(json.dumps(out), flush=True)
                 sys.stdout.flush()
                 os._exit(5 if rank == 0 else 0)
-    if rank == 0 and world == 1 and wl == "ml1m" and not args.no_bpmf_exe:
+    if args.full and rank == 0 and world == 1 and wl == "ml1m" and not args.no_bpmf_exe:
         wd.stage("bpmf executable", 330)
         out["bpmf_exe"] = bpmf_exe_record(M, T, nusers, nmovies, K, nsims=400)      # (0.1 ms per iteration: a 25-iteration run is all start-up)
         if out["bpmf_exe"].get("steady_items_per_s"):
             out["bpmf_exe"]["over_python_host"] = out["bpmf_exe"]["steady_items_per_s"] / out["value"]
     # (a run without the CPU leg is a development / test run: no configs legs either -- their parity objects need the oracle's chain)
-    if rank == 0 and world == 1 and wl == "ml1m" and not args.no_configs and not args.no_cpu_baseline and args.ablate is None:
+    if args.full and rank == 0 and world == 1 and wl == "ml1m" and not args.no_configs and not args.no_cpu_baseline and args.ablate is None:
         # every other single-GPU configuration of BASELINE.json in the SAME line: driver-timed, not builder-run
         out["configs"] = {}
         leg_limit = float(os.environ.get("BPMF_BENCH_CONFIG_LEG_TIMEOUT_S", "150"))
@@ -1291,7 +1351,7 @@ def run(args, wl, R, wd):
                 out["configs"][name] = {"what": what, "value": None, "error": repr(e)[:400]}
     if rank == 0:
         wd.stage("cpu baseline", 700)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(M, Mt, T, Tt, K, nusers, nmovies, parity=parity_cfg if gpu_chain else None,
                                                    parity_only=args.cpu_parity_only)

@@ -26,7 +26,7 @@ import pytest
 
 from tests import util
 from tests.conftest import ROOT
-from tests.test_gpu_parity import RTOL, check_half_iteration, rel_err, sampler_mode, _one_form_only  # noqa: F401 (fixture)
+from tests.test_gpu_parity import RTOL, check_half_iteration, rel_err, sampler_mode  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -32,16 +32,6 @@ def double_mode(request, monkeypatch):
     an NCCL kernel does, a helper thread per communicator completes the operations after random, rank-dependent delays --
     so that the two communicators and the exchange stream of a rank interleave differently from its peers' (VERDICT r3:
     what the synchronous double serialises away).  Same assertions in both modes."""
-    # the tests that go through a whole `bench.py` / `bpmf` process (tens of seconds each: preflight children, watchdogs) run in
-    # the asynchronous mode only -- the library-level tests below them keep both
-    # (the stalled-rank test: synchronous mode only -- 14 s against 34 s in the asynchronous mode, whose helper threads the abort
-    #  has to wait out; what it checks -- a bounded wait turns a stalled peer into an error record -- does not depend on the mode)
-    if request.node.name.startswith("test_bench_stalled_rank"):
-        if request.param == "async":
-            pytest.skip("synchronous mode only")
-    elif request.param == "sync" and request.node.name.startswith(("test_bench_", "test_bpmf_g2", "test_bounded_staleness_exchange", "test_fp32_context",
-                                                                 "test_reduce_formulation", "test_connectivity_lists", "test_auto_overlap", "test_bounded_staleness_replica_age")):
-        pytest.skip("asynchronous mode only (the mesh / parts / replica-age tests keep both modes)")
     if request.param == "async":
         monkeypatch.setenv("BPMF_RCCL_DOUBLE_ASYNC", "1")
         # The double's helper threads move the data with HIP copies on streams of their own, and HIP maps the streams of a
@@ -108,8 +98,6 @@ def check_against_oracle(oracle, res, dataset, K, nsims, burnin, tol=1e-7, owned
     (2, 64, {}),                                           # slab form, unfused (sharded) launch
 ])
 def test_mesh_exchange_between_two_ranks(oracle, tmp_path, nranks, K, env, double_mode):
-    if double_mode == "sync" and (env or K == 64):
-        pytest.skip("asynchronous mode only (both modes: the default exchange with 2 and with 3 ranks)")
     nsims, burnin = 4, 1
     res = run_ranks(tmp_path, nranks, "mesh", "ml100k", K, nsims, burnin, env)
     check_against_oracle(oracle, res, "ml100k", K, nsims, burnin)
@@ -119,8 +107,6 @@ def test_mesh_exchange_between_two_ranks(oracle, tmp_path, nranks, K, env, doubl
 def test_parts_overlap_between_ranks(oracle, tmp_path, nranks, parts, double_mode):
     """bpmf_hip_side_set_overlap with a peer: the per-part sub-ranges of every rank are all-gathered once, part c travels
     on the exchange stream while part c + 1 is sampled; `heavy`: a 650-rating column that is cut into chunks."""
-    if double_mode == "sync" and (nranks, parts) != (2, 4):
-        pytest.skip("asynchronous mode only (both modes: two ranks, four parts)")
     nsims, burnin = 4, 1
     res = run_ranks(tmp_path, nranks, "parts", "heavy", 32, nsims, burnin, {"BPMF_HIP_OVERLAP": str(parts)})
     check_against_oracle(oracle, res, "heavy", 32, nsims, burnin)
@@ -273,8 +259,8 @@ def test_bench_self_launches_two_ranks_on_the_shared_gpu():
     env = dict(os.environ, BPMF_BENCH_SHARED_GPU="1", BPMF_HIP_RCCL_LIBRARY=DOUBLE, BPMF_BENCH_STRONG_SCALE="0.01")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "1", "--prewarm-ms", "0",
-                        "--strong-steps", "8"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "1",
+                        "--prewarm-ms", "0", "--prewarm-steps", "0", "--strong-steps", "8"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
     assert j["n_gpus"] == 2 and j["rccl_nranks"] == 2 and j["launcher"] == "self" and len(j["per_rank"]) == 2
@@ -321,7 +307,7 @@ def test_bench_stalled_rank_is_an_error_record_not_a_hang(double_mode):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "0", "--repeats", "1", "--prewarm-ms", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "0", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0",
                         "--no-strong"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     took = time.time() - t0
     j = _bench_line(r.stdout)
@@ -345,7 +331,8 @@ def test_bench_under_the_drivers_launcher(double_mode):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "1", "--prewarm-ms", "0", "--strong-steps", "8"],
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0",
+                        "--strong-steps", "8"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     j = _bench_line(r.stdout)
     assert r.returncode == 0 and j is not None and j["value"] and not j.get("error"), (r.stdout[-800:], r.stderr[-3000:])

@@ -21,7 +21,7 @@ def sampler_mode(request):
     single-wave workgroup (k_sample1: what a side with < 20 000 columns runs), 3 = four columns per wave with the factorisation
     on the 4x4x4 MFMA shape (k_sample4: what a bigger side runs).  `auto` picks by size, so the small matrices of these tests
     reach k_sample4 only when it is forced.  K = 64 (slab form + product form) and K = 128 (workgroup form) have one form each:
-    the switch does nothing there and the tests skip the forced runs.  (Rounds 1-4 kept seven more forms behind this switch:
+    the switch does nothing there, and the forced runs check that they still give the oracle's numbers.  (Rounds 1-4 kept seven more forms behind this switch:
     docs/FINDINGS.md.)"""
     import os
     old = os.environ.get("BPMF_HIP_MODE")
@@ -38,11 +38,6 @@ def sampler_mode(request):
 
 def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _one_form_only(K, mode):
-    if K > 32 and mode is not None:
-        pytest.skip("K = %d has one form: BPMF_HIP_MODE does nothing" % K)
 
 
 def half_iteration_pair(oracle, eng, K, M, nrows, other_items, it, alpha=2.0, cov=None, chunk_note=""):
@@ -83,7 +78,6 @@ def test_device_normal_stream(oracle, hip_engine_factory, counter):
 
 @pytest.mark.parametrize("K", [8, 16, 32, 64])
 def test_tiny_first_half_iterations(oracle, hip_engine_factory, K, sampler_mode):
-    _one_form_only(K, sampler_mode)
     M, Mt, T, Tt, nu, nm = util.tiny()
     eng = hip_engine_factory(K)
     rng = np.random.default_rng(K)
@@ -152,7 +146,6 @@ def test_low_rank_columns(oracle, hip_engine_factory, monkeypatch):
 
 @pytest.mark.parametrize("K", [16, 32, 64])
 def test_ml100k_half_iterations(oracle, hip_engine_factory, K, sampler_mode):
-    _one_form_only(K, sampler_mode)
     M, Mt, T, Tt, nu, nm = util.ml100k()
     eng = hip_engine_factory(K)
     rng = np.random.default_rng(100 + K)
@@ -558,14 +551,14 @@ def test_sharded_path_over_rccl_single_rank(tmp_path):
     from tests.conftest import ROOT
     env = dict(os.environ, BPMF_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0"]
     a = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert a.returncode == 0, a.stderr[-2000:]
     t = subprocess.run(cmd, env=dict(env, BPMF_DIST="torch", MASTER_PORT="29534"), cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert t.returncode == 0, t.stderr[-2000:]
     # (one communicator, BPMF_HIP_COMM_STREAMS=1: test_real_rccl_split_parts_and_packed_lists_single_rank[1])
-    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0"],
+    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0"],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert b.returncode == 0, b.stderr[-2000:]
     pick = lambda out: json.loads([l for l in out.splitlines() if l.startswith('{"metric"')][-1])
@@ -674,7 +667,6 @@ def test_real_rccl_split_parts_and_packed_lists_single_rank(streams):
 
 @pytest.mark.parametrize("K", [16, 32, 64])
 def test_propagated_posterior_priors(oracle, hip_engine_factory, K, sampler_mode):
-    _one_form_only(K, sampler_mode)
     """-m / -l of the reference (c++/sample.cpp:157-174,272-277): every column has its own prior
     precision Lambda_i (from a previous run's *-Lambda.ddm); rr = Lambda_i * hp.mu keeps the
     global mu (the loaded per-column mu is never used: SURVEY Q2)."""
@@ -717,7 +709,7 @@ def test_blocking_fallback_paths_give_the_same_chain():
     import subprocess
     import sys
     from tests.conftest import ROOT
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-strong", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0"]
     pick = lambda out: json.loads([l for l in out.splitlines() if l.startswith('{"metric"')][-1])
     runs = []
     for extra in ({}, {"BPMF_HIP_SPIN_MS": "0"},
@@ -733,7 +725,6 @@ def test_blocking_fallback_paths_give_the_same_chain():
 
 @pytest.mark.parametrize("K", [16, 32, 64])
 def test_no_covariance_variant(oracle, hip_engine_factory, K, sampler_mode):
-    _one_form_only(K, sampler_mode)
     """BPMF_NO_COVARIANCE (c++/sample.cpp:300-304) as a run-time switch: only the diagonal of
     Lambda* is factorised."""
     M, Mt, T, Tt, nu, nm = util.ml100k()

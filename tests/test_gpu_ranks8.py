@@ -68,7 +68,7 @@ def test_bench_gpus8_preflight_ladder_and_per_rank_record():
                BPMF_BENCH_PREFLIGHT_TIMEOUT_S="16", BPMF_RCCL_DOUBLE_TIMEOUT_S="8")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--repeats", "1", "--prewarm-ms", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--repeats", "1", "--prewarm-ms", "0", "--prewarm-steps", "0",
                         "--no-strong"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     j = _bench_line(r.stdout)
     assert r.returncode == 0 and j is not None and j["value"] and not j.get("error"), (r.stdout[-800:], r.stderr[-3000:])

@@ -5,6 +5,6 @@ line() { grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.r
 for wl in ml1m_k128 ml1m_k128_f64; do
   for c in 0 256 384 512 768 1024 1536; do
     E=""; [ $c != 0 ] && E="BPMF_HIP_CHUNK=$c"
-    env $E timeout 300 python bench.py --workload $wl --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 60 --warmup 10 2>/dev/null | line "$wl chunk=$c"
+    env $E timeout 300 python bench.py --repeats 0 --workload $wl --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 60 --warmup 10 2>/dev/null | line "$wl chunk=$c"
   done
 done

@@ -7,7 +7,7 @@ for wl in ml1m_k128 ml1m_k128_f64; do
   for ab in 1 9; do
    for lib in tree halfload; do
     E=""; [ $lib = halfload ] && E="BPMF_HIP_LIBRARY=$PWD/bpmf_amd/csrc/variants/halfload.so"
-    env $E BPMF_HIP_F32_RIDERS=0 timeout 300 python bench.py --workload $wl --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 --ablate $ab 2>/dev/null | line "$wl $lib ablate=$ab"
+    env $E BPMF_HIP_F32_RIDERS=0 timeout 300 python bench.py --repeats 0 --workload $wl --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 --ablate $ab 2>/dev/null | line "$wl $lib ablate=$ab"
    done
   done
 done

@@ -4,7 +4,7 @@ line() { grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.r
 for lib in "" base; do
   for ab in 0 1 2; do
     E=""; [ -n "$lib" ] && E="BPMF_HIP_LIBRARY=$PWD/bpmf_amd/csrc/variants/$lib.so"
-    if [ $ab = 0 ]; then env $E python bench.py --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 2>/dev/null | line "${lib:-new} full"
-    else env $E BPMF_HIP_F32_RIDERS=0 python bench.py --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 --ablate $ab 2>/dev/null | line "${lib:-new} ablate=$ab"; fi
+    if [ $ab = 0 ]; then env $E python bench.py --repeats 0 --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 2>/dev/null | line "${lib:-new} full"
+    else env $E BPMF_HIP_F32_RIDERS=0 python bench.py --repeats 0 --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity --steps 50 --warmup 10 --ablate $ab 2>/dev/null | line "${lib:-new} ablate=$ab"; fi
   done
 done

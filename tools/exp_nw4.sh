@@ -6,6 +6,6 @@ line() { grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.r
 for r in 1 2; do
   for lib in tree nw4_3 nw4_4; do
     E=""; [ $lib != tree ] && E="BPMF_HIP_LIBRARY=$PWD/bpmf_amd/csrc/variants/$lib.so"
-    env $E BPMF_HIP_F32_RIDERS=0 timeout 300 python bench.py --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --steps 60 --warmup 10 2>&1 | line "ml1m_k128 $lib"
+    env $E BPMF_HIP_F32_RIDERS=0 timeout 300 python bench.py --repeats 0 --workload ml1m_k128 --no-cpu-baseline --no-strong --no-bpmf-exe --steps 60 --warmup 10 2>&1 | line "ml1m_k128 $lib"
   done
 done

@@ -6,9 +6,9 @@ O=gpurun_out/check; mkdir -p $O
 for what in "$@"; do
 case $what in
 tests) timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -4 $O/pytest.log ;;
-bench) timeout 600 python bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-2500 ;;
-benchfast) timeout 600 python bench.py --no-cpu-baseline > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-2500 ;;
-prof) rm -rf $O/prof; rocprofv3 --kernel-trace -d $O/prof -o r -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/prof.log 2>&1
+bench) timeout 600 python bench.py --full --repeats 0 > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-2500 ;;
+benchfast) timeout 600 python bench.py --full --repeats 0 --no-cpu-baseline > $O/bench.log 2>&1; tail -1 $O/bench.log | cut -c1-2500 ;;
+prof) rm -rf $O/prof; rocprofv3 --kernel-trace -d $O/prof -o r -- python bench.py --full --repeats 0 --steps 20 --warmup 3 --no-cpu-baseline > $O/prof.log 2>&1
       DB=$(find $O/prof -name "*.db" | head -1); python tools/kstats.py $DB | head -12
       python - "$DB" <<'PY'
 import sqlite3, sys

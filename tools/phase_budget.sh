@@ -15,7 +15,7 @@ for ab in 0 1 2 3; do
     DB=$(find /tmp/prof_pmc -name "*.db" | head -1)
     python tools/pmc_dump.py "$DB" pmc "%k_sample1%" >> $F
   done
-  python bench.py --workload ml1m --steps 200 --warmup 20 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity $AB 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('launch (HIP events, 200-step blocks): %.2f us  %s' % (r['launch_ms']*1e3, {k: round(v*1e3,2) for k,v in r['launch_ms_per_side'].items()}))" >> $F
+  python bench.py --repeats 0 --workload ml1m --steps 200 --warmup 20 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity $AB 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('launch (HIP events, 200-step blocks): %.2f us  %s' % (r['launch_ms']*1e3, {k: round(v*1e3,2) for k,v in r['launch_ms_per_side'].items()}))" >> $F
 done
 echo >> $F
 echo "## static ISA budget of one work item (tools/isa_phases.py on the built bpmf_amd/csrc/k32.o; RATINGS=160: a mid-size whole column)" >> $F

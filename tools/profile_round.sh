@@ -8,7 +8,7 @@ O=gpurun_out/profiles; mkdir -p $O; rm -f $O/${R}_pmc_$W.txt
 # the kernel sources these counters belong to (bench.py reports figures of a profile of OTHER sources as stale)
 echo "# kernel-source-sha: $(python -c 'import bench; print(bench.kernel_source_sha())')" > $O/${R}_pmc_$W.txt
 echo "# rocprofv3 --pmc <one group per pass> --kernel-trace -- python bench.py --workload $W --steps 10 --warmup 2 --repeats 1 --prewarm-ms 0 --no-cpu-baseline --no-strong   (per-launch averages of the sampler kernels)" >> $O/${R}_pmc_$W.txt
-CMD="python bench.py --workload $W --no-cpu-baseline --no-strong --no-bpmf-exe"
+CMD="python bench.py --repeats 0 --workload $W --no-cpu-baseline --no-strong --no-bpmf-exe"
 PCMD="python bench.py --workload $W --steps 10 --warmup 2 --repeats 1 --prewarm-ms 0 --no-cpu-baseline --no-strong --no-bpmf-exe --no-parity"
 PAT="%k_sample%"
 PENV=""
@@ -20,7 +20,7 @@ if [ "$W" = "ml1m_k128" ]; then
   echo "# counter passes with BPMF_HIP_F32_RIDERS=0 (kernel serialisation under --pmc; see tools/profile_round.sh)" >> $O/${R}_pmc_$W.txt
 fi
 if [ "$W" = "strong_10Mx1M" ]; then      # the strong-scaling record of the default workload (k_sample4<32> over the device-generated 10M x 1M matrix)
-  CMD="python bench.py --steps 5 --warmup 2 --repeats 1 --prewarm-ms 0 --no-cpu-baseline --no-bpmf-exe --strong-steps 8"
+  CMD="python bench.py --full --steps 5 --warmup 2 --repeats 1 --prewarm-ms 0 --no-cpu-baseline --no-bpmf-exe --strong-steps 8"
   PCMD="$CMD"; PAT="%k_sample4%"
 fi
 rm -rf /tmp/prof_kt; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o kt -- $CMD > $O/${R}_bench_under_rocprof_$W.json 2> /tmp/prof_kt.err
@@ -56,6 +56,6 @@ cat $O/${R}_pmc_$W.txt
 fi
 # the 20-step line AFTER the counter passes, with their file in place: `profiled.current` is true, `traffic` is this source's
 if [ "$PMC" = "1" ]; then cp $O/${R}_pmc_$W.txt profiles/; fi
-if [ "$W" = "strong_10Mx1M" ]; then python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bpmf-exe > $O/${R}_bench20_$W.json 2>/dev/null
-else python bench.py --workload $W --steps 20 --warmup 5 --no-strong --no-cpu-baseline --no-bpmf-exe > $O/${R}_bench20_$W.json 2>/dev/null; fi
+if [ "$W" = "strong_10Mx1M" ]; then python bench.py --full --repeats 0 --steps 20 --warmup 5 --no-cpu-baseline --no-bpmf-exe > $O/${R}_bench20_$W.json 2>/dev/null
+else python bench.py --repeats 0 --workload $W --steps 20 --warmup 5 --no-strong --no-cpu-baseline --no-bpmf-exe > $O/${R}_bench20_$W.json 2>/dev/null; fi
 tail -1 $O/${R}_bench_under_rocprof_$W.json | cut -c1-400

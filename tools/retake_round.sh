@@ -10,8 +10,8 @@ case "$2" in
   c) bash tools/pmc_chembl_by_kernel.sh $R > gpurun_out/${R}_pmc_by_kernel.log 2>&1
      bash tools/phase_budget.sh $R > gpurun_out/${R}_phase_budget.log 2>&1 ;;
   d) # the full bench lines LAST, with the counter files of stages a / b copied to profiles/ (else `profiled.current` is false, `traffic` null)
-     python bench.py > $O/${R}_bench.json 2> $O/${R}_bench.err
-     python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_20steps.json 2>/dev/null
-     for w in ml1m_k64 chembl ml1m_k128 ml1m_k128_f64; do python bench.py --workload $w --steps 20 --warmup 5 --no-strong --no-bpmf-exe > $O/${R}_bench20_full_$w.json 2>/dev/null; done
+     python bench.py --full --repeats 0 > $O/${R}_bench.json 2> $O/${R}_bench.err
+     python bench.py --full --repeats 0 --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_20steps.json 2>/dev/null
+     for w in ml1m_k64 chembl ml1m_k128 ml1m_k128_f64; do python bench.py --full --repeats 0 --workload $w --steps 20 --warmup 5 --no-strong --no-bpmf-exe > $O/${R}_bench20_full_$w.json 2>/dev/null; done
      for f in $O/${R}_bench.json $O/${R}_bench_20steps.json $O/${R}_bench20_full_*.json; do tail -1 $f | cut -c1-160; done ;;
 esac
