@@ -55,6 +55,11 @@ _SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "bpmf_hip_sys_norm": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "bpmf_hip_failed_column": (C.c_int64, [C.c_void_p]),
+    "bpmf_hip_side_samples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
+    "bpmf_hip_side_samples_add": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_samples_count": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_aggr_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_aggr_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

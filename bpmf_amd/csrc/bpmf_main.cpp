@@ -12,6 +12,9 @@
 // 100) is chosen at run time: -d K, else the environment variable BPMF_NUMLATENT, else 32.  Any 1 <= K <= 128, always in the
 // reference's fp64 arithmetic.  --fp32 (or BPMF_HIP_F32=1; K > 64 only) opts into the library's mixed-precision large-K path
 // and says so on stdout: never chosen silently.
+// --topn N (with -o DIR, one GPU): the N unrated items of every user with the highest posterior-mean prediction over the kept
+// samples, and its spread, to DIR/topn.csv (query,rank,candidate,mean,std; 1-based ids in the numbering of the input);
+// --topn-by cols ranks the users of every item instead.  stdout is the same as without it.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -48,7 +51,7 @@ double tick()
 
 void usage()
 {
-    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32]\n"
+    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -68,6 +71,9 @@ void usage()
               << "  [-k]: do not balance the item-to-GPU assignment on work (equal column counts per GPU instead)\n"
               << "  [-r]: redirect stdout to bpmf_<rank>.out (always with more than one GPU)\n"
               << "  [-v]: write every sample (U-<i>.ddm, V-<i>.ddm)\n"
+              << "  [--topn N]: the N unrated items of every user with the highest posterior-mean prediction, with its standard\n"
+              << "              deviation over the kept samples, to DIR/topn.csv (needs -o DIR; one GPU; 1 <= N <= 32)\n"
+              << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -203,6 +209,9 @@ struct Job {
     int K = 32, dtype = BPMF_HIP_F64, nsims = 20, burnin = 5, update_freq = 1, nthrds = -1, nranks = 1;
     double alpha = 2.0, mean_m = 0.0, mean_u = 0.0;
     bool verbose = false, redirect = false, sharded = false;
+    int topn = 0;                                                    // --topn N (0: off)
+    bool topn_by_cols = false;                                       // --topn-by cols: rank the rows (users) of every column (item)
+    std::vector<int32_t> topn_idx; std::vector<double> topn_mean, topn_std;   // queries x N, in the numbering of the run
     std::string odirname;
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
     std::vector<int64_t> bm, bu;                                     // column ranges of the ranks
@@ -245,6 +254,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
         const std::vector<int64_t> cp = slice_ptr(J.Mt, u0, u1);
         const size_t off = (size_t)J.Mt.colptr[(size_t)u0];
         check(bpmf_hip_side_create(ctx, nusers, nmovies, u0, u1, cp.data(), J.Mt.rowidx.data() + off, J.Mt.vals.data() + off, J.mean_u, &users));
+    }
+    if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
+        check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
+        check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     }
     if (J.sharded) {
         check(bpmf_hip_side_set_ranges(movies, J.bm.data()));
@@ -371,6 +384,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
 
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
+        if (J.topn > 0 && iter >= burnin) { check(bpmf_hip_side_samples_add(users)); check(bpmf_hip_side_samples_add(movies)); }
         // (-v: the replicas of both factor matrices are complete on every rank -- the all-gather form of the exchange;
         // users.bcast() / movies.bcast() of c++/bpmf.cpp:202-203 have nothing left to do)
         if (J.verbose && rank == 0) {
@@ -404,6 +418,15 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_side_aggr_finalize(movies, nsamples, J.m_mu.data() + (size_t)K * m0, J.m_lambda.data() + (size_t)K * K * m0));
         }
     }
+    if (J.topn > 0) {                                                // one rank (main refuses -g > 1)
+        const double t0 = tick();
+        bpmf_hip_side *q = J.topn_by_cols ? movies : users, *cand = J.topn_by_cols ? users : movies;
+        const int64_t nq = J.topn_by_cols ? nmovies : nusers;
+        J.topn_idx.resize((size_t)nq * J.topn); J.topn_mean.resize(J.topn_idx.size()); J.topn_std.resize(J.topn_idx.size());
+        check(bpmf_hip_topn(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_idx.data(), J.topn_mean.data(), J.topn_std.data()));
+        std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
+                  << (tick() - t0) * 1e3 << " ms" << std::endl;
+    }
     if (rank == 0) {
         J.elapsed = elapsed; J.rmse_avg = rmse_avg; J.num_predict = num_predict;
         J.average_items_sec = average_items_sec; J.average_ratings_sec = average_ratings_sec;
@@ -426,11 +449,15 @@ int main(int argc, char *argv[])
     if (const char *e = getenv("BPMF_NUMLATENT")) K = atoi(e);
 
     bool fp32 = getenv("BPMF_HIP_F32") && atoi(getenv("BPMF_HIP_F32")) != 0;
-    static const struct option long_opts[] = {{"fp32", no_argument, nullptr, 1000}, {nullptr, 0, nullptr, 0}};
+    static const struct option long_opts[] = {{"fp32", no_argument, nullptr, 1000}, {"topn", required_argument, nullptr, 1001},
+                                              {"topn-by", required_argument, nullptr, 1002}, {nullptr, 0, nullptr, 0}};
+    std::string topn_by = "rows";
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
         switch (ch) {
         case 1000: fp32 = true; break;
+        case 1001: J.topn = atoi(optarg); if (J.topn < 1) die("--topn expects N >= 1"); break;
+        case 1002: topn_by = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -450,6 +477,15 @@ int main(int argc, char *argv[])
         }
     }
     if (fname.empty() || probename.empty()) { usage(); return 1; }
+    // --topn: checked before anything touches a GPU
+    if (topn_by != "rows" && topn_by != "cols") die("--topn-by expects rows or cols, not '" + topn_by + "'");
+    J.topn_by_cols = topn_by == "cols";
+    if (J.topn > 0) {
+        if (J.odirname.empty()) die("--topn needs -o DIR (the lists go to DIR/topn.csv)");
+        if (ngpu > 1) die("--topn runs on one GPU: -g " + std::to_string(ngpu) + " is not supported (the sharded replicas are not complete on every rank)");
+        if (J.topn > 32) die("--topn expects 1 <= N <= 32");
+        if (J.nsims <= J.burnin) die("--topn needs at least one post-burn-in sample (-i > -b)");
+    }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -600,6 +636,26 @@ int main(int argc, char *argv[])
             d.nrows = (int64_t)K * K; d.data.swap(J.m_lambda);
             bpmf::io::write_dense(J.odirname + "/V-Lambda.ddm", d);
         } catch (const std::exception &e) { die(e.what()); }
+    }
+
+    if (J.topn > 0) {                                                // 1-based ids in the ORIGINAL numbering, like the -o writers
+        const std::vector<int64_t> &pq = J.topn_by_cols ? J.perm_m : J.perm_u, &pc = J.topn_by_cols ? J.perm_u : J.perm_m;
+        const int64_t nq = (int64_t)(J.topn_idx.size() / (size_t)J.topn);
+        std::vector<int64_t> order((size_t)nq);                      // queries in original order
+        for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
+        if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
+        FILE *f = fopen((J.odirname + "/topn.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/topn.csv");
+        fprintf(f, "query,rank,candidate,mean,std\n");
+        for (int64_t q : order)
+            for (int r = 0; r < J.topn; ++r) {
+                const size_t at = (size_t)q * J.topn + r;
+                const int32_t c = J.topn_idx[at];
+                if (c < 0) break;                                      // (padding slots are not written)
+                fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), r + 1,
+                        (long long)((pc.empty() ? c : pc[(size_t)c]) + 1), J.topn_mean[at], J.topn_std[at]);
+            }
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
     }
 
     os << "Total time: " << J.elapsed << std::endl;

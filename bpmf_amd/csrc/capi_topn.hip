@@ -1,0 +1,143 @@
+// capi_topn.hip -- sample rings of the sides and the posterior top-N ranking (bpmf_hip_topn; kernels in kernels_topn.h)
+// (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
+#include "capi_internal.h"
+
+using namespace bpmf_capi;
+
+static int ring_kp(const bpmf_hip_ctx *c) { return (c->Kt + 3) / 4 * 4; }
+
+extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
+{
+    if (!s || max_samples < 0) return fail(BPMF_HIP_EINVAL, "samples_reserve: bad argument");
+    bpmf_hip_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(s); if (rc) return rc; }
+    if (s->d_ring) {
+        { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+        (void)hipFree(s->d_ring);
+        s->d_ring = nullptr;
+    }
+    s->ring_max = s->ring_count = 0;
+    if (max_samples == 0) return BPMF_HIP_OK;
+    const int kp = ring_kp(c);
+    const size_t words = (size_t)s->ncols * (size_t)max_samples * (size_t)kp;
+    if (hipMalloc((void **)&s->d_ring, words * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        s->d_ring = nullptr;
+        return fail(BPMF_HIP_ENOMEM, "samples_reserve: " + std::to_string(max_samples) + " samples of " + std::to_string((long long)s->ncols) +
+                    " columns x " + std::to_string(kp) + " doubles (" + std::to_string(words * sizeof(double) >> 20) + " MiB) do not fit in device memory");
+    }
+    HIP_TRY(hipMemsetAsync(s->d_ring, 0, words * sizeof(double), c->stream));
+    s->ring_max = max_samples;
+    s->ring_kp = kp;
+    return BPMF_HIP_OK;
+}
+
+// the current factors into the next slot, ordered like bpmf_hip_side_aggr_add (behind the side's samplers, on its copy)
+extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
+{
+    if (!s) return fail(BPMF_HIP_EINVAL, "samples_add: NULL");
+    if (!s->d_ring) return fail(BPMF_HIP_EINVAL, "samples_add: no sample ring (bpmf_hip_side_samples_reserve)");
+    if (s->ring_count >= s->ring_max) return fail(BPMF_HIP_EINVAL, "samples_add: the ring is full (" + std::to_string(s->ring_max) + " samples)");
+    bpmf_hip_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(s); if (rc) return rc; }
+    bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, s->ring_kp, s->ncols, s->d_ring,
+                             (int64_t)s->ring_max * s->ring_kp, s->ring_count, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->last_sampler_done = nullptr;
+    ++s->ring_count;
+    return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hip_side_samples_count(const bpmf_hip_side *s) { return s ? s->ring_count : 0; }
+
+// the rated candidates of every column of the side, sorted: read back from the device ratings once
+static int build_exclusion(bpmf_hip_side *s)
+{
+    if (s->d_ex_ptr) return 0;
+    if (s->from != 0 || s->to != s->ncols)
+        return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs a query side that holds all its columns (this rank has " +
+                    std::to_string((long long)s->from) + " .. " + std::to_string((long long)s->to) + ")");
+    bpmf_hip_ctx *c = s->ctx;
+    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    const std::vector<int64_t> &cp = s->h_colptr;
+    std::vector<int32_t> rows((size_t)std::max<int64_t>(s->nnz, 1));
+    if (s->nnz > 0) HIP_TRY(hipMemcpy(rows.data(), s->d_rowidx, (size_t)s->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t q = 0; q < s->ncols; ++q) std::sort(rows.begin() + cp[(size_t)q], rows.begin() + cp[(size_t)q + 1]);
+    int rc = dev_upload(&s->d_ex_ptr, cp.data(), cp.size());
+    if (!rc) rc = dev_upload(&s->d_ex_rows, rows.data(), rows.size());
+    if (rc) {
+        if (s->d_ex_ptr) (void)hipFree(s->d_ex_ptr);
+        if (s->d_ex_rows) (void)hipFree(s->d_ex_rows);
+        s->d_ex_ptr = nullptr; s->d_ex_rows = nullptr;
+    }
+    return rc;
+}
+
+extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
+                             int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out)
+{
+    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "topn: NULL side");
+    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "topn: the two sides belong to different contexts");
+    if (n < 1 || n > bpmf_launch::topn_max_n())
+        return fail(BPMF_HIP_EINVAL, "topn: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
+    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "topn: query range out of bounds");
+    const int64_t nq = q_to - q_from;
+    if (nq > 0 && (!idx_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "topn: NULL output");
+    bpmf_hip_ctx *c = query->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(query); if (rc) return rc; }        // every half-iteration in flight on both sides (as bpmf_hip_sys_state)
+    { const int rc = settle_async(cand); if (rc) return rc; }
+    if (!query->d_ring || !cand->d_ring) return fail(BPMF_HIP_EINVAL, "topn: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    const int S = query->ring_count;
+    if (S < 1 || cand->ring_count != S)
+        return fail(BPMF_HIP_EINVAL, "topn: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
+                    std::to_string(cand->ring_count));
+    if (exclude_rated && query->nrows != cand->ncols)
+        return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs the query side's rows to be the candidate side's columns");
+    if (nq == 0) return BPMF_HIP_OK;
+    if (exclude_rated) { const int rc = build_exclusion(query); if (rc) return rc; }
+
+    // candidates split over workgroups when the query blocks alone do not fill the device (a split is a multiple of 64 candidates)
+    const int64_t nc = cand->ncols, nqb = (nq + 63) / 64;
+    int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)c->num_cu + nqb - 1) / nqb, (nc + 255) / 256));
+    const int64_t cspan = ((nc + nsplit - 1) / nsplit + 63) / 64 * 64;
+    nsplit = (nc + cspan - 1) / cspan;
+
+    const size_t pn = (size_t)nq * (size_t)n;
+    double *part_mean = nullptr, *out = nullptr;
+    int32_t *part_idx = nullptr, *out_idx = nullptr;
+    auto release = [&]() {
+        if (part_mean) (void)hipFree(part_mean);
+        if (part_idx) (void)hipFree(part_idx);
+        if (out) (void)hipFree(out);
+        if (out_idx) (void)hipFree(out_idx);
+    };
+    if (hipMalloc((void **)&part_mean, (size_t)nsplit * pn * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&part_idx, (size_t)nsplit * pn * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void **)&out, 2 * pn * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&out_idx, pn * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        release();
+        return fail(BPMF_HIP_ENOMEM, "topn: device allocation of the result lists failed");
+    }
+    bpmf_launch::TopnLaunch p{};
+    p.qring = query->d_ring; p.cring = cand->d_ring;
+    p.qstride = (int64_t)query->ring_max * query->ring_kp; p.cstride = (int64_t)cand->ring_max * cand->ring_kp;
+    p.Kp = query->ring_kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
+    p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
+    p.ex_ptr = exclude_rated ? query->d_ex_ptr : nullptr; p.ex_rows = exclude_rated ? query->d_ex_rows : nullptr;
+    p.part_mean = part_mean; p.part_idx = part_idx;
+    p.out_mean = out; p.out_std = out + pn; p.out_idx = out_idx;
+    bpmf_launch::topn(p, c->stream);
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
+    if (!rc) rc = bounded_stream_sync(c, c->stream, __func__);
+    if (!rc && (hipMemcpy(mean_out, out, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(std_out, out + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(idx_out, out_idx, pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
+    release();
+    return rc;
+}

@@ -92,4 +92,17 @@ void randn_probe(uint32_t counter, int n, double *out_dev, hipStream_t st);
 void aggr_add(const void *items, bool f32, int ld, int K, int64_t c0, int64_t ncols, double *mu, double *lambda, hipStream_t st);   // ld: device leading dimension, K: the caller's num_latent
 void aggr_finalize(int K, int nsamples, int64_t ncols, double *mu, double *lambda, hipStream_t st);
 
+// posterior top-N (kernels_topn.h, ktopn.hip)
+void samples_add(const void *items, bool f32, int ld, int Kt, int Kp, int64_t ncols, double *ring, int64_t stride, int slot, hipStream_t st);
+int topn_max_n();
+struct TopnLaunch {
+    const double *qring, *cring; int64_t qstride, cstride;
+    int Kp, S, n; double mean_rating;
+    int64_t q_from, nq, nc, cspan; int nsplit;
+    const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
+    double *part_mean; int32_t *part_idx;                  // nsplit x nq x n
+    double *out_mean, *out_std; int32_t *out_idx;          // nq x n
+};
+void topn(const TopnLaunch &p, hipStream_t st);             // score + select, merge of the splits, std of the selected pairs
+
 }  // namespace bpmf_launch

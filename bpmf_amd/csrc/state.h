@@ -199,6 +199,10 @@ struct bpmf_hip_side {
     struct bpmf_hip_test *deferred_eval = nullptr;      // evaluation waiting for this side's next gate kernel (flush_deferred)
     double *d_aggr_mu = nullptr, *d_aggr_lambda = nullptr;   // -o: aggrMu (K x nloc) / aggrLambda (K*K x nloc) of the local columns
     double *d_prop = nullptr;            // propagated posterior (-m / -l): K x K prior precision per local column, or NULL
+    // posterior top-N (capi_topn.hip): ring of kept samples, fp64, column c / sample s / row k at c * ring_max * ring_kp + s * ring_kp + k,
+    // and the sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
+    double *d_ring = nullptr; int ring_max = 0, ring_count = 0, ring_kp = 0;
+    int64_t *d_ex_ptr = nullptr; int32_t *d_ex_rows = nullptr;
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
     // K = 64: columns with <= 16 ratings take the product form (k_sample_pf), the rest the slab form --

@@ -240,6 +240,30 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_side_aggr_finalize(side.handle, int(nsamples), _ptr(mu), _ptr(lam)))
         return mu, lam
 
+    # -- posterior top-N ------------------------------------------------------
+    def samples_reserve(self, side, max_samples):
+        """Room for max_samples fp64 copies of the side's factors on the device (0 frees it)."""
+        _lib.check(self.lib.bpmf_hip_side_samples_reserve(side.handle, int(max_samples)))
+
+    def samples_add(self, side):
+        """The current factors into the next slot of the side's sample ring (after a post-burn-in sys_sample)."""
+        _lib.check(self.lib.bpmf_hip_side_samples_add(side.handle))
+
+    def samples_count(self, side):
+        return int(self.lib.bpmf_hip_side_samples_count(side.handle))
+
+    def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
+        """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
+        (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""
+        q_to = query.ncols if q_to is None else int(q_to)
+        nq = max(0, q_to - int(q_from))
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        mean = np.empty((nq, int(n)))
+        std = np.empty((nq, int(n)))
+        _lib.check(self.lib.bpmf_hip_topn(query.handle, cand.handle, float(mean_rating), int(n), int(q_from), int(q_to),
+                                          1 if exclude_rated else 0, _ptr(idx), _ptr(mean), _ptr(std)))
+        return idx, mean, std
+
     def kernel_name(self, side):
         """The kernel(s) one sampler launch of the side consists of, as a profile names them."""
         buf = C.create_string_buffer(512)

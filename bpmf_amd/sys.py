@@ -177,7 +177,8 @@ class Sys:
             Sys.procid, phase, self.iter, self.rmse, self.rmse_avg, norm_u, norm_m, items_per_sec, ratings_per_sec / 1e6)
 
 
-def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=None, keep_samples=False, Tt=None, pipelined=False):
+def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=None, keep_samples=False, Tt=None, pipelined=False,
+          topn=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -186,13 +187,27 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
     pipelined=True: the same iterations the way the `bpmf` executable (bpmf_main.cpp) and bench.py's timed
     region run them -- the line of iteration i - 1 (RMSE sums, norms) is collected after iteration i has been
     enqueued, the evaluation of i - 1 runs beside the samplers of i (which write the other copy of the factors).
-    Same chain, same numbers; `secs` is then the time between two collected lines."""
+    Same chain, same numbers; `secs` is then the time between two collected lines.
+
+    topn=N: every post-burn-in sample of both sides is kept on the device (nsims - burnin slots each) and res["topn"] holds
+    engine.topn(users, movies, ...) after the loop -- (idx, mean, std), [nusers, N] each: the N unrated movies of every user
+    with the highest posterior-mean prediction."""
+    if topn is not None and nsims - burnin < 1:
+        raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
     movies = Sys("movs", engine, M, nmovies, nusers, T=T)
     users = Sys("users", engine, Mt, nusers, nmovies, T=Tt)
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
+    if topn is not None:
+        engine.samples_reserve(movies.side, nsims - burnin)
+        engine.samples_reserve(users.side, nsims - burnin)
+
+    def keep(i):                                     # where the -o aggregation sits (bpmf_main.cpp)
+        if topn is not None and i >= burnin:
+            engine.samples_add(users.side)
+            engine.samples_add(movies.side)
     nnz = movies.local_nnz
 
     def line(it, secs, norm_u, norm_m):
@@ -210,6 +225,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
         for i in range(nsims):
             movies.sample(users)
             users.sample(movies)
+            keep(i)
             if i > 0:
                 norm_m = engine.sys_norm(movies.side, i - 1)
                 norm_u = engine.sys_norm(users.side, i - 1)
@@ -231,6 +247,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
             start = time.perf_counter()
             movies.sample(users)
             users.sample(movies)
+            keep(i)
             movies.predict(users)
             if Tt is not None:
                 users.predict(movies)                # c++/bpmf.cpp:190 (nothing reads its results; Tt = None leaves it out)
@@ -245,6 +262,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
     res["final_rmse_avg"] = movies.rmse_avg
     res["num_predict"] = movies.num_predict
     res["U"] = users.items(); res["V"] = movies.items()
+    if topn is not None:
+        res["topn"] = engine.topn(users.side, movies.side, movies.mean_rating, topn)
     res["movies"], res["users"] = movies, users
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)

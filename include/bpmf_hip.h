@@ -262,6 +262,25 @@ BPMF_API int bpmf_hip_side_aggr_finalize(bpmf_hip_side *side, int nsamples, doub
 /* global id of the first column whose factorisation failed, or -1 */
 BPMF_API int64_t bpmf_hip_failed_column(const bpmf_hip_side *side);
 
+/* ---- posterior top-N ranking --------------------------------------------------
+ * Sample ring of a side: room for max_samples copies of the factor matrix in fp64 (fp32 factors are widened), one column's
+ * samples contiguous: column c, sample s, row k at [c * max_samples * Kp + s * Kp + k], Kp = num_latent rounded up to 4, the
+ * pad rows zero.  _reserve(side, 0) frees it (side_destroy does too); reserving again starts an empty ring.  _add copies the
+ * current factors (every column of the matrix this rank holds) into the next slot: call it where _aggr_add sits, after a
+ * post-burn-in bpmf_hip_sys_sample of both sides; BPMF_HIP_EINVAL once the ring is full. */
+BPMF_API int bpmf_hip_side_samples_reserve(bpmf_hip_side *side, int max_samples);
+BPMF_API int bpmf_hip_side_samples_add(bpmf_hip_side *side);
+BPMF_API int bpmf_hip_side_samples_count(const bpmf_hip_side *side);
+/* For every query column q in [q_from, q_to) of `query` and every column c of `cand`, with both rings holding the same S >= 1
+ * samples: mean = mean_rating + (1/S) sum_s u_s(q) . v_s(c), std = sqrt(sum_s (p_s - mean)^2 / (S - 1)) (0 for S = 1),
+ * p_s = mean_rating + u_s(q) . v_s(c).  Writes the n best candidates by mean (descending; equal means: lower candidate index
+ * first) to the host arrays idx_out / mean_out / std_out, (q_to - q_from) x n row-major; exclude_rated != 0 skips the
+ * candidates q rated in training (its column of the query side's ratings; the query side must hold all its columns).  Slots
+ * beyond the eligible candidates: idx -1, mean 0, std 0.  1 <= n <= 64.  Waits for the half-iterations in flight on both sides.
+ * The mean is the plain mean over the samples added (not the running Pavg of the test-set evaluation). */
+BPMF_API int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
+                           int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
