@@ -60,6 +60,8 @@ _SIGNATURES = {
     "bpmf_hip_side_samples_count": (C.c_int, [C.c_void_p]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_train_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "bpmf_hip_noise_sample": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "bpmf_hip_side_aggr_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_aggr_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -15,6 +15,9 @@
 // --topn N (with -o DIR, one GPU): the N unrated items of every user with the highest posterior-mean prediction over the kept
 // samples, and its spread, to DIR/topn.csv (query,rank,candidate,mean,std; 1-based ids in the numbering of the input);
 // --topn-by cols ranks the users of every item instead.  stdout is the same as without it.
+// --noise adaptive (one GPU, no -g): the noise precision is sampled after every iteration from its Gamma posterior (prior
+// --alpha-prior A0,B0, default 1,1; cap --alpha-max F), -a is its initial value; every iteration line then ends with the alpha
+// it ran with and the training RMSE after it, and -o DIR also gets DIR/alpha.csv.  Without these flags nothing changes.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -51,7 +54,8 @@ double tick()
 
 void usage()
 {
-    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]\n"
+    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -74,6 +78,10 @@ void usage()
               << "  [--topn N]: the N unrated items of every user with the highest posterior-mean prediction, with its standard\n"
               << "              deviation over the kept samples, to DIR/topn.csv (needs -o DIR; one GPU; 1 <= N <= 32)\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
+              << "  [--noise fixed|adaptive]: fixed: alpha = -a throughout (the default); adaptive: alpha is sampled after every\n"
+              << "              iteration from its Gamma posterior given the training residuals, -a is its initial value (one GPU)\n"
+              << "  [--alpha-prior A0,B0]: Gamma prior of the adaptive alpha, shape A0 > 0 and rate B0 >= 0 (1,1)\n"
+              << "  [--alpha-max F]: cap of the adaptive alpha (none)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -212,6 +220,9 @@ struct Job {
     int topn = 0;                                                    // --topn N (0: off)
     bool topn_by_cols = false;                                       // --topn-by cols: rank the rows (users) of every column (item)
     std::vector<int32_t> topn_idx; std::vector<double> topn_mean, topn_std;   // queries x N, in the numbering of the run
+    bool adaptive = false;                                           // --noise adaptive
+    double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
+    std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
     std::string odirname;
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
     std::vector<int64_t> bm, bu;                                     // column ranges of the ranks
@@ -309,12 +320,17 @@ void rank_main(Job &J, int rank, std::ostream &os)
     os << "nsims: " << J.nsims << std::endl;
     os << "burnin: " << J.burnin << std::endl;
     os << "alpha: " << J.alpha << std::endl;
+    if (J.adaptive) {
+        os << "noise: adaptive, alpha ~ Gamma(shape " << J.a0 << ", rate " << J.b0 << ") prior, initial alpha " << J.alpha;
+        if (J.alpha_max > 0.0) os << ", capped at " << J.alpha_max;
+        os << std::endl;
+    }
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
 
     const int nsims = J.nsims, burnin = J.burnin;
-    const double alpha = J.alpha;
+    double alpha = J.alpha;                                          // (--noise adaptive: redrawn after every iteration)
     long double average_items_sec = 0, average_ratings_sec = 0;
     double rmse = NAN, rmse_avg = NAN, se, se_avg;
     int64_t num_predict = 0;
@@ -325,11 +341,23 @@ void rank_main(Job &J, int rank, std::ostream &os)
         const double items_per_sec = (double)(nusers + nmovies) / secs;
         const double ratings_per_sec = (double)J.M.nnz() / secs;
         char buf[1024];
-        snprintf(buf, sizeof buf, "%d: %s iteration %d:\t RMSE: %3.4f\tavg RMSE: %3.4f\tFU(%6.2f)\tFM(%6.2f)\titems/sec: %6.2f\tratings/sec: %6.2fM\n",
-                 rank, (it < burnin) ? "Burnin" : "Sampling", it, rm, rma, std::sqrt(nu), std::sqrt(nm), items_per_sec, ratings_per_sec / 1e6);
-        os << buf << std::flush;
+        int len = snprintf(buf, sizeof buf, "%d: %s iteration %d:\t RMSE: %3.4f\tavg RMSE: %3.4f\tFU(%6.2f)\tFM(%6.2f)\titems/sec: %6.2f\tratings/sec: %6.2fM",
+                           rank, (it < burnin) ? "Burnin" : "Sampling", it, rm, rma, std::sqrt(nu), std::sqrt(nm), items_per_sec, ratings_per_sec / 1e6);
+        if (J.adaptive && it < (int)J.alpha_trace.size() && len > 0 && len < (int)sizeof buf)
+            snprintf(buf + len, sizeof buf - (size_t)len, "\talpha: %.4f\ttrain RMSE: %.4f", J.alpha_trace[(size_t)it], J.train_rmse[(size_t)it]);
+        os << buf << "\n" << std::flush;
         average_items_sec += items_per_sec;
         average_ratings_sec += ratings_per_sec;
+    };
+    // --noise adaptive, after both sides of iteration i: SSE_i on the device, then the alpha of iteration i + 1 on the host.
+    // The pipelined loop waits here once per iteration: iteration i + 1 needs this alpha before its first sampler is enqueued.
+    auto adapt = [&](int i) {
+        double sse = 0.0;
+        int64_t n = 0;
+        J.alpha_trace.push_back(alpha);
+        check(bpmf_hip_train_sse(movies, users, &sse, &n));
+        J.train_rmse.push_back(std::sqrt(sse / (double)n));
+        if (i + 1 < nsims) check(bpmf_hip_noise_sample(J.a0, J.b0, sse, n, i, J.alpha_max, &alpha));
     };
     if (J.odirname.empty() && !J.verbose) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
@@ -340,6 +368,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         for (int i = 0; i < nsims; ++i) {
             check(bpmf_hip_sys_sample(movies, users, alpha));   // movies.sample(users)
             check(bpmf_hip_sys_sample(users, movies, alpha));   // users.sample(movies)
+            if (J.adaptive) adapt(i);
             if (i > 0) {
                 // norms of iteration i-1 (bpmf_hip_sys_norm waits for THAT half-iteration's sums only: asking bpmf_hip_sys_state
                 // here drained each side's pipeline once per iteration -- 83 M against the 100 M samples/s of the same loop
@@ -370,6 +399,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         const double start = tick();
         check(bpmf_hip_sys_sample(movies, users, alpha));       // movies.sample(users)
         check(bpmf_hip_sys_sample(users, movies, alpha));       // users.sample(movies)
+        if (J.adaptive) adapt(i);
         iter = i;
         const int n = (iter < burnin) ? 0 : (iter - burnin);
         check(bpmf_hip_predict_launch(test, movies, users, n));
@@ -450,14 +480,19 @@ int main(int argc, char *argv[])
 
     bool fp32 = getenv("BPMF_HIP_F32") && atoi(getenv("BPMF_HIP_F32")) != 0;
     static const struct option long_opts[] = {{"fp32", no_argument, nullptr, 1000}, {"topn", required_argument, nullptr, 1001},
-                                              {"topn-by", required_argument, nullptr, 1002}, {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows";
+                                              {"topn-by", required_argument, nullptr, 1002}, {"noise", required_argument, nullptr, 1003},
+                                              {"alpha-prior", required_argument, nullptr, 1004}, {"alpha-max", required_argument, nullptr, 1005},
+                                              {nullptr, 0, nullptr, 0}};
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
         switch (ch) {
         case 1000: fp32 = true; break;
         case 1001: J.topn = atoi(optarg); if (J.topn < 1) die("--topn expects N >= 1"); break;
         case 1002: topn_by = optarg; break;
+        case 1003: noise = optarg; break;
+        case 1004: alpha_prior = optarg; break;
+        case 1005: alpha_max = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -485,6 +520,31 @@ int main(int argc, char *argv[])
         if (ngpu > 1) die("--topn runs on one GPU: -g " + std::to_string(ngpu) + " is not supported (the sharded replicas are not complete on every rank)");
         if (J.topn > 32) die("--topn expects 1 <= N <= 32");
         if (J.nsims <= J.burnin) die("--topn needs at least one post-burn-in sample (-i > -b)");
+    }
+    // --noise / --alpha-prior / --alpha-max: checked before anything touches a GPU
+    if (noise != "fixed" && noise != "adaptive") die("--noise expects fixed or adaptive, not '" + noise + "'");
+    J.adaptive = noise == "adaptive";
+    if (!J.adaptive && (!alpha_prior.empty() || !alpha_max.empty())) die("--alpha-prior and --alpha-max need --noise adaptive");
+    if (J.adaptive) {
+        if (!alpha_prior.empty()) {
+            const char *s0 = alpha_prior.c_str();
+            char *e1 = nullptr, *e2 = nullptr;
+            J.a0 = strtod(s0, &e1);
+            if (e1 == s0 || *e1 != ',') die("--alpha-prior expects A0,B0, not '" + alpha_prior + "'");
+            J.b0 = strtod(e1 + 1, &e2);
+            if (e2 == e1 + 1 || *e2 != '\0') die("--alpha-prior expects A0,B0, not '" + alpha_prior + "'");
+            if (!(J.a0 > 0.0) || !(J.b0 >= 0.0) || !std::isfinite(J.a0) || !std::isfinite(J.b0))
+                die("--alpha-prior expects a shape A0 > 0 and a rate B0 >= 0, not '" + alpha_prior + "'");
+        }
+        if (!alpha_max.empty()) {
+            char *e = nullptr;
+            J.alpha_max = strtod(alpha_max.c_str(), &e);
+            if (e == alpha_max.c_str() || *e != '\0' || !(J.alpha_max > 0.0) || !std::isfinite(J.alpha_max))
+                die("--alpha-max expects a number F > 0, not '" + alpha_max + "'");
+        }
+        if (ngpu >= 1) die("--noise adaptive runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sum of the "
+                           "training residuals is not all-reduced over ranks)");
+        if (!(J.alpha > 0.0)) die("--noise adaptive needs an initial alpha -a F > 0");
     }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
@@ -656,6 +716,14 @@ int main(int argc, char *argv[])
                         (long long)((pc.empty() ? c : pc[(size_t)c]) + 1), J.topn_mean[at], J.topn_std[at]);
             }
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
+    }
+
+    if (J.adaptive && !J.odirname.empty()) {
+        FILE *f = fopen((J.odirname + "/alpha.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/alpha.csv");
+        fprintf(f, "iteration,alpha,train_rmse\n");
+        for (size_t i = 0; i < J.alpha_trace.size(); ++i) fprintf(f, "%zu,%.17g,%.17g\n", i, J.alpha_trace[i], J.train_rmse[i]);
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/alpha.csv");
     }
 
     os << "Total time: " << J.elapsed << std::endl;

@@ -6,6 +6,7 @@
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
+//   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>

@@ -387,3 +387,27 @@ extern "C" void bpmf_randn_stream(uint32_t counter, int n, double *out)
     bpmf::MicroPhilox rng(counter);
     for (int i = 0; i < n; ++i) out[i] = randn(rng);
 }
+
+// Adaptive noise precision (bpmf --noise adaptive): alpha_{i+1} = g / (b0 + SSE_i / 2), g ~ Gamma(a0 + n / 2, 1) drawn with
+// libstdc++'s gamma_distribution on the Philox stream BPMF_NOISE_COUNTER(i) (bpmf_hip.h).  Here, beside the Wishart gammas, so that the
+// same compiler settings produce the same bits.  g depends on the shape and the counter only: a restatement that sums SSE in
+// another order differs in the last bits of the rate, never in the rejection branch the draw takes.
+extern "C" int bpmf_hip_noise_sample(double a0, double b0, double sse, int64_t n, int iter, double alpha_max, double *alpha)
+{
+    if (!alpha || !(a0 > 0.0) || !(b0 >= 0.0) || !std::isfinite(a0) || !std::isfinite(b0) || n <= 0 || iter < 0 ||
+        !(sse >= 0.0) || !std::isfinite(sse) || std::isnan(alpha_max)) {
+        bpmf_hip_set_error_("noise_sample: needs a0 > 0, b0 >= 0, n > 0, iter >= 0 and a finite sse >= 0");
+        return BPMF_HIP_EINVAL;
+    }
+    const double rate = b0 + 0.5 * sse;
+    if (!(rate > 0.0)) {
+        bpmf_hip_set_error_("noise_sample: b0 = 0 and sse = 0 leave the Gamma posterior without a rate");
+        return BPMF_HIP_EINVAL;
+    }
+    bpmf::MicroPhilox rng(BPMF_NOISE_COUNTER(iter));
+    const double g = std::gamma_distribution<>(a0 + 0.5 * (double)n)(rng);
+    double a = g / rate;
+    if (alpha_max > 0.0 && a > alpha_max) a = alpha_max;
+    *alpha = a;
+    return BPMF_HIP_OK;
+}

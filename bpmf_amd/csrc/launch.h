@@ -105,4 +105,15 @@ struct TopnLaunch {
 };
 void topn(const TopnLaunch &p, hipStream_t st);             // score + select, merge of the splits, std of the selected pairs
 
+// training residuals for the adaptive noise precision (kernels_noise.h, knoise.hip)
+struct SseLaunch {
+    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
+    const int32_t *rowidx; const double *vals; int64_t nnz;
+    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    double mean;
+    double *partial; int nblk;                             // nblk partials, then the sum
+};
+int train_sse_blocks(int64_t nnz, int num_cu);
+int train_sse(const SseLaunch &p, hipStream_t st);         // -1: unsupported K (nothing launched)
+
 }  // namespace bpmf_launch

@@ -203,6 +203,8 @@ struct bpmf_hip_side {
     // and the sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
     double *d_ring = nullptr; int ring_max = 0, ring_count = 0, ring_kp = 0;
     int64_t *d_ex_ptr = nullptr; int32_t *d_ex_rows = nullptr;
+    // adaptive noise (capi_noise.hip): device copy of the column pointers and the partials | sum of bpmf_hip_train_sse
+    int64_t *d_sse_colptr = nullptr; double *d_sse_part = nullptr; int sse_nblk = 0;
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
     // K = 64: columns with <= 16 ratings take the product form (k_sample_pf), the rest the slab form --

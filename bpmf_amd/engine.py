@@ -264,6 +264,20 @@ class HipEngine:
                                           1 if exclude_rated else 0, _ptr(idx), _ptr(mean), _ptr(std)))
         return idx, mean, std
 
+    # -- adaptive noise precision ----------------------------------------------
+    def train_sse(self, side, other):
+        """(SSE, n): the sum of squared training residuals (v - mean - x_c . y_r)^2 over the n ratings of `side`, with the
+        current factors of both sides (behind the newest sampler; waits for the result)."""
+        sse = C.c_double()
+        n = C.c_int64()
+        _lib.check(self.lib.bpmf_hip_train_sse(side.handle, other.handle, C.byref(sse), C.byref(n)))
+        return sse.value, n.value
+
+    def noise_sample(self, a0, b0, sse, n, it, alpha_max=None):
+        """The noise precision after iteration `it`: g / (b0 + sse / 2), g ~ Gamma(a0 + n / 2, 1) on the Philox stream
+        BPMF_NOISE_COUNTER(it), capped at alpha_max (None: no cap).  Host only."""
+        return noise_sample(a0, b0, sse, n, it, alpha_max)
+
     def kernel_name(self, side):
         """The kernel(s) one sampler launch of the side consists of, as a profile names them."""
         buf = C.create_string_buffer(512)
@@ -369,6 +383,14 @@ class HipEngine:
         out = np.empty(n)
         _lib.check(self.lib.bpmf_hip_randn_stream(self.ctx, int(counter) & 0xFFFFFFFF, int(n), _ptr(out)))
         return out
+
+
+def noise_sample(a0, b0, sse, n, it, alpha_max=None):
+    """bpmf_hip_noise_sample (host only: needs the library, not a GPU)."""
+    out = C.c_double()
+    _lib.check(_lib.load_library().bpmf_hip_noise_sample(float(a0), float(b0), float(sse), int(n), int(it),
+                                                         0.0 if alpha_max is None else float(alpha_max), C.byref(out)))
+    return out.value
 
 
 def hyper_sample(K, N, cov, counter, Um=None):

@@ -178,7 +178,7 @@ class Sys:
 
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=None, keep_samples=False, Tt=None, pipelined=False,
-          topn=None):
+          topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -191,9 +191,22 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
 
     topn=N: every post-burn-in sample of both sides is kept on the device (nsims - burnin slots each) and res["topn"] holds
     engine.topn(users, movies, ...) after the loop -- (idx, mean, std), [nusers, N] each: the N unrated movies of every user
-    with the highest posterior-mean prediction."""
+    with the highest posterior-mean prediction.
+
+    noise="adaptive": the noise precision is sampled too.  Iteration 0 runs with `alpha`; after iteration i (both sides
+    sampled) the sum of squared training residuals SSE_i is reduced on the device (engine.train_sse over the movies' ratings)
+    and iteration i + 1 runs with alpha = g / (b0 + SSE_i / 2), g ~ Gamma(a0 + n / 2, 1) (engine.noise_sample, alpha_prior =
+    (a0, b0) = shape / rate of the Gamma prior), capped at alpha_max.  The pipelined loop then waits once per iteration for
+    SSE_i before it enqueues iteration i + 1.  res["alpha"]: the alpha each iteration ran with, res["train_rmse"]:
+    sqrt(SSE_i / n).  noise="fixed" (the default) is the reference's constant alpha."""
     if topn is not None and nsims - burnin < 1:
         raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
+    if noise not in ("fixed", "adaptive"):
+        raise ValueError("noise must be 'fixed' or 'adaptive', not %r" % (noise,))
+    adaptive = noise == "adaptive"
+    a0, b0 = (float(alpha_prior[0]), float(alpha_prior[1])) if adaptive else (0.0, 0.0)
+    if adaptive and not (a0 > 0 and b0 >= 0):
+        raise ValueError("alpha_prior = (a0, b0) needs a0 > 0 and b0 >= 0")
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
     movies = Sys("movs", engine, M, nmovies, nusers, T=T)
     users = Sys("users", engine, Mt, nusers, nmovies, T=Tt)
@@ -208,6 +221,18 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
         if topn is not None and i >= burnin:
             engine.samples_add(users.side)
             engine.samples_add(movies.side)
+
+    if adaptive:
+        res["alpha"], res["train_rmse"] = [], []
+
+    def adapt(i):                                    # after both sides of iteration i: the alpha of iteration i + 1
+        if not adaptive:
+            return
+        res["alpha"].append(Sys.alpha)
+        sse, n = engine.train_sse(movies.side, users.side)
+        res["train_rmse"].append(math.sqrt(sse / n))
+        if i + 1 < nsims:
+            Sys.alpha = engine.noise_sample(a0, b0, sse, n, i, alpha_max)
     nnz = movies.local_nnz
 
     def line(it, secs, norm_u, norm_m):
@@ -226,6 +251,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
             movies.sample(users)
             users.sample(movies)
             keep(i)
+            adapt(i)
             if i > 0:
                 norm_m = engine.sys_norm(movies.side, i - 1)
                 norm_u = engine.sys_norm(users.side, i - 1)
@@ -248,6 +274,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
             movies.sample(users)
             users.sample(movies)
             keep(i)
+            adapt(i)
             movies.predict(users)
             if Tt is not None:
                 users.predict(movies)                # c++/bpmf.cpp:190 (nothing reads its results; Tt = None leaves it out)

@@ -281,6 +281,21 @@ BPMF_API int bpmf_hip_side_samples_count(const bpmf_hip_side *side);
 BPMF_API int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                            int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out);
 
+/* ---- adaptive noise precision -------------------------------------------------
+ * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
+ * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
+ * (fp32 factors are widened), a fixed order of summation: the same bits on every call.  Enqueued on the context stream behind
+ * the newest sampler of both sides (bpmf_hip_sys_sample or bpmf_hip_sample_side), on the copy of the factors it writes; waits
+ * for the sum.  Both sides whole on a context without a communicator, else BPMF_HIP_EINVAL. */
+BPMF_API int bpmf_hip_train_sse(bpmf_hip_side *side, bpmf_hip_side *other, double *sse, int64_t *n);
+/* Host only.  The noise precision of iteration iter + 1 after iteration iter left SSE `sse` over n training ratings, with a
+ * Gamma(a0, b0) prior (shape, rate): *alpha = g / (b0 + sse / 2), g ~ Gamma(a0 + n / 2, 1) drawn with libstdc++'s
+ * gamma_distribution on the Philox stream BPMF_NOISE_COUNTER(iter) (the top of the counter range, counting down: apart from
+ * the hyper-parameter streams, which count up from 0).  alpha_max > 0 caps the result; <= 0: no cap.  BPMF_HIP_EINVAL for
+ * a0 <= 0, b0 < 0, n <= 0, iter < 0, a negative or non-finite sse, or b0 = sse = 0. */
+#define BPMF_NOISE_COUNTER(iter) (0xFFFFFFFFu - (uint32_t)(iter))
+BPMF_API int bpmf_hip_noise_sample(double a0, double b0, double sse, int64_t n, int iter, double alpha_max, double *alpha);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
