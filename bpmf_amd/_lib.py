@@ -62,6 +62,11 @@ _SIGNATURES = {
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_train_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bpmf_hip_noise_sample": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_probit": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),
+    "bpmf_hip_side_probit_latent": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_test_probit_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_test_probit_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "bpmf_hip_auc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
     "bpmf_hip_side_aggr_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_aggr_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

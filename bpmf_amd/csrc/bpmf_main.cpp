@@ -17,7 +17,11 @@
 // --topn-by cols ranks the users of every item instead.  stdout is the same as without it.
 // --noise adaptive (one GPU, no -g): the noise precision is sampled after every iteration from its Gamma posterior (prior
 // --alpha-prior A0,B0, default 1,1; cap --alpha-max F), -a is its initial value; every iteration line then ends with the alpha
-// it ran with and the training RMSE after it, and -o DIR also gets DIR/alpha.csv.  Without these flags nothing changes.
+// it ran with and the training RMSE after it, and -o DIR also gets DIR/alpha.csv.
+// --probit [--probit-threshold F] (one GPU, no -g): the ratings are labels (positive if > F, default 0.5) under the probit
+// likelihood: mean rating 0, alpha 1, latent scores redrawn on the device ahead of every sampler launch.
+// After "Final Avg RMSE" the run prints "Final AUC" and "Final Brier" of the posterior-mean probabilities of the test entries,
+// and -o DIR also gets DIR/probit.csv (row,col,label,prob).  Without these flags nothing changes.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -55,7 +59,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -82,6 +86,9 @@ void usage()
               << "              iteration from its Gamma posterior given the training residuals, -a is its initial value (one GPU)\n"
               << "  [--alpha-prior A0,B0]: Gamma prior of the adaptive alpha, shape A0 > 0 and rate B0 >= 0 (1,1)\n"
               << "  [--alpha-max F]: cap of the adaptive alpha (none)\n"
+              << "  [--probit]: probit likelihood for binary matrices: a rating is a label, positive if > the threshold; mean rating 0,\n"
+              << "              alpha 1; prints Final AUC / Final Brier over the test matrix, -o DIR also gets DIR/probit.csv (one GPU, no -g)\n"
+              << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -223,6 +230,10 @@ struct Job {
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
+    bool probit = false;                                             // --probit
+    double probit_threshold = 0.5;                                   // --probit-threshold F
+    std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
+    double auc = NAN, brier = NAN;
     std::string odirname;
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
     std::vector<int64_t> bm, bu;                                     // column ranges of the ranks
@@ -265,6 +276,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
         const std::vector<int64_t> cp = slice_ptr(J.Mt, u0, u1);
         const size_t off = (size_t)J.Mt.colptr[(size_t)u0];
         check(bpmf_hip_side_create(ctx, nusers, nmovies, u0, u1, cp.data(), J.Mt.rowidx.data() + off, J.Mt.vals.data() + off, J.mean_u, &users));
+    }
+    if (J.probit) {                                                  // (streams: tag 1 = movies, 2 = users)
+        check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
+        check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
     }
     if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
         check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
@@ -325,12 +340,16 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.alpha_max > 0.0) os << ", capped at " << J.alpha_max;
         os << std::endl;
     }
+    if (J.probit)
+        os << "likelihood: probit, a rating > " << J.probit_threshold << " is a positive label; the RMSE columns compare the latent score "
+              "with the raw label and are not an error measure" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
 
     const int nsims = J.nsims, burnin = J.burnin;
     double alpha = J.alpha;                                          // (--noise adaptive: redrawn after every iteration)
+    const bool probit_eval = J.probit && J.T.nnz() > 0;              // Phi(u . v) of every kept sample, summed on the device (enqueue only)
     long double average_items_sec = 0, average_ratings_sec = 0;
     double rmse = NAN, rmse_avg = NAN, se, se_avg;
     int64_t num_predict = 0;
@@ -369,6 +388,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_sys_sample(movies, users, alpha));   // movies.sample(users)
             check(bpmf_hip_sys_sample(users, movies, alpha));   // users.sample(movies)
             if (J.adaptive) adapt(i);
+            if (probit_eval && i >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
             if (i > 0) {
                 // norms of iteration i-1 (bpmf_hip_sys_norm waits for THAT half-iteration's sums only: asking bpmf_hip_sys_state
                 // here drained each side's pipeline once per iteration -- 83 M against the 100 M samples/s of the same loop
@@ -415,6 +435,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
         if (J.topn > 0 && iter >= burnin) { check(bpmf_hip_side_samples_add(users)); check(bpmf_hip_side_samples_add(movies)); }
+        if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
         // (-v: the replicas of both factor matrices are complete on every rank -- the all-gather form of the exchange;
         // users.bcast() / movies.bcast() of c++/bpmf.cpp:202-203 have nothing left to do)
         if (J.verbose && rank == 0) {
@@ -447,6 +468,18 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_side_aggr_finalize(users, nsamples, J.u_mu.data() + (size_t)K * u0, J.u_lambda.data() + (size_t)K * K * u0));
             check(bpmf_hip_side_aggr_finalize(movies, nsamples, J.m_mu.data() + (size_t)K * m0, J.m_lambda.data() + (size_t)K * K * m0));
         }
+    }
+    if (probit_eval && nsims > burnin) {                             // one rank (main refuses -g)
+        J.prob.resize((size_t)J.T.nnz());
+        check(bpmf_hip_test_probit_get(test, J.prob.data(), nullptr));
+        std::vector<double> label(J.prob.size());
+        double sq = 0.0;
+        for (size_t q = 0; q < label.size(); ++q) {
+            label[q] = J.T.vals[q] > J.probit_threshold ? 1.0 : 0.0;
+            sq += (J.prob[q] - label[q]) * (J.prob[q] - label[q]);
+        }
+        check(bpmf_hip_auc(J.prob.data(), label.data(), (int64_t)label.size(), 0.5, &J.auc));
+        J.brier = sq / (double)label.size();
     }
     if (J.topn > 0) {                                                // one rank (main refuses -g > 1)
         const double t0 = tick();
@@ -482,8 +515,10 @@ int main(int argc, char *argv[])
     static const struct option long_opts[] = {{"fp32", no_argument, nullptr, 1000}, {"topn", required_argument, nullptr, 1001},
                                               {"topn-by", required_argument, nullptr, 1002}, {"noise", required_argument, nullptr, 1003},
                                               {"alpha-prior", required_argument, nullptr, 1004}, {"alpha-max", required_argument, nullptr, 1005},
+                                              {"probit", no_argument, nullptr, 1006}, {"probit-threshold", required_argument, nullptr, 1007},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold;
+    bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
         switch (ch) {
@@ -493,11 +528,13 @@ int main(int argc, char *argv[])
         case 1003: noise = optarg; break;
         case 1004: alpha_prior = optarg; break;
         case 1005: alpha_max = optarg; break;
+        case 1006: J.probit = true; break;
+        case 1007: probit_threshold = optarg; threshold_given = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
         case 't': J.nthrds = atoi(optarg); break;
-        case 'a': J.alpha = atof(optarg); break;
+        case 'a': J.alpha = atof(optarg); alpha_given = true; break;
         case 'd': K = atoi(optarg); break;
         case 'g': ngpu = atoi(optarg); break;
         case 'n': fname = optarg; break;
@@ -546,6 +583,22 @@ int main(int argc, char *argv[])
                            "training residuals is not all-reduced over ranks)");
         if (!(J.alpha > 0.0)) die("--noise adaptive needs an initial alpha -a F > 0");
     }
+    // --probit / --probit-threshold: checked before anything touches a GPU
+    if (threshold_given && !J.probit) die("--probit-threshold needs --probit");
+    if (J.probit) {
+        if (threshold_given) {
+            char *e = nullptr;
+            J.probit_threshold = strtod(probit_threshold.c_str(), &e);
+            if (e == probit_threshold.c_str() || *e != '\0' || !std::isfinite(J.probit_threshold))
+                die("--probit-threshold expects a number, not '" + probit_threshold + "'");
+        }
+        if (J.adaptive) die("--probit does not go together with --noise adaptive (the latent scores have unit variance)");
+        if (ngpu >= 1) die("--probit runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the latent scores of a "
+                           "sharded side are not drawn)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--probit does not go together with BPMF_REDUCE=1");
+        if (alpha_given && J.alpha != 1.0) die("--probit runs with alpha = 1: -a " + std::to_string(J.alpha) + " is not supported");
+        J.alpha = 1.0;
+    }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -571,6 +624,7 @@ int main(int argc, char *argv[])
     for (double v : J.M.vals) msum += v;
     for (double v : J.Mt.vals) usum += v;
     J.mean_m = msum / (double)J.M.nnz(); J.mean_u = usum / (double)J.Mt.nnz();
+    if (J.probit) J.mean_m = J.mean_u = 0.0;                    // labels, not measurements: the latent scores are centred at 0
 
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {
@@ -726,8 +780,26 @@ int main(int argc, char *argv[])
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/alpha.csv");
     }
 
+    if (J.probit && !J.odirname.empty() && !J.prob.empty()) {        // test-set order of T, 1-based ids in the ORIGINAL numbering
+        FILE *f = fopen((J.odirname + "/probit.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/probit.csv");
+        fprintf(f, "row,col,label,prob\n");
+        for (int64_t c = 0; c < J.T.ncols; ++c)
+            for (int64_t q = J.T.colptr[(size_t)c]; q < J.T.colptr[(size_t)c + 1]; ++q) {
+                const int64_t r = J.T.rowidx[(size_t)q];
+                fprintf(f, "%lld,%lld,%d,%.17g\n", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                        (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.T.vals[(size_t)q] > J.probit_threshold ? 1 : 0,
+                        J.prob[(size_t)q]);
+            }
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/probit.csv");
+    }
+
     os << "Total time: " << J.elapsed << std::endl;
     os << "Final Avg RMSE: " << J.rmse_avg << std::endl;
+    if (J.probit && !J.prob.empty()) {
+        os << "Final AUC: " << J.auc << std::endl;
+        os << "Final Brier: " << J.brier << std::endl;
+    }
     os << "  computed on " << J.num_predict << " items (" << (J.T.nnz() ? int(100. * (double)J.num_predict / (double)J.T.nnz()) : 0)
        << "% of total items in test set)" << std::endl;
     // the reference divides by movies.iter = nsims-1; this build reports the true mean

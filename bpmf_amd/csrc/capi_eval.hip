@@ -105,7 +105,7 @@ extern "C" int bpmf_hip_test_destroy(bpmf_hip_test *t)
     }
     if (t->ev_in) (void)hipEventDestroy(t->ev_in);
     for (hipEvent_t e : t->ev_done) if (e) (void)hipEventDestroy(e);
-    void *ptrs[] = {t->d_tcol, t->d_trow, t->d_tval, t->d_pavg, t->d_pm2, t->d_partial, t->d_ticket, t->d_twin_perm};
+    void *ptrs[] = {t->d_tcol, t->d_trow, t->d_tval, t->d_pavg, t->d_pm2, t->d_partial, t->d_ticket, t->d_twin_perm, t->d_prob_sum};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (t->h_res) (void)hipHostFree(t->h_res);
     delete t;

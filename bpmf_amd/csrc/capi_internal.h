@@ -7,6 +7,7 @@
 //   capi_eval.hip      test sets and Sys::predict
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
+//   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -37,6 +38,10 @@ void unpad_square(int Kt, int K, const double *src, double *dst);
 int settle_async(bpmf_hip_side *s);                                    // waits until the worker is done with `s`; returns its deferred error
 void predraw_stop(bpmf_hip_side *s);                                   // joins the side's pre-draw helper threads
 int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statistics without a launch to ride in: a kernel of their own
+
+// probit likelihood (capi_probit.hip)
+int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a probit side
+void probit_free(bpmf_hip_side *s);
 
 // evaluation (capi_eval.hip)
 void flush_deferred(bpmf_hip_test *t, bool on_main = false);           // enqueues an evaluation whose launch was put off

@@ -1,0 +1,151 @@
+// capi_probit.hip -- probit likelihood for binary matrices (kernels in kernels_probit.h):
+// bpmf_hip_side_set_probit, the latent step ahead of every sampler launch of such a side, the posterior predictive
+// probabilities of a test matrix, and the host-only bpmf_hip_auc.
+// (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
+#include "capi_internal.h"
+
+using namespace bpmf_capi;
+
+static bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
+
+namespace bpmf_capi {
+
+void probit_free(bpmf_hip_side *s)
+{
+    if (s->d_probit_z) (void)hipFree(s->d_probit_z);
+    if (s->d_probit_sign) (void)hipFree(s->d_probit_sign);
+    if (s->d_probit_colptr) (void)hipFree(s->d_probit_colptr);
+    if (s->h_probit_fail) (void)hipHostFree(s->h_probit_fail);
+    s->d_probit_z = nullptr; s->d_probit_sign = nullptr; s->d_probit_colptr = nullptr;
+    s->h_probit_fail = nullptr; s->h_probit_fail_dev = nullptr;
+}
+
+// The latent kernel of the half-iteration being enqueued, on the stream `st` its sampler goes on, ahead of it: `self->d_items` is
+// still the copy the side holds before this update (the sampler behind writes the other copy, or this one in place, later in
+// the same queue), and `other->d_items` the copy that sampler reads.  Called by bpmf_hip_sys_sample BEFORE it makes that stream
+// wait for the gate kernel of the hyper-parameters (unfused form: the kernel needs none and runs while the host still draws
+// them), and by launch_sampler (capi_sample.hip) for every other path.
+int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
+{
+    bpmf_hip_ctx *c = self->ctx;
+    if (alpha != 1.0) return fail(BPMF_HIP_EINVAL, "probit: a probit side is sampled with alpha = 1 (the latent scores have unit variance)");
+    if (c->comm || sharded(self) || self->reduce_on || self->item_n >= 0)
+        return fail(BPMF_HIP_EINVAL, "probit: needs the side whole on one GPU, without a communicator and without BPMF_REDUCE");
+    bpmf_launch::ProbitLatentLaunch p{};
+    p.colptr = self->d_probit_colptr; p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.sign = self->d_probit_sign; p.nnz = self->nnz;
+    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.iter = (uint32_t)iter; p.tag = self->probit_tag; p.z = self->d_probit_z; p.fail = self->h_probit_fail_dev;
+    if (bpmf_launch::probit_latent(p, st)) return fail(BPMF_HIP_EINVAL, "probit: unsupported K " + std::to_string(c->K));
+    return 0;
+}
+
+}  // namespace bpmf_capi
+
+extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsigned tag)
+{
+    if (!s) return fail(BPMF_HIP_EINVAL, "side_set_probit: NULL");
+    bpmf_hip_ctx *c = s->ctx;
+    if (s->d_probit_z) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
+    if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side must have been created with mean_rating = 0");
+    if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_probit: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
+    if (!std::isfinite(threshold)) return fail(BPMF_HIP_EINVAL, "side_set_probit: the threshold is not finite");
+    if (c->comm || sharded(s))
+        return fail(BPMF_HIP_EINVAL, "side_set_probit: needs the side whole on one GPU, on a context without a communicator");
+    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with the BPMF_REDUCE formulation");
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(s); if (rc) return rc; }
+    int rc = dev_upload<double>(&s->d_probit_z, nullptr, (size_t)s->nnz);
+    if (!rc) rc = dev_upload<int8_t>(&s->d_probit_sign, nullptr, (size_t)s->nnz);
+    if (!rc) rc = dev_upload(&s->d_probit_colptr, s->h_colptr.data(), s->h_colptr.size());
+    if (!rc && (hipHostMalloc((void **)&s->h_probit_fail, sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
+                hipHostGetDevicePointer((void **)&s->h_probit_fail_dev, s->h_probit_fail, 0) != hipSuccess))
+        rc = fail(BPMF_HIP_ENOMEM, "side_set_probit: pinned allocation failed");
+    if (!rc && hipMemsetAsync(s->d_probit_z, 0, std::max<size_t>((size_t)s->nnz, 1) * sizeof(double), c->stream) != hipSuccess)
+        rc = fail(BPMF_HIP_ENODEV, "side_set_probit: memset failed");
+    if (rc) { (void)hipGetLastError(); probit_free(s); return rc; }
+    *s->h_probit_fail = ~0ull;
+    s->probit_tag = (uint32_t)tag;
+    bpmf_launch::probit_sign(s->d_vals, s->nnz, threshold, s->d_probit_sign, c->stream);
+    if (hipGetLastError() != hipSuccess) { probit_free(s); return fail(BPMF_HIP_ENODEV, "side_set_probit: kernel launch failed"); }
+    return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hip_side_probit_latent(bpmf_hip_side *s, double *z_host)
+{
+    if (!s || !z_host) return fail(BPMF_HIP_EINVAL, "side_probit_latent: NULL argument");
+    if (!s->d_probit_z) return fail(BPMF_HIP_EINVAL, "side_probit_latent: not a probit side (bpmf_hip_side_set_probit)");
+    bpmf_hip_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(s); if (rc) return rc; }
+    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { std::string m; if (check_probit(s, &m)) return fail(BPMF_HIP_ENUM, m); }
+    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->d_probit_z, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hip_test_probit_add(bpmf_hip_test *t, bpmf_hip_side *self, bpmf_hip_side *other)
+{
+    if (!t || !self || !other) return fail(BPMF_HIP_EINVAL, "test_probit_add: NULL argument");
+    bpmf_hip_ctx *c = self->ctx;
+    if (t->side != self) return fail(BPMF_HIP_EINVAL, "test_probit_add: the test matrix belongs to another side");
+    if (other->ctx != c || other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "test_probit_add: the two sides do not belong together");
+    if (c->comm || sharded(self) || sharded(other))
+        return fail(BPMF_HIP_EINVAL, "test_probit_add: needs both sides whole on one GPU, on a context without a communicator");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!t->d_prob_sum) {
+        const int rc = dev_upload<double>(&t->d_prob_sum, nullptr, (size_t)t->nnz);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(t->d_prob_sum, 0, std::max<size_t>((size_t)t->nnz, 1) * sizeof(double), c->stream));
+    }
+    // S0 holds the newest sampler of both sides and d_items is the copy it writes (as in bpmf_hip_train_sse); whichever
+    // sampler rewrites one of these copies later is behind this kernel in the same queue.  Enqueue only: nothing waits.
+    bpmf_launch::ProbitProbLaunch p{};
+    p.tcol = t->d_tcol; p.trow = t->d_trow; p.nnz = t->nnz;
+    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.sum = t->d_prob_sum;
+    if (bpmf_launch::probit_prob(p, c->stream)) return fail(BPMF_HIP_EINVAL, "test_probit_add: unsupported K " + std::to_string(c->K));
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "test_probit_add: kernel launch failed");
+    c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
+    ++t->prob_n;
+    return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hip_test_probit_get(bpmf_hip_test *t, double *prob_host, int *nsamples)
+{
+    if (!t || !prob_host) return fail(BPMF_HIP_EINVAL, "test_probit_get: NULL argument");
+    if (nsamples) *nsamples = t->prob_n;
+    if (!t->d_prob_sum || t->prob_n == 0) return fail(BPMF_HIP_EINVAL, "test_probit_get: nothing added (bpmf_hip_test_probit_add)");
+    bpmf_hip_ctx *c = t->side->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    if (t->nnz > 0) HIP_TRY(hipMemcpy(prob_host, t->d_prob_sum, (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    const double inv = (double)t->prob_n;
+    for (int64_t q = 0; q < t->nnz; ++q) prob_host[q] /= inv;
+    return BPMF_HIP_OK;
+}
+
+// Host only.  AUC = (sum of the average ranks of the positives - P (P + 1) / 2) / (P N): the fraction of (positive, negative)
+// pairs the score orders correctly, ties counted half.
+extern "C" int bpmf_hip_auc(const double *score, const double *value, int64_t n, double threshold, double *auc)
+{
+    if (!auc || n < 0 || (n > 0 && (!score || !value))) return fail(BPMF_HIP_EINVAL, "auc: bad argument");
+    for (int64_t i = 0; i < n; ++i) if (score[i] != score[i]) return fail(BPMF_HIP_EINVAL, "auc: score " + std::to_string((long long)i) + " is NaN");
+    std::vector<int64_t> order((size_t)n);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::sort(order.begin(), order.end(), [score](int64_t a, int64_t b) { return score[a] < score[b]; });
+    // twice the rank sum of the positives, in integers (average ranks are half-integers): exact up to 2^63
+    unsigned long long twice = 0, npos = 0;
+    for (int64_t i = 0; i < n;) {
+        int64_t j = i;
+        unsigned long long pos = 0;
+        while (j < n && score[order[(size_t)j]] == score[order[(size_t)i]]) { pos += value[order[(size_t)j]] > threshold; ++j; }
+        twice += pos * (unsigned long long)(i + 1 + j);              // ranks i + 1 .. j: average (i + 1 + j) / 2
+        npos += pos;
+        i = j;
+    }
+    const unsigned long long nneg = (unsigned long long)n - npos;
+    if (npos == 0 || nneg == 0) { *auc = std::numeric_limits<double>::quiet_NaN(); return BPMF_HIP_OK; }
+    const unsigned long long num2 = twice - npos * (npos + 1);       // 2 x (pairs in order + half the ties)
+    *auc = (double)num2 / (2.0 * (double)npos * (double)nneg);
+    return BPMF_HIP_OK;
+}

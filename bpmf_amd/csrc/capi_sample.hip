@@ -11,6 +11,10 @@ template <int K, bool F32>
 int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, double *d_in, hipStream_t st,
                    hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr)
 {
+    // probit side: its latent scores are redrawn first, on the same stream, from the factors this side holds now (the copy
+    // the sampler below replaces or overwrites) and the copy of the other side's the sampler reads.  No host wait.  The
+    // stateful path has enqueued the kernel already, ahead of its wait for the gate kernel (bpmf_hip_sys_sample).
+    if (self->d_probit_z && !self->probit_latent_queued) { const int rp = probit_latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
     const int tgt = self->cur_buf ^ 1;
@@ -252,6 +256,7 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sample_side: other side has the wrong number of columns");
     if (iter < 0) return fail(BPMF_HIP_EINVAL, "sample_side: iter < 0");
     if (self->pending) return fail(BPMF_HIP_EINVAL, "sample_side_launch: previous launch not finished");
+    self->probit_latent_queued = false;                               // (a stateful call that failed half-way may have left it set)
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sample_side: the communicator of this context was aborted (a collective timed out)");
     const int K = c->K;
     HIP_TRY(hipSetDevice(c->device));
@@ -286,6 +291,7 @@ extern "C" int bpmf_hip_sample_side_finish(bpmf_hip_side *self, double *sum_out,
     self->pending = false;
     { const int rcw = wait_host(c); if (rcw) return rcw; }
     { std::string m; if (check_timeout(c->h_out, K, &m)) return fail(BPMF_HIP_ENODEV, m); }
+    { std::string m; if (check_probit(self, &m)) return fail(BPMF_HIP_ENUM, m); }
     const int Kt = c->Kt;                                           // (the caller's size; the extra rows / columns of the sums are zero)
     unpad_square(Kt, K, c->h_out, prod_out);
     memcpy(sum_out, c->h_out + (size_t)K * K, sizeof(double) * Kt);
@@ -559,6 +565,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
         }
     }
     if (!rc) rc = check_timeout(s->a_h_out, K, &msg);     // a bounded in-kernel wait gave up: the sums are not to be used
+    if (!rc) rc = check_probit(s, &msg);                  // (the latent kernel ran ahead of the sampler whose sums these are)
     if (!rc) {
         const double *prod = s->a_h_out, *sum = s->a_h_out + (size_t)K * K;
         unsigned long long f;
@@ -764,6 +771,16 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
         riders.flag = reinterpret_cast<unsigned *>(P->a_h_out_dev + c->out_words - 1); riders.seq = c->pending_seq;
         riders.tmo = tmo_word(P->a_h_out_dev, K); riders.wait_ticks = wait_ticks();
     }
+    // probit side: the latent kernel goes onto S0 HERE, before S0 is made to wait for the gate kernel below (unfused form:
+    // gate_stage spins on S1 until the host has drawn and staged this half-iteration's hyper-parameters, and S0 continues
+    // behind ev[3]).  It needs no hyper-parameters, only the factors the samplers already on S0 wrote, so it runs while the
+    // host chain (sums -> cov -> Normal-Wishart -> staging) is still at work.  Fused form: the same place in the queue as
+    // before, directly ahead of the sampler launch that carries its own gate.
+    self->probit_latent_queued = false;
+    if (self->d_probit_z) {
+        if ((rc = probit_latent_enqueue(self, other, iter, alpha, s0))) return rc;
+        self->probit_latent_queued = true;
+    }
     if (fused) {
         fz.gate_host = self->a_gate_dev; fz.gate_want = (unsigned)(iter + 1); fz.src_host = self->a_h_in_dev;
         fz.dst = self->a_d_in; fz.n = (int)stage_words; fz.dflag = self->a_dflag; fz.dval = seq;
@@ -803,6 +820,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, self->a_d_in, s0, (ride && timed) ? ev[0] : nullptr,
                                                     ride ? ev[1] : nullptr));
     self->cur_gate_flag = nullptr;
+    self->probit_latent_queued = false;
     self->cur_fused = bpmf::FusedArgs{};
     self->cur_riders = bpmf::StatRiders{};
     bpmf_launch::next_flags() = 0;                                    // (a sampler sequence without a kernel leaves it pending)

@@ -116,4 +116,23 @@ struct SseLaunch {
 int train_sse_blocks(int64_t nnz, int num_cu);
 int train_sse(const SseLaunch &p, hipStream_t st);         // -1: unsupported K (nothing launched)
 
+
+// probit likelihood (kernels_probit.h, kprobit.hip)
+struct ProbitLatentLaunch {
+    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
+    const int32_t *rowidx; const int8_t *sign; int64_t nnz;
+    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    uint32_t iter, tag;
+    double *z;                                             // the latent scores, layout of the side's ratings
+    unsigned long long *fail;                              // raised (rating position) when a draw runs into the attempt cap
+};
+struct ProbitProbLaunch {
+    const int32_t *tcol, *trow; int64_t nnz;               // column and row of every test entry
+    const void *items, *other; bool f32; int K, kt;
+    double *sum;                                           // running sums of Phi(x . y) per test entry
+};
+void probit_sign(const double *vals, int64_t nnz, double threshold, int8_t *sign, hipStream_t st);
+int probit_latent(const ProbitLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched)
+int probit_prob(const ProbitProbLaunch &p, hipStream_t st);
+
 }  // namespace bpmf_launch

@@ -26,7 +26,8 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     using namespace bpmf;
     bpmf_hip_ctx *c = self->ctx;
     SampleArgs a;
-    a.rowidx = self->d_rowidx; a.vals = self->d_vals;
+    const double *vals = self->d_probit_z ? self->d_probit_z : self->d_vals;      // probit side: the latent scores stand in for the ratings
+    a.rowidx = self->d_rowidx; a.vals = vals;
     // (item window: the whole list, or the items of one part of the columns -- bpmf_hip_side_set_overlap)
     const int w0 = self->item_n >= 0 ? self->item_off : 0, nwork = self->item_n >= 0 ? self->item_n : self->nwork;
     a.wi_col = self->d_wi_col + w0; a.wi_p0 = self->d_wi_p0 + w0; a.wi_len = self->d_wi_len + w0; a.wi_mc = self->d_wi_mc + w0; a.wi_chunk = self->d_wi_chunk + w0;
@@ -65,7 +66,7 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
                 k64_slab(self->hv_nwork, st, ev_start, nullptr, a);
             }
             LrArgs l;
-            l.rowidx = self->d_rowidx; l.vals = self->d_vals; l.col = self->d_lr_col; l.p0 = self->d_lr_p0; l.len = self->d_lr_len;
+            l.rowidx = self->d_rowidx; l.vals = vals; l.col = self->d_lr_col; l.p0 = self->d_lr_p0; l.len = self->d_lr_len;
             l.nitems = self->lr_n; l.other_items = other->d_items; l.items = out_items; l.col_from = self->from;
             l.R0 = d_in + (size_t)K * K + K + 2 + K; l.S0t = l.R0 + (size_t)K * K; l.y0 = l.S0t + (size_t)K * K;
             l.Lmu = a.Lmu; l.fail = a.fail;

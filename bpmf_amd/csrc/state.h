@@ -205,6 +205,13 @@ struct bpmf_hip_side {
     int64_t *d_ex_ptr = nullptr; int32_t *d_ex_rows = nullptr;
     // adaptive noise (capi_noise.hip): device copy of the column pointers and the partials | sum of bpmf_hip_train_sse
     int64_t *d_sse_colptr = nullptr; double *d_sse_part = nullptr; int sse_nblk = 0;
+    // probit likelihood (capi_probit.hip): d_probit_z != NULL marks a probit side.  The latent scores (layout of d_vals; the
+    // samplers read them in its place), the sign of every rating, the column pointers on the device, and a pinned word the
+    // latent kernel raises (to a rating position) when a draw runs into its attempt cap (~0: none)
+    double *d_probit_z = nullptr; int8_t *d_probit_sign = nullptr; int64_t *d_probit_colptr = nullptr;
+    unsigned long long *h_probit_fail = nullptr, *h_probit_fail_dev = nullptr;
+    uint32_t probit_tag = 0;
+    bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
     // K = 64: columns with <= 16 ratings take the product form (k_sample_pf), the rest the slab form --
@@ -340,6 +347,7 @@ struct bpmf_hip_test {
     // ONE kernel writes both copies (k_predict's TwinArgs).  NULL: the twin runs as a kernel of its own (sharded, fp32).
     int32_t *d_twin_perm = nullptr;
     std::vector<int32_t> h_col, h_row;   // global column / row of every entry (kept for the matching)
+    double *d_prob_sum = nullptr; int prob_n = 0;        // probit: running sums of Phi(x . y) per entry and the samples added (capi_probit.hip)
 };
 
 // sticky "a device-side wait timed out" word of a result blob (prod | sum | failD | fail | TMO | - | flag)
@@ -352,6 +360,17 @@ inline int check_timeout(double *h_blob, int K, std::string *msg)
     __atomic_store_n(w, 0ull, __ATOMIC_RELEASE);
     *msg = std::string("device wait timed out: ") + kTimeoutWhat[v < 5 ? v : 0];
     return BPMF_HIP_ENODEV;
+}
+
+// probit: did a latent draw of this side run into its attempt cap?  Checked where a half-iteration's results are collected.
+inline int check_probit(bpmf_hip_side *s, std::string *msg)
+{
+    if (!s->h_probit_fail) return 0;
+    const unsigned long long v = __atomic_load_n(s->h_probit_fail, __ATOMIC_ACQUIRE);
+    if (v == ~0ull) return 0;
+    __atomic_store_n(s->h_probit_fail, ~0ull, __ATOMIC_RELEASE);
+    *msg = "probit: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
+    return BPMF_HIP_ENUM;
 }
 
 // doubles in the partial of one chunk of a heavy column: the larger of the two accumulator layouts

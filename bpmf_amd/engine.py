@@ -278,6 +278,30 @@ class HipEngine:
         BPMF_NOISE_COUNTER(it), capped at alpha_max (None: no cap).  Host only."""
         return noise_sample(a0, b0, sse, n, it, alpha_max)
 
+    # -- probit likelihood -------------------------------------------------------
+    def set_probit(self, side, threshold=0.5, tag=1):
+        """Turns `side` (created with mean_rating 0) into a probit side: a rating is a label, positive if > threshold, and every
+        sampler launch of the side is preceded by the draw of its latent scores (include/bpmf_hip.h).  tag >= 1 names the
+        side's random streams: give the two sides of a model different tags.  Such a side is sampled with alpha = 1."""
+        _lib.check(self.lib.bpmf_hip_side_set_probit(side.handle, float(threshold), int(tag)))
+
+    def probit_latent(self, side, nnz):
+        """The latent scores the side's newest sampler launch read, in the order of its ratings (waits)."""
+        z = np.empty(int(nnz))
+        _lib.check(self.lib.bpmf_hip_side_probit_latent(side.handle, _ptr(z)))
+        return z
+
+    def probit_add(self, test, side, other):
+        """Adds Phi(x . y) of the current factors to the running sums of the test matrix' entries (enqueue only)."""
+        _lib.check(self.lib.bpmf_hip_test_probit_add(test[0], side.handle, other.handle))
+
+    def probit_get(self, test):
+        """(prob, nsamples): the mean probability of a positive per test entry, in the order given to test_create."""
+        prob = np.empty(test[1])
+        n = C.c_int()
+        _lib.check(self.lib.bpmf_hip_test_probit_get(test[0], _ptr(prob), C.byref(n)))
+        return prob, n.value
+
     def kernel_name(self, side):
         """The kernel(s) one sampler launch of the side consists of, as a profile names them."""
         buf = C.create_string_buffer(512)
@@ -390,6 +414,18 @@ def noise_sample(a0, b0, sse, n, it, alpha_max=None):
     out = C.c_double()
     _lib.check(_lib.load_library().bpmf_hip_noise_sample(float(a0), float(b0), float(sse), int(n), int(it),
                                                          0.0 if alpha_max is None else float(alpha_max), C.byref(out)))
+    return out.value
+
+
+def auc(score, value, threshold=0.5):
+    """bpmf_hip_auc (host only): area under the ROC curve of `score` against the labels value > threshold, ties counted half;
+    NaN when one class is empty."""
+    score = np.ascontiguousarray(score, np.float64)
+    value = np.ascontiguousarray(value, np.float64)
+    if score.shape != value.shape or score.ndim != 1:
+        raise ValueError("auc: score and value must be vectors of one length")
+    out = C.c_double()
+    _lib.check(_lib.load_library().bpmf_hip_auc(_ptr(score), _ptr(value), len(score), float(threshold), C.byref(out)))
     return out.value
 
 

@@ -177,8 +177,8 @@ class Sys:
             Sys.procid, phase, self.iter, self.rmse, self.rmse_avg, norm_u, norm_m, items_per_sec, ratings_per_sec / 1e6)
 
 
-def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=None, keep_samples=False, Tt=None, pipelined=False,
-          topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None):
+def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
+          topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -198,18 +198,41 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
     and iteration i + 1 runs with alpha = g / (b0 + SSE_i / 2), g ~ Gamma(a0 + n / 2, 1) (engine.noise_sample, alpha_prior =
     (a0, b0) = shape / rate of the Gamma prior), capped at alpha_max.  The pipelined loop then waits once per iteration for
     SSE_i before it enqueues iteration i + 1.  res["alpha"]: the alpha each iteration ran with, res["train_rmse"]:
-    sqrt(SSE_i / n).  noise="fixed" (the default) is the reference's constant alpha."""
+    sqrt(SSE_i / n).  noise="fixed" (the default) is the reference's constant alpha.
+
+    alpha: the noise precision (None: the reference's default 2, or 1 with probit=True).
+
+    probit=True: the ratings are labels (positive if > threshold) under the probit likelihood: both sides
+    are created with mean rating 0 and turned into probit sides (engine.set_probit, tags 1 = movies, 2 = users), alpha is 1, and
+    every post-burn-in sample adds Phi(u . v) to the running sums of the test entries (engine.probit_add, enqueue only: the
+    pipelined loop does not drain).  res["prob"]: the posterior-mean probability of a positive per test entry (order of T),
+    res["auc"]: bpmf_amd.auc of it against the test labels (NaN for a single class or no test matrix), res["brier"]: the mean
+    squared difference of prob and the 0 / 1 label.  The RMSE columns of the trace then compare the latent score u . v with the
+    raw label and are not an error measure."""
     if topn is not None and nsims - burnin < 1:
         raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
     if noise not in ("fixed", "adaptive"):
         raise ValueError("noise must be 'fixed' or 'adaptive', not %r" % (noise,))
     adaptive = noise == "adaptive"
+    if probit:
+        if adaptive:
+            raise ValueError("probit=True does not go together with noise='adaptive' (the latent scores have unit variance)")
+        if alpha is not None and float(alpha) != 1.0:
+            raise ValueError("probit=True runs with alpha = 1, not %r" % (alpha,))
+        if not math.isfinite(float(threshold)):
+            raise ValueError("threshold must be finite")
+        alpha = 1.0
+    elif alpha is None:
+        alpha = 2.0
     a0, b0 = (float(alpha_prior[0]), float(alpha_prior[1])) if adaptive else (0.0, 0.0)
     if adaptive and not (a0 > 0 and b0 >= 0):
         raise ValueError("alpha_prior = (a0, b0) needs a0 > 0 and b0 >= 0")
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
-    movies = Sys("movs", engine, M, nmovies, nusers, T=T)
-    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt)
+    movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit else None)
+    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit else None)
+    if probit:
+        engine.set_probit(movies.side, threshold, 1)
+        engine.set_probit(users.side, threshold, 2)
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
@@ -221,6 +244,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
         if topn is not None and i >= burnin:
             engine.samples_add(users.side)
             engine.samples_add(movies.side)
+        if probit and i >= burnin and movies.test is not None:
+            engine.probit_add(movies.test, movies.side, users.side)
 
     if adaptive:
         res["alpha"], res["train_rmse"] = [], []
@@ -291,6 +316,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=2.0, out=
     res["U"] = users.items(); res["V"] = movies.items()
     if topn is not None:
         res["topn"] = engine.topn(users.side, movies.side, movies.mean_rating, topn)
+    if probit:
+        have = movies.test is not None and movies.T_nnz > 0 and nsims > burnin
+        res["prob"] = engine.probit_get(movies.test)[0] if have else np.zeros(0)
+        label = (np.asarray(T[2]) > threshold).astype(np.float64) if have else np.zeros(0)
+        res["auc"] = _engine.auc(res["prob"], label, 0.5) if have else float("nan")
+        res["brier"] = float(np.mean((res["prob"] - label) ** 2)) if have else float("nan")
     res["movies"], res["users"] = movies, users
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)

@@ -296,6 +296,40 @@ BPMF_API int bpmf_hip_train_sse(bpmf_hip_side *side, bpmf_hip_side *other, doubl
 #define BPMF_NOISE_COUNTER(iter) (0xFFFFFFFFu - (uint32_t)(iter))
 BPMF_API int bpmf_hip_noise_sample(double a0, double b0, double sse, int64_t n, int iter, double alpha_max, double *alpha);
 
+/* ---- probit likelihood for binary matrices ---------------------------------------
+ * A rating v is a label: positive (s = +1) if v > threshold, else negative (s = -1).  Every rating p of a probit side carries a
+ * latent score z_p whose sign is s_p (Albert-Chib); the column samplers read the scores in place of the ratings, with mean 0
+ * and alpha = 1.  DESIGN.md section 12 has the model and the draw.
+ *
+ * bpmf_hip_side_set_probit turns `side` into a probit side: it allocates the latent array (layout of the side's ratings, which
+ * are never written), derives the signs once on the device, and from then on every sampler launch of the side
+ * (bpmf_hip_sys_sample, bpmf_hip_sample_side[_launch]; iteration `iter`) is preceded on the same stream by the latent step
+ *     m = x_c . y_r  (x: the side's factors before this update, y: the other side's newest; fp64),
+ *     z_p ~ N(m, 1) truncated to (0, inf) if s_p = +1, to (-inf, 0) otherwise,
+ * drawn from the Philox4x32-10 blocks (counter = p low, p high, iter, attempt; key = 42, tag).  tag >= 1 keeps the side's
+ * streams apart from every other stream of the library (key word 1 = 0) and from the other side's (give the two sides different
+ * tags).  Such a side must be sampled with alpha = 1.  No host wait is added to the sampling calls, and the
+ * latent step is ahead of the wait for the hyper-parameters in the queue (it needs none).  A draw rejected 64 times
+ * (probability < 2^-128 per rating with finite factors) stores s_p and makes the sampling call that collects the
+ * half-iteration fail with BPMF_HIP_ENUM.
+ * BPMF_HIP_EINVAL: mean_rating != 0, tag = 0, a non-finite threshold, a context with a communicator, a sharded side, the
+ * BPMF_REDUCE formulation on, or a side that is a probit side already. */
+BPMF_API int bpmf_hip_side_set_probit(bpmf_hip_side *side, double threshold, unsigned tag);
+/* The side's latent scores as the newest sampler launch read them, nnz doubles in the order of the side's ratings (waits for
+ * the work in flight). */
+BPMF_API int bpmf_hip_side_probit_latent(bpmf_hip_side *side, double *z_host);
+/* Adds Phi(x_c . y_r) of the current factors of `self` (the side of `test`) and `other` to the running sum of every entry of
+ * the test matrix.  Enqueued on the context stream behind the newest sampler of both sides, on the copies of the factors they
+ * wrote; does not wait.  Both sides whole on a context without a communicator, else BPMF_HIP_EINVAL. */
+BPMF_API int bpmf_hip_test_probit_add(bpmf_hip_test *test, bpmf_hip_side *self, bpmf_hip_side *other);
+/* The mean of the added probabilities per entry, in the order of the test matrix as given to bpmf_hip_test_create, and the
+ * number of samples added (nsamples may be NULL).  Waits.  BPMF_HIP_EINVAL when nothing was added. */
+BPMF_API int bpmf_hip_test_probit_get(bpmf_hip_test *test, double *prob_host, int *nsamples);
+/* Host only.  Area under the ROC curve of `score` against the labels value[i] > threshold: the fraction of (positive, negative)
+ * pairs that the score orders correctly, ties counted half (average ranks).  *auc = NaN when one class is empty (n = 0
+ * included).  BPMF_HIP_EINVAL for NULL arguments, n < 0 or a NaN score. */
+BPMF_API int bpmf_hip_auc(const double *score, const double *value, int64_t n, double threshold, double *auc);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
