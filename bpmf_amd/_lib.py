@@ -67,6 +67,16 @@ _SIGNATURES = {
     "bpmf_hip_test_probit_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_probit_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "bpmf_hip_auc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint]),
+    "bpmf_hip_link_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
+    "bpmf_hip_side_link_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_link_set": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_link_add": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_link_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "bpmf_hip_side_link_residual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_link_shift": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "bpmf_hip_link_gemm_tn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_link_gemm_nn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "bpmf_hip_side_aggr_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_aggr_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -79,8 +89,14 @@ _SIGNATURES = {
     "bpmf_hyper_sample": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hyper_draws": (C.c_int, [C.c_int, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bpmf_hyper_finish": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hyper_sample_ex": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "bpmf_hyper_draws_ex": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bpmf_hyper_finish_ex": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "bpmf_cov_from_sums": (None, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_randn_stream": (None, [C.c_uint32, C.c_int, C.c_void_p]),
+    "bpmf_randn_stream_tag": (None, [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "bpmf_hip_randn_stream": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "bpmf_hip_side_kernel_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "bpmf_hip_side_kernel_resources": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int]),

@@ -22,6 +22,9 @@
 // likelihood: mean rating 0, alpha 1, latent scores redrawn on the device ahead of every sampler launch.
 // After "Final Avg RMSE" the run prints "Final AUC" and "Final Brier" of the posterior-mean probabilities of the test entries,
 // and -o DIR also gets DIR/probit.csv (row,col,label,prob).  Without these flags nothing changes.
+// --row-features FILE / --col-features FILE [--lambda-beta F] (one GPU, no -g): side information.  FILE is a
+// dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
+// -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -88,6 +91,10 @@ void usage()
               << "  [--alpha-max F]: cap of the adaptive alpha (none)\n"
               << "  [--probit]: probit likelihood for binary matrices: a rating is a label, positive if > the threshold; mean rating 0,\n"
               << "              alpha 1; prints Final AUC / Final Brier over the test matrix, -o DIR also gets DIR/probit.csv (one GPU, no -g)\n"
+              << "  [--row-features FILE] [--col-features FILE]: side information: a dense matrix (.ddm / .csv) with one row of D features per\n"
+              << "              user / movie; the prior mean of its factors becomes mu + beta^T f with a sampled link matrix beta (one GPU, no -g,\n"
+              << "              not with --probit, --noise adaptive, --fp32, -m / -l or BPMF_REDUCE=1); -o DIR also gets DIR/U-link.ddm / V-link.ddm\n"
+              << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
               << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
@@ -234,6 +241,9 @@ struct Job {
     double probit_threshold = 0.5;                                   // --probit-threshold F
     std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
     double auc = NAN, brier = NAN;
+    Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
+    double lambda_beta = 5.0;                                        // --lambda-beta F
+    std::vector<double> beta_u, beta_m;                              // posterior mean of the link matrices, D x K row-major
     std::string odirname;
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
     std::vector<int64_t> bm, bu;                                     // column ranges of the ranks
@@ -281,6 +291,9 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
         check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
     }
+    const bool linked = !J.feat_u.data.empty() || !J.feat_m.data.empty();   // (streams: tag 3 = movies, 4 = users)
+    if (!J.feat_m.data.empty()) check(bpmf_hip_side_set_features(movies, J.feat_m.data.data(), (int)J.feat_m.ncols, 0, J.lambda_beta, 3));
+    if (!J.feat_u.data.empty()) check(bpmf_hip_side_set_features(users, J.feat_u.data.data(), (int)J.feat_u.ncols, 0, J.lambda_beta, 4));
     if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
         check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
         check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
@@ -343,6 +356,12 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.probit)
         os << "likelihood: probit, a rating > " << J.probit_threshold << " is a positive label; the RMSE columns compare the latent score "
               "with the raw label and are not an error measure" << std::endl;
+    if (linked) {
+        os << "side information:";
+        if (!J.feat_u.data.empty()) os << " row features D = " << J.feat_u.ncols << ",";
+        if (!J.feat_m.data.empty()) os << " column features D = " << J.feat_m.ncols << ",";
+        os << " lambda_beta = " << J.lambda_beta << "; blocking loop (bpmf_hip_link_sample)" << std::endl;
+    }
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -378,7 +397,9 @@ void rank_main(Job &J, int rank, std::ostream &os)
         J.train_rmse.push_back(std::sqrt(sse / (double)n));
         if (i + 1 < nsims) check(bpmf_hip_noise_sample(J.a0, J.b0, sse, n, i, J.alpha_max, &alpha));
     };
-    if (J.odirname.empty() && !J.verbose) {
+    // a model with side information steps both sides through the blocking half-iteration
+    auto sample = [&](bpmf_hip_side *a, bpmf_hip_side *b) { check(linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha)); };
+    if (J.odirname.empty() && !J.verbose && !linked) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -417,8 +438,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
     } else
     for (int i = 0; i < nsims; ++i) {
         const double start = tick();
-        check(bpmf_hip_sys_sample(movies, users, alpha));       // movies.sample(users)
-        check(bpmf_hip_sys_sample(users, movies, alpha));       // users.sample(movies)
+        sample(movies, users);                                  // movies.sample(users)
+        sample(users, movies);                                  // users.sample(movies)
         if (J.adaptive) adapt(i);
         iter = i;
         const int n = (iter < burnin) ? 0 : (iter - burnin);
@@ -436,6 +457,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
         if (J.topn > 0 && iter >= burnin) { check(bpmf_hip_side_samples_add(users)); check(bpmf_hip_side_samples_add(movies)); }
         if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
+        if (linked && iter >= burnin) {
+            if (!J.feat_u.data.empty()) check(bpmf_hip_side_link_add(users));
+            if (!J.feat_m.data.empty()) check(bpmf_hip_side_link_add(movies));
+        }
         // (-v: the replicas of both factor matrices are complete on every rank -- the all-gather form of the exchange;
         // users.bcast() / movies.bcast() of c++/bpmf.cpp:202-203 have nothing left to do)
         if (J.verbose && rank == 0) {
@@ -468,6 +493,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_side_aggr_finalize(users, nsamples, J.u_mu.data() + (size_t)K * u0, J.u_lambda.data() + (size_t)K * K * u0));
             check(bpmf_hip_side_aggr_finalize(movies, nsamples, J.m_mu.data() + (size_t)K * m0, J.m_lambda.data() + (size_t)K * K * m0));
         }
+    }
+    if (linked && nsims > burnin) {                                  // one rank (main refuses -g)
+        if (!J.feat_u.data.empty()) { J.beta_u.resize((size_t)J.feat_u.ncols * K); check(bpmf_hip_side_link_mean(users, J.beta_u.data(), nullptr)); }
+        if (!J.feat_m.data.empty()) { J.beta_m.resize((size_t)J.feat_m.ncols * K); check(bpmf_hip_side_link_mean(movies, J.beta_m.data(), nullptr)); }
     }
     if (probit_eval && nsims > burnin) {                             // one rank (main refuses -g)
         J.prob.resize((size_t)J.T.nnz());
@@ -516,8 +545,10 @@ int main(int argc, char *argv[])
                                               {"topn-by", required_argument, nullptr, 1002}, {"noise", required_argument, nullptr, 1003},
                                               {"alpha-prior", required_argument, nullptr, 1004}, {"alpha-max", required_argument, nullptr, 1005},
                                               {"probit", no_argument, nullptr, 1006}, {"probit-threshold", required_argument, nullptr, 1007},
+                                              {"row-features", required_argument, nullptr, 1008}, {"col-features", required_argument, nullptr, 1009},
+                                              {"lambda-beta", required_argument, nullptr, 1010},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -530,6 +561,9 @@ int main(int argc, char *argv[])
         case 1005: alpha_max = optarg; break;
         case 1006: J.probit = true; break;
         case 1007: probit_threshold = optarg; threshold_given = true; break;
+        case 1008: row_features = optarg; break;
+        case 1009: col_features = optarg; break;
+        case 1010: lambda_beta = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -599,6 +633,24 @@ int main(int argc, char *argv[])
         if (alpha_given && J.alpha != 1.0) die("--probit runs with alpha = 1: -a " + std::to_string(J.alpha) + " is not supported");
         J.alpha = 1.0;
     }
+    // --row-features / --col-features / --lambda-beta: checked before anything touches a GPU
+    const bool linked = !row_features.empty() || !col_features.empty();
+    if (!lambda_beta.empty() && !linked) die("--lambda-beta needs --row-features or --col-features");
+    if (linked) {
+        if (!lambda_beta.empty()) {
+            char *e = nullptr;
+            J.lambda_beta = strtod(lambda_beta.c_str(), &e);
+            if (e == lambda_beta.c_str() || *e != '\0' || !std::isfinite(J.lambda_beta) || !(J.lambda_beta > 0.0))
+                die("--lambda-beta expects a number F > 0, not '" + lambda_beta + "'");
+        }
+        if (ngpu >= 1) die("--row-features / --col-features run on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the "
+                           "products over the features of a sharded side are not formed)");
+        if (J.probit) die("--row-features / --col-features do not go together with --probit");
+        if (J.adaptive) die("--row-features / --col-features do not go together with --noise adaptive");
+        if (fp32) die("--row-features / --col-features do not go together with --fp32 (the link is fp64)");
+        if (!mname.empty() || !lname.empty()) die("--row-features / --col-features do not go together with a propagated posterior (-m / -l)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--row-features / --col-features do not go together with BPMF_REDUCE=1");
+    }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -626,6 +678,15 @@ int main(int argc, char *argv[])
     J.mean_m = msum / (double)J.M.nnz(); J.mean_u = usum / (double)J.Mt.nnz();
     if (J.probit) J.mean_m = J.mean_u = 0.0;                    // labels, not measurements: the latent scores are centred at 0
 
+    auto read_features = [&](const std::string &name, int64_t n, const char *what, Dense &F) {
+        if (name.empty()) return;
+        try { F = bpmf::io::read_dense(name); } catch (const std::exception &e) { die(e.what()); }
+        if (F.nrows != n) die(std::string("--") + what + ": " + name + " has " + std::to_string(F.nrows) + " rows, the side has " + std::to_string(n));
+        if (F.ncols < 1 || F.ncols > 1024) die(std::string("--") + what + ": expects 1 .. 1024 feature columns, not " + std::to_string(F.ncols));
+    };
+    read_features(row_features, nusers, "row-features", J.feat_u);
+    read_features(col_features, nmovies, "col-features", J.feat_m);
+
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {
         if (fnames.empty()) return;
@@ -651,6 +712,7 @@ int main(int argc, char *argv[])
     // GPU can check of the permute / unpermute plumbing)
     const int assign_parts = getenv("BPMF_TEST_ASSIGN_PARTS") ? atoi(getenv("BPMF_TEST_ASSIGN_PARTS")) : J.nranks;
     const bool greedy = balance && assign_parts > 1 && !(assign_env && std::string(assign_env) == "contiguous");
+    if (greedy && linked) die("--row-features / --col-features do not go together with a renumbering assignment of the columns");
     if (greedy) {
         J.perm_m.resize((size_t)nmovies); J.perm_u.resize((size_t)nusers);
         for (int64_t i = 0; i < nmovies; ++i) J.perm_m[(size_t)i] = i;
@@ -749,6 +811,16 @@ int main(int argc, char *argv[])
             bpmf::io::write_dense(J.odirname + "/V-mu.ddm", d);
             d.nrows = (int64_t)K * K; d.data.swap(J.m_lambda);
             bpmf::io::write_dense(J.odirname + "/V-Lambda.ddm", d);
+            auto write_link = [&](const std::vector<double> &beta, const char *name) {     // D x K, row-major -> column-major
+                if (beta.empty()) return;
+                Dense b;
+                b.nrows = (int64_t)(beta.size() / (size_t)K); b.ncols = K; b.data.resize(beta.size());
+                for (int64_t dd = 0; dd < b.nrows; ++dd)
+                    for (int k = 0; k < K; ++k) b.data[(size_t)k * (size_t)b.nrows + (size_t)dd] = beta[(size_t)dd * K + k];
+                bpmf::io::write_dense(J.odirname + name, b);
+            };
+            write_link(J.beta_u, "/U-link.ddm");
+            write_link(J.beta_m, "/V-link.ddm");
         } catch (const std::exception &e) { die(e.what()); }
     }
 

@@ -8,6 +8,7 @@
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
+//   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -42,6 +43,10 @@ int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statis
 // probit likelihood (capi_probit.hip)
 int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a probit side
 void probit_free(bpmf_hip_side *s);
+
+// side information (capi_link.hip)
+void link_free(bpmf_hip_side *s);
+int ensure_state(bpmf_hip_side *s);                                    // (capi_sample.hip) the Sys state of a side: cov, hyper-parameters
 
 // evaluation (capi_eval.hip)
 void flush_deferred(bpmf_hip_test *t, bool on_main = false);           // enqueues an evaluation whose launch was put off

@@ -256,6 +256,8 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sample_side: other side has the wrong number of columns");
     if (iter < 0) return fail(BPMF_HIP_EINVAL, "sample_side: iter < 0");
     if (self->pending) return fail(BPMF_HIP_EINVAL, "sample_side_launch: previous launch not finished");
+    if (self->d_link_f && !self->link_in_call)
+        return fail(BPMF_HIP_EINVAL, "sample_side: the side has features: step it with bpmf_hip_link_sample");
     self->probit_latent_queued = false;                               // (a stateful call that failed half-way may have left it set)
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sample_side: the communicator of this context was aborted (a collective timed out)");
     const int K = c->K;
@@ -707,6 +709,8 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     bpmf_hip_ctx *c = self->ctx;
     if (other->ctx != c) return fail(BPMF_HIP_EINVAL, "sys_sample: sides belong to different contexts");
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sys_sample: other side has the wrong number of columns");
+    if (self->d_link_f)
+        return fail(BPMF_HIP_EINVAL, "sys_sample: the side has features: step BOTH sides of the model with bpmf_hip_link_sample");
     if (self->to - self->from != self->ncols && !(c->comm && !self->bounds.empty()))
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side is a shard: give the context a communicator "
                                      "(bpmf_hip_ctx_comm_init) and the side its ranges (bpmf_hip_side_set_ranges), "

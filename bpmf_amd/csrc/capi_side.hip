@@ -316,6 +316,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     if (s->d_sse_colptr) (void)hipFree(s->d_sse_colptr);
     if (s->d_sse_part) (void)hipFree(s->d_sse_part);
     probit_free(s);
+    link_free(s);
     if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
     if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
     void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,

@@ -222,14 +222,15 @@ extern "C" void bpmf_hip_set_error_(const char *msg);   // capi.cpp
 // normal draws of WishartUnitChol, c++/mvnormal.cpp:64-73, with df = K + N) and the K normals `z`
 // of MvNormalChol_prec (:58) consume the Philox stream `counter` in a data-independent way.  It
 // can therefore be produced ahead of time, before the sums of the half-iteration have arrived.
-extern "C" int bpmf_hyper_draws(int K, int64_t N, uint32_t counter, double *au_out, double *z_out)
+// (extra_dof: degrees of freedom on top of nu + N -- the rows of a link matrix, bpmf_hyper_draws_ex; 0: the reference's draw)
+static int hyper_draws(int K, int64_t N, int64_t extra_dof, uint32_t counter, double *au_out, double *z_out)
 {
-    if (K <= 0 || K > 1024 || N <= 0 || !au_out || !z_out) {
+    if (K <= 0 || K > 1024 || N <= 0 || extra_dof < 0 || !au_out || !z_out) {
         bpmf_hip_set_error_("bpmf_hyper_draws: bad argument");
         return BPMF_HIP_EINVAL;
     }
     bpmf::MicroPhilox rng(counter);                      // rng_set_pos(iter), c++/sample.cpp:349
-    const double nu_c = (double)((int64_t)K + N);          // nu + N with nu = df = K
+    const double nu_c = (double)((int64_t)K + N + extra_dof);   // nu + N with nu = df = K
     std::memset(au_out, 0, sizeof(double) * K * K);
     Mat AU{au_out, K};
     for (int i = 0; i < K; ++i) {                         // WishartUnitChol (c++/mvnormal.cpp:64-73)
@@ -242,10 +243,22 @@ extern "C" int bpmf_hyper_draws(int K, int64_t N, uint32_t counter, double *au_o
     return BPMF_HIP_OK;
 }
 
+extern "C" int bpmf_hyper_draws(int K, int64_t N, uint32_t counter, double *au_out, double *z_out)
+{
+    return hyper_draws(K, N, 0, counter, au_out, z_out);
+}
+
+extern "C" int bpmf_hyper_draws_ex(int K, int64_t N, int64_t extra_dof, uint32_t counter, double *au_out, double *z_out)
+{
+    return hyper_draws(K, N, extra_dof, counter, au_out, z_out);
+}
+
 // The part that needs cov: CondNormalWishart's posterior parameters, WishartChol's product and
 // the triangular solve of MvNormalChol_prec (c++/mvnormal.cpp:56-61,75-92,116-135), LambdaF.
-extern "C" int bpmf_hyper_finish(int K, int64_t N, const double *cov, const double *Um, const double *au, const double *z_in,
-                                 double *mu, double *LambdaU, double *LambdaF)
+// (extra_scatter: a K x K matrix added to the posterior scale matrix -- lambda_beta beta^T beta of a link matrix,
+//  bpmf_hyper_finish_ex; NULL: the reference's draw, bit for bit)
+static int hyper_finish(int K, int64_t N, const double *cov, const double *Um, const double *extra_scatter, const double *au, const double *z_in,
+                        double *mu, double *LambdaU, double *LambdaF)
 {
     if (K <= 0 || K > 1024 || N <= 0 || !cov || !au || !z_in || !mu || !LambdaU || !LambdaF) {
         bpmf_hip_set_error_("bpmf_hyper_finish: bad argument");
@@ -266,6 +279,8 @@ extern "C" int bpmf_hyper_finish(int K, int64_t N, const double *cov, const doub
     for (int j = 0; j < K; ++j)
         for (int i = 0; i < K; ++i)
             X[(size_t)j * K + i] = ((i == j ? 1.0 : 0.0) + dN * cov[(size_t)j * K + i]) + kappa_m * (mu_m[i] * mu_m[j]);
+    if (extra_scatter)
+        for (size_t q = 0; q < KK; ++q) X[q] += extra_scatter[q];
     if (K >= 128) {
         if (!inverse_factor_spd(K, X.data(), R.data())) {
             bpmf_hip_set_error_("bpmf_hyper_sample: posterior scale matrix not positive definite");
@@ -360,6 +375,38 @@ extern "C" int bpmf_hyper_finish(int K, int64_t N, const double *cov, const doub
         }
     }
     return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hyper_finish(int K, int64_t N, const double *cov, const double *Um, const double *au, const double *z_in,
+                                 double *mu, double *LambdaU, double *LambdaF)
+{
+    return hyper_finish(K, N, cov, Um, nullptr, au, z_in, mu, LambdaU, LambdaF);
+}
+
+extern "C" int bpmf_hyper_finish_ex(int K, int64_t N, const double *cov, const double *Um, const double *extra_scatter, const double *au,
+                                    const double *z_in, double *mu, double *LambdaU, double *LambdaF)
+{
+    return hyper_finish(K, N, cov, Um, extra_scatter, au, z_in, mu, LambdaU, LambdaF);
+}
+
+extern "C" int bpmf_hyper_sample_ex(int K, int64_t N, const double *cov, const double *Um, const double *extra_scatter, int64_t extra_dof,
+                                    uint32_t counter, double *mu, double *LambdaU, double *LambdaF)
+{
+    if (K <= 0 || K > 1024 || N <= 0 || extra_dof < 0 || !cov || !mu || !LambdaU || !LambdaF) {
+        bpmf_hip_set_error_("bpmf_hyper_sample_ex: bad argument");
+        return BPMF_HIP_EINVAL;
+    }
+    std::vector<double> au((size_t)K * K), z(K);
+    int rc = hyper_draws(K, N, extra_dof, counter, au.data(), z.data());
+    if (rc) return rc;
+    return hyper_finish(K, N, cov, Um, extra_scatter, au.data(), z.data(), mu, LambdaU, LambdaF);
+}
+
+// the normal stream `counter` with key word 1 = tag (0: bpmf_randn_stream): the Z of a link draw (bpmf_hip_link_sample)
+extern "C" void bpmf_randn_stream_tag(uint32_t counter, uint32_t tag, int n, double *out)
+{
+    bpmf::MicroPhilox rng(counter, tag);
+    for (int i = 0; i < n; ++i) out[i] = randn(rng);
 }
 
 extern "C" int bpmf_hyper_sample(int K, int64_t N, const double *cov, const double *Um, uint32_t counter,

@@ -135,4 +135,32 @@ void probit_sign(const double *vals, int64_t nnz, double threshold, int8_t *sign
 int probit_latent(const ProbitLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched)
 int probit_prob(const ProbitProbLaunch &p, hipStream_t st);
 
+// side information (kernels_link.h, klink.hip): fp64, row-major operands
+struct LinkTnLaunch {                                      // C (D x n, leading dimension ldc) = A^T (B - 1 bvec^T)
+    const double *A; int64_t lda;                          // N x D
+    const double *B; int64_t ldb; const double *bvec;      // N x n (n <= 128), bvec: n doubles or NULL
+    int64_t N; int D, n;
+    double *C; int64_t ldc;
+    double *part;                                          // link_tn_part_words(N, D, n) doubles: the partial of every chunk of N
+};
+struct LinkNnLaunch {                                      // C (N x ncw, leading dimension ldc) = A B, columns n .. ncw - 1 zero
+    const double *A; int64_t lda;                          // N x Dr
+    const double *B; int64_t ldb;                          // Dr x n
+    int64_t N; int Dr, n;
+    double *C; int64_t ldc; int ncw;                       // n <= ncw <= 128
+};
+struct LinkResidualLaunch {
+    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
+    const int32_t *rowidx; const double *vals; int64_t nnz;
+    const double *offs, *other; int K, kt;                 // the side's offsets and the other side's factors (leading dimension K)
+    double *out;                                           // vals - offs_c . other_r, layout of vals
+};
+int64_t link_chunks(int64_t N);
+size_t link_tn_part_words(int64_t N, int D, int n);
+int link_gemm_tn(const LinkTnLaunch &p, hipStream_t st);    // -1: shape not supported (nothing launched)
+int link_gemm_nn(const LinkNnLaunch &p, hipStream_t st);
+int link_residual(const LinkResidualLaunch &p, hipStream_t st);
+int link_shift_blocks(int64_t total);
+void link_shift(double *items, const double *offs, int64_t total, double *partial, hipStream_t st);   // partial: link_shift_blocks(total) doubles
+
 }  // namespace bpmf_launch

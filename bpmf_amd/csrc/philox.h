@@ -148,18 +148,18 @@ BPMF_HD double polar_mult(double r2)
 // Host-side URNG with the MicroURNG interface expected by <random>.
 struct MicroPhilox {
     typedef uint32_t result_type;
-    uint32_t c0 = 0, n = 0;
+    uint32_t c0 = 0, n = 0, k1 = 0;          // k1: the second key word (0: the reference's streams)
     int last = 0;
     uint32_t r[4] = {0, 0, 0, 0};
     MicroPhilox() {}
-    explicit MicroPhilox(uint32_t c) : c0(c) {}
+    explicit MicroPhilox(uint32_t c, uint32_t key1 = 0) : c0(c), k1(key1) {}
     void reset(uint32_t c) { c0 = c; n = 0; last = 0; }
     static constexpr result_type min() { return 0u; }
     static constexpr result_type max() { return 0xFFFFFFFFu; }
     result_type operator()()
     {
         if (last == 0) {
-            const Philox4 b = stream_block(c0, n);
+            const Philox4 b = philox4x32_10(c0, 0u, 0u, n, 42u, k1);     // (k1 = 0: stream_block(c0, n))
             r[0] = b.w[0]; r[1] = b.w[1]; r[2] = b.w[2]; r[3] = b.w[3];
             ++n; last = 4;
         }

@@ -211,6 +211,14 @@ struct bpmf_hip_side {
     double *d_probit_z = nullptr; int8_t *d_probit_sign = nullptr; int64_t *d_probit_colptr = nullptr;
     unsigned long long *h_probit_fail = nullptr, *h_probit_fail_dev = nullptr;
     uint32_t probit_tag = 0;
+    // side information (capi_link.hip): d_link_f != NULL marks a side with features.  F (ncols x D, row-major),
+    // W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld), beta (D x ld), the offsets M = F beta in the
+    // factors' layout, the residual ratings the samplers read in place of d_vals, the partials of the long-dimension product, and
+    // small staging arrays.  link_in_call: bpmf_hip_link_sample is driving the stateless half-iteration of this side.
+    int link_d = 0; double link_lambda = 0.0; uint32_t link_tag = 0; bool link_in_call = false;
+    double *d_link_f = nullptr, *d_link_w = nullptr, *d_link_pe = nullptr, *d_link_beta = nullptr, *d_link_m = nullptr, *d_link_r = nullptr;
+    double *d_link_part = nullptr, *d_link_mu = nullptr, *d_link_btb = nullptr, *d_link_norm = nullptr, *d_link_beta_sum = nullptr;
+    int64_t *d_link_colptr = nullptr; int link_nsum = 0;
     bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;

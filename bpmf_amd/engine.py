@@ -302,6 +302,57 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_test_probit_get(test[0], _ptr(prob), C.byref(n)))
         return prob, n.value
 
+    # -- side information ---------------------------------------------------------
+    def set_features(self, side, F, lambda_beta=5.0, tag=3):
+        """Gives `side` the dense feature matrix F [ncols, D] (one row per column of the side), a link matrix beta (D x K, 0) and
+        the fixed lambda_beta.  tag >= 1 names the random stream of the link draw: different per side.
+        From then on the side -- and its partner -- are stepped with link_sample."""
+        F = np.asarray(F, np.float64)
+        if F.ndim != 2 or F.shape[0] != side.ncols:
+            raise ValueError("set_features: F must be [%d, D], one row per column of the side" % side.ncols)
+        row_major = not (F.flags.f_contiguous and not F.flags.c_contiguous)
+        F = np.asfortranarray(F) if not row_major else np.ascontiguousarray(F)
+        _lib.check(self.lib.bpmf_hip_side_set_features(side.handle, _ptr(F), int(F.shape[1]), 1 if row_major else 0, float(lambda_beta), int(tag)))
+        side.link_d = int(F.shape[1])
+
+    def link_sample(self, side, other, alpha):
+        """The blocking half-iteration of a model with side information (both sides go through it; include/bpmf_hip.h)."""
+        _lib.check(self.lib.bpmf_hip_link_sample(side.handle, other.handle, float(alpha)))
+
+    def link_get(self, side):
+        """(beta [D, K], offsets M = F beta [ncols, K]) of a side with features."""
+        beta = np.empty((getattr(side, "link_d", 0), self.K)); offs = np.empty((side.ncols, self.K))
+        _lib.check(self.lib.bpmf_hip_side_link_get(side.handle, _ptr(beta), _ptr(offs)))
+        return beta, offs
+
+    def link_set(self, side, beta):
+        """Sets beta [D, K]; the offsets are recomputed on the device."""
+        beta = np.ascontiguousarray(beta, np.float64)
+        assert beta.shape == (side.link_d, self.K)
+        _lib.check(self.lib.bpmf_hip_side_link_set(side.handle, _ptr(beta)))
+
+    def link_add(self, side):
+        """Adds the current beta to the side's running sum (where aggr_add sits)."""
+        _lib.check(self.lib.bpmf_hip_side_link_add(side.handle))
+
+    def link_mean(self, side):
+        """(mean of the added beta [D, K], samples added)."""
+        beta = np.empty((getattr(side, "link_d", 0), self.K)); n = C.c_int()
+        _lib.check(self.lib.bpmf_hip_side_link_mean(side.handle, _ptr(beta), C.byref(n)))
+        return beta, n.value
+
+    def link_residual(self, side, other, nnz):
+        """r - m_c . y_r of the side's ratings for its current offsets and the other side's current factors (tests, tools)."""
+        r = np.empty(int(nnz))
+        _lib.check(self.lib.bpmf_hip_side_link_residual(side.handle, other.handle, _ptr(r)))
+        return r
+
+    def link_shift(self, side):
+        """U += M on the side's current factors; returns sum |u|^2 (tests, tools)."""
+        nrm = C.c_double()
+        _lib.check(self.lib.bpmf_hip_side_link_shift(side.handle, C.byref(nrm)))
+        return nrm.value
+
     def kernel_name(self, side):
         """The kernel(s) one sampler launch of the side consists of, as a profile names them."""
         buf = C.create_string_buffer(512)
@@ -400,8 +451,8 @@ class HipEngine:
         return pavg, pm2
 
     # -- host-side hyper parameters (also in the library, not device code) -------
-    def hyper_sample(self, N, cov, counter, Um=None):
-        return hyper_sample(self.K, N, cov, counter, Um)
+    def hyper_sample(self, N, cov, counter, Um=None, extra_scatter=None, extra_dof=0):
+        return hyper_sample(self.K, N, cov, counter, Um, extra_scatter, extra_dof)
 
     def randn_device(self, counter, n):
         out = np.empty(n)
@@ -429,12 +480,21 @@ def auc(score, value, threshold=0.5):
     return out.value
 
 
-def hyper_sample(K, N, cov, counter, Um=None):
-    """HyperParams::sample on the host (c++/bpmf.h:98-103): returns mu[K], LambdaU[K,K], LambdaF[K,K]."""
+def hyper_sample(K, N, cov, counter, Um=None, extra_scatter=None, extra_dof=0):
+    """HyperParams::sample on the host (c++/bpmf.h:98-103): returns mu[K], LambdaU[K,K], LambdaF[K,K].
+    extra_scatter [K, K] / extra_dof: added to the posterior scale matrix / the Wishart degrees of freedom (side information:
+    lambda_beta beta^T beta and D); None and 0: the plain draw."""
     lib = _lib.load_library()
     cov = np.asfortranarray(cov, np.float64)
     mu = np.empty(K); LU = np.empty((K, K), order="F"); LF = np.empty((K, K), order="F")
     um = np.ascontiguousarray(Um, np.float64) if Um is not None else None
+    if extra_scatter is not None or extra_dof:
+        sc = np.asfortranarray(extra_scatter, np.float64) if extra_scatter is not None else None
+        if sc is not None and sc.shape != (K, K):
+            raise ValueError("extra_scatter must be [K, K]")
+        _lib.check(lib.bpmf_hyper_sample_ex(int(K), int(N), _ptr(cov), _ptr(um), _ptr(sc), int(extra_dof), int(counter) & 0xFFFFFFFF,
+                                            _ptr(mu), _ptr(LU), _ptr(LF)))
+        return mu, LU, LF
     _lib.check(lib.bpmf_hyper_sample(int(K), int(N), _ptr(cov), _ptr(um), int(counter) & 0xFFFFFFFF, _ptr(mu), _ptr(LU), _ptr(LF)))
     return mu, LU, LF
 
@@ -447,8 +507,33 @@ def cov_from_sums(K, N, s, prod):
     return cov
 
 
-def randn_host(counter, n):
+def randn_host(counter, n, tag=0):
+    """n normals of the host stream `counter`; tag: key word 1 of the stream (0: the samplers' streams)."""
     lib = _lib.load_library()
     out = np.empty(n)
-    lib.bpmf_randn_stream(int(counter) & 0xFFFFFFFF, int(n), _ptr(out))
+    if tag:
+        lib.bpmf_randn_stream_tag(int(counter) & 0xFFFFFFFF, int(tag) & 0xFFFFFFFF, int(n), _ptr(out))
+    else:
+        lib.bpmf_randn_stream(int(counter) & 0xFFFFFFFF, int(n), _ptr(out))
+    return out
+
+
+def link_gemm_tn(A, B=None, bvec=None, device=0):
+    """A^T (B - 1 bvec^T) on the device through k_link_gemm_tn (B = None: A^T A).  Row-major fp64 host arrays; tests and tools."""
+    A = np.ascontiguousarray(A, np.float64)
+    N, D = A.shape
+    n = D if B is None else B.shape[1]
+    Bc = np.ascontiguousarray(B, np.float64) if B is not None else None
+    v = np.ascontiguousarray(bvec, np.float64) if bvec is not None else None
+    out = np.empty((D, n))
+    _lib.check(_lib.load_library().bpmf_hip_link_gemm_tn(int(device), _ptr(A), N, D, _ptr(Bc), n, _ptr(v), _ptr(out)))
+    return out
+
+
+def link_gemm_nn(A, B, device=0):
+    """A B on the device through k_link_gemm_nn (B: D x n, n <= 128).  Row-major fp64 host arrays; tests and tools."""
+    A = np.ascontiguousarray(A, np.float64); B = np.ascontiguousarray(B, np.float64)
+    N, D = A.shape
+    out = np.empty((N, B.shape[1]))
+    _lib.check(_lib.load_library().bpmf_hip_link_gemm_nn(int(device), _ptr(A), N, D, _ptr(B), B.shape[1], _ptr(out)))
     return out

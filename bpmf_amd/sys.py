@@ -108,6 +108,12 @@ class Sys:
 
     # -- Sys::sample(Sys&), c++/sample.cpp:341-385 ------------------------------
     def sample(self, other):
+        if getattr(self, "linked", False):
+            # a model with side information: BOTH sides take the blocking half-iteration
+            self.engine.link_sample(self.side, other.side, Sys.alpha)
+            self.iter += 1
+            self._stale = True
+            return
         if (self.comm is None or getattr(self.comm, "native", False)) and hasattr(self.engine, "sys_sample"):
             # NO_COMM: the whole of Sys::sample(Sys&) (iter++, hyper draw, column loop, cov) runs
             # behind one C-ABI call, which also overlaps the host draws with the kernels
@@ -178,7 +184,8 @@ class Sys:
 
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
-          topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5):
+          topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
+          row_features=None, col_features=None, lambda_beta=5.0):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -208,7 +215,23 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     pipelined loop does not drain).  res["prob"]: the posterior-mean probability of a positive per test entry (order of T),
     res["auc"]: bpmf_amd.auc of it against the test labels (NaN for a single class or no test matrix), res["brier"]: the mean
     squared difference of prob and the 0 / 1 label.  The RMSE columns of the trace then compare the latent score u . v with the
-    raw label and are not an error measure."""
+    raw label and are not an error measure.
+
+    row_features [nusers, D] / col_features [nmovies, D]: side information.  The prior mean of a user's
+    (movie's) factors becomes mu + beta^T f with a link matrix beta (D x K) that is sampled too, its rows N(0, (lambda_beta
+    Lambda)^-1) a priori; lambda_beta is fixed (5 is a default, not a tuned number).  Either or both.  The loop is then the plain
+    one over engine.link_sample (blocking, both sides); pipelined=True, probit=True and noise="adaptive" are refused with
+    features.  res["beta_rows"] / res["beta_cols"]: the mean of beta over the post-burn-in samples (None without such samples)."""
+    linked = row_features is not None or col_features is not None
+    if linked:
+        if pipelined:
+            raise ValueError("pipelined=True does not go together with row_features / col_features (the features loop is blocking)")
+        if probit:
+            raise ValueError("probit=True does not go together with row_features / col_features")
+        if noise == "adaptive":
+            raise ValueError("noise='adaptive' does not go together with row_features / col_features")
+        if not (float(lambda_beta) > 0 and math.isfinite(float(lambda_beta))):
+            raise ValueError("lambda_beta must be positive and finite")
     if topn is not None and nsims - burnin < 1:
         raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
     if noise not in ("fixed", "adaptive"):
@@ -233,6 +256,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if probit:
         engine.set_probit(movies.side, threshold, 1)
         engine.set_probit(users.side, threshold, 2)
+    if linked:
+        if col_features is not None:
+            engine.set_features(movies.side, col_features, lambda_beta, 3)
+        if row_features is not None:
+            engine.set_features(users.side, row_features, lambda_beta, 4)
+        movies.linked = users.linked = True
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
@@ -246,6 +275,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             engine.samples_add(movies.side)
         if probit and i >= burnin and movies.test is not None:
             engine.probit_add(movies.test, movies.side, users.side)
+        if linked and i >= burnin:
+            if col_features is not None:
+                engine.link_add(movies.side)
+            if row_features is not None:
+                engine.link_add(users.side)
 
     if adaptive:
         res["alpha"], res["train_rmse"] = [], []
@@ -322,6 +356,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         label = (np.asarray(T[2]) > threshold).astype(np.float64) if have else np.zeros(0)
         res["auc"] = _engine.auc(res["prob"], label, 0.5) if have else float("nan")
         res["brier"] = float(np.mean((res["prob"] - label) ** 2)) if have else float("nan")
+    if linked:
+        res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
+        res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None
     res["movies"], res["users"] = movies, users
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)

@@ -330,6 +330,46 @@ BPMF_API int bpmf_hip_test_probit_get(bpmf_hip_test *test, double *prob_host, in
  * included).  BPMF_HIP_EINVAL for NULL arguments, n < 0 or a NaN score. */
 BPMF_API int bpmf_hip_auc(const double *score, const double *value, int64_t n, double threshold, double *auc);
 
+/* ---- side information: row / column features linked to the factor priors -----------
+ * A side with N columns may carry a dense feature matrix F (N x D, fp64), a link matrix beta (D x K) and a fixed
+ * lambda_beta > 0:
+ *     u_i | mu, Lambda, beta ~ N(mu + beta^T f_i, Lambda^-1),   rows of beta: beta_d ~ N(0, (lambda_beta Lambda)^-1).
+ * With u~_i = u_i - m_i, m_i = beta^T f_i, the unchanged column samplers draw u~ from the residual ratings r - m_c . y_r.
+ *
+ * bpmf_hip_side_set_features uploads F (row_major != 0: F[i * D + d]; 0: column-major, F[d * N + i], the layout of a .ddm file),
+ * forms G = F^T F + lambda_beta I on the device, factors and inverts it on the host (once), and allocates beta (0), the offsets
+ * M = F beta (0) and the residual array.  tag >= 1 is key word 1 of the Philox stream the normals of the link draw come from:
+ * different per side, and different from the probit tags in use.
+ * BPMF_HIP_EINVAL: D < 1 or > 1024, lambda_beta <= 0 or not finite, tag 0, a non-finite feature, an fp32 context, a sharded
+ * side, a context with a communicator, the BPMF_REDUCE formulation on, a probit side, propagated priors, or features set
+ * already.  BPMF_HIP_ENUM: G is not positive definite. */
+BPMF_API int bpmf_hip_side_set_features(bpmf_hip_side *side, const double *F_host, int D, int row_major, double lambda_beta, unsigned tag);
+/* The stateful, BLOCKING half-iteration of `self` against `other` (iter++):
+ *   1. hyper-parameters as bpmf_hyper_sample_ex at counter iter with the scatter lambda_beta beta^T beta and D extra degrees of freedom
+ *   2. beta = G^-1 F^T (U - 1 mu^T) + L_G^-T Z R^-T, Z: D x K normals of bpmf_randn_stream_tag(iter, tag), Lambda = R^T R
+ *   3. M = F beta      4. r~ = r - m_c . y_r      5. the column samplers on r~ write U~; cov from their sums      6. U = U~ + M
+ * A side without features takes steps 1 (plain) and 5 only.  A model with side information steps BOTH sides through this call;
+ * bpmf_hip_sys_sample and bpmf_hip_sample_side refuse a side with features.  bpmf_hip_sys_state reports iter, norm (of U), cov
+ * (of U~), mu, Lambda of a side stepped this way. */
+BPMF_API int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, double alpha);
+/* beta (D x K, row-major) and the offsets M (N x K, one row per column of the side); either may be NULL.  Waits. */
+BPMF_API int bpmf_hip_side_link_get(bpmf_hip_side *side, double *beta_host, double *offsets_host);
+/* Sets beta (D x K, row-major) and recomputes M = F beta on the device (a chain continued from stored state; the tests). */
+BPMF_API int bpmf_hip_side_link_set(bpmf_hip_side *side, const double *beta_host);
+/* The running mean of beta: _add adds the current beta (where bpmf_hip_side_aggr_add sits), _mean returns sum / nsamples. */
+BPMF_API int bpmf_hip_side_link_add(bpmf_hip_side *side);
+BPMF_API int bpmf_hip_side_link_mean(bpmf_hip_side *side, double *beta_host, int *nsamples);
+/* Steps 4 and 6 alone, for tests and tools: the residuals of the side's ratings for its current offsets and the current factors
+ * of `other` (nnz doubles, order of the ratings), and U += M on the side's current factors (norm: sum |u|^2 afterwards). */
+BPMF_API int bpmf_hip_side_link_residual(bpmf_hip_side *side, const bpmf_hip_side *other, double *r_host);
+BPMF_API int bpmf_hip_side_link_shift(bpmf_hip_side *side, double *norm);
+/* The two dense products of the link on host arrays (row-major fp64), for tests and tools; no handle needed.
+ *   tn: C (D x n) = A^T (B - 1 bvec^T), A: N x D, B: N x n, bvec: n doubles or NULL; n <= 128, or B = A (n = D: pass B = NULL)
+ *   nn: C (N x n) = A B, A: N x D, B: D x n, n <= 128
+ * Both are bit-identical from call to call; tn adds the partials of fixed chunks of N in chunk order, whatever the grid. */
+BPMF_API int bpmf_hip_link_gemm_tn(int device, const double *A, int64_t N, int D, const double *B, int n, const double *bvec, double *C);
+BPMF_API int bpmf_hip_link_gemm_nn(int device, const double *A, int64_t N, int D, const double *B, int n, double *C);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
@@ -376,11 +416,21 @@ BPMF_API int bpmf_hyper_sample(int K, int64_t N, const double *cov, const double
 BPMF_API int bpmf_hyper_draws(int K, int64_t N, uint32_t counter, double *au, double *z);
 BPMF_API int bpmf_hyper_finish(int K, int64_t N, const double *cov, const double *Um, const double *au, const double *z,
                                double *mu, double *LambdaU, double *LambdaF);
+/* The draw with an extra scatter matrix and extra degrees of freedom (side information: lambda_beta beta^T beta and the D rows
+ * of the link matrix): posterior scale X = I + N cov + kappa_m (..) + extra_scatter, Wishart degrees of freedom K + N + extra_dof;
+ * kappa_c = 2 + N is unchanged.  extra_scatter = NULL and extra_dof = 0: the bits of the functions above. */
+BPMF_API int bpmf_hyper_sample_ex(int K, int64_t N, const double *cov, const double *Um, const double *extra_scatter, int64_t extra_dof,
+                                  uint32_t counter, double *mu, double *LambdaU, double *LambdaF);
+BPMF_API int bpmf_hyper_draws_ex(int K, int64_t N, int64_t extra_dof, uint32_t counter, double *au, double *z);
+BPMF_API int bpmf_hyper_finish_ex(int K, int64_t N, const double *cov, const double *Um, const double *extra_scatter, const double *au,
+                                  const double *z, double *mu, double *LambdaU, double *LambdaF);
 /* cov = (prod - sum sum^T / N) / (N - 1)  (c++/sample.cpp:383-384) */
 BPMF_API void bpmf_cov_from_sums(int K, int64_t N, const double *sum, const double *prod, double *cov);
 /* the per-column normal stream, for tests: out[i] = i-th randn() after
  * rng_set_pos(counter) (c++/mvnormal.cpp:34-43) */
 BPMF_API void bpmf_randn_stream(uint32_t counter, int n, double *out);
+/* the same stream with key word 1 = tag (tag 0: bpmf_randn_stream) */
+BPMF_API void bpmf_randn_stream_tag(uint32_t counter, uint32_t tag, int n, double *out);
 /* the same n draws produced by the device sampler (n <= 128) */
 BPMF_API int bpmf_hip_randn_stream(bpmf_hip_ctx *ctx, uint32_t counter, int n, double *out);
 
