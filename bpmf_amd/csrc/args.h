@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "blob.h"
+
 namespace bpmf {
 
 // offset of row i in the packed lower-triangular row-major storage of L: row i keeps its

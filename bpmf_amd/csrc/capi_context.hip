@@ -129,17 +129,9 @@ int bounded_event_sync(bpmf_hip_ctx *c, hipEvent_t ev, const char *what)
 // half-iteration) on a path whose device work is only tens of microseconds.
 int wait_host(bpmf_hip_ctx *c)
 {
-    unsigned *flag = reinterpret_cast<unsigned *>(c->h_out + c->out_words - 1);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == c->seq) return 0;
-        if (spin_limit_s() <= 0.0) break;
-        __builtin_ia32_pause();
-        if ((spins & 0xFFFu) == 0xFFFu) {
-            const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (s > spin_limit_s()) break;       // long kernel (big matrix) or an error: fall back to a blocking wait
-        }
-    }
+    unsigned *flag = blob::res_flag_word(c->h_out, c->K);
+    if (spin_for_seq(flag, c->seq)) return 0;
+    // long kernel (big matrix) or an error: fall back to a blocking wait
     { const int rc = bounded_stream_sync(c, c->stream, "sampler + exchange + all-reduce of a half-iteration"); if (rc) return rc; }
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != c->seq) return fail(BPMF_HIP_ENODEV, "device did not publish its results");
     return 0;
@@ -214,17 +206,15 @@ static int ctx_create_impl(int device, int Ktrue, int dtype, void *stream, bpmf_
 #endif
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
     else { HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
-    c->in_words = (size_t)K * K + K + 2 + K;                           // LambdaF | Lmu | fail | pad | mu (even: staged as 16-byte words)
-    // | R0 = chol(LambdaF).matrixU() row-major | (R0^-1)^T | R0^-T LambdaF mu (k_sample_pf)
-    if (K == 64 && dtype == BPMF_HIP_F64) c->in_words += 2 * (size_t)K * K + K;
-    c->out_words = (size_t)K * K + K + 1 + 1 + 2 + 1;
+    c->in_words = (K == 64 && dtype == BPMF_HIP_F64) ? blob::par_words_pf(K) : blob::par_words(K);
+    c->out_words = blob::res_words(K);
     HIP_TRY(hipHostMalloc((void **)&c->h_in, c->in_words * sizeof(double), hipHostMallocMapped));
     HIP_TRY(hipHostMalloc((void **)&c->h_out, c->out_words * sizeof(double), hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer((void **)&c->h_in_dev, c->h_in, 0));
     HIP_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out, 0));
     memset(c->h_out, 0, c->out_words * sizeof(double));
     HIP_TRY(hipMalloc((void **)&c->d_in, (c->in_words + lf32_words(c)) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->d_red, (c->out_words + 8) * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&c->d_red, (size_t)blob::red_words(K) * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&c->d_ticket, 64));
     HIP_TRY(hipMemset(c->d_ticket, 0, 64));
     HIP_TRY(hipMalloc((void **)&c->d_zero, 1024));

@@ -292,20 +292,10 @@ extern "C" int bpmf_hip_predict_finish(bpmf_hip_test *t, double *se, double *se_
     HIP_TRY(hipSetDevice(c->device));
     const bool dist = c->comm && !self->bounds.empty();
     if (t->nnz == 0 && !dist) { *se = 0.0; *se_avg = 0.0; *count = 0; return BPMF_HIP_OK; }
-    {   // spin on the sequence number published behind the two sums
-        unsigned *flag = reinterpret_cast<unsigned *>(t->h_res + 2);
-        const auto t0 = std::chrono::steady_clock::now();
-        bool seen = false;
-        for (unsigned spins = 0; !seen; ++spins) {
-            seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == t->seq;
-            if (seen || spin_limit_s() <= 0.0) break;
-            __builtin_ia32_pause();
-            if ((spins & 0xFFFu) == 0xFFFu && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > spin_limit_s()) break;
-        }
-        if (!seen) {
-            { const int rs_ = bounded_stream_sync(t->side->ctx, live_pstream(t), __func__); if (rs_) return rs_; }
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->seq) return fail(BPMF_HIP_ENODEV, "device did not publish its results");
-        }
+    unsigned *flag = reinterpret_cast<unsigned *>(t->h_res + 2);     // the sequence number published behind the two sums
+    if (!spin_for_seq(flag, t->seq)) {
+        { const int rs_ = bounded_stream_sync(t->side->ctx, live_pstream(t), __func__); if (rs_) return rs_; }
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->seq) return fail(BPMF_HIP_ENODEV, "device did not publish its results");
     }
     t->done_seq = t->seq;                                           // every block has read its factors
     trace("predict: sums landed", self, 0);
@@ -315,7 +305,7 @@ extern "C" int bpmf_hip_predict_finish(bpmf_hip_test *t, double *se, double *se_
     if (dist) {
         if (t->global_nnz < 0) {                                   // once: number of test ratings over all ranks
             COMM_ALIVE_OR_FAIL(c, "predict_finish");
-            long long v = (long long)t->nnz, *d = reinterpret_cast<long long *>(c->d_red + c->out_words + 4);
+            long long v = (long long)t->nnz, *d = reinterpret_cast<long long *>(c->d_red + blob::red_count(c->K));
             HIP_TRY(hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
             NCCL_TRY(rccl()->AllReduce(d, d, 1, ncclInt64, ncclSum, c->comm, c->stream));
             HIP_TRY(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, c->stream));

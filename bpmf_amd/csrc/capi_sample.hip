@@ -7,6 +7,18 @@ namespace bpmf_capi {
 
 using bpmf_launch::sampler_into;
 
+// the copy of the factors the side's next sampler writes: wait (on `st`) for the evaluation that may still read it
+int claim_second_copy(bpmf_hip_side *s, hipStream_t st)
+{
+    bpmf_hip_side::Reader &rd = s->readers[s->cur_buf ^ 1];
+    if (rd.t) {
+        if (rd.t->deferred && rd.seq == rd.t->seq + 1) flush_deferred(rd.t);      // (the one that reads this copy, not a later one)
+        if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u], 0));
+    }
+    rd.t = nullptr;
+    return 0;
+}
+
 template <int K, bool F32>
 int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, double *d_in, hipStream_t st,
                    hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr)
@@ -17,17 +29,11 @@ int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, do
     if (self->d_probit_z && !self->probit_latent_queued) { const int rp = probit_latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
-    const int tgt = self->cur_buf ^ 1;
-    bpmf_hip_side::Reader &rd = self->readers[tgt];
-    if (rd.t) {
-        if (rd.t->deferred && rd.seq == rd.t->seq + 1) flush_deferred(rd.t);      // (the one that reads this copy, not a later one)
-        if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u], 0));
-    }
-    rd.t = nullptr;
-    const int rc = sampler_into<K, F32>(self, self->d_items_alt, other, iter, alpha, d_in, st, ev_start, ev_stop);
+    int rc = claim_second_copy(self, st);
+    if (!rc) rc = sampler_into<K, F32>(self, self->d_items_alt, other, iter, alpha, d_in, st, ev_start, ev_stop);
     if (rc) return rc;
     std::swap(self->d_items, self->d_items_alt);                    // everything enqueued from here on sees the new factors
-    self->cur_buf = tgt;
+    self->cur_buf ^= 1;
     return 0;
 }
 
@@ -68,22 +74,11 @@ int reduce_half_iteration(bpmf_hip_side *self, const bpmf_hip_side *other, int i
     double *out_items = self->d_items;
     const bool swap = second_copy_usable(self);
     if (swap) {
-        const int tgt = self->cur_buf ^ 1;
-        bpmf_hip_side::Reader &rd = self->readers[tgt];
-        if (rd.t) {
-            if (rd.t->deferred && rd.seq == rd.t->seq + 1) flush_deferred(rd.t);
-            if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u], 0));
-        }
-        rd.t = nullptr;
+        { const int rcc = claim_second_copy(self, st); if (rcc) return rcc; }
         out_items = self->d_items_alt;                              // (complete after this launch + the exchange: second_copy_usable)
     }
-    bpmf::SampleArgs a{};
+    bpmf::SampleArgs a = bpmf_launch::blob_args(self, out_items, d_in, iter, alpha);
     a.nwork = (int)(self->to - self->from);
-    a.items = out_items; a.col_from = self->from;
-    a.LambdaF = d_in; a.Lmu = d_in + (size_t)K * K;
-    a.fail = (unsigned long long *)(d_in + (size_t)K * K + K);
-    a.mu = d_in + (size_t)K * K + K + 2; a.prop_lambda = self->d_prop; a.diag_only = c->diag_only;
-    a.mean_rating = self->mean_rating; a.alpha = alpha; a.iter_plus_1 = (uint32_t)(iter + 1); a.ktrue = c->Kt;
     const int resident = c->num_cu * 4 * bpmf_launch::reduce_waves_per_simd(K);
     const int C = 64 / K;
     const int grid = std::max(1, std::min((a.nwork + C - 1) / C, resident));
@@ -159,7 +154,7 @@ int sample_and_exchange(bpmf_hip_side *self, const bpmf_hip_side *other, int ite
 }
 
 
-// parameter blob of one half-iteration: LambdaF | LambdaF*mu | "no column failed"
+// parameter blob of one half-iteration (blob.h), "no column failed"; with_factor: with the tail of the product form
 // LambdaU (optional): the upper factor the hyper-parameter draw produced, LambdaF = LambdaU^T LambdaU (c++/bpmf.h:101) -- it IS
 // chol(LambdaF).matrixU() up to rounding (upper triangular, positive diagonal), so the factorisation below is skipped
 void fill_blob(int K, const double *mu, const double *LambdaF, double *h_in, bool with_factor, const double *LambdaU = nullptr)
@@ -169,17 +164,17 @@ void fill_blob(int K, const double *mu, const double *LambdaF, double *h_in, boo
     for (int i = 0; i < K; ++i) {
         double s = 0.0;
         for (int j = 0; j < K; ++j) s += LambdaF[(size_t)j * K + i] * mu[j];
-        h_in[(size_t)K * K + i] = s;
+        h_in[blob::par_Lmu(K) + i] = s;
     }
-    const unsigned long long nofail = ~0ull;
-    memcpy(&h_in[(size_t)K * K + K], &nofail, sizeof(nofail));
-    h_in[(size_t)K * K + K + 1] = 0.0;
-    memcpy(&h_in[(size_t)K * K + K + 2], mu, sizeof(double) * K);       // hp.mu itself: the propagated-posterior columns need it
+    *blob::par_fail_word(h_in, K) = ~0ull;
+    h_in[blob::par_fail(K) + 1] = 0.0;                                  // (the pad word)
+    memcpy(&h_in[blob::par_mu(K)], mu, sizeof(double) * K);             // hp.mu itself: the propagated-posterior columns need it
     if (with_factor) {
         // R0 = chol(LambdaF).matrixU(), row-major with zeros below the diagonal: the factor shared by every
         // light column (k_sample_pf).  Not positive definite: NaN, which reaches the samples
         // and is reported as "Cholesky failed" like the reference's own LLT (c++/sample.cpp:306-308).
-        double *R = h_in + (size_t)K * K + K + 2 + K;
+        double *R = h_in + blob::par_R0(K), *S0t = h_in + blob::par_S0t(K), *y0 = h_in + blob::par_y0(K);
+        const size_t tail = (size_t)(blob::par_words_pf(K) - blob::par_words(K));      // R0 | S0t | y0
         bool ok = true;
         if (LambdaU) {
             for (int i = 0; i < K; ++i)
@@ -195,9 +190,8 @@ void fill_blob(int K, const double *mu, const double *LambdaF, double *h_in, boo
                 else R[(size_t)i * K + j] = v / R[(size_t)i * K + i];
             }
         }
-        double *S0t = R + (size_t)K * K, *y0 = S0t + (size_t)K * K;
         if (!ok) {
-            for (size_t q = 0; q < 2 * (size_t)K * K + K; ++q) R[q] = std::numeric_limits<double>::quiet_NaN();
+            for (size_t q = 0; q < tail; ++q) R[q] = std::numeric_limits<double>::quiet_NaN();
         } else {
             // S = R0^-1 (upper), stored transposed (S0t[j*K + i] = S[i][j]); y0 = R0^-T (LambdaF mu): what the
             // columns WITHOUT ratings need (x = S (y0 + z))
@@ -220,8 +214,8 @@ void fill_blob(int K, const double *mu, const double *LambdaF, double *h_in, boo
             for (int c = 0; c < K && ok; ++c)
                 for (int r = c + 1; r < K; ++r)
                     if (S0t[(size_t)c * K + r] != 0.0) { ok = false; break; }
-            if (!ok) { for (size_t q = 0; q < 2 * (size_t)K * K + K; ++q) R[q] = std::numeric_limits<double>::quiet_NaN(); return; }
-            const double *Lmu = h_in + (size_t)K * K;
+            if (!ok) { for (size_t q = 0; q < tail; ++q) R[q] = std::numeric_limits<double>::quiet_NaN(); return; }
+            const double *Lmu = h_in + blob::par_Lmu(K);
             for (int k = 0; k < K; ++k) {                  // R0^T y = Lmu
                 double v = Lmu[k];
                 for (int i = 0; i < k; ++i) v -= R[(size_t)i * K + k] * y0[i];
@@ -272,15 +266,51 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     int rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, c->d_in, c->stream, nullptr, nullptr));
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    unsigned *flag = reinterpret_cast<unsigned *>(c->h_out_dev + c->out_words - 1);
-    rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, c->stream, c->d_in, c->h_out_dev, flag, ++c->seq, c->d_ticket));
+    const bpmf_launch::StatPass sp = bpmf_launch::stat_pass(self, c->d_in, c->h_out_dev, c->d_ticket, ++c->seq);
+    rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, c->stream, sp));
     if (rc) return rc;
     HIP_TRY(hipEventRecord(c->ev[2], c->stream));
-    // prod | sum | - | fail word land in the pinned result blob; the last wave of k_colstats
+    // the sums and the fail word land in the pinned result blob; the last wave of k_colstats
     // publishes the sequence number behind them
     HIP_TRY(hipGetLastError());
     self->pending = true;
     return BPMF_HIP_OK;
+}
+
+// Reads the result blob `h_out` of a completed half-iteration of `s`.  In this order: a device-side wait that timed out
+// (BPMF_HIP_ENODEV) or a probit draw that ran into its cap (BPMF_HIP_ENUM) -- the sums are not to be used, nothing else is
+// touched; norm = sum |x|^2 = trace(sum x x^T) (c++/sample.cpp:381); the fail word -> failed_column and BPMF_HIP_ECHOL.
+// sum_out / prod_out given (stateless path): the sums in the caller's size Kt (the extra rows / columns are zero), handed
+// out whether a column failed or not.  NULL (stateful path): unless a column failed, cov of the side (c++/sample.cpp:383-384).
+int read_result_blob(bpmf_hip_side *s, double *h_out, double *sum_out, double *prod_out, double *norm, std::string *msg)
+{
+    const int K = s->ctx->K, Kt = s->ctx->Kt;
+    int rc = check_timeout(h_out, K, msg);
+    if (!rc) rc = check_probit(s, msg);                   // (the latent kernel ran ahead of the sampler whose sums these are)
+    if (rc) return rc;
+    const double *prod = h_out + blob::res_prod(K), *sum = h_out + blob::res_sum(K);
+    const unsigned long long f = *blob::res_fail_word(h_out, K);
+    const bool failed = f != ~0ull;
+    s->failed_column = failed ? (int64_t)f : -1;
+    if (failed) *msg = "Cholesky failed in column " + std::to_string((long long)f);
+    if (!failed || prod_out) {
+        double nn = 0.0;
+        for (int i = 0; i < Kt; ++i) nn += prod[(size_t)i * K + i];
+        *norm = nn;
+    }
+    if (prod_out) {
+        unpad_square(Kt, K, prod, prod_out);
+        memcpy(sum_out, sum, sizeof(double) * Kt);
+    } else if (!failed) {
+        if (Kt == K) bpmf_cov_from_sums(K, s->ncols, sum, prod, s->cov.data());
+        else {                                                        // padded num_latent: the leading Kt x Kt block of the sums
+            static thread_local std::vector<double> pc;
+            pc.resize((size_t)Kt * Kt);
+            unpad_square(Kt, K, prod, pc.data());
+            bpmf_cov_from_sums(Kt, s->ncols, sum, pc.data(), s->cov.data());
+        }
+    }
+    return failed ? BPMF_HIP_ECHOL : 0;
 }
 
 extern "C" int bpmf_hip_sample_side_finish(bpmf_hip_side *self, double *sum_out, double *prod_out, double *norm_out)
@@ -288,29 +318,13 @@ extern "C" int bpmf_hip_sample_side_finish(bpmf_hip_side *self, double *sum_out,
     if (!self || !sum_out || !prod_out || !norm_out) return fail(BPMF_HIP_EINVAL, "sample_side_finish: NULL argument");
     if (!self->pending) return fail(BPMF_HIP_EINVAL, "sample_side_finish: nothing launched");
     bpmf_hip_ctx *c = self->ctx;
-    const int K = c->K;
     HIP_TRY(hipSetDevice(c->device));
     self->pending = false;
     { const int rcw = wait_host(c); if (rcw) return rcw; }
-    { std::string m; if (check_timeout(c->h_out, K, &m)) return fail(BPMF_HIP_ENODEV, m); }
-    { std::string m; if (check_probit(self, &m)) return fail(BPMF_HIP_ENUM, m); }
-    const int Kt = c->Kt;                                           // (the caller's size; the extra rows / columns of the sums are zero)
-    unpad_square(Kt, K, c->h_out, prod_out);
-    memcpy(sum_out, c->h_out + (size_t)K * K, sizeof(double) * Kt);
-    {   // sum |x|^2 = trace(sum x x^T)
-        double nn = 0.0;
-        for (int i = 0; i < Kt; ++i) nn += c->h_out[(size_t)i * K + i];
-        *norm_out = nn;
-    }
-    unsigned long long f;
-    memcpy(&f, &c->h_out[(size_t)K * K + K + 1], sizeof(f));
-    self->timing_valid = false;
-    if (f != ~0ull) {
-        self->failed_column = (int64_t)f;
-        return fail(BPMF_HIP_ECHOL, "Cholesky failed in column " + std::to_string((long long)f));
-    }
-    self->failed_column = -1;
-    return BPMF_HIP_OK;
+    std::string m;
+    const int rc = read_result_blob(self, c->h_out, sum_out, prod_out, norm_out, &m);
+    if (rc != BPMF_HIP_ENODEV && rc != BPMF_HIP_ENUM) self->timing_valid = false;     // (the blob was read)
+    return rc ? fail(rc, m) : BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_sample_side(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha,
@@ -423,7 +437,7 @@ int ensure_state(bpmf_hip_side *s)
     HIP_TRY(hipMemset(s->a_ticket, 0, 256));
     HIP_TRY(hipMalloc((void **)&s->a_dflag, 64));
     HIP_TRY(hipMemset(s->a_dflag, 0, 64));
-    HIP_TRY(hipMalloc((void **)&s->a_d_red, (c->out_words + 8) * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&s->a_d_red, (size_t)blob::red_words(c->K) * sizeof(double)));
     static const unsigned evflags = hipEventDisableSystemFence;
     for (auto &set : s->evs) for (hipEvent_t &e : set) HIP_TRY(hipEventCreateWithFlags(&e, evflags));
     int lo = 0, hi = 0;                                              // numerically lowest = most urgent
@@ -527,7 +541,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
     bpmf_hip_ctx *c = s->ctx;
     const int K = c->K;
     trace("collect: start", s, job.iter);
-    unsigned *flag = reinterpret_cast<unsigned *>(s->a_h_out + c->out_words - 1);
+    unsigned *flag = blob::res_flag_word(s->a_h_out, K);
     // while the device is still sampling: the random part of the next draw (gamma / normal stream
     // of WishartUnitChol and MvNormalChol_prec), which needs no result of this half-iteration
     if (s->nx_iter == job.iter) {                                     // the parameters this half-iteration ran with
@@ -535,14 +549,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
         s->nx_iter = -2;
     }
     trace("collect: draws ready, spinning", s, job.iter);
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (unsigned spins = 0; !seen; ++spins) {
-        seen = __atomic_load_n(flag, __ATOMIC_ACQUIRE) == job.seq;
-        if (seen || spin_limit_s() <= 0.0) break;
-        __builtin_ia32_pause();
-        if ((spins & 0xFFFu) == 0xFFFu && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > spin_limit_s()) break;
-    }
+    const bool seen = spin_for_seq(flag, job.seq);
     trace("collect: sums landed", s, job.iter);
     (void)hipSetDevice(c->device);
     hipEvent_t *ev = s->evs[job.evset];
@@ -566,31 +573,10 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
             rc = BPMF_HIP_ENODEV;
         }
     }
-    if (!rc) rc = check_timeout(s->a_h_out, K, &msg);     // a bounded in-kernel wait gave up: the sums are not to be used
-    if (!rc) rc = check_probit(s, &msg);                  // (the latent kernel ran ahead of the sampler whose sums these are)
+    if (!rc) rc = read_result_blob(s, s->a_h_out, nullptr, nullptr, &s->norm, &msg);
     if (!rc) {
-        const double *prod = s->a_h_out, *sum = s->a_h_out + (size_t)K * K;
-        unsigned long long f;
-        memcpy(&f, &s->a_h_out[(size_t)K * K + K + 1], sizeof f);
-        if (f != ~0ull) {
-            s->failed_column = (int64_t)f;
-            rc = BPMF_HIP_ECHOL; msg = "Cholesky failed in column " + std::to_string((long long)f);
-        } else {
-            s->failed_column = -1;
-            const int Kt = c->Kt;
-            double nn = 0.0;                                          // sum |x|^2 = trace(sum x x^T)  (:381)
-            for (int i = 0; i < Kt; ++i) nn += prod[(size_t)i * K + i];
-            s->norm = nn;
-            { std::lock_guard<std::mutex> lk(s->wm); s->norm_hist[job.iter & 7] = nn; s->collected_iter = job.iter; }
-            s->wcv.notify_all();
-            if (Kt == K) bpmf_cov_from_sums(K, s->ncols, sum, prod, s->cov.data());   // :383-384
-            else {                                                    // padded num_latent: the leading Kt x Kt block of the sums
-                static thread_local std::vector<double> pc;
-                pc.resize((size_t)Kt * Kt);
-                unpad_square(Kt, K, prod, pc.data());
-                bpmf_cov_from_sums(Kt, s->ncols, sum, pc.data(), s->cov.data());
-            }
-        }
+        { std::lock_guard<std::mutex> lk(s->wm); s->norm_hist[job.iter & 7] = s->norm; s->collected_iter = job.iter; }
+        s->wcv.notify_all();
     }
     // the next half-iteration of this side: parameters + gate (opened in every case, see above)
     const int rd = draw_and_release(s, job.iter + 1, s->nx_mu.data(), s->nx_LambdaU.data(), s->nx_LambdaF.data());
@@ -638,6 +624,12 @@ void post_collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
     s->wcv.notify_all();
 }
 
+// the statistics pass of a stateful side, sequence number `seq`: the side's own parameter / result blobs and tickets
+static bpmf_launch::StatPass own_stat_pass(const bpmf_hip_side *P, unsigned seq)
+{
+    return bpmf_launch::stat_pass(P, P->a_d_in, P->a_h_out_dev, P->a_ticket, seq);
+}
+
 // fused stateful path: the statistics of the newest half-iteration ride in the NEXT sampler launch;
 // when somebody needs them and no launch has come, they run as a kernel of their own on the side's stream
 // on_main: on the main stream, in order behind P's sampler (end of a run: nothing else is coming on that stream, and a
@@ -654,8 +646,7 @@ int flush_pending_stats(bpmf_hip_ctx *c, bool on_main)
     hipStream_t sst = on_main ? c->stream : P->saux;
     if (!on_main) HIP_TRY(hipStreamWaitEvent(sst, ev[1], 0));        // (ev[1]: recorded with / behind P's sampler)
     else c->last_sampler_done = nullptr;                              // (the newest thing on S0 is no longer a sampler)
-    unsigned *flag = reinterpret_cast<unsigned *>(P->a_h_out_dev + c->out_words - 1);
-    const int rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(P, sst, P->a_d_in, P->a_h_out_dev, flag, c->pending_seq, P->a_ticket));
+    const int rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(P, sst, own_stat_pass(P, c->pending_seq)));
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ev[2], sst));
     P->stats_ev[c->pending_evset].store(ev[2], std::memory_order_release);
@@ -688,19 +679,6 @@ int wait_async(bpmf_hip_side *s, int depth)
 
 
 int settle_async(bpmf_hip_side *s) { return wait_async(s, 0); }
-
-
-// the copy of the factors the side's next sampler writes: wait (on `st`) for the evaluation that may still read it
-int claim_second_copy(bpmf_hip_side *s, hipStream_t st)
-{
-    bpmf_hip_side::Reader &rd = s->readers[s->cur_buf ^ 1];
-    if (rd.t) {
-        if (rd.t->deferred && rd.seq == rd.t->seq + 1) flush_deferred(rd.t);
-        if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u], 0));
-    }
-    rd.t = nullptr;
-    return 0;
-}
 
 
 extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, double alpha)
@@ -749,7 +727,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     const bool dist = c->comm != nullptr && !self->bounds.empty();
     // (K = 64, slab form without low-rank columns: the same launch format, k_sample1s<64>; only the words the slab
     // form reads are staged -- the R0 / R0^-1 tail of the K = 64 blob belongs to the low-rank forms)
-    const size_t stage_words = (K == 64 && self->lr_n == 0) ? (size_t)K * K + K + 2 + K : c->in_words;
+    const size_t stage_words = (K == 64 && self->lr_n == 0) ? (size_t)blob::par_words(K) : c->in_words;
     const bool fusable_form = (K <= 32 && self->mode == 1) || (K == 64 && self->lr_n == 0 && self->nsub <= 1);
     const bool fused = s1 != s0 && !dist && stage_words <= 8192 && fusable_form && self->nwork > 0 && !self->reduce_on &&
                        c->dtype == BPMF_HIP_F64 && env_int("BPMF_HIP_FUSED", 1) != 0;
@@ -764,16 +742,12 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     if (carry && P == self && !second_copy_usable(self)) carry = false;
     if (P && !carry) { if ((rc = flush_pending_stats(c))) return rc; }
     bpmf::StatRiders riders{};
+    const bpmf_launch::StatPass sp = carry ? own_stat_pass(P, c->pending_seq) : bpmf_launch::StatPass{};
     if (carry && ride_f32) {
         const int nw = 2;                                             // waves per workgroup of k_sample_wg2<128, 2, float>
-        const int njobs = P->nstat_waves * (K / 16) * (K / 16 + 1) / 2;
-        riders.nblocks = (njobs + nw - 1) / nw;
-        riders.items = P->d_items; riders.c0 = P->from; riders.c1 = P->to; riders.nsl = P->nstat_waves;
-        riders.partials = P->d_stat_partials;
-        riders.fail_in = (const unsigned long long *)(P->a_d_in + (size_t)K * K + K);
-        riders.out = P->a_h_out_dev; riders.ticket = P->a_ticket;
-        riders.flag = reinterpret_cast<unsigned *>(P->a_h_out_dev + c->out_words - 1); riders.seq = c->pending_seq;
-        riders.tmo = tmo_word(P->a_h_out_dev, K); riders.wait_ticks = wait_ticks();
+        const int njobs = sp.nwaves * (K / 16) * (K / 16 + 1) / 2;
+        riders = {(njobs + nw - 1) / nw, sp.items, sp.c0, sp.c1, sp.nwaves, sp.partials, sp.fail_in, sp.out,
+                  sp.ticket, sp.flag, sp.seq, sp.tmo, wait_ticks()};
     }
     // probit side: the latent kernel goes onto S0 HERE, before S0 is made to wait for the gate kernel below (unfused form:
     // gate_stage spins on S1 until the host has drawn and staged this half-iteration's hyper-parameters, and S0 continues
@@ -789,16 +763,13 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
         fz.gate_host = self->a_gate_dev; fz.gate_want = (unsigned)(iter + 1); fz.src_host = self->a_h_in_dev;
         fz.dst = self->a_d_in; fz.n = (int)stage_words; fz.dflag = self->a_dflag; fz.dval = seq;
         if (carry && !ride_f32) {
-            fz.nstat = P->nstat_waves; fz.st_items = P->d_items; fz.st_c0 = P->from; fz.st_c1 = P->to;
-            fz.st_partials = P->d_stat_partials;
-            fz.st_fail = (const unsigned long long *)(P->a_d_in + (size_t)K * K + K);
-            fz.st_out = P->a_h_out_dev; fz.st_ticket = P->a_ticket;
-            fz.st_flag = reinterpret_cast<unsigned *>(P->a_h_out_dev + c->out_words - 1); fz.st_seq = c->pending_seq;
-            fz.st_tmo = tmo_word(P->a_h_out_dev, K);
+            fz.nstat = sp.nwaves; fz.st_items = static_cast<const double *>(sp.items); fz.st_c0 = sp.c0; fz.st_c1 = sp.c1;
+            fz.st_partials = sp.partials; fz.st_fail = sp.fail_in; fz.st_out = sp.out; fz.st_ticket = sp.ticket;
+            fz.st_flag = sp.flag; fz.st_seq = sp.seq; fz.st_tmo = sp.tmo;
         }
     } else {
         bpmf_launch::gate_stage(c->in_words > 8192 ? 16 : 1, self->a_gate_dev, (unsigned)(iter + 1), self->a_h_in_dev, self->a_d_in, (int)c->in_words,
-                                tmo_word(self->a_h_out_dev, K), wait_ticks(), s1);
+                                blob::tmo_word(self->a_h_out_dev, K), wait_ticks(), s1);
         if (lf32_words(c)) bpmf_launch::lf32_tiles(self->a_d_in, reinterpret_cast<float *>(self->a_d_in + c->in_words), K, s1);
         if (s1 != s0) {
             HIP_TRY(hipEventRecord(ev[3], s1));
@@ -872,8 +843,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
             HIP_TRY(hipEventRecord(self->ev_stat_go, sst));
             HIP_TRY(hipStreamWaitEvent(s0, self->ev_stat_go, 0));
         }
-        unsigned *flag = reinterpret_cast<unsigned *>(self->a_h_out_dev + c->out_words - 1);
-        rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, sst, self->a_d_in, self->a_h_out_dev, flag, seq, self->a_ticket));
+        rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, sst, own_stat_pass(self, seq)));
         if (rc) return rc;
         HIP_TRY(hipEventRecord(ev[2], sst));
         self->stats_ev[evset].store(ev[2], std::memory_order_release);
@@ -923,8 +893,5 @@ extern "C" int bpmf_hip_sys_norm(bpmf_hip_side *s, int iter, double *norm)
     *norm = s->norm_hist[iter & 7];
     return BPMF_HIP_OK;
 }
-
-// Which kernel(s) the sampler launch of this side is, as the dispatch in launch_impl.h (sampler_into) decides it:
-// what a profile of the run shows, for the labels of bench.py's roofline object.
 
 }  // namespace bpmf_capi

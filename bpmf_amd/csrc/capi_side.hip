@@ -181,7 +181,7 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
         // column statistics: <= 32 slices of columns x 36 tiles (k_colstats_f32), one partial (tiles | sum) per slice
         // (128 partials of 132 KB were 17 MB written and read back per half-iteration: the two kernels took 55 us alone)
         s->nstat_waves = (int)std::max<int64_t>(1, std::min<int64_t>((nloc + 63) / 64, 32));
-        if ((rc = dev_upload<double>(&s->d_stat_partials, nullptr, (size_t)s->nstat_waves * ((size_t)K * K + K)))) return rc;
+        if ((rc = dev_upload<double>(&s->d_stat_partials, nullptr, (size_t)s->nstat_waves * blob::stat_partial_words(K)))) return rc;
         if ((rc = dev_upload<double>(&s->d_partials, nullptr, (size_t)slots * part_words_rt(K, f32)))) return rc;     // chunks of heavy columns
         return 0;
     }

@@ -1236,7 +1236,7 @@ __device__ __forceinline__ void colstats_body(int w, const double *__restrict__ 
 {
     // img: kColstatsRot<K> ? 512 doubles of the (single-wave) workgroup's LDS : unused
     constexpr int NT = Geo<K>::NT, NTRI = Geo<K>::NTRI, PART = Geo<K>::PART;
-    constexpr int NSLICE = (K * K + K + 15) / 16;
+    constexpr int NSUMS = blob::res_sums(K), NSLICE = (NSUMS + 15) / 16, FAILD = blob::res_failD(K), FAIL = blob::res_fail(K);
     const int lane = threadIdx.x;
     const int64_t n = c1 - c0;
     const int64_t per = (((n + nwaves - 1) / nwaves) + 3) & ~(int64_t)3;
@@ -1284,7 +1284,7 @@ __device__ __forceinline__ void colstats_body(int w, const double *__restrict__ 
     for (int slice = f; slice < NSLICE; slice += nfin) {
         const int eo = slice * 16 + o;
         double s = 0.0;
-        if (eo < K * K + K) {
+        if (eo < NSUMS) {
             int off;
             if (eo < K * K) {
                 int i = eo % K, j = eo / K;
@@ -1320,15 +1320,15 @@ __device__ __forceinline__ void colstats_body(int w, const double *__restrict__ 
         }
         s += __shfl_xor(s, 16);                                      // (g0 + g1), (g2 + g3)
         s += __shfl_xor(s, 32);                                      // fixed order: ((g0 + g1) + (g2 + g3))
-        if (grp == 0 && eo < K * K + K) __hip_atomic_store(&out[eo], s, BPMF_RLX_SYSTEM);
+        if (grp == 0 && eo < NSUMS) __hip_atomic_store(&out[eo], s, BPMF_RLX_SYSTEM);
     }
     if (f == 0 && lane == 0) {
         // failed column: as the u64 word of the blob, and as a double (0 = none, id + 1 otherwise)
         // that survives a SUM all-reduce of the blob over the ranks
         // (device-scope load: as riders of a fused launch the pass runs beside items that may lower the word on another XCD)
         const unsigned long long fw = __hip_atomic_load(fail_in, BPMF_RLX_AGENT);
-        __hip_atomic_store(&out[K * K + K], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
-        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[K * K + K + 1], fw, BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&out[FAILD], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[FAIL], fw, BPMF_RLX_SYSTEM);
     }
     publish_when_last(ticket + 1, (unsigned)nfin, flag, seq, ticket);
 }
@@ -1367,7 +1367,7 @@ __global__ __launch_bounds__(256) void k_colstats_wg(const double *__restrict__ 
     // items' column `from` = part of the pointer: `items` already points at local column 0).  This launch's workgroups write
     // the partials part0 .. part0 + nwg - 1; with `finish` its last arrivals add all `ntot` partials (those of earlier
     // launches on the same stream included) and publish, without it the launch only leaves its partials.
-    constexpr int NT = Geo<K>::NT, NTRI = Geo<K>::NTRI, PART = Geo<K>::PART, NBLK = (PART + 63) / 64;
+    constexpr int NT = Geo<K>::NT, NTRI = Geo<K>::NTRI, PART = Geo<K>::PART, NBLK = (PART + 63) / 64, FAILD = blob::res_failD(K), FAIL = blob::res_fail(K);
     __shared__ double red[PART];
     __shared__ double fin[4][64];
     __shared__ unsigned stk;
@@ -1477,8 +1477,8 @@ __global__ __launch_bounds__(256) void k_colstats_wg(const double *__restrict__ 
     }
     if (f == 0 && tid == 0) {
         const unsigned long long fw = *fail_in;
-        __hip_atomic_store(&out[K * K + K], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
-        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[K * K + K + 1], fw, BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&out[FAILD], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[FAIL], fw, BPMF_RLX_SYSTEM);
     }
     publish_when_last(ticket + 1, (unsigned)nfin, flag, seq, ticket);
 }

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void k_colstats_f32_final(const double *__rest
                                                             const unsigned long long *__restrict__ fail_in,
                                                             double *__restrict__ out, unsigned *ticket, unsigned *flag, unsigned seq)
 {
-    constexpr int NT = K / 16, NTRI = NT * (NT + 1) / 2, PARTW = NTRI * 256 + K, NOUT = K * K + K;
+    constexpr int NT = K / 16, NTRI = NT * (NT + 1) / 2, PARTW = NTRI * 256 + K, NOUT = blob::res_sums(K), FAILD = blob::res_failD(K), FAIL = blob::res_fail(K);
     const int o = blockIdx.x * 256 + threadIdx.x;
     if (o < NOUT) {
         int at;
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(256) void k_colstats_f32_final(const double *__rest
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const unsigned long long fw = *fail_in;
-        __hip_atomic_store(&out[NOUT], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
-        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[NOUT + 1], fw, BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&out[FAILD], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(out)[FAIL], fw, BPMF_RLX_SYSTEM);
     }
     publish_when_last(ticket, gridDim.x, flag, seq);
 }
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_colstats_f32_final(const double *__rest
 template <int K, int NW, typename T = float>
 __device__ __forceinline__ void colstats_f32_rider(const StatRiders &r, int rb, int tid)
 {
-    constexpr int NT = K / 16, NTRI = NT * (NT + 1) / 2, PARTW = NTRI * 256 + K, NOUT = K * K + K, NTH = 64 * NW;
+    constexpr int NT = K / 16, NTRI = NT * (NT + 1) / 2, PARTW = NTRI * 256 + K, NOUT = blob::res_sums(K), NTH = 64 * NW, FAILD = blob::res_failD(K), FAIL = blob::res_fail(K);
     __shared__ unsigned stk;
     const int wave = tid >> 6, lane = tid & 63, kq = lane >> 4, li = lane & 15;
     const int job = rb * NW + wave;
@@ -242,8 +242,8 @@ __device__ __forceinline__ void colstats_f32_rider(const StatRiders &r, int rb, 
     }
     if (f == 0 && tid == 0) {
         const unsigned long long fw = *r.fail_in;
-        __hip_atomic_store(&r.out[NOUT], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
-        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(r.out)[NOUT + 1], fw, BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&r.out[FAILD], (fw == ~0ull) ? 0.0 : (double)(fw + 1ull), BPMF_RLX_SYSTEM);
+        __hip_atomic_store(&reinterpret_cast<unsigned long long *>(r.out)[FAIL], fw, BPMF_RLX_SYSTEM);
     }
     publish_when_last(r.ticket + 1, (unsigned)nfin, r.flag, r.seq, r.ticket);
 }

@@ -47,6 +47,34 @@ inline Probe *&probe() { static thread_local Probe *p = nullptr; return p; }
 inline unsigned &next_flags() { static thread_local unsigned f = 0; return f; }
 inline unsigned take_flags() { unsigned &f = next_flags(); const unsigned v = f; f = 0; return v; }
 
+// A sampler's arguments pointed at the parameter blob `d_in` (blob.h) and at the side: the per-call members every form of
+// the sampler reads.  Value-initialised: the schedule, gate and profiling members are left to the caller.
+inline bpmf::SampleArgs blob_args(const bpmf_hip_side *self, double *out_items, double *d_in, int iter, double alpha)
+{
+    const bpmf_hip_ctx *c = self->ctx;
+    const int K = c->K;
+    bpmf::SampleArgs a{};
+    a.items = out_items; a.col_from = self->from;
+    a.LambdaF = d_in + blob::par_LambdaF(K); a.Lmu = d_in + blob::par_Lmu(K); a.fail = blob::par_fail_word(d_in, K);
+    a.mu = d_in + blob::par_mu(K); a.prop_lambda = self->d_prop; a.diag_only = c->diag_only;
+    a.mean_rating = self->mean_rating; a.alpha = alpha; a.iter_plus_1 = (uint32_t)(iter + 1); a.ktrue = c->Kt;
+    return a;
+}
+
+// The statistics pass of side P with sequence number `seq`: what it reads (P's current factors, the fail word of the
+// parameter blob `d_in` its sampler ran with) and where its sums, flag and time-out word go (the result blob `out`).
+// The stand-alone kernels (stats below) and the riders of a sampler launch (FusedArgs::st_*, StatRiders) are filled from it.
+struct StatPass {
+    const void *items; int64_t c0, c1; int nwaves; double *partials;
+    const unsigned long long *fail_in; double *out; unsigned *ticket, *flag; unsigned seq; unsigned long long *tmo;
+};
+inline StatPass stat_pass(const bpmf_hip_side *P, const double *d_in, double *out_host_dev, unsigned *ticket, unsigned seq)
+{
+    const int K = P->ctx->K;
+    return {P->d_items, P->from, P->to, P->nstat_waves, P->d_stat_partials, blob::par_fail_word(d_in, K),
+            out_host_dev, ticket, blob::res_flag_word(out_host_dev, K), seq, blob::tmo_word(out_host_dev, K)};
+}
+
 // the per-column update of `self` into `out_items`, reading the parameter blob `d_in`
 template <int K, bool F32>
 int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *other, int iter, double alpha, double *d_in, hipStream_t st,
@@ -56,9 +84,9 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
 // the exchange of one part of a side's columns runs on a stream of its own beside the sampling of the next part)
 template <int K, bool F32>
 int exchange(bpmf_hip_side *self, hipStream_t st, int sub);
-// sum x / sum x x^T of this rank's columns (+ all-reduce), published to `out_host_dev`
+// sum x / sum x x^T of this rank's columns (+ all-reduce), published to the result blob of `p`
 template <int K, bool F32>
-int stats(bpmf_hip_side *self, hipStream_t st, const double *d_in, double *out_host_dev, unsigned *flag, unsigned seq, unsigned *ticket,
+int stats(bpmf_hip_side *self, hipStream_t st, const StatPass &p,
           hipEvent_t ev_done = nullptr);     // ev_done: rides on the dispatch packet of the pass's last kernel (single GPU; no marker packet behind it)
 template <int K, bool F32>
 void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items, const void *other_items, int n, hipStream_t ps, bool beside);

@@ -25,7 +25,7 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
 {
     using namespace bpmf;
     bpmf_hip_ctx *c = self->ctx;
-    SampleArgs a;
+    SampleArgs a = blob_args(self, out_items, d_in, iter, alpha);
     // probit side: the latent scores stand in for the ratings; side with features: the residuals r - m_c . y_r (capi_link.hip)
     const double *vals = self->d_probit_z ? self->d_probit_z : self->d_link_r ? self->d_link_r : self->d_vals;
     a.rowidx = self->d_rowidx; a.vals = vals;
@@ -34,14 +34,10 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     a.wi_col = self->d_wi_col + w0; a.wi_p0 = self->d_wi_p0 + w0; a.wi_len = self->d_wi_len + w0; a.wi_mc = self->d_wi_mc + w0; a.wi_chunk = self->d_wi_chunk + w0;
     a.mc_slot0 = self->d_mc_slot0; a.mc_nchunks = self->d_mc_nch; a.mc_count = self->d_mc_count;
     a.partials = self->d_partials; a.nwork = nwork;
-    a.other_items = other->d_items; a.items = out_items; a.col_from = self->from;
-    a.LambdaF = d_in; a.Lmu = d_in + (size_t)K * K;
-    a.fail = (unsigned long long *)(d_in + (size_t)K * K + K);
-    a.mu = d_in + (size_t)K * K + K + 2; a.prop_lambda = self->d_prop; a.diag_only = c->diag_only;
-    a.mean_rating = self->mean_rating; a.alpha = alpha; a.iter_plus_1 = (uint32_t)(iter + 1); a.ktrue = c->Kt;
+    a.other_items = other->d_items;
     a.ablate = c->ablate; a.stamps = c->d_stamps;
     a.gate_flag = self->cur_gate_flag; a.gate_want = self->cur_gate_want;
-    a.tmo = self->cur_gate_flag ? tmo_word(self->a_h_out_dev, K) : nullptr; a.wait_ticks = wait_ticks();
+    a.tmo = self->cur_gate_flag ? blob::tmo_word(self->a_h_out_dev, K) : nullptr; a.wait_ticks = wait_ticks();
     a.zero_row = c->d_zero;
     a.lf32 = (lf32_words(c) && !self->d_prop) ? reinterpret_cast<const float *>(d_in + c->in_words) : nullptr;
     const bpmf::StatRiders &rr = self->cur_riders;                   // (K = 128 fp32 only)
@@ -69,7 +65,7 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
             LrArgs l;
             l.rowidx = self->d_rowidx; l.vals = vals; l.col = self->d_lr_col; l.p0 = self->d_lr_p0; l.len = self->d_lr_len;
             l.nitems = self->lr_n; l.other_items = other->d_items; l.items = out_items; l.col_from = self->from;
-            l.R0 = d_in + (size_t)K * K + K + 2 + K; l.S0t = l.R0 + (size_t)K * K; l.y0 = l.S0t + (size_t)K * K;
+            l.R0 = d_in + blob::par_R0(K); l.S0t = d_in + blob::par_S0t(K); l.y0 = d_in + blob::par_y0(K);
             l.Lmu = a.Lmu; l.fail = a.fail;
             l.mean_rating = self->mean_rating; l.alpha = alpha; l.sqrt_alpha = std::sqrt(alpha); l.iter_plus_1 = (uint32_t)(iter + 1); l.ktrue = c->Kt;
             // three instantiations (<= 3, <= 6, <= 16 ratings), persistent workgroups of eight waves with R0^-1 in LDS
@@ -197,85 +193,56 @@ int exchange(bpmf_hip_side *self, hipStream_t st, int sub)
     return 0;
 }
 
+// one kernel of the statistics pass or of an evaluation, with a completion event on its dispatch packet when one is given
+// (not BPMF_LAUNCH: that macro consumes next_flags(), which belongs to the next SAMPLER launch, and records into the probe)
+template <typename... P, typename... A>
+inline void launch_ev(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t st, hipEvent_t ev_done, A... args)
+{
+    if (ev_done) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, nullptr, ev_done, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, st, static_cast<P>(args)...);
+}
+
 template <int K, bool F32>
-int stats(bpmf_hip_side *self, hipStream_t st, const double *d_in, double *out_host_dev, unsigned *flag, unsigned seq, unsigned *ticket,
-          hipEvent_t ev_done)
+int stats(bpmf_hip_side *self, hipStream_t st, const StatPass &p, hipEvent_t ev_done)
 {
     using namespace bpmf;
     bpmf_hip_ctx *c = self->ctx;
-    const unsigned long long *failp = (const unsigned long long *)(d_in + (size_t)K * K + K);
+    // single GPU: the sums go straight to the pinned blob.  Sharded: local sums into a device blob, all-reduced (cov is then
+    // formed once from the GLOBAL sums: SURVEY Q19) together with the failed-column word, then published to the host -- on
+    // the side's own stream: its own reduction blob and the second communicator
+    const bool dist = c->comm != nullptr && !self->bounds.empty();
+    const bool own = st != c->stream && c->comm2 && self->a_d_red;
+    if (dist) COMM_ALIVE_OR_FAIL(c, "statistics all-reduce");
+    double *red = own ? self->a_d_red : c->d_red;
+    double *out = dist ? red : p.out;
+    unsigned *flag = dist ? p.ticket + 8 : p.flag;
+    const unsigned seq = dist ? 0u : p.seq;
+    if (dist) ev_done = nullptr;
     if constexpr (K == 128) {                           // one wave per (slice of columns, 16 x 16 tile): fp32 or fp64 factors, fp64 sums
         typedef typename std::conditional<F32, float, double>::type T;
-        const bool dist = c->comm != nullptr && !self->bounds.empty();
-        const bool own = st != c->stream && c->comm2 && self->a_d_red;
-        if (dist) COMM_ALIVE_OR_FAIL(c, "statistics all-reduce");
-        double *red = own ? self->a_d_red : c->d_red;
-        hipLaunchKernelGGL((k_colstats_f32<K, T>), dim3(self->nstat_waves * (K / 16) * (K / 16 + 1) / 2), dim3(64), 0, st, reinterpret_cast<const T *>(self->d_items),
-                           self->from, self->to, self->nstat_waves, self->d_stat_partials);
-        // single GPU: the sums go straight to the pinned blob; sharded: into a device blob, all-reduced, then published
-        if (ev_done && !dist)
-            hipExtLaunchKernelGGL(k_colstats_f32_final<K>, dim3((K * K + K + 255) / 256), dim3(256), 0, st, nullptr, ev_done, 0,
-                                  (const double *)self->d_stat_partials, self->nstat_waves, failp, out_host_dev, ticket, flag, seq);
-        else
-        hipLaunchKernelGGL(k_colstats_f32_final<K>, dim3((K * K + K + 255) / 256), dim3(256), 0, st,
-                           (const double *)self->d_stat_partials, self->nstat_waves, failp, dist ? red : out_host_dev, ticket,
-                           dist ? ticket + 8 : flag, dist ? 0u : seq);
-        if (dist) {
-            NCCL_TRY(rccl()->AllReduce(red, red, (size_t)K * K + K + 1, ncclDouble, ncclSum, own ? c->comm2 : c->comm, st));
-            publish(red, out_host_dev, K * K + K + 1, flag, seq, K * K + K, st);
-        }
-        return 0;
+        hipLaunchKernelGGL((k_colstats_f32<K, T>), dim3(p.nwaves * (K / 16) * (K / 16 + 1) / 2), dim3(64), 0, st, reinterpret_cast<const T *>(p.items),
+                           p.c0, p.c1, p.nwaves, p.partials);
+        launch_ev(k_colstats_f32_final<K>, dim3((blob::res_sums(K) + 255) / 256), dim3(256), st, ev_done,
+                  p.partials, p.nwaves, p.fail_in, out, p.ticket, flag, seq);
+    } else if (self->nstat_wg > 0) {
+        launch_ev(k_colstats_wg<K>, dim3(self->nstat_wg), dim3(256), st, ev_done, reinterpret_cast<const double *>(p.items), p.c0, p.c1,
+                  self->nstat_wg, p.partials, p.fail_in, out, p.ticket, flag, seq, p.tmo, wait_ticks(), nullptr, 0, self->nstat_wg, 1);
     } else {
-    if (!(c->comm != nullptr && !self->bounds.empty())) {
-        if (self->nstat_wg > 0) {
-            if (ev_done)
-                hipExtLaunchKernelGGL(k_colstats_wg<K>, dim3(self->nstat_wg), dim3(256), 0, st, nullptr, ev_done, 0,
-                                      (const double *)self->d_items, self->from, self->to, self->nstat_wg, self->d_stat_partials,
-                                      failp, out_host_dev, ticket, flag, seq, tmo_word(out_host_dev, K), wait_ticks(),
-                                      (const int32_t *)nullptr, 0, self->nstat_wg, 1);
-            else
-            hipLaunchKernelGGL(k_colstats_wg<K>, dim3(self->nstat_wg), dim3(256), 0, st,
-                               (const double *)self->d_items, self->from, self->to, self->nstat_wg, self->d_stat_partials,
-                               failp, out_host_dev, ticket, flag, seq, tmo_word(out_host_dev, K), wait_ticks(),
-                               (const int32_t *)nullptr, 0, self->nstat_wg, 1);
-        } else {
-            if (ev_done)
-                hipExtLaunchKernelGGL(k_colstats<K>, dim3(self->nstat_waves), dim3(64), 0, st, nullptr, ev_done, 0,
-                                      (const double *)self->d_items, self->from, self->to, self->nstat_waves, self->d_stat_partials,
-                                      failp, out_host_dev, ticket, flag, seq, tmo_word(out_host_dev, K), wait_ticks());
-            else
-        hipLaunchKernelGGL(k_colstats<K>, dim3(self->nstat_waves), dim3(64), 0, st,
-                           (const double *)self->d_items, self->from, self->to, self->nstat_waves, self->d_stat_partials,
-                           failp, out_host_dev, ticket, flag, seq, tmo_word(out_host_dev, K), wait_ticks());
-        }
-    } else {
-        // local sums into a device blob, all-reduce them (cov is then formed once from the GLOBAL
-        // sums: SURVEY Q19) together with the failed-column word, publish to the host
-        Rccl *R = rccl();
-        COMM_ALIVE_OR_FAIL(c, "statistics all-reduce");
-        // on the side's own stream: its own reduction blob and the second communicator
-        const bool own = st != c->stream && c->comm2 && self->a_d_red;
-        double *red = own ? self->a_d_red : c->d_red;
-        if (self->nstat_wg > 0)
-            hipLaunchKernelGGL(k_colstats_wg<K>, dim3(self->nstat_wg), dim3(256), 0, st,
-                               (const double *)self->d_items, self->from, self->to, self->nstat_wg, self->d_stat_partials,
-                               failp, red, ticket, ticket + 8, 0u, tmo_word(out_host_dev, K), wait_ticks(),
-                               (const int32_t *)nullptr, 0, self->nstat_wg, 1);
-        else
-        hipLaunchKernelGGL(k_colstats<K>, dim3(self->nstat_waves), dim3(64), 0, st,
-                           (const double *)self->d_items, self->from, self->to, self->nstat_waves, self->d_stat_partials,
-                           failp, red, ticket, ticket + 8, 0u, tmo_word(out_host_dev, K), wait_ticks());
-        NCCL_TRY(R->AllReduce(red, red, (size_t)K * K + K + 1, ncclDouble, ncclSum, own ? c->comm2 : c->comm, st));   // prod | sum | failed-column word
-        publish(red, out_host_dev, K * K + K + 1, flag, seq, K * K + K, st);
+        launch_ev(k_colstats<K>, dim3(p.nwaves), dim3(64), st, ev_done, reinterpret_cast<const double *>(p.items), p.c0, p.c1,
+                  p.nwaves, p.partials, p.fail_in, out, p.ticket, flag, seq, p.tmo, wait_ticks());
+    }
+    if (dist) {
+        NCCL_TRY(rccl()->AllReduce(red, red, (size_t)blob::res_reduced_words(K), ncclDouble, ncclSum, own ? c->comm2 : c->comm, st));
+        publish(red, p.out, blob::res_reduced_words(K), p.flag, p.seq, blob::res_failD(K), st);
     }
     return 0;
-    }
 }
 
 template <int K, bool F32>
 void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items, const void *other_items, int n,
                     hipStream_t ps, bool beside)
 {
+    typedef typename std::conditional<F32, float, double>::type T;
     bpmf_hip_ctx *c = self->ctx;
     unsigned *flag = reinterpret_cast<unsigned *>(t->h_res_dev + 2);
     const bool dist = c->comm && !self->bounds.empty();
@@ -290,56 +257,33 @@ void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items
         t->twin->launched = true;
     }
     // se | se_avg of this rank's test ratings: straight to the host, or -> all-reduce -> host
-    double *red = c->d_red + c->out_words + (t->owner ? 2 : 0);      // 2 spare words behind the sampler's blob (the twin: the next 2)
-    if constexpr (F32) {
-        if (fused_twin) {
-            // round 4: the twin inside the same kernel here too (k_predict<K, 256, float>) -- as two kernels the second one
-            // started when the partner's sampler had filled the chip and ended with it (347 us for 20 us of work), and the
-            // host loop, which collects both sums before it enqueues the next iteration, came 45 us late every iteration
-            bpmf::TwinArgs tw{};
-            bpmf_hip_test *u = t->twin;
-            tw.perm = t->d_twin_perm; tw.pavg = u->d_pavg; tw.pm2 = u->d_pm2; tw.mean = u->side->mean_rating;
-            tw.partial = u->d_partial; tw.out = u->h_res_dev; tw.flag = reinterpret_cast<unsigned *>(u->h_res_dev + 2); tw.seq = ++u->seq;
-            u->pstream = ps; u->launched = true;
-            hipLaunchKernelGGL((bpmf::k_predict<K, 256, float>), dim3((unsigned)t->nblocks), dim3(256), 0, ps,
-                               (const int32_t *)t->d_tcol, (const int32_t *)t->d_trow, (const double *)t->d_tval, t->nnz,
-                               reinterpret_cast<const float *>(self_items), reinterpret_cast<const float *>(other_items), self->from,
-                               self->mean_rating, n, t->d_pavg, t->d_pm2, t->d_partial, t->h_res_dev, t->d_ticket, flag, ++t->seq, tw);
-        } else
-        hipLaunchKernelGGL(bpmf::k_predict_f32<K>, dim3((unsigned)t->nblocks), dim3(256), 0, ps,
-                           (const int32_t *)t->d_tcol, (const int32_t *)t->d_trow, (const double *)t->d_tval, t->nnz,
-                           reinterpret_cast<const float *>(self_items), reinterpret_cast<const float *>(other_items), self->from,
-                           self->mean_rating, n, t->d_pavg, t->d_pm2, t->d_partial, dist ? red : t->h_res_dev, t->d_ticket,
-                           dist ? t->d_ticket + 8 : flag, dist ? 0u : ++t->seq);
-        if (dist) {
-            if (rccl()->AllReduce(red, red, 2, ncclDouble, ncclSum, c->comm, c->stream) != ncclSuccess) return;
-            publish(red, t->h_res_dev, 2, flag, ++t->seq, -1, c->stream);
-        }
-    } else {
+    double *red = c->d_red + (t->owner ? blob::red_twin(K) : blob::red_eval(K));
+    // one kernel, both copies of the test entries.  fp32 too (round 4: k_predict<K, 256, float>) -- as two kernels the second
+    // one started when the partner's sampler had filled the chip and ended with it (347 us for 20 us of work), and the
+    // host loop, which collects both sums before it enqueues the next iteration, came 45 us late every iteration
     bpmf::TwinArgs tw{};
-    if (fused_twin) {                                                 // one kernel, both copies of the test entries
+    if (fused_twin) {
         bpmf_hip_test *u = t->twin;
         tw.perm = t->d_twin_perm; tw.pavg = u->d_pavg; tw.pm2 = u->d_pm2; tw.mean = u->side->mean_rating;
         tw.partial = u->d_partial; tw.out = u->h_res_dev; tw.flag = reinterpret_cast<unsigned *>(u->h_res_dev + 2); tw.seq = ++u->seq;
         u->pstream = ps; u->launched = true;
     }
     const unsigned pseq = dist ? 0u : ++t->seq;
-    if (t->wg == 64)                                                  // single-wave workgroups (small test sets: see k_predict)
-        hipLaunchKernelGGL((bpmf::k_predict<K, 64>), dim3((unsigned)t->nblocks), dim3(64), 0, ps,
-                           (const int32_t *)t->d_tcol, (const int32_t *)t->d_trow, (const double *)t->d_tval, t->nnz,
-                           (const double *)self_items, (const double *)other_items, self->from, self->mean_rating, n,
-                           t->d_pavg, t->d_pm2, t->d_partial, dist ? red : t->h_res_dev, t->d_ticket,
-                           dist ? t->d_ticket + 8 : flag, pseq, tw);
-    else
-    hipLaunchKernelGGL((bpmf::k_predict<K, 256>), dim3((unsigned)t->nblocks), dim3(256), 0, ps,
-                       (const int32_t *)t->d_tcol, (const int32_t *)t->d_trow, (const double *)t->d_tval, t->nnz,
-                       (const double *)self_items, (const double *)other_items, self->from, self->mean_rating, n,
-                       t->d_pavg, t->d_pm2, t->d_partial, dist ? red : t->h_res_dev, t->d_ticket,
-                       dist ? t->d_ticket + 8 : flag, pseq, tw);
+    auto run = [&](auto kernel, unsigned wg, auto... twin) {          // (k_predict takes the twin's arguments, k_predict_f32 has none)
+        launch_ev(kernel, dim3((unsigned)t->nblocks), dim3(wg), ps, nullptr, t->d_tcol, t->d_trow, t->d_tval, t->nnz,
+                  reinterpret_cast<const T *>(self_items), reinterpret_cast<const T *>(other_items), self->from, self->mean_rating, n,
+                  t->d_pavg, t->d_pm2, t->d_partial, dist ? red : t->h_res_dev, t->d_ticket, dist ? t->d_ticket + 8 : flag, pseq, twin...);
+    };
+    if constexpr (F32) {
+        if (fused_twin) run(bpmf::k_predict<K, 256, float>, 256u, tw);
+        else run(bpmf::k_predict_f32<K>, 256u);
+    } else {
+        if (t->wg == 64) run(bpmf::k_predict<K, 64>, 64u, tw);        // single-wave workgroups (small test sets: see k_predict)
+        else run(bpmf::k_predict<K, 256>, 256u, tw);
+    }
     if (dist) {
         if (rccl()->AllReduce(red, red, 2, ncclDouble, ncclSum, c->comm, c->stream) != ncclSuccess) return;
         publish(red, t->h_res_dev, 2, flag, ++t->seq, -1, c->stream);
-    }
     }
     if (beside) (void)hipEventRecord(t->ev_done[t->seq & 1u], ps);
 }
@@ -350,5 +294,5 @@ void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items
     template int bpmf_launch::sampler_into<KK, FF>(bpmf_hip_side *, double *, const bpmf_hip_side *, int, double, double *, hipStream_t, \
                                                hipEvent_t, hipEvent_t);                                                          \
     template int bpmf_launch::exchange<KK, FF>(bpmf_hip_side *, hipStream_t, int);                                                        \
-    template int bpmf_launch::stats<KK, FF>(bpmf_hip_side *, hipStream_t, const double *, double *, unsigned *, unsigned, unsigned *, hipEvent_t); \
+    template int bpmf_launch::stats<KK, FF>(bpmf_hip_side *, hipStream_t, const bpmf_launch::StatPass &, hipEvent_t);                        \
     template void bpmf_launch::predict<KK, FF>(bpmf_hip_test *, const bpmf_hip_side *, const void *, const void *, int, hipStream_t, bool);

@@ -51,15 +51,7 @@ inline int dev_upload(T **dst, const T *src, size_t n)
     return 0;
 }
 
-inline int env_int(const char *name, int dflt);
-inline unsigned long long wait_ticks();
-// how long a host thread spins on a result word before it falls back to a blocking wait on the
-// event behind the kernels (BPMF_HIP_SPIN_MS, default 50; 0 = always block: used by the tests)
-inline double spin_limit_s()
-{
-    static const double v = env_int("BPMF_HIP_SPIN_MS", 50) * 1e-3;
-    return v;
-}
+namespace blob = bpmf::blob;      // the layouts of the parameter / result / reduction blobs (blob.h)
 
 inline int env_int(const char *name, int dflt)
 {
@@ -67,9 +59,28 @@ inline int env_int(const char *name, int dflt)
     return (s && *s) ? atoi(s) : dflt;
 }
 
+// how long a host thread spins on a result word before it falls back to a blocking wait on the
+// event behind the kernels (BPMF_HIP_SPIN_MS, default 50; 0 = always block: used by the tests)
+inline double spin_limit_s()
+{
+    static const double v = env_int("BPMF_HIP_SPIN_MS", 50) * 1e-3;
+    return v;
+}
+// spins until the flag word of a result blob shows `seq`; false: the limit ran out first (the caller then blocks)
+inline bool spin_for_seq(const unsigned *flag, unsigned seq)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0;; ++spins) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return true;
+        if (spin_limit_s() <= 0.0) return false;
+        __builtin_ia32_pause();
+        if ((spins & 0xFFFu) == 0xFFFu && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > spin_limit_s()) return false;
+    }
+}
+
 // bound of every in-kernel wait (gate of the hyper-parameters, staged-parameter word, arrival count of
 // the statistics waves), in ticks of the 100 MHz wall clock the kernels read: BPMF_HIP_WAIT_TIMEOUT_MS,
-// default 20 s.  A wait that runs into it sets the sticky word `tmo_word` of the result blob and the
+// default 20 s.  A wait that runs into it sets the sticky word `tmo` of the result blob (blob.h) and the
 // host reports BPMF_HIP_ENODEV "device wait timed out" instead of using the results.
 inline unsigned long long wait_ticks()
 {
@@ -154,15 +165,13 @@ struct bpmf_hip_ctx {
     int num_cu = 256;
     unsigned ablate = 0;
     unsigned diag_only = 0;              // BPMF_NO_COVARIANCE variant (bpmf_hip_ctx_set_no_covariance)
-    // per-call parameter blob: LambdaF[K*K] | Lmu[K] | fail (u64); pinned host copy + device copy
+    // per-call parameter blob (blob.h): pinned host copy + device copy
     double *h_in = nullptr, *h_in_dev = nullptr, *d_in = nullptr;
-    // result blob in pinned host memory the kernels write directly (zero-copy):
-    // prod[K*K] | sum[K] | - | fail (u64) | se | se_avg | flag (u32)
+    // result blob (blob.h) in pinned host memory the kernels write directly (zero-copy)
     double *h_out = nullptr, *h_out_dev = nullptr;
-    size_t in_words = 0, out_words = 0;
+    size_t in_words = 0, out_words = 0;  // their sizes: blob::par_words / par_words_pf (K = 64 in fp64), blob::res_words
     std::mutex launch_mutex;             // kernel launches come from the caller's thread and from the sides' workers
-    // multi-GPU: RCCL communicator (one rank per process / GPU) and a device staging blob for the
-    // all-reduced sums: prod[K*K] | sum[K] | - | fail (u64) | se | se_avg | count
+    // multi-GPU: RCCL communicator (one rank per process / GPU) and the reduction blob (blob.h) for the all-reduced sums
     ncclComm_t comm = nullptr;
     // second communicator over the same ranks (ncclCommSplit): the all-reduce of a side's column
     // statistics runs on the side's own stream, beside the other side's sampler and exchange, which
@@ -358,11 +367,10 @@ struct bpmf_hip_test {
     double *d_prob_sum = nullptr; int prob_n = 0;        // probit: running sums of Phi(x . y) per entry and the samples added (capi_probit.hip)
 };
 
-// sticky "a device-side wait timed out" word of a result blob (prod | sum | failD | fail | TMO | - | flag)
-inline unsigned long long *tmo_word(double *blob, int K) { return reinterpret_cast<unsigned long long *>(blob + (size_t)K * K + K + 2); }
+// did a device-side wait of the pass that wrote this result blob time out?  (the word is sticky: cleared here)
 inline int check_timeout(double *h_blob, int K, std::string *msg)
 {
-    unsigned long long *w = tmo_word(h_blob, K);
+    unsigned long long *w = blob::tmo_word(h_blob, K);
     const unsigned long long v = __atomic_load_n(w, __ATOMIC_ACQUIRE);
     if (!v) return 0;
     __atomic_store_n(w, 0ull, __ATOMIC_RELEASE);
@@ -405,7 +413,7 @@ inline size_t part_words_rt(int K, bool f32)
 
 
 // doubles behind the parameter blob of a half-iteration that hold LambdaF as fp32 tiles (fp32 path only)
-inline size_t lf32_words(const bpmf_hip_ctx *c) { return c->dtype == BPMF_HIP_F32 ? (size_t)(c->K / 16) * (c->K / 16 + 1) / 2 * 256 / 2 : 0; }
+inline size_t lf32_words(const bpmf_hip_ctx *c) { return c->dtype == BPMF_HIP_F32 ? (size_t)blob::par_lf32_words(c->K) : 0; }
 
 // may this side's samplers write the second copy of the factors?  Every column of the new copy must
 // be produced by this launch or arrive through the exchange that follows it.
