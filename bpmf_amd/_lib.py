@@ -77,6 +77,15 @@ _SIGNATURES = {
     "bpmf_hip_side_link_shift": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "bpmf_hip_link_gemm_tn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_link_gemm_nn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bpmf_hip_side_set_features_sparse": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint]),
+    "bpmf_hip_side_link_cg_set": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
+    "bpmf_hip_side_link_cg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "bpmf_hip_link_spmm_nn": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bpmf_hip_link_spmm_tn": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                        C.c_void_p]),
+    "bpmf_hip_link_cg_solve": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_double,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "bpmf_hip_link_noise_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_aggr_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_aggr_finalize": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),

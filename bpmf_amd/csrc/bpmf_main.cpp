@@ -24,7 +24,8 @@
 // and -o DIR also gets DIR/probit.csv (row,col,label,prob).  Without these flags nothing changes.
 // --row-features FILE / --col-features FILE [--lambda-beta F] (one GPU, no -g): side information.  FILE is a
 // dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
-// -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).
+// -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).  A sparse FILE (.sdm / .sbm /
+// coordinate .mtx) of any width takes the CG draw of DESIGN.md section 14 (bpmf_hip_side_set_features_sparse; --link-tol, --link-max-iter).
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -94,6 +95,10 @@ void usage()
               << "  [--row-features FILE] [--col-features FILE]: side information: a dense matrix (.ddm / .csv) with one row of D features per\n"
               << "              user / movie; the prior mean of its factors becomes mu + beta^T f with a sampled link matrix beta (one GPU, no -g,\n"
               << "              not with --probit, --noise adaptive, --fp32, -m / -l or BPMF_REDUCE=1); -o DIR also gets DIR/U-link.ddm / V-link.ddm\n"
+              << "              A sparse FILE (.sdm, .sbm = all ones, coordinate .mtx; optional .gz) may have any number of feature columns: beta\n"
+              << "              is then drawn by conjugate gradients on the device, F^T F is never formed (a dense FILE keeps 1 .. 1024 columns)\n"
+              << "  [--link-tol F] [--link-max-iter N]: the stopping rule of that CG draw: relative residual (1e-6), most iterations (1000);\n"
+              << "              need a sparse feature file\n"
               << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
               << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
@@ -243,6 +248,11 @@ struct Job {
     double auc = NAN, brier = NAN;
     Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
     double lambda_beta = 5.0;                                        // --lambda-beta F
+    Csc sfeat_u, sfeat_m;                                            // the same from a sparse file: F^T column-compressed = F by rows (D x N)
+    int64_t sfeat_u_d = 0, sfeat_m_d = 0;                            // their D (0: none)
+    double link_tol = 1e-6; int link_max_iter = 1000;                // --link-tol F / --link-max-iter N (sparse features: the CG draw)
+    bool has_feat_u() const { return !feat_u.data.empty() || sfeat_u_d > 0; }
+    bool has_feat_m() const { return !feat_m.data.empty() || sfeat_m_d > 0; }
     std::vector<double> beta_u, beta_m;                              // posterior mean of the link matrices, D x K row-major
     std::string odirname;
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
@@ -291,9 +301,19 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
         check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
     }
-    const bool linked = !J.feat_u.data.empty() || !J.feat_m.data.empty();   // (streams: tag 3 = movies, 4 = users)
-    if (!J.feat_m.data.empty()) check(bpmf_hip_side_set_features(movies, J.feat_m.data.data(), (int)J.feat_m.ncols, 0, J.lambda_beta, 3));
-    if (!J.feat_u.data.empty()) check(bpmf_hip_side_set_features(users, J.feat_u.data.data(), (int)J.feat_u.ncols, 0, J.lambda_beta, 4));
+    const bool linked = J.has_feat_u() || J.has_feat_m();   // (streams: tag 3 = movies, 4 = users)
+    auto set_sparse = [&](bpmf_hip_side *side, const Csc &Fr, int64_t D, unsigned tag) {       // Fr: F by rows (column = item)
+        bool ones = true;
+        for (double v : Fr.vals) if (v != 1.0) { ones = false; break; }
+        static const int32_t none = 0;
+        check(bpmf_hip_side_set_features_sparse(side, (int)D, Fr.colptr.data(), Fr.rowidx.empty() ? &none : Fr.rowidx.data(),
+                                                ones ? nullptr : Fr.vals.data(), J.lambda_beta, tag));
+        check(bpmf_hip_side_link_cg_set(side, J.link_tol, J.link_max_iter));
+    };
+    if (J.sfeat_m_d > 0) set_sparse(movies, J.sfeat_m, J.sfeat_m_d, 3);
+    else if (J.has_feat_m()) check(bpmf_hip_side_set_features(movies, J.feat_m.data.data(), (int)J.feat_m.ncols, 0, J.lambda_beta, 3));
+    if (J.sfeat_u_d > 0) set_sparse(users, J.sfeat_u, J.sfeat_u_d, 4);
+    else if (J.has_feat_u()) check(bpmf_hip_side_set_features(users, J.feat_u.data.data(), (int)J.feat_u.ncols, 0, J.lambda_beta, 4));
     if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
         check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
         check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
@@ -358,8 +378,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
               "with the raw label and are not an error measure" << std::endl;
     if (linked) {
         os << "side information:";
-        if (!J.feat_u.data.empty()) os << " row features D = " << J.feat_u.ncols << ",";
-        if (!J.feat_m.data.empty()) os << " column features D = " << J.feat_m.ncols << ",";
+        if (J.sfeat_u_d > 0) os << " row features sparse D = " << J.sfeat_u_d << " nnz = " << J.sfeat_u.nnz() << ",";
+        else if (J.has_feat_u()) os << " row features D = " << J.feat_u.ncols << ",";
+        if (J.sfeat_m_d > 0) os << " column features sparse D = " << J.sfeat_m_d << " nnz = " << J.sfeat_m.nnz() << ",";
+        else if (J.has_feat_m()) os << " column features D = " << J.feat_m.ncols << ",";
+        if (J.sfeat_u_d > 0 || J.sfeat_m_d > 0) os << " CG tol = " << J.link_tol << " max_iter = " << J.link_max_iter << ",";
         os << " lambda_beta = " << J.lambda_beta << "; blocking loop (bpmf_hip_link_sample)" << std::endl;
     }
     os << "update_freq: " << J.update_freq << std::endl;
@@ -437,6 +460,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         }
     } else
     for (int i = 0; i < nsims; ++i) {
+        static bool cg_warned = false;
         const double start = tick();
         sample(movies, users);                                  // movies.sample(users)
         sample(users, movies);                                  // users.sample(movies)
@@ -457,9 +481,19 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
         if (J.topn > 0 && iter >= burnin) { check(bpmf_hip_side_samples_add(users)); check(bpmf_hip_side_samples_add(movies)); }
         if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
+        if (!cg_warned && (J.sfeat_u_d > 0 || J.sfeat_m_d > 0)) {       // CG at max_iter with a column still active: said once
+            int hit_u = 0, hit_m = 0;
+            if (J.sfeat_u_d > 0) check(bpmf_hip_side_link_cg_stats(users, nullptr, nullptr, nullptr, &hit_u));
+            if (J.sfeat_m_d > 0) check(bpmf_hip_side_link_cg_stats(movies, nullptr, nullptr, nullptr, &hit_m));
+            if (hit_u || hit_m) {
+                std::cerr << "warning: the CG draw of the link matrix reached --link-max-iter " << J.link_max_iter << " in iteration " << iter
+                          << " before its residual fell below --link-tol " << J.link_tol << std::endl;
+                cg_warned = true;
+            }
+        }
         if (linked && iter >= burnin) {
-            if (!J.feat_u.data.empty()) check(bpmf_hip_side_link_add(users));
-            if (!J.feat_m.data.empty()) check(bpmf_hip_side_link_add(movies));
+            if (J.has_feat_u()) check(bpmf_hip_side_link_add(users));
+            if (J.has_feat_m()) check(bpmf_hip_side_link_add(movies));
         }
         // (-v: the replicas of both factor matrices are complete on every rank -- the all-gather form of the exchange;
         // users.bcast() / movies.bcast() of c++/bpmf.cpp:202-203 have nothing left to do)
@@ -495,8 +529,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
         }
     }
     if (linked && nsims > burnin) {                                  // one rank (main refuses -g)
-        if (!J.feat_u.data.empty()) { J.beta_u.resize((size_t)J.feat_u.ncols * K); check(bpmf_hip_side_link_mean(users, J.beta_u.data(), nullptr)); }
-        if (!J.feat_m.data.empty()) { J.beta_m.resize((size_t)J.feat_m.ncols * K); check(bpmf_hip_side_link_mean(movies, J.beta_m.data(), nullptr)); }
+        if (J.has_feat_u()) { J.beta_u.resize((size_t)(J.sfeat_u_d > 0 ? J.sfeat_u_d : J.feat_u.ncols) * K); check(bpmf_hip_side_link_mean(users, J.beta_u.data(), nullptr)); }
+        if (J.has_feat_m()) { J.beta_m.resize((size_t)(J.sfeat_m_d > 0 ? J.sfeat_m_d : J.feat_m.ncols) * K); check(bpmf_hip_side_link_mean(movies, J.beta_m.data(), nullptr)); }
     }
     if (probit_eval && nsims > burnin) {                             // one rank (main refuses -g)
         J.prob.resize((size_t)J.T.nnz());
@@ -547,8 +581,9 @@ int main(int argc, char *argv[])
                                               {"probit", no_argument, nullptr, 1006}, {"probit-threshold", required_argument, nullptr, 1007},
                                               {"row-features", required_argument, nullptr, 1008}, {"col-features", required_argument, nullptr, 1009},
                                               {"lambda-beta", required_argument, nullptr, 1010},
+                                              {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -564,6 +599,8 @@ int main(int argc, char *argv[])
         case 1008: row_features = optarg; break;
         case 1009: col_features = optarg; break;
         case 1010: lambda_beta = optarg; break;
+        case 1011: link_tol = optarg; break;
+        case 1012: link_max_iter = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -636,6 +673,26 @@ int main(int argc, char *argv[])
     // --row-features / --col-features / --lambda-beta: checked before anything touches a GPU
     const bool linked = !row_features.empty() || !col_features.empty();
     if (!lambda_beta.empty() && !linked) die("--lambda-beta needs --row-features or --col-features");
+    auto sparse_file = [](const std::string &name) {
+        if (name.empty()) return false;
+        const bpmf::io::FileType ft = bpmf::io::file_type(name);
+        if (ft.kind == bpmf::io::Kind::sdm || ft.kind == bpmf::io::Kind::sbm) return true;
+        return ft.kind == bpmf::io::Kind::mtx && bpmf::io::mtx_is_coordinate(name);
+    };
+    const bool sparse_u = sparse_file(row_features), sparse_m = sparse_file(col_features);
+    if ((!link_tol.empty() || !link_max_iter.empty()) && !sparse_u && !sparse_m)
+        die("--link-tol / --link-max-iter need a sparse feature file (--row-features / --col-features FILE.sdm, .sbm or a coordinate .mtx)");
+    if (!link_tol.empty()) {
+        char *e = nullptr;
+        J.link_tol = strtod(link_tol.c_str(), &e);
+        if (e == link_tol.c_str() || *e != '\0' || !(J.link_tol > 0.0) || !(J.link_tol < 1.0)) die("--link-tol expects a number 0 < F < 1, not '" + link_tol + "'");
+    }
+    if (!link_max_iter.empty()) {
+        char *e = nullptr;
+        const long v = strtol(link_max_iter.c_str(), &e, 10);
+        if (e == link_max_iter.c_str() || *e != '\0' || v < 1 || v > 1000000) die("--link-max-iter expects an integer 1 .. 1000000, not '" + link_max_iter + "'");
+        J.link_max_iter = (int)v;
+    }
     if (linked) {
         if (!lambda_beta.empty()) {
             char *e = nullptr;
@@ -684,8 +741,18 @@ int main(int argc, char *argv[])
         if (F.nrows != n) die(std::string("--") + what + ": " + name + " has " + std::to_string(F.nrows) + " rows, the side has " + std::to_string(n));
         if (F.ncols < 1 || F.ncols > 1024) die(std::string("--") + what + ": expects 1 .. 1024 feature columns, not " + std::to_string(F.ncols));
     };
-    read_features(row_features, nusers, "row-features", J.feat_u);
-    read_features(col_features, nmovies, "col-features", J.feat_m);
+    auto read_sparse_features = [&](const std::string &name, int64_t n, const char *what, Csc &Fr, int64_t &D) {
+        Csc F;                                                  // N x D, column-compressed
+        try { F = bpmf::io::read_sparse(name); } catch (const std::exception &e) { die(e.what()); }
+        if (F.nrows != n) die(std::string("--") + what + ": " + name + " has " + std::to_string(F.nrows) + " rows, the side has " + std::to_string(n));
+        if (F.ncols < 1 || F.ncols > 0x7FFFFFFF) die(std::string("--") + what + ": expects at least one feature column, not " + std::to_string(F.ncols));
+        D = F.ncols;
+        Fr = bpmf::io::transpose(F);                            // column i of F^T = row i of F, its feature indices sorted
+    };
+    if (sparse_u) read_sparse_features(row_features, nusers, "row-features", J.sfeat_u, J.sfeat_u_d);
+    else read_features(row_features, nusers, "row-features", J.feat_u);
+    if (sparse_m) read_sparse_features(col_features, nmovies, "col-features", J.sfeat_m, J.sfeat_m_d);
+    else read_features(col_features, nmovies, "col-features", J.feat_m);
 
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {

@@ -9,6 +9,7 @@
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
+//   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>

@@ -3,6 +3,7 @@
 // residual ratings r - m_c . y_r.
 // (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
 #include "capi_internal.h"
+#include "link_sparse.h"
 
 using namespace bpmf_capi;
 
@@ -80,6 +81,7 @@ int nn_product(const double *A, int64_t lda, const double *B, int64_t ldb, int64
 int offsets_update(bpmf_hip_side *s)
 {
     const bpmf_hip_ctx *c = s->ctx;
+    if (s->link_sp) return link_sparse_offsets(s);
     return nn_product(s->d_link_f, s->link_d, s->d_link_beta, c->K, s->ncols, s->link_d, c->Kt, s->d_link_m, c->K, c->K, c->stream);
 }
 
@@ -124,6 +126,7 @@ namespace bpmf_capi {
 
 void link_free(bpmf_hip_side *s)
 {
+    link_sparse_free(s);
     free_dev(s->d_link_f); free_dev(s->d_link_w); free_dev(s->d_link_pe); free_dev(s->d_link_beta); free_dev(s->d_link_m);
     free_dev(s->d_link_r); free_dev(s->d_link_part); free_dev(s->d_link_mu); free_dev(s->d_link_btb); free_dev(s->d_link_norm);
     free_dev(s->d_link_beta_sum); free_dev(s->d_link_colptr);
@@ -243,7 +246,11 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
                               LF.data());
     if (rc) return rc;
 
-    if (link) {
+    if (link && self->link_sp) {
+        // 2'. beta by CG on a noise-injected right-hand side, 3'. M = F beta by the sparse product (capi_link_sparse.hip); 4. residuals
+        if ((rc = link_sparse_draw(self, mu.data(), LU.data(), iter))) return rc;
+        if ((rc = residual_enqueue(self, other, self->d_link_r))) return rc;
+    } else if (link) {
         // 2. beta = G^-1 P + L_G^-T E = [G^-1 | L_G^-T] [P ; E],  P = F^T (U - 1 mu^T),  E = Z R^-T with Lambda = R^T R
         std::vector<double> pad((size_t)K, 0.0);
         memcpy(pad.data(), mu.data(), sizeof(double) * Kt);

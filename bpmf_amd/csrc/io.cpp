@@ -308,6 +308,19 @@ void resize(Csc &m, int64_t nrows, int64_t ncols)
     m.ncols = ncols;
 }
 
+bool mtx_is_coordinate(const std::string &path)
+{
+    try {
+        const FileType t = file_type(path);
+        if (t.kind != Kind::mtx) return false;
+        const std::string bytes = slurp(path, t.gz);
+        Lines in{bytes};
+        return mm_header(in).coordinate;
+    } catch (const std::exception &) {
+        return false;                                                  // (unreadable: the reader that opens it next says why)
+    }
+}
+
 Csc read_sparse(const std::string &path)
 {
     const FileType t = file_type(path);

@@ -34,6 +34,8 @@ Csc transpose(const Csc &m);
 // grows the shape without touching the entries (conservativeResize, c++/sample.cpp:119-122)
 void resize(Csc &m, int64_t nrows, int64_t ncols);
 
+// a Matrix Market file in coordinate (sparse) format; false for an array file, another kind or an unreadable file
+bool mtx_is_coordinate(const std::string &path);
 Csc read_sparse(const std::string &path);
 Dense read_dense(const std::string &path);
 void write_sparse(const std::string &path, const Csc &m);

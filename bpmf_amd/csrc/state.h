@@ -228,6 +228,9 @@ struct bpmf_hip_side {
     double *d_link_f = nullptr, *d_link_w = nullptr, *d_link_pe = nullptr, *d_link_beta = nullptr, *d_link_m = nullptr, *d_link_r = nullptr;
     double *d_link_part = nullptr, *d_link_mu = nullptr, *d_link_btb = nullptr, *d_link_norm = nullptr, *d_link_beta_sum = nullptr;
     int64_t *d_link_colptr = nullptr; int link_nsum = 0;
+    // sparse features (capi_link_sparse.hip): F compressed both ways and the work arrays of the CG draw of beta;
+    // d_link_f is then a one-word placeholder, d_link_w / d_link_pe stay NULL
+    struct bpmf_link_sparse *link_sp = nullptr;
     bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;

@@ -304,9 +304,19 @@ class HipEngine:
 
     # -- side information ---------------------------------------------------------
     def set_features(self, side, F, lambda_beta=5.0, tag=3):
-        """Gives `side` the dense feature matrix F [ncols, D] (one row per column of the side), a link matrix beta (D x K, 0) and
-        the fixed lambda_beta.  tag >= 1 names the random stream of the link draw: different per side.
-        From then on the side -- and its partner -- are stepped with link_sample."""
+        """Gives `side` the feature matrix F [ncols, D] (one row per column of the side), a link matrix beta (D x K, 0) and the
+        fixed lambda_beta.  tag >= 1 names the random stream of the link draw: different per side.  From then on the side -- and
+        its partner -- are stepped with link_sample.  A dense ndarray (D <= 1024) takes the dense path of DESIGN.md section 13; a
+        scipy.sparse matrix (any D, tag < 0x10000) is converted to canonical CSR and takes the CG path of section 14.  Nothing is
+        converted from dense to sparse or back."""
+        if _is_sparse(F):
+            if F.ndim != 2 or F.shape[0] != side.ncols:
+                raise ValueError("set_features: F must be [%d, D], one row per column of the side" % side.ncols)
+            rowptr, colidx, vals = csr_arrays(F)
+            _lib.check(self.lib.bpmf_hip_side_set_features_sparse(side.handle, int(F.shape[1]), _ptr(rowptr), _ptr(colidx), _ptr(vals),
+                                                                  float(lambda_beta), int(tag)))
+            side.link_d = int(F.shape[1]); side.link_sparse = True
+            return
         F = np.asarray(F, np.float64)
         if F.ndim != 2 or F.shape[0] != side.ncols:
             raise ValueError("set_features: F must be [%d, D], one row per column of the side" % side.ncols)
@@ -318,6 +328,16 @@ class HipEngine:
     def link_sample(self, side, other, alpha):
         """The blocking half-iteration of a model with side information (both sides go through it; include/bpmf_hip.h)."""
         _lib.check(self.lib.bpmf_hip_link_sample(side.handle, other.handle, float(alpha)))
+
+    def link_cg_set(self, side, tol=1e-6, max_iter=1000):
+        """The stopping rule of the CG draw of a side with sparse features: relative residual tol, at most max_iter iterations."""
+        _lib.check(self.lib.bpmf_hip_side_link_cg_set(side.handle, float(tol), int(max_iter)))
+
+    def link_cg_stats(self, side):
+        """dict(iters_last, iters_total, relres_max_last, hit_max_iter) of the CG draws of a side with sparse features."""
+        it, tot, rel, hit = C.c_int(), C.c_int64(), C.c_double(), C.c_int()
+        _lib.check(self.lib.bpmf_hip_side_link_cg_stats(side.handle, C.byref(it), C.byref(tot), C.byref(rel), C.byref(hit)))
+        return dict(iters_last=it.value, iters_total=tot.value, relres_max_last=rel.value, hit_max_iter=bool(hit.value))
 
     def link_get(self, side):
         """(beta [D, K], offsets M = F beta [ncols, K]) of a side with features."""
@@ -536,4 +556,68 @@ def link_gemm_nn(A, B, device=0):
     N, D = A.shape
     out = np.empty((N, B.shape[1]))
     _lib.check(_lib.load_library().bpmf_hip_link_gemm_nn(int(device), _ptr(A), N, D, _ptr(B), B.shape[1], _ptr(out)))
+    return out
+
+
+def _is_sparse(F):
+    """a scipy.sparse matrix or array (without importing scipy for a dense caller)"""
+    return hasattr(F, "tocsr") and hasattr(F, "nnz") and not isinstance(F, np.ndarray)
+
+
+def csr_arrays(F):
+    """(rowptr int64, colidx int32, vals float64 or None) of a scipy.sparse matrix in canonical CSR: duplicates summed, indices
+    sorted within a row.  Stored zeros are kept (they are part of the pattern).  vals is None when every stored value is 1."""
+    F = F.tocsr().astype(np.float64)
+    if not F.has_canonical_format:
+        F = F.copy()
+        F.sum_duplicates()
+    rowptr = np.ascontiguousarray(F.indptr, np.int64)
+    colidx = np.ascontiguousarray(F.indices, np.int32)
+    vals = np.ascontiguousarray(F.data, np.float64)
+    if len(colidx) == 0:
+        colidx = np.zeros(1, np.int32)
+    return rowptr, colidx, (None if len(vals) and np.all(vals == 1.0) else (vals if len(vals) else None))
+
+
+def link_spmm_nn(F, V, device=0):
+    """F V on the device through k_sp_rows (F: scipy.sparse N x D, V: D x n, n <= 128); tests and tools."""
+    V = np.ascontiguousarray(V, np.float64)
+    rowptr, colidx, vals = csr_arrays(F)
+    N, D = F.shape
+    out = np.empty((N, V.shape[1]))
+    _lib.check(_lib.load_library().bpmf_hip_link_spmm_nn(int(device), N, D, _ptr(rowptr), _ptr(colidx), _ptr(vals), _ptr(V), V.shape[1], _ptr(out)))
+    return out
+
+
+def link_spmm_tn(F, X, lam=0.0, P=None, device=0):
+    """F^T X (+ lam P) on the device (F: scipy.sparse N x D, X: N x n, P: D x n, n <= 128); tests and tools."""
+    X = np.ascontiguousarray(X, np.float64)
+    Pc = np.ascontiguousarray(P, np.float64) if P is not None else None
+    rowptr, colidx, vals = csr_arrays(F)
+    N, D = F.shape
+    out = np.empty((D, X.shape[1]))
+    _lib.check(_lib.load_library().bpmf_hip_link_spmm_tn(int(device), N, D, _ptr(rowptr), _ptr(colidx), _ptr(vals), _ptr(X), X.shape[1], float(lam),
+                                                         _ptr(Pc), _ptr(out)))
+    return out
+
+
+def link_cg_solve(F, lam, RHS, tol=1e-6, max_iter=1000, device=0):
+    """(X, iters per column, hit_max_iter): (F^T F + lam I) X = RHS by the device's lockstep CG (RHS: D x n, n <= 128)."""
+    RHS = np.ascontiguousarray(RHS, np.float64)
+    rowptr, colidx, vals = csr_arrays(F)
+    N, D = F.shape
+    n = RHS.shape[1]
+    X = np.empty((D, n)); iters = np.zeros(n, np.int32); hit = C.c_int()
+    _lib.check(_lib.load_library().bpmf_hip_link_cg_solve(int(device), N, D, _ptr(rowptr), _ptr(colidx), _ptr(vals), float(lam), _ptr(RHS), n,
+                                                          float(tol), int(max_iter), _ptr(X), _ptr(iters), C.byref(hit)))
+    return X, iters, bool(hit.value)
+
+
+def link_noise_rows(nrows, K, it, key_word, Rinv=None, device=0):
+    """Rows 0 .. nrows - 1 of the device's noise matrix of iteration `it` and key word `key_word` [nrows, K], times R^-T when Rinv
+    (K x K, upper triangular) is given."""
+    R = np.ascontiguousarray(Rinv, np.float64) if Rinv is not None else None
+    out = np.empty((int(nrows), int(K)))
+    _lib.check(_lib.load_library().bpmf_hip_link_noise_rows(int(device), int(nrows), int(K), int(it) & 0xFFFFFFFF, int(key_word) & 0xFFFFFFFF,
+                                                            _ptr(R), _ptr(out)))
     return out

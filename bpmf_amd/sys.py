@@ -185,7 +185,7 @@ class Sys:
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
-          row_features=None, col_features=None, lambda_beta=5.0):
+          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -221,7 +221,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     (movie's) factors becomes mu + beta^T f with a link matrix beta (D x K) that is sampled too, its rows N(0, (lambda_beta
     Lambda)^-1) a priori; lambda_beta is fixed (5 is a default, not a tuned number).  Either or both.  The loop is then the plain
     one over engine.link_sample (blocking, both sides); pipelined=True, probit=True and noise="adaptive" are refused with
-    features.  res["beta_rows"] / res["beta_cols"]: the mean of beta over the post-burn-in samples (None without such samples)."""
+    features.  res["beta_rows"] / res["beta_cols"]: the mean of beta over the post-burn-in samples (None without such samples).
+
+    A scipy.sparse feature matrix (any D) takes the CG path of DESIGN.md section 14: beta is drawn by conjugate gradients on the
+    device to the relative residual link_tol in at most link_max_iter iterations.  res["link_cg_iters"]: per iteration the CG
+    iterations of (movies, users), None for a side without sparse features; res["link_cg_hit_max_iter"]: whether any draw ran
+    into link_max_iter.  A dense ndarray keeps the dense path; nothing is converted either way."""
     linked = row_features is not None or col_features is not None
     if linked:
         if pipelined:
@@ -232,6 +237,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             raise ValueError("noise='adaptive' does not go together with row_features / col_features")
         if not (float(lambda_beta) > 0 and math.isfinite(float(lambda_beta))):
             raise ValueError("lambda_beta must be positive and finite")
+        if not (0.0 < float(link_tol) < 1.0) or int(link_max_iter) < 1:
+            raise ValueError("link_tol must lie in (0, 1) and link_max_iter must be >= 1")
     if topn is not None and nsims - burnin < 1:
         raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
     if noise not in ("fixed", "adaptive"):
@@ -262,12 +269,19 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         if row_features is not None:
             engine.set_features(users.side, row_features, lambda_beta, 4)
         movies.linked = users.linked = True
+        sparse_sides = [sd for sd, F in ((movies, col_features), (users, row_features)) if F is not None and _engine._is_sparse(F)]
+        for sd in sparse_sides:
+            engine.link_cg_set(sd.side, link_tol, link_max_iter)
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
     if topn is not None:
         engine.samples_reserve(movies.side, nsims - burnin)
         engine.samples_reserve(users.side, nsims - burnin)
+
+    if linked and sparse_sides:
+        res["link_cg_iters"] = []
+        res["link_cg_hit_max_iter"] = False
 
     def keep(i):                                     # where the -o aggregation sits (bpmf_main.cpp)
         if topn is not None and i >= burnin:
@@ -280,6 +294,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
                 engine.link_add(movies.side)
             if row_features is not None:
                 engine.link_add(users.side)
+        if linked and sparse_sides:
+            st = [engine.link_cg_stats(sd.side) if sd in sparse_sides else None for sd in (movies, users)]
+            res["link_cg_iters"].append(tuple(None if t is None else t["iters_last"] for t in st))
+            res["link_cg_hit_max_iter"] = res["link_cg_hit_max_iter"] or any(t is not None and t["hit_max_iter"] for t in st)
 
     if adaptive:
         res["alpha"], res["train_rmse"] = [], []

@@ -370,6 +370,43 @@ BPMF_API int bpmf_hip_side_link_shift(bpmf_hip_side *side, double *norm);
 BPMF_API int bpmf_hip_link_gemm_tn(int device, const double *A, int64_t N, int D, const double *B, int n, const double *bvec, double *C);
 BPMF_API int bpmf_hip_link_gemm_nn(int device, const double *A, int64_t N, int D, const double *B, int n, double *C);
 
+/* ---- side information with a SPARSE feature matrix ------------
+ * F (N x D) is given in canonical CSR: rowptr (N + 1, rowptr[0] = 0), colidx (strictly increasing within a row, inside [0, D)),
+ * vals (fp64, or NULL: every stored entry is 1, a fingerprint).  Any D >= 1: G = F^T F + lambda_beta I is never formed.  The side
+ * keeps F compressed by rows and by columns on the device, and step 2 of bpmf_hip_link_sample becomes
+ *   2'. X = U - 1 mu^T + Z1 R^-T,  RHS = F^T X + sqrt(lambda_beta) Z2 R^-T,  (F^T F + lambda_beta I) beta = RHS by conjugate
+ *       gradients, the K columns in lockstep from beta = 0 (the same conditional of beta as the dense path draws)
+ * with M = F beta by the sparse product.  Row i of Z1 (Z2) is the first K normals of the polar method on the blocks
+ * Philox4x32-10(counter = {i low, i high, iter, attempt}, key = {42, tag + 0x10000 (tag + 0x20000)}), generated on the device.
+ * Column k of the solve is active in an iteration iff |r_k|^2 > tol^2 |rhs_k|^2 at its start; only active columns are updated;
+ * the solve ends at the first iteration without an active column or at max_iter (defaults: tol 1e-6, max_iter 1000).  Reaching
+ * max_iter is not an error: bpmf_hip_side_link_cg_stats reports it.
+ * Everything else -- bpmf_hip_side_link_get / _set / _add / _mean / _residual / _shift, bpmf_hip_sys_state, prediction,
+ * aggregation, top-N -- works as for a side with dense features.
+ * BPMF_HIP_EINVAL: the refusals of bpmf_hip_side_set_features except the bound on D, and: rowptr not starting at 0 or decreasing,
+ * a column index outside [0, D), unsorted or duplicate column indices within a row, a non-finite value, tag >= 0x10000. */
+BPMF_API int bpmf_hip_side_set_features_sparse(bpmf_hip_side *side, int D, const int64_t *rowptr, const int32_t *colidx, const double *vals,
+                                               double lambda_beta, unsigned tag);
+/* tol in (0, 1), max_iter >= 1, for the following draws.  BPMF_HIP_EINVAL on a side without sparse features. */
+BPMF_API int bpmf_hip_side_link_cg_set(bpmf_hip_side *side, double tol, int max_iter);
+/* Of the last draw: the iterations of the column that needed most, the largest |r_k| / |rhs_k| (recursion residual), whether a
+ * column was still active at max_iter; iters_total adds iters_last over all draws.  Any pointer may be NULL. */
+BPMF_API int bpmf_hip_side_link_cg_stats(bpmf_hip_side *side, int *iters_last, int64_t *iters_total, double *relres_max_last, int *hit_max_iter);
+/* The pieces on host arrays (row-major fp64; F in CSR as above), for tests and tools; no handle needed.
+ *   spmm_nn: Y (N x n) = F V, V: D x n            spmm_tn: C (D x n) = F^T X (+ lambda P), X: N x n, P: D x n or NULL
+ *   cg_solve: (F^T F + lambda I) X = RHS (D x n) as above; iters: n ints (per column) or NULL
+ *   noise_rows: out (nrows x K) = rows 0 .. nrows - 1 of the noise matrix of iteration `it` and key word `key_word`, times R^-T
+ *               (Rinv: K x K row-major upper triangular) or the normals themselves (Rinv = NULL)
+ * n, K <= 128.  All are bit-identical from call to call and whatever the grid (BPMF_LINK_WG_CHUNKS) or the host's look-ahead
+ * (BPMF_LINK_CG_CHECK: CG iterations enqueued between two looks at the convergence word). */
+BPMF_API int bpmf_hip_link_spmm_nn(int device, int64_t N, int D, const int64_t *rowptr, const int32_t *colidx, const double *vals, const double *V,
+                                   int n, double *Y);
+BPMF_API int bpmf_hip_link_spmm_tn(int device, int64_t N, int D, const int64_t *rowptr, const int32_t *colidx, const double *vals, const double *X,
+                                   int n, double lambda, const double *P, double *C);
+BPMF_API int bpmf_hip_link_cg_solve(int device, int64_t N, int D, const int64_t *rowptr, const int32_t *colidx, const double *vals, double lambda,
+                                    const double *RHS, int n, double tol, int max_iter, double *X, int *iters, int *hit_max_iter);
+BPMF_API int bpmf_hip_link_noise_rows(int device, int64_t nrows, int K, uint32_t it, uint32_t key_word, const double *Rinv, double *out);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
