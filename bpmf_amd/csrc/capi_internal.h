@@ -10,6 +10,7 @@
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
+// The device memory of the last five (probit, features, sample ring, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -35,6 +36,11 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr);
 void free_schedule(bpmf_hip_side *s);
 void pad_square(int Kt, int K, const double *src, double *dst, double diag);
 void unpad_square(int Kt, int K, const double *src, double *dst);
+inline bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
+// refuses with "<who>: needs the side (both sides) whole on one GPU<tail>" when the context has a communicator or a side is a shard
+int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_side *a, const bpmf_hip_side *b = nullptr,
+                       const char *tail = ", on a context without a communicator");
+int ensure_colptr(bpmf_hip_side *s);                                   // s->d_colptr, uploaded on first use (the device is set)
 
 // the stateful pipeline (capi_sample.hip)
 int settle_async(bpmf_hip_side *s);                                    // waits until the worker is done with `s`; returns its deferred error
@@ -43,10 +49,10 @@ int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statis
 
 // probit likelihood (capi_probit.hip)
 int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a probit side
-void probit_free(bpmf_hip_side *s);
 
-// side information (capi_link.hip)
-void link_free(bpmf_hip_side *s);
+// side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
+// then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.
+int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, unsigned tag, size_t part_words, std::unique_ptr<bpmf_link> *out);
 int ensure_state(bpmf_hip_side *s);                                    // (capi_sample.hip) the Sys state of a side: cov, hyper-parameters
 
 // evaluation (capi_eval.hip)

@@ -7,8 +7,6 @@
 
 using namespace bpmf_capi;
 
-static bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
-
 namespace {
 
 constexpr int kMaxD = 1024;
@@ -51,9 +49,6 @@ bool factor_and_invert(int D, const std::vector<double> &G, std::vector<double> 
     return true;
 }
 
-template <typename T>
-void free_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
-
 // C = A^T (B - 1 bvec^T) for any n: column tiles of 128 through the one kernel (B = A, n = D for F^T F)
 int tn_product(const double *A, int64_t lda, const double *B, int64_t ldb, const double *bvec, int64_t N, int D, int n, double *C, int64_t ldc,
                double *part, hipStream_t st)
@@ -81,16 +76,17 @@ int nn_product(const double *A, int64_t lda, const double *B, int64_t ldb, int64
 int offsets_update(bpmf_hip_side *s)
 {
     const bpmf_hip_ctx *c = s->ctx;
-    if (s->link_sp) return link_sparse_offsets(s);
-    return nn_product(s->d_link_f, s->link_d, s->d_link_beta, c->K, s->ncols, s->link_d, c->Kt, s->d_link_m, c->K, c->K, c->stream);
+    const bpmf_link *L = s->link.get();
+    if (L->sparse) return link_sparse_offsets(s);
+    return nn_product(L->dense->F.get(), L->D, L->beta.get(), c->K, s->ncols, L->D, c->Kt, L->m.get(), c->K, c->K, c->stream);
 }
 
 int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
 {
     const bpmf_hip_ctx *c = s->ctx;
     bpmf_launch::LinkResidualLaunch p{};
-    p.colptr = s->d_link_colptr; p.ncols = s->ncols; p.rowidx = s->d_rowidx; p.vals = s->d_vals; p.nnz = s->nnz;
-    p.offs = s->d_link_m; p.other = other->d_items; p.K = c->K; p.kt = c->Kt; p.out = out;
+    p.colptr = s->d_colptr.get(); p.ncols = s->ncols; p.rowidx = s->d_rowidx; p.vals = s->d_vals; p.nnz = s->nnz;
+    p.offs = s->link->m.get(); p.other = other->d_items; p.K = c->K; p.kt = c->Kt; p.out = out;
     if (bpmf_launch::link_residual(p, c->stream)) return fail(BPMF_HIP_EINVAL, "link: unsupported K " + std::to_string(c->K));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -100,12 +96,12 @@ int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
 int shift_and_norm(bpmf_hip_side *s, double *items, const double *offs, int64_t total, double *norm)
 {
     bpmf_hip_ctx *c = s->ctx;
-    bpmf_launch::link_shift(items, offs, total, s->d_link_norm, c->stream);
+    bpmf_launch::link_shift(items, offs, total, s->link->norm.get(), c->stream);
     HIP_TRY(hipGetLastError());
     const int nb = bpmf_launch::link_shift_blocks(total);
     std::vector<double> part((size_t)std::max(nb, 1), 0.0);
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    if (nb > 0) HIP_TRY(hipMemcpy(part.data(), s->d_link_norm, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
+    if (nb > 0) HIP_TRY(hipMemcpy(part.data(), s->link->norm.get(), (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
     double nn = 0.0;
     for (int b = 0; b < nb; ++b) nn += part[(size_t)b];
     if (norm) *norm = nn;
@@ -124,13 +120,34 @@ int check_pair(const char *who, const bpmf_hip_side *self, const bpmf_hip_side *
 
 namespace bpmf_capi {
 
-void link_free(bpmf_hip_side *s)
+int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, unsigned tag, size_t part_words, std::unique_ptr<bpmf_link> *out)
 {
-    link_sparse_free(s);
-    free_dev(s->d_link_f); free_dev(s->d_link_w); free_dev(s->d_link_pe); free_dev(s->d_link_beta); free_dev(s->d_link_m);
-    free_dev(s->d_link_r); free_dev(s->d_link_part); free_dev(s->d_link_mu); free_dev(s->d_link_btb); free_dev(s->d_link_norm);
-    free_dev(s->d_link_beta_sum); free_dev(s->d_link_colptr);
-    s->link_d = 0; s->link_nsum = 0;
+    const std::string w(who);
+    bpmf_hip_ctx *c = s->ctx;
+    if (s->link) return fail(BPMF_HIP_EINVAL, w + ": the side has features already");
+    if (!(lambda > 0.0) || !std::isfinite(lambda)) return fail(BPMF_HIP_EINVAL, w + ": lambda_beta must be positive and finite");
+    if (tag == 0) return fail(BPMF_HIP_EINVAL, w + ": tag must be >= 1 (key word 0 belongs to the samplers' streams)");
+    if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, w + ": not on an fp32 context");
+    int rc = require_single_gpu(who, c, s);
+    if (rc) return rc;
+    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, w + ": not together with the BPMF_REDUCE formulation");
+    if (s->probit) return fail(BPMF_HIP_EINVAL, w + ": not on a probit side");
+    if (s->d_prop) return fail(BPMF_HIP_EINVAL, w + ": not together with propagated priors");
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = settle_async(s))) return rc;
+    const size_t N = (size_t)s->ncols, ld = (size_t)c->K, Kt = (size_t)c->Kt;
+    const int nblk = std::max(bpmf_launch::link_shift_blocks((int64_t)(N * ld)), bpmf_launch::link_shift_blocks((int64_t)D * c->K));
+    auto L = std::make_unique<bpmf_link>();
+    L->D = D; L->lambda = lambda; L->tag = (uint32_t)tag;
+    if ((rc = L->beta.alloc((size_t)D * ld)) || (rc = L->beta_sum.alloc((size_t)D * ld)) || (rc = L->m.alloc(N * ld)) ||
+        (rc = L->r.alloc((size_t)s->nnz)) || (rc = L->part.alloc(part_words)) || (rc = L->mu.alloc(ld)) || (rc = L->btb.alloc(Kt * Kt)) ||
+        (rc = L->norm.alloc((size_t)nblk)) || (rc = ensure_colptr(s)))
+        return rc;
+    if ((rc = L->beta.zero_async(c->stream)) || (rc = L->beta_sum.zero_async(c->stream)) || (rc = L->m.zero_async(c->stream))) return rc;
+    // (the residuals of M = 0 are the ratings: a sampler that ran before the first link_sample would still read ratings)
+    if (s->nnz > 0) HIP_TRY(hipMemcpyAsync(L->r.get(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    *out = std::move(L);
+    return 0;
 }
 
 }  // namespace bpmf_capi
@@ -139,22 +156,16 @@ extern "C" int bpmf_hip_side_set_features(bpmf_hip_side *s, const double *F_host
 {
     if (!s || !F_host) return fail(BPMF_HIP_EINVAL, "side_set_features: NULL argument");
     bpmf_hip_ctx *c = s->ctx;
-    if (s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_set_features: the side has features already");
     if (D < 1 || D > kMaxD) return fail(BPMF_HIP_EINVAL, "side_set_features: D must be 1 .. " + std::to_string(kMaxD));
-    if (!(lambda_beta > 0.0) || !std::isfinite(lambda_beta)) return fail(BPMF_HIP_EINVAL, "side_set_features: lambda_beta must be positive and finite");
-    if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_features: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
-    if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_features: not on an fp32 context");
-    if (c->comm || sharded(s)) return fail(BPMF_HIP_EINVAL, "side_set_features: needs the side whole on one GPU, on a context without a communicator");
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_features: not together with the BPMF_REDUCE formulation");
-    if (s->d_probit_z) return fail(BPMF_HIP_EINVAL, "side_set_features: not on a probit side");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_features: not together with propagated priors");
     const int64_t N = s->ncols;
-    const size_t nD = (size_t)N * (size_t)D;
+    const size_t nD = (size_t)N * (size_t)D, DD = (size_t)D * D;
     for (size_t q = 0; q < nD; ++q)
         if (!std::isfinite(F_host[q])) return fail(BPMF_HIP_EINVAL, "side_set_features: feature " + std::to_string(q) + " is not finite");
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
     const int K = c->K, Kt = c->Kt;
+    std::unique_ptr<bpmf_link> L;
+    int rc = link_attach_common("side_set_features", s, D, lambda_beta, tag,
+                                std::max(bpmf_launch::link_tn_part_words(N, D, Kt), bpmf_launch::link_tn_part_words(D, Kt, Kt)), &L);
+    if (rc) return rc;
     std::vector<double> tmp;
     const double *Frm = F_host;
     if (!row_major) {                                                  // column-major (.ddm): F[d * N + i] -> F[i * D + d], in tiles
@@ -166,52 +177,27 @@ extern "C" int bpmf_hip_side_set_features(bpmf_hip_side *s, const double *F_host
                     for (int64_t d = d0; d < std::min<int64_t>(D, d0 + TL); ++d) tmp[(size_t)i * D + d] = F_host[(size_t)d * N + i];
         Frm = tmp.data();
     }
-    const size_t ld = (size_t)K, DD = (size_t)D * D;
-    double *d_G = nullptr, *d_part0 = nullptr;
-    int rc = dev_upload(&s->d_link_f, Frm, nD);
+    auto dn = std::make_unique<bpmf_link_dense>();
+    if ((rc = dn->F.upload(Frm, nD))) return rc;
     tmp.clear(); tmp.shrink_to_fit();
-    if (!rc) rc = dev_upload<double>(&d_G, nullptr, DD);
-    if (!rc) rc = dev_upload<double>(&d_part0, nullptr, bpmf_launch::link_tn_part_words(N, D, std::min(D, 128)));
-    if (!rc) rc = tn_product(s->d_link_f, D, s->d_link_f, D, nullptr, N, D, D, d_G, D, d_part0, c->stream);
     std::vector<double> G(DD), T, Ginv;
-    if (!rc) rc = bounded_stream_sync(c, c->stream, __func__);
-    if (!rc && hipMemcpy(G.data(), d_G, DD * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "side_set_features: copy of G failed");
-    free_dev(d_G); free_dev(d_part0);
-    if (!rc) {
-        for (int d = 0; d < D; ++d) G[(size_t)d * D + d] += lambda_beta;
-        if (!factor_and_invert(D, G, T, Ginv)) rc = fail(BPMF_HIP_ENUM, "side_set_features: F^T F + lambda_beta I is not positive definite");
+    {   // G = F^T F on the device, factored and inverted on the host
+        DevBuf<double> d_G, d_part0;
+        if ((rc = d_G.alloc(DD)) || (rc = d_part0.alloc(bpmf_launch::link_tn_part_words(N, D, std::min(D, 128))))) return rc;
+        if ((rc = tn_product(dn->F.get(), D, dn->F.get(), D, nullptr, N, D, D, d_G.get(), D, d_part0.get(), c->stream))) return rc;
+        if ((rc = bounded_stream_sync(c, c->stream, __func__))) return rc;
+        if (hipMemcpy(G.data(), d_G.get(), DD * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_set_features: copy of G failed");
     }
-    if (!rc) {
-        std::vector<double> W(2 * DD);                                 // [G^-1 | L_G^-T], D x 2 D
-        for (int a = 0; a < D; ++a) {
-            memcpy(&W[(size_t)a * 2 * D], &Ginv[(size_t)a * D], sizeof(double) * D);
-            memcpy(&W[(size_t)a * 2 * D + D], &T[(size_t)a * D], sizeof(double) * D);
-        }
-        rc = dev_upload(&s->d_link_w, W.data(), 2 * DD);
+    for (int d = 0; d < D; ++d) G[(size_t)d * D + d] += lambda_beta;
+    if (!factor_and_invert(D, G, T, Ginv)) return fail(BPMF_HIP_ENUM, "side_set_features: F^T F + lambda_beta I is not positive definite");
+    std::vector<double> W(2 * DD);                                     // [G^-1 | L_G^-T], D x 2 D
+    for (int a = 0; a < D; ++a) {
+        memcpy(&W[(size_t)a * 2 * D], &Ginv[(size_t)a * D], sizeof(double) * D);
+        memcpy(&W[(size_t)a * 2 * D + D], &T[(size_t)a * D], sizeof(double) * D);
     }
-    const size_t part_words = std::max(bpmf_launch::link_tn_part_words(N, D, Kt), bpmf_launch::link_tn_part_words(D, Kt, Kt));
-    const int nblk = std::max(bpmf_launch::link_shift_blocks((int64_t)N * K), bpmf_launch::link_shift_blocks((int64_t)D * K));
-    if (!rc) rc = dev_upload<double>(&s->d_link_pe, nullptr, 2 * (size_t)D * ld);
-    if (!rc) rc = dev_upload<double>(&s->d_link_beta, nullptr, (size_t)D * ld);
-    if (!rc) rc = dev_upload<double>(&s->d_link_beta_sum, nullptr, (size_t)D * ld);
-    if (!rc) rc = dev_upload<double>(&s->d_link_m, nullptr, (size_t)N * ld);
-    if (!rc) rc = dev_upload<double>(&s->d_link_r, nullptr, (size_t)s->nnz);
-    if (!rc) rc = dev_upload<double>(&s->d_link_part, nullptr, part_words);
-    if (!rc) rc = dev_upload<double>(&s->d_link_mu, nullptr, ld);
-    if (!rc) rc = dev_upload<double>(&s->d_link_btb, nullptr, (size_t)Kt * Kt);
-    if (!rc) rc = dev_upload<double>(&s->d_link_norm, nullptr, (size_t)nblk);
-    if (!rc) rc = dev_upload(&s->d_link_colptr, s->h_colptr.data(), s->h_colptr.size());
-    if (!rc) {
-        hipError_t e = hipMemsetAsync(s->d_link_pe, 0, std::max<size_t>(2 * (size_t)D * ld, 1) * sizeof(double), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_link_beta, 0, std::max<size_t>((size_t)D * ld, 1) * sizeof(double), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_link_beta_sum, 0, std::max<size_t>((size_t)D * ld, 1) * sizeof(double), c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(s->d_link_m, 0, std::max<size_t>((size_t)N * ld, 1) * sizeof(double), c->stream);
-        // (the residuals of M = 0 are the ratings: a sampler that ran before the first link_sample would still read ratings)
-        if (e == hipSuccess && s->nnz > 0) e = hipMemcpyAsync(s->d_link_r, s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-        if (e != hipSuccess) rc = fail(BPMF_HIP_ENODEV, std::string("side_set_features: ") + hipGetErrorString(e));
-    }
-    if (rc) { (void)hipGetLastError(); const std::string keep = g_err; link_free(s); g_err = keep; return rc; }
-    s->link_d = D; s->link_lambda = lambda_beta; s->link_tag = (uint32_t)tag; s->link_nsum = 0;
+    if ((rc = dn->W.upload(W.data(), 2 * DD)) || (rc = dn->PE.alloc(2 * (size_t)D * K)) || (rc = dn->PE.zero_async(c->stream))) return rc;
+    L->dense = std::move(dn);
+    s->link = std::move(L);
     return BPMF_HIP_OK;
 }
 
@@ -219,45 +205,46 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
 {
     { const int rc = check_pair("link_sample", self, other); if (rc) return rc; }
     bpmf_hip_ctx *c = self->ctx;
-    if (c->comm || sharded(self) || sharded(other)) return fail(BPMF_HIP_EINVAL, "link_sample: needs both sides whole on one GPU, on a context without a communicator");
-    if (self->d_link_f && (self->reduce_on || self->d_probit_z || self->d_prop))
+    { const int rc = require_single_gpu("link_sample", c, self, other); if (rc) return rc; }
+    bpmf_link *L = self->link.get();
+    if (L && (self->reduce_on || self->probit || self->d_prop))
         return fail(BPMF_HIP_EINVAL, "link_sample: features do not go together with BPMF_REDUCE, a probit side or propagated priors");
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_state(self)) || (rc = ensure_state(other))) return rc;
     if ((rc = settle_async(self)) || (rc = settle_async(other))) return rc;
     if ((rc = flush_pending_stats(c, true))) return rc;
-    const int K = c->K, Kt = c->Kt, D = self->link_d;
+    const int K = c->K, Kt = c->Kt, D = L ? L->D : 0;
     const int64_t N = self->ncols;
     const int iter = self->iter + 1;
-    const bool link = self->d_link_f != nullptr;
+    const bool link = L != nullptr;
     hipStream_t st = c->stream;
     std::vector<double> mu((size_t)Kt), LU((size_t)Kt * Kt), LF((size_t)Kt * Kt), scatter;
 
     // 1. hyper-parameters: the link's scatter lambda_beta beta^T beta (K x K, formed on the device) and its D degrees of freedom
     if (link) {
         scatter.assign((size_t)Kt * Kt, 0.0);
-        if ((rc = tn_product(self->d_link_beta, K, self->d_link_beta, K, nullptr, D, Kt, Kt, self->d_link_btb, Kt, self->d_link_part, st))) return rc;
+        if ((rc = tn_product(L->beta.get(), K, L->beta.get(), K, nullptr, D, Kt, Kt, L->btb.get(), Kt, L->part.get(), st))) return rc;
         if ((rc = bounded_stream_sync(c, st, __func__))) return rc;
-        HIP_TRY(hipMemcpy(scatter.data(), self->d_link_btb, scatter.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (double &v : scatter) v *= self->link_lambda;
+        HIP_TRY(hipMemcpy(scatter.data(), L->btb.get(), scatter.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (double &v : scatter) v *= L->lambda;
     }
     rc = bpmf_hyper_sample_ex(Kt, N, self->cov.data(), nullptr, link ? scatter.data() : nullptr, link ? D : 0, (uint32_t)iter, mu.data(), LU.data(),
                               LF.data());
     if (rc) return rc;
 
-    if (link && self->link_sp) {
+    if (link && L->sparse) {
         // 2'. beta by CG on a noise-injected right-hand side, 3'. M = F beta by the sparse product (capi_link_sparse.hip); 4. residuals
         if ((rc = link_sparse_draw(self, mu.data(), LU.data(), iter))) return rc;
-        if ((rc = residual_enqueue(self, other, self->d_link_r))) return rc;
+        if ((rc = residual_enqueue(self, other, L->r.get()))) return rc;
     } else if (link) {
         // 2. beta = G^-1 P + L_G^-T E = [G^-1 | L_G^-T] [P ; E],  P = F^T (U - 1 mu^T),  E = Z R^-T with Lambda = R^T R
         std::vector<double> pad((size_t)K, 0.0);
         memcpy(pad.data(), mu.data(), sizeof(double) * Kt);
-        HIP_TRY(hipMemcpyAsync(self->d_link_mu, pad.data(), sizeof(double) * K, hipMemcpyHostToDevice, st));
-        if ((rc = tn_product(self->d_link_f, D, self->d_items, K, self->d_link_mu, N, D, Kt, self->d_link_pe, K, self->d_link_part, st))) return rc;
+        HIP_TRY(hipMemcpyAsync(L->mu.get(), pad.data(), sizeof(double) * K, hipMemcpyHostToDevice, st));
+        if ((rc = tn_product(L->dense->F.get(), D, self->d_items, K, L->mu.get(), N, D, Kt, L->dense->PE.get(), K, L->part.get(), st))) return rc;
         std::vector<double> Z((size_t)D * Kt), E((size_t)D * K, 0.0);
-        bpmf_randn_stream_tag((uint32_t)iter, self->link_tag, D * Kt, Z.data());
+        bpmf_randn_stream_tag((uint32_t)iter, L->tag, D * Kt, Z.data());
         for (int d = 0; d < D; ++d) {                                   // row d: R e = z, R = LambdaU (upper, column-major)
             const double *z = &Z[(size_t)d * Kt];
             double *e = &E[(size_t)d * K];
@@ -267,23 +254,23 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
                 e[i] = v / LU[(size_t)i * Kt + i];
             }
         }
-        HIP_TRY(hipMemcpyAsync(self->d_link_pe + (size_t)D * K, E.data(), E.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(L->dense->PE.get() + (size_t)D * K, E.data(), E.size() * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                              // (the host buffers above go out of use here)
-        if ((rc = nn_product(self->d_link_w, 2 * D, self->d_link_pe, K, D, 2 * D, Kt, self->d_link_beta, K, K, st))) return rc;
+        if ((rc = nn_product(L->dense->W.get(), 2 * D, L->dense->PE.get(), K, D, 2 * D, Kt, L->beta.get(), K, K, st))) return rc;
         // 3. offsets, 4. residuals: from the copy of the other side's factors the sampler below reads
         if ((rc = offsets_update(self))) return rc;
-        if ((rc = residual_enqueue(self, other, self->d_link_r))) return rc;
+        if ((rc = residual_enqueue(self, other, L->r.get()))) return rc;
     }
 
-    // 5. the unchanged column samplers (on the residuals: launch_impl.h picks d_link_r), their sums, cov
+    // 5. the unchanged column samplers (on the residuals: launch_impl.h picks link->r), their sums, cov
     std::vector<double> sum((size_t)Kt), prod((size_t)Kt * Kt);
     double norm = 0.0;
-    self->link_in_call = true;
+    if (link) L->in_call = true;
     rc = bpmf_hip_sample_side(self, other, iter, alpha, mu.data(), LF.data(), sum.data(), prod.data(), &norm);
-    self->link_in_call = false;
+    if (link) L->in_call = false;
     if (rc) return rc;
     // 6. U = U~ + M on the copy the sampler wrote (d_items after its swap), and the norm of U
-    if (link && (rc = shift_and_norm(self, self->d_items, self->d_link_m, N * (int64_t)K, &norm))) return rc;
+    if (link && (rc = shift_and_norm(self, self->d_items, L->m.get(), N * (int64_t)K, &norm))) return rc;
     c->last_sampler_done = nullptr;
     self->iter = iter;
     self->norm = norm;
@@ -296,58 +283,58 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
 extern "C" int bpmf_hip_side_link_get(bpmf_hip_side *s, double *beta_host, double *offsets_host)
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "side_link_get: NULL");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_get: the side has no features (bpmf_hip_side_set_features)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_get: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
     const size_t K = (size_t)c->K, Kt = (size_t)c->Kt;
-    if (beta_host) HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->d_link_beta, K * sizeof(double), Kt * sizeof(double), (size_t)s->link_d, hipMemcpyDeviceToHost));
+    if (beta_host) HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->link->beta.get(), K * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyDeviceToHost));
     if (offsets_host && s->ncols > 0)
-        HIP_TRY(hipMemcpy2D(offsets_host, Kt * sizeof(double), s->d_link_m, K * sizeof(double), Kt * sizeof(double), (size_t)s->ncols, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy2D(offsets_host, Kt * sizeof(double), s->link->m.get(), K * sizeof(double), Kt * sizeof(double), (size_t)s->ncols, hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_side_link_set(bpmf_hip_side *s, const double *beta_host)
 {
     if (!s || !beta_host) return fail(BPMF_HIP_EINVAL, "side_link_set: NULL argument");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_set: the side has no features (bpmf_hip_side_set_features)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_set: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     const size_t K = (size_t)c->K, Kt = (size_t)c->Kt;
-    for (size_t q = 0; q < (size_t)s->link_d * Kt; ++q)
+    for (size_t q = 0; q < (size_t)s->link->D * Kt; ++q)
         if (!std::isfinite(beta_host[q])) return fail(BPMF_HIP_EINVAL, "side_link_set: beta is not finite");
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    HIP_TRY(hipMemcpy2D(s->d_link_beta, K * sizeof(double), beta_host, Kt * sizeof(double), Kt * sizeof(double), (size_t)s->link_d, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(s->link->beta.get(), K * sizeof(double), beta_host, Kt * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyHostToDevice));
     return offsets_update(s);
 }
 
 extern "C" int bpmf_hip_side_link_add(bpmf_hip_side *s)
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "side_link_add: NULL");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_add: the side has no features (bpmf_hip_side_set_features)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_add: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    bpmf_launch::link_shift(s->d_link_beta_sum, s->d_link_beta, (int64_t)s->link_d * c->K, s->d_link_norm, c->stream);   // (sum += beta; the norm goes unused)
+    bpmf_launch::link_shift(s->link->beta_sum.get(), s->link->beta.get(), (int64_t)s->link->D * c->K, s->link->norm.get(), c->stream);   // (sum += beta; the norm goes unused)
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
-    ++s->link_nsum;
+    ++s->link->nsum;
     return BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_side_link_mean(bpmf_hip_side *s, double *beta_host, int *nsamples)
 {
     if (!s || !beta_host) return fail(BPMF_HIP_EINVAL, "side_link_mean: NULL argument");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_mean: the side has no features (bpmf_hip_side_set_features)");
-    if (nsamples) *nsamples = s->link_nsum;
-    if (s->link_nsum == 0) return fail(BPMF_HIP_EINVAL, "side_link_mean: nothing added (bpmf_hip_side_link_add)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_mean: the side has no features (bpmf_hip_side_set_features)");
+    if (nsamples) *nsamples = s->link->nsum;
+    if (s->link->nsum == 0) return fail(BPMF_HIP_EINVAL, "side_link_mean: nothing added (bpmf_hip_side_link_add)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
     const size_t K = (size_t)c->K, Kt = (size_t)c->Kt;
-    HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->d_link_beta_sum, K * sizeof(double), Kt * sizeof(double), (size_t)s->link_d, hipMemcpyDeviceToHost));
-    const double n = (double)s->link_nsum;
-    for (size_t q = 0; q < (size_t)s->link_d * Kt; ++q) beta_host[q] /= n;
+    HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->link->beta_sum.get(), K * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyDeviceToHost));
+    const double n = (double)s->link->nsum;
+    for (size_t q = 0; q < (size_t)s->link->D * Kt; ++q) beta_host[q] /= n;
     return BPMF_HIP_OK;
 }
 
@@ -355,24 +342,24 @@ extern "C" int bpmf_hip_side_link_residual(bpmf_hip_side *s, const bpmf_hip_side
 {
     { const int rc = check_pair("side_link_residual", s, other); if (rc) return rc; }
     if (!r_host) return fail(BPMF_HIP_EINVAL, "side_link_residual: NULL argument");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_residual: the side has no features (bpmf_hip_side_set_features)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_residual: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rc = residual_enqueue(s, other, s->d_link_r); if (rc) return rc; }
+    { const int rc = residual_enqueue(s, other, s->link->r.get()); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(r_host, s->d_link_r, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (s->nnz > 0) HIP_TRY(hipMemcpy(r_host, s->link->r.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_side_link_shift(bpmf_hip_side *s, double *norm)
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "side_link_shift: NULL");
-    if (!s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_link_shift: the side has no features (bpmf_hip_side_set_features)");
+    if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_shift: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    return shift_and_norm(s, s->d_items, s->d_link_m, s->ncols * (int64_t)c->K, norm);
+    return shift_and_norm(s, s->d_items, s->link->m.get(), s->ncols * (int64_t)c->K, norm);
 }
 
 // ---- the two products on host arrays (tests, tools) ------------------------------------------------------------------------
@@ -383,30 +370,26 @@ extern "C" int bpmf_hip_link_gemm_tn(int device, const double *A, int64_t N, int
     if (!B && n != D) return fail(BPMF_HIP_EINVAL, "link_gemm_tn: B = NULL means B = A, n = D");
     if (B && n > 128) return fail(BPMF_HIP_EINVAL, "link_gemm_tn: n <= 128 (or B = NULL for A^T A)");
     HIP_TRY(hipSetDevice(device));
-    double *dA = nullptr, *dB = nullptr, *dv = nullptr, *dC = nullptr, *dP = nullptr;
-    int rc = dev_upload(&dA, A, (size_t)N * D);
-    if (!rc && B) rc = dev_upload(&dB, B, (size_t)N * n);
-    if (!rc && bvec) rc = dev_upload(&dv, bvec, (size_t)n);
-    if (!rc) rc = dev_upload<double>(&dC, nullptr, (size_t)D * n);
-    if (!rc) rc = dev_upload<double>(&dP, nullptr, bpmf_launch::link_tn_part_words(N, D, std::min(n, 128)));
-    if (!rc) rc = tn_product(dA, D, B ? dB : dA, B ? n : D, dv, N, D, n, dC, n, dP, nullptr);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "link_gemm_tn: kernel failed");
-    if (!rc && hipMemcpy(C, dC, (size_t)D * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "link_gemm_tn: copy failed");
-    free_dev(dA); free_dev(dB); free_dev(dv); free_dev(dC); free_dev(dP);
-    return rc;
+    DevBuf<double> dA, dB, dv, dC, dP;
+    int rc;
+    if ((rc = dA.upload(A, (size_t)N * D)) || (B && (rc = dB.upload(B, (size_t)N * n))) || (bvec && (rc = dv.upload(bvec, (size_t)n))) ||
+        (rc = dC.alloc((size_t)D * n)) || (rc = dP.alloc(bpmf_launch::link_tn_part_words(N, D, std::min(n, 128)))))
+        return rc;
+    if ((rc = tn_product(dA.get(), D, B ? dB.get() : dA.get(), B ? n : D, dv.get(), N, D, n, dC.get(), n, dP.get(), nullptr))) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) return fail(BPMF_HIP_ENODEV, "link_gemm_tn: kernel failed");
+    if (hipMemcpy(C, dC.get(), (size_t)D * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(BPMF_HIP_ENODEV, "link_gemm_tn: copy failed");
+    return BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_link_gemm_nn(int device, const double *A, int64_t N, int D, const double *B, int n, double *C)
 {
     if (!A || !B || !C || N < 1 || D < 1 || n < 1 || n > 128) return fail(BPMF_HIP_EINVAL, "link_gemm_nn: bad argument (n <= 128)");
     HIP_TRY(hipSetDevice(device));
-    double *dA = nullptr, *dB = nullptr, *dC = nullptr;
-    int rc = dev_upload(&dA, A, (size_t)N * D);
-    if (!rc) rc = dev_upload(&dB, B, (size_t)D * n);
-    if (!rc) rc = dev_upload<double>(&dC, nullptr, (size_t)N * n);
-    if (!rc) rc = nn_product(dA, D, dB, n, N, D, n, dC, n, n, nullptr);
-    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "link_gemm_nn: kernel failed");
-    if (!rc && hipMemcpy(C, dC, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "link_gemm_nn: copy failed");
-    free_dev(dA); free_dev(dB); free_dev(dC);
-    return rc;
+    DevBuf<double> dA, dB, dC;
+    int rc;
+    if ((rc = dA.upload(A, (size_t)N * D)) || (rc = dB.upload(B, (size_t)D * n)) || (rc = dC.alloc((size_t)N * n))) return rc;
+    if ((rc = nn_product(dA.get(), D, dB.get(), n, N, D, n, dC.get(), n, n, nullptr))) return rc;
+    if (hipDeviceSynchronize() != hipSuccess) return fail(BPMF_HIP_ENODEV, "link_gemm_nn: kernel failed");
+    if (hipMemcpy(C, dC.get(), (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(BPMF_HIP_ENODEV, "link_gemm_nn: copy failed");
+    return BPMF_HIP_OK;
 }

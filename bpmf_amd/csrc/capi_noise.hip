@@ -5,43 +5,35 @@
 
 using namespace bpmf_capi;
 
-static bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
-
 extern "C" int bpmf_hip_train_sse(bpmf_hip_side *self, bpmf_hip_side *other, double *sse, int64_t *n)
 {
     if (!self || !other || !sse || !n) return fail(BPMF_HIP_EINVAL, "train_sse: NULL argument");
     bpmf_hip_ctx *c = self->ctx;
     if (other->ctx != c) return fail(BPMF_HIP_EINVAL, "train_sse: the two sides belong to different contexts");
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "train_sse: the other side must have one column per row of this side's ratings");
-    if (c->comm || sharded(self) || sharded(other))
-        return fail(BPMF_HIP_EINVAL, "train_sse: needs both sides whole on one GPU (a sharded side or a communicator would need an all-reduce "
-                                     "of the sum, which adaptive noise does not do)");
+    int rc = require_single_gpu("train_sse", c, self, other, " (a sharded side or a communicator would need an all-reduce of the sum, which adaptive noise does not do)");
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     *sse = 0.0;
     *n = self->nnz;
     if (self->nnz == 0) return BPMF_HIP_OK;
-    if (!self->d_sse_part) {                                          // first call: the column pointers and the partials, once
-        const int nblk = bpmf_launch::train_sse_blocks(self->nnz, c->num_cu);
-        int rc = dev_upload(&self->d_sse_colptr, self->h_colptr.data(), self->h_colptr.size());
-        if (!rc) rc = dev_upload<double>(&self->d_sse_part, nullptr, (size_t)nblk + 1);
-        if (rc) {
-            if (self->d_sse_colptr) (void)hipFree(self->d_sse_colptr);
-            self->d_sse_colptr = nullptr; self->d_sse_part = nullptr;
-            return rc;
-        }
-        self->sse_nblk = nblk;
+    if (!self->sse) {                                                 // first call: the column pointers and the partials, once
+        auto e = std::make_unique<bpmf_sse>();
+        e->nblk = bpmf_launch::train_sse_blocks(self->nnz, c->num_cu);
+        if ((rc = ensure_colptr(self)) || (rc = e->part.alloc((size_t)e->nblk + 1))) return rc;
+        self->sse = std::move(e);
     }
     // S0 holds the newest sampler of both sides (bpmf_hip_sys_sample and bpmf_hip_sample_side enqueue there) and d_items is
     // the copy it writes: behind it in the queue, nothing else needed.  Nothing this waits for depends on a later enqueue:
     // statistics waiting for a rider and a deferred evaluation go to other launches, not to the samplers ahead of this one.
     bpmf_launch::SseLaunch p{};
-    p.colptr = self->d_sse_colptr; p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.vals = self->d_vals; p.nnz = self->nnz;
+    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.vals = self->d_vals; p.nnz = self->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
-    p.mean = self->mean_rating; p.partial = self->d_sse_part; p.nblk = self->sse_nblk;
+    p.mean = self->mean_rating; p.partial = self->sse->part.get(); p.nblk = self->sse->nblk;
     if (bpmf_launch::train_sse(p, c->stream)) return fail(BPMF_HIP_EINVAL, "train_sse: unsupported K " + std::to_string(c->K));
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "train_sse: kernel launch failed");
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    HIP_TRY(hipMemcpy(sse, self->d_sse_part + self->sse_nblk, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sse, self->sse->part.get() + self->sse->nblk, sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }

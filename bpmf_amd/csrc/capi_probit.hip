@@ -6,19 +6,7 @@
 
 using namespace bpmf_capi;
 
-static bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
-
 namespace bpmf_capi {
-
-void probit_free(bpmf_hip_side *s)
-{
-    if (s->d_probit_z) (void)hipFree(s->d_probit_z);
-    if (s->d_probit_sign) (void)hipFree(s->d_probit_sign);
-    if (s->d_probit_colptr) (void)hipFree(s->d_probit_colptr);
-    if (s->h_probit_fail) (void)hipHostFree(s->h_probit_fail);
-    s->d_probit_z = nullptr; s->d_probit_sign = nullptr; s->d_probit_colptr = nullptr;
-    s->h_probit_fail = nullptr; s->h_probit_fail_dev = nullptr;
-}
 
 // The latent kernel of the half-iteration being enqueued, on the stream `st` its sampler goes on, ahead of it: `self->d_items` is
 // still the copy the side holds before this update (the sampler behind writes the other copy, or this one in place, later in
@@ -32,9 +20,10 @@ int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
     if (c->comm || sharded(self) || self->reduce_on || self->item_n >= 0)
         return fail(BPMF_HIP_EINVAL, "probit: needs the side whole on one GPU, without a communicator and without BPMF_REDUCE");
     bpmf_launch::ProbitLatentLaunch p{};
-    p.colptr = self->d_probit_colptr; p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.sign = self->d_probit_sign; p.nnz = self->nnz;
+    const bpmf_probit *pb = self->probit.get();
+    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.sign = pb->sign.get(); p.nnz = self->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
-    p.iter = (uint32_t)iter; p.tag = self->probit_tag; p.z = self->d_probit_z; p.fail = self->h_probit_fail_dev;
+    p.iter = (uint32_t)iter; p.tag = pb->tag; p.z = pb->z.get(); p.fail = pb->fail.dev();
     if (bpmf_launch::probit_latent(p, st)) return fail(BPMF_HIP_EINVAL, "probit: unsupported K " + std::to_string(c->K));
     return 0;
 }
@@ -45,42 +34,38 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "side_set_probit: NULL");
     bpmf_hip_ctx *c = s->ctx;
-    if (s->d_probit_z) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
-    if (s->d_link_f) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with features (bpmf_hip_side_set_features)");
+    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
+    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with features (bpmf_hip_side_set_features)");
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_probit: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if (!std::isfinite(threshold)) return fail(BPMF_HIP_EINVAL, "side_set_probit: the threshold is not finite");
-    if (c->comm || sharded(s))
-        return fail(BPMF_HIP_EINVAL, "side_set_probit: needs the side whole on one GPU, on a context without a communicator");
+    int rc = require_single_gpu("side_set_probit", c, s);
+    if (rc) return rc;
     if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with the BPMF_REDUCE formulation");
     HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
-    int rc = dev_upload<double>(&s->d_probit_z, nullptr, (size_t)s->nnz);
-    if (!rc) rc = dev_upload<int8_t>(&s->d_probit_sign, nullptr, (size_t)s->nnz);
-    if (!rc) rc = dev_upload(&s->d_probit_colptr, s->h_colptr.data(), s->h_colptr.size());
-    if (!rc && (hipHostMalloc((void **)&s->h_probit_fail, sizeof(unsigned long long), hipHostMallocMapped) != hipSuccess ||
-                hipHostGetDevicePointer((void **)&s->h_probit_fail_dev, s->h_probit_fail, 0) != hipSuccess))
-        rc = fail(BPMF_HIP_ENOMEM, "side_set_probit: pinned allocation failed");
-    if (!rc && hipMemsetAsync(s->d_probit_z, 0, std::max<size_t>((size_t)s->nnz, 1) * sizeof(double), c->stream) != hipSuccess)
-        rc = fail(BPMF_HIP_ENODEV, "side_set_probit: memset failed");
-    if (rc) { (void)hipGetLastError(); probit_free(s); return rc; }
-    *s->h_probit_fail = ~0ull;
-    s->probit_tag = (uint32_t)tag;
-    bpmf_launch::probit_sign(s->d_vals, s->nnz, threshold, s->d_probit_sign, c->stream);
-    if (hipGetLastError() != hipSuccess) { probit_free(s); return fail(BPMF_HIP_ENODEV, "side_set_probit: kernel launch failed"); }
+    if ((rc = settle_async(s))) return rc;
+    auto pb = std::make_unique<bpmf_probit>();
+    if ((rc = pb->z.alloc((size_t)s->nnz)) || (rc = pb->sign.alloc((size_t)s->nnz)) || (rc = ensure_colptr(s)) || (rc = pb->fail.alloc(1)) ||
+        (rc = pb->z.zero_async(c->stream)))
+        return rc;
+    *pb->fail.host() = ~0ull;
+    pb->tag = (uint32_t)tag;
+    bpmf_launch::probit_sign(s->d_vals, s->nnz, threshold, pb->sign.get(), c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_set_probit: kernel launch failed");
+    s->probit = std::move(pb);
     return BPMF_HIP_OK;
 }
 
 extern "C" int bpmf_hip_side_probit_latent(bpmf_hip_side *s, double *z_host)
 {
     if (!s || !z_host) return fail(BPMF_HIP_EINVAL, "side_probit_latent: NULL argument");
-    if (!s->d_probit_z) return fail(BPMF_HIP_EINVAL, "side_probit_latent: not a probit side (bpmf_hip_side_set_probit)");
+    if (!s->probit) return fail(BPMF_HIP_EINVAL, "side_probit_latent: not a probit side (bpmf_hip_side_set_probit)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
     { std::string m; if (check_probit(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->d_probit_z, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->probit->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
 
@@ -90,8 +75,7 @@ extern "C" int bpmf_hip_test_probit_add(bpmf_hip_test *t, bpmf_hip_side *self, b
     bpmf_hip_ctx *c = self->ctx;
     if (t->side != self) return fail(BPMF_HIP_EINVAL, "test_probit_add: the test matrix belongs to another side");
     if (other->ctx != c || other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "test_probit_add: the two sides do not belong together");
-    if (c->comm || sharded(self) || sharded(other))
-        return fail(BPMF_HIP_EINVAL, "test_probit_add: needs both sides whole on one GPU, on a context without a communicator");
+    { const int rc = require_single_gpu("test_probit_add", c, self, other); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
     if (!t->d_prob_sum) {
         const int rc = dev_upload<double>(&t->d_prob_sum, nullptr, (size_t)t->nnz);

@@ -26,7 +26,7 @@ int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, do
     // probit side: its latent scores are redrawn first, on the same stream, from the factors this side holds now (the copy
     // the sampler below replaces or overwrites) and the copy of the other side's the sampler reads.  No host wait.  The
     // stateful path has enqueued the kernel already, ahead of its wait for the gate kernel (bpmf_hip_sys_sample).
-    if (self->d_probit_z && !self->probit_latent_queued) { const int rp = probit_latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
+    if (self->probit && !self->probit_latent_queued) { const int rp = probit_latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
     int rc = claim_second_copy(self, st);
@@ -250,7 +250,7 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sample_side: other side has the wrong number of columns");
     if (iter < 0) return fail(BPMF_HIP_EINVAL, "sample_side: iter < 0");
     if (self->pending) return fail(BPMF_HIP_EINVAL, "sample_side_launch: previous launch not finished");
-    if (self->d_link_f && !self->link_in_call)
+    if (self->link && !self->link->in_call)
         return fail(BPMF_HIP_EINVAL, "sample_side: the side has features: step it with bpmf_hip_link_sample");
     self->probit_latent_queued = false;                               // (a stateful call that failed half-way may have left it set)
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sample_side: the communicator of this context was aborted (a collective timed out)");
@@ -687,7 +687,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     bpmf_hip_ctx *c = self->ctx;
     if (other->ctx != c) return fail(BPMF_HIP_EINVAL, "sys_sample: sides belong to different contexts");
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sys_sample: other side has the wrong number of columns");
-    if (self->d_link_f)
+    if (self->link)
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side has features: step BOTH sides of the model with bpmf_hip_link_sample");
     if (self->to - self->from != self->ncols && !(c->comm && !self->bounds.empty()))
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side is a shard: give the context a communicator "
@@ -755,7 +755,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     // host chain (sums -> cov -> Normal-Wishart -> staging) is still at work.  Fused form: the same place in the queue as
     // before, directly ahead of the sampler launch that carries its own gate.
     self->probit_latent_queued = false;
-    if (self->d_probit_z) {
+    if (self->probit) {
         if ((rc = probit_latent_enqueue(self, other, iter, alpha, s0))) return rc;
         self->probit_latent_queued = true;
     }

@@ -310,13 +310,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     if (s->own_items && s->d_items) (void)hipFree(s->d_items);
     if (s->d_items_alt) (void)hipFree(s->d_items_alt);
     if (s->d_prop) (void)hipFree(s->d_prop);
-    if (s->d_ring) (void)hipFree(s->d_ring);
-    if (s->d_ex_ptr) (void)hipFree(s->d_ex_ptr);
-    if (s->d_ex_rows) (void)hipFree(s->d_ex_rows);
-    if (s->d_sse_colptr) (void)hipFree(s->d_sse_colptr);
-    if (s->d_sse_part) (void)hipFree(s->d_sse_part);
-    probit_free(s);
-    link_free(s);
+    s->probit.reset(); s->link.reset(); s->ring.reset(); s->sse.reset(); s->d_colptr.reset();
     if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
     if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
     void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,
@@ -335,6 +329,16 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     delete s;
     return BPMF_HIP_OK;
 }
+
+int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_side *a, const bpmf_hip_side *b, const char *tail)
+{
+    if (!c->comm && !sharded(a) && !(b && sharded(b))) return 0;
+    return fail(BPMF_HIP_EINVAL, std::string(who) + (b ? ": needs both sides whole on one GPU" : ": needs the side whole on one GPU") + tail);
+}
+
+int ensure_colptr(bpmf_hip_side *s) { return s->d_colptr ? 0 : s->d_colptr.upload(s->h_colptr.data(), s->h_colptr.size()); }
+
+extern "C" int64_t bpmf_hip_live_device_bytes(void) { return g_live_bytes.load(std::memory_order_relaxed); }
 
 // ---- padded num_latent (ctx->Kt < ctx->K) -----------------------------------------------------
 // Everything that crosses the C ABI has the caller's size Kt; the device side has the instantiated size K.

@@ -12,24 +12,19 @@ extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    if (s->d_ring) {
+    if (s->ring) {
         { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-        (void)hipFree(s->d_ring);
-        s->d_ring = nullptr;
+        s->ring.reset();
     }
-    s->ring_max = s->ring_count = 0;
     if (max_samples == 0) return BPMF_HIP_OK;
-    const int kp = ring_kp(c);
-    const size_t words = (size_t)s->ncols * (size_t)max_samples * (size_t)kp;
-    if (hipMalloc((void **)&s->d_ring, words * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        s->d_ring = nullptr;
+    auto ring = std::make_unique<bpmf_ring>();
+    ring->max = max_samples; ring->kp = ring_kp(c);
+    const size_t words = (size_t)s->ncols * (size_t)max_samples * (size_t)ring->kp;
+    if (ring->samples.alloc(words))
         return fail(BPMF_HIP_ENOMEM, "samples_reserve: " + std::to_string(max_samples) + " samples of " + std::to_string((long long)s->ncols) +
-                    " columns x " + std::to_string(kp) + " doubles (" + std::to_string(words * sizeof(double) >> 20) + " MiB) do not fit in device memory");
-    }
-    HIP_TRY(hipMemsetAsync(s->d_ring, 0, words * sizeof(double), c->stream));
-    s->ring_max = max_samples;
-    s->ring_kp = kp;
+                    " columns x " + std::to_string(ring->kp) + " doubles (" + std::to_string(words * sizeof(double) >> 20) + " MiB) do not fit in device memory");
+    { const int rc = ring->samples.zero_async(c->stream); if (rc) return rc; }
+    s->ring = std::move(ring);
     return BPMF_HIP_OK;
 }
 
@@ -37,25 +32,26 @@ extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
 extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "samples_add: NULL");
-    if (!s->d_ring) return fail(BPMF_HIP_EINVAL, "samples_add: no sample ring (bpmf_hip_side_samples_reserve)");
-    if (s->ring_count >= s->ring_max) return fail(BPMF_HIP_EINVAL, "samples_add: the ring is full (" + std::to_string(s->ring_max) + " samples)");
+    bpmf_ring *ring = s->ring.get();
+    if (!ring) return fail(BPMF_HIP_EINVAL, "samples_add: no sample ring (bpmf_hip_side_samples_reserve)");
+    if (ring->count >= ring->max) return fail(BPMF_HIP_EINVAL, "samples_add: the ring is full (" + std::to_string(ring->max) + " samples)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, s->ring_kp, s->ncols, s->d_ring,
-                             (int64_t)s->ring_max * s->ring_kp, s->ring_count, c->stream);
+    bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, ring->kp, s->ncols, ring->samples.get(),
+                             (int64_t)ring->max * ring->kp, ring->count, c->stream);
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
-    ++s->ring_count;
+    ++ring->count;
     return BPMF_HIP_OK;
 }
 
-extern "C" int bpmf_hip_side_samples_count(const bpmf_hip_side *s) { return s ? s->ring_count : 0; }
+extern "C" int bpmf_hip_side_samples_count(const bpmf_hip_side *s) { return s && s->ring ? s->ring->count : 0; }
 
 // the rated candidates of every column of the side, sorted: read back from the device ratings once
 static int build_exclusion(bpmf_hip_side *s)
 {
-    if (s->d_ex_ptr) return 0;
+    if (s->ring->ex_ptr) return 0;
     if (s->from != 0 || s->to != s->ncols)
         return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs a query side that holds all its columns (this rank has " +
                     std::to_string((long long)s->from) + " .. " + std::to_string((long long)s->to) + ")");
@@ -65,14 +61,11 @@ static int build_exclusion(bpmf_hip_side *s)
     std::vector<int32_t> rows((size_t)std::max<int64_t>(s->nnz, 1));
     if (s->nnz > 0) HIP_TRY(hipMemcpy(rows.data(), s->d_rowidx, (size_t)s->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int64_t q = 0; q < s->ncols; ++q) std::sort(rows.begin() + cp[(size_t)q], rows.begin() + cp[(size_t)q + 1]);
-    int rc = dev_upload(&s->d_ex_ptr, cp.data(), cp.size());
-    if (!rc) rc = dev_upload(&s->d_ex_rows, rows.data(), rows.size());
-    if (rc) {
-        if (s->d_ex_ptr) (void)hipFree(s->d_ex_ptr);
-        if (s->d_ex_rows) (void)hipFree(s->d_ex_rows);
-        s->d_ex_ptr = nullptr; s->d_ex_rows = nullptr;
-    }
-    return rc;
+    DevBuf<int64_t> ptr; DevBuf<int32_t> sorted;
+    int rc;
+    if ((rc = ptr.upload(cp.data(), cp.size())) || (rc = sorted.upload(rows.data(), rows.size()))) return rc;
+    s->ring->ex_ptr = std::move(ptr); s->ring->ex_rows = std::move(sorted);
+    return 0;
 }
 
 extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
@@ -89,11 +82,12 @@ extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double m
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(query); if (rc) return rc; }        // every half-iteration in flight on both sides (as bpmf_hip_sys_state)
     { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->d_ring || !cand->d_ring) return fail(BPMF_HIP_EINVAL, "topn: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    const int S = query->ring_count;
-    if (S < 1 || cand->ring_count != S)
+    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
+    const int S = qr->count;
+    if (S < 1 || cr->count != S)
         return fail(BPMF_HIP_EINVAL, "topn: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cand->ring_count));
+                    std::to_string(cr->count));
     if (exclude_rated && query->nrows != cand->ncols)
         return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs the query side's rows to be the candidate side's columns");
     if (nq == 0) return BPMF_HIP_OK;
@@ -106,38 +100,24 @@ extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double m
     nsplit = (nc + cspan - 1) / cspan;
 
     const size_t pn = (size_t)nq * (size_t)n;
-    double *part_mean = nullptr, *out = nullptr;
-    int32_t *part_idx = nullptr, *out_idx = nullptr;
-    auto release = [&]() {
-        if (part_mean) (void)hipFree(part_mean);
-        if (part_idx) (void)hipFree(part_idx);
-        if (out) (void)hipFree(out);
-        if (out_idx) (void)hipFree(out_idx);
-    };
-    if (hipMalloc((void **)&part_mean, (size_t)nsplit * pn * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&part_idx, (size_t)nsplit * pn * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void **)&out, 2 * pn * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&out_idx, pn * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
+    DevBuf<double> part_mean, out;
+    DevBuf<int32_t> part_idx, out_idx;
+    if (part_mean.alloc((size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(2 * pn) || out_idx.alloc(pn))
         return fail(BPMF_HIP_ENOMEM, "topn: device allocation of the result lists failed");
-    }
     bpmf_launch::TopnLaunch p{};
-    p.qring = query->d_ring; p.cring = cand->d_ring;
-    p.qstride = (int64_t)query->ring_max * query->ring_kp; p.cstride = (int64_t)cand->ring_max * cand->ring_kp;
-    p.Kp = query->ring_kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
+    p.qring = qr->samples.get(); p.cring = cr->samples.get();
+    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
+    p.Kp = qr->kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
     p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
-    p.ex_ptr = exclude_rated ? query->d_ex_ptr : nullptr; p.ex_rows = exclude_rated ? query->d_ex_rows : nullptr;
-    p.part_mean = part_mean; p.part_idx = part_idx;
-    p.out_mean = out; p.out_std = out + pn; p.out_idx = out_idx;
+    p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
+    p.part_mean = part_mean.get(); p.part_idx = part_idx.get();
+    p.out_mean = out.get(); p.out_std = out.get() + pn; p.out_idx = out_idx.get();
     bpmf_launch::topn(p, c->stream);
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) rc = fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
-    if (!rc) rc = bounded_stream_sync(c, c->stream, __func__);
-    if (!rc && (hipMemcpy(mean_out, out, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(std_out, out + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(idx_out, out_idx, pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
-    release();
-    return rc;
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
+    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    if (hipMemcpy(mean_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(std_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
+    return BPMF_HIP_OK;
 }

@@ -1,0 +1,66 @@
+// ext_state.h -- what the add-ons of a side own on the device (included by state.h): bpmf_hip_side holds one owning pointer per
+// add-on, NULL while the side has none; everything below is released when that pointer is reset.
+#pragma once
+#include <memory>
+
+#include "devbuf.h"
+
+namespace bpmf { struct CgState; }
+
+namespace bpmf_launch {
+
+// A matrix compressed by rows on the device (F by rows, or F^T by rows = F by columns).  Rows of more than kSpChunk nonzeros are
+// "long": cut into chunks whose partial sums are added in chunk order.  (link_sparse.h: sp_upload, sp_product)
+struct SpMat {
+    int64_t nrows = 0, nnz = 0;
+    DevBuf<int64_t> ptr;
+    DevBuf<int32_t> idx;
+    DevBuf<double> vals;                                    // empty: every stored value is 1
+    int nlong = 0; int64_t nchunks = 0;
+    DevBuf<int32_t> lrow; DevBuf<int64_t> lfirst, cbeg, cend;
+    DevBuf<double> part; int part_n = 0;                    // nchunks x part_n doubles
+};
+
+// the work arrays of K conjugate-gradient solves in lockstep on D x ld arrays (link_sparse.h: cg_alloc, cg_solve)
+struct CgWork {
+    DevBuf<double> p, q, t;                                 // D x ld, D x ld, N x ld
+    DevBuf<double> partial;                                 // cg_blocks(D) x 128
+    DevBuf<bpmf::CgState> state;
+    Pinned<int> word;                                       // the number of active columns, written by the device
+};
+
+}  // namespace bpmf_launch
+
+// probit likelihood (capi_probit.hip): the latent scores (layout of d_vals; the samplers read them in its
+// place), the sign of every rating, and a word the latent kernel raises to a rating position when a draw runs into its attempt cap
+struct bpmf_probit { DevBuf<double> z; DevBuf<int8_t> sign; Pinned<unsigned long long> fail; uint32_t tag = 0; };
+
+// dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
+struct bpmf_link_dense { DevBuf<double> F, W, PE; };
+
+// sparse features (capi_link_sparse.hip): F compressed both ways, the work arrays of the CG draw of beta, its
+// right-hand side / residual (D x K) and R^-1 (Kt x Kt), the settings and the statistics of the solves
+struct bpmf_link_sparse {
+    bpmf_launch::SpMat F, Ft;
+    bpmf_launch::CgWork cg;
+    DevBuf<double> rhs, rinv;
+    double tol = 1e-6; int max_iter = 1000;
+    int iters_last = 0; int64_t iters_total = 0; double relres_max_last = 0.0; int hit_max_iter = 0;
+};
+
+// side information: beta (D x ld) and its running sum, the offsets M = F beta in the factors' layout, the
+// residual ratings the samplers read in place of d_vals, staging arrays, and the features as exactly one of dense / sparse.
+// in_call: bpmf_hip_link_sample is driving the stateless half-iteration of this side.
+struct bpmf_link {
+    int D = 0; double lambda = 0.0; uint32_t tag = 0; int nsum = 0; bool in_call = false;
+    DevBuf<double> beta, beta_sum, m, r, part, mu, btb, norm;
+    std::unique_ptr<bpmf_link_dense> dense;
+    std::unique_ptr<bpmf_link_sparse> sparse;
+};
+
+// posterior top-N (capi_topn.hip): ring of kept samples, fp64, column c / sample s / row k at c * max * kp + s * kp + k, and the
+// sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
+struct bpmf_ring { DevBuf<double> samples; int max = 0, count = 0, kp = 0; DevBuf<int64_t> ex_ptr; DevBuf<int32_t> ex_rows; };
+
+// adaptive noise (capi_noise.hip): the block partials | sum of bpmf_hip_train_sse
+struct bpmf_sse { DevBuf<double> part; int nblk = 0; };

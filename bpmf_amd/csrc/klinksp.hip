@@ -6,9 +6,6 @@ namespace bpmf_launch {
 
 namespace {
 
-template <typename T>
-void free_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
-
 int lanes_for(int ncw) { return ncw <= 8 ? 8 : ncw <= 16 ? 16 : ncw <= 32 ? 32 : 64; }
 
 // BPMF_LINK_WG_CHUNKS (read at every launch; the tests flip it): groups of rows / chunks one workgroup computes one after the
@@ -21,13 +18,13 @@ void rows_launch(const SpMat &m, const double *V, int64_t ldv, int n, int ncw, d
 {
     const int wgg = wg_groups();
     const int64_t per_wg = (int64_t)(256 / LPR) * wgg;
-    hipLaunchKernelGGL((bpmf::k_sp_rows<LPR>), dim3((unsigned)((m.nrows + per_wg - 1) / per_wg)), dim3(256), 0, st, m.d_ptr, m.d_idx, m.d_vals, m.nrows,
+    hipLaunchKernelGGL((bpmf::k_sp_rows<LPR>), dim3((unsigned)((m.nrows + per_wg - 1) / per_wg)), dim3(256), 0, st, m.ptr.get(), m.idx.get(), m.vals.get(), m.nrows,
                        V, ldv, n, ncw, C, ldc, lambda, P, ldp, wgg);
     if (m.nlong > 0) {
-        hipLaunchKernelGGL((bpmf::k_sp_chunks<LPR>), dim3((unsigned)((m.nchunks + per_wg - 1) / per_wg)), dim3(256), 0, st, m.d_cbeg, m.d_cend,
-                           m.nchunks, m.d_idx, m.d_vals, V, ldv, n, m.d_part, wgg);
+        hipLaunchKernelGGL((bpmf::k_sp_chunks<LPR>), dim3((unsigned)((m.nchunks + per_wg - 1) / per_wg)), dim3(256), 0, st, m.cbeg.get(), m.cend.get(),
+                           m.nchunks, m.idx.get(), m.vals.get(), V, ldv, n, m.part.get(), wgg);
         const int64_t tot = (int64_t)m.nlong * ncw;
-        hipLaunchKernelGGL(bpmf::k_sp_sum_long, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m.d_lrow, m.d_lfirst, m.nlong, m.d_part, n, ncw,
+        hipLaunchKernelGGL(bpmf::k_sp_sum_long, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m.lrow.get(), m.lfirst.get(), m.nlong, m.part.get(), n, ncw,
                            C, ldc, lambda, P, ldp);
     }
 }
@@ -87,25 +84,18 @@ int sp_upload(SpMat &m, int64_t nrows, const int64_t *ptr, const int32_t *idx, c
     }
     lfirst.push_back((int64_t)cbeg.size());
     m.nlong = (int)lrow.size(); m.nchunks = (int64_t)cbeg.size(); m.part_n = max_n;
-    int rc = dev_upload(&m.d_ptr, ptr, (size_t)nrows + 1);
-    if (!rc) rc = dev_upload(&m.d_idx, idx, (size_t)m.nnz);
-    if (!rc && vals) rc = dev_upload(&m.d_vals, vals, (size_t)m.nnz);
+    int rc = m.ptr.upload(ptr, (size_t)nrows + 1);
+    if (!rc) rc = m.idx.upload(idx, (size_t)m.nnz);
+    if (!rc && vals) rc = m.vals.upload(vals, (size_t)m.nnz);
     if (!rc && m.nlong > 0) {
-        rc = dev_upload(&m.d_lrow, lrow.data(), lrow.size());
-        if (!rc) rc = dev_upload(&m.d_lfirst, lfirst.data(), lfirst.size());
-        if (!rc) rc = dev_upload(&m.d_cbeg, cbeg.data(), cbeg.size());
-        if (!rc) rc = dev_upload(&m.d_cend, cend.data(), cend.size());
-        if (!rc) rc = dev_upload<double>(&m.d_part, nullptr, (size_t)m.nchunks * (size_t)max_n);
+        rc = m.lrow.upload(lrow.data(), lrow.size());
+        if (!rc) rc = m.lfirst.upload(lfirst.data(), lfirst.size());
+        if (!rc) rc = m.cbeg.upload(cbeg.data(), cbeg.size());
+        if (!rc) rc = m.cend.upload(cend.data(), cend.size());
+        if (!rc) rc = m.part.alloc((size_t)m.nchunks * (size_t)max_n);
     }
-    if (rc) sp_free(m);
+    if (rc) m = SpMat{};
     return rc;
-}
-
-void sp_free(SpMat &m)
-{
-    free_dev(m.d_ptr); free_dev(m.d_idx); free_dev(m.d_vals); free_dev(m.d_lrow); free_dev(m.d_lfirst); free_dev(m.d_cbeg); free_dev(m.d_cend);
-    free_dev(m.d_part);
-    m = SpMat{};
 }
 
 int sp_product(const SpMat &m, const double *V, int64_t ldv, int n, int ncw, double *C, int64_t ldc, double lambda, const double *P, int64_t ldp,
@@ -127,21 +117,14 @@ int64_t cg_blocks(int64_t D) { return (D + bpmf::kCgBlock - 1) / bpmf::kCgBlock;
 int cg_alloc(CgWork &w, int64_t N, int64_t D, int64_t ld, bool with_t)
 {
     w = CgWork{};
-    int rc = dev_upload<double>(&w.d_p, nullptr, (size_t)D * (size_t)ld);
-    if (!rc) rc = dev_upload<double>(&w.d_q, nullptr, (size_t)D * (size_t)ld);
-    if (!rc && with_t) rc = dev_upload<double>(&w.d_t, nullptr, (size_t)N * (size_t)ld);
-    if (!rc) rc = dev_upload<double>(&w.d_partial, nullptr, (size_t)cg_blocks(D) * bpmf::kCgMaxN);
-    if (!rc) rc = dev_upload<bpmf::CgState>(&w.d_state, nullptr, 1);
-    if (!rc && hipHostMalloc((void **)&w.h_word, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) rc = fail(BPMF_HIP_ENOMEM, "link: no pinned word");
-    if (rc) cg_free(w);
+    int rc = w.p.alloc((size_t)D * (size_t)ld);
+    if (!rc) rc = w.q.alloc((size_t)D * (size_t)ld);
+    if (!rc && with_t) rc = w.t.alloc((size_t)N * (size_t)ld);
+    if (!rc) rc = w.partial.alloc((size_t)cg_blocks(D) * bpmf::kCgMaxN);
+    if (!rc) rc = w.state.alloc(1);
+    if (!rc) rc = w.word.alloc(2);
+    if (rc) w = CgWork{};
     return rc;
-}
-
-void cg_free(CgWork &w)
-{
-    free_dev(w.d_p); free_dev(w.d_q); free_dev(w.d_t); free_dev(w.d_partial); free_dev(w.d_state);
-    if (w.h_word) (void)hipHostFree(w.h_word);
-    w = CgWork{};
 }
 
 int cg_solve(const SpMat &F, const SpMat &Ft, double lambda, double *x, double *r, int64_t ld, int n, int64_t D, double tol, int max_iter, CgWork &w,
@@ -155,23 +138,25 @@ int cg_solve(const SpMat &F, const SpMat &Ft, double lambda, double *x, double *
     // BPMF_LINK_CG_CHECK (read at every solve): iterations enqueued between two looks of the host at the convergence word.  A
     // column is frozen on the device the moment it converges, so the look-ahead iterations change nothing.
     const int check = std::max(1, env_int("BPMF_LINK_CG_CHECK", 4));
-    w.h_word[0] = -1;
-    hipLaunchKernelGGL(bpmf::k_cg_start, dim3(ge), dim3(256), 0, st, x, w.d_p, r, ld, D, n);
-    cg_dot(r, r, ld, D, n, w.d_partial, st);
-    hipLaunchKernelGGL(bpmf::k_cg_init, dim3(1), dim3(bpmf::kCgMaxN), 0, st, w.d_partial, nb, n, tol2, w.d_state, w.h_word);
+    double *const p = w.p.get(), *const q = w.q.get(), *const t = w.t.get(), *const partial = w.partial.get();
+    bpmf::CgState *const state = w.state.get();
+    w.word.host()[0] = -1;
+    hipLaunchKernelGGL(bpmf::k_cg_start, dim3(ge), dim3(256), 0, st, x, p, r, ld, D, n);
+    cg_dot(r, r, ld, D, n, partial, st);
+    hipLaunchKernelGGL(bpmf::k_cg_init, dim3(1), dim3(bpmf::kCgMaxN), 0, st, partial, nb, n, tol2, state, w.word.dev());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     int done = 0;
-    while (done < max_iter && __atomic_load_n(&w.h_word[0], __ATOMIC_ACQUIRE) != 0) {
+    while (done < max_iter && __atomic_load_n(&w.word.host()[0], __ATOMIC_ACQUIRE) != 0) {
         const int batch = std::min(check, max_iter - done);
         for (int b = 0; b < batch; ++b) {
-            if (sp_product(F, w.d_p, ld, n, n, w.d_t, ld, 0.0, nullptr, 0, st)) return bad();             // t = F p
-            if (sp_product(Ft, w.d_t, ld, n, n, w.d_q, ld, lambda, w.d_p, ld, st)) return bad();          // q = F^T t + lambda p
-            cg_dot(w.d_p, w.d_q, ld, D, n, w.d_partial, st);
-            hipLaunchKernelGGL(bpmf::k_cg_alpha, dim3(1), dim3(bpmf::kCgMaxN), 0, st, w.d_partial, nb, n, w.d_state);
-            cg_xr(x, r, w.d_p, w.d_q, ld, D, n, w.d_state, w.d_partial, st);
-            hipLaunchKernelGGL(bpmf::k_cg_beta, dim3(1), dim3(bpmf::kCgMaxN), 0, st, w.d_partial, nb, n, tol2, w.d_state, w.h_word);
-            hipLaunchKernelGGL(bpmf::k_cg_p, dim3(ge), dim3(256), 0, st, w.d_p, r, ld, D, n, w.d_state);
+            if (sp_product(F, p, ld, n, n, t, ld, 0.0, nullptr, 0, st)) return bad();                        // t = F p
+            if (sp_product(Ft, t, ld, n, n, q, ld, lambda, p, ld, st)) return bad();                   // q = F^T t + lambda p
+            cg_dot(p, q, ld, D, n, partial, st);
+            hipLaunchKernelGGL(bpmf::k_cg_alpha, dim3(1), dim3(bpmf::kCgMaxN), 0, st, partial, nb, n, state);
+            cg_xr(x, r, p, q, ld, D, n, state, partial, st);
+            hipLaunchKernelGGL(bpmf::k_cg_beta, dim3(1), dim3(bpmf::kCgMaxN), 0, st, partial, nb, n, tol2, state, w.word.dev());
+            hipLaunchKernelGGL(bpmf::k_cg_p, dim3(ge), dim3(256), 0, st, p, r, ld, D, n, state);
         }
         done += batch;
         HIP_TRY(hipGetLastError());
@@ -179,7 +164,7 @@ int cg_solve(const SpMat &F, const SpMat &Ft, double lambda, double *x, double *
     }
     if (res) {
         bpmf::CgState hs;
-        HIP_TRY(hipMemcpy(&hs, w.d_state, sizeof hs, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&hs, state, sizeof hs, hipMemcpyDeviceToHost));
         *res = CgResult{};
         for (int k = 0; k < n; ++k) {
             res->iters[k] = hs.iters[k];

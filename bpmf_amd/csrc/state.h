@@ -51,6 +51,8 @@ inline int dev_upload(T **dst, const T *src, size_t n)
     return 0;
 }
 
+#include "ext_state.h"      // DevBuf and the owned state of the add-ons (uses fail / HIP_TRY above)
+
 namespace blob = bpmf::blob;      // the layouts of the parameter / result / reduction blobs (blob.h)
 
 inline int env_int(const char *name, int dflt)
@@ -208,29 +210,12 @@ struct bpmf_hip_side {
     struct bpmf_hip_test *deferred_eval = nullptr;      // evaluation waiting for this side's next gate kernel (flush_deferred)
     double *d_aggr_mu = nullptr, *d_aggr_lambda = nullptr;   // -o: aggrMu (K x nloc) / aggrLambda (K*K x nloc) of the local columns
     double *d_prop = nullptr;            // propagated posterior (-m / -l): K x K prior precision per local column, or NULL
-    // posterior top-N (capi_topn.hip): ring of kept samples, fp64, column c / sample s / row k at c * ring_max * ring_kp + s * ring_kp + k,
-    // and the sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
-    double *d_ring = nullptr; int ring_max = 0, ring_count = 0, ring_kp = 0;
-    int64_t *d_ex_ptr = nullptr; int32_t *d_ex_rows = nullptr;
-    // adaptive noise (capi_noise.hip): device copy of the column pointers and the partials | sum of bpmf_hip_train_sse
-    int64_t *d_sse_colptr = nullptr; double *d_sse_part = nullptr; int sse_nblk = 0;
-    // probit likelihood (capi_probit.hip): d_probit_z != NULL marks a probit side.  The latent scores (layout of d_vals; the
-    // samplers read them in its place), the sign of every rating, the column pointers on the device, and a pinned word the
-    // latent kernel raises (to a rating position) when a draw runs into its attempt cap (~0: none)
-    double *d_probit_z = nullptr; int8_t *d_probit_sign = nullptr; int64_t *d_probit_colptr = nullptr;
-    unsigned long long *h_probit_fail = nullptr, *h_probit_fail_dev = nullptr;
-    uint32_t probit_tag = 0;
-    // side information (capi_link.hip): d_link_f != NULL marks a side with features.  F (ncols x D, row-major),
-    // W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld), beta (D x ld), the offsets M = F beta in the
-    // factors' layout, the residual ratings the samplers read in place of d_vals, the partials of the long-dimension product, and
-    // small staging arrays.  link_in_call: bpmf_hip_link_sample is driving the stateless half-iteration of this side.
-    int link_d = 0; double link_lambda = 0.0; uint32_t link_tag = 0; bool link_in_call = false;
-    double *d_link_f = nullptr, *d_link_w = nullptr, *d_link_pe = nullptr, *d_link_beta = nullptr, *d_link_m = nullptr, *d_link_r = nullptr;
-    double *d_link_part = nullptr, *d_link_mu = nullptr, *d_link_btb = nullptr, *d_link_norm = nullptr, *d_link_beta_sum = nullptr;
-    int64_t *d_link_colptr = nullptr; int link_nsum = 0;
-    // sparse features (capi_link_sparse.hip): F compressed both ways and the work arrays of the CG draw of beta;
-    // d_link_f is then a one-word placeholder, d_link_w / d_link_pe stay NULL
-    struct bpmf_link_sparse *link_sp = nullptr;
+    // the add-ons (ext_state.h), each NULL until its entry point attaches it; released in bpmf_hip_side_destroy
+    std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
+    std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
+    std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
+    std::unique_ptr<bpmf_sse> sse;         // partials of the training residuals (bpmf_hip_train_sse)
+    DevBuf<int64_t> d_colptr;              // the column pointers on the device, uploaded when an add-on first needs them (ensure_colptr)
     bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
@@ -384,10 +369,11 @@ inline int check_timeout(double *h_blob, int K, std::string *msg)
 // probit: did a latent draw of this side run into its attempt cap?  Checked where a half-iteration's results are collected.
 inline int check_probit(bpmf_hip_side *s, std::string *msg)
 {
-    if (!s->h_probit_fail) return 0;
-    const unsigned long long v = __atomic_load_n(s->h_probit_fail, __ATOMIC_ACQUIRE);
+    if (!s->probit) return 0;
+    unsigned long long *word = s->probit->fail.host();
+    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
     if (v == ~0ull) return 0;
-    __atomic_store_n(s->h_probit_fail, ~0ull, __ATOMIC_RELEASE);
+    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
     *msg = "probit: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
     return BPMF_HIP_ENUM;
 }

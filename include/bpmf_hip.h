@@ -58,6 +58,9 @@ typedef struct bpmf_hip_test bpmf_hip_test;   /* test matrix T with Pavg / Pm2  
 /* message of the last failing call on this thread */
 BPMF_API const char *bpmf_hip_last_error(void);
 BPMF_API int bpmf_hip_abi_version(void);
+/* diagnostic: device bytes the add-ons of all sides of this process own right now (probit, features, sample rings, residual partials,
+ * the temporaries of their calls): hipMemGetInfo counts the whole card, other processes included */
+BPMF_API int64_t bpmf_hip_live_device_bytes(void);
 /* 1 if a context of num_latent K (BPMF_NUMLATENT, c++/bpmf.h:22-24,53: the reference ships bpmf-8 ... bpmf-128 incl. 10, 20 ... 100,
  * ci/multilatent.sh:5) can be created in fp64: 1 <= K <= 128.  The kernels are instantiated for 8, 16, 32, 64, 128; any other K
  * runs on the next instantiated size (bpmf_hip_kernel_k) with zero factor rows and an identity block of the prior precision in
