@@ -78,6 +78,11 @@ _SIGNATURES = {
     "bpmf_hip_side_link_shift": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "bpmf_hip_link_gemm_tn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_link_gemm_nn": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bpmf_hip_link_lambda_sample": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int, C.c_uint, C.POINTER(C.c_double)]),
+    "bpmf_hip_side_link_lambda_prior": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "bpmf_hip_side_link_lambda_set": (C.c_int, [C.c_void_p, C.c_double]),
+    "bpmf_hip_side_link_lambda_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "bpmf_hip_link_chol_solve": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_set_features_sparse": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_uint]),
     "bpmf_hip_side_link_cg_set": (C.c_int, [C.c_void_p, C.c_double, C.c_int]),
     "bpmf_hip_side_link_cg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int)]),

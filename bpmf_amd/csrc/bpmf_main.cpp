@@ -26,6 +26,8 @@
 // dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
 // -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).  A sparse FILE (.sdm / .sbm /
 // coordinate .mtx) of any width takes the CG draw of DESIGN.md section 14 (bpmf_hip_side_set_features_sparse; --link-tol, --link-max-iter).
+// --lambda-beta-prior A0,B0: lambda_beta is sampled per side with features (bpmf_hip_side_link_lambda_prior), one
+// more header line names the prior, and -o DIR also gets DIR/lambda_beta.csv (iteration,lambda_rows,lambda_cols).
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -100,6 +102,10 @@ void usage()
               << "  [--link-tol F] [--link-max-iter N]: the stopping rule of that CG draw: relative residual (1e-6), most iterations (1000);\n"
               << "              need a sparse feature file\n"
               << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
+              << "  [--lambda-beta-prior A0,B0]: sample lambda_beta per side with features from its Gamma conditional, prior shape A0 > 0 and\n"
+              << "              rate B0 >= 0 (5e-4,5e-4 is a weak default, not a tuned number); --lambda-beta is then the initial value.  The\n"
+              << "              first draws are large (the chain starts at beta = 0): give the burn-in (-b) some tens of iterations.  With\n"
+              << "              -o DIR the value every iteration used goes to DIR/lambda_beta.csv (iteration,lambda_rows,lambda_cols)\n"
               << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
@@ -248,6 +254,8 @@ struct Job {
     double auc = NAN, brier = NAN;
     Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
     double lambda_beta = 5.0;                                        // --lambda-beta F
+    bool lb_sampled = false; double lb_a0 = 5e-4, lb_b0 = 5e-4;      // --lambda-beta-prior A0,B0: lambda_beta is sampled
+    std::vector<double> lb_trace_u, lb_trace_m;                      // the lambda_beta every half-iteration used (-o: DIR/lambda_beta.csv)
     Csc sfeat_u, sfeat_m;                                            // the same from a sparse file: F^T column-compressed = F by rows (D x N)
     int64_t sfeat_u_d = 0, sfeat_m_d = 0;                            // their D (0: none)
     double link_tol = 1e-6; int link_max_iter = 1000;                // --link-tol F / --link-max-iter N (sparse features: the CG draw)
@@ -314,6 +322,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
     else if (J.has_feat_m()) check(bpmf_hip_side_set_features(movies, J.feat_m.data.data(), (int)J.feat_m.ncols, 0, J.lambda_beta, 3));
     if (J.sfeat_u_d > 0) set_sparse(users, J.sfeat_u, J.sfeat_u_d, 4);
     else if (J.has_feat_u()) check(bpmf_hip_side_set_features(users, J.feat_u.data.data(), (int)J.feat_u.ncols, 0, J.lambda_beta, 4));
+    if (J.lb_sampled) {
+        if (J.has_feat_m()) check(bpmf_hip_side_link_lambda_prior(movies, J.lb_a0, J.lb_b0));
+        if (J.has_feat_u()) check(bpmf_hip_side_link_lambda_prior(users, J.lb_a0, J.lb_b0));
+    }
     if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
         check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
         check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
@@ -384,6 +396,9 @@ void rank_main(Job &J, int rank, std::ostream &os)
         else if (J.has_feat_m()) os << " column features D = " << J.feat_m.ncols << ",";
         if (J.sfeat_u_d > 0 || J.sfeat_m_d > 0) os << " CG tol = " << J.link_tol << " max_iter = " << J.link_max_iter << ",";
         os << " lambda_beta = " << J.lambda_beta << "; blocking loop (bpmf_hip_link_sample)" << std::endl;
+        if (J.lb_sampled)
+            os << "lambda_beta: sampled per side, prior Gamma(shape " << J.lb_a0 << ", rate " << J.lb_b0 << "), initial value " << J.lambda_beta
+               << std::endl;
     }
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
@@ -491,6 +506,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
                 cg_warned = true;
             }
         }
+        if (J.lb_sampled) {
+            double lam = 0.0;
+            if (J.has_feat_u()) { check(bpmf_hip_side_link_lambda_get(users, &lam, nullptr, nullptr)); J.lb_trace_u.push_back(lam); }
+            if (J.has_feat_m()) { check(bpmf_hip_side_link_lambda_get(movies, &lam, nullptr, nullptr)); J.lb_trace_m.push_back(lam); }
+        }
         if (linked && iter >= burnin) {
             if (J.has_feat_u()) check(bpmf_hip_side_link_add(users));
             if (J.has_feat_m()) check(bpmf_hip_side_link_add(movies));
@@ -582,8 +602,9 @@ int main(int argc, char *argv[])
                                               {"row-features", required_argument, nullptr, 1008}, {"col-features", required_argument, nullptr, 1009},
                                               {"lambda-beta", required_argument, nullptr, 1010},
                                               {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
+                                              {"lambda-beta-prior", required_argument, nullptr, 1013},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -601,6 +622,7 @@ int main(int argc, char *argv[])
         case 1010: lambda_beta = optarg; break;
         case 1011: link_tol = optarg; break;
         case 1012: link_max_iter = optarg; break;
+        case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -673,6 +695,17 @@ int main(int argc, char *argv[])
     // --row-features / --col-features / --lambda-beta: checked before anything touches a GPU
     const bool linked = !row_features.empty() || !col_features.empty();
     if (!lambda_beta.empty() && !linked) die("--lambda-beta needs --row-features or --col-features");
+    if (J.lb_sampled) {
+        if (!linked) die("--lambda-beta-prior needs --row-features or --col-features");
+        const char *s0 = lambda_beta_prior.c_str();
+        char *e1 = nullptr, *e2 = nullptr;
+        J.lb_a0 = strtod(s0, &e1);
+        if (e1 == s0 || *e1 != ',') die("--lambda-beta-prior expects A0,B0, not '" + lambda_beta_prior + "'");
+        J.lb_b0 = strtod(e1 + 1, &e2);
+        if (e2 == e1 + 1 || *e2 != '\0') die("--lambda-beta-prior expects A0,B0, not '" + lambda_beta_prior + "'");
+        if (!(J.lb_a0 > 0.0) || !(J.lb_b0 >= 0.0) || !std::isfinite(J.lb_a0) || !std::isfinite(J.lb_b0))
+            die("--lambda-beta-prior expects a shape A0 > 0 and a rate B0 >= 0, not '" + lambda_beta_prior + "'");
+    }
     auto sparse_file = [](const std::string &name) {
         if (name.empty()) return false;
         const bpmf::io::FileType ft = bpmf::io::file_type(name);
@@ -909,6 +942,21 @@ int main(int argc, char *argv[])
                         (long long)((pc.empty() ? c : pc[(size_t)c]) + 1), J.topn_mean[at], J.topn_std[at]);
             }
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
+    }
+
+    if (J.lb_sampled && !J.odirname.empty()) {                       // a cell is empty where a side has no features
+        FILE *f = fopen((J.odirname + "/lambda_beta.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/lambda_beta.csv");
+        fprintf(f, "iteration,lambda_rows,lambda_cols\n");
+        const size_t n = std::max(J.lb_trace_u.size(), J.lb_trace_m.size());
+        for (size_t i = 0; i < n; ++i) {
+            fprintf(f, "%zu,", i);
+            if (i < J.lb_trace_u.size()) fprintf(f, "%.17g", J.lb_trace_u[i]);
+            fprintf(f, ",");
+            if (i < J.lb_trace_m.size()) fprintf(f, "%.17g", J.lb_trace_m[i]);
+            fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/lambda_beta.csv");
     }
 
     if (J.adaptive && !J.odirname.empty()) {

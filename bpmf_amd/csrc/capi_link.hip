@@ -4,6 +4,7 @@
 // (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
 #include "capi_internal.h"
 #include "link_sparse.h"
+#include "link_lambda.h"
 
 using namespace bpmf_capi;
 
@@ -120,6 +121,12 @@ int check_pair(const char *who, const bpmf_hip_side *self, const bpmf_hip_side *
 
 namespace bpmf_capi {
 
+int link_tn_product(const double *A, int64_t lda, const double *B, int64_t ldb, const double *bvec, int64_t N, int D, int n, double *C,
+                    int64_t ldc, double *part, hipStream_t st)
+{
+    return tn_product(A, lda, B, ldb, bvec, N, D, n, C, ldc, part, st);
+}
+
 int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, unsigned tag, size_t part_words, std::unique_ptr<bpmf_link> *out)
 {
     const std::string w(who);
@@ -221,12 +228,14 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
     hipStream_t st = c->stream;
     std::vector<double> mu((size_t)Kt), LU((size_t)Kt * Kt), LF((size_t)Kt * Kt), scatter;
 
-    // 1. hyper-parameters: the link's scatter lambda_beta beta^T beta (K x K, formed on the device) and its D degrees of freedom
+    // 1. hyper-parameters: the link's scatter lambda_beta beta^T beta (K x K, formed on the device) and its D degrees of freedom.
+    // 0. (a side that samples lambda_beta, section 15) lambda_beta | beta, Lambda first, from the same beta^T beta
     if (link) {
         scatter.assign((size_t)Kt * Kt, 0.0);
         if ((rc = tn_product(L->beta.get(), K, L->beta.get(), K, nullptr, D, Kt, Kt, L->btb.get(), Kt, L->part.get(), st))) return rc;
         if ((rc = bounded_stream_sync(c, st, __func__))) return rc;
         HIP_TRY(hipMemcpy(scatter.data(), L->btb.get(), scatter.size() * sizeof(double), hipMemcpyDeviceToHost));
+        if (L->sample_lambda && (rc = link_lambda_draw(self, scatter.data(), iter))) return rc;
         for (double &v : scatter) v *= L->lambda;
     }
     rc = bpmf_hyper_sample_ex(Kt, N, self->cov.data(), nullptr, link ? scatter.data() : nullptr, link ? D : 0, (uint32_t)iter, mu.data(), LU.data(),
@@ -256,7 +265,10 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
         }
         HIP_TRY(hipMemcpyAsync(L->dense->PE.get() + (size_t)D * K, E.data(), E.size() * sizeof(double), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                              // (the host buffers above go out of use here)
-        if ((rc = nn_product(L->dense->W.get(), 2 * D, L->dense->PE.get(), K, D, 2 * D, Kt, L->beta.get(), K, K, st))) return rc;
+        if (L->dense->devfac) {                                         // beta = L^-T (L^-1 P + E), G(lambda_beta) = L L^T factored on the device
+            if ((rc = link_chol_draw(self))) return rc;
+        } else if ((rc = nn_product(L->dense->W.get(), 2 * D, L->dense->PE.get(), K, D, 2 * D, Kt, L->beta.get(), K, K, st)))
+            return rc;
         // 3. offsets, 4. residuals: from the copy of the other side's factors the sampler below reads
         if ((rc = offsets_update(self))) return rc;
         if ((rc = residual_enqueue(self, other, L->r.get()))) return rc;

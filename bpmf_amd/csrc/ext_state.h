@@ -1,6 +1,7 @@
 // ext_state.h -- what the add-ons of a side own on the device (included by state.h): bpmf_hip_side holds one owning pointer per
 // add-on, NULL while the side has none; everything below is released when that pointer is reset.
 #pragma once
+#include <limits>
 #include <memory>
 
 #include "devbuf.h"
@@ -36,7 +37,14 @@ struct CgWork {
 struct bpmf_probit { DevBuf<double> z; DevBuf<int8_t> sign; Pinned<unsigned long long> fail; uint32_t tag = 0; };
 
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
-struct bpmf_link_dense { DevBuf<double> F, W, PE; };
+struct bpmf_link_dense {
+    DevBuf<double> F, W, PE;
+    // device-factor mode (capi_link_lambda.hip; W is released): F^T F (D x D), the padded factor of
+    // F^T F + fact_lambda I with its inverted diagonal blocks, the padded right-hand sides, the pivot flag
+    bool devfac = false; double fact_lambda = 0.0;
+    DevBuf<double> FtF, Lp, Linv, LinvT, Xp, Ep;
+    DevBuf<int> flag;
+};
 
 // sparse features (capi_link_sparse.hip): F compressed both ways, the work arrays of the CG draw of beta, its
 // right-hand side / residual (D x K) and R^-1 (Kt x Kt), the settings and the statistics of the solves
@@ -51,8 +59,11 @@ struct bpmf_link_sparse {
 // side information: beta (D x ld) and its running sum, the offsets M = F beta in the factors' layout, the
 // residual ratings the samplers read in place of d_vals, staging arrays, and the features as exactly one of dense / sparse.
 // in_call: bpmf_hip_link_sample is driving the stateless half-iteration of this side.
+// sample_lambda: lambda is drawn at the start of every half-iteration but the side's first from Gamma(a0 + D K / 2, b0 + trace / 2)
+// (DESIGN.md section 15); trace_last: the trace of the newest draw (NaN before it).
 struct bpmf_link {
     int D = 0; double lambda = 0.0; uint32_t tag = 0; int nsum = 0; bool in_call = false;
+    bool sample_lambda = false; double a0 = 0.0, b0 = 0.0, trace_last = std::numeric_limits<double>::quiet_NaN();
     DevBuf<double> beta, beta_sum, m, r, part, mu, btb, norm;
     std::unique_ptr<bpmf_link_dense> dense;
     std::unique_ptr<bpmf_link_sparse> sparse;

@@ -458,3 +458,28 @@ extern "C" int bpmf_hip_noise_sample(double a0, double b0, double sse, int64_t n
     *alpha = a;
     return BPMF_HIP_OK;
 }
+
+// The link precision of a side with features: lambda = g / (b0 + trace / 2), g ~ Gamma(a0 + count / 2, 1) on the
+// Philox stream BPMF_LINK_LAMBDA_COUNTER(iter, tag), key word 1 = 0 as above: g depends on the shape and the counter only, so lambda
+// is a smooth function of the trace.
+extern "C" int bpmf_hip_link_lambda_sample(double a0, double b0, double trace, int64_t count, int iter, unsigned tag, double *lambda)
+{
+    if (!lambda || !(a0 > 0.0) || !(b0 >= 0.0) || !std::isfinite(a0) || !std::isfinite(b0) || count <= 0 || !(trace >= 0.0) ||
+        !std::isfinite(trace)) {
+        bpmf_hip_set_error_("link_lambda_sample: needs a0 > 0, b0 >= 0, count > 0 and a finite trace >= 0");
+        return BPMF_HIP_EINVAL;
+    }
+    if (tag < 1 || tag > 15 || iter < 0 || iter >= (1 << 27)) {
+        bpmf_hip_set_error_("link_lambda_sample: needs 1 <= tag <= 15 and 0 <= iter < 2^27 (the counter range of the lambda_beta streams)");
+        return BPMF_HIP_EINVAL;
+    }
+    const double rate = b0 + 0.5 * trace;
+    if (!(rate > 0.0)) {
+        bpmf_hip_set_error_("link_lambda_sample: b0 = 0 and trace = 0 leave the Gamma posterior without a rate");
+        return BPMF_HIP_EINVAL;
+    }
+    bpmf::MicroPhilox rng(BPMF_LINK_LAMBDA_COUNTER(iter, tag));
+    const double g = std::gamma_distribution<>(a0 + 0.5 * (double)count)(rng);
+    *lambda = g / rate;
+    return BPMF_HIP_OK;
+}

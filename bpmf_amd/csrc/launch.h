@@ -191,4 +191,21 @@ int link_residual(const LinkResidualLaunch &p, hipStream_t st);
 int link_shift_blocks(int64_t total);
 void link_shift(double *items, const double *offs, int64_t total, double *partial, hipStream_t st);   // partial: link_shift_blocks(total) doubles
 
+// the device factorisation of G(lambda) = F^T F + lambda I and the draw of beta against it (kernels_link_chol.h, klinkchol.hip).
+// Work arrays: Lp (dp x dp doubles, dp = link_chol_dp(D)), Linv and LinvT (dp x 64 each), Xp and Ep (dp x 128 each), flag (one int,
+// raised by a pivot that is not positive and finite; the caller zeroes and collects it).
+struct LinkCholLaunch {                                    // Lp = the factor of [FtF + lambda I, 0; 0, I]
+    const double *FtF; int D; double lambda;               // D x D, row-major
+    double *Lp, *Linv, *LinvT; int *flag;
+};
+struct LinkCholSolveLaunch {                               // out (D x ncw, leading dimension ldo) = L^-T (L^-1 P + E), columns n .. ncw - 1 zero
+    const double *Lp, *Linv, *LinvT; int D;
+    const double *P; int64_t ldp; const double *E; int64_t lde; int n;   // D x n (n <= 128); E may be NULL
+    double *Xp, *Ep;
+    double *out; int64_t ldo; int ncw;                     // n <= ncw <= 128
+};
+int link_chol_dp(int D);
+int link_chol_factor(const LinkCholLaunch &p, hipStream_t st);         // -1: shape not supported (nothing launched)
+int link_chol_solve(const LinkCholSolveLaunch &p, hipStream_t st);
+
 }  // namespace bpmf_launch

@@ -329,6 +329,26 @@ class HipEngine:
         """The blocking half-iteration of a model with side information (both sides go through it; include/bpmf_hip.h)."""
         _lib.check(self.lib.bpmf_hip_link_sample(side.handle, other.handle, float(alpha)))
 
+    def link_lambda_prior(self, side, a0=5e-4, b0=5e-4):
+        """Switches the sampling of the side's lambda_beta on: prior Gamma(shape a0, rate b0), one draw at the start of every
+        half-iteration but the side's first.  Only before the side's first half-iteration.  A side with
+        dense features factors G(lambda_beta) on the device from then on."""
+        _lib.check(self.lib.bpmf_hip_side_link_lambda_prior(side.handle, float(a0), float(b0)))
+
+    def link_lambda_set(self, side, lam):
+        """Sets lambda_beta for the following draws of beta (a chain continued from stored state; tests).  A side with dense
+        features factors G(lambda_beta) on the device from then on; without a prior the value stays fixed."""
+        _lib.check(self.lib.bpmf_hip_side_link_lambda_set(side.handle, float(lam)))
+
+    def link_lambda_get(self, side):
+        """(lambda_beta, the trace tr(Lambda beta^T beta) of its newest draw or NaN, whether it is sampled)."""
+        lam, tr, on = C.c_double(), C.c_double(), C.c_int()
+        _lib.check(self.lib.bpmf_hip_side_link_lambda_get(side.handle, C.byref(lam), C.byref(tr), C.byref(on)))
+        return lam.value, tr.value, bool(on.value)
+
+    def link_chol_solve(self, A, P, E=None, want_factor=False):
+        return link_chol_solve(A, P, E, want_factor, self.device)
+
     def link_cg_set(self, side, tol=1e-6, max_iter=1000):
         """The stopping rule of the CG draw of a side with sparse features: relative residual tol, at most max_iter iterations."""
         _lib.check(self.lib.bpmf_hip_side_link_cg_set(side.handle, float(tol), int(max_iter)))
@@ -488,6 +508,21 @@ def noise_sample(a0, b0, sse, n, it, alpha_max=None):
     return out.value
 
 
+def link_lambda_counter(it, tag):
+    """BPMF_LINK_LAMBDA_COUNTER(it, tag) of include/bpmf_hip.h: the Philox stream of the lambda_beta draw of half-iteration `it`."""
+    return (0x80000000 + 16 * int(it) + (int(tag) & 15)) & 0xFFFFFFFF
+
+
+def link_lambda_sample(a0, b0, trace, count, it, tag):
+    """bpmf_hip_link_lambda_sample (host only): g / (b0 + trace / 2), g ~ Gamma(a0 + count / 2, 1) on the Philox stream
+    BPMF_LINK_LAMBDA_COUNTER(it, tag).  count = D K, trace = tr(Lambda beta^T beta)."""
+    if int(tag) < 0:
+        raise ValueError("link_lambda_sample: tag must be 1 .. 15")
+    out = C.c_double()
+    _lib.check(_lib.load_library().bpmf_hip_link_lambda_sample(float(a0), float(b0), float(trace), int(count), int(it), int(tag), C.byref(out)))
+    return out.value
+
+
 def auc(score, value, threshold=0.5):
     """bpmf_hip_auc (host only): area under the ROC curve of `score` against the labels value > threshold, ties counted half;
     NaN when one class is empty."""
@@ -557,6 +592,22 @@ def link_gemm_nn(A, B, device=0):
     out = np.empty((N, B.shape[1]))
     _lib.check(_lib.load_library().bpmf_hip_link_gemm_nn(int(device), _ptr(A), N, D, _ptr(B), B.shape[1], _ptr(out)))
     return out
+
+
+def link_chol_solve(A, P, E=None, want_factor=False, device=0):
+    """X = L^-T (L^-1 P + E) with A = L L^T, by the blocked Cholesky and the two blocked triangular solves of kernels_link_chol.h
+    (A: D x D symmetric positive definite, D <= 1024; P, E: D x n, n <= 128).  Returns X, or (X, L) with want_factor.  Row-major
+    fp64 host arrays; tests and tools."""
+    A = np.ascontiguousarray(A, np.float64); P = np.ascontiguousarray(P, np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or P.ndim != 2 or P.shape[0] != A.shape[0]:
+        raise ValueError("link_chol_solve: A must be [D, D] and P [D, n]")
+    Ec = np.ascontiguousarray(E, np.float64) if E is not None else None
+    if Ec is not None and Ec.shape != P.shape:
+        raise ValueError("link_chol_solve: E must have the shape of P")
+    D, n = P.shape
+    X = np.empty((D, n)); Lo = np.empty((D, D)) if want_factor else None
+    _lib.check(_lib.load_library().bpmf_hip_link_chol_solve(int(device), _ptr(A), D, _ptr(P), _ptr(Ec), n, _ptr(X), _ptr(Lo)))
+    return (X, Lo) if want_factor else X
 
 
 def _is_sparse(F):

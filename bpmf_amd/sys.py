@@ -185,7 +185,7 @@ class Sys:
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
-          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000):
+          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -226,7 +226,14 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     A scipy.sparse feature matrix (any D) takes the CG path of DESIGN.md section 14: beta is drawn by conjugate gradients on the
     device to the relative residual link_tol in at most link_max_iter iterations.  res["link_cg_iters"]: per iteration the CG
     iterations of (movies, users), None for a side without sparse features; res["link_cg_hit_max_iter"]: whether any draw ran
-    into link_max_iter.  A dense ndarray keeps the dense path; nothing is converted either way."""
+    into link_max_iter.  A dense ndarray keeps the dense path; nothing is converted either way.
+
+    lambda_beta_prior=(A0, B0): lambda_beta is sampled too, per side with features: prior Gamma(shape A0,
+    rate B0), conditional Gamma(A0 + D K / 2, B0 + tr(Lambda beta^T beta) / 2), drawn at the start of every half-iteration but
+    the first, for which `lambda_beta` is the initial value.  (5e-4, 5e-4) is a weak default, not a tuned number.  The chain
+    starts at beta = 0, so the first draws are large (10^2 .. 10^3) and take tens of iterations to come down: the burn-in has to
+    cover that.  res["lambda_beta_rows"] / res["lambda_beta_cols"]: the value each half-iteration used, one per iteration (None
+    for a side without features).  None (the default): lambda_beta stays fixed and nothing changes."""
     linked = row_features is not None or col_features is not None
     if linked:
         if pipelined:
@@ -239,6 +246,15 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             raise ValueError("lambda_beta must be positive and finite")
         if not (0.0 < float(link_tol) < 1.0) or int(link_max_iter) < 1:
             raise ValueError("link_tol must lie in (0, 1) and link_max_iter must be >= 1")
+    if lambda_beta_prior is not None:
+        if not linked:
+            raise ValueError("lambda_beta_prior needs row_features or col_features")
+        try:
+            lb_a0, lb_b0 = (float(v) for v in lambda_beta_prior)
+        except (TypeError, ValueError):
+            raise ValueError("lambda_beta_prior must be a pair (A0, B0)")
+        if not (lb_a0 > 0 and lb_b0 >= 0 and math.isfinite(lb_a0) and math.isfinite(lb_b0)):
+            raise ValueError("lambda_beta_prior = (A0, B0) needs a finite A0 > 0 and a finite B0 >= 0")
     if topn is not None and nsims - burnin < 1:
         raise ValueError("topn needs at least one post-burn-in sample (nsims > burnin)")
     if noise not in ("fixed", "adaptive"):
@@ -272,6 +288,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         sparse_sides = [sd for sd, F in ((movies, col_features), (users, row_features)) if F is not None and _engine._is_sparse(F)]
         for sd in sparse_sides:
             engine.link_cg_set(sd.side, link_tol, link_max_iter)
+        if lambda_beta_prior is not None:
+            for sd, F in ((movies, col_features), (users, row_features)):
+                if F is not None:
+                    engine.link_lambda_prior(sd.side, lb_a0, lb_b0)
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
@@ -282,6 +302,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if linked and sparse_sides:
         res["link_cg_iters"] = []
         res["link_cg_hit_max_iter"] = False
+    if lambda_beta_prior is not None:
+        res["lambda_beta_rows"] = [] if row_features is not None else None
+        res["lambda_beta_cols"] = [] if col_features is not None else None
 
     def keep(i):                                     # where the -o aggregation sits (bpmf_main.cpp)
         if topn is not None and i >= burnin:
@@ -294,6 +317,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
                 engine.link_add(movies.side)
             if row_features is not None:
                 engine.link_add(users.side)
+        if lambda_beta_prior is not None:
+            if col_features is not None:
+                res["lambda_beta_cols"].append(engine.link_lambda_get(movies.side)[0])
+            if row_features is not None:
+                res["lambda_beta_rows"].append(engine.link_lambda_get(users.side)[0])
         if linked and sparse_sides:
             st = [engine.link_cg_stats(sd.side) if sd in sparse_sides else None for sd in (movies, users)]
             res["link_cg_iters"].append(tuple(None if t is None else t["iters_last"] for t in st))

@@ -410,6 +410,39 @@ BPMF_API int bpmf_hip_link_cg_solve(int device, int64_t N, int D, const int64_t 
                                     const double *RHS, int n, double tol, int max_iter, double *X, int *iters, int *hit_max_iter);
 BPMF_API int bpmf_hip_link_noise_rows(int device, int64_t nrows, int K, uint32_t it, uint32_t key_word, const double *Rinv, double *out);
 
+/* ---- a sampled link precision lambda_beta --------------------------
+ * Opt-in per side, on a side with dense or sparse features.  Prior lambda_beta ~ Gamma(shape a0, rate b0); conditional
+ *     lambda_beta | beta, Lambda ~ Gamma(a0 + D K / 2, b0 + t / 2),   t = tr(Lambda beta^T beta) = |beta R^T|_F^2,  Lambda = R^T R,
+ * K = num_latent.  bpmf_hip_link_sample draws it at the START of a half-iteration `iter`, before step 1, from the beta of the
+ * side's previous half-iteration and the Lambda that beta was drawn under; everything after it (the scatter, G(lambda_beta), the
+ * sparse operator) uses the new value.  At the side's first half-iteration there is no draw: the lambda_beta given to
+ * bpmf_hip_side_set_features* is used.
+ *
+ * Host only: *lambda = g / (b0 + trace / 2), g ~ Gamma(a0 + count / 2, 1) drawn with libstdc++'s gamma_distribution on the Philox
+ * stream BPMF_LINK_LAMBDA_COUNTER(iter, tag), key word 1 = 0: the middle of the counter range, apart from the hyper-parameter
+ * streams (counting up from 0) and the noise streams (counting down from 2^32 - 1) while iter < 2^27.  BPMF_HIP_EINVAL for
+ * a0 <= 0, b0 < 0, non-finite values, count <= 0, a negative trace, tag outside 1 .. 15, iter outside [0, 2^27), or b0 = trace = 0. */
+#define BPMF_LINK_LAMBDA_COUNTER(iter, tag) (0x80000000u + 16u * (uint32_t)(iter) + ((uint32_t)(tag) & 15u))
+BPMF_API int bpmf_hip_link_lambda_sample(double a0, double b0, double trace, int64_t count, int iter, unsigned tag, double *lambda);
+/* Switches the sampling of lambda_beta on, with the prior Gamma(a0, b0).  Only before the side's first half-iteration.  A side with
+ * dense features enters DEVICE-FACTOR MODE: F^T F is formed once on the device and kept; every half-iteration forms
+ * G = F^T F + lambda_beta I, factors it G = L L^T by a blocked Cholesky on the device and draws beta = L^-T (L^-1 P + E) by two
+ * blocked triangular solves (P, E as in step 2 of bpmf_hip_link_sample); W = [G^-1 | L_G^-T] is released.  A non-positive or
+ * non-finite pivot makes that bpmf_hip_link_sample fail with BPMF_HIP_ENUM.
+ * BPMF_HIP_EINVAL: no features on the side, a0 <= 0, b0 < 0, non-finite values, a tag above 15 (given to set_features*), or a side
+ * that has been stepped. */
+BPMF_API int bpmf_hip_side_link_lambda_prior(bpmf_hip_side *side, double a0, double b0);
+/* Sets lambda_beta (> 0, finite) for the following draws of beta: a chain continued from stored state; the tests.  A side with
+ * dense features enters device-factor mode on first use.  Without a prior the value then stays fixed (G is factored once). */
+BPMF_API int bpmf_hip_side_link_lambda_set(bpmf_hip_side *side, double lambda);
+/* The current lambda_beta, the trace t of its newest draw (NaN before the first), whether it is sampled.  Any pointer may be NULL. */
+BPMF_API int bpmf_hip_side_link_lambda_get(bpmf_hip_side *side, double *lambda, double *trace_last, int *sampled);
+/* The factorisation and the two solves on host arrays (row-major fp64), for tests and tools; no handle needed.  A: D x D symmetric
+ * positive definite (the lower triangle is read), 1 <= D <= 1024; P and E: D x n, 1 <= n <= 128, E may be NULL (zero);
+ * X (D x n) = L^-T (L^-1 P + E) with A = L L^T; L_out (D x D, lower triangular, zeros above) if not NULL.  Bit-identical from call
+ * to call.  BPMF_HIP_ENUM: A is not positive definite (a pivot was not positive and finite). */
+BPMF_API int bpmf_hip_link_chol_solve(int device, const double *A, int D, const double *P, const double *E, int n, double *X, double *L_out);
+
 /* ---- prediction / RMSE -------------------------------------------------------
  * Replaces Sys::predict (c++/sample.cpp:48-96).  The test matrix slice covers
  * the same columns [col_from,col_to) as `side`; Pavg = Pm2 = T initially
