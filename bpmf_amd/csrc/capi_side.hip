@@ -47,6 +47,7 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
         if (s->mode == 3) chunk = std::max(chunk / 4, 4 * K);
     }
     chunk = (chunk + 15) / 16 * 16;
+    s->chunk = chunk;
 
     struct Item { int32_t col; int64_t p0; int32_t len; int32_t mc; int32_t chunk; int64_t cost; };
     std::vector<Item> items;
@@ -540,7 +541,8 @@ extern "C" int bpmf_hip_side_kernel_resources(bpmf_hip_side *s, int64_t *out, in
 //   0 sampler form (mode)   1 work items   2 chunks of heavy columns (partial slots)   3 heavy columns cut into chunks
 //   4 light columns in the low-rank / product forms   5 work items of the others   6..8 product-form columns with <= 3 | 4..6 | 7..16 ratings
 //   9 (was: columns in k_sample_lr; 0 since round 5)   10 parts (bpmf_hip_side_set_overlap)   11 local columns   12 local ratings
-//   13, 14 sum over the product-form columns of their number of ratings n, of n^2   15 reserved (0)
+//   13, 14 sum over the product-form columns of their number of ratings n, of n^2
+//   15 the chunk: a column with more ratings is cut into work items of at most this many (BPMF_HIP_CHUNK or the automatic value, rounded up to 16)
 extern "C" int bpmf_hip_side_schedule_info(const bpmf_hip_side *s, int64_t *out, int n)
 {
     if (!s || !out || n < 16) return fail(BPMF_HIP_EINVAL, "side_schedule_info: bad argument (16 words)");
@@ -551,6 +553,7 @@ extern "C" int bpmf_hip_side_schedule_info(const bpmf_hip_side *s, int64_t *out,
     for (int pc = 0; pc < 3; ++pc) out[6 + pc] = s->lr_n > 0 ? s->pf_class[pc + 1] - s->pf_class[pc] : 0;
     out[9] = 0;                                                       // (round 2's reflector sweeps, k_sample_lr: gone)
     out[10] = s->nsub; out[11] = s->to - s->from; out[12] = s->nnz; out[13] = s->lr_n > 0 ? s->pf_ratings : 0; out[14] = s->lr_n > 0 ? s->pf_ratings2 : 0;
+    out[15] = s->chunk;
     return BPMF_HIP_OK;
 }
 

@@ -219,6 +219,7 @@ struct bpmf_hip_side {
     bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
+    int chunk = 0;                         // ratings per work item above which a column is cut (BPMF_HIP_CHUNK or the automatic value, rounded up to 16)
     // K = 64: columns with <= 16 ratings take the product form (k_sample_pf), the rest the slab form --
     // lr_n light items + hv_nwork others (the full list above stays for per-column priors etc.)
     int lr_n = 0, hv_nwork = 0;
