@@ -68,6 +68,9 @@ _SIGNATURES = {
     "bpmf_hip_test_probit_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_probit_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "bpmf_hip_auc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_censored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
+    "bpmf_hip_side_censored_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "bpmf_hip_side_censored_latent": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_set_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint]),
     "bpmf_hip_link_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     "bpmf_hip_side_link_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

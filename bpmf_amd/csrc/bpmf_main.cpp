@@ -28,6 +28,10 @@
 // coordinate .mtx) of any width takes the CG draw of DESIGN.md section 14 (bpmf_hip_side_set_features_sparse; --link-tol, --link-max-iter).
 // --lambda-beta-prior A0,B0: lambda_beta is sampled per side with features (bpmf_hip_side_link_lambda_prior), one
 // more header line names the prior, and -o DIR also gets DIR/lambda_beta.csv (iteration,lambda_rows,lambda_cols).
+// --censored FILE (one GPU, no -g): FILE is a sparse matrix of the training matrix's shape that lists the training cells whose value
+// is only a bound: an entry > 0 = the true value is at least the recorded one, < 0 = at most (.sbm: every
+// listed cell is a lower bound).  Both sides redraw the latent values of their censored cells on the device ahead of every sampler
+// launch (bpmf_hip_side_set_censored); one more header line counts the bounds, everything else keeps its format.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -65,7 +69,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -107,6 +111,11 @@ void usage()
               << "              first draws are large (the chain starts at beta = 0): give the burn-in (-b) some tens of iterations.  With\n"
               << "              -o DIR the value every iteration used goes to DIR/lambda_beta.csv (iteration,lambda_rows,lambda_cols)\n"
               << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
+              << "  [--censored FILE]: training cells whose value is only a bound: a sparse matrix of the training matrix's shape (.sdm,\n"
+              << "              coordinate .mtx, .sbm = all lower bounds; optional .gz), an entry > 0 = the true value is at least the recorded\n"
+              << "              one, < 0 = at most; every entry must be a cell of the training matrix.  The latent values of these cells are\n"
+              << "              redrawn on the device in every half-iteration (one GPU, no -g; not with --probit, --noise adaptive,\n"
+              << "              --row-features / --col-features, -m / -l or BPMF_REDUCE=1)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -250,6 +259,9 @@ struct Job {
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
     bool probit = false;                                             // --probit
     double probit_threshold = 0.5;                                   // --probit-threshold F
+    bool censored = false;                                           // --censored FILE
+    std::vector<int8_t> cens_m, cens_u;                              // the flags of every rating of M / Mt (0, +1 lower bound, -1 upper bound)
+    int64_t cens_right = 0, cens_left = 0;
     std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
     double auc = NAN, brier = NAN;
     Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
@@ -308,6 +320,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.probit) {                                                  // (streams: tag 1 = movies, 2 = users)
         check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
         check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
+    }
+    if (J.censored) {                                                // (streams: tag 5 = movies, 6 = users)
+        check(bpmf_hip_side_set_censored(movies, J.cens_m.data(), 5));
+        check(bpmf_hip_side_set_censored(users, J.cens_u.data(), 6));
     }
     const bool linked = J.has_feat_u() || J.has_feat_m();   // (streams: tag 3 = movies, 4 = users)
     auto set_sparse = [&](bpmf_hip_side *side, const Csc &Fr, int64_t D, unsigned tag) {       // Fr: F by rows (column = item)
@@ -388,6 +404,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.probit)
         os << "likelihood: probit, a rating > " << J.probit_threshold << " is a positive label; the RMSE columns compare the latent score "
               "with the raw label and are not an error measure" << std::endl;
+    if (J.censored)
+        os << "censored: " << J.cens_right << " lower bounds, " << J.cens_left << " upper bounds of " << J.M.nnz() << " training ratings" << std::endl;
     if (linked) {
         os << "side information:";
         if (J.sfeat_u_d > 0) os << " row features sparse D = " << J.sfeat_u_d << " nnz = " << J.sfeat_u.nnz() << ",";
@@ -603,8 +621,9 @@ int main(int argc, char *argv[])
                                               {"lambda-beta", required_argument, nullptr, 1010},
                                               {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
                                               {"lambda-beta-prior", required_argument, nullptr, 1013},
+                                              {"censored", required_argument, nullptr, 1014},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -623,6 +642,7 @@ int main(int argc, char *argv[])
         case 1011: link_tol = optarg; break;
         case 1012: link_max_iter = optarg; break;
         case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
+        case 1014: censored_file = optarg; J.censored = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -741,6 +761,20 @@ int main(int argc, char *argv[])
         if (!mname.empty() || !lname.empty()) die("--row-features / --col-features do not go together with a propagated posterior (-m / -l)");
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--row-features / --col-features do not go together with BPMF_REDUCE=1");
     }
+    // --censored: checked before anything touches a GPU (the file itself below, once the training matrix is read)
+    if (J.censored) {
+        if (censored_file.empty()) die("--censored expects a file");
+        if (ngpu >= 1) die("--censored runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the latent values of a "
+                           "sharded side are not drawn)");
+        if (J.probit) die("--censored does not go together with --probit (labels have no bounds)");
+        if (J.adaptive) die("--censored does not go together with --noise adaptive (alpha | y needs a fresh draw of every censored value from "
+                            "the newest factors of both sides)");
+        if (linked) die("--censored does not go together with --row-features / --col-features (the residuals would have to be formed from the "
+                        "latent values)");
+        if (!mname.empty() || !lname.empty()) die("--censored does not go together with a propagated posterior (-m / -l)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--censored does not go together with BPMF_REDUCE=1");
+        if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--censored needs a noise precision -a F > 0");
+    }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -756,7 +790,32 @@ int main(int argc, char *argv[])
         J.M = bpmf::io::read_sparse(fname);
         J.T = bpmf::io::read_sparse(probename);
     } catch (const std::exception &e) { die(e.what()); }
+    // --censored FILE: the flags as a matrix with the structure of M (value = flag), so that they follow the ratings through the
+    // renumbering and the transpose below.  Cells are named in 1-based ids of the input.
+    Csc CF;
+    if (J.censored) {
+        Csc C;
+        try { C = bpmf::io::read_sparse(censored_file); } catch (const std::exception &e) { die(e.what()); }
+        if (C.nrows != J.M.nrows || C.ncols != J.M.ncols)
+            die("--censored: " + censored_file + " is " + std::to_string(C.nrows) + " x " + std::to_string(C.ncols) + ", the training matrix is " +
+                std::to_string(J.M.nrows) + " x " + std::to_string(J.M.ncols));
+        CF = J.M;
+        std::fill(CF.vals.begin(), CF.vals.end(), 0.0);
+        for (int64_t c = 0; c < C.ncols; ++c)
+            for (int64_t q = C.colptr[(size_t)c]; q < C.colptr[(size_t)c + 1]; ++q) {
+                const int32_t r = C.rowidx[(size_t)q];
+                const double v = C.vals[(size_t)q];
+                const std::string cell = "cell (" + std::to_string((long long)r + 1) + ", " + std::to_string((long long)c + 1) + ")";
+                if (!std::isfinite(v) || v == 0.0) die("--censored: the value of " + cell + " of " + censored_file + " is zero or not finite");
+                const int32_t *b = J.M.rowidx.data() + J.M.colptr[(size_t)c], *e = J.M.rowidx.data() + J.M.colptr[(size_t)c + 1];
+                const int32_t *at = std::lower_bound(b, e, r);
+                if (at == e || *at != r) die("--censored: " + cell + " of " + censored_file + " is not a cell of the training matrix");
+                CF.vals[(size_t)(at - J.M.rowidx.data())] = v > 0.0 ? 1.0 : -1.0;
+                (v > 0.0 ? J.cens_right : J.cens_left) += 1;
+            }
+    }
     const int64_t rows = std::max(J.M.nrows, J.T.nrows), cols = std::max(J.M.ncols, J.T.ncols);
+    if (J.censored) bpmf::io::resize(CF, rows, cols);
     bpmf::io::resize(J.M, rows, cols);
     bpmf::io::resize(J.T, rows, cols);
     if (J.M.nnz() == 0) die("the training matrix is empty");
@@ -836,6 +895,7 @@ int main(int argc, char *argv[])
         const std::vector<int64_t> inv_u = inverse(J.perm_u);
         J.M = permute(J.M, J.perm_m, inv_u);
         J.T = permute(J.T, J.perm_m, inv_u);
+        if (J.censored) CF = permute(CF, J.perm_m, inv_u);
         J.Mt = bpmf::io::transpose(J.M);
         permute_columns(J.prop_m_mu.data, K, J.perm_m); permute_columns(J.prop_m_lambda.data, (int64_t)K * K, J.perm_m);
         permute_columns(J.prop_u_mu.data, K, J.perm_u); permute_columns(J.prop_u_lambda.data, (int64_t)K * K, J.perm_u);
@@ -849,6 +909,12 @@ int main(int argc, char *argv[])
         std::stringstream ss(e);
         std::string tok;
         while (std::getline(ss, tok, ',')) if (!tok.empty()) J.devices.push_back(atoi(tok.c_str()));
+    }
+    if (J.censored) {                                                // (CF has the structure of M, its transpose that of Mt)
+        const Csc CFt = bpmf::io::transpose(CF);
+        J.cens_m.assign(std::max<size_t>(CF.vals.size(), 1), 0); J.cens_u.assign(std::max<size_t>(CFt.vals.size(), 1), 0);
+        for (size_t q = 0; q < CF.vals.size(); ++q) J.cens_m[q] = (int8_t)CF.vals[q];
+        for (size_t q = 0; q < CFt.vals.size(); ++q) J.cens_u[q] = (int8_t)CFt.vals[q];
     }
     J.Tt = bpmf::io::transpose(J.T);
     if (J.sharded) check(bpmf_hip_comm_unique_id(J.rccl_id));      // (also loads RCCL before the rank threads start)

@@ -8,10 +8,11 @@
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
+//   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last five (probit, features, sample ring, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last six (probit, censoring, features, sample ring, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -50,6 +51,14 @@ int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statis
 
 // probit likelihood (capi_probit.hip)
 int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a probit side
+
+// censored ratings (capi_censor.hip)
+int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a censored side
+// the latent kernel of a probit or a censored side, whichever `self` is (a side is never both)
+inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
+{
+    return self->probit ? probit_latent_enqueue(self, other, iter, alpha, st) : censor_latent_enqueue(self, other, iter, alpha, st);
+}
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.

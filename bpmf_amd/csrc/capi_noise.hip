@@ -13,6 +13,8 @@ extern "C" int bpmf_hip_train_sse(bpmf_hip_side *self, bpmf_hip_side *other, dou
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "train_sse: the other side must have one column per row of this side's ratings");
     int rc = require_single_gpu("train_sse", c, self, other, " (a sharded side or a communicator would need an all-reduce of the sum, which adaptive noise does not do)");
     if (rc) return rc;
+    // (alpha | y needs a fresh draw of every censored y from the newest factors of BOTH sides ahead of the sum: DESIGN.md section 16)
+    if (self->censor || other->censor) return fail(BPMF_HIP_EINVAL, "train_sse: not with a censored side (the sum would take the bounds for measurements)");
     HIP_TRY(hipSetDevice(c->device));
     *sse = 0.0;
     *n = self->nnz;

@@ -36,6 +36,16 @@ struct CgWork {
 // place), the sign of every rating, and a word the latent kernel raises to a rating position when a draw runs into its attempt cap
 struct bpmf_probit { DevBuf<double> z; DevBuf<int8_t> sign; Pinned<unsigned long long> fail; uint32_t tag = 0; };
 
+// censored ratings (capi_censor.hip): the censored entries of the side as compact lists (position in the CSC,
+// column, row, +1 = the rating is a lower bound / -1 = an upper bound), the latent values (layout of d_vals: a copy of the ratings
+// of which only the censored positions are ever rewritten; the samplers read it in place of d_vals), and the word the latent kernel
+// raises to a rating position when a draw runs into its attempt cap
+struct bpmf_censor {
+    DevBuf<int64_t> pos; DevBuf<int32_t> col, row; DevBuf<int8_t> sign;
+    DevBuf<double> z; Pinned<unsigned long long> fail;
+    int64_t n = 0, nright = 0, nleft = 0; uint32_t tag = 0;
+};
+
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
 struct bpmf_link_dense {
     DevBuf<double> F, W, PE;

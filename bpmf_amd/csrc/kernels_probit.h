@@ -30,7 +30,8 @@ namespace bpmf {
 constexpr int kProbitMaxAttempts = 64;      // a rejected attempt has probability <= 1/4: the cap is reached with probability < 2^-128 per rating
 constexpr double kProbitCapValue = 1.0;     // |z| stored for a rating whose draw ran into the cap (with the failure word raised)
 
-__global__ __launch_bounds__(256) void k_probit_sign(const double *__restrict__ vals, int64_t nnz, double threshold, int8_t *__restrict__ sign)
+// (static: not a template, and kernels_censor.h brings this header into a second translation unit for probit_truncated)
+static __global__ __launch_bounds__(256) void k_probit_sign(const double *__restrict__ vals, int64_t nnz, double threshold, int8_t *__restrict__ sign)
 {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p < nnz) sign[p] = vals[p] > threshold ? (int8_t)1 : (int8_t)-1;

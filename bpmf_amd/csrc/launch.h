@@ -163,6 +163,18 @@ void probit_sign(const double *vals, int64_t nnz, double threshold, int8_t *sign
 int probit_latent(const ProbitLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched)
 int probit_prob(const ProbitProbLaunch &p, hipStream_t st);
 
+// censored ratings (kernels_censor.h, kcensor.hip)
+struct CensorLatentLaunch {
+    const int64_t *pos; const int32_t *col, *row; const int8_t *sign; int64_t n;   // the censored entries: position in the CSC, column, row, +-1
+    const double *vals;                                    // the side's ratings: vals[pos] is the bound
+    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    uint32_t iter, tag;
+    double mean, sqrt_alpha, inv_sqrt_alpha;               // the side's mean rating; sqrt(alpha) and 1 / sqrt(alpha), formed on the host
+    double *z;                                             // the latent values, layout of the side's ratings: z[pos] is written
+    unsigned long long *fail;                              // raised (rating position) when a draw runs into the attempt cap
+};
+int censor_latent(const CensorLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched); n = 0: nothing launched
+
 // side information (kernels_link.h, klink.hip): fp64, row-major operands
 struct LinkTnLaunch {                                      // C (D x n, leading dimension ldc) = A^T (B - 1 bvec^T)
     const double *A; int64_t lda;                          // N x D

@@ -26,8 +26,9 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     using namespace bpmf;
     bpmf_hip_ctx *c = self->ctx;
     SampleArgs a = blob_args(self, out_items, d_in, iter, alpha);
-    // probit side: the latent scores stand in for the ratings; side with features: the residuals r - m_c . y_r (capi_link.hip)
-    const double *vals = self->probit ? self->probit->z.get() : self->link ? self->link->r.get() : self->d_vals;
+    // probit side: the latent scores stand in for the ratings; censored side: the ratings with a fresh draw at every censored
+    // position (capi_censor.hip); side with features: the residuals r - m_c . y_r (capi_link.hip)
+    const double *vals = self->probit ? self->probit->z.get() : self->censor ? self->censor->z.get() : self->link ? self->link->r.get() : self->d_vals;
     a.rowidx = self->d_rowidx; a.vals = vals;
     // (item window: the whole list, or the items of one part of the columns -- bpmf_hip_side_set_overlap)
     const int w0 = self->item_n >= 0 ? self->item_off : 0, nwork = self->item_n >= 0 ? self->item_n : self->nwork;

@@ -212,6 +212,7 @@ struct bpmf_hip_side {
     double *d_prop = nullptr;            // propagated posterior (-m / -l): K x K prior precision per local column, or NULL
     // the add-ons (ext_state.h), each NULL until its entry point attaches it; released in bpmf_hip_side_destroy
     std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
+    std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
     std::unique_ptr<bpmf_sse> sse;         // partials of the training residuals (bpmf_hip_train_sse)
@@ -376,6 +377,18 @@ inline int check_probit(bpmf_hip_side *s, std::string *msg)
     if (v == ~0ull) return 0;
     __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
     *msg = "probit: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
+    return BPMF_HIP_ENUM;
+}
+
+// censored ratings: the same for the latent draw of a censored side
+inline int check_censor(bpmf_hip_side *s, std::string *msg)
+{
+    if (!s->censor) return 0;
+    unsigned long long *word = s->censor->fail.host();
+    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (v == ~0ull) return 0;
+    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
+    *msg = "censored: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
     return BPMF_HIP_ENUM;
 }
 

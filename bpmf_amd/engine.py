@@ -18,6 +18,7 @@ class _Side:
     def __init__(self, handle, K, ncols, nrows, col_from, col_to, keep):
         self.handle, self.K, self.ncols, self.nrows = handle, K, ncols, nrows
         self.col_from, self.col_to = col_from, col_to
+        self.nnz = 0               # ratings of the local columns (set by side_create / side_create_dev)
         self._keep = keep          # arrays / tensors that must outlive the handle
 
 
@@ -120,6 +121,7 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_side_create(self.ctx, ncols, nrows, col_from, col_to, _ptr(colptr), _ptr(rowidx),
                                                  _ptr(vals), float(mean_rating), C.byref(h)))
         s = _Side(h, self.K, ncols, nrows, col_from, col_to, None)
+        s.nnz = int(colptr[-1])
         self._sides.append(s)
         return s
 
@@ -132,6 +134,7 @@ class HipEngine:
                                                      C.c_void_p(rowidx_dev_ptr), C.c_void_p(vals_dev_ptr),
                                                      float(mean_rating), C.byref(h)))
         s = _Side(h, self.K, ncols, nrows, col_from, col_to, keep)
+        s.nnz = int(colptr_host[-1])
         self._sides.append(s)
         return s
 
@@ -301,6 +304,38 @@ class HipEngine:
         n = C.c_int()
         _lib.check(self.lib.bpmf_hip_test_probit_get(test[0], _ptr(prob), C.byref(n)))
         return prob, n.value
+
+    # -- censored ratings ----------------------------------------------------------
+    def set_censored(self, side, flags, tag):
+        """Marks ratings of `side` as bounds: flags holds one int8 per rating in the side's order, 0 = the value is the measurement,
+        +1 = the true value is at least the recorded one, -1 = at most (bpmf_amd.censor_flags builds them from a sparse matrix).
+        Every sampler launch of the side is then preceded by the draw of the latent values of its censored ratings
+        (include/bpmf_hip.h).  tag >= 1 names the side's random streams: different per side, and apart from
+        the tags of probit sides and features (gibbs: 5 = movies, 6 = users).  Any alpha > 0."""
+        f = np.asarray(flags)
+        if f.dtype != np.int8:
+            if f.size and not np.all((f == -1) | (f == 0) | (f == 1)):
+                raise ValueError("set_censored: the flags must be -1, 0 or +1")
+            f = f.astype(np.int8)
+        f = np.ascontiguousarray(f)
+        if f.ndim != 1:
+            raise ValueError("set_censored: the flags must be one array, one flag per rating of the side")
+        if len(f) != side.nnz:
+            raise ValueError("set_censored: %d flags for a side of %d ratings" % (len(f), side.nnz))
+        _lib.check(self.lib.bpmf_hip_side_set_censored(side.handle, _ptr(f), int(tag)))
+
+    def censored_count(self, side):
+        """(lower bounds, upper bounds) of a censored side."""
+        r, l = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.bpmf_hip_side_censored_count(side.handle, C.byref(r), C.byref(l)))
+        return r.value, l.value
+
+    def censored_latent(self, side):
+        """The values the side's newest sampler launch read in place of its ratings, in their order: the ratings at the exact
+        positions, the newest draws at the censored ones (waits)."""
+        z = np.empty(side.nnz)
+        _lib.check(self.lib.bpmf_hip_side_censored_latent(side.handle, _ptr(z)))
+        return z
 
     # -- side information ---------------------------------------------------------
     def set_features(self, side, F, lambda_beta=5.0, tag=3):

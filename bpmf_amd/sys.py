@@ -13,6 +13,7 @@ import time
 import numpy as np
 
 from . import engine as _engine
+from .censor import censor_flags, transpose_csc
 
 
 class HyperParams:
@@ -185,7 +186,7 @@ class Sys:
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
-          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None):
+          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -233,8 +234,25 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     the first, for which `lambda_beta` is the initial value.  (5e-4, 5e-4) is a weak default, not a tuned number.  The chain
     starts at beta = 0, so the first draws are large (10^2 .. 10^3) and take tens of iterations to come down: the burn-in has to
     cover that.  res["lambda_beta_rows"] / res["lambda_beta_cols"]: the value each half-iteration used, one per iteration (None
-    for a side without features).  None (the default): lambda_beta stays fixed and nothing changes."""
+    for a side without features).  None (the default): lambda_beta stays fixed and nothing changes.
+
+    censored=C: some training ratings are bounds, not measurements.  C is a CSC triple of M's shape: an
+    entry > 0 says that the rating of that cell is a lower bound of the true value, an entry < 0 an upper bound (bpmf_amd.
+    censor_flags; every entry must be a stored cell of M).  Both sides get their flags (engine.set_censored, tags 5 = movies,
+    6 = users; those of Mt from C transposed) and redraw the latent values of their censored cells ahead of every sampler launch,
+    on the device, without a host wait: the pipelined loop does not drain.  Any alpha > 0, with or without topn; the test matrix
+    is taken as exact values.  probit=True, noise="adaptive" and features are refused with censored.  res["censored"] = (lower
+    bounds, upper bounds).  None (the default): nothing changes."""
     linked = row_features is not None or col_features is not None
+    if censored is not None:
+        if probit:
+            raise ValueError("censored does not go together with probit=True (labels have no bounds)")
+        if noise == "adaptive":
+            raise ValueError("censored does not go together with noise='adaptive' (alpha | y needs a fresh draw of every censored "
+                             "value from the newest factors of both sides)")
+        if linked:
+            raise ValueError("censored does not go together with row_features / col_features (the residuals would have to be "
+                             "formed from the latent values)")
     if linked:
         if pipelined:
             raise ValueError("pipelined=True does not go together with row_features / col_features (the features loop is blocking)")
@@ -273,12 +291,19 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     a0, b0 = (float(alpha_prior[0]), float(alpha_prior[1])) if adaptive else (0.0, 0.0)
     if adaptive and not (a0 > 0 and b0 >= 0):
         raise ValueError("alpha_prior = (a0, b0) needs a0 > 0 and b0 >= 0")
+    if censored is not None:                         # (checked before a side is created)
+        if not (float(alpha) > 0 and math.isfinite(float(alpha))):
+            raise ValueError("censored needs a finite alpha > 0")
+        cflags = (censor_flags(M, censored), censor_flags(Mt, transpose_csc(censored, nusers)))
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
     movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit else None)
     users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit else None)
     if probit:
         engine.set_probit(movies.side, threshold, 1)
         engine.set_probit(users.side, threshold, 2)
+    if censored is not None:
+        engine.set_censored(movies.side, cflags[0], 5)
+        engine.set_censored(users.side, cflags[1], 6)
     if linked:
         if col_features is not None:
             engine.set_features(movies.side, col_features, lambda_beta, 3)
@@ -402,6 +427,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         label = (np.asarray(T[2]) > threshold).astype(np.float64) if have else np.zeros(0)
         res["auc"] = _engine.auc(res["prob"], label, 0.5) if have else float("nan")
         res["brier"] = float(np.mean((res["prob"] - label) ** 2)) if have else float("nan")
+    if censored is not None:
+        res["censored"] = engine.censored_count(movies.side)
     if linked:
         res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
         res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None

@@ -333,6 +333,36 @@ BPMF_API int bpmf_hip_test_probit_get(bpmf_hip_test *test, double *prob_host, in
  * included).  BPMF_HIP_EINVAL for NULL arguments, n < 0 or a NaN score. */
 BPMF_API int bpmf_hip_auc(const double *score, const double *value, int64_t n, double threshold, double *auc);
 
+/* ---- censored ratings (Tobit) ----------------------------------------------------
+ * A training rating may be a bound on the measurement instead of the measurement.  Every rating p of a side (position in the
+ * side's CSC) has a flag c_p: 0 = the recorded value b_p is the measurement, +1 = the true value is at least b_p, -1 = at most
+ * b_p.  With y_p ~ N(mean_rating + x_c . y_r, 1 / alpha) a censored cell carries a latent value z_p drawn from that normal
+ * truncated to (b_p, inf) or (-inf, b_p); the column samplers read z in place of the ratings, with the side's own mean rating and
+ * the caller's alpha (any alpha > 0).  DESIGN.md section 16 has the model and the draw.
+ *
+ * bpmf_hip_side_set_censored takes the flags (nnz of them, in the order of the side's ratings), builds the lists of the censored
+ * entries on the device and the array z (layout of the side's ratings, a copy of them; the ratings are never written).  From then
+ * on every sampler launch of the side (bpmf_hip_sys_sample, bpmf_hip_sample_side[_launch]; iteration `iter`) is preceded on the
+ * same stream by the latent step over the censored entries only, with s = c_p:
+ *     m = x_c . y_r  (x: the side's factors before this update, y: the other side's newest; fp64),
+ *     e = (b_p - mean_rating) - m,  a = s (sqrt(alpha) e),  t ~ N(0, 1) | t > a,  z_p = b_p + s ((t - a) / sqrt(alpha)),
+ * t drawn as for a probit side from the Philox4x32-10 blocks (counter = p low, p high, iter, attempt; key = 42, tag).  tag >= 1
+ * names the side's streams: different for the two sides of a model, and different from the tags of every probit side and of
+ * every side with features (bpmf_amd.gibbs and `bpmf` use 5 = movies, 6 = users here; 1 / 2 probit; 3 / 4 features).  No host
+ * wait is added to the sampling calls; a side whose flags are all 0 launches no kernel and samples exactly as a side without
+ * flags.  A draw rejected 64 times (non-finite factors) stores b_p + s / sqrt(alpha) and makes the call that collects the
+ * half-iteration fail with BPMF_HIP_ENUM.  fp32 contexts are allowed: z and the bounds are fp64 as the ratings are.
+ * BPMF_HIP_EINVAL: a NULL argument, a flag outside {-1, 0, +1}, tag = 0, a side that is censored already, a probit side, a side
+ * with features, propagated priors, the BPMF_REDUCE formulation, a context with a communicator or a sharded side.  In turn
+ * bpmf_hip_side_set_probit, bpmf_hip_side_set_features[_sparse], bpmf_hip_sys_set_reduce and bpmf_hip_train_sse refuse a
+ * censored side (the residuals of the last would take the bounds for measurements). */
+BPMF_API int bpmf_hip_side_set_censored(bpmf_hip_side *side, const int8_t *flags, unsigned tag);
+/* The numbers of lower bounds (flag +1) and upper bounds (flag -1) of a censored side. */
+BPMF_API int bpmf_hip_side_censored_count(bpmf_hip_side *side, int64_t *right, int64_t *left);
+/* The array z as the side's newest sampler launch read it, nnz doubles in the order of the side's ratings: the ratings at the
+ * exact positions, the newest draws at the censored ones (waits for the work in flight). */
+BPMF_API int bpmf_hip_side_censored_latent(bpmf_hip_side *side, double *z_host);
+
 /* ---- side information: row / column features linked to the factor priors -----------
  * A side with N columns may carry a dense feature matrix F (N x D, fp64), a link matrix beta (D x K) and a fixed
  * lambda_beta > 0:
