@@ -923,6 +923,10 @@ int main(int argc, char *argv[])
         const double nan = std::nan("");                              // (no post-burn-in sample: the reference divides 0 by 0)
         J.u_mu.assign((size_t)K * nusers, nan); J.u_lambda.assign((size_t)K * K * nusers, nan);
         J.m_mu.assign((size_t)K * nmovies, nan); J.m_lambda.assign((size_t)K * K * nmovies, nan);
+        // (bpmf_hip_side_aggr_finalize: a covariance of n samples has rank n - 1 at most)
+        if (J.nsims - J.burnin <= K)
+            std::cerr << "note: U-Lambda.ddm / V-Lambda.ddm are NaN: the " << std::max(J.nsims - J.burnin, 0) << " kept samples (-i " << J.nsims
+                      << " -b " << J.burnin << ") do not determine a " << K << " x " << K << " covariance; keep more than " << K << std::endl;
     }
 
     // stdout of the ranks: bpmf_<rank>.out when there are several or with -r (c++/bpmf.cpp:111-117)

@@ -82,7 +82,10 @@ __global__ __launch_bounds__(256) void k_aggr_add(const T *__restrict__ items, i
 
 // cov = (prod - sum sum^T / n) / (n - 1); Lambda = cov^-1 (in-place Gauss-Jordan with partial pivoting, the matrix
 // stays in global memory -- a column's K x K block is L2-resident while its workgroup works on it); mu = sum / n.
-// A singular covariance (n <= K samples) gives NaN like the reference's inverse of a singular matrix gives inf / NaN.
+// 1 <= n <= K samples: every entry of Lambda is NaN and nothing is eliminated -- the covariance of n samples has rank at most
+// n - 1 < K, whatever the rounding leaves in its pivots (in floating point they are tiny, not zero: the elimination would return
+// finite entries of 1e15 .. 1e17).  With n > K a pivot that is exactly zero gives NaN too, like the reference's inverse of a
+// singular matrix gives inf / NaN.  mu = sum / n either way.
 __global__ __launch_bounds__(256) void k_aggr_finalize(int K, int nsamples, double *__restrict__ mu, double *__restrict__ lambda)
 {
     __shared__ int piv[256];
@@ -94,6 +97,11 @@ __global__ __launch_bounds__(256) void k_aggr_finalize(int K, int nsamples, doub
     double *a = lambda + (size_t)c * K * K;
     double *m = mu + (size_t)c * K;
     auto A = [&](int r, int cc) -> double & { return a[(size_t)cc * K + r]; };
+    if (nsamples >= 1 && nsamples <= K) {                           // (the whole workgroup takes this branch)
+        for (int e = tid; e < K * K; e += 256) a[e] = __builtin_nan("");
+        for (int e = tid; e < K; e += 256) m[e] /= nsamples;
+        return;
+    }
     for (int e = tid; e < K * K; e += 256) {
         const int i = e % K, j = e / K;
         a[e] = (a[e] - (m[i] * m[j] / nsamples)) / (nsamples - 1);

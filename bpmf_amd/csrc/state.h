@@ -45,9 +45,9 @@ template <typename T>
 inline int dev_upload(T **dst, const T *src, size_t n)
 {
     *dst = nullptr;
-    if (n == 0) n = 1;
-    HIP_TRY(hipMalloc((void **)dst, n * sizeof(T)));
-    if (src) HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    // (an empty array still gets one element of storage; nothing is read from src then: the caller's array has none)
+    HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
+    if (src && n) HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -259,7 +259,9 @@ BPMF_API int bpmf_hip_sys_norm(bpmf_hip_side *side, int iter, double *norm);
  * per LOCAL column live on the device.  _aggr_finalize replaces Sys::finalize_mu_lambda (c++/bpmf.cpp:281-295):
  * cov = (prod - sum sum^T / n) / (n - 1), Lambda = cov^-1 (batched, one workgroup per column), mu = sum / n; it
  * copies this rank's K x nloc means and K*K x nloc precisions (column-major per column, the layout of U-mu.ddm /
- * U-Lambda.ddm) to the host and frees the device buffers.  A singular covariance (n <= K) gives NaN. */
+ * U-Lambda.ddm) to the host and frees the device buffers.  1 <= n <= K samples do not determine a K x K covariance (its rank
+ * is at most n - 1): every entry of every Lambda is then NaN and no inverse is attempted, mu is still sum / n.  With n > K a
+ * covariance with a pivot that is exactly zero gives NaN for that column. */
 BPMF_API int bpmf_hip_side_aggr_add(bpmf_hip_side *side);
 BPMF_API int bpmf_hip_side_aggr_finalize(bpmf_hip_side *side, int nsamples, double *mu_host, double *lambda_host);
 /* global id of the first column whose factorisation failed, or -1 */

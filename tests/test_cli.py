@@ -74,6 +74,15 @@ def test_tiny_run_test_sh(oracle, tmp_path):
     assert lam.shape == (64, nu)
     cov0 = np.cov(samples[:, :, 0].T)                                          # 9 samples of an 8-vector: invertible
     assert np.allclose(lam[:, 0].reshape(8, 8, order="F"), np.linalg.inv(cov0), rtol=1e-6, atol=1e-8)
+    # ... and every column at the bar of tests/test_gpu_posterior_outputs.py: the .ddm files are binary, so neither the samples
+    # nor Lambda lost a digit in print -- the error against the longdouble inverse may be 8 x that of numpy's fp64 inverse of
+    # the one-pass covariance of the same samples (which scales with the condition number of this matrix; no constant does)
+    from tests.test_gpu_posterior_outputs import LAMBDA_FACTOR, lambda_err, lambda_reference, lambda_restatement
+    X = samples.transpose(0, 2, 1)                                             # [sample, column, K]
+    mu_ref, lam_ref = lambda_reference(X)
+    err, err_np = lambda_err(lam.T.reshape(nu, 8, 8).transpose(0, 2, 1), lam_ref), lambda_err(lambda_restatement(X)[1], lam_ref)
+    print("bpmf -o U-Lambda.ddm: err %s, numpy's %s" % (err, err_np))
+    assert np.all(err <= LAMBDA_FACTOR * err_np), (err, err_np)
 
 
 @pytest.mark.gpu
