@@ -42,6 +42,18 @@ struct Geo44 {
     __host__ __device__ static constexpr int idx(int g, int x) { return 8 * (g >> 1) + 2 * x + (g & 1); }
 };
 
+// One rating of a side's gather stream (capi_side.hip: build_schedule), what k_sample1 reads in place of the row id and
+// the rating: where the rated row's K-vector lies and r - mean_rating.  The ratings of a work item follow each other in
+// the item's rating order, padded to a multiple of 16 (one group of the 4x4x4 Gram); a padding record has off < 0 and
+// d = 0 -- it gathers SampleArgs::zero_row.
+struct GatherRec {
+    int32_t off;                // row * K / 2: the row's offset into the other side's factor matrix in 16-byte units
+    int32_t unused;
+    double d;                   // rating - mean_rating (c++/sample.cpp:256; times alpha in the kernel)
+};
+static_assert(sizeof(GatherRec) == 16, "one 16-byte load per record");
+constexpr int kGatherTailGroups = 4;   // padding groups behind the last item: the record loads run two groups ahead, unconditionally
+
 struct SampleArgs {
     // ratings of this rank's columns
     const int32_t *rowidx;
@@ -52,6 +64,11 @@ struct SampleArgs {
     const int32_t *wi_len;      // ratings in the chunk
     const int32_t *wi_mc;       // heavy column index the chunk belongs to, or -1 (whole column)
     const int32_t *wi_chunk;    // ordinal of the chunk inside its column
+    // gather stream of the side (k_sample1, launches that read the side's own ratings), or gs_rec = NULL: item w's
+    // records are gs_rec[16 * gs_g0[w] ...], gs_ng[w] groups of 16
+    const GatherRec *gs_rec;
+    const int32_t *gs_g0;       // first group of the item
+    const int32_t *gs_ng;       // groups of the item: (wi_len + 15) / 16
     const int32_t *mc_slot0;    // heavy columns: first partial slot, number of chunks
     const int32_t *mc_nchunks;
     unsigned *mc_count;         // arrival counters of the heavy columns (zero between launches)

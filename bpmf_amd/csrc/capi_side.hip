@@ -4,6 +4,52 @@
 
 namespace bpmf_capi {
 
+// The gather stream of a k_sample1 side (args.h: GatherRec): per rating, in the order the work items consume them, where
+// the rated row's K-vector lies and r - mean_rating -- what the kernel would otherwise work out again in every launch of
+// every iteration from the row ids and ratings (a cross-lane permute of each, row * K, the 64-bit address, the compare and
+// selects of the padding slots, the subtraction).  All of it is fixed when the side is created; alpha is not and stays a
+// multiply in the kernel.  16 bytes per rating plus the padding of every item to a multiple of 16 ratings (ML-1M shape:
+// ~14.4 MB + ~1.5 MB per side).  BPMF_HIP_GATHER_STREAM=0: not built, every launch takes the index-block form.
+static int build_gather_stream(bpmf_hip_side *s, const std::vector<int64_t> &wp0, const std::vector<int32_t> &wlen)
+{
+    const int K = s->ctx->K;
+    if (s->mode != 1 || K > 32 || s->ctx->dtype != BPMF_HIP_F64 || env_int("BPMF_HIP_GATHER_STREAM", 1) == 0) return 0;
+    if (s->nrows * (int64_t)(K / 2) > (int64_t)INT32_MAX) return 0;          // (offsets are 32-bit)
+    const size_t nw = wlen.size();
+    int64_t groups = 0;
+    for (size_t i = 0; i < nw; ++i) groups += (wlen[i] + 15) / 16;
+    groups += bpmf::kGatherTailGroups;
+    if (groups > (int64_t)INT32_MAX / 16) return 0;
+    // (the ratings may have been handed over as device arrays: read them back)
+    std::vector<int32_t> ri((size_t)s->nnz);
+    std::vector<double> rv((size_t)s->nnz);
+    if (s->nnz > 0) {
+        HIP_TRY(hipMemcpy(ri.data(), s->d_rowidx, (size_t)s->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rv.data(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    const bpmf::GatherRec pad = {-1, 0, 0.0};
+    std::vector<bpmf::GatherRec> rec((size_t)groups * 16, pad);
+    std::vector<int32_t> g0(nw), ng(nw);
+    int64_t g = 0;
+    for (size_t i = 0; i < nw; ++i) {
+        g0[i] = (int32_t)g; ng[i] = (wlen[i] + 15) / 16;
+        bpmf::GatherRec *out = rec.data() + (size_t)g * 16;
+        for (int32_t q = 0; q < wlen[i]; ++q) {
+            const int64_t p = wp0[i] + q;
+            if (ri[(size_t)p] < 0 || ri[(size_t)p] >= s->nrows) return fail(BPMF_HIP_EINVAL, "side_create: row index out of range");
+            out[q].off = (int32_t)((int64_t)ri[(size_t)p] * (K / 2));
+            out[q].d = rv[(size_t)p] - s->mean_rating;
+        }
+        g += ng[i];
+    }
+    int rc;
+    if ((rc = dev_upload(&s->d_gs_rec, rec.data(), rec.size()))) return rc;
+    if ((rc = dev_upload(&s->d_gs_g0, g0.data(), nw))) return rc;
+    if ((rc = dev_upload(&s->d_gs_ng, ng.data(), nw))) return rc;
+    s->gs_groups = groups;
+    return 0;
+}
+
 int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
 {
     const int64_t nloc = s->to - s->from;
@@ -172,6 +218,7 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
     if ((rc = dev_upload(&s->d_wi_mc, wmc.data(), nw))) return rc;
     if ((rc = dev_upload(&s->d_wi_chunk, wchunk.data(), nw))) return rc;
     if ((rc = dev_upload(&s->d_wi_p0, wp0.data(), nw))) return rc;
+    if ((rc = build_gather_stream(s, wp0, wlen))) return rc;
     if ((rc = dev_upload(&s->d_mc_slot0, mc_slot0.data(), mc_slot0.size()))) return rc;
     if ((rc = dev_upload(&s->d_mc_nch, mc_nch.data(), mc_nch.size()))) return rc;
     {
@@ -207,9 +254,10 @@ void free_schedule(bpmf_hip_side *s)
     void **ptrs[] = {(void **)&s->d_wi_col, (void **)&s->d_wi_len, (void **)&s->d_wi_mc, (void **)&s->d_wi_chunk, (void **)&s->d_wi_p0,
                      (void **)&s->d_mc_slot0, (void **)&s->d_mc_nch, (void **)&s->d_mc_count, (void **)&s->d_partials, (void **)&s->d_stat_partials,
                      (void **)&s->d_lr_col, (void **)&s->d_lr_len, (void **)&s->d_lr_p0, (void **)&s->d_hv_col, (void **)&s->d_hv_len,
-                     (void **)&s->d_hv_mc, (void **)&s->d_hv_chunk, (void **)&s->d_hv_p0, (void **)&s->d_pf_q};
+                     (void **)&s->d_hv_mc, (void **)&s->d_hv_chunk, (void **)&s->d_hv_p0, (void **)&s->d_pf_q,
+                     (void **)&s->d_gs_rec, (void **)&s->d_gs_g0, (void **)&s->d_gs_ng};
     for (void **p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    s->lr_n = s->hv_nwork = 0;
+    s->lr_n = s->hv_nwork = 0; s->gs_groups = 0;
 }
 
 
@@ -318,7 +366,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
                     s->d_stat_partials, s->a_d_in,
                     s->d_lr_col, s->d_lr_len, s->d_lr_p0, s->d_hv_col, s->d_hv_len, s->d_hv_mc, s->d_hv_chunk, s->d_hv_p0,
                     s->d_conn_send, s->d_conn_recv, s->d_conn_sbuf, s->d_conn_rbuf, s->d_pf_q,
-                    s->d_prec, s->d_t_colptr, s->d_t_rowidx, s->d_t_vals, s->d_t_order};
+                    s->d_prec, s->d_t_colptr, s->d_t_rowidx, s->d_t_vals, s->d_t_order, s->d_gs_rec, s->d_gs_g0, s->d_gs_ng};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (s->a_h_in) (void)hipHostFree(s->a_h_in);
     if (s->a_h_out) (void)hipHostFree(s->a_h_out);
@@ -504,7 +552,7 @@ extern "C" int bpmf_hip_side_kernel_name(const bpmf_hip_side *s, char *buf, int 
                 if (s->pf_class[pc + 1] > s->pf_class[pc]) name += std::string(name.empty() ? "" : " + ") + "k_sample_pf<64," + nb[pc] + ">";
             if (s->hv_nwork > 0) name += " + k_sample_slab<64>";
         } else name = (fusable && s->lr_n == 0 && s->nsub <= 1) ? "k_sample1s<64>" : "k_sample_slab<64>";
-    } else name = (s->mode == 3 ? "k_sample4<" : "k_sample1<") + k + ">";
+    } else name = (s->mode == 3 ? "k_sample4<" : uses_gather_stream(s) ? "k_sample1<" : "k_sample1i<") + k + ">";     // (k_sample1i: the index-block form)
     snprintf(buf, (size_t)n, "%s", name.c_str());
     return BPMF_HIP_OK;
 }

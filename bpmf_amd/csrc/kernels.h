@@ -554,6 +554,80 @@ __device__ __forceinline__ void gram_chunk44(const int32_t *__restrict__ rowidx,
     }
 }
 
+// The same Gram from the side's gather stream (args.h: GatherRec, built once per side by build_schedule): lane (slot, x)
+// reads the record of ITS slot of every group with one 16-byte load (the four x lanes share the address) -- no index
+// blocks, no cross-lane permutes, no row * K, no r - mean; a padding record (off < 0, d = 0) gathers the row of zeros.
+// One loop over the item's groups of 16 ratings, unrolled by two over the two operand sets: the records run two groups
+// ahead of the MFMAs, the gathers one group ahead.  The record loads are unconditional (they run into the next item's
+// records, or the kGatherTailGroups padding groups behind the last item); a gather is only issued for a group the item
+// has.  Slot-to-block mapping, order of the groups and every floating-point operation are gram_chunk44's: the two forms
+// give the same bits (d * alpha is the (v - mean) * alpha of the other form with the subtraction done on the host).
+// r0, r1: the records of groups 0 and 1, requested by the caller ahead of the normal draw.
+typedef double gs_raw __attribute__((ext_vector_type(2)));        // a record as loaded: .x = off | unused, .y = d
+// rec: the item's first record (wave-uniform); slot_bytes: 16 * the lane's slot -- a scalar base the loop advances on the
+// scalar unit plus a fixed 32-bit lane offset: no vector address arithmetic per load
+__device__ __forceinline__ gs_raw load_gs_rec(const GatherRec *__restrict__ rec, int g, unsigned slot_bytes)
+{
+    return *reinterpret_cast<const gs_raw *>(reinterpret_cast<const char *>(rec + 16 * g) + slot_bytes);
+}
+
+template <int K>
+__device__ __forceinline__ void gram_stream44(const GatherRec *__restrict__ rec, int ng, const double *__restrict__ other,
+                                              const double *__restrict__ zero_row, double alpha, gs_raw r0, gs_raw r1, unsigned slot_bytes,
+                                              double (&acc)[Geo44<K>::NB], double (&rr)[Geo44<K>::NG], int lane)
+{
+    using G = Geo44<K>;
+    constexpr int NG = G::NG, NL = G::NL;
+    typedef double dd2 __attribute__((ext_vector_type(2)));
+    const int x = lane & 3;
+    const dd2 *ox = reinterpret_cast<const dd2 *>(other + 2 * x), *zx = reinterpret_cast<const dd2 *>(zero_row + 2 * x);
+    auto gather = [&](const gs_raw &rc, dd2 (&yy)[NL], double &ww) {
+        const int off = (int)__builtin_bit_cast(long long, rc.x);
+        ww = rc.y * alpha;                                                        // c++/sample.cpp:256
+        const dd2 *p = (off >= 0) ? ox + off : zx;
+#pragma unroll
+        for (int h = 0; h < NL; ++h) yy[h] = p[4 * h];
+    };
+    auto contract = [&](const dd2 (&yy)[NL], double ww) {
+        double R[NG];
+#pragma unroll
+        for (int h = 0; h < NL; ++h) { R[2 * h] = yy[h].x; R[2 * h + 1] = yy[h].y; }
+#pragma unroll
+        for (int g = 0; g < NG; ++g) rr[g] = fma(R[g], ww, rr[g]);
+        int blk = 0;
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int g2 = g; g2 < NG; ++g2, ++blk) acc[blk] = mfma44(R[g], R[g2], acc[blk]);
+    };
+    if (ng <= 0) return;
+    dd2 yA[NL], yB[NL];
+    double wA, wB = 0.0;
+    gather(r0, yA, wA);
+    r0 = load_gs_rec(rec, 2, slot_bytes);
+    if (ng > 1) gather(r1, yB, wB);                                              // group 1
+    r1 = load_gs_rec(rec, 3, slot_bytes);
+    // group 0 on its own: the accumulators are known to be zero here (the caller cleared them), so its MFMAs take the
+    // constant 0 as their C operand and 44 register clears per item go away
+    contract(yA, wA);
+    int g = 1;
+    // two groups per trip while the second of them has a successor; yB holds group g at the top
+    for (; g + 2 < ng; g += 2) {
+        gather(r0, yA, wA);                                                      // group g + 1
+        r0 = load_gs_rec(rec, g + 3, slot_bytes);
+        contract(yB, wB);
+        gather(r1, yB, wB);                                                      // group g + 2
+        r1 = load_gs_rec(rec, g + 4, slot_bytes);
+        contract(yA, wA);
+    }
+    // the last one or two groups
+    if (g < ng) {
+        if (g + 1 < ng) gather(r0, yA, wA);
+        contract(yB, wB);
+        if (g + 1 < ng) contract(yA, wA);
+    }
+}
+
 // The four b of every accumulator are added (fixed order: (b + b^2) + the same of b^1; every lane ends up with the
 // total), then the full symmetric G goes into the K x LD LDS matrix finish_single reads: the lanes b = 0 write the
 // upper blocks, the lanes b = 1 their mirror images, two block rows (g, g + 1) at a time -- two exec regions per row
@@ -1022,10 +1096,11 @@ __device__ __forceinline__ void gate_stage_body(int block, int nblocks, const un
                                                 double *__restrict__ dst, int n, unsigned *dflag, unsigned dval,
                                                 unsigned long long *tmo, unsigned long long wait_ticks);
 
-template <int K>
-__global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1(SampleArgs a, FusedArgs f)
+// GS: the Gram reads the side's gather stream (gram_stream44: k_sample1) / the row ids and a value array through index
+// blocks (gram_chunk44: k_sample1i, the launches that read other values than the side's own ratings and BPMF_HIP_GATHER_STREAM=0)
+template <int K, bool GS>
+__device__ __forceinline__ void sample1_body(const SampleArgs &a, const FusedArgs &f, double *lds)
 {
-    __shared__ __attribute__((aligned(16))) double lds[Geo1<K>::LDS_WORDS];
     const int lane = threadIdx.x;
     int bid = blockIdx.x;
     if (f.gate_host) {
@@ -1043,10 +1118,22 @@ __global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1(SampleArgs a, Fuse
     const int len = a.wi_len[w];
     const int mc = a.wi_mc[w];
 
-    // the first index blocks of the chunk are requested before anything else
+    // the first index blocks (records of the first two groups) of the chunk are requested before anything else
     const int glen = (ablate_bits(a) & 2u) ? 0 : len;
-    const IdxBlock ib0 = load_idx_block(a.rowidx + p0, a.vals + p0, 0, lane, glen, a.zero_row);
-    const IdxBlock ib1 = load_idx_block(a.rowidx + p0, a.vals + p0, 64, lane, glen, a.zero_row);
+    IdxBlock ib0{}, ib1{};
+    gs_raw gr0{}, gr1{};
+    const GatherRec *rec = nullptr;
+    const unsigned slot_bytes = 16u * ((unsigned)lane >> 2);
+    int ng = 0;
+    if constexpr (GS) {
+        rec = a.gs_rec + (size_t)a.gs_g0[w] * 16;
+        ng = (ablate_bits(a) & 2u) ? 0 : a.gs_ng[w];
+        gr0 = load_gs_rec(rec, 0, slot_bytes);
+        gr1 = load_gs_rec(rec, 1, slot_bytes);
+    } else {
+        ib0 = load_idx_block(a.rowidx + p0, a.vals + p0, 0, lane, glen, a.zero_row);
+        ib1 = load_idx_block(a.rowidx + p0, a.vals + p0, 64, lane, glen, a.zero_row);
+    }
 
     // whole column in one item: its normals do not depend on the Gram -- draw them first so that
     // the Philox / log / sqrt chain is off the critical path between the last MFMA and the factorisation
@@ -1063,8 +1150,11 @@ __global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1(SampleArgs a, Fuse
         for (int t = 0; t < NB; ++t) acc[t] = 0.0;
 #pragma unroll
         for (int t = 0; t < NG; ++t) rr[t] = 0.0;
-        gram_chunk44<K>(a.rowidx + p0, a.vals + p0, glen, a.other_items, a.zero_row, a.mean_rating, a.alpha, ib0, ib1, acc, rr, lane,
-                        (ablate_bits(a) & 4u) ? 63 : -1);
+        if constexpr (GS)
+            gram_stream44<K>(rec, ng, a.other_items, a.zero_row, a.alpha, gr0, gr1, slot_bytes, acc, rr, lane);
+        else
+            gram_chunk44<K>(a.rowidx + p0, a.vals + p0, glen, a.other_items, a.zero_row, a.mean_rating, a.alpha, ib0, ib1, acc, rr, lane,
+                            (ablate_bits(a) & 4u) ? 63 : -1);
         if (ablate_bits(a) & 1u) {
             double v = rr[0];
 #pragma unroll
@@ -1106,6 +1196,21 @@ __global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1(SampleArgs a, Fuse
         finish_single<K>(a, col, lds, lane, mc < 0,
                          [&](double *sA, double *sb, int LD, int ln) { assemble44<K>(acc, rr, sA, sb, LD, ln); });
     }
+}
+
+template <int K>
+__global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1(SampleArgs a, FusedArgs f)
+{
+    __shared__ __attribute__((aligned(16))) double lds[Geo1<K>::LDS_WORDS];
+    sample1_body<K, true>(a, f, lds);
+}
+
+// the index-block form
+template <int K>
+__global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1i(SampleArgs a, FusedArgs f)
+{
+    __shared__ __attribute__((aligned(16))) double lds[Geo1<K>::LDS_WORDS];
+    sample1_body<K, false>(a, f, lds);
 }
 
 // ---------------------------------------------------------------------------

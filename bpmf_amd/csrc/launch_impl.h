@@ -107,7 +107,12 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     if (nwork > 0) {                                                 // K <= 32: one work item per single-wave workgroup (k_sample1)
         const FusedArgs &f = self->cur_fused;                        // (all zero outside the fused stateful path)
         const dim3 grid((unsigned)(nwork + (f.gate_host ? 1 : 0) + f.nstat));
-        BPMF_LAUNCH(k_sample1<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
+        if (uses_gather_stream(self) && vals == self->d_vals) {      // the Gram reads the side's gather stream (build_schedule)
+            a.gs_rec = self->d_gs_rec; a.gs_g0 = self->d_gs_g0 + w0; a.gs_ng = self->d_gs_ng + w0;
+            BPMF_LAUNCH(k_sample1<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
+        } else {                                                     // other values than the side's own ratings: index blocks
+            BPMF_LAUNCH(k_sample1i<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
+        }
     }
     return 0;
     }

@@ -232,6 +232,11 @@ struct bpmf_hip_side {
     int32_t *d_hv_col = nullptr, *d_hv_len = nullptr, *d_hv_mc = nullptr, *d_hv_chunk = nullptr; int64_t *d_hv_p0 = nullptr;
     int32_t *d_wi_col = nullptr, *d_wi_len = nullptr, *d_wi_mc = nullptr, *d_wi_chunk = nullptr;
     int64_t *d_wi_p0 = nullptr;
+    // gather stream (mode 1, K <= 32; build_schedule): one 16-byte record per rating in item order, per item its first
+    // group of 16 records and its number of groups.  NULL: not built (BPMF_HIP_GATHER_STREAM=0, another form of the sampler)
+    bpmf::GatherRec *d_gs_rec = nullptr;
+    int32_t *d_gs_g0 = nullptr, *d_gs_ng = nullptr;
+    int64_t gs_groups = 0;                 // groups of 16 records in the stream, the padding groups behind the last item included
     int32_t *d_mc_slot0 = nullptr, *d_mc_nch = nullptr;
     unsigned *d_mc_count = nullptr;
     double *d_partials = nullptr;
@@ -329,6 +334,14 @@ struct bpmf_hip_side {
         bool stop = false;
     } predraw;
 };
+
+// Does a k_sample1 launch of the side read its gather stream?  The stream holds r - mean_rating of the side's OWN ratings:
+// a probit, censored or side-information launch reads other values in their place and keeps the index-block form
+// (k_sample1i), and so does the hot-row profiling switch (BPMF_HIP_ABLATE & 4), which rewrites the row ids.
+inline bool uses_gather_stream(const bpmf_hip_side *s)
+{
+    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->censor && !s->link && !(s->ctx->ablate & 4u);
+}
 
 struct bpmf_hip_test {
     bpmf_hip_side *side = nullptr;

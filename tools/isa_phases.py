@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Static per-phase instruction budget of ONE work item of k_sample1<32> (the headline kernel), from the ISA of the built object:
 
-    python tools/isa_phases.py [bpmf_amd/csrc/k32.o]
+    python tools/isa_phases.py [bpmf_amd/csrc/k32.o] [k_sample1ILi32 | k_sample1iILi32]
 
-The kernel is straight-line code around ONE loop (the 64-rating blocks of the Gram), so its phases can be cut at landmarks of
+(k_sample1: the gather-stream form, a loop trip is two groups of 16 ratings; k_sample1i: the index-block form, a trip is a
+64-rating block.)  The kernel is straight-line code around ONE loop (the Gram), so its phases can be cut at landmarks of
 the instruction stream: the first MFMA (end of the prologue: index loads + the Philox / polar normal draw), the loop's back
 edge, the DPP moves of assemble44 (the cross-block sums of the accumulators), the 2 x 16 v_rsq_f64 of the two-columns-per-step
 Cholesky in finish_single, the v_rcp_f64 of the backward solve.  Printed per phase: VALU / MFMA / LDS / VMEM / SALU
@@ -63,39 +64,28 @@ def kind(m):
 
 def main():
     obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "bpmf_amd", "csrc", "k32.o")
-    ins = disassemble(obj, "k_sample1ILi32")
+    sym = sys.argv[2] if len(sys.argv) > 2 else "k_sample1ILi32"     # (k_sample1iILi32: the index-block form)
+    ins = disassemble(obj, sym)
     n = len(ins)
     addr = {a: i for i, (m, o, a) in enumerate(ins)}
-    mf = [i for i, (m, o, a) in enumerate(ins) if m.startswith("v_mfma")]
+    mf = [i for i, (m, o, a) in enumerate(ins) if m.startswith("v_mfma_f64_4x4x4")]     # (the Gram; the statistics riders use the 16x16x4 shape)
     rsq = [i for i, (m, o, a) in enumerate(ins) if m.startswith("v_rsq_f64")]
     dpp = [i for i, (m, o, a) in enumerate(ins) if "dpp" in m]
-    # the Gram loop: the backward branch whose span holds the most MFMAs
-    loops = []
+    # the Gram loop: the innermost backward branch whose span holds MFMAs (the target is simm16 dwords from the next instruction)
+    body_start = body_end = None
     for i, (m, o, a) in enumerate(ins):
-        if m.startswith("s_cbranch") or m == "s_branch":
-            t = re.search(r"<.*\+0x([0-9a-f]+)>", o)
-            if not t:
-                continue
-            # objdump prints the target as symbol+offset: the function starts at ins[0]'s address
-            tgt = ins[0][2] + int(t.group(1), 16) - (ins[0][2] - ins[0][2])
-            tgt_i = None
-            base = None
-    # simpler: the loop body = from the first MFMA-dense run's start to the back edge `s_cbranch_scc1` that follows >= 100 MFMAs
-    back = [i for i, (m, o, a) in enumerate(ins) if m in ("s_cbranch_scc1", "s_cbranch_scc0", "s_cbranch_vccnz", "s_cbranch_vccz") and i > mf[0]]
-    body_end = None
-    for b in back:
-        if sum(1 for q in mf if q < b) >= 140:
-            body_end = b
-            break
-    # loop start: the instruction the branch jumps back to -- approximate as the first MFMA minus its operand prologue
-    # (find the label by the branch's signed offset, simm16 dwords from the next instruction)
-    word = ins[body_end][1]
-    m16 = re.match(r"(\d+)", word)
-    off = int(m16.group(1))
-    if off >= 32768:
-        off -= 65536
-    tgt_addr = ins[body_end + 1][2] + 4 * off
-    body_start = addr[tgt_addr]
+        if not m.startswith("s_cbranch") or i <= mf[0] or i + 1 >= n:
+            continue
+        m16 = re.match(r"(\d+)", o)
+        off = int(m16.group(1)) if m16 else 0
+        if off >= 32768:
+            off -= 65536
+        tgt = addr.get(ins[i + 1][2] + 4 * off)
+        if off >= 0 or tgt is None or not any(tgt <= q < i for q in mf):
+            continue
+        if body_start is None or i - tgt < body_end - body_start:
+            body_start, body_end = tgt, i
+    per_trip = sum(1 for q in mf if body_start <= q < body_end) // 36   # groups of 16 ratings per trip: 4 (index blocks) or 2 (gather stream)
     draw_rsq = [i for i in rsq if i < body_start]
     fin_rsq = [i for i in rsq if i > body_end]
     # pairs of v_rsq of the factorisation: 32 of them, the first after the DPP block of assemble44
@@ -114,15 +104,16 @@ def main():
     stores = [i for i, (m, o, a) in enumerate(ins) if m.startswith("global_store") and i > bwd_start]
     end_item = stores[0] + 12
     cuts = [("item words, two index blocks, normal draw (Philox rounds, polar test, polar_mult) of a whole column", draw0, body_start, 1),
-            ("Gram: one 64-rating block of the loop (gathers one group ahead, 4 x 36 MFMAs, rhs FMAs)", body_start, body_end + 1, None),
-            ("Gram: last block of the chunk (1-4 groups of 16 ratings)", body_end + 1, park0 - 30, 1),
+            ("Gram: one trip of the loop, %d groups of 16 ratings (gathers one group ahead, %d x 36 MFMAs, rhs FMAs)" % (per_trip, per_trip), body_start, body_end + 1, None),
+            ("Gram: after the loop (index blocks: last block of 1-4 groups; stream: last 1-2 groups)", body_end + 1, park0 - 30, 1),
             ("[chunk hand-over: park partials, ticket, sum partials, second normal draw -- NOT executed by a whole column]", park0 - 30, asm_start, 0),
             ("assembly: cross-block sums (DPP), G -> LDS (mirrored), Lambda* = LambdaF + alpha G, rhs", asm_start, fac_start, 1),
             ("factorisation: 16 steps of two columns (10 readlanes, 2 x 1/sqrt + Halley, scale + publish, rank-2 update, forward solve)", fac_start, bwd_start, 1),
             ("backward solve (31 readlane broadcasts), store, failure check", bwd_start, end_item, 1)]
     nr = int(os.environ.get("RATINGS", "160"))
-    blocks = max(0, (nr - 1) // 64)                               # full loop iterations; the last block runs in the tail code
-    print("k_sample1<32>: %d instructions in the kernel; budget of a whole-column item with %d ratings (%d loop blocks + tail)" % (n, nr, blocks))
+    # trips of the loop; the rest runs in the tail code (index blocks: the last block of 1-4 groups; stream: the last 1-2 groups)
+    blocks = max(0, (nr - 1) // 64) if per_trip == 4 else max(0, ((nr + 15) // 16 - 1) // 2)
+    print("%s: %d instructions in the kernel; budget of a whole-column item with %d ratings (%d loop trips of %d groups + tail)" % (sym, n, nr, blocks, per_trip))
     print("%-118s %6s %6s %6s %6s %6s" % ("phase (static count x times executed)", "VALU", "MFMA", "LDS", "VMEM", "SALU"))
     tot = collections.Counter()
     for name, a0, a1, times in cuts:
