@@ -61,6 +61,16 @@ _SIGNATURES = {
     "bpmf_hip_side_samples_count": (C.c_int, [C.c_void_p]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_predict_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_predict_block_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_newrows_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]),
+    "bpmf_hip_side_newrows_set_sparse": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "bpmf_hip_side_newrows_add": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_newrows_count": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_newrows_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_newrows_get_padded": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_newrows_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_newrows_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_train_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bpmf_hip_noise_sample": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "bpmf_hip_side_set_probit": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),

@@ -22,6 +22,10 @@
 // likelihood: mean rating 0, alpha 1, latent scores redrawn on the device ahead of every sampler launch.
 // After "Final Avg RMSE" the run prints "Final AUC" and "Final Brier" of the posterior-mean probabilities of the test entries,
 // and -o DIR also gets DIR/probit.csv (row,col,label,prob).  Without these flags nothing changes.
+// --new-row-features FILE / --new-col-features FILE (with the matching --row-features / --col-features, -o DIR, -i > -b): users /
+// movies that are NOT in the training matrix, predicted from their features alone: DIR/new-rows-mean.ddm,
+// new-rows-std.ddm (new x movies), new-cols-mean.ddm, new-cols-std.ddm (users x new); with --topn N also DIR/new-rows-topn.csv /
+// new-cols-topn.csv.  std does not include the observation noise 1 / alpha.
 // --row-features FILE / --col-features FILE [--lambda-beta F] (one GPU, no -g): side information.  FILE is a
 // dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
 // -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).  A sparse FILE (.sdm / .sbm /
@@ -103,6 +107,12 @@ void usage()
               << "              not with --probit, --noise adaptive, --fp32, -m / -l or BPMF_REDUCE=1); -o DIR also gets DIR/U-link.ddm / V-link.ddm\n"
               << "              A sparse FILE (.sdm, .sbm = all ones, coordinate .mtx; optional .gz) may have any number of feature columns: beta\n"
               << "              is then drawn by conjugate gradients on the device, F^T F is never formed (a dense FILE keeps 1 .. 1024 columns)\n"
+              << "  [--new-row-features FILE] [--new-col-features FILE]: users / movies that are not in the training matrix, one row of features\n"
+              << "              each (the kind and the D of --row-features / --col-features, which it needs, with -o DIR and -i > -b): predicted from\n"
+              << "              their features against every movie / user, to DIR/new-rows-mean.ddm, new-rows-std.ddm (new x movies) and\n"
+              << "              DIR/new-cols-mean.ddm, new-cols-std.ddm (users x new); std leaves the observation noise 1 / alpha out.  With\n"
+              << "              --topn N also DIR/new-rows-topn.csv / new-cols-topn.csv (--topn-by rows: the best columns of every new row, the\n"
+              << "              best new columns of every row; cols: the columns are the queries); files of more than 2^28 cells need --topn\n"
               << "  [--link-tol F] [--link-max-iter N]: the stopping rule of that CG draw: relative residual (1e-6), most iterations (1000);\n"
               << "              need a sparse feature file\n"
               << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
@@ -271,6 +281,13 @@ struct Job {
     Csc sfeat_u, sfeat_m;                                            // the same from a sparse file: F^T column-compressed = F by rows (D x N)
     int64_t sfeat_u_d = 0, sfeat_m_d = 0;                            // their D (0: none)
     double link_tol = 1e-6; int link_max_iter = 1000;                // --link-tol F / --link-max-iter N (sparse features: the CG draw)
+    // --new-row-features / --new-col-features: n x D row-major, or F by rows from a sparse file; n = 0: none
+    struct NewRows {
+        int64_t n = 0; std::vector<double> F; Csc Fr;
+        bool dense_out = true;                                       // the mean / std files fit the cap of 2^28 cells
+        std::vector<double> mean, std;                               // new x other side, row-major
+        std::vector<int32_t> topn_idx; std::vector<double> topn_mean, topn_std; bool new_are_queries = true;
+    } new_u, new_m;
     bool has_feat_u() const { return !feat_u.data.empty() || sfeat_u_d > 0; }
     bool has_feat_m() const { return !feat_m.data.empty() || sfeat_m_d > 0; }
     std::vector<double> beta_u, beta_m;                              // posterior mean of the link matrices, D x K row-major
@@ -342,10 +359,23 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.has_feat_m()) check(bpmf_hip_side_link_lambda_prior(movies, J.lb_a0, J.lb_b0));
         if (J.has_feat_u()) check(bpmf_hip_side_link_lambda_prior(users, J.lb_a0, J.lb_b0));
     }
-    if (J.topn > 0) {                                                // a ring of the post-burn-in samples of both sides
-        check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
-        check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
-    }
+    // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0, ring_u = J.topn > 0 || J.new_m.n > 0;
+    if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
+    if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
+    auto set_new = [&](bpmf_hip_side *side, const Job::NewRows &N) {
+        if (N.n == 0) return;
+        if (N.F.empty()) {
+            bool ones = true;
+            for (double v : N.Fr.vals) if (v != 1.0) { ones = false; break; }
+            static const int32_t none = 0;
+            check(bpmf_hip_side_newrows_set_sparse(side, N.n, N.Fr.colptr.data(), N.Fr.rowidx.empty() ? &none : N.Fr.rowidx.data(),
+                                                   ones ? nullptr : N.Fr.vals.data(), J.nsims - J.burnin));
+        } else
+            check(bpmf_hip_side_newrows_set(side, N.n, N.F.data(), J.nsims - J.burnin));
+    };
+    set_new(users, J.new_u);
+    set_new(movies, J.new_m);
     if (J.sharded) {
         check(bpmf_hip_side_set_ranges(movies, J.bm.data()));
         check(bpmf_hip_side_set_ranges(users, J.bu.data()));
@@ -418,6 +448,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
             os << "lambda_beta: sampled per side, prior Gamma(shape " << J.lb_a0 << ", rate " << J.lb_b0 << "), initial value " << J.lambda_beta
                << std::endl;
     }
+    if (J.new_u.n > 0) os << "new rows: " << J.new_u.n << " (--new-row-features), predicted from their features over the kept samples" << std::endl;
+    if (J.new_m.n > 0) os << "new columns: " << J.new_m.n << " (--new-col-features), predicted from their features over the kept samples" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -512,7 +544,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
 
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
-        if (J.topn > 0 && iter >= burnin) { check(bpmf_hip_side_samples_add(users)); check(bpmf_hip_side_samples_add(movies)); }
+        if (ring_u && iter >= burnin) check(bpmf_hip_side_samples_add(users));
+        if (ring_m && iter >= burnin) check(bpmf_hip_side_samples_add(movies));
+        if (J.new_u.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(users, movies));
+        if (J.new_m.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(movies, users));
         if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
         if (!cg_warned && (J.sfeat_u_d > 0 || J.sfeat_m_d > 0)) {       // CG at max_iter with a column still active: said once
             int hit_u = 0, hit_m = 0;
@@ -591,6 +626,28 @@ void rank_main(Job &J, int rank, std::ostream &os)
         std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
                   << (tick() - t0) * 1e3 << " ms" << std::endl;
     }
+    // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
+    auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
+        if (N.n == 0) return;
+        const double t0 = tick();
+        if (N.dense_out) {
+            N.mean.resize((size_t)N.n * (size_t)nc); N.std.resize(N.mean.size());
+            const int64_t step = std::max<int64_t>(64, ((int64_t)1 << 24) / std::max<int64_t>(nc, 1) / 64 * 64);
+            for (int64_t q0 = 0; q0 < N.n; q0 += step) {
+                const int64_t q1 = std::min(N.n, q0 + step);
+                check(bpmf_hip_newrows_predict(side, cand, J.mean_m, q0, q1, 0, nc, N.mean.data() + (size_t)q0 * nc, N.std.data() + (size_t)q0 * nc));
+            }
+        }
+        if (J.topn > 0) {
+            N.new_are_queries = by_new;
+            const int64_t nq = by_new ? N.n : nc;
+            N.topn_idx.resize((size_t)nq * J.topn); N.topn_mean.resize(N.topn_idx.size()); N.topn_std.resize(N.topn_idx.size());
+            check(bpmf_hip_newrows_topn(side, cand, J.mean_m, J.topn, by_new ? 1 : 0, N.topn_idx.data(), N.topn_mean.data(), N.topn_std.data()));
+        }
+        std::cerr << "new " << (side == users ? "rows" : "columns") << ": " << N.n << " x " << nc << " predictions, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+    };
+    predict_new(users, movies, J.new_u, nmovies, !J.topn_by_cols);   // --topn-by rows: the new rows are the queries
+    predict_new(movies, users, J.new_m, nusers, J.topn_by_cols);     // --topn-by cols: the new columns are the queries
     if (rank == 0) {
         J.elapsed = elapsed; J.rmse_avg = rmse_avg; J.num_predict = num_predict;
         J.average_items_sec = average_items_sec; J.average_ratings_sec = average_ratings_sec;
@@ -622,8 +679,9 @@ int main(int argc, char *argv[])
                                               {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
                                               {"lambda-beta-prior", required_argument, nullptr, 1013},
                                               {"censored", required_argument, nullptr, 1014},
+                                              {"new-row-features", required_argument, nullptr, 1015}, {"new-col-features", required_argument, nullptr, 1016},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, new_row_features, new_col_features;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -643,6 +701,8 @@ int main(int argc, char *argv[])
         case 1012: link_max_iter = optarg; break;
         case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
         case 1014: censored_file = optarg; J.censored = true; break;
+        case 1015: new_row_features = optarg; break;
+        case 1016: new_col_features = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -733,6 +793,19 @@ int main(int argc, char *argv[])
         return ft.kind == bpmf::io::Kind::mtx && bpmf::io::mtx_is_coordinate(name);
     };
     const bool sparse_u = sparse_file(row_features), sparse_m = sparse_file(col_features);
+    // --new-row-features / --new-col-features: checked before anything touches a GPU
+    auto check_new = [&](const std::string &name, const std::string &have, bool have_sparse, const char *what, const char *partner) {
+        if (name.empty()) return;
+        const std::string w = std::string("--") + what;
+        if (have.empty()) die(w + " needs --" + partner + " (the link matrix is fitted on the features of the training matrix)");
+        if (J.odirname.empty()) die(w + " needs -o DIR (the predictions go to files in DIR)");
+        if (J.nsims <= J.burnin) die(w + " needs at least one post-burn-in sample (-i > -b)");
+        if (sparse_file(name) != have_sparse)
+            die(w + ": " + name + " is " + (have_sparse ? "dense" : "sparse") + ", --" + partner + " " + have + " is " + (have_sparse ? "sparse" : "dense") +
+                " (both files must be of the same kind)");
+    };
+    check_new(new_row_features, row_features, sparse_u, "new-row-features", "row-features");
+    check_new(new_col_features, col_features, sparse_m, "new-col-features", "col-features");
     if ((!link_tol.empty() || !link_max_iter.empty()) && !sparse_u && !sparse_m)
         die("--link-tol / --link-max-iter need a sparse feature file (--row-features / --col-features FILE.sdm, .sbm or a coordinate .mtx)");
     if (!link_tol.empty()) {
@@ -845,6 +918,42 @@ int main(int argc, char *argv[])
     else read_features(row_features, nusers, "row-features", J.feat_u);
     if (sparse_m) read_sparse_features(col_features, nmovies, "col-features", J.sfeat_m, J.sfeat_m_d);
     else read_features(col_features, nmovies, "col-features", J.feat_m);
+
+    // the features of the new entities: the same number of feature columns, finite; n x other side within the cap of a dense file
+    auto read_new = [&](const std::string &name, bool sparse, int64_t D, int64_t nother, const char *what, const char *partner, Job::NewRows &N) {
+        if (name.empty()) return;
+        const std::string w = std::string("--") + what;
+        // the shape is judged before anything of the file's size is scanned or copied
+        auto shape = [&](int64_t n, int64_t d) {
+            if (d != D) die(w + ": " + name + " has " + std::to_string(d) + " feature columns, --" + partner + " has " + std::to_string(D));
+            if (n < 1) die(w + ": " + name + " has no rows");
+            N.n = n;
+            if (n > ((int64_t)1 << 28) / std::max<int64_t>(nother, 1)) {
+                const std::string cells = std::to_string(n) + " x " + std::to_string(nother) + " predictions are more than 2^28 cells per file";
+                if (J.topn < 1) die(w + ": " + cells + ": ask for the best N of every query with --topn N instead");
+                std::cerr << w << ": " << cells << ": the dense mean / std files are skipped, the --topn lists are written" << std::endl;
+                N.dense_out = false;
+            }
+        };
+        if (sparse) {
+            Csc F;
+            try { F = bpmf::io::read_sparse(name); } catch (const std::exception &e) { die(e.what()); }
+            shape(F.nrows, F.ncols);
+            for (double v : F.vals) if (!std::isfinite(v)) die(w + ": " + name + " holds a value that is not finite");
+            N.Fr = bpmf::io::transpose(F);
+        } else {
+            Dense F;
+            try { F = bpmf::io::read_dense(name); } catch (const std::exception &e) { die(e.what()); }
+            const int64_t n = F.nrows, d = F.ncols;
+            shape(n, d);
+            for (double v : F.data) if (!std::isfinite(v)) die(w + ": " + name + " holds a value that is not finite");
+            N.F.resize((size_t)n * (size_t)d);                          // column-major file -> n x D row-major
+            for (int64_t j = 0; j < d; ++j)
+                for (int64_t i = 0; i < n; ++i) N.F[(size_t)i * (size_t)d + (size_t)j] = F.data[(size_t)j * (size_t)n + (size_t)i];
+        }
+    };
+    read_new(new_row_features, sparse_u, sparse_u ? J.sfeat_u_d : J.feat_u.ncols, nmovies, "new-row-features", "row-features", J.new_u);
+    read_new(new_col_features, sparse_m, sparse_m ? J.sfeat_m_d : J.feat_m.ncols, nusers, "new-col-features", "col-features", J.new_m);
 
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {
@@ -1013,6 +1122,43 @@ int main(int argc, char *argv[])
             }
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
     }
+
+    // the new entities: new x movies as it is computed; users x new = the transpose of what is computed (row-major new x users IS
+    // column-major users x new).  Lists: 1-based ids, the new entities numbered by their row in the feature file.
+    auto write_new = [&](Job::NewRows &N, bool rows, int64_t nother) {
+        if (N.n == 0) return;
+        const std::string base = J.odirname + (rows ? "/new-rows" : "/new-cols");
+        try {
+            if (N.dense_out) {
+                for (int which = 0; which < 2; ++which) {
+                    std::vector<double> &src = which ? N.std : N.mean;
+                    Dense d;
+                    if (rows) {                                        // row-major new x movies -> column-major
+                        d.nrows = N.n; d.ncols = nother; d.data.resize(src.size());
+                        for (int64_t i = 0; i < N.n; ++i)
+                            for (int64_t c = 0; c < nother; ++c) d.data[(size_t)c * (size_t)N.n + (size_t)i] = src[(size_t)i * (size_t)nother + (size_t)c];
+                    } else { d.nrows = nother; d.ncols = N.n; d.data.swap(src); }
+                    bpmf::io::write_dense(base + (which ? "-std.ddm" : "-mean.ddm"), d);
+                }
+            }
+        } catch (const std::exception &e) { die(e.what()); }
+        if (J.topn > 0) {
+            const std::string name = base + "-topn.csv";
+            FILE *f = fopen(name.c_str(), "w");
+            if (!f) die("cannot write " + name);
+            fprintf(f, "query,rank,candidate,mean,std\n");
+            const int64_t nq = (int64_t)(N.topn_idx.size() / (size_t)J.topn);
+            for (int64_t q = 0; q < nq; ++q)
+                for (int r = 0; r < J.topn; ++r) {
+                    const size_t at = (size_t)q * J.topn + r;
+                    if (N.topn_idx[at] < 0) break;                     // (padding slots are not written)
+                    fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", (long long)(q + 1), r + 1, (long long)(N.topn_idx[at] + 1), N.topn_mean[at], N.topn_std[at]);
+                }
+            if (fclose(f) != 0) die("cannot write " + name);
+        }
+    };
+    write_new(J.new_u, true, nmovies);
+    write_new(J.new_m, false, nusers);
 
     if (J.lb_sampled && !J.odirname.empty()) {                       // a cell is empty where a side has no features
         FILE *f = fopen((J.odirname + "/lambda_beta.csv").c_str(), "w");

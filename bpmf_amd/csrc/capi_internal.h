@@ -6,13 +6,14 @@
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
+//   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last six (probit, censoring, features, sample ring, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last seven (probit, censoring, features, sample ring, new rows, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -64,6 +65,17 @@ inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.
 int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, unsigned tag, size_t part_words, std::unique_ptr<bpmf_link> *out);
 int ensure_state(bpmf_hip_side *s);                                    // (capi_sample.hip) the Sys state of a side: cov, hyper-parameters
+
+// C (N x ncw, leading dimension ldc) = A B on k_link_gemm_nn, columns n .. ncw - 1 zero (capi_link.hip)
+int link_nn_product(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t N, int Dr, int n, double *C, int64_t ldc, int ncw, hipStream_t st);
+// canonical CSR or a refusal reported as `who` (capi_link_sparse.hip)
+int link_check_csr(const char *who, int64_t N, int64_t D, const int64_t *rowptr, const int32_t *colidx, const double *vals);
+
+// posterior top-N over two rings of S samples (capi_topn.hip): what bpmf_hip_topn and bpmf_hip_newrows_topn share.  Queries
+// [q_from, q_from + nq) of qring against the candidates [0, nc) of cring; ex_ptr / ex_rows: the exclusion lists or NULL.  Waits.
+struct TopnRings { const double *qring, *cring; int64_t qstride, cstride; int kp, S; };
+int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
+               const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out);
 
 // evaluation (capi_eval.hip)
 void flush_deferred(bpmf_hip_test *t, bool on_main = false);           // enqueues an evaluation whose launch was put off

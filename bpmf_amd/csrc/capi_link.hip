@@ -127,6 +127,11 @@ int link_tn_product(const double *A, int64_t lda, const double *B, int64_t ldb, 
     return tn_product(A, lda, B, ldb, bvec, N, D, n, C, ldc, part, st);
 }
 
+int link_nn_product(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t N, int Dr, int n, double *C, int64_t ldc, int ncw, hipStream_t st)
+{
+    return nn_product(A, lda, B, ldb, N, Dr, n, C, ldc, ncw, st);
+}
+
 int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, unsigned tag, size_t part_words, std::unique_ptr<bpmf_link> *out)
 {
     const std::string w(who);

@@ -67,6 +67,11 @@ int upload_both(SpMat &F, SpMat &Ft, int64_t N, int64_t D, const int64_t *rowptr
 
 namespace bpmf_capi {
 
+int link_check_csr(const char *who, int64_t N, int64_t D, const int64_t *rowptr, const int32_t *colidx, const double *vals)
+{
+    return check_csr(who, N, D, rowptr, colidx, vals);
+}
+
 int link_sparse_offsets(bpmf_hip_side *s)
 {
     const bpmf_hip_ctx *c = s->ctx;

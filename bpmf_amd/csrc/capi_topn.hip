@@ -68,6 +68,42 @@ static int build_exclusion(bpmf_hip_side *s)
     return 0;
 }
 
+namespace bpmf_capi {
+
+int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
+               const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out)
+{
+    // candidates split over workgroups when the query blocks alone do not fill the device (a split is a multiple of 64 candidates)
+    const int64_t nqb = (nq + 63) / 64;
+    int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)c->num_cu + nqb - 1) / nqb, (nc + 255) / 256));
+    const int64_t cspan = ((nc + nsplit - 1) / nsplit + 63) / 64 * 64;
+    nsplit = (nc + cspan - 1) / cspan;
+
+    const size_t pn = (size_t)nq * (size_t)n;
+    DevBuf<double> part_mean, out;
+    DevBuf<int32_t> part_idx, out_idx;
+    if (part_mean.alloc((size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(2 * pn) || out_idx.alloc(pn))
+        return fail(BPMF_HIP_ENOMEM, "topn: device allocation of the result lists failed");
+    bpmf_launch::TopnLaunch p{};
+    p.qring = r.qring; p.cring = r.cring;
+    p.qstride = r.qstride; p.cstride = r.cstride;
+    p.Kp = r.kp; p.S = r.S; p.n = n; p.mean_rating = mean_rating;
+    p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
+    p.ex_ptr = ex_ptr; p.ex_rows = ex_rows;
+    p.part_mean = part_mean.get(); p.part_idx = part_idx.get();
+    p.out_mean = out.get(); p.out_std = out.get() + pn; p.out_idx = out_idx.get();
+    bpmf_launch::topn(p, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
+    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    if (hipMemcpy(mean_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(std_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
+    return BPMF_HIP_OK;
+}
+
+}  // namespace bpmf_capi
+
 extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                              int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out)
 {
@@ -92,32 +128,7 @@ extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double m
         return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs the query side's rows to be the candidate side's columns");
     if (nq == 0) return BPMF_HIP_OK;
     if (exclude_rated) { const int rc = build_exclusion(query); if (rc) return rc; }
-
-    // candidates split over workgroups when the query blocks alone do not fill the device (a split is a multiple of 64 candidates)
-    const int64_t nc = cand->ncols, nqb = (nq + 63) / 64;
-    int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)c->num_cu + nqb - 1) / nqb, (nc + 255) / 256));
-    const int64_t cspan = ((nc + nsplit - 1) / nsplit + 63) / 64 * 64;
-    nsplit = (nc + cspan - 1) / cspan;
-
-    const size_t pn = (size_t)nq * (size_t)n;
-    DevBuf<double> part_mean, out;
-    DevBuf<int32_t> part_idx, out_idx;
-    if (part_mean.alloc((size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(2 * pn) || out_idx.alloc(pn))
-        return fail(BPMF_HIP_ENOMEM, "topn: device allocation of the result lists failed");
-    bpmf_launch::TopnLaunch p{};
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
-    p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
-    p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
-    p.part_mean = part_mean.get(); p.part_idx = part_idx.get();
-    p.out_mean = out.get(); p.out_std = out.get() + pn; p.out_idx = out_idx.get();
-    bpmf_launch::topn(p, c->stream);
-    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
-    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
-    if (hipMemcpy(mean_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
-    return BPMF_HIP_OK;
+    const TopnRings r{qr->samples.get(), cr->samples.get(), (int64_t)qr->max * qr->kp, (int64_t)cr->max * cr->kp, qr->kp, S};
+    return topn_rings(c, r, mean_rating, n, q_from, nq, cand->ncols, exclude_rated ? qr->ex_ptr.get() : nullptr,
+                      exclude_rated ? qr->ex_rows.get() : nullptr, idx_out, mean_out, std_out);
 }

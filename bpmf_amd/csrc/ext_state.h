@@ -3,6 +3,7 @@
 #pragma once
 #include <limits>
 #include <memory>
+#include <vector>
 
 #include "devbuf.h"
 
@@ -82,6 +83,22 @@ struct bpmf_link {
 // posterior top-N (capi_topn.hip): ring of kept samples, fp64, column c / sample s / row k at c * max * kp + s * kp + k, and the
 // sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
 struct bpmf_ring { DevBuf<double> samples; int max = 0, count = 0, kp = 0; DevBuf<int64_t> ex_ptr; DevBuf<int32_t> ex_rows; };
+
+// rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as
+// exactly one of dense (n x D, row-major) / sparse; the ring of their projected factors E[i, s, :] = mu_s + beta_s^T f_i (layout
+// of bpmf_ring); w[c] = sum_s v_s(c)^T Lambda_s^-1 v_s(c) over the columns of the other side (nw of them; divided by the count
+// when read); Y = V R^-1 of the newest sample (nw x kp), R^-1 and mu of it, and two pinned halves (R^-1 | mu) the copies to them
+// are made from in turn, each with the event that says its last copy is done
+struct bpmf_newrows {
+    int64_t n = 0, nw = 0; int D = 0, max = 0, count = 0, kp = 0;
+    DevBuf<double> F; std::unique_ptr<bpmf_launch::SpMat> sp;
+    DevBuf<double> ring, w, y, rinv, mu;
+    Pinned<double> stage; hipEvent_t staged[2] = {nullptr, nullptr};
+    bpmf_newrows() = default;
+    bpmf_newrows(const bpmf_newrows &) = delete;
+    bpmf_newrows &operator=(const bpmf_newrows &) = delete;
+    ~bpmf_newrows() { for (hipEvent_t e : staged) if (e) (void)hipEventDestroy(e); }
+};
 
 // adaptive noise (capi_noise.hip): the block partials | sum of bpmf_hip_train_sse
 struct bpmf_sse { DevBuf<double> part; int nblk = 0; };

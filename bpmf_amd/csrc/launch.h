@@ -133,6 +133,18 @@ struct TopnLaunch {
 };
 void topn(const TopnLaunch &p, hipStream_t st);             // score + select, merge of the splits, std of the selected pairs
 
+// dense blocks of predictions from two sample rings; rows unseen in training (kernels_predblock.h, kpredblock.hip)
+struct PredBlockLaunch {
+    const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column
+    int Kp, S; double mean_rating;
+    int64_t q_from, nq, c_from, nc;                        // queries [q_from, q_from + nq), candidates [c_from, c_from + nc)
+    const double *w;                                       // added to the variance as w[candidate id] / S, or NULL
+    double *mean, *std;                                    // nq x nc, row-major
+};
+int predict_block(const PredBlockLaunch &p, hipStream_t st);   // -1: shape not supported (nothing launched)
+void rowsq_add(const double *Y, int64_t ldy, int n, int64_t ncols, double *w, hipStream_t st);      // w[c] += |Y[c][0 .. n)|^2
+void ring_add_mu(double *ring, int64_t stride, int slot, int Kp, int Kt, int64_t nrows, const double *mu, hipStream_t st);
+
 // training residuals for the adaptive noise precision (kernels_noise.h, knoise.hip)
 struct SseLaunch {
     const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)

@@ -267,6 +267,101 @@ class HipEngine:
                                           1 if exclude_rated else 0, _ptr(idx), _ptr(mean), _ptr(std)))
         return idx, mean, std
 
+    def predict_block(self, query, cand, mean_rating, q_from=0, q_to=None, c_from=0, c_to=None):
+        """(mean, std), [q_to - q_from, c_to - c_from] each: the posterior-mean prediction and its spread over the samples of the
+        two sides' rings for every pair of the block, in one kernel.  The bits of an element do not depend
+        on the ranges.  std does not include the observation noise 1 / alpha."""
+        q_to = query.ncols if q_to is None else int(q_to)
+        c_to = cand.ncols if c_to is None else int(c_to)
+        mean = np.empty((max(0, q_to - int(q_from)), max(0, c_to - int(c_from))))
+        std = np.empty_like(mean)
+        _lib.check(self.lib.bpmf_hip_predict_block(query.handle, cand.handle, float(mean_rating), int(q_from), q_to, int(c_from), c_to,
+                                                   _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def predict_block_device(self, query, cand, mean_rating, mean_ptr, std_ptr, q_from=0, q_to=None, c_from=0, c_to=None):
+        """predict_block into two device addresses of (q_to - q_from) (c_to - c_from) doubles each on the engine's device, written
+        in place by the kernel: for a consumer on the device (tools/predblock_bench.py)."""
+        q_to = query.ncols if q_to is None else int(q_to)
+        c_to = cand.ncols if c_to is None else int(c_to)
+        _lib.check(self.lib.bpmf_hip_predict_block_device(query.handle, cand.handle, float(mean_rating), int(q_from), q_to, int(c_from), c_to,
+                                                          C.c_void_p(int(mean_ptr)), C.c_void_p(int(std_ptr))))
+
+    # -- rows unseen in training ----------------------------------------------
+    def newrows_set(self, side, F, max_samples):
+        """Gives a side with features the feature rows F [n_new, D] of entities that are not in the training matrix, and room for
+        max_samples projected samples of them.  F is of the kind of the side's features (a dense ndarray
+        or a scipy.sparse matrix) with the same D.  Calling again replaces them; F = None or max_samples = 0 frees them."""
+        if F is None or int(max_samples) == 0:
+            _lib.check(self.lib.bpmf_hip_side_newrows_set(side.handle, 0, None, 0))
+            side.newrows_n = 0
+            return
+        D = getattr(side, "link_d", None)
+        if D is None:
+            raise ValueError("newrows_set: the side has no features (set_features)")
+        if not _is_sparse(F):
+            F = np.asarray(F, np.float64)
+        if _is_sparse(F) != bool(getattr(side, "link_sparse", False)):
+            raise ValueError("newrows_set: the side's features are %s, the new rows' must be of the same kind"
+                             % ("sparse" if getattr(side, "link_sparse", False) else "dense"))
+        if F.ndim != 2 or F.shape[1] != D:
+            raise ValueError("newrows_set: F must be [n_new, %d], the side's features have D = %d" % (D, D))
+        if F.shape[0] < 1:
+            raise ValueError("newrows_set: n_new must be >= 1")
+        if _is_sparse(F):
+            rowptr, colidx, vals = csr_arrays(F)
+            _lib.check(self.lib.bpmf_hip_side_newrows_set_sparse(side.handle, int(F.shape[0]), _ptr(rowptr), _ptr(colidx), _ptr(vals),
+                                                                 int(max_samples)))
+        else:
+            F = np.ascontiguousarray(F, np.float64)
+            _lib.check(self.lib.bpmf_hip_side_newrows_set(side.handle, int(F.shape[0]), _ptr(F), int(max_samples)))
+        side.newrows_n = int(F.shape[0])
+
+    def newrows_add(self, side, other):
+        """Projects the side's new rows with its current beta and mu into the next slot and adds v^T Lambda^-1 v of the other side's
+        current factors to w (where link_add sits: after a post-burn-in iteration, both sides sampled)."""
+        _lib.check(self.lib.bpmf_hip_side_newrows_add(side.handle, other.handle))
+
+    def newrows_count(self, side):
+        return int(self.lib.bpmf_hip_side_newrows_count(side.handle))
+
+    def newrows_get(self, side, padded=False):
+        """(E [n_new, S, K]: the projected factors mu_s + beta_s^T f of every new row and kept sample, w [nrows of the side]:
+        (1/S) sum_s v_s(c)^T Lambda_s^-1 v_s(c) per column of the other side).  padded=True: E alone as the ring stores it,
+        [n_new, S, Kp] with Kp = K rounded up to a multiple of 4; the components k >= K are the ring's zero padding."""
+        S = self.newrows_count(side)
+        if padded:
+            E = np.empty((getattr(side, "newrows_n", 0), S, (self.K + 3) // 4 * 4))
+            _lib.check(self.lib.bpmf_hip_side_newrows_get_padded(side.handle, _ptr(E)))
+            return E
+        E = np.empty((getattr(side, "newrows_n", 0), S, self.K)); w = np.empty(side.nrows)
+        _lib.check(self.lib.bpmf_hip_side_newrows_get(side.handle, _ptr(E), _ptr(w)))
+        return E, w
+
+    def newrows_predict(self, side, cand, mean_rating, q_from=0, q_to=None, c_from=0, c_to=None):
+        """(mean, std), [q_to - q_from, c_to - c_from] each, of the side's new rows [q_from, q_to) against the columns [c_from, c_to)
+        of `cand` (the side's partner, with a sample ring of as many samples).  std joins the spread between the samples with the
+        spread of a cold row's factors around their conditional mean; it does not include the observation noise 1 / alpha."""
+        q_to = getattr(side, "newrows_n", 0) if q_to is None else int(q_to)
+        c_to = cand.ncols if c_to is None else int(c_to)
+        mean = np.empty((max(0, q_to - int(q_from)), max(0, c_to - int(c_from))))
+        std = np.empty_like(mean)
+        _lib.check(self.lib.bpmf_hip_newrows_predict(side.handle, cand.handle, float(mean_rating), int(q_from), q_to, int(c_from), c_to,
+                                                     _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def newrows_topn(self, side, cand, mean_rating, n, new_are_queries=True):
+        """(idx int32, mean, std), [n_new, n] each: the n best columns of `cand` for every new row of `side`; or, with
+        new_are_queries=False, [cand.ncols, n]: the n best new rows for every column of `cand`.  Nothing is excluded (new rows
+        rated nothing); std is the total one of newrows_predict.  Empty slots: idx -1, mean 0, std 0."""
+        nq = getattr(side, "newrows_n", 0) if new_are_queries else cand.ncols
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        mean = np.empty((nq, int(n)))
+        std = np.empty((nq, int(n)))
+        _lib.check(self.lib.bpmf_hip_newrows_topn(side.handle, cand.handle, float(mean_rating), int(n), 1 if new_are_queries else 0,
+                                                  _ptr(idx), _ptr(mean), _ptr(std)))
+        return idx, mean, std
+
     # -- adaptive noise precision ----------------------------------------------
     def train_sse(self, side, other):
         """(SSE, n): the sum of squared training residuals (v - mean - x_c . y_r)^2 over the n ratings of `side`, with the

@@ -186,7 +186,8 @@ class Sys:
 
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
-          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None):
+          row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
+          new_row_features=None, new_col_features=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -242,7 +243,33 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     6 = users; those of Mt from C transposed) and redraw the latent values of their censored cells ahead of every sampler launch,
     on the device, without a host wait: the pipelined loop does not drain.  Any alpha > 0, with or without topn; the test matrix
     is taken as exact values.  probit=True, noise="adaptive" and features are refused with censored.  res["censored"] = (lower
-    bounds, upper bounds).  None (the default): nothing changes."""
+    bounds, upper bounds).  None (the default): nothing changes.
+
+    new_row_features [n_new, D] / new_col_features [n_new, D]: users (movies) that are NOT in the training matrix, predicted from
+    their features alone.  Needs row_features (col_features) of the same kind and D, and nsims > burnin.
+    Every post-burn-in iteration projects them with that iteration's mu and beta (engine.newrows_add; nsims - burnin slots) and
+    keeps the other side's factors in its sample ring (reserved here when topn did not).  res["new_rows"] = dict(mean, std),
+    [n_new, nmovies] each, res["new_cols"] = dict(mean, std), [nusers, n_new] each: the mean over the kept samples of mean_rating
+    + (mu_s + beta_s^T f) . v_s and the total deviation -- the spread between the samples joined with the spread of a cold row's
+    factors around their conditional mean, (1/S) sum_s v_s^T Lambda_s^-1 v_s.  The observation noise 1 / alpha is not part of std.
+    With topn=N also res["new_rows_topn"] / res["new_cols_topn"] = (idx, mean, std), [n_new, N] each, the new entities as the
+    queries.  None (the default): nothing changes."""
+    for new, have, nn, hn in ((new_row_features, row_features, "new_row_features", "row_features"),
+                              (new_col_features, col_features, "new_col_features", "col_features")):
+        if new is None:
+            continue
+        if have is None:
+            raise ValueError("%s needs %s (the link matrix is fitted on the training entities' features)" % (nn, hn))
+        if _engine._is_sparse(new) != _engine._is_sparse(have):
+            raise ValueError("%s and %s must be of the same kind (both dense or both sparse)" % (nn, hn))
+        if not _engine._is_sparse(new):
+            new = np.asarray(new, np.float64)
+        if new.ndim != 2 or new.shape[0] < 1 or new.shape[1] != np.shape(have)[1]:
+            raise ValueError("%s must be [n_new >= 1, %d]: the D of %s" % (nn, np.shape(have)[1], hn))
+        if not np.all(np.isfinite(new.data if _engine._is_sparse(new) else new)):
+            raise ValueError("%s holds a value that is not finite" % nn)
+        if nsims - burnin < 1:
+            raise ValueError("%s needs at least one post-burn-in sample (nsims > burnin)" % nn)
     linked = row_features is not None or col_features is not None
     if censored is not None:
         if probit:
@@ -320,9 +347,16 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    if topn is not None:
+    ring_movies = topn is not None or new_row_features is not None       # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None
+    if ring_movies:
         engine.samples_reserve(movies.side, nsims - burnin)
+    if ring_users:
         engine.samples_reserve(users.side, nsims - burnin)
+    if new_row_features is not None:
+        engine.newrows_set(users.side, new_row_features, nsims - burnin)
+    if new_col_features is not None:
+        engine.newrows_set(movies.side, new_col_features, nsims - burnin)
 
     if linked and sparse_sides:
         res["link_cg_iters"] = []
@@ -332,9 +366,14 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         res["lambda_beta_cols"] = [] if col_features is not None else None
 
     def keep(i):                                     # where the -o aggregation sits (bpmf_main.cpp)
-        if topn is not None and i >= burnin:
+        if ring_users and i >= burnin:
             engine.samples_add(users.side)
+        if ring_movies and i >= burnin:
             engine.samples_add(movies.side)
+        if new_row_features is not None and i >= burnin:
+            engine.newrows_add(users.side, movies.side)
+        if new_col_features is not None and i >= burnin:
+            engine.newrows_add(movies.side, users.side)
         if probit and i >= burnin and movies.test is not None:
             engine.probit_add(movies.test, movies.side, users.side)
         if linked and i >= burnin:
@@ -432,6 +471,16 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if linked:
         res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
         res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None
+    if new_row_features is not None:
+        mean, std = engine.newrows_predict(users.side, movies.side, movies.mean_rating)
+        res["new_rows"] = dict(mean=mean, std=std)
+        if topn is not None:
+            res["new_rows_topn"] = engine.newrows_topn(users.side, movies.side, movies.mean_rating, topn)
+    if new_col_features is not None:
+        mean, std = engine.newrows_predict(movies.side, users.side, movies.mean_rating)
+        res["new_cols"] = dict(mean=mean.T.copy(), std=std.T.copy())
+        if topn is not None:
+            res["new_cols_topn"] = engine.newrows_topn(movies.side, users.side, movies.mean_rating, topn)
     res["movies"], res["users"] = movies, users
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)

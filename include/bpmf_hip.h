@@ -286,6 +286,52 @@ BPMF_API int bpmf_hip_side_samples_count(const bpmf_hip_side *side);
 BPMF_API int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                            int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out);
 
+/* ---- dense blocks of predictions; rows unseen in training ---------
+ * bpmf_hip_predict_block: for every query column q in [q_from, q_to) of `query` and every candidate column c in [c_from, c_to)
+ * of `cand`, from the sample rings of both sides (the same S >= 1 samples, bpmf_hip_side_samples_add): mean and std as
+ * bpmf_hip_topn defines them, to the host arrays mean_out / std_out, (q_to - q_from) x (c_to - c_from) row-major.  One kernel,
+ * no intermediate of S blocks; an element's bits do not depend on the ranges or the call.  Works on fp32 contexts (the rings are
+ * fp64).  Waits.  The observation noise 1 / alpha is NOT part of std.
+ * bpmf_hip_predict_block_device: the same with mean_dev / std_dev in device memory of the context's device (anything else is
+ * BPMF_HIP_EINVAL), which the kernel writes in place: for a consumer on the device, and for timing the kernel without the copies.
+ *
+ * New rows: a side with features draws u ~ N(mu_s + beta_s^T f, Lambda_s^-1) in kept sample s, so an entity that was not in the
+ * training matrix is predicted from its features f alone: e_s = mu_s + beta_s^T f, p_s = mean_rating + e_s . v_s(c),
+ *   mean = (1/S) sum_s p_s,   var = sum_s (p_s - mean)^2 / (S - 1) + (1/S) sum_s v_s(c)^T Lambda_s^-1 v_s(c),   std = sqrt(var)
+ * (the law of total variance over the kept samples; the first term is 0 for S = 1; 1 / alpha is not included).
+ *   _newrows_set / _set_sparse  n_new >= 1 feature rows (dense: n_new x D row-major, D that of the side's features; sparse:
+ *       canonical CSR as bpmf_hip_side_set_features_sparse, vals NULL = ones) of the same kind as the side's features, finite, and
+ *       room for max_samples projected samples.  Calling again replaces them; max_samples = 0 frees them (side_destroy does too).
+ *       BPMF_HIP_ENOMEM names the size that did not fit.
+ *   _newrows_add(side, other)   where bpmf_hip_side_link_add sits, after a post-burn-in iteration with both sides sampled:
+ *       projects the new rows into the next slot with the side's current beta, mu, and adds v(c)^T Lambda^-1 v(c) of the current
+ *       factors of `other` and the side's current Lambda to w[c].  Enqueue only.  BPMF_HIP_EINVAL once max_samples are held.
+ *   _newrows_get                E (n_new x S x K, the projected factors) and w (one per column of `other`, divided by S); either
+ *       may be NULL.  Waits.
+ *   _newrows_get_padded         E as the ring stores it, n_new x S x Kp with Kp = K rounded up to a multiple of 4: the components
+ *       k >= K of every sample are the zero padding the kernels rely on.  Waits.
+ *   bpmf_hip_newrows_predict    bpmf_hip_predict_block with the new rows of `side` as the queries and the sample ring of `cand`
+ *       (the side's partner; the same number >= 1 of samples, else BPMF_HIP_EINVAL) as the candidates, std with the second term.
+ *   bpmf_hip_newrows_topn       bpmf_hip_topn without exclusion (new rows rated nothing) with the new rows as the queries
+ *       (new_are_queries != 0: n_new x n) or as the candidates (0: for every column of `cand` the n best new rows, ncols x n);
+ *       std is the total one.
+ * Every entry point needs both sides whole on a context without a communicator. */
+BPMF_API int bpmf_hip_predict_block(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                    int64_t c_from, int64_t c_to, double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_predict_block_device(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                           int64_t c_from, int64_t c_to, double *mean_dev, double *std_dev);
+BPMF_API int bpmf_hip_side_newrows_set(bpmf_hip_side *side, int64_t n_new, const double *F_host, int max_samples);
+BPMF_API int bpmf_hip_side_newrows_set_sparse(bpmf_hip_side *side, int64_t n_new, const int64_t *rowptr, const int32_t *colidx,
+                                              const double *vals, int max_samples);
+BPMF_API int bpmf_hip_side_newrows_add(bpmf_hip_side *side, bpmf_hip_side *other);
+BPMF_API int bpmf_hip_side_newrows_count(const bpmf_hip_side *side);
+BPMF_API int bpmf_hip_side_newrows_get(bpmf_hip_side *side, double *E_host, double *w_host);
+BPMF_API int bpmf_hip_side_newrows_get_padded(bpmf_hip_side *side, double *E_host);
+BPMF_API int bpmf_hip_newrows_predict(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                      int64_t c_from, int64_t c_to, double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_newrows_topn(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int n, int new_are_queries,
+                                   int32_t *idx_out, double *mean_out, double *std_out);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
