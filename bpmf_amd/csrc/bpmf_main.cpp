@@ -15,6 +15,9 @@
 // --topn N (with -o DIR, one GPU): the N unrated items of every user with the highest posterior-mean prediction over the kept
 // samples, and its spread, to DIR/topn.csv (query,rank,candidate,mean,std; 1-based ids in the numbering of the input);
 // --topn-by cols ranks the users of every item instead.  stdout is the same as without it.
+// --topn-score ucb|prob|ei ranks by an acquisition score of the kept samples instead of their mean:
+// mean + kappa std (--topn-kappa), the posterior probability that a rating exceeds --topn-threshold, or the expected excess over
+// it, with sigma = 1 / sqrt(-a) (1 under --probit); topn.csv then has the columns query,rank,candidate,score,mean,std.
 // --noise adaptive (one GPU, no -g): the noise precision is sampled after every iteration from its Gamma posterior (prior
 // --alpha-prior A0,B0, default 1,1; cap --alpha-max F), -a is its initial value; every iteration line then ends with the alpha
 // it ran with and the training RMSE after it, and -o DIR also gets DIR/alpha.csv.
@@ -72,7 +75,7 @@ double tick()
 
 void usage()
 {
-    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols]]"
+    std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
               << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE]\n"
               << "\n"
               << "Parameters:\n"
@@ -96,6 +99,13 @@ void usage()
               << "  [--topn N]: the N unrated items of every user with the highest posterior-mean prediction, with its standard\n"
               << "              deviation over the kept samples, to DIR/topn.csv (needs -o DIR; one GPU; 1 <= N <= 32)\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
+              << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
+              << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
+              << "              observation noise is sigma = 1 / sqrt(-a), 1 under --probit.  DIR/topn.csv then has the columns\n"
+              << "              query,rank,candidate,score,mean,std\n"
+              << "  [--topn-kappa F]: kappa of ucb (default 1; negative: a lower confidence bound)\n"
+              << "  [--topn-threshold F]: the threshold of prob and ei, required with them; on the rating scale, or on the\n"
+              << "              latent-score scale under --probit (0 is the natural value there)\n"
               << "  [--noise fixed|adaptive]: fixed: alpha = -a throughout (the default); adaptive: alpha is sampled after every\n"
               << "              iteration from its Gamma posterior given the training residuals, -a is its initial value (one GPU)\n"
               << "  [--alpha-prior A0,B0]: Gamma prior of the adaptive alpha, shape A0 > 0 and rate B0 >= 0 (1,1)\n"
@@ -264,6 +274,9 @@ struct Job {
     int topn = 0;                                                    // --topn N (0: off)
     bool topn_by_cols = false;                                       // --topn-by cols: rank the rows (users) of every column (item)
     std::vector<int32_t> topn_idx; std::vector<double> topn_mean, topn_std;   // queries x N, in the numbering of the run
+    int topn_kind = -1;                                              // --topn-score: -1 mean, else BPMF_HIP_SCORE_*
+    double topn_param = 0.0, topn_sigma = 0.0;                       // kappa or the threshold; the observation noise of prob / ei
+    std::vector<double> topn_score;
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
@@ -622,7 +635,16 @@ void rank_main(Job &J, int rank, std::ostream &os)
         bpmf_hip_side *q = J.topn_by_cols ? movies : users, *cand = J.topn_by_cols ? users : movies;
         const int64_t nq = J.topn_by_cols ? nmovies : nusers;
         J.topn_idx.resize((size_t)nq * J.topn); J.topn_mean.resize(J.topn_idx.size()); J.topn_std.resize(J.topn_idx.size());
-        check(bpmf_hip_topn(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_idx.data(), J.topn_mean.data(), J.topn_std.data()));
+        if (J.topn_kind < 0) {
+            check(bpmf_hip_topn(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_idx.data(), J.topn_mean.data(), J.topn_std.data()));
+        } else {
+            J.topn_score.resize(J.topn_idx.size());
+            check(bpmf_hip_topn_scored(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_kind, J.topn_param, J.topn_sigma, J.topn_idx.data(),
+                                       J.topn_score.data(), J.topn_mean.data(), J.topn_std.data()));
+            if (J.topn_kind == BPMF_HIP_SCORE_UCB) std::cerr << "topn score: ucb, kappa = " << J.topn_param << std::endl;
+            else std::cerr << "topn score: " << (J.topn_kind == BPMF_HIP_SCORE_PROB ? "prob" : "ei") << ", threshold = " << J.topn_param
+                           << ", sigma = " << J.topn_sigma << std::endl;
+        }
         std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
                   << (tick() - t0) * 1e3 << " ms" << std::endl;
     }
@@ -680,8 +702,12 @@ int main(int argc, char *argv[])
                                               {"lambda-beta-prior", required_argument, nullptr, 1013},
                                               {"censored", required_argument, nullptr, 1014},
                                               {"new-row-features", required_argument, nullptr, 1015}, {"new-col-features", required_argument, nullptr, 1016},
+                                              {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
+                                              {"topn-threshold", required_argument, nullptr, 1019},
                                               {nullptr, 0, nullptr, 0}};
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, new_row_features, new_col_features;
+    std::string topn_score = "mean", topn_kappa, topn_threshold;
+    bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -703,6 +729,9 @@ int main(int argc, char *argv[])
         case 1014: censored_file = optarg; J.censored = true; break;
         case 1015: new_row_features = optarg; break;
         case 1016: new_col_features = optarg; break;
+        case 1017: topn_score = optarg; break;
+        case 1018: topn_kappa = optarg; topn_kappa_given = true; break;
+        case 1019: topn_threshold = optarg; topn_threshold_given = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -734,6 +763,32 @@ int main(int argc, char *argv[])
     // --noise / --alpha-prior / --alpha-max: checked before anything touches a GPU
     if (noise != "fixed" && noise != "adaptive") die("--noise expects fixed or adaptive, not '" + noise + "'");
     J.adaptive = noise == "adaptive";
+    // --topn-score / --topn-kappa / --topn-threshold: checked before anything touches a GPU
+    {
+        if (topn_score != "mean" && topn_score != "ucb" && topn_score != "prob" && topn_score != "ei")
+            die("--topn-score expects mean, ucb, prob or ei, not '" + topn_score + "'");
+        const bool ucb = topn_score == "ucb", thr = topn_score == "prob" || topn_score == "ei";
+        if (topn_score != "mean" && J.topn < 1) die("--topn-score " + topn_score + " needs --topn N (it ranks the top-N lists)");
+        if (topn_kappa_given && !ucb) die("--topn-kappa goes with --topn-score ucb only");
+        if (topn_threshold_given && !thr) die("--topn-threshold goes with --topn-score prob or ei only");
+        auto number = [&](const std::string &text, const char *flag) {
+            char *e = nullptr;
+            const double v = strtod(text.c_str(), &e);
+            if (e == text.c_str() || *e != '\0' || !std::isfinite(v)) die(std::string(flag) + " expects a finite number, not '" + text + "'");
+            return v;
+        };
+        if (thr && !topn_threshold_given) die("--topn-score " + topn_score + " needs --topn-threshold F");
+        if (thr && J.adaptive) die("--topn-score " + topn_score + " does not go together with --noise adaptive (alpha is not a single number, and sigma = 1 / sqrt(alpha) is part of the score)");
+        if (topn_score != "mean" && (!new_row_features.empty() || !new_col_features.empty()))
+            die("--topn-score " + topn_score + " does not go together with --new-row-features / --new-col-features (their lists are ranked by the mean)");
+        if (ucb) { J.topn_kind = BPMF_HIP_SCORE_UCB; J.topn_param = topn_kappa_given ? number(topn_kappa, "--topn-kappa") : 1.0; }
+        if (thr) {
+            J.topn_kind = topn_score == "prob" ? BPMF_HIP_SCORE_PROB : BPMF_HIP_SCORE_EI;
+            J.topn_param = number(topn_threshold, "--topn-threshold");
+            if (!J.probit && !(J.alpha > 0.0 && std::isfinite(J.alpha))) die("--topn-score " + topn_score + " needs a finite -a > 0 (sigma = 1 / sqrt(alpha))");
+            J.topn_sigma = J.probit ? 1.0 : 1.0 / std::sqrt(J.alpha);
+        }
+    }
     if (!J.adaptive && (!alpha_prior.empty() || !alpha_max.empty())) die("--alpha-prior and --alpha-max need --noise adaptive");
     if (J.adaptive) {
         if (!alpha_prior.empty()) {
@@ -1111,14 +1166,15 @@ int main(int argc, char *argv[])
         if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
         FILE *f = fopen((J.odirname + "/topn.csv").c_str(), "w");
         if (!f) die("cannot write " + J.odirname + "/topn.csv");
-        fprintf(f, "query,rank,candidate,mean,std\n");
+        fprintf(f, J.topn_kind < 0 ? "query,rank,candidate,mean,std\n" : "query,rank,candidate,score,mean,std\n");
         for (int64_t q : order)
             for (int r = 0; r < J.topn; ++r) {
                 const size_t at = (size_t)q * J.topn + r;
                 const int32_t c = J.topn_idx[at];
                 if (c < 0) break;                                      // (padding slots are not written)
-                fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), r + 1,
-                        (long long)((pc.empty() ? c : pc[(size_t)c]) + 1), J.topn_mean[at], J.topn_std[at]);
+                const long long qid = (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), cid = (long long)((pc.empty() ? c : pc[(size_t)c]) + 1);
+                if (J.topn_kind < 0) fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", qid, r + 1, cid, J.topn_mean[at], J.topn_std[at]);
+                else fprintf(f, "%lld,%d,%lld,%.17g,%.17g,%.17g\n", qid, r + 1, cid, J.topn_score[at], J.topn_mean[at], J.topn_std[at]);
             }
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
     }

@@ -5,7 +5,7 @@
 //   capi_sample.hip    sampler launches, stateless half-iteration, posterior aggregation, the stateful pipeline (bpmf_hip_sys_sample)
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
-//   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn)
+//   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn, bpmf_hip_topn_scored)
 //   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
@@ -76,6 +76,9 @@ int link_check_csr(const char *who, int64_t N, int64_t D, const int64_t *rowptr,
 struct TopnRings { const double *qring, *cring; int64_t qstride, cstride; int kp, S; };
 int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
                const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out);
+// the candidate splits both rankings use: a split is a multiple of 64 candidates; they are used when the query blocks alone do not
+// fill the device
+void topn_splits(const bpmf_hip_ctx *c, int64_t nq, int64_t nc, int64_t *nsplit, int64_t *cspan);
 
 // evaluation (capi_eval.hip)
 void flush_deferred(bpmf_hip_test *t, bool on_main = false);           // enqueues an evaluation whose launch was put off

@@ -70,14 +70,21 @@ static int build_exclusion(bpmf_hip_side *s)
 
 namespace bpmf_capi {
 
-int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
-               const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out)
+// candidates split over workgroups when the query blocks alone do not fill the device (a split is a multiple of 64 candidates)
+void topn_splits(const bpmf_hip_ctx *c, int64_t nq, int64_t nc, int64_t *nsplit_out, int64_t *cspan_out)
 {
-    // candidates split over workgroups when the query blocks alone do not fill the device (a split is a multiple of 64 candidates)
     const int64_t nqb = (nq + 63) / 64;
     int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>((2 * (int64_t)c->num_cu + nqb - 1) / nqb, (nc + 255) / 256));
     const int64_t cspan = ((nc + nsplit - 1) / nsplit + 63) / 64 * 64;
     nsplit = (nc + cspan - 1) / cspan;
+    *nsplit_out = nsplit; *cspan_out = cspan;
+}
+
+int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
+               const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out)
+{
+    int64_t nsplit, cspan;
+    topn_splits(c, nq, nc, &nsplit, &cspan);
 
     const size_t pn = (size_t)nq * (size_t)n;
     DevBuf<double> part_mean, out;
@@ -131,4 +138,67 @@ extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double m
     const TopnRings r{qr->samples.get(), cr->samples.get(), (int64_t)qr->max * qr->kp, (int64_t)cr->max * cr->kp, qr->kp, S};
     return topn_rings(c, r, mean_rating, n, q_from, nq, cand->ncols, exclude_rated ? qr->ex_ptr.get() : nullptr,
                       exclude_rated ? qr->ex_rows.get() : nullptr, idx_out, mean_out, std_out);
+}
+
+extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
+                                    int exclude_rated, int kind, double param, double sigma, int32_t *idx_out, double *score_out,
+                                    double *mean_out, double *std_out)
+{
+    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "topn_scored: NULL side");
+    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "topn_scored: the two sides belong to different contexts");
+    if (kind != BPMF_HIP_SCORE_UCB && kind != BPMF_HIP_SCORE_PROB && kind != BPMF_HIP_SCORE_EI)
+        return fail(BPMF_HIP_EINVAL, "topn_scored: unknown score kind " + std::to_string(kind) + " (BPMF_HIP_SCORE_UCB, _PROB or _EI)");
+    if (!std::isfinite(param))
+        return fail(BPMF_HIP_EINVAL, std::string("topn_scored: ") + (kind == BPMF_HIP_SCORE_UCB ? "kappa" : "the threshold") + " is not finite");
+    if (kind != BPMF_HIP_SCORE_UCB && !(std::isfinite(sigma) && sigma >= 0.0))
+        return fail(BPMF_HIP_EINVAL, "topn_scored: sigma must be finite and >= 0");
+    if (n < 1 || n > bpmf_launch::topn_max_n())
+        return fail(BPMF_HIP_EINVAL, "topn_scored: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
+    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "topn_scored: query range out of bounds");
+    const int64_t nq = q_to - q_from;
+    if (nq > 0 && (!idx_out || !score_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "topn_scored: NULL output");
+    bpmf_hip_ctx *c = query->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(query); if (rc) return rc; }
+    { const int rc = settle_async(cand); if (rc) return rc; }
+    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn_scored: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
+    const int S = qr->count;
+    if (S < 1 || cr->count != S)
+        return fail(BPMF_HIP_EINVAL, "topn_scored: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
+                    std::to_string(cr->count));
+    if (exclude_rated && query->nrows != cand->ncols)
+        return fail(BPMF_HIP_EINVAL, "topn_scored: exclude_rated needs the query side's rows to be the candidate side's columns");
+    if (nq == 0) return BPMF_HIP_OK;
+    if (exclude_rated) { const int rc = build_exclusion(query); if (rc) return rc; }
+
+    const int64_t nc = cand->ncols;
+    int64_t nsplit, cspan;
+    topn_splits(c, nq, nc, &nsplit, &cspan);
+    const size_t pn = (size_t)nq * (size_t)n;
+    DevBuf<double> part, out;                                             // score | mean | std of the splits / of the result
+    DevBuf<int32_t> part_idx, out_idx;
+    if (part.alloc(3 * (size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(3 * pn) || out_idx.alloc(pn))
+        return fail(BPMF_HIP_ENOMEM, "topn_scored: device allocation of the result lists failed");
+    bpmf_launch::TopnScoredLaunch p{};
+    p.qring = qr->samples.get(); p.cring = cr->samples.get();
+    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
+    p.Kp = qr->kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
+    p.kind = kind; p.param = param; p.sigma = kind == BPMF_HIP_SCORE_UCB ? 0.0 : sigma;
+    p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
+    p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
+    p.part_score = part.get(); p.part_mean = part.get() + (size_t)nsplit * pn; p.part_std = part.get() + 2 * (size_t)nsplit * pn;
+    p.part_idx = part_idx.get();
+    p.out_score = out.get(); p.out_mean = out.get() + pn; p.out_std = out.get() + 2 * pn; p.out_idx = out_idx.get();
+    const int lrc = bpmf_launch::topn_scored(p, c->stream);
+    if (lrc == -2) return fail(BPMF_HIP_ENODEV, "topn_scored: the device refused the LDS of lists of " + std::to_string(n));
+    if (lrc) return fail(BPMF_HIP_EINVAL, "topn_scored: unsupported shape");
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn_scored: kernel launch failed");
+    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    if (hipMemcpy(score_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(mean_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(std_out, out.get() + 2 * pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(BPMF_HIP_ENODEV, "topn_scored: copying the results back failed");
+    return BPMF_HIP_OK;
 }

@@ -26,17 +26,9 @@
 //                      form v(c)^T Lambda^-1 v(c) = |R^-T v(c)|^2 (k_quadform_add of the design)
 //   k_ring_add_mu      ring[i][slot][k] += mu[k], k < Kt: the mean of a projected row (the product F beta sits in the slot)
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "kernels_predtile.h"               // the staged tile product and the moment update, shared with k_topn_scored
 
 namespace bpmf {
-
-typedef double pred_d4 __attribute__((ext_vector_type(4)));
-typedef double pred_d2 __attribute__((ext_vector_type(2)));
-
-constexpr int kPredTile = 64;               // queries and candidates per workgroup
-constexpr int kPredStep = 16;               // rows of k staged per slice (4 MFMA k-steps)
-constexpr int kPredPitch = kPredStep + 2;   // row pitch in LDS (doubles): the 32 lanes of a half-wave's 8-byte read fall into 32 different bank pairs
 
 struct PredBlockArgs {
     const double *qring, *cring;            // sample rings of the queries / the candidates
@@ -91,26 +83,12 @@ __global__ __launch_bounds__(256) void k_predict_block(PredBlockArgs a)
         for (int ks = 0; ks < nk; ++ks) {
             const bool more = ls < a.S;                                    // (uniform over the workgroup)
             if (more) load();
-#pragma unroll
-            for (int kk = 0; kk < kPredStep / 4; ++kk) {
-                const double av = sQ[buf][w * 16 + li][kk * 4 + kq];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, sC[buf][j * 16 + li][kk * 4 + kq], acc[j], 0, 0, 0);
-            }
+            pred_slice_mfma(sQ[buf], sC[buf], w, li, kq, acc);
             if (more) store(buf ^ 1);
             __syncthreads();
             buf ^= 1;
         }
-        // sample s + 1 = n: the deviation from the mean of the n - 1 before it, then the sum
-        const double c1 = s > 0 ? 1.0 / (double)s : 0.0, c2 = (double)s / (double)(s + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double p = acc[j][r], d = p - sum[j][r] * c1;
-                m2[j][r] = fma(d * d, c2, m2[j][r]);
-                sum[j][r] += p;
-            }
+        pred_fold(s, acc, sum, m2);
     }
     const double S = (double)a.S;
 #pragma unroll

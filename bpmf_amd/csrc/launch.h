@@ -133,6 +133,18 @@ struct TopnLaunch {
 };
 void topn(const TopnLaunch &p, hipStream_t st);             // score + select, merge of the splits, std of the selected pairs
 
+// posterior top-N by an acquisition score (kernels_topn_score.h, ktopnscore.hip)
+struct TopnScoredLaunch {
+    const double *qring, *cring; int64_t qstride, cstride;
+    int Kp, S, n; double mean_rating;
+    int kind; double param, sigma;                         // BPMF_HIP_SCORE_*; kappa or the threshold; sigma = 0: the noise-free forms
+    int64_t q_from, nq, nc, cspan; int nsplit;
+    const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
+    double *part_score, *part_mean, *part_std; int32_t *part_idx;   // nsplit x nq x n
+    double *out_score, *out_mean, *out_std; int32_t *out_idx;       // nq x n
+};
+int topn_scored(const TopnScoredLaunch &p, hipStream_t st);    // score + select, merge of the splits.  -1: shape not supported, -2: the LDS of the lists was refused (nothing launched)
+
 // dense blocks of predictions from two sample rings; rows unseen in training (kernels_predblock.h, kpredblock.hip)
 struct PredBlockLaunch {
     const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column

@@ -267,6 +267,27 @@ class HipEngine:
                                           1 if exclude_rated else 0, _ptr(idx), _ptr(mean), _ptr(std)))
         return idx, mean, std
 
+    SCORE_KINDS = {"ucb": 0, "prob": 1, "ei": 2}     # BPMF_HIP_SCORE_*
+
+    def topn_scored(self, query, cand, mean_rating, n, kind, param, sigma=0.0, q_from=0, q_to=None, exclude_rated=True):
+        """The n best columns of `cand` by an acquisition score of the per-sample predictions for every
+        column q_from .. q_to - 1 of `query`: kind "ucb" (mean + param std; param = kappa, negative for a lower bound), "prob"
+        (the posterior probability that a rating with noise deviation sigma exceeds param = t) or "ei" (the expected excess over
+        t).  (idx int32[nq, n], score, mean, std f64[nq, n]); mean and std of a pick are predict_block's, bit for bit; empty slots
+        have idx -1 and zeros."""
+        if kind not in self.SCORE_KINDS:
+            raise ValueError("topn_scored: kind must be one of 'ucb', 'prob', 'ei', not %r" % (kind,))
+        q_to = query.ncols if q_to is None else int(q_to)
+        nq = max(0, q_to - int(q_from))
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        score = np.empty((nq, int(n)))
+        mean = np.empty((nq, int(n)))
+        std = np.empty((nq, int(n)))
+        _lib.check(self.lib.bpmf_hip_topn_scored(query.handle, cand.handle, float(mean_rating), int(n), int(q_from), int(q_to),
+                                                 1 if exclude_rated else 0, self.SCORE_KINDS[kind], float(param), float(sigma),
+                                                 _ptr(idx), _ptr(score), _ptr(mean), _ptr(std)))
+        return idx, score, mean, std
+
     def predict_block(self, query, cand, mean_rating, q_from=0, q_to=None, c_from=0, c_to=None):
         """(mean, std), [q_to - q_from, c_to - c_from] each: the posterior-mean prediction and its spread over the samples of the
         two sides' rings for every pair of the block, in one kernel.  The bits of an element do not depend

@@ -187,7 +187,7 @@ class Sys:
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
-          new_row_features=None, new_col_features=None):
+          new_row_features=None, new_col_features=None, topn_score=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -201,6 +201,13 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     topn=N: every post-burn-in sample of both sides is kept on the device (nsims - burnin slots each) and res["topn"] holds
     engine.topn(users, movies, ...) after the loop -- (idx, mean, std), [nusers, N] each: the N unrated movies of every user
     with the highest posterior-mean prediction.
+
+    topn_score=("ucb", kappa) | ("prob", t) | ("ei", t), with topn=N: the lists are ranked by an acquisition score of the kept
+    samples instead of their mean -- mean + kappa std (kappa < 0: a lower bound), the posterior probability
+    that a rating exceeds t, or the expected excess over t, with the observation noise sigma = 1 / sqrt(alpha) of the run (1 under
+    probit=True, where t is on the latent-score scale and 0 the natural value).  res["topn"] is then engine.topn_scored's
+    (idx, score, mean, std).  "prob" and "ei" are refused with noise="adaptive" (alpha is not one number).  res["new_rows_topn"]
+    / res["new_cols_topn"] stay the 3-tuples ranked by the mean (see new_row_features below).  None (the default): nothing changes.
 
     noise="adaptive": the noise precision is sampled too.  Iteration 0 runs with `alpha`; after iteration i (both sides
     sampled) the sum of squared training residuals SSE_i is reduced on the device (engine.train_sse over the movies' ratings)
@@ -253,7 +260,24 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     + (mu_s + beta_s^T f) . v_s and the total deviation -- the spread between the samples joined with the spread of a cold row's
     factors around their conditional mean, (1/S) sum_s v_s^T Lambda_s^-1 v_s.  The observation noise 1 / alpha is not part of std.
     With topn=N also res["new_rows_topn"] / res["new_cols_topn"] = (idx, mean, std), [n_new, N] each, the new entities as the
-    queries.  None (the default): nothing changes."""
+    queries.  These two are ALWAYS ranked by the posterior mean, also when topn_score ranks res["topn"] by another key: the score
+    of a new entity would need the w[c] / S term of its variance (out of scope).  None (the default):
+    nothing changes."""
+    if topn_score is not None:                       # (refused before the engine is used)
+        if topn is None:
+            raise ValueError("topn_score needs topn=N (it ranks the top-N lists)")
+        try:
+            score_kind, score_param = topn_score
+            score_param = float(score_param)
+        except (TypeError, ValueError):
+            raise ValueError("topn_score must be a pair (kind, parameter): ('ucb', kappa), ('prob', t) or ('ei', t)")
+        if score_kind not in ("ucb", "prob", "ei"):
+            raise ValueError("topn_score: unknown kind %r (one of 'ucb', 'prob', 'ei')" % (score_kind,))
+        if not math.isfinite(score_param):
+            raise ValueError("topn_score: the parameter of %r must be finite" % (score_kind,))
+        if score_kind != "ucb" and noise == "adaptive":
+            raise ValueError("topn_score %r does not go together with noise='adaptive' (alpha is not a single number, and sigma = "
+                             "1 / sqrt(alpha) is part of the score)" % (score_kind,))
     for new, have, nn, hn in ((new_row_features, row_features, "new_row_features", "row_features"),
                               (new_col_features, col_features, "new_col_features", "col_features")):
         if new is None:
@@ -459,7 +483,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     res["num_predict"] = movies.num_predict
     res["U"] = users.items(); res["V"] = movies.items()
     if topn is not None:
-        res["topn"] = engine.topn(users.side, movies.side, movies.mean_rating, topn)
+        if topn_score is None:
+            res["topn"] = engine.topn(users.side, movies.side, movies.mean_rating, topn)
+        else:
+            sigma = 0.0 if score_kind == "ucb" else 1.0 / math.sqrt(float(alpha))
+            res["topn"] = engine.topn_scored(users.side, movies.side, movies.mean_rating, topn, score_kind, score_param, sigma)
     if probit:
         have = movies.test is not None and movies.T_nnz > 0 and nsims > burnin
         res["prob"] = engine.probit_get(movies.test)[0] if have else np.zeros(0)

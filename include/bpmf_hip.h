@@ -286,6 +286,23 @@ BPMF_API int bpmf_hip_side_samples_count(const bpmf_hip_side *side);
 BPMF_API int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                            int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out);
 
+/* The n best candidates by an ACQUISITION SCORE of the per-sample predictions p_s instead of their mean.
+ * With mean and std as bpmf_hip_predict_block computes them (w = NULL), Phi / phi the standard normal cdf / pdf and
+ * z_s = (p_s - t) / sigma:
+ *   BPMF_HIP_SCORE_UCB   mean + param std                                   param = kappa, any finite value (negative: a lower bound)
+ *   BPMF_HIP_SCORE_PROB  (1/S) sum_s Phi(z_s)                               param = t; sigma = 0: (1/S) #{s : p_s > t}
+ *   BPMF_HIP_SCORE_EI    (1/S) sum_s [(p_s - t) Phi(z_s) + sigma phi(z_s)]  param = t; sigma = 0: (1/S) sum_s max(p_s - t, 0)
+ * sigma >= 0 is an observation-noise standard deviation (1 / sqrt(alpha)); it is ignored for UCB, and a sigma below DBL_MIN
+ * (a subnormal) takes the sigma = 0 forms.  Everything else is
+ * bpmf_hip_topn's: the order (score descending, lower candidate index first), exclude_rated, the padding (idx -1, zeros), the
+ * preconditions and the waits.  1 <= n <= 32.  BPMF_HIP_EINVAL also for an unknown kind, a non-finite param and a sigma that is
+ * negative or not finite.  score_out / mean_out / std_out / idx_out: (q_to - q_from) x n row-major host arrays; mean and std of
+ * a pick have the bits bpmf_hip_predict_block gives that pair. */
+enum { BPMF_HIP_SCORE_UCB = 0, BPMF_HIP_SCORE_PROB = 1, BPMF_HIP_SCORE_EI = 2 };
+BPMF_API int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
+                                  int exclude_rated, int kind, double param, double sigma, int32_t *idx_out, double *score_out,
+                                  double *mean_out, double *std_out);
+
 /* ---- dense blocks of predictions; rows unseen in training ---------
  * bpmf_hip_predict_block: for every query column q in [q_from, q_to) of `query` and every candidate column c in [c_from, c_to)
  * of `cand`, from the sample rings of both sides (the same S >= 1 samples, bpmf_hip_side_samples_add): mean and std as
