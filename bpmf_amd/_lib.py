@@ -73,6 +73,19 @@ _SIGNATURES = {
     "bpmf_hip_side_newrows_get_padded": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bpmf_hip_newrows_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "bpmf_hip_newrows_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_hyper_reserve": (C.c_int, [C.c_void_p, C.c_int]),
+    "bpmf_hip_side_hyper_add": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_hyper_count": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_hyper_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_foldin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_int]),
+    "bpmf_hip_foldin_count": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_foldin_samples": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_foldin_get": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_foldin_get_padded": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_foldin_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_foldin_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_foldin_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bpmf_hip_foldin_chunk": (C.c_int, []),
     "bpmf_hip_train_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bpmf_hip_noise_sample": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "bpmf_hip_side_set_probit": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),

@@ -29,6 +29,12 @@
 // movies that are NOT in the training matrix, predicted from their features alone: DIR/new-rows-mean.ddm,
 // new-rows-std.ddm (new x movies), new-cols-mean.ddm, new-cols-std.ddm (users x new); with --topn N also DIR/new-rows-topn.csv /
 // new-cols-topn.csv.  std does not include the observation noise 1 / alpha.
+// --fold-in-rows FILE / --fold-in-cols FILE (with -o DIR, -i > -b; one GPU, no -g): users / movies that arrive after training with a
+// few ratings and no features.  FILE is a sparse matrix, new users x movies / users x new movies, oriented as the
+// training matrix.  After the chain every kept sample gives one draw of their factors from their conditional given that sample of the
+// other side (bpmf_hip_foldin): DIR/foldin-rows-mean.ddm, foldin-rows-std.ddm (new x movies), foldin-cols-mean.ddm, foldin-cols-std.ddm
+// (users x new); with --topn N also DIR/foldin-rows-topn.csv / foldin-cols-topn.csv, the new entities as the queries, their own
+// ratings excluded.  One more header line names the counts; everything else keeps its format.
 // --row-features FILE / --col-features FILE [--lambda-beta F] (one GPU, no -g): side information.  FILE is a
 // dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
 // -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).  A sparse FILE (.sdm / .sbm /
@@ -76,7 +82,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -123,6 +129,14 @@ void usage()
               << "              DIR/new-cols-mean.ddm, new-cols-std.ddm (users x new); std leaves the observation noise 1 / alpha out.  With\n"
               << "              --topn N also DIR/new-rows-topn.csv / new-cols-topn.csv (--topn-by rows: the best columns of every new row, the\n"
               << "              best new columns of every row; cols: the columns are the queries); files of more than 2^28 cells need --topn\n"
+              << "  [--fold-in-rows FILE] [--fold-in-cols FILE]: users / movies that arrive after training with a few ratings and no features: a\n"
+              << "              sparse matrix (.sdm, coordinate .mtx; optional .gz), new users x movies / users x new movies, as the training\n"
+              << "              matrix is oriented (needs -o DIR and -i > -b; one GPU, no -g; not with --probit, -m / -l, BPMF_REDUCE=1, features on\n"
+              << "              the same side or a --topn-score other than mean).  Every kept sample gives one draw of their factors from their\n"
+              << "              ratings: DIR/foldin-rows-mean.ddm, foldin-rows-std.ddm (new x movies), foldin-cols-mean.ddm, foldin-cols-std.ddm\n"
+              << "              (users x new); std leaves the observation noise 1 / alpha out.  With --topn N also DIR/foldin-rows-topn.csv /\n"
+              << "              foldin-cols-topn.csv: the best N for every new entity, its own ratings excluded; files of more than 2^28 cells\n"
+              << "              need --topn\n"
               << "  [--link-tol F] [--link-max-iter N]: the stopping rule of that CG draw: relative residual (1e-6), most iterations (1000);\n"
               << "              need a sparse feature file\n"
               << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
@@ -301,6 +315,9 @@ struct Job {
         std::vector<double> mean, std;                               // new x other side, row-major
         std::vector<int32_t> topn_idx; std::vector<double> topn_mean, topn_std; bool new_are_queries = true;
     } new_u, new_m;
+    // --fold-in-rows / --fold-in-cols: Fr holds the RATINGS of the new entities (column i = new entity i, its
+    // rows = columns of the other side); n = 0: none
+    NewRows fold_u, fold_m;
     bool has_feat_u() const { return !feat_u.data.empty() || sfeat_u_d > 0; }
     bool has_feat_m() const { return !feat_m.data.empty() || sfeat_m_d > 0; }
     std::vector<double> beta_u, beta_m;                              // posterior mean of the link matrices, D x K row-major
@@ -373,9 +390,12 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.has_feat_u()) check(bpmf_hip_side_link_lambda_prior(users, J.lb_a0, J.lb_b0));
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0, ring_u = J.topn > 0 || J.new_m.n > 0;
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
+    // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
+    if (J.fold_u.n > 0) check(bpmf_hip_side_hyper_reserve(users, J.nsims - J.burnin));
+    if (J.fold_m.n > 0) check(bpmf_hip_side_hyper_reserve(movies, J.nsims - J.burnin));
     auto set_new = [&](bpmf_hip_side *side, const Job::NewRows &N) {
         if (N.n == 0) return;
         if (N.F.empty()) {
@@ -463,6 +483,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     if (J.new_u.n > 0) os << "new rows: " << J.new_u.n << " (--new-row-features), predicted from their features over the kept samples" << std::endl;
     if (J.new_m.n > 0) os << "new columns: " << J.new_m.n << " (--new-col-features), predicted from their features over the kept samples" << std::endl;
+    if (J.fold_u.n > 0) os << "fold-in rows: " << J.fold_u.n << " (--fold-in-rows), " << J.fold_u.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
+    if (J.fold_m.n > 0) os << "fold-in columns: " << J.fold_m.n << " (--fold-in-cols), " << J.fold_m.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -559,6 +581,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
         if (ring_u && iter >= burnin) check(bpmf_hip_side_samples_add(users));
         if (ring_m && iter >= burnin) check(bpmf_hip_side_samples_add(movies));
+        if (J.fold_u.n > 0 && iter >= burnin) check(bpmf_hip_side_hyper_add(users, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
+        if (J.fold_m.n > 0 && iter >= burnin) check(bpmf_hip_side_hyper_add(movies, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
         if (J.new_u.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(users, movies));
         if (J.new_m.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(movies, users));
         if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
@@ -670,6 +694,30 @@ void rank_main(Job &J, int rank, std::ostream &os)
     };
     predict_new(users, movies, J.new_u, nmovies, !J.topn_by_cols);   // --topn-by rows: the new rows are the queries
     predict_new(movies, users, J.new_m, nusers, J.topn_by_cols);     // --topn-by cols: the new columns are the queries
+    // fold-in (streams: tag 7 = new users, 8 = new movies): one launch over every (new entity, kept sample), then the block and the lists
+    auto fold_in = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, unsigned tag) {
+        if (N.n == 0) return;
+        const double t0 = tick();
+        static const int32_t none = 0; static const double zero = 0.0;
+        check(bpmf_hip_foldin(side, cand, J.mean_m, N.n, N.Fr.colptr.data(), N.Fr.rowidx.empty() ? &none : N.Fr.rowidx.data(),
+                              N.Fr.vals.empty() ? &zero : N.Fr.vals.data(), tag, 1));
+        if (N.dense_out) {
+            N.mean.resize((size_t)N.n * (size_t)nc); N.std.resize(N.mean.size());
+            const int64_t step = std::max<int64_t>(64, ((int64_t)1 << 24) / std::max<int64_t>(nc, 1) / 64 * 64);
+            for (int64_t q0 = 0; q0 < N.n; q0 += step) {
+                const int64_t q1 = std::min(N.n, q0 + step);
+                check(bpmf_hip_foldin_predict(side, cand, J.mean_m, q0, q1, 0, nc, N.mean.data() + (size_t)q0 * nc, N.std.data() + (size_t)q0 * nc));
+            }
+        }
+        if (J.topn > 0) {
+            N.new_are_queries = true;
+            N.topn_idx.resize((size_t)N.n * J.topn); N.topn_mean.resize(N.topn_idx.size()); N.topn_std.resize(N.topn_idx.size());
+            check(bpmf_hip_foldin_topn(side, cand, J.mean_m, J.topn, 1, N.topn_idx.data(), N.topn_mean.data(), N.topn_std.data()));
+        }
+        std::cerr << "fold-in " << (side == users ? "rows" : "columns") << ": " << N.n << " x " << nc << " predictions, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+    };
+    fold_in(users, movies, J.fold_u, nmovies, 7);
+    fold_in(movies, users, J.fold_m, nusers, 8);
     if (rank == 0) {
         J.elapsed = elapsed; J.rmse_avg = rmse_avg; J.num_predict = num_predict;
         J.average_items_sec = average_items_sec; J.average_ratings_sec = average_ratings_sec;
@@ -704,8 +752,9 @@ int main(int argc, char *argv[])
                                               {"new-row-features", required_argument, nullptr, 1015}, {"new-col-features", required_argument, nullptr, 1016},
                                               {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
                                               {"topn-threshold", required_argument, nullptr, 1019},
+                                              {"fold-in-rows", required_argument, nullptr, 1020}, {"fold-in-cols", required_argument, nullptr, 1021},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, new_row_features, new_col_features;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
     bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
@@ -732,6 +781,8 @@ int main(int argc, char *argv[])
         case 1017: topn_score = optarg; break;
         case 1018: topn_kappa = optarg; topn_kappa_given = true; break;
         case 1019: topn_threshold = optarg; topn_threshold_given = true; break;
+        case 1020: fold_in_rows = optarg; break;
+        case 1021: fold_in_cols = optarg; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -903,6 +954,23 @@ int main(int argc, char *argv[])
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--censored does not go together with BPMF_REDUCE=1");
         if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--censored needs a noise precision -a F > 0");
     }
+    // --fold-in-rows / --fold-in-cols: checked before anything touches a GPU (the files themselves below, once the shape is known)
+    for (int which = 0; which < 2; ++which) {
+        const std::string &name = which ? fold_in_cols : fold_in_rows;
+        if (name.empty()) continue;
+        const std::string w = which ? "--fold-in-cols" : "--fold-in-rows";
+        if (J.odirname.empty()) die(w + " needs -o DIR (the predictions go to files in DIR)");
+        if (J.nsims <= J.burnin) die(w + " needs at least one post-burn-in sample (-i > -b)");
+        if (ngpu >= 1) die(w + " runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample rings of a sharded side are not complete)");
+        if (J.probit) die(w + " does not go together with --probit (labels would need a latent iteration of their own)");
+        if (!mname.empty() || !lname.empty()) die(w + " does not go together with a propagated posterior (-m / -l): a new entity has none");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die(w + " does not go together with BPMF_REDUCE=1");
+        if (!(which ? col_features : row_features).empty())
+            die(w + " does not go together with " + (which ? "--col-features" : "--row-features") + ": the prior mean of a new " + (which ? "column" : "row") +
+                " needs its features (" + (which ? "--new-col-features" : "--new-row-features") + " predicts such " + (which ? "columns" : "rows") + ")");
+        if (topn_score != "mean") die(w + " does not go together with --topn-score " + topn_score + " (its lists are ranked by the mean)");
+        if (!sparse_file(name)) die(w + ": " + name + " is not a sparse matrix file (.sdm, .sbm or a coordinate .mtx)");
+    }
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -1010,6 +1078,33 @@ int main(int argc, char *argv[])
     read_new(new_row_features, sparse_u, sparse_u ? J.sfeat_u_d : J.feat_u.ncols, nmovies, "new-row-features", "row-features", J.new_u);
     read_new(new_col_features, sparse_m, sparse_m ? J.sfeat_m_d : J.feat_m.ncols, nusers, "new-col-features", "col-features", J.new_m);
 
+    // the ratings of the entities to fold in: new users x movies / users x new movies; every cell once, finite; stored by new entity
+    auto read_fold = [&](const std::string &name, bool rows, Job::NewRows &N) {
+        if (name.empty()) return;
+        const std::string w = rows ? "--fold-in-rows" : "--fold-in-cols";
+        const int64_t nother = rows ? nmovies : nusers;
+        Csc F;
+        try { F = bpmf::io::read_sparse(name); } catch (const std::exception &e) { die(e.what()); }
+        if ((rows ? F.ncols : F.nrows) != nother)
+            die(w + ": " + name + " is " + std::to_string(F.nrows) + " x " + std::to_string(F.ncols) + ", the training matrix has " + std::to_string(nother) +
+                (rows ? " columns" : " rows"));
+        const int64_t n = rows ? F.nrows : F.ncols;
+        if (n < 1) die(w + ": " + name + (rows ? " has no rows" : " has no columns"));
+        if (F.dup_row >= 0)
+            die(w + ": " + name + " lists cell (" + std::to_string((long long)F.dup_row + 1) + ", " + std::to_string((long long)F.dup_col + 1) + ") twice");
+        for (double v : F.vals) if (!std::isfinite(v)) die(w + ": " + name + " holds a value that is not finite");
+        N.n = n;
+        if (n > ((int64_t)1 << 28) / std::max<int64_t>(nother, 1)) {
+            const std::string cells = std::to_string(n) + " x " + std::to_string(nother) + " predictions are more than 2^28 cells per file";
+            if (J.topn < 1) die(w + ": " + cells + ": ask for the best N of every query with --topn N instead");
+            std::cerr << w << ": " << cells << ": the dense mean / std files are skipped, the --topn lists are written" << std::endl;
+            N.dense_out = false;
+        }
+        N.Fr = rows ? bpmf::io::transpose(F) : F;                     // column i = new entity i, its row ids ascending
+    };
+    read_fold(fold_in_rows, true, J.fold_u);
+    read_fold(fold_in_cols, false, J.fold_m);
+
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {
         if (fnames.empty()) return;
@@ -1035,6 +1130,7 @@ int main(int argc, char *argv[])
     // GPU can check of the permute / unpermute plumbing)
     const int assign_parts = getenv("BPMF_TEST_ASSIGN_PARTS") ? atoi(getenv("BPMF_TEST_ASSIGN_PARTS")) : J.nranks;
     const bool greedy = balance && assign_parts > 1 && !(assign_env && std::string(assign_env) == "contiguous");
+    if (greedy && (J.fold_u.n > 0 || J.fold_m.n > 0)) die("--fold-in-rows / --fold-in-cols do not go together with a renumbering assignment of the columns");
     if (greedy && linked) die("--row-features / --col-features do not go together with a renumbering assignment of the columns");
     if (greedy) {
         J.perm_m.resize((size_t)nmovies); J.perm_u.resize((size_t)nusers);
@@ -1181,9 +1277,9 @@ int main(int argc, char *argv[])
 
     // the new entities: new x movies as it is computed; users x new = the transpose of what is computed (row-major new x users IS
     // column-major users x new).  Lists: 1-based ids, the new entities numbered by their row in the feature file.
-    auto write_new = [&](Job::NewRows &N, bool rows, int64_t nother) {
+    auto write_new = [&](Job::NewRows &N, bool rows, int64_t nother, const char *stem) {
         if (N.n == 0) return;
-        const std::string base = J.odirname + (rows ? "/new-rows" : "/new-cols");
+        const std::string base = J.odirname + "/" + stem + (rows ? "-rows" : "-cols");
         try {
             if (N.dense_out) {
                 for (int which = 0; which < 2; ++which) {
@@ -1213,8 +1309,12 @@ int main(int argc, char *argv[])
             if (fclose(f) != 0) die("cannot write " + name);
         }
     };
-    write_new(J.new_u, true, nmovies);
-    write_new(J.new_m, false, nusers);
+    write_new(J.new_u, true, nmovies, "new");
+    write_new(J.new_m, false, nusers, "new");
+
+    // the folded-in entities: the same layout, queries numbered by their row (column) in FILE
+    write_new(J.fold_u, true, nmovies, "foldin");
+    write_new(J.fold_m, false, nusers, "foldin");
 
     if (J.lb_sampled && !J.odirname.empty()) {                       // a cell is empty where a side has no features
         FILE *f = fopen((J.odirname + "/lambda_beta.csv").c_str(), "w");

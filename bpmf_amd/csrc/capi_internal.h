@@ -7,13 +7,14 @@
 //   capi_eval.hip      test sets and Sys::predict
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn, bpmf_hip_topn_scored)
 //   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
+//   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last seven (probit, censoring, features, sample ring, new rows, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last eight (probit, censoring, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -79,6 +80,12 @@ int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, i
 // the candidate splits both rankings use: a split is a multiple of 64 candidates; they are used when the query blocks alone do not
 // fill the device
 void topn_splits(const bpmf_hip_ctx *c, int64_t nq, int64_t nc, int64_t *nsplit, int64_t *cspan);
+
+// mean / std (nq x nc each) of queries [q_from, q_to) against candidates [c_from, c_to) of two rings of S samples (capi_newrows.hip):
+// what bpmf_hip_predict_block, bpmf_hip_newrows_predict and bpmf_hip_foldin_predict share.  w: added to the variance as w[candidate] / S,
+// or NULL.  device_out: the outputs are device memory of the context's device and written in place, else host arrays.  Waits.
+int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
+                  int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to, double *mean_out, double *std_out, bool device_out = false);
 
 // evaluation (capi_eval.hip)
 void flush_deferred(bpmf_hip_test *t, bool on_main = false);           // enqueues an evaluation whose launch was put off

@@ -58,10 +58,14 @@ int newrows_free(bpmf_hip_side *s)
     return BPMF_HIP_OK;
 }
 
+}  // namespace
+
+namespace bpmf_capi {
+
 // mean / std (nq x nc each) of queries [q_from, q_to) against candidates [c_from, c_to) of two rings of S samples; waits.
 // device_out: mean_out / std_out are device memory of the context's device and written in place, else host arrays
 int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
-                  int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to, double *mean_out, double *std_out, bool device_out = false)
+                  int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to, double *mean_out, double *std_out, bool device_out)
 {
     const std::string ws(who);
     if (q_from < 0 || q_to < q_from || q_to > nqcols) return fail(BPMF_HIP_EINVAL, ws + ": query range out of bounds");
@@ -95,6 +99,10 @@ int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t 
         return fail(BPMF_HIP_ENODEV, ws + ": copying the results back failed");
     return BPMF_HIP_OK;
 }
+
+}  // namespace bpmf_capi
+
+namespace {
 
 // the new rows of `side` against the sample ring of `cand`: the checks both consumers share
 int newrows_pair(const char *who, bpmf_hip_side *side, bpmf_hip_side *cand)

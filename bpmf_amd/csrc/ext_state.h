@@ -100,5 +100,22 @@ struct bpmf_newrows {
     ~bpmf_newrows() { for (hipEvent_t e : staged) if (e) (void)hipEventDestroy(e); }
 };
 
+// fold-in (capi_foldin.hip): the hyper ring of the side -- alpha_s, mu_s (kt), Lambda_s (kt x kt) and Lambda_s mu_s
+// (kt) of every kept sample, held on the host (kilobytes per sample) and uploaded by the fold-in that reads it -- and the newest
+// set of folded-in rows: their ratings by rows (the exclusion lists of their ranking), the ring of their draws (n x S x kp, layout of
+// bpmf_ring), the word the kernel raises to a row whose pivot was not positive and finite, and two events around the launch
+struct bpmf_foldin {
+    int hmax = 0, hcount = 0;
+    std::vector<double> alpha, mu, lam, lmu;
+    int64_t n = 0; int S = 0, kp = 0;
+    DevBuf<int64_t> rowptr; DevBuf<int32_t> colidx; DevBuf<double> ring;
+    Pinned<unsigned long long> fail;
+    hipEvent_t timed[2] = {nullptr, nullptr}; float last_ms = -1.f;   // around the newest launch of k_foldin (bpmf_hip_foldin_last_ms)
+    bpmf_foldin() = default;
+    bpmf_foldin(const bpmf_foldin &) = delete;
+    bpmf_foldin &operator=(const bpmf_foldin &) = delete;
+    ~bpmf_foldin() { for (hipEvent_t e : timed) if (e) (void)hipEventDestroy(e); }
+};
+
 // adaptive noise (capi_noise.hip): the block partials | sum of bpmf_hip_train_sse
 struct bpmf_sse { DevBuf<double> part; int nblk = 0; };

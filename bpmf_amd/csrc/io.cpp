@@ -274,7 +274,10 @@ Csc csc_from_triplets(int64_t nrows, int64_t ncols, const std::vector<int32_t> &
         std::stable_sort(perm.begin(), perm.end(), [&](size_t x, size_t y) { return r2[x] < r2[y]; });
         for (size_t q = 0; q < perm.size(); ++q) {
             const size_t k = perm[q];
-            if (q > 0 && r2[k] == m.rowidx.back() && (int64_t)m.rowidx.size() > m.colptr[(size_t)c]) m.vals.back() += v2[k];
+            if (q > 0 && r2[k] == m.rowidx.back() && (int64_t)m.rowidx.size() > m.colptr[(size_t)c]) {
+                m.vals.back() += v2[k];
+                if (m.dup_row < 0) { m.dup_row = r2[k]; m.dup_col = c; }
+            }
             else { m.rowidx.push_back(r2[k]); m.vals.push_back(v2[k]); }
         }
         m.colptr[(size_t)c + 1] = (int64_t)m.rowidx.size();

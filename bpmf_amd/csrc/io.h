@@ -15,6 +15,7 @@ struct Csc {                       // sorted rows per column, duplicates summed
     std::vector<int64_t> colptr;   // ncols + 1
     std::vector<int32_t> rowidx;
     std::vector<double> vals;
+    int64_t dup_row = -1, dup_col = -1;   // the first cell the file listed more than once (0-based; -1: none)
     int64_t nnz() const { return colptr.empty() ? 0 : colptr.back(); }
 };
 

@@ -157,6 +157,19 @@ int predict_block(const PredBlockLaunch &p, hipStream_t st);   // -1: shape not 
 void rowsq_add(const double *Y, int64_t ldy, int n, int64_t ncols, double *w, hipStream_t st);      // w[c] += |Y[c][0 .. n)|^2
 void ring_add_mu(double *ring, int64_t stride, int slot, int Kp, int Kt, int64_t nrows, const double *mu, hipStream_t st);
 
+// fold-in of new rows from their ratings (kernels_foldin.h, kfoldin.hip)
+struct FoldinLaunch {
+    const int64_t *rowptr; const int32_t *colidx; const double *vals; int64_t n_new;   // the new rows by rows, on the device
+    const double *cring; int64_t cstride;                  // the candidate side's ring, doubles per column
+    const double *alpha, *lam, *lmu; int S;                // the hyper ring: S | S x kt x kt | S x kt
+    int K, kt, kp;                                         // the context's device num_latent, the caller's, the ring's
+    double mean_rating; uint32_t tag; int draw;
+    double *out;                                           // n_new x S x kp
+    unsigned long long *fail;                              // raised to a row whose pivot was not positive and finite
+};
+int foldin_chunk();                                        // ratings staged per pass (kFoldinChunk)
+int foldin(const FoldinLaunch &p, hipStream_t st);         // -1: shape not supported (nothing launched)
+
 // training residuals for the adaptive noise precision (kernels_noise.h, knoise.hip)
 struct SseLaunch {
     const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)

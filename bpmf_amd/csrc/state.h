@@ -216,6 +216,7 @@ struct bpmf_hip_side {
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
     std::unique_ptr<bpmf_newrows> newrows; // rows unseen in training: their features and projected samples (bpmf_hip_side_newrows_set)
+    std::unique_ptr<bpmf_foldin> foldin;   // fold-in: the per-sample hyper-parameters and the folded-in rows (bpmf_hip_side_hyper_reserve, bpmf_hip_foldin)
     std::unique_ptr<bpmf_sse> sse;         // partials of the training residuals (bpmf_hip_train_sse)
     DevBuf<int64_t> d_colptr;              // the column pointers on the device, uploaded when an add-on first needs them (ensure_colptr)
     bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)

@@ -383,6 +383,95 @@ class HipEngine:
                                                   _ptr(idx), _ptr(mean), _ptr(std)))
         return idx, mean, std
 
+    # -- fold-in: new rows from their ratings -------------------------------------
+    def hyper_reserve(self, side, max_samples):
+        """Room for the hyper-parameters (alpha, mu, Lambda) of max_samples kept samples of the side (0 frees
+        it): what a fold-in into this side reads beside the other side's sample ring."""
+        _lib.check(self.lib.bpmf_hip_side_hyper_reserve(side.handle, int(max_samples)))
+
+    def hyper_add(self, side, alpha, mu=None, LambdaF=None):
+        """The next slot of the side's hyper ring: the hyper-parameters its newest sys_sample ran with (mu = LambdaF = None; where
+        samples_add of the other side sits), or explicit mu [K] and a symmetric LambdaF [K, K] (tests, a caller's own loop)."""
+        if (mu is None) != (LambdaF is None):
+            raise ValueError("hyper_add: mu and LambdaF are given together or not at all")
+        if mu is not None:
+            mu = np.ascontiguousarray(mu, np.float64); LambdaF = np.asfortranarray(LambdaF, np.float64)
+            if mu.shape != (self.K,) or LambdaF.shape != (self.K, self.K):
+                raise ValueError("hyper_add: mu must be [%d] and LambdaF [%d, %d]" % (self.K, self.K, self.K))
+        _lib.check(self.lib.bpmf_hip_side_hyper_add(side.handle, float(alpha), _ptr(mu), _ptr(LambdaF)))
+
+    def hyper_count(self, side):
+        return int(self.lib.bpmf_hip_side_hyper_count(side.handle))
+
+    def hyper_get(self, side):
+        """(alpha [S], mu [S, K], LambdaF [S, K, K]) of the side's hyper ring"""
+        S = self.hyper_count(side)
+        alpha = np.empty(S); mu = np.empty((S, self.K)); LF = np.empty((S, self.K, self.K))
+        _lib.check(self.lib.bpmf_hip_side_hyper_get(side.handle, _ptr(alpha), _ptr(mu), _ptr(LF)))
+        return alpha, mu, np.ascontiguousarray(np.transpose(LF, (0, 2, 1)))      # (column-major slots)
+
+    def foldin_chunk(self):
+        """Ratings the fold-in kernel stages per pass over the Gram (kFoldinChunk; the tests sit on its edges)."""
+        return int(self.lib.bpmf_hip_foldin_chunk())
+
+    def foldin(self, side, cand, mean_rating, rows, tag, draw=True):
+        """Folds new rows of `side` in from their ratings: rows is a scipy.sparse matrix [n_new, cand.ncols]
+        (stored zeros are ratings of 0; entries of one cell are NOT summed: the library refuses a cell listed twice) or a CSR triple
+        (rowptr, colidx, vals).  Every kept sample s of cand's ring and slot s of the side's hyper ring give one draw of each row's
+        factors -- draw=False: the conditional mean -- from the streams named by tag >= 1.  Replaces an earlier set; rows = None
+        frees it.  A row whose Lambda* has a pivot that is not positive raises BpmfHipError (code -4) naming it; its factors are
+        stored as zeros."""
+        if rows is None:
+            _lib.check(self.lib.bpmf_hip_foldin(side.handle, cand.handle if cand is not None else None, 0.0, 0, None, None, None, 1, 0))
+            return
+        rowptr, colidx, vals = foldin_csr(rows, cand.ncols)
+        _lib.check(self.lib.bpmf_hip_foldin(side.handle, cand.handle, float(mean_rating), len(rowptr) - 1, _ptr(rowptr), _ptr(colidx), _ptr(vals),
+                                            int(tag), 1 if draw else 0))
+
+    def foldin_last_ms(self, side):
+        """Device time of the newest launch of the fold-in kernel of the side, between two events (tools/foldin_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_foldin_last_ms(side.handle, C.byref(ms)))
+        return ms.value
+
+    def foldin_count(self, side):
+        return int(self.lib.bpmf_hip_foldin_count(side.handle))
+
+    def foldin_get(self, side, padded=False):
+        """The folded-in factors u_is, [n_new, S, K]; padded=True: as the ring stores them, [n_new, S, Kp] with Kp = K rounded up to a
+        multiple of 4 (the pad components are zeros)."""
+        n, S = self.foldin_count(side), int(self.lib.bpmf_hip_foldin_samples(side.handle))
+        if padded:
+            E = np.empty((n, S, (self.K + 3) // 4 * 4))
+            _lib.check(self.lib.bpmf_hip_foldin_get_padded(side.handle, _ptr(E)))
+            return E
+        E = np.empty((n, S, self.K))
+        _lib.check(self.lib.bpmf_hip_foldin_get(side.handle, _ptr(E)))
+        return E
+
+    def foldin_predict(self, side, cand, mean_rating, q_from=0, q_to=None, c_from=0, c_to=None):
+        """(mean, std), [q_to - q_from, c_to - c_from] each, of the folded-in rows [q_from, q_to) of `side` against the columns
+        [c_from, c_to) of `cand`: predict_block with the fold-in ring as the queries.  The observation noise 1 / alpha is not part of
+        std."""
+        q_to = self.foldin_count(side) if q_to is None else int(q_to)
+        c_to = cand.ncols if c_to is None else int(c_to)
+        mean = np.empty((max(0, q_to - int(q_from)), max(0, c_to - int(c_from))))
+        std = np.empty_like(mean)
+        _lib.check(self.lib.bpmf_hip_foldin_predict(side.handle, cand.handle, float(mean_rating), int(q_from), q_to, int(c_from), c_to,
+                                                    _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def foldin_topn(self, side, cand, mean_rating, n, exclude_rated=True):
+        """(idx int32, mean, std), [n_new, n] each: the n best columns of `cand` for every folded-in row by posterior mean, without
+        the columns the row itself rated (exclude_rated).  Empty slots: idx -1, mean 0, std 0."""
+        nq = self.foldin_count(side)
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        mean = np.empty((nq, int(n)))
+        std = np.empty((nq, int(n)))
+        _lib.check(self.lib.bpmf_hip_foldin_topn(side.handle, cand.handle, float(mean_rating), int(n), 1 if exclude_rated else 0,
+                                                 _ptr(idx), _ptr(mean), _ptr(std)))
+        return idx, mean, std
+
     # -- adaptive noise precision ----------------------------------------------
     def train_sse(self, side, other):
         """(SSE, n): the sum of squared training residuals (v - mean - x_c . y_r)^2 over the n ratings of `side`, with the
@@ -779,6 +868,30 @@ def csr_arrays(F):
     if len(colidx) == 0:
         colidx = np.zeros(1, np.int32)
     return rowptr, colidx, (None if len(vals) and np.all(vals == 1.0) else (vals if len(vals) else None))
+
+
+def foldin_csr(rows, ncols):
+    """(rowptr int64, colidx int32, vals float64) of the new rows of a fold-in: a scipy.sparse matrix [n_new, ncols] with its
+    indices sorted within a row and NOTHING summed (a cell stored twice stays twice, for the library to refuse), or a CSR triple
+    passed through."""
+    if _is_sparse(rows):
+        if rows.ndim != 2 or rows.shape[1] != ncols:
+            raise ValueError("foldin: the new rows must be [n_new, %d], one column per column of the candidate side" % ncols)
+        R = rows.tocsr().astype(np.float64)
+        if not R.has_sorted_indices:
+            R = R.copy()
+            R.sort_indices()
+        rowptr, colidx, vals = R.indptr, R.indices, R.data
+    else:
+        rowptr, colidx, vals = rows
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    colidx = np.ascontiguousarray(colidx, np.int32)
+    vals = np.ascontiguousarray(vals, np.float64)
+    if rowptr.ndim != 1 or len(rowptr) < 1 or len(colidx) != len(vals) or (len(rowptr) and int(rowptr[-1]) != len(colidx)):
+        raise ValueError("foldin: (rowptr, colidx, vals) is not a CSR triple")
+    if len(colidx) == 0:
+        colidx = np.zeros(1, np.int32); vals = np.zeros(1)
+    return rowptr, colidx, vals
 
 
 def link_spmm_nn(F, V, device=0):

@@ -187,7 +187,7 @@ class Sys:
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
-          new_row_features=None, new_col_features=None, topn_score=None):
+          new_row_features=None, new_col_features=None, topn_score=None, foldin=False):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -262,7 +262,21 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     With topn=N also res["new_rows_topn"] / res["new_cols_topn"] = (idx, mean, std), [n_new, N] each, the new entities as the
     queries.  These two are ALWAYS ranked by the posterior mean, also when topn_score ranks res["topn"] by another key: the score
     of a new entity would need the w[c] / S term of its variance (out of scope).  None (the default):
-    nothing changes."""
+    nothing changes.
+
+    foldin=True: the run keeps what bpmf_amd.fold_in(res, ...) needs to give users (movies) that arrive AFTER it, with a few ratings
+    and no features, their factors: the sample rings of both sides and, per side without features, the
+    hyper-parameters (alpha, mu, Lambda) every post-burn-in iteration ran with (engine.hyper_add, where samples_add sits; nsims -
+    burnin slots; with noise="adaptive" the iteration's own alpha).  The engine must stay open for fold_in.  Needs nsims > burnin;
+    refused with probit=True and when both sides have features.  res["foldin"] = True.  False (the default): nothing changes."""
+    if foldin:                                       # (refused before the engine is used)
+        if probit:
+            raise ValueError("foldin=True does not go together with probit=True (labels would need a latent iteration of their own)")
+        if row_features is not None and col_features is not None:
+            raise ValueError("foldin=True: both sides have features, so neither can be folded into (the prior mean of a new row "
+                             "needs its features: new_row_features / new_col_features)")
+        if nsims - burnin < 1:
+            raise ValueError("foldin=True needs at least one post-burn-in sample (nsims > burnin)")
     if topn_score is not None:                       # (refused before the engine is used)
         if topn is None:
             raise ValueError("topn_score needs topn=N (it ranks the top-N lists)")
@@ -361,6 +375,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         if row_features is not None:
             engine.set_features(users.side, row_features, lambda_beta, 4)
         movies.linked = users.linked = True
+        movies.linked_features, users.linked_features = col_features is not None, row_features is not None
         sparse_sides = [sd for sd, F in ((movies, col_features), (users, row_features)) if F is not None and _engine._is_sparse(F)]
         for sd in sparse_sides:
             engine.link_cg_set(sd.side, link_tol, link_max_iter)
@@ -371,8 +386,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None       # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None
+    ring_movies = topn is not None or new_row_features is not None or foldin   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin
+    hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if foldin and F is None]
+    for sd in hyper_sides:
+        engine.hyper_reserve(sd.side, nsims - burnin)
     if ring_movies:
         engine.samples_reserve(movies.side, nsims - burnin)
     if ring_users:
@@ -394,6 +412,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             engine.samples_add(users.side)
         if ring_movies and i >= burnin:
             engine.samples_add(movies.side)
+        if i >= burnin:
+            for sd in hyper_sides:                   # (mu, Lambda) this iteration's half-iteration of the side ran with, and its alpha
+                engine.hyper_add(sd.side, Sys.alpha)
         if new_row_features is not None and i >= burnin:
             engine.newrows_add(users.side, movies.side)
         if new_col_features is not None and i >= burnin:
@@ -509,10 +530,58 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         res["new_cols"] = dict(mean=mean.T.copy(), std=std.T.copy())
         if topn is not None:
             res["new_cols_topn"] = engine.newrows_topn(movies.side, users.side, movies.mean_rating, topn)
+    if foldin:
+        res["foldin"] = True
     res["movies"], res["users"] = movies, users
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res
+
+
+FOLDIN_TAGS = {"rows": 7, "cols": 8}                 # the random streams of folded-in users / movies (1 .. 6 are taken: gibbs)
+
+
+def fold_in(res, new_rows=None, new_cols=None, topn=None, draw=True):
+    """Predictions for users / movies that arrived after the run `res` = gibbs(..., foldin=True), from their ratings alone (DESIGN.md
+    section 19).  new_rows: scipy.sparse [n_new, nmovies], the ratings of new users; new_cols: scipy.sparse [nusers, n_new], the
+    ratings of new movies (oriented as the training matrix).  Every kept sample gives one draw of an entity's factors from their
+    conditional given that sample of the other side (draw=False: the conditional mean); mean and std are those of the predictions
+    over the samples (the observation noise 1 / alpha is not part of std).
+
+    Returns a dict with "rows": dict(mean, std), [n_new, nmovies] each, and / or "cols": dict(mean, std), [nusers, n_new] each;
+    with topn=N each also has "topn": (idx, mean, std), [n_new, N] each, the new entities as the queries and their own ratings
+    excluded (the format of res["new_rows_topn"]).  The engine of the run must still be open."""
+    if not isinstance(res, dict) or not res.get("foldin"):
+        raise ValueError("fold_in needs the result of gibbs(..., foldin=True) (the kept samples and hyper-parameters)")
+    if new_rows is None and new_cols is None:
+        raise ValueError("fold_in: give new_rows and / or new_cols")
+    if topn is not None and int(topn) < 1:
+        raise ValueError("fold_in: topn must be >= 1")
+    users, movies = res["users"], res["movies"]
+    jobs = []
+    for key, new, side, cand in (("rows", new_rows, users, movies), ("cols", new_cols, movies, users)):
+        if new is None:
+            continue
+        if not _engine._is_sparse(new):
+            raise ValueError("fold_in: new_%s must be a scipy.sparse matrix" % key)
+        if getattr(side, "linked_features", False):
+            raise ValueError("fold_in: the %s have features: the prior mean of a new one needs its features (gibbs(new_%s_features=))"
+                             % ("users" if key == "rows" else "movies", "row" if key == "rows" else "col"))
+        R = new.tocsr() if key == "rows" else new.T.tocsr()
+        if R.shape[1] != cand.num() or R.shape[0] < 1:
+            raise ValueError("fold_in: new_%s must be %s" % (key, "[n_new >= 1, %d]" % cand.num() if key == "rows" else "[%d, n_new >= 1]" % cand.num()))
+        if not np.all(np.isfinite(R.data)):
+            raise ValueError("fold_in: new_%s holds a rating that is not finite" % key)
+        jobs.append((key, R, side, cand))
+    out = {}
+    for key, R, side, cand in jobs:
+        engine = side.engine
+        engine.foldin(side.side, cand.side, movies.mean_rating, R, FOLDIN_TAGS[key], draw)
+        mean, std = engine.foldin_predict(side.side, cand.side, movies.mean_rating)
+        out[key] = dict(mean=mean, std=std) if key == "rows" else dict(mean=mean.T.copy(), std=std.T.copy())
+        if topn is not None:
+            out[key]["topn"] = engine.foldin_topn(side.side, cand.side, movies.mean_rating, int(topn))
+    return out
 
 
 if __name__ == "__main__":

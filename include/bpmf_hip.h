@@ -349,6 +349,54 @@ BPMF_API int bpmf_hip_newrows_predict(bpmf_hip_side *side, bpmf_hip_side *cand, 
 BPMF_API int bpmf_hip_newrows_topn(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int n, int new_are_queries,
                                    int32_t *idx_out, double *mean_out, double *std_out);
 
+/* ---- fold-in: new rows from their ratings against the kept samples ---------
+ * A row i that arrives after training with ratings {(j, r_ij)} over the columns of `cand` and no features.  Given kept sample s of
+ * `cand` (v_js, its sample ring) and the hyper-parameters (alpha_s, mu_s, Lambda_s) the side of the row ran with at that iteration,
+ *   Lambda* = Lambda_s + alpha_s sum_j v_js v_js^T,   b = Lambda_s mu_s + alpha_s sum_j (r_ij - mean_rating) v_js,
+ *   Lambda* = L L^T,   u_is = L^-T (L^-1 b + z),   z ~ N(0, I)
+ * the conditional bpmf_hip_sample_side draws from; no rating: a draw from the prior N(mu_s, Lambda_s^-1).  The influence of the
+ * row on `cand` and on the hyper-parameters is ignored.  fp64 on every context.
+ *   _hyper_reserve(side, max)   room for the hyper-parameters of max kept samples of the side (host memory); again: an empty ring
+ *       of the new size; 0 frees it.
+ *   _hyper_add(side, alpha, mu, LambdaF)   the next slot: alpha finite >= 0, mu (K), LambdaF (K x K, symmetric), finite.  mu ==
+ *       NULL && LambdaF == NULL: the hyper-parameters the side's newest bpmf_hip_sys_sample ran with (waits for its collection,
+ *       as bpmf_hip_sys_state); call it where bpmf_hip_side_samples_add of the OTHER side sits.  BPMF_HIP_EINVAL once the ring
+ *       is full.
+ *   _hyper_get                  the held slots: alpha (S), mu (S x K), LambdaF (S x K x K, each as given); any may be NULL.
+ *   bpmf_hip_foldin(side, cand, mean_rating, n_new, rowptr, colidx, vals, tag, draw)   n_new >= 1 rows by rows (rowptr n_new + 1
+ *       entries from 0, monotone; colidx in [0, cand's columns), strictly ascending within a row -- a column listed twice is an
+ *       error that names row and column; vals finite), checked on the host before the device is used.  The hyper ring of `side`
+ *       and the sample ring of `cand` must hold the same number S >= 1 of samples.  tag >= 1 names the random streams: block n
+ *       of (row i of the batch, slot s) is Philox (i lo, i hi, s, n; 42, tag) and gives the normals 2 n, 2 n + 1 by Box-Muller,
+ *       so the factors of a row depend on its index in the batch, not on the other rows; draw == 0: z = 0, the conditional
+ *       mean.  Replaces an earlier set; n_new = 0 frees it.  Waits.  BPMF_HIP_ECHOL names a row with a pivot that is not positive
+ *       and finite: its factors are stored as zeros, the set is kept.  BPMF_HIP_ENOMEM names the size that did not fit.
+ *   _foldin_get / _get_padded   the factors, n_new x S x K / as the ring stores them, n_new x S x Kp (Kp = K rounded up to a
+ *       multiple of 4, pad components 0).
+ *   _foldin_predict             bpmf_hip_predict_block with the folded-in rows as the queries: a folded-in row is predicted like a
+ *       row that had been in the matrix (the draw carries its uncertainty; 1 / alpha is not part of std).
+ *   _foldin_topn                bpmf_hip_topn with the folded-in rows as the queries (n_new x n); exclude_rated != 0: without the
+ *       columns the row itself rated.
+ * Refused (BPMF_HIP_EINVAL): a communicator or a sharded side, the BPMF_REDUCE formulation, propagated priors, a probit side, and
+ * a `side` with features (bpmf_hip_side_newrows_set predicts such rows).  A censored training side is fine; the ratings of a
+ * folded-in row are exact values.  bpmf_hip_foldin_chunk: the ratings the kernel stages per pass (tests). */
+BPMF_API int bpmf_hip_side_hyper_reserve(bpmf_hip_side *side, int max_samples);
+BPMF_API int bpmf_hip_side_hyper_add(bpmf_hip_side *side, double alpha, const double *mu, const double *LambdaF);
+BPMF_API int bpmf_hip_side_hyper_count(const bpmf_hip_side *side);
+BPMF_API int bpmf_hip_side_hyper_get(const bpmf_hip_side *side, double *alpha, double *mu, double *LambdaF);
+BPMF_API int bpmf_hip_foldin(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int64_t n_new, const int64_t *rowptr,
+                             const int32_t *colidx, const double *vals, unsigned tag, int draw);
+BPMF_API int bpmf_hip_foldin_count(const bpmf_hip_side *side);      /* n_new of the held set (0: none) */
+BPMF_API int bpmf_hip_foldin_samples(const bpmf_hip_side *side);    /* S of the held set */
+BPMF_API int bpmf_hip_foldin_get(bpmf_hip_side *side, double *E_host);
+BPMF_API int bpmf_hip_foldin_get_padded(bpmf_hip_side *side, double *E_host);
+BPMF_API int bpmf_hip_foldin_predict(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                     int64_t c_from, int64_t c_to, double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_foldin_topn(bpmf_hip_side *side, bpmf_hip_side *cand, double mean_rating, int n, int exclude_rated,
+                                  int32_t *idx_out, double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_foldin_last_ms(const bpmf_hip_side *side, float *ms);   /* device time of the newest launch of the kernel, between two events */
+BPMF_API int bpmf_hip_foldin_chunk(void);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
