@@ -9,5 +9,6 @@ from ._lib import load_library, library_path, BpmfHipError  # noqa: F401
 from .engine import HipEngine, auc, hyper_sample, link_lambda_sample  # noqa: F401
 from .sys import Sys, HyperParams, gibbs, fold_in  # noqa: F401
 from .censor import censor_flags  # noqa: F401
+from .weights import rating_weights  # noqa: F401
 
-__all__ = ["load_library", "library_path", "BpmfHipError", "HipEngine", "auc", "hyper_sample", "Sys", "HyperParams", "gibbs", "fold_in", "censor_flags"]
+__all__ = ["load_library", "library_path", "BpmfHipError", "HipEngine", "auc", "hyper_sample", "Sys", "HyperParams", "gibbs", "fold_in", "censor_flags", "rating_weights"]

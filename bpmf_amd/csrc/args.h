@@ -104,6 +104,9 @@ struct SampleArgs {
     unsigned long long wait_ticks;
     unsigned long long *stamps; // profiling only (BPMF_HIP_STAMPS=1): s_memtime at phase boundaries of two probe items, or NULL
     uint32_t ablate;            // profiling only (BPMF_HIP_ABLATE): 1 = skip the factorisation, 2 = skip the Gram, 4 = gather from 64 hot rows only
+    // per-rating precision weights (the weighted forms only: k_sample1w, k_sample4w, k_sample_slabw, k_sample1sw, k_sample_wg2w; DESIGN.md
+    // section 20): sqrt(w) of every rating in the layout of `vals`, which then holds sqrt(w) (r - mean) and is read with mean_rating = 0
+    const double *sw;
 };
 
 // What else one k_sample1 launch carries besides its work items (see k_sample1 in kernels.h): the gate +

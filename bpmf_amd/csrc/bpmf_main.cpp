@@ -45,6 +45,10 @@
 // is only a bound: an entry > 0 = the true value is at least the recorded one, < 0 = at most (.sbm: every
 // listed cell is a lower bound).  Both sides redraw the latent values of their censored cells on the device ahead of every sampler
 // launch (bpmf_hip_side_set_censored); one more header line counts the bounds, everything else keeps its format.
+// --weights FILE (one GPU, no -g): FILE is a sparse matrix of the training matrix's shape with a precision weight w > 0 for the
+// training cells it lists: such a rating is observed with the precision alpha w, every other one with alpha.
+// Both sides get their weights once (bpmf_hip_side_set_weights) and run the weighted form of their sampler; one more header line
+// counts the weighted cells, everything else keeps its format.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -82,7 +86,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--weights FILE] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -150,6 +154,10 @@ void usage()
               << "              one, < 0 = at most; every entry must be a cell of the training matrix.  The latent values of these cells are\n"
               << "              redrawn on the device in every half-iteration (one GPU, no -g; not with --probit, --noise adaptive,\n"
               << "              --row-features / --col-features, -m / -l or BPMF_REDUCE=1)\n"
+              << "  [--weights FILE]: a precision weight per training rating: a sparse matrix of the training matrix's shape (.sdm, coordinate\n"
+              << "              .mtx; optional .gz) whose entries w > 0 weight the ratings of their cells -- precision alpha w instead of alpha;\n"
+              << "              every entry must be a cell of the training matrix, every other rating has weight 1 (one GPU, no -g; not with\n"
+              << "              --probit, --censored, --noise adaptive, --row-features / --col-features, -m / -l, --fp32 or BPMF_REDUCE=1)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -299,6 +307,9 @@ struct Job {
     bool censored = false;                                           // --censored FILE
     std::vector<int8_t> cens_m, cens_u;                              // the flags of every rating of M / Mt (0, +1 lower bound, -1 upper bound)
     int64_t cens_right = 0, cens_left = 0;
+    bool weighted = false;                                           // --weights FILE
+    std::vector<double> w_m, w_u;                                    // the weight of every rating of M / Mt
+    int64_t w_count = 0; double w_min = 1.0, w_max = 1.0;            // listed cells whose weight is not 1; the smallest / largest weight
     std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
     double auc = NAN, brier = NAN;
     Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
@@ -371,6 +382,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.censored) {                                                // (streams: tag 5 = movies, 6 = users)
         check(bpmf_hip_side_set_censored(movies, J.cens_m.data(), 5));
         check(bpmf_hip_side_set_censored(users, J.cens_u.data(), 6));
+    }
+    if (J.weighted) {
+        check(bpmf_hip_side_set_weights(movies, J.w_m.data()));
+        check(bpmf_hip_side_set_weights(users, J.w_u.data()));
     }
     const bool linked = J.has_feat_u() || J.has_feat_m();   // (streams: tag 3 = movies, 4 = users)
     auto set_sparse = [&](bpmf_hip_side *side, const Csc &Fr, int64_t D, unsigned tag) {       // Fr: F by rows (column = item)
@@ -469,6 +484,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
               "with the raw label and are not an error measure" << std::endl;
     if (J.censored)
         os << "censored: " << J.cens_right << " lower bounds, " << J.cens_left << " upper bounds of " << J.M.nnz() << " training ratings" << std::endl;
+    if (J.weighted)
+        os << "weights: " << J.w_count << " of " << J.M.nnz() << " training ratings weighted, min " << J.w_min << ", max " << J.w_max << std::endl;
     if (linked) {
         os << "side information:";
         if (J.sfeat_u_d > 0) os << " row features sparse D = " << J.sfeat_u_d << " nnz = " << J.sfeat_u.nnz() << ",";
@@ -749,12 +766,13 @@ int main(int argc, char *argv[])
                                               {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
                                               {"lambda-beta-prior", required_argument, nullptr, 1013},
                                               {"censored", required_argument, nullptr, 1014},
+                                              {"weights", required_argument, nullptr, 1030},
                                               {"new-row-features", required_argument, nullptr, 1015}, {"new-col-features", required_argument, nullptr, 1016},
                                               {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
                                               {"topn-threshold", required_argument, nullptr, 1019},
                                               {"fold-in-rows", required_argument, nullptr, 1020}, {"fold-in-cols", required_argument, nullptr, 1021},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
     bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
@@ -776,6 +794,7 @@ int main(int argc, char *argv[])
         case 1012: link_max_iter = optarg; break;
         case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
         case 1014: censored_file = optarg; J.censored = true; break;
+        case 1030: weights_file = optarg; J.weighted = true; break;
         case 1015: new_row_features = optarg; break;
         case 1016: new_col_features = optarg; break;
         case 1017: topn_score = optarg; break;
@@ -954,6 +973,19 @@ int main(int argc, char *argv[])
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--censored does not go together with BPMF_REDUCE=1");
         if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--censored needs a noise precision -a F > 0");
     }
+    // --weights: checked before anything touches a GPU (the file itself below, once the training matrix is read)
+    if (J.weighted) {
+        if (weights_file.empty()) die("--weights expects a file");
+        if (ngpu >= 1) die("--weights runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (a sharded side has no weighted sampler)");
+        if (J.probit) die("--weights does not go together with --probit (the latent scores have unit variance)");
+        if (J.censored) die("--weights does not go together with --censored (the latent draw would need the weight of its cell)");
+        if (J.adaptive) die("--weights does not go together with --noise adaptive (alpha | r would need the weighted residuals)");
+        if (linked) die("--weights does not go together with --row-features / --col-features (the link matrix would need the weighted residuals)");
+        if (!mname.empty() || !lname.empty()) die("--weights does not go together with a propagated posterior (-m / -l)");
+        if (fp32) die("--weights does not go together with --fp32 (the weighted samplers are fp64)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--weights does not go together with BPMF_REDUCE=1");
+        if (!sparse_file(weights_file)) die("--weights: " + weights_file + " is not a sparse matrix file (.sdm or a coordinate .mtx)");
+    }
     // --fold-in-rows / --fold-in-cols: checked before anything touches a GPU (the files themselves below, once the shape is known)
     for (int which = 0; which < 2; ++which) {
         const std::string &name = which ? fold_in_cols : fold_in_rows;
@@ -1010,8 +1042,37 @@ int main(int argc, char *argv[])
                 (v > 0.0 ? J.cens_right : J.cens_left) += 1;
             }
     }
+    // --weights FILE: the weights as a matrix with the structure of M (1 where FILE lists nothing), so that they follow the ratings
+    // through the renumbering and the transpose below.  Cells are named in 1-based ids of the input.
+    Csc WF;
+    if (J.weighted) {
+        Csc W;
+        try { W = bpmf::io::read_sparse(weights_file); } catch (const std::exception &e) { die(e.what()); }
+        if (W.nrows != J.M.nrows || W.ncols != J.M.ncols)
+            die("--weights: " + weights_file + " is " + std::to_string(W.nrows) + " x " + std::to_string(W.ncols) + ", the training matrix is " +
+                std::to_string(J.M.nrows) + " x " + std::to_string(J.M.ncols));
+        WF = J.M;
+        std::fill(WF.vals.begin(), WF.vals.end(), 1.0);
+        bool first = true;
+        for (int64_t c = 0; c < W.ncols; ++c)
+            for (int64_t q = W.colptr[(size_t)c]; q < W.colptr[(size_t)c + 1]; ++q) {
+                const int32_t r = W.rowidx[(size_t)q];
+                const double v = W.vals[(size_t)q];
+                const std::string cell = "cell (" + std::to_string((long long)r + 1) + ", " + std::to_string((long long)c + 1) + ")";
+                if (!std::isfinite(v) || !(v > 0.0)) die("--weights: the weight of " + cell + " of " + weights_file + " is not finite and > 0");
+                const int32_t *b = J.M.rowidx.data() + J.M.colptr[(size_t)c], *e = J.M.rowidx.data() + J.M.colptr[(size_t)c + 1];
+                const int32_t *at = std::lower_bound(b, e, r);
+                if (at == e || *at != r) die("--weights: " + cell + " of " + weights_file + " is not a cell of the training matrix");
+                WF.vals[(size_t)(at - J.M.rowidx.data())] = v;
+                J.w_count += v != 1.0;
+                J.w_min = first ? v : std::min(J.w_min, v); J.w_max = first ? v : std::max(J.w_max, v);
+                first = false;
+            }
+        if ((int64_t)W.vals.size() < J.M.nnz()) { J.w_min = std::min(J.w_min, 1.0); J.w_max = std::max(J.w_max, 1.0); }   // (the unlisted cells)
+    }
     const int64_t rows = std::max(J.M.nrows, J.T.nrows), cols = std::max(J.M.ncols, J.T.ncols);
     if (J.censored) bpmf::io::resize(CF, rows, cols);
+    if (J.weighted) bpmf::io::resize(WF, rows, cols);
     bpmf::io::resize(J.M, rows, cols);
     bpmf::io::resize(J.T, rows, cols);
     if (J.M.nnz() == 0) die("the training matrix is empty");
@@ -1156,6 +1217,7 @@ int main(int argc, char *argv[])
         J.M = permute(J.M, J.perm_m, inv_u);
         J.T = permute(J.T, J.perm_m, inv_u);
         if (J.censored) CF = permute(CF, J.perm_m, inv_u);
+        if (J.weighted) WF = permute(WF, J.perm_m, inv_u);
         J.Mt = bpmf::io::transpose(J.M);
         permute_columns(J.prop_m_mu.data, K, J.perm_m); permute_columns(J.prop_m_lambda.data, (int64_t)K * K, J.perm_m);
         permute_columns(J.prop_u_mu.data, K, J.perm_u); permute_columns(J.prop_u_lambda.data, (int64_t)K * K, J.perm_u);
@@ -1175,6 +1237,11 @@ int main(int argc, char *argv[])
         J.cens_m.assign(std::max<size_t>(CF.vals.size(), 1), 0); J.cens_u.assign(std::max<size_t>(CFt.vals.size(), 1), 0);
         for (size_t q = 0; q < CF.vals.size(); ++q) J.cens_m[q] = (int8_t)CF.vals[q];
         for (size_t q = 0; q < CFt.vals.size(); ++q) J.cens_u[q] = (int8_t)CFt.vals[q];
+    }
+    if (J.weighted) {                                                // (WF has the structure of M, its transpose that of Mt)
+        const Csc WFt = bpmf::io::transpose(WF);
+        J.w_m = WF.vals; J.w_u = WFt.vals;
+        if (J.w_m.empty()) { J.w_m.assign(1, 1.0); J.w_u.assign(1, 1.0); }
     }
     J.Tt = bpmf::io::transpose(J.T);
     if (J.sharded) check(bpmf_hip_comm_unique_id(J.rccl_id));      // (also loads RCCL before the rank threads start)

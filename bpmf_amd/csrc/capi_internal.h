@@ -11,10 +11,11 @@
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
+//   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last eight (probit, censoring, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last nine (probit, censoring, weights, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>

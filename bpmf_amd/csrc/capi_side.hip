@@ -359,7 +359,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     if (s->own_items && s->d_items) (void)hipFree(s->d_items);
     if (s->d_items_alt) (void)hipFree(s->d_items_alt);
     if (s->d_prop) (void)hipFree(s->d_prop);
-    s->probit.reset(); s->censor.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
+    s->probit.reset(); s->censor.reset(); s->weights.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
     if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
     if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
     void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,
@@ -410,6 +410,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: NULL");
     (void)mu;
+    if (Lambda && s->weights) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }
@@ -542,17 +543,21 @@ extern "C" int bpmf_hip_side_kernel_name(const bpmf_hip_side *s, char *buf, int 
     const bool dist = c->comm != nullptr && !s->bounds.empty();
     const bool fusable = !dist && !s->reduce_on && env_int("BPMF_HIP_FUSED", 1) != 0 && s->nwork > 0;
     std::string name;
+    // a side with per-rating weights (capi_weights.hip) launches the weighted form of its family: "w" behind the kernel's name; at
+    // K <= 32 never the gather stream, at K = 64 every column in the slab form
+    const bool wt = s->weights != nullptr;
+    const std::string w = wt ? "w" : "";
     if (s->reduce_on) name = "k_sample_prec<" + k + "> + k_precompute<" + k + ">";
     else if (c->dtype == BPMF_HIP_F32) name = "k_sample_wg2<128,2>";
-    else if (K == 128) name = "k_sample_wg2<128,4,double>";
+    else if (K == 128) name = "k_sample_wg2" + w + "<128,4,double>";
     else if (K == 64) {
-        if (s->lr_n > 0 && !s->d_prop && !c->diag_only) {
+        if (s->lr_n > 0 && !s->d_prop && !c->diag_only && !wt) {
             static const char *nb[3] = {"3", "6", "16"};
             for (int pc = 0; pc < 3; ++pc)
                 if (s->pf_class[pc + 1] > s->pf_class[pc]) name += std::string(name.empty() ? "" : " + ") + "k_sample_pf<64," + nb[pc] + ">";
             if (s->hv_nwork > 0) name += " + k_sample_slab<64>";
-        } else name = (fusable && s->lr_n == 0 && s->nsub <= 1) ? "k_sample1s<64>" : "k_sample_slab<64>";
-    } else name = (s->mode == 3 ? "k_sample4<" : uses_gather_stream(s) ? "k_sample1<" : "k_sample1i<") + k + ">";     // (k_sample1i: the index-block form)
+        } else name = ((fusable && s->lr_n == 0 && s->nsub <= 1) ? "k_sample1s" : "k_sample_slab") + w + "<64>";
+    } else name = (s->mode == 3 ? "k_sample4" + w + "<" : wt ? "k_sample1w<" : uses_gather_stream(s) ? "k_sample1<" : "k_sample1i<") + k + ">";     // (k_sample1i: the index-block form)
     snprintf(buf, (size_t)n, "%s", name.c_str());
     return BPMF_HIP_OK;
 }

@@ -47,6 +47,10 @@ struct bpmf_censor {
     int64_t n = 0, nright = 0, nleft = 0; uint32_t tag = 0;
 };
 
+// per-rating precision weights (capi_weights.hip): sw = sqrt(w) and zw = sqrt(w) (r - mean_rating) of every rating
+// (layout of d_vals).  The weighted forms of the samplers read zw in place of d_vals with mean 0 and multiply every gathered row by sw.
+struct bpmf_weights { DevBuf<double> sw, zw; int64_t nweighted = 0; double wmin = 1.0, wmax = 1.0; };
+
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
 struct bpmf_link_dense {
     DevBuf<double> F, W, PE;

@@ -471,25 +471,35 @@ __device__ __forceinline__ double row_ror_add(double x)
 // nothing is computed from the loads here, so the wave does not wait for them before their first use in gather().
 // (With `(q < len) ? (vals[q] - mean) * alpha : 0` the compiler put each load in a branch of its own and waited for it
 // on the spot: the normal draw that was meant to run in the shadow of these loads started after them.)
-struct IdxBlock { int ri; double v; int base; };
-__device__ __forceinline__ IdxBlock load_idx_block(const int32_t *__restrict__ rowidx, const double *__restrict__ vals, int base, int lane, int len,
-                                                   const double *__restrict__ safe)
+// WT (the weighted forms): the block also keeps sqrt(w) of its slot, loaded from `sw` the same way (slots beyond
+// the chunk: the 0.0 of `safe`); gather() hands it on, contract() multiplies the gathered row by it.
+template <bool WT> struct IdxBlockT { int ri; double v; int base; };
+template <> struct IdxBlockT<true> { int ri; double v; int base; double s; };
+typedef IdxBlockT<false> IdxBlock;
+template <bool WT = false>
+__device__ __forceinline__ IdxBlockT<WT> load_idx_block(const int32_t *__restrict__ rowidx, const double *__restrict__ vals, int base, int lane, int len,
+                                                        const double *__restrict__ safe, const double *__restrict__ sw = nullptr)
 {
-    IdxBlock r;
+    IdxBlockT<WT> r;
     const int q = base + lane;
     const int32_t *pr = (q < len) ? rowidx + q : reinterpret_cast<const int32_t *>(safe);
     const double *pv = (q < len) ? vals + q : safe;
     r.ri = *pr;
     r.v = *pv;
+    if constexpr (WT) {
+        const double *ps = (q < len) ? sw + q : safe;
+        r.s = *ps;
+    }
     r.base = base;
     return r;
 }
 
-template <int K>
+template <int K, bool WT = false>
 __device__ __forceinline__ void gram_chunk44(const int32_t *__restrict__ rowidx, const double *__restrict__ vals, int len,
                                              const double *__restrict__ other, const double *__restrict__ zero_row,
-                                             double mean, double alpha, IdxBlock cur, IdxBlock nxt,
-                                             double (&acc)[Geo44<K>::NB], double (&rr)[Geo44<K>::NG], int lane, int rowmask = -1)
+                                             double mean, double alpha, IdxBlockT<WT> cur, IdxBlockT<WT> nxt,
+                                             double (&acc)[Geo44<K>::NB], double (&rr)[Geo44<K>::NG], int lane, int rowmask = -1,
+                                             const double *__restrict__ sw = nullptr)
 {
     using G = Geo44<K>;
     constexpr int NG = G::NG, NL = G::NL;
@@ -499,19 +509,26 @@ __device__ __forceinline__ void gram_chunk44(const int32_t *__restrict__ rowidx,
     // the four 16-rating groups of a block fetch their row ids with a cross-lane permute.  The
     // gathers run one group ahead of the MFMAs in two alternating operand sets, across block
     // boundaries too; padding slots of a ragged last group gather a row of zeros.
-    auto gather = [&](const IdxBlock &ib, int gg, dd2 (&yy)[NL], double &ww) {
+    auto gather = [&](const IdxBlockT<WT> &ib, int gg, dd2 (&yy)[NL], double &ww, double &ss) {
         const int src = gg * 16 + slot;
         const int row = __shfl(ib.ri, src);
         ww = (__shfl(ib.v, src) - mean) * alpha;                                  // c++/sample.cpp:256 (padding slots: times a row of zeros)
+        if constexpr (WT) ss = __shfl(ib.s, src);
         const double *base = (ib.base + src < len) ? other + (size_t)(row & rowmask) * K : zero_row;
         const dd2 *p = reinterpret_cast<const dd2 *>(base + 2 * x);
 #pragma unroll
         for (int h = 0; h < NL; ++h) yy[h] = p[4 * h];
     };
-    auto contract = [&](const dd2 (&yy)[NL], double ww) {
+    // (weighted: the row enters the rhs update and the MFMAs as sqrt(w) u -- scaled here, where the gathered row is first used, so
+    //  that nothing waits for a gather where it is issued)
+    auto contract = [&](const dd2 (&yy)[NL], double ww, double ss) {
         double R[NG];
 #pragma unroll
         for (int h = 0; h < NL; ++h) { R[2 * h] = yy[h].x; R[2 * h + 1] = yy[h].y; }
+        if constexpr (WT) {
+#pragma unroll
+            for (int g = 0; g < NG; ++g) R[g] *= ss;
+        }
 #pragma unroll
         for (int g = 0; g < NG; ++g) rr[g] = fma(R[g], ww, rr[g]);
         int blk = 0;
@@ -522,34 +539,39 @@ __device__ __forceinline__ void gram_chunk44(const int32_t *__restrict__ rowidx,
     };
     if (len <= 0) return;
     dd2 yA[NL], yB[NL];
-    double wA, wB = 0.0;
-    gather(cur, 0, yA, wA);
+    double wA, wB = 0.0, sA = 0.0, sB = 0.0;
+    gather(cur, 0, yA, wA, sA);
     int b0 = 0;
     // full blocks that have a successor: straight-line code, the operand sets simply alternate
     for (; b0 + 64 < len; b0 += 64) {
-        const IdxBlock nn = load_idx_block(rowidx, vals, b0 + 128, lane, len, zero_row);   // index block after the next one
-        gather(cur, 1, yB, wB);
-        contract(yA, wA);
-        gather(cur, 2, yA, wA);
-        contract(yB, wB);
-        gather(cur, 3, yB, wB);
-        contract(yA, wA);
-        gather(nxt, 0, yA, wA);                                                  // first group of the next block
-        contract(yB, wB);
+        // the index block after the next one: requested here, a whole block ahead of its first use -- except by the weighted form, whose
+        // blocks are two registers wider: three of them in flight spill at K = 32 (140 bytes per lane, 0.137 ms per ML-1M iteration
+        // against 0.098 with the request at the end of the trip, which is still three groups of MFMAs ahead of the block's first gather)
+        IdxBlockT<WT> nn{};
+        if constexpr (!WT) nn = load_idx_block<WT>(rowidx, vals, b0 + 128, lane, len, zero_row, sw);
+        gather(cur, 1, yB, wB, sB);
+        contract(yA, wA, sA);
+        gather(cur, 2, yA, wA, sA);
+        contract(yB, wB, sB);
+        gather(cur, 3, yB, wB, sB);
+        contract(yA, wA, sA);
+        gather(nxt, 0, yA, wA, sA);                                                  // first group of the next block
+        contract(yB, wB, sB);
         cur = nxt;
-        nxt = nn;
+        if constexpr (WT) nxt = load_idx_block<WT>(rowidx, vals, b0 + 128, lane, len, zero_row, sw);
+        else nxt = nn;
     }
     // last block: 1..4 groups
     const int ng = (len - b0 + 15) >> 4;
-    if (ng > 1) gather(cur, 1, yB, wB);
-    contract(yA, wA);
+    if (ng > 1) gather(cur, 1, yB, wB, sB);
+    contract(yA, wA, sA);
     if (ng > 1) {
-        if (ng > 2) gather(cur, 2, yA, wA);
-        contract(yB, wB);
+        if (ng > 2) gather(cur, 2, yA, wA, sA);
+        contract(yB, wB, sB);
         if (ng > 2) {
-            if (ng > 3) gather(cur, 3, yB, wB);
-            contract(yA, wA);
-            if (ng > 3) contract(yB, wB);
+            if (ng > 3) gather(cur, 3, yB, wB, sB);
+            contract(yA, wA, sA);
+            if (ng > 3) contract(yB, wB, sB);
         }
     }
 }
@@ -1098,7 +1120,8 @@ __device__ __forceinline__ void gate_stage_body(int block, int nblocks, const un
 
 // GS: the Gram reads the side's gather stream (gram_stream44: k_sample1) / the row ids and a value array through index
 // blocks (gram_chunk44: k_sample1i, the launches that read other values than the side's own ratings and BPMF_HIP_GATHER_STREAM=0)
-template <int K, bool GS>
+// WT: the weighted form (k_sample1w; never with GS): a.vals = sqrt(w) (r - mean), a.mean_rating = 0, a.sw = sqrt(w)
+template <int K, bool GS, bool WT = false>
 __device__ __forceinline__ void sample1_body(const SampleArgs &a, const FusedArgs &f, double *lds)
 {
     const int lane = threadIdx.x;
@@ -1120,7 +1143,8 @@ __device__ __forceinline__ void sample1_body(const SampleArgs &a, const FusedArg
 
     // the first index blocks (records of the first two groups) of the chunk are requested before anything else
     const int glen = (ablate_bits(a) & 2u) ? 0 : len;
-    IdxBlock ib0{}, ib1{};
+    static_assert(!(GS && WT), "the gather stream carries no weights");
+    IdxBlockT<WT> ib0{}, ib1{};
     gs_raw gr0{}, gr1{};
     const GatherRec *rec = nullptr;
     const unsigned slot_bytes = 16u * ((unsigned)lane >> 2);
@@ -1131,8 +1155,8 @@ __device__ __forceinline__ void sample1_body(const SampleArgs &a, const FusedArg
         gr0 = load_gs_rec(rec, 0, slot_bytes);
         gr1 = load_gs_rec(rec, 1, slot_bytes);
     } else {
-        ib0 = load_idx_block(a.rowidx + p0, a.vals + p0, 0, lane, glen, a.zero_row);
-        ib1 = load_idx_block(a.rowidx + p0, a.vals + p0, 64, lane, glen, a.zero_row);
+        ib0 = load_idx_block<WT>(a.rowidx + p0, a.vals + p0, 0, lane, glen, a.zero_row, WT ? a.sw + p0 : nullptr);
+        ib1 = load_idx_block<WT>(a.rowidx + p0, a.vals + p0, 64, lane, glen, a.zero_row, WT ? a.sw + p0 : nullptr);
     }
 
     // whole column in one item: its normals do not depend on the Gram -- draw them first so that
@@ -1153,8 +1177,8 @@ __device__ __forceinline__ void sample1_body(const SampleArgs &a, const FusedArg
         if constexpr (GS)
             gram_stream44<K>(rec, ng, a.other_items, a.zero_row, a.alpha, gr0, gr1, slot_bytes, acc, rr, lane);
         else
-            gram_chunk44<K>(a.rowidx + p0, a.vals + p0, glen, a.other_items, a.zero_row, a.mean_rating, a.alpha, ib0, ib1, acc, rr, lane,
-                            (ablate_bits(a) & 4u) ? 63 : -1);
+            gram_chunk44<K, WT>(a.rowidx + p0, a.vals + p0, glen, a.other_items, a.zero_row, a.mean_rating, a.alpha, ib0, ib1, acc, rr, lane,
+                                (ablate_bits(a) & 4u) ? 63 : -1, WT ? a.sw + p0 : nullptr);
         if (ablate_bits(a) & 1u) {
             double v = rr[0];
 #pragma unroll
@@ -1211,6 +1235,14 @@ __global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1i(SampleArgs a, Fus
 {
     __shared__ __attribute__((aligned(16))) double lds[Geo1<K>::LDS_WORDS];
     sample1_body<K, false>(a, f, lds);
+}
+
+// the index-block form with per-rating weights
+template <int K>
+__global__ __launch_bounds__(64, Geo1<K>::WPS) void k_sample1w(SampleArgs a, FusedArgs f)
+{
+    __shared__ __attribute__((aligned(16))) double lds[Geo1<K>::LDS_WORDS];
+    sample1_body<K, false, true>(a, f, lds);
 }
 
 // ---------------------------------------------------------------------------

@@ -218,6 +218,73 @@ __device__ __forceinline__ void gram_slab(const int32_t *__restrict__ rowidx, co
     }
 }
 
+// gram_slab with per-rating weights (k_sample_slabw / k_sample1sw): vals holds sqrt(w) (r - mean) and is read with
+// mean = 0; sqrt(w) of a rating (`sw`, the layout of vals) travels with its rhs weight through the row broadcast, and the gathered row is
+// multiplied by it where it is first used, in contract() -- the loads stay unconditional and nothing waits where a gather is issued.
+// A sibling, not a template parameter of gram_slab: the unweighted kernels compile to the instructions they compiled to before.
+// Same order of operations: weights that are all 1.0 give gram_slab's bits.
+template <int K>
+__device__ __forceinline__ void gram_slabw(const int32_t *__restrict__ rowidx, const double *__restrict__ vals, int len,
+                                          const double *__restrict__ other, const double *__restrict__ zero_row, double mean, double alpha,
+                                          double (&C)[GeoS<K>::NACC], double (&r)[K / 16], int lane, const double *__restrict__ sw)
+{
+    using G = GeoS<K>;
+    constexpr int NT = K / 16;
+    const int kq = lane >> 4, li = lane & 15;
+    if (len <= 0) return;
+    // (index blocks, row broadcasts, operand sets and guards: gram_slab's, comment for comment; what is new carries `s`)
+    const int slot = 4 * li + kq;
+    int ri = (slot < len) ? rowidx[slot] : -1;
+    double wv = (slot < len) ? (vals[slot] - mean) * alpha : 0.0;                // c++/sample.cpp:256
+    int ri_n = (64 + slot < len) ? rowidx[64 + slot] : -1;
+    double wv_n = (64 + slot < len) ? (vals[64 + slot] - mean) * alpha : 0.0;
+    double sv = (slot < len) ? sw[slot] : 0.0;
+    double sv_n = (64 + slot < len) ? sw[64 + slot] : 0.0;
+    auto gather = [&](auto stc, double (&yy)[NT], double &ww, double &ss) {
+        constexpr int ST = decltype(stc)::value;
+        constexpr bool nx = ST >= 16;
+        const int row = row_lane_i<(ST & 15)>(nx ? ri_n : ri);
+        ww = row_lane_d<(ST & 15)>(nx ? wv_n : wv);
+        ss = row_lane_d<(ST & 15)>(nx ? sv_n : sv);
+        const double *u = ((row >= 0) ? other + (size_t)row * K : zero_row) + li;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) yy[t] = u[16 * t];
+    };
+    auto contract = [&](const double (&y0)[NT], double ww, double ss) {
+        double yy[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) yy[t] = y0[t] * ss;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) r[t] = fma(yy[t], ww, r[t]);
+        rot44_contract<K>(yy, C);
+    };
+    constexpr int D = G::DEPTH;
+    static_assert(D >= 2 && 16 % D == 0, "the operand sets must rotate evenly through the 16 groups of an index block");
+    double y[D][NT], w[D], s[D];
+    slab_static_for<0, D - 1>([&](auto uc) { gather(uc, y[decltype(uc)::value], w[decltype(uc)::value], s[decltype(uc)::value]); });
+    for (int b0 = 0; b0 < len; b0 += 64) {
+        const int ngroups = (len - b0 >= 64) ? 16 : (len - b0 + 3) >> 2;         // groups of 4 ratings in this block
+        slab_static_for<0, 16>([&](auto gc) {
+            constexpr int g = decltype(gc)::value;
+            if (g < ngroups) {
+                gather(std::integral_constant<int, g + D - 1>{}, y[(g + D - 1) % D], w[(g + D - 1) % D], s[(g + D - 1) % D]);
+                contract(y[g % D], w[g % D], s[g % D]);
+            }
+        });
+        ri = ri_n; wv = wv_n;
+        const int q = b0 + 128 + slot;
+        ri_n = (q < len) ? rowidx[q] : -1;
+        wv_n = (q < len) ? (vals[q] - mean) * alpha : 0.0;
+        sv = sv_n;
+        sv_n = (q < len) ? sw[q] : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        r[t] += __shfl_xor(r[t], 16);
+        r[t] += __shfl_xor(r[t], 32);
+    }
+}
+
 // The accumulators of gram_slab() -> the slabs the factorisation works on, once per column (a chunked column: after its
 // partials were added; the map is a permutation, so it commutes with the sums).  Tile by tile through 2 KB of LDS (the
 // block-row buffer and the buffer of the inverted diagonal blocks, both idle until the factorisation, taken in turn): lane
@@ -321,7 +388,7 @@ __device__ __forceinline__ void slab_cholesky_solve(double (&A)[GeoS<K>::NREG], 
 }
 
 // one work item (column or chunk of a heavy column) by one wave; lds: GeoS<K>::LDS_WORDS doubles
-template <int K, typename T>
+template <int K, typename T, bool WT = false>
 __device__ __forceinline__ void slab_item(const SampleArgs &a, int w, double *lds, int lane)
 {
     using G = GeoS<K>;
@@ -350,7 +417,8 @@ __device__ __forceinline__ void slab_item(const SampleArgs &a, int w, double *ld
         for (int t = 0; t < NACC; ++t) C[t] = 0.0;
 #pragma unroll
         for (int t = 0; t < NT; ++t) rsum[t] = 0.0;
-        gram_slab<K>(a.rowidx + p0, a.vals + p0, len, a.other_items, a.zero_row, a.mean_rating, a.alpha, C, rsum, lane);
+        if constexpr (WT) gram_slabw<K>(a.rowidx + p0, a.vals + p0, len, a.other_items, a.zero_row, a.mean_rating, a.alpha, C, rsum, lane, a.sw + p0);
+        else gram_slab<K>(a.rowidx + p0, a.vals + p0, len, a.other_items, a.zero_row, a.mean_rating, a.alpha, C, rsum, lane);
         if (mc >= 0) {
             // chunk of a heavy column: park the accumulators; whichever chunk arrives last adds them up (chunk order)
             constexpr int PART = G::PART;
@@ -454,6 +522,14 @@ __global__ __launch_bounds__(64, GeoS<K>::WPS) void k_sample_slab(SampleArgs a)
     slab_item<K, T>(a, (int)blockIdx.x, lds, (int)threadIdx.x);
 }
 
+// the slab form with per-rating weights
+template <int K, typename T>
+__global__ __launch_bounds__(64, GeoS<K>::WPS) void k_sample_slabw(SampleArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double lds[GeoS<K>::LDS_WORDS];
+    slab_item<K, T, true>(a, (int)blockIdx.x, lds, (int)threadIdx.x);
+}
+
 // The same item body behind k_sample1's launch format (K <= 32, the fused stateful path: workgroup 0 = gate +
 // staging of this launch's parameters, the next f.nstat workgroups = column statistics of the previous side).
 template <int K>
@@ -472,6 +548,25 @@ __global__ __launch_bounds__(64, GeoS<K>::WPS) void k_sample1s(SampleArgs a, Fus
         return;
     }
     slab_item<K, double>(a, bid - f.nstat, lds, (int)threadIdx.x);
+}
+
+// ... with per-rating weights
+template <int K>
+__global__ __launch_bounds__(64, GeoS<K>::WPS) void k_sample1sw(SampleArgs a, FusedArgs f)
+{
+    __shared__ __attribute__((aligned(16))) double lds[GeoS<K>::LDS_WORDS];
+    int bid = blockIdx.x;
+    if (f.gate_host) {
+        if (bid == 0) { gate_stage_body(0, 1, f.gate_host, f.gate_want, f.src_host, f.dst, f.n, f.dflag, f.dval, a.tmo, a.wait_ticks); return; }
+        --bid;
+    }
+    if (bid < f.nstat) {
+        static_assert(!kColstatsRot<K> || GeoS<K>::LDS_WORDS >= 512, "the riders' images");
+        colstats_body<K>(bid, f.st_items, f.st_c0, f.st_c1, f.nstat, f.st_partials, f.st_fail, f.st_out, f.st_ticket, f.st_flag, f.st_seq,
+                         f.st_tmo, a.wait_ticks, lds);
+        return;
+    }
+    slab_item<K, double, true>(a, bid - f.nstat, lds, (int)threadIdx.x);
 }
 
 }  // namespace bpmf

@@ -121,13 +121,15 @@ __device__ __forceinline__ void diag16_factor_invert(double (&A)[4], double (&E)
 }
 
 // per-wave part of one work item: Gram of the wave's tiles, then (whole column / last chunk) the factorisation
-template <int K, int NW, int W, typename T = float>
+// WT: the weighted form (k_sample_wg2w, fp64 only): a.vals = sqrt(w) (r - mean), a.mean_rating = 0, a.sw = sqrt(w)
+template <int K, int NW, int W, typename T = float, bool WT = false>
 __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned char *smem, int tid)
 {
     using G = GeoF<K>;
     using X = WgTraits<T>;
     typedef typename X::acc_t acc_t;
     constexpr bool F32 = sizeof(T) == 4;
+    static_assert(!(WT && F32), "per-rating weights: fp64 only");
     constexpr int NT = G::NT, TPW = (G::NTRI + NW - 1) / NW;
     double *zs = reinterpret_cast<double *>(smem);
     T *R = reinterpret_cast<T *>(zs + K);
@@ -238,6 +240,14 @@ __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned 
         T wv = (lane < len) ? (T)((vals[lane] - a.mean_rating) * a.alpha) : (T)0;                 // c++/sample.cpp:256
         int ri_n = (64 + lane < len) ? rowidx[64 + lane] : -1;
         T wv_n = (64 + lane < len) ? (T)((vals[64 + lane] - a.mean_rating) * a.alpha) : (T)0;
+        // (weighted: sqrt(w) of the ratings beside their row ids; the wave that gathers a row multiplies it by its sqrt(w) on the way
+        //  into LDS, once per workgroup -- every wave then reads sqrt(w) u as its operand and wave 0 adds sqrt(w) u times sqrt(w) (r - mean) alpha)
+        T sv = 0, sv_n = 0;
+        if constexpr (WT) {
+            const double *swp = a.sw + p0;
+            sv = (lane < len) ? (T)swp[lane] : (T)0;
+            sv_n = (64 + lane < len) ? (T)swp[64 + lane] : (T)0;
+        }
         const int rowmask = (ablate_bits(a) & 4u) ? 63 : -1;                 // (profiling switch: gather from 64 hot rows only)
         const bool no_mfma = (ablate_bits(a) & 8u) != 0;                     // (profiling switch: operands are loaded and summed, no MFMA)
         constexpr int SPW = 4 / NW;                                    // k-steps of a group gathered by one wave
@@ -246,6 +256,9 @@ __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned 
         constexpr int SBUF = 16 * K;                                   // elements of one staging buffer: 16 ratings x K
         static_assert(2 * SBUF <= G::RWORDS, "the staging buffers live where R will");
         T pre[SPW][NT];
+        T psw[SPW];
+#pragma unroll
+        for (int u = 0; u < SPW; ++u) psw[u] = 0;
         auto fetch = [&](int gg) {                                     // gg = 1 .. 3: group of this index block, 4: group 0 of the next
             const bool nx = gg >= 4;
 #pragma unroll
@@ -253,6 +266,7 @@ __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned 
                 const int st = W + u * NW;
                 const int src = ((gg & 3) * 4 + st) * 4 + kq;
                 const int row = __shfl(nx ? ri_n : ri, src);
+                if constexpr (WT) psw[u] = __shfl(nx ? sv_n : sv, src);
                 const T *up = ((row >= 0) ? other + (size_t)(row & rowmask) * K : reinterpret_cast<const T *>(a.zero_row)) + li;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) pre[u][t] = up[16 * t];
@@ -266,7 +280,7 @@ __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned 
                 for (int v = 0; v < VPR; ++v) {
                     tvec x;
 #pragma unroll
-                    for (int e = 0; e < EPV; ++e) x[e] = pre[u][v * EPV + e];
+                    for (int e = 0; e < EPV; ++e) x[e] = WT ? pre[u][v * EPV + e] * psw[u] : pre[u][v * EPV + e];
                     reinterpret_cast<tvec *>(R + buf * SBUF)[(st * VPR + v) * 64 + lane] = x;
                 }
             }
@@ -313,6 +327,7 @@ __device__ __forceinline__ void wg2_column(const SampleArgs &a, int w, unsigned 
                 const int q = (g >> 2) * 64 + 128 + lane;
                 ri_n = (q < len) ? rowidx[q] : -1;
                 wv_n = (q < len) ? (T)((vals[q] - a.mean_rating) * a.alpha) : (T)0;
+                if constexpr (WT) { sv = sv_n; sv_n = (q < len) ? (T)a.sw[p0 + q] : (T)0; }
             }
             __syncthreads();
         }
@@ -687,6 +702,35 @@ __global__ __launch_bounds__(64 * NW, 2) void k_sample_wg2(SampleArgs a, StatRid
         case 1: wg2_column<K, 4, 1, T>(a, w, smem, tid); break;
         case 2: wg2_column<K, 4, 2, T>(a, w, smem, tid); break;
         default: wg2_column<K, 4, 3, T>(a, w, smem, tid); break;
+        }
+    }
+    if (kProfiling && a.stamps && tid == 0) {                                        // profiling: sum of the items' lifetimes (wave 0), their number, first start / last end
+        atomicAdd(&a.stamps[128 + 0], wall_clock64() - t_begin);
+        atomicAdd(&a.stamps[128 + 1], 1ull);
+        atomicMin(&a.stamps[128 + 2], t_begin);
+        atomicMax(&a.stamps[128 + 3], wall_clock64());
+    }
+}
+
+// the same kernel with per-rating weights (instantiated in a unit of its own, k128_f64w.hip)
+template <int K, int NW, typename T = float>
+__global__ __launch_bounds__(64 * NW, 2) void k_sample_wg2w(SampleArgs a, StatRiders r)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[GeoW2<K>::template lds_bytes<T>()];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    // column statistics as rider workgroups (colstats_f32_rider): the previous launch's side at the head of the grid
+    if ((int)blockIdx.x < r.nblocks) { colstats_f32_rider<K, NW, T>(r, (int)blockIdx.x, tid); return; }
+    const int w = (int)blockIdx.x - r.nblocks;
+    const unsigned long long t_begin = (kProfiling && a.stamps) ? wall_clock64() : 0ull;
+    if constexpr (NW == 2) {
+        if (wave == 0) wg2_column<K, 2, 0, T, true>(a, w, smem, tid);
+        else wg2_column<K, 2, 1, T, true>(a, w, smem, tid);
+    } else {
+        switch (wave) {
+        case 0: wg2_column<K, 4, 0, T, true>(a, w, smem, tid); break;
+        case 1: wg2_column<K, 4, 1, T, true>(a, w, smem, tid); break;
+        case 2: wg2_column<K, 4, 2, T, true>(a, w, smem, tid); break;
+        default: wg2_column<K, 4, 3, T, true>(a, w, smem, tid); break;
         }
     }
     if (kProfiling && a.stamps && tid == 0) {                                        // profiling: sum of the items' lifetimes (wave 0), their number, first start / last end

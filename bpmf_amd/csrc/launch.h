@@ -98,11 +98,19 @@ void k64_pf_prepare(int grid, hipStream_t st, hipEvent_t e0, const double *S0t, 
 
 // slab form (kernels_slab.h): K = 64 fp64, one wave per work item
 void k64_slab(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a);
+// the weighted forms (a.sw) sit in units of their own: k64_slabw.hip, k128_f64w.hip, kw8.hip .. kw32.hip (launch_w.h)
+void k64_slabw(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a);
+void k64_1sw(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a, const bpmf::FusedArgs &f);   // k_sample1sw<64>: gate + riders + items
+template <int K>
+void sample1w(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a, const bpmf::FusedArgs &f);  // K <= 32: k_sample1w<K>
+template <int K>
+void sample4w(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a);                             // K <= 32: k_sample4w<K>
 // K = 128 fp32: workgroup of two waves per item (kernels_wg2.h)
 // (r: column statistics of another side as rider workgroups at the head of the grid, or r.nblocks == 0)
 void k128_wg2(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a, const bpmf::StatRiders &r);
 // K = 128 fp64 (num_latent 65 .. 128 in the reference's arithmetic): the same form with fp64 factors, four waves per item (k128_f64.hip)
 void k128_wg2_f64(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a, const bpmf::StatRiders &r);
+void k128_wg2w_f64(int grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const bpmf::SampleArgs &a, const bpmf::StatRiders &r);
 
 // BPMF_REDUCE formulation (kernels_reduce.h, kreduce.hip): fp64, K = 8 .. 64
 int reduce_part_words(int K);                  // doubles per column of a side's `prec` array (0: K not supported)

@@ -30,6 +30,15 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     // position (capi_censor.hip); side with features: the residuals r - m_c . y_r (capi_link.hip)
     const double *vals = self->probit ? self->probit->z.get() : self->censor ? self->censor->z.get() : self->link ? self->link->r.get() : self->d_vals;
     a.rowidx = self->d_rowidx; a.vals = vals;
+    // side with per-rating weights (capi_weights.hip): the weighted form of the side's family reads
+    // zw = sqrt(w) (r - mean) as its values with mean 0 and multiplies every gathered row by sw = sqrt(w)
+    const bool wt = self->weights != nullptr;
+    if (wt) {
+        if constexpr (F32) return fail(BPMF_HIP_EINVAL, "per-rating weights: not on an fp32 context");
+        if (self->probit || self->censor || self->link || self->d_prop || self->reduce_on)
+            return fail(BPMF_HIP_EINVAL, "per-rating weights: not together with probit, censored ratings, features, propagated priors or BPMF_REDUCE");
+        a.vals = self->weights->zw.get(); a.sw = self->weights->sw.get(); a.mean_rating = 0.0;
+    }
     // (item window: the whole list, or the items of one part of the columns -- bpmf_hip_side_set_overlap)
     const int w0 = self->item_n >= 0 ? self->item_off : 0, nwork = self->item_n >= 0 ? self->item_n : self->nwork;
     a.wi_col = self->d_wi_col + w0; a.wi_p0 = self->d_wi_p0 + w0; a.wi_len = self->d_wi_len + w0; a.wi_mc = self->d_wi_mc + w0; a.wi_chunk = self->d_wi_chunk + w0;
@@ -46,17 +55,20 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
         if (nwork > 0) k128_wg2(nwork, st, ev_start, ev_stop, a, rr);
         return 0;
     } else if constexpr (K == 128) {                                 // fp64 factors, workgroup of four waves per item (kernels_wg2.h, T = double)
-        if (nwork > 0) k128_wg2_f64(nwork, st, ev_start, ev_stop, a, rr);
+        if (nwork > 0 && wt) k128_wg2w_f64(nwork, st, ev_start, ev_stop, a, rr);
+        else if (nwork > 0) k128_wg2_f64(nwork, st, ev_start, ev_stop, a, rr);
         return 0;
     } else {
     if constexpr (K <= 32) {
         if (nwork > 0 && self->mode == 3) {                          // four columns per wave (k_sample4)
-            BPMF_LAUNCH(k_sample4<K>, dim3((nwork + 3) / 4), dim3(64), st, ev_start, ev_stop, a);
+            if (wt) sample4w<K>((nwork + 3) / 4, st, ev_start, ev_stop, a);
+            else BPMF_LAUNCH(k_sample4<K>, dim3((nwork + 3) / 4), dim3(64), st, ev_start, ev_stop, a);
             return 0;
         }
     }
     if constexpr (K == 64) {
-        if (self->lr_n > 0 && !self->d_prop && !c->diag_only && !(c->ablate & 3u)) {
+        // (a weighted side: every column in the slab form -- the product form has no weighted variant)
+        if (self->lr_n > 0 && !self->d_prop && !c->diag_only && !(c->ablate & 3u) && !wt) {
             // light columns (<= 16 ratings): product form over the shared factor of LambdaF (k_sample_pf); the others in the slab form
             if (self->hv_nwork > 0) {
                 a.wi_col = self->d_hv_col; a.wi_p0 = self->d_hv_p0; a.wi_len = self->d_hv_len; a.wi_mc = self->d_hv_mc;
@@ -97,7 +109,10 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
             const FusedArgs &f = self->cur_fused;                    // (all zero outside the fused stateful path)
             if (f.gate_host || f.nstat) {                            // gate workgroup + statistics riders + items in one launch
                 const dim3 grid((unsigned)(nwork + (f.gate_host ? 1 : 0) + f.nstat));
-                BPMF_LAUNCH(k_sample1s<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
+                if (wt) k64_1sw((int)grid.x, st, ev_start, ev_stop, a, f);
+                else BPMF_LAUNCH(k_sample1s<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
+            } else if (wt) {
+                k64_slabw(nwork, st, ev_start, ev_stop, a);
             } else {
                 k64_slab(nwork, st, ev_start, ev_stop, a);
             }
@@ -107,7 +122,9 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     if (nwork > 0) {                                                 // K <= 32: one work item per single-wave workgroup (k_sample1)
         const FusedArgs &f = self->cur_fused;                        // (all zero outside the fused stateful path)
         const dim3 grid((unsigned)(nwork + (f.gate_host ? 1 : 0) + f.nstat));
-        if (uses_gather_stream(self) && vals == self->d_vals) {      // the Gram reads the side's gather stream (build_schedule)
+        if (wt) {                                                    // weighted index blocks (never the gather stream)
+            sample1w<K>((int)grid.x, st, ev_start, ev_stop, a, f);
+        } else if (uses_gather_stream(self) && vals == self->d_vals) {      // the Gram reads the side's gather stream (build_schedule)
             a.gs_rec = self->d_gs_rec; a.gs_g0 = self->d_gs_g0 + w0; a.gs_ng = self->d_gs_ng + w0;
             BPMF_LAUNCH(k_sample1<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
         } else {                                                     // other values than the side's own ratings: index blocks

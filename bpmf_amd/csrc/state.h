@@ -213,6 +213,7 @@ struct bpmf_hip_side {
     // the add-ons (ext_state.h), each NULL until its entry point attaches it; released in bpmf_hip_side_destroy
     std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
     std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
+    std::unique_ptr<bpmf_weights> weights; // per-rating precision weights (bpmf_hip_side_set_weights)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
     std::unique_ptr<bpmf_newrows> newrows; // rows unseen in training: their features and projected samples (bpmf_hip_side_newrows_set)
@@ -339,10 +340,11 @@ struct bpmf_hip_side {
 
 // Does a k_sample1 launch of the side read its gather stream?  The stream holds r - mean_rating of the side's OWN ratings:
 // a probit, censored or side-information launch reads other values in their place and keeps the index-block form
-// (k_sample1i), and so does the hot-row profiling switch (BPMF_HIP_ABLATE & 4), which rewrites the row ids.
+// (k_sample1i), and so does the hot-row profiling switch (BPMF_HIP_ABLATE & 4), which rewrites the row ids.  A weighted side
+// never reads it either: a record has no room for sqrt(w) (k_sample1w, the weighted index-block form).
 inline bool uses_gather_stream(const bpmf_hip_side *s)
 {
-    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->censor && !s->link && !(s->ctx->ablate & 4u);
+    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->censor && !s->link && !s->weights && !(s->ctx->ablate & 4u);
 }
 
 struct bpmf_hip_test {

@@ -542,6 +542,34 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_side_censored_latent(side.handle, _ptr(z)))
         return z
 
+    # -- per-rating precision weights ---------------------------------------------
+    def set_weights(self, side, w):
+        """Gives every rating of `side` a precision weight: w holds one float64 per rating in the side's order, finite and > 0
+        (bpmf_amd.rating_weights builds them from a sparse matrix); rating p is then observed with the precision alpha w[p].  The
+        side's sampler launches run the weighted form of their kernel from now on (include/bpmf_hip.h).  A
+        second call replaces the weights.  fp64 contexts, one GPU; not with probit, censored ratings, features, propagated priors
+        or BPMF_REDUCE."""
+        w = np.ascontiguousarray(w, np.float64)
+        if w.ndim != 1:
+            raise ValueError("set_weights: the weights must be one array, one weight per rating of the side")
+        if len(w) != side.nnz:
+            raise ValueError("set_weights: %d weights for a side of %d ratings" % (len(w), side.nnz))
+        if len(w) == 0:
+            w = np.ones(1)
+        _lib.check(self.lib.bpmf_hip_side_set_weights(side.handle, _ptr(w)))
+
+    def weights_get(self, side):
+        """(sw, zw) of a side with weights as the device holds them: sqrt(w) and sqrt(w) (r - mean_rating), in the ratings' order."""
+        sw, zw = np.empty(side.nnz), np.empty(side.nnz)
+        _lib.check(self.lib.bpmf_hip_side_weights_get(side.handle, _ptr(sw), _ptr(zw)))
+        return sw, zw
+
+    def weights_count(self, side):
+        """(ratings whose weight is not 1, the smallest weight, the largest weight) of a side with weights."""
+        n, lo, hi = C.c_int64(), C.c_double(), C.c_double()
+        _lib.check(self.lib.bpmf_hip_side_weights_count(side.handle, C.byref(n), C.byref(lo), C.byref(hi)))
+        return n.value, lo.value, hi.value
+
     # -- side information ---------------------------------------------------------
     def set_features(self, side, F, lambda_beta=5.0, tag=3):
         """Gives `side` the feature matrix F [ncols, D] (one row per column of the side), a link matrix beta (D x K, 0) and the

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import engine as _engine
 from .censor import censor_flags, transpose_csc
+from .weights import rating_weights
 
 
 class HyperParams:
@@ -187,7 +188,7 @@ class Sys:
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
-          new_row_features=None, new_col_features=None, topn_score=None, foldin=False):
+          new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -268,7 +269,26 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     and no features, their factors: the sample rings of both sides and, per side without features, the
     hyper-parameters (alpha, mu, Lambda) every post-burn-in iteration ran with (engine.hyper_add, where samples_add sits; nsims -
     burnin slots; with noise="adaptive" the iteration's own alpha).  The engine must stay open for fold_in.  Needs nsims > burnin;
-    refused with probit=True and when both sides have features.  res["foldin"] = True.  False (the default): nothing changes."""
+    refused with probit=True and when both sides have features.  res["foldin"] = True.  False (the default): nothing changes.
+
+    weights=W: a precision weight per training rating, r ~ N(mean + u . v, 1 / (alpha w)).  W is a CSC triple
+    of M's shape: the rating of a listed cell takes that entry (finite, > 0) as its weight, every other rating the weight 1
+    (bpmf_amd.rating_weights; every entry must be a stored cell of M).  Both sides get their weights once (engine.set_weights;
+    those of Mt from W transposed) and run the weighted form of their sampler: nothing is enqueued per iteration, the pipelined
+    loop does not drain.  With or without topn, topn_score, foldin (a folded-in row's own ratings have weight 1); the test matrix
+    is unweighted.  probit=True, censored, noise="adaptive", features and an fp32 engine are refused with weights.  res["weights"]
+    = (cells whose weight is not 1, smallest weight, largest weight).  None (the default): nothing changes."""
+    if weights is not None:                          # (refused before the engine is used)
+        if probit:
+            raise ValueError("weights does not go together with probit=True (the latent scores have unit variance)")
+        if censored is not None:
+            raise ValueError("weights does not go together with censored (the latent draw would need the weight of its cell)")
+        if noise == "adaptive":
+            raise ValueError("weights does not go together with noise='adaptive' (alpha | r would need the weighted residuals)")
+        if row_features is not None or col_features is not None:
+            raise ValueError("weights does not go together with row_features / col_features (the link matrix would need the weighted residuals)")
+        if getattr(engine, "dtype", "f64") == "f32":
+            raise ValueError("weights needs an fp64 engine")
     if foldin:                                       # (refused before the engine is used)
         if probit:
             raise ValueError("foldin=True does not go together with probit=True (labels would need a latent iteration of their own)")
@@ -360,6 +380,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         if not (float(alpha) > 0 and math.isfinite(float(alpha))):
             raise ValueError("censored needs a finite alpha > 0")
         cflags = (censor_flags(M, censored), censor_flags(Mt, transpose_csc(censored, nusers)))
+    if weights is not None:                          # (checked before a side is created)
+        wts = (rating_weights(M, weights), rating_weights(Mt, transpose_csc(weights, nusers)))
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
     movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit else None)
     users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit else None)
@@ -369,6 +391,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if censored is not None:
         engine.set_censored(movies.side, cflags[0], 5)
         engine.set_censored(users.side, cflags[1], 6)
+    if weights is not None:
+        engine.set_weights(movies.side, wts[0])
+        engine.set_weights(users.side, wts[1])
     if linked:
         if col_features is not None:
             engine.set_features(movies.side, col_features, lambda_beta, 3)
@@ -517,6 +542,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         res["brier"] = float(np.mean((res["prob"] - label) ** 2)) if have else float("nan")
     if censored is not None:
         res["censored"] = engine.censored_count(movies.side)
+    if weights is not None:
+        res["weights"] = engine.weights_count(movies.side)
     if linked:
         res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
         res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None

@@ -476,6 +476,34 @@ BPMF_API int bpmf_hip_side_censored_count(bpmf_hip_side *side, int64_t *right, i
  * exact positions, the newest draws at the censored ones (waits for the work in flight). */
 BPMF_API int bpmf_hip_side_censored_latent(bpmf_hip_side *side, double *z_host);
 
+/* ---- per-rating precision weights ---------------------------------------------------
+ * Every rating p of a side may carry a weight w_p > 0: r_p ~ N(mean_rating + x_c . y_r, 1 / (alpha w_p)) -- assays of different
+ * quality, a mean of w_p replicates, a confidence per cell.  The conditional of column c becomes
+ *     Lambda* = Lambda + alpha sum_p w_p y_r y_r^T,   b = Lambda mu + alpha sum_p w_p (r_p - mean_rating) y_r,
+ * and since w y y^T = (sqrt(w) y)(sqrt(w) y)^T the samplers need one change: the weighted form of a kernel reads
+ * zw_p = sqrt(w_p) (r_p - mean_rating) as its values with mean 0 and multiplies every gathered factor row by sw_p = sqrt(w_p)
+ * before it enters the right-hand side and the Gram.  DESIGN.md section 20 has the forms and what they cost.
+ *
+ * bpmf_hip_side_set_weights takes nnz weights in the order of the side's ratings, waits for the side's work in flight and stores sw
+ * and zw on the device: bitwise the IEEE doubles sqrt(w) and sqrt(w) * (r - mean_rating) (formed on the host).  Every sampler launch
+ * of the side (bpmf_hip_sys_sample, bpmf_hip_sample_side[_launch]) then runs the weighted form -- its kernel's name with a `w`
+ * (bpmf_hip_side_kernel_name: k_sample1w<K>, k_sample4w<K>, k_sample_slabw<64>, k_sample1sw<64>, k_sample_wg2w<128,4,double>);
+ * at K <= 32 never the gather stream, at K = 64 every column in the slab form (no product form).  Nothing is enqueued per
+ * iteration and nothing waits on the host.  Weights that are all 1 give the unweighted side's factors and statistics bit for bit.
+ * A second call replaces the weights (the hook for weights that are redrawn per iteration); the side's ratings are never written.
+ * Evaluation, the sample rings, top-N, new rows and fold-in work on top unchanged (the test matrix and a folded-in row's own
+ * ratings have weight 1).
+ * BPMF_HIP_EINVAL: a NULL argument, a weight that is not finite and > 0 (the first one is named by its position), an fp32 context,
+ * a probit side, a censored side, a side with features, propagated priors, the BPMF_REDUCE formulation, a context with a
+ * communicator or a sharded side.  In turn bpmf_hip_side_set_probit, bpmf_hip_side_set_censored,
+ * bpmf_hip_side_set_features[_sparse], bpmf_hip_side_set_prop_posterior, bpmf_hip_sys_set_reduce and bpmf_hip_train_sse refuse a
+ * side with weights. */
+BPMF_API int bpmf_hip_side_set_weights(bpmf_hip_side *side, const double *w_host);
+/* sw and zw as the device holds them, nnz doubles each in the order of the side's ratings; either pointer may be NULL. */
+BPMF_API int bpmf_hip_side_weights_get(bpmf_hip_side *side, double *sw_host, double *zw_host);
+/* The number of ratings whose weight is not 1, the smallest and the largest weight of a side with weights. */
+BPMF_API int bpmf_hip_side_weights_count(bpmf_hip_side *side, int64_t *nweighted, double *wmin, double *wmax);
+
 /* ---- side information: row / column features linked to the factor priors -----------
  * A side with N columns may carry a dense feature matrix F (N x D, fp64), a link matrix beta (D x K) and a fixed
  * lambda_beta > 0:

@@ -1,0 +1,137 @@
+"""Per-rating precision weights (gibbs(..., weights=W)): what the weighted forms of the samplers cost.
+
+    python tools/weights_bench.py iter [ml1m chembl k128] [--secs 2] [--rounds 3]
+        ms per Gibbs iteration of the pipelined loop (bench.py's), in interleaved windows of >= secs each, of
+          plain      the unweighted sides in their default forms (K <= 32: the gather stream; K = 64: product form + slab)
+          plain_idx  the unweighted sides with BPMF_HIP_GATHER_STREAM=0 and BPMF_HIP_PF=0: the index-block form / every column in the
+                     slab form -- the forms a weighted side runs, without the weights
+          weighted   every training rating with a seeded weight Gamma(2, 0.5)
+        plain_idx - plain is what losing the stream / the product form costs, weighted - plain_idx what the sqrt(w) loads and the
+        multiplies cost.  k128 = the ML-1M shape at K = 128 fp64 (neither a stream nor a product form: plain_idx = plain).
+    python tools/weights_bench.py resources
+        registers, LDS and resident workgroups of every weighted form beside its unweighted form (bpmf_hip_side_kernel_resources)
+
+One JSON line per measurement.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import bpmf_amd                                            # noqa: E402
+from bpmf_amd import synth                                 # noqa: E402
+
+MODES = ("plain", "plain_idx", "weighted")
+IDX_ENV = {"BPMF_HIP_GATHER_STREAM": "0", "BPMF_HIP_PF": "0"}
+
+
+def shape(name):
+    if name in ("ml1m", "k128"):
+        M, Mt, T, Tt, nu, nm = synth.ml1m_shaped(seed=42)
+        return dict(K=128 if name == "k128" else 32, M=M, Mt=Mt, T=T, Tt=Tt, nu=nu, nm=nm)
+    M, Mt, T, Tt, nu, nm = synth.ratings(483500, 5775, 1_023_952, seed=42, real_valued=True)
+    return dict(K=64, M=M, Mt=Mt, T=T, Tt=Tt, nu=nu, nm=nm)
+
+
+class _env:
+    def __init__(self, kv):
+        self.kv, self.old = kv, {}
+
+    def __enter__(self):
+        for k, v in self.kv.items():
+            self.old[k] = os.environ.get(k)
+            os.environ[k] = v
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def run(d, mode, W, nsims):
+    """-> (gibbs result, wall seconds, the kernels of the two sides)"""
+    with _env(IDX_ENV if mode == "plain_idx" else {}):
+        eng = bpmf_amd.HipEngine(d["K"])
+        try:
+            t0 = time.perf_counter()
+            res = bpmf_amd.gibbs(eng, d["M"], d["Mt"], d["T"], d["nu"], d["nm"], nsims=nsims, burnin=10, Tt=d["Tt"], pipelined=True,
+                                 weights=W if mode == "weighted" else None)
+            wall = time.perf_counter() - t0
+            names = (eng.kernel_name(res["movies"].side), eng.kernel_name(res["users"].side))
+        finally:
+            eng.close()
+    return res, wall, names
+
+
+def iters(names, secs, rounds):
+    for name in names:
+        d = shape(name)
+        K = d["K"]
+        M = d["M"]
+        W = (M[0], M[1], np.random.default_rng(7).gamma(2.0, 0.5, len(M[2])))
+        probe, kernels = {}, {}
+        for mode in MODES:                                   # size the windows
+            res, _, kernels[mode] = run(d, mode, W, 40)
+            probe[mode] = statistics.median(res["secs"][5:])
+        nsims = max(50, int(secs / min(probe.values())))
+        per = {m: [] for m in MODES}
+        for r in range(rounds):
+            for mode in (MODES if r % 2 == 0 else MODES[::-1]):
+                res, wall, _ = run(d, mode, W, nsims)
+                ms = 1e3 * sum(res["secs"][10:]) / (nsims - 10)
+                per[mode].append(ms)
+                print(json.dumps(dict(mode="iter", shape=name, K=K, form=mode, round=r, nsims=nsims, window_s=round(wall, 2),
+                                      ms_per_iter=round(ms, 4))), flush=True)
+        med = {m: statistics.median(per[m]) for m in MODES}
+        print(json.dumps(dict(mode="iter_summary", shape=name, K=K, kernels={m: kernels[m] for m in MODES},
+                              **{m + "_ms": round(med[m], 4) for m in MODES},
+                              **{m + "_spread_ms": round(max(per[m]) - min(per[m]), 4) for m in MODES},
+                              lost_forms_ms=round(med["plain_idx"] - med["plain"], 4), multiply_ms=round(med["weighted"] - med["plain_idx"], 4),
+                              weighted_over_plain=round(med["weighted"] / med["plain"], 3))), flush=True)
+
+
+def resources():
+    """one small side per family: the forms do not depend on the data"""
+    rng = np.random.default_rng(3)
+    counts = np.concatenate([np.full(40, 20), np.full(8, 300)])
+    colptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    nrows = 400
+    rowidx = np.concatenate([np.sort(rng.choice(nrows, size=c, replace=False)) for c in counts]).astype(np.int32)
+    vals = rng.integers(1, 6, len(rowidx)).astype(np.float64)
+    for K, env in ((8, {}), (8, {"BPMF_HIP_MODE": "3"}), (16, {}), (16, {"BPMF_HIP_MODE": "3"}), (32, {}), (32, {"BPMF_HIP_MODE": "3"}),
+                   (64, {}), (128, {})):
+        with _env(dict(env, **IDX_ENV)):
+            eng = bpmf_amd.HipEngine(K)
+            try:
+                side = eng.side_create(len(counts), nrows, colptr, rowidx, vals, 3.0)
+                plain = eng.kernel_resources(side)
+                eng.set_weights(side, np.ones(len(vals)))
+                weighted = eng.kernel_resources(side)
+                print(json.dumps(dict(mode="resources", K=K, env=env, plain_name=eng.kernel_name(side).replace("w<", "<"),
+                                      weighted_name=eng.kernel_name(side), plain=plain, weighted=weighted)), flush=True)
+            finally:
+                eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("iter", "resources"))
+    ap.add_argument("shapes", nargs="*")
+    ap.add_argument("--secs", type=float, default=2.0)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    if a.mode == "iter":
+        iters(a.shapes or ["ml1m", "chembl", "k128"], a.secs, a.rounds)
+    else:
+        resources()
+
+
+if __name__ == "__main__":
+    main()
