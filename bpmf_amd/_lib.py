@@ -99,6 +99,9 @@ _SIGNATURES = {
     "bpmf_hip_side_set_weights": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_weights_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_weights_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_robust": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),
+    "bpmf_hip_side_robust_add": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_robust_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "bpmf_hip_side_set_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint]),
     "bpmf_hip_link_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     "bpmf_hip_side_link_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

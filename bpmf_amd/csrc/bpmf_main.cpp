@@ -49,6 +49,10 @@
 // training cells it lists: such a rating is observed with the precision alpha w, every other one with alpha.
 // Both sides get their weights once (bpmf_hip_side_set_weights) and run the weighted form of their sampler; one more header line
 // counts the weighted cells, everything else keeps its format.
+// --robust NU (one GPU, no -g): Student-t noise with NU >= 1 degrees of freedom instead of Gaussian noise: both
+// sides redraw a precision weight per rating on the device ahead of every sampler launch (bpmf_hip_side_set_robust); one more header
+// line names NU, -o DIR also writes DIR/robust-weights.sdm (the posterior-mean weight of every training cell), everything else keeps
+// its format.
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -86,7 +90,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--weights FILE] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--weights FILE] [--robust NU] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -158,6 +162,11 @@ void usage()
               << "              .mtx; optional .gz) whose entries w > 0 weight the ratings of their cells -- precision alpha w instead of alpha;\n"
               << "              every entry must be a cell of the training matrix, every other rating has weight 1 (one GPU, no -g; not with\n"
               << "              --probit, --censored, --noise adaptive, --row-features / --col-features, -m / -l, --fp32 or BPMF_REDUCE=1)\n"
+              << "  [--robust NU]: Student-t noise with NU >= 1 degrees of freedom (1: Cauchy) instead of Gaussian noise, scale 1 / sqrt(alpha): a\n"
+              << "              precision weight per training rating is redrawn on the device in every half-iteration, so that a gross outlier\n"
+              << "              stops dragging its factors; -o DIR also gets robust-weights.sdm, the posterior-mean weight of every training\n"
+              << "              cell (one GPU, no -g; not with --weights, --probit, --censored, --noise adaptive, --row-features /\n"
+              << "              --col-features, -m / -l, --fp32, --topn-score prob|ei or BPMF_REDUCE=1)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -310,6 +319,8 @@ struct Job {
     bool weighted = false;                                           // --weights FILE
     std::vector<double> w_m, w_u;                                    // the weight of every rating of M / Mt
     int64_t w_count = 0; double w_min = 1.0, w_max = 1.0;            // listed cells whose weight is not 1; the smallest / largest weight
+    bool robust = false; double robust_nu = 0.0;                     // --robust NU
+    std::vector<double> robust_w;                                    // the posterior-mean weight of every rating of M
     std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
     double auc = NAN, brier = NAN;
     Dense feat_u, feat_m;                                            // --row-features / --col-features (N x D, column-major; empty: none)
@@ -386,6 +397,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.weighted) {
         check(bpmf_hip_side_set_weights(movies, J.w_m.data()));
         check(bpmf_hip_side_set_weights(users, J.w_u.data()));
+    }
+    if (J.robust) {                                          // (streams: tag 9 = movies, 10 = users; 7 and 8 are the fold-in's)
+        check(bpmf_hip_side_set_robust(movies, J.robust_nu, 9));
+        check(bpmf_hip_side_set_robust(users, J.robust_nu, 10));
     }
     const bool linked = J.has_feat_u() || J.has_feat_m();   // (streams: tag 3 = movies, 4 = users)
     auto set_sparse = [&](bpmf_hip_side *side, const Csc &Fr, int64_t D, unsigned tag) {       // Fr: F by rows (column = item)
@@ -486,6 +501,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         os << "censored: " << J.cens_right << " lower bounds, " << J.cens_left << " upper bounds of " << J.M.nnz() << " training ratings" << std::endl;
     if (J.weighted)
         os << "weights: " << J.w_count << " of " << J.M.nnz() << " training ratings weighted, min " << J.w_min << ", max " << J.w_max << std::endl;
+    if (J.robust) os << "robust: Student-t noise, nu = " << J.robust_nu << std::endl;
     if (linked) {
         os << "side information:";
         if (J.sfeat_u_d > 0) os << " row features sparse D = " << J.sfeat_u_d << " nnz = " << J.sfeat_u.nnz() << ",";
@@ -596,6 +612,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
 
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
+        if (J.robust && aggregate && iter >= burnin) check(bpmf_hip_side_robust_add(movies));
         if (ring_u && iter >= burnin) check(bpmf_hip_side_samples_add(users));
         if (ring_m && iter >= burnin) check(bpmf_hip_side_samples_add(movies));
         if (J.fold_u.n > 0 && iter >= burnin) check(bpmf_hip_side_hyper_add(users, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
@@ -654,6 +671,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_side_aggr_finalize(users, nsamples, J.u_mu.data() + (size_t)K * u0, J.u_lambda.data() + (size_t)K * K * u0));
             check(bpmf_hip_side_aggr_finalize(movies, nsamples, J.m_mu.data() + (size_t)K * m0, J.m_lambda.data() + (size_t)K * K * m0));
         }
+    }
+    if (J.robust && aggregate && nsims > burnin) {                   // one rank (main refuses -g)
+        J.robust_w.resize((size_t)std::max<int64_t>(J.M.nnz(), 1));
+        check(bpmf_hip_side_robust_get(movies, J.robust_w.data(), nullptr, nullptr));
+        J.robust_w.resize((size_t)J.M.nnz());
     }
     if (linked && nsims > burnin) {                                  // one rank (main refuses -g)
         if (J.has_feat_u()) { J.beta_u.resize((size_t)(J.sfeat_u_d > 0 ? J.sfeat_u_d : J.feat_u.ncols) * K); check(bpmf_hip_side_link_mean(users, J.beta_u.data(), nullptr)); }
@@ -766,13 +788,13 @@ int main(int argc, char *argv[])
                                               {"link-tol", required_argument, nullptr, 1011}, {"link-max-iter", required_argument, nullptr, 1012},
                                               {"lambda-beta-prior", required_argument, nullptr, 1013},
                                               {"censored", required_argument, nullptr, 1014},
-                                              {"weights", required_argument, nullptr, 1030},
+                                              {"weights", required_argument, nullptr, 1030}, {"robust", required_argument, nullptr, 1031},
                                               {"new-row-features", required_argument, nullptr, 1015}, {"new-col-features", required_argument, nullptr, 1016},
                                               {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
                                               {"topn-threshold", required_argument, nullptr, 1019},
                                               {"fold-in-rows", required_argument, nullptr, 1020}, {"fold-in-cols", required_argument, nullptr, 1021},
                                               {nullptr, 0, nullptr, 0}};
-    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
+    std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
     bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
@@ -795,6 +817,7 @@ int main(int argc, char *argv[])
         case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
         case 1014: censored_file = optarg; J.censored = true; break;
         case 1030: weights_file = optarg; J.weighted = true; break;
+        case 1031: robust_nu = optarg; J.robust = true; break;
         case 1015: new_row_features = optarg; break;
         case 1016: new_col_features = optarg; break;
         case 1017: topn_score = optarg; break;
@@ -985,6 +1008,25 @@ int main(int argc, char *argv[])
         if (fp32) die("--weights does not go together with --fp32 (the weighted samplers are fp64)");
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--weights does not go together with BPMF_REDUCE=1");
         if (!sparse_file(weights_file)) die("--weights: " + weights_file + " is not a sparse matrix file (.sdm or a coordinate .mtx)");
+    }
+    // --robust: checked before anything touches a GPU
+    if (J.robust) {
+        char *end = nullptr;
+        J.robust_nu = robust_nu.empty() ? NAN : strtod(robust_nu.c_str(), &end);
+        if (robust_nu.empty() || *end != '\0' || !std::isfinite(J.robust_nu) || !(J.robust_nu >= 1.0))
+            die("--robust expects the degrees of freedom NU, a finite number >= 1, not '" + robust_nu + "'");
+        if (ngpu >= 1) die("--robust runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (a sharded side has no weighted sampler)");
+        if (J.weighted) die("--robust does not go together with --weights (the weights of Student-t noise are redrawn in every half-iteration)");
+        if (J.probit) die("--robust does not go together with --probit (the latent scores have unit variance)");
+        if (J.censored) die("--robust does not go together with --censored (the latent draw would need the weight of its cell)");
+        if (J.adaptive) die("--robust does not go together with --noise adaptive (alpha | r would need the weighted residuals)");
+        if (linked) die("--robust does not go together with --row-features / --col-features (the link matrix would need the weighted residuals)");
+        if (!mname.empty() || !lname.empty()) die("--robust does not go together with a propagated posterior (-m / -l)");
+        if (fp32) die("--robust does not go together with --fp32 (the weighted samplers are fp64)");
+        if (topn_score == "prob" || topn_score == "ei")
+            die("--robust does not go together with --topn-score " + topn_score + " (its sigma = 1 / sqrt(alpha) assumes Gaussian noise; mean and ucb are fine)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--robust does not go together with BPMF_REDUCE=1");
+        if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--robust needs a noise precision -a F > 0");
     }
     // --fold-in-rows / --fold-in-cols: checked before anything touches a GPU (the files themselves below, once the shape is known)
     for (int which = 0; which < 2; ++which) {
@@ -1294,6 +1336,11 @@ int main(int argc, char *argv[])
             P = J.T; P.vals = J.pm2;
             if (!J.perm_m.empty()) P = permute(P, inverse(J.perm_m), J.perm_u);
             bpmf::io::write_sparse(J.odirname + "/Pm2.sdm", P);
+            if (J.robust && J.robust_w.size() == J.M.vals.size() && !J.robust_w.empty()) {    // (no kept sample: no file)
+                P = J.M; P.vals = J.robust_w;
+                if (!J.perm_m.empty()) P = permute(P, inverse(J.perm_m), J.perm_u);
+                bpmf::io::write_sparse(J.odirname + "/robust-weights.sdm", P);
+            }
             if (!J.perm_m.empty()) {
                 const std::vector<int64_t> im = inverse(J.perm_m), iu = inverse(J.perm_u);
                 permute_columns(J.u_mu, K, iu); permute_columns(J.u_lambda, (int64_t)K * K, iu);

@@ -35,6 +35,7 @@ extern "C" int bpmf_hip_side_set_censored(bpmf_hip_side *s, const int8_t *flags,
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_censored: the side is a censored side already");
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a probit side (bpmf_hip_side_set_probit)");
     if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with features (bpmf_hip_side_set_features)");
+    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
     if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with propagated priors");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_censored: tag must be >= 1 (key word 0 belongs to the samplers' streams)");

@@ -12,10 +12,11 @@
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
+//   capi_robust.hip    Student-t noise: the weights of a side redrawn on the device ahead of every sampler launch, their posterior mean
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last nine (probit, censoring, weights, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last ten (probit, censoring, weights, Student-t noise, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
@@ -57,10 +58,13 @@ int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
 
 // censored ratings (capi_censor.hip)
 int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a censored side
-// the latent kernel of a probit or a censored side, whichever `self` is (a side is never both)
+// Student-t noise (capi_robust.hip)
+int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a robust side
+// the latent kernel of a probit, a censored or a robust side, whichever `self` is (a side is at most one of them)
 inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
 {
-    return self->probit ? probit_latent_enqueue(self, other, iter, alpha, st) : censor_latent_enqueue(self, other, iter, alpha, st);
+    return self->probit ? probit_latent_enqueue(self, other, iter, alpha, st)
+           : self->censor ? censor_latent_enqueue(self, other, iter, alpha, st) : robust_latent_enqueue(self, other, iter, alpha, st);
 }
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),

@@ -37,6 +37,7 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
     if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with features (bpmf_hip_side_set_features)");
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a censored side (bpmf_hip_side_set_censored)");
+    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_probit: tag must be >= 1 (key word 0 belongs to the samplers' streams)");

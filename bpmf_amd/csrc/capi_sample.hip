@@ -27,7 +27,8 @@ int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, do
     // the sampler below replaces or overwrites) and the copy of the other side's the sampler reads.  No host wait.  The
     // stateful path has enqueued the kernel already, ahead of its wait for the gate kernel (bpmf_hip_sys_sample).
     // censored side: the same for the latent values of its censored entries (capi_censor.hip).
-    if ((self->probit || self->censor) && !self->probit_latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
+    // robust side: the same for its per-rating weights (capi_robust.hip).
+    if ((self->probit || self->censor || self->robust) && !self->probit_latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
     int rc = claim_second_copy(self, st);
@@ -289,6 +290,7 @@ int read_result_blob(bpmf_hip_side *s, double *h_out, double *sum_out, double *p
     int rc = check_timeout(h_out, K, msg);
     if (!rc) rc = check_probit(s, msg);                   // (the latent kernel ran ahead of the sampler whose sums these are)
     if (!rc) rc = check_censor(s, msg);
+    if (!rc) rc = check_robust(s, msg);
     if (rc) return rc;
     const double *prod = h_out + blob::res_prod(K), *sum = h_out + blob::res_sum(K);
     const unsigned long long f = *blob::res_fail_word(h_out, K);
@@ -755,9 +757,10 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     // gate_stage spins on S1 until the host has drawn and staged this half-iteration's hyper-parameters, and S0 continues
     // behind ev[3]).  It needs no hyper-parameters, only the factors the samplers already on S0 wrote, so it runs while the
     // host chain (sums -> cov -> Normal-Wishart -> staging) is still at work.  Fused form: the same place in the queue as
-    // before, directly ahead of the sampler launch that carries its own gate.  The latent kernel of a censored side: likewise.
+    // before, directly ahead of the sampler launch that carries its own gate.  The latent kernel of a censored side and the weight
+    // kernel of a robust side: likewise.
     self->probit_latent_queued = false;
-    if (self->probit || self->censor) {
+    if (self->probit || self->censor || self->robust) {
         if ((rc = latent_enqueue(self, other, iter, alpha, s0))) return rc;
         self->probit_latent_queued = true;
     }

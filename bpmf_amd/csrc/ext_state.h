@@ -51,6 +51,11 @@ struct bpmf_censor {
 // (layout of d_vals).  The weighted forms of the samplers read zw in place of d_vals with mean 0 and multiply every gathered row by sw.
 struct bpmf_weights { DevBuf<double> sw, zw; int64_t nweighted = 0; double wmin = 1.0, wmax = 1.0; };
 
+// Student-t noise (capi_robust.hip): the side's bpmf_weights are redrawn on the device ahead of every sampler
+// launch.  nu: the degrees of freedom; wsum: the running sum of w over the kept samples (layout of d_vals), `kept` of them; the word
+// the weight kernel raises to a rating position when a draw runs into its attempt cap or meets a residual that is not finite
+struct bpmf_robust { double nu = 0.0; uint32_t tag = 0; DevBuf<double> wsum; int kept = 0; Pinned<unsigned long long> fail; };
+
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
 struct bpmf_link_dense {
     DevBuf<double> F, W, PE;

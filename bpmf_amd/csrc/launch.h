@@ -220,6 +220,20 @@ struct CensorLatentLaunch {
 };
 int censor_latent(const CensorLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched); n = 0: nothing launched
 
+// Student-t noise (kernels_robust.h, krobust.hip): fp64 factors only
+struct RobustWeightsLaunch {
+    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
+    const int32_t *rowidx; const double *vals; int64_t nnz;
+    const void *items, *other; int K, kt;                  // both factor matrices (leading dimension K), the caller's num_latent kt
+    uint32_t iter, tag;
+    double mean, sqrt_alpha, nu;                           // the side's mean rating; sqrt(alpha), formed on the host; the degrees of freedom
+    double dd, c;                                          // a - 1 / 3 and 1 / sqrt(9 dd) of the shape a = (nu + 1) / 2, formed on the host
+    double *sw, *zw;                                       // sqrt(w) and sqrt(w) (r - mean), layout of the side's ratings
+    unsigned long long *fail;                              // raised (rating position) when a draw runs into the attempt cap
+};
+int robust_weights(const RobustWeightsLaunch &p, hipStream_t st);        // -1: unsupported K (nothing launched)
+void robust_accumulate(const double *sw, int64_t nnz, double *wsum, hipStream_t st);   // wsum[p] += sw[p]^2
+
 // side information (kernels_link.h, klink.hip): fp64, row-major operands
 struct LinkTnLaunch {                                      // C (D x n, leading dimension ldc) = A^T (B - 1 bvec^T)
     const double *A; int64_t lda;                          // N x D

@@ -214,6 +214,7 @@ struct bpmf_hip_side {
     std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
     std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
     std::unique_ptr<bpmf_weights> weights; // per-rating precision weights (bpmf_hip_side_set_weights)
+    std::unique_ptr<bpmf_robust> robust;   // Student-t noise: the weights are redrawn per launch (bpmf_hip_side_set_robust)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
     std::unique_ptr<bpmf_newrows> newrows; // rows unseen in training: their features and projected samples (bpmf_hip_side_newrows_set)
@@ -406,6 +407,18 @@ inline int check_censor(bpmf_hip_side *s, std::string *msg)
     if (v == ~0ull) return 0;
     __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
     *msg = "censored: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
+    return BPMF_HIP_ENUM;
+}
+
+// Student-t noise: the same for the Gamma draw of a robust side's weights
+inline int check_robust(bpmf_hip_side *s, std::string *msg)
+{
+    if (!s->robust) return 0;
+    unsigned long long *word = s->robust->fail.host();
+    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (v == ~0ull) return 0;
+    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
+    *msg = "robust: the weight of rating " + std::to_string(v) + " could not be drawn: 64 rejections, or a residual that is not finite (non-finite factors?)";
     return BPMF_HIP_ENUM;
 }
 

@@ -570,6 +570,25 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_side_weights_count(side.handle, C.byref(n), C.byref(lo), C.byref(hi)))
         return n.value, lo.value, hi.value
 
+    # -- Student-t noise ------------------------------------------------------------
+    def set_robust(self, side, nu, tag):
+        """Makes `side` a robust side: Student-t noise with nu >= 1 degrees of freedom as a scale mixture (include/bpmf_hip.h, DESIGN.md
+        section 21).  The side gets per-rating weights that start at 1 and are redrawn on the device ahead of every one of its
+        sampler launches, on the Philox streams `tag` (>= 1; one per side, used by nothing else in the run).  fp64 contexts, one
+        GPU; not with set_weights, probit, censored ratings, features, propagated priors or BPMF_REDUCE."""
+        _lib.check(self.lib.bpmf_hip_side_set_robust(side.handle, float(nu), int(tag)))
+
+    def robust_add(self, side):
+        """Adds the weights the newest launch of a robust side read to their running sums (enqueue only, no host wait)."""
+        _lib.check(self.lib.bpmf_hip_side_robust_add(side.handle))
+
+    def robust_get(self, side):
+        """(posterior-mean weight per rating in the side's order, samples added, nu) of a robust side."""
+        w = np.empty(side.nnz)
+        n, nu = C.c_int(), C.c_double()
+        _lib.check(self.lib.bpmf_hip_side_robust_get(side.handle, _ptr(w), C.byref(n), C.byref(nu)))
+        return w, n.value, nu.value
+
     # -- side information ---------------------------------------------------------
     def set_features(self, side, F, lambda_beta=5.0, tag=3):
         """Gives `side` the feature matrix F [ncols, D] (one row per column of the side), a link matrix beta (D x K, 0) and the

@@ -188,7 +188,7 @@ class Sys:
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
-          new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None):
+          new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -277,7 +277,42 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     those of Mt from W transposed) and run the weighted form of their sampler: nothing is enqueued per iteration, the pipelined
     loop does not drain.  With or without topn, topn_score, foldin (a folded-in row's own ratings have weight 1); the test matrix
     is unweighted.  probit=True, censored, noise="adaptive", features and an fp32 engine are refused with weights.  res["weights"]
-    = (cells whose weight is not 1, smallest weight, largest weight).  None (the default): nothing changes."""
+    = (cells whose weight is not 1, smallest weight, largest weight).  None (the default): nothing changes.
+
+    robust=NU: Student-t noise with NU >= 1 degrees of freedom (1: Cauchy) instead of Gaussian noise, location mean + u . v, scale
+    1 / sqrt(alpha): r | w ~ N(mean + u . v, 1 / (alpha w)), w ~ Gamma(NU / 2, rate NU / 2).  Both sides
+    become robust sides (engine.set_robust, tags 9 = movies, 10 = users) and redraw the weights of their ratings ahead of every
+    sampler launch, on the device, without a host wait: the pipelined loop does not drain.  A gross outlier draws a small weight
+    and stops dragging its factors.  Every post-burn-in iteration adds the movies' weights to their running sums
+    (engine.robust_add, enqueue only).  res["robust"] = dict(nu=NU, weight_mean=the posterior-mean weight of every training
+    rating in M's CSC order (zeros without a kept sample), kept=the samples in it).  With or without topn, foldin (a folded-in
+    row's own ratings are Gaussian with weight 1) and topn_score ("ucb" only: the sigma = 1 / sqrt(alpha) of "prob" and "ei"
+    assumes Gaussian noise).  weights, probit=True, censored, noise="adaptive", features and an fp32 engine are refused with
+    robust.  None (the default): nothing changes."""
+    if robust is not None:                           # (refused before the engine is used)
+        try:
+            robust = float(robust)
+        except (TypeError, ValueError):
+            raise ValueError("robust must be a number: the degrees of freedom nu >= 1")
+        if not (math.isfinite(robust) and robust >= 1.0):
+            raise ValueError("robust = %r: the degrees of freedom nu must be finite and >= 1" % (robust,))
+        if weights is not None:
+            raise ValueError("robust does not go together with weights (the weights of a robust side are redrawn in every half-iteration)")
+        if probit:
+            raise ValueError("robust does not go together with probit=True (the latent scores have unit variance)")
+        if censored is not None:
+            raise ValueError("robust does not go together with censored (the latent draw would need the weight of its cell)")
+        if noise == "adaptive":
+            raise ValueError("robust does not go together with noise='adaptive' (alpha | r would need the weighted residuals)")
+        if row_features is not None or col_features is not None:
+            raise ValueError("robust does not go together with row_features / col_features (the link matrix would need the weighted residuals)")
+        if getattr(engine, "dtype", "f64") == "f32":
+            raise ValueError("robust needs an fp64 engine")
+        if topn_score is not None and isinstance(topn_score, (tuple, list)) and len(topn_score) > 0 and topn_score[0] in ("prob", "ei"):
+            raise ValueError("robust does not go together with topn_score %r (its sigma = 1 / sqrt(alpha) assumes Gaussian noise; "
+                             "'ucb' is fine)" % (topn_score[0],))
+        if alpha is not None and not (float(alpha) > 0 and math.isfinite(float(alpha))):
+            raise ValueError("robust needs a finite alpha > 0")
     if weights is not None:                          # (refused before the engine is used)
         if probit:
             raise ValueError("weights does not go together with probit=True (the latent scores have unit variance)")
@@ -394,6 +429,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if weights is not None:
         engine.set_weights(movies.side, wts[0])
         engine.set_weights(users.side, wts[1])
+    if robust is not None:
+        engine.set_robust(movies.side, robust, ROBUST_TAGS[0])
+        engine.set_robust(users.side, robust, ROBUST_TAGS[1])
     if linked:
         if col_features is not None:
             engine.set_features(movies.side, col_features, lambda_beta, 3)
@@ -444,6 +482,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             engine.newrows_add(users.side, movies.side)
         if new_col_features is not None and i >= burnin:
             engine.newrows_add(movies.side, users.side)
+        if robust is not None and i >= burnin:
+            engine.robust_add(movies.side)
         if probit and i >= burnin and movies.test is not None:
             engine.probit_add(movies.test, movies.side, users.side)
         if linked and i >= burnin:
@@ -544,6 +584,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         res["censored"] = engine.censored_count(movies.side)
     if weights is not None:
         res["weights"] = engine.weights_count(movies.side)
+    if robust is not None:
+        kept = max(nsims - burnin, 0)
+        wm = engine.robust_get(movies.side)[0] if kept > 0 else np.zeros(len(M[2]))
+        res["robust"] = dict(nu=robust, weight_mean=wm, kept=kept)
     if linked:
         res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
         res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None
@@ -565,7 +609,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     return res
 
 
-FOLDIN_TAGS = {"rows": 7, "cols": 8}                 # the random streams of folded-in users / movies (1 .. 6 are taken: gibbs)
+FOLDIN_TAGS = {"rows": 7, "cols": 8}                 # the random streams of folded-in users / movies (1 .. 6 and 9, 10 are taken: gibbs)
+ROBUST_TAGS = (9, 10)                                # the random streams of the weights of Student-t noise: movies, users
 
 
 def fold_in(res, new_rows=None, new_cols=None, topn=None, draw=True):

@@ -504,6 +504,34 @@ BPMF_API int bpmf_hip_side_weights_get(bpmf_hip_side *side, double *sw_host, dou
 /* The number of ratings whose weight is not 1, the smallest and the largest weight of a side with weights. */
 BPMF_API int bpmf_hip_side_weights_count(bpmf_hip_side *side, int64_t *nweighted, double *wmin, double *wmax);
 
+/* ---- Student-t noise: the weights redrawn on the device ------------------------------
+ * r_p ~ Student-t with nu degrees of freedom, location mean_rating + x_c . y_r, scale 1 / sqrt(alpha), as a scale mixture:
+ *     r_p | w_p ~ N(mean_rating + x_c . y_r, 1 / (alpha w_p)),   w_p ~ Gamma(nu / 2, rate nu / 2),
+ *     w_p | rest ~ Gamma((nu + 1) / 2, rate (nu + alpha e^2) / 2),   e = (r_p - mean_rating) - x_c . y_r.
+ * A gross outlier draws a small weight and stops dragging its factor columns.  nu >= 1 is fixed by the caller (1: Cauchy noise;
+ * large: the Gaussian model), alpha by the sampling calls.  DESIGN.md section 21 has the draw and what it costs.
+ *
+ * bpmf_hip_side_set_robust makes `side` a side with per-rating weights (above) that start at 1 and are redrawn on the device ahead of
+ * every sampler launch of the side (bpmf_hip_sys_sample, bpmf_hip_sample_side[_launch]) by k_robust_weights, from the factors that
+ * launch reads, on the Philox blocks (rating lo, rating hi, iteration, 2 attempt [+ 1]; 42, tag): in the launch's queue, without a
+ * host wait.  The launch itself is the weighted form of the side's sampler, as after bpmf_hip_side_set_weights;
+ * bpmf_hip_side_weights_get then waits for the work in flight and returns the arrays the newest launch read.  Give the two sides of
+ * a model different tags that no other add-on of the run uses.
+ * A draw that is rejected 64 times (probability < 2^-270) or meets a residual that is not finite (NaN factors) stores w = 1 and
+ * is reported by the next call that collects the side's results as BPMF_HIP_ENUM naming the rating.
+ * BPMF_HIP_EINVAL: NULL, nu not finite or < 1, tag 0, an fp32 context, a side that has weights or is robust already, a probit side,
+ * a censored side, a side with features, propagated priors, the BPMF_REDUCE formulation, a context with a communicator or a
+ * sharded side; a launch with an alpha that is not finite and > 0.  In turn bpmf_hip_side_set_weights, bpmf_hip_side_set_probit,
+ * bpmf_hip_side_set_censored, bpmf_hip_side_set_features[_sparse], bpmf_hip_side_set_prop_posterior, bpmf_hip_sys_set_reduce and
+ * bpmf_hip_train_sse refuse a robust side. */
+BPMF_API int bpmf_hip_side_set_robust(bpmf_hip_side *side, double nu, unsigned tag);
+/* Adds the weights the side's newest launch read to their running sums (k_robust_accumulate behind that launch: enqueue only). */
+BPMF_API int bpmf_hip_side_robust_add(bpmf_hip_side *side);
+/* The posterior-mean weight of every rating (nnz doubles in the order of the side's ratings: the sums over the count of
+ * bpmf_hip_side_robust_add calls; waits for the work in flight), that count and nu.  Any pointer may be NULL; wmean_host given and
+ * nothing added: BPMF_HIP_EINVAL. */
+BPMF_API int bpmf_hip_side_robust_get(bpmf_hip_side *side, double *wmean_host, int *count, double *nu);
+
 /* ---- side information: row / column features linked to the factor priors -----------
  * A side with N columns may carry a dense feature matrix F (N x D, fp64), a link matrix beta (D x K) and a fixed
  * lambda_beta > 0:
