@@ -102,6 +102,17 @@ _SIGNATURES = {
     "bpmf_hip_side_set_robust": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),
     "bpmf_hip_side_robust_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_robust_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "bpmf_hip_tensor_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.POINTER(C.c_void_p)]),
+    "bpmf_hip_tensor_destroy": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_tensor_side": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "bpmf_hip_tensor_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_tensor_product": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "bpmf_hip_tensor_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bpmf_hip_tensor_test_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bpmf_hip_tensor_test_destroy": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_tensor_predict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_tensor_test_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_set_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint]),
     "bpmf_hip_link_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     "bpmf_hip_side_link_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -161,6 +172,9 @@ _SIGNATURES = {
     "bpmf_io_read_dense": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(c_f64p)]),
     "bpmf_io_write_dense": (C.c_int, [C.c_char_p, C.c_int64, C.c_int64, C.c_void_p]),
     "bpmf_io_free": (None, [C.c_void_p]),
+    "bpmf_io_read_tns": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(c_i32p), C.POINTER(c_i32p), C.POINTER(c_i32p),
+                                   C.POINTER(c_f64p)]),
+    "bpmf_io_write_tns": (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_assign_greedy": (C.c_int, [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_assign_contiguous": (C.c_int, [C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
 }

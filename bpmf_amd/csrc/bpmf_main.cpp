@@ -53,6 +53,12 @@
 // sides redraw a precision weight per rating on the device ahead of every sampler launch (bpmf_hip_side_set_robust); one more header
 // line names NU, -o DIR also writes DIR/robust-weights.sdm (the posterior-mean weight of every training cell), everything else keeps
 // its format.
+// --tensor FILE.tns [--tensor-test FILE.tns] [--tensor-dims I,J,T] (one GPU, no -g): Bayesian CP factorisation of a sparse tensor of
+// order 3 in the place of -n / -p.  FROSTT .tns files (one entry per line, "i j t value", 1-based, # comments,
+// optional .gz); the sizes default to the largest index of either file.  -i, -b, -a, -d and -o apply.  stdout: the header line
+// "tensor: I x J x T, NNZ ratings, NNZT test", one line per iteration (RMSE, avg RMSE, the norms F1 F2 F3 of the three factor
+// matrices, items/sec), "Final Avg RMSE:".  -o DIR gets mode1-mu.ddm .. mode3-mu.ddm (the posterior-mean factors, num_latent x size)
+// and Pavg.tns / Pm2.tns (the test entries in the order of their file, 1-based).
 #include <getopt.h>
 #include <fcntl.h>
 #include <unistd.h>
@@ -91,6 +97,7 @@ void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
               << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--weights FILE] [--robust NU] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << "       bpmf --tensor <TNS> [--tensor-test <TNS>] [--tensor-dims I,J,T] [-o DIR/] [-i N] [-b N] [-a F] [-d K]\n"
               << "\n"
               << "Parameters:\n"
               << "  -n MTX: training matrix (rows = users, columns = items)\n"
@@ -167,6 +174,12 @@ void usage()
               << "              stops dragging its factors; -o DIR also gets robust-weights.sdm, the posterior-mean weight of every training\n"
               << "              cell (one GPU, no -g; not with --weights, --probit, --censored, --noise adaptive, --row-features /\n"
               << "              --col-features, -m / -l, --fp32, --topn-score prob|ei or BPMF_REDUCE=1)\n"
+              << "  [--tensor FILE.tns]: factorise a sparse tensor of order 3 (Bayesian CP) instead of a matrix: FILE takes the place of -n / -p;\n"
+              << "              FROSTT format, one entry per line, i j t value, 1-based indices, # comments, optional .gz (one GPU, no -g; -i, -b,\n"
+              << "              -a, -d and -o apply; not with --fp32, -m / -l, --probit, --censored, --weights, --robust, --noise adaptive,\n"
+              << "              features, --topn, fold-in or BPMF_REDUCE=1).  -o DIR gets mode1-mu.ddm .. mode3-mu.ddm, Pavg.tns and Pm2.tns\n"
+              << "  [--tensor-test FILE.tns]: held-out entries of the tensor, evaluated after every iteration\n"
+              << "  [--tensor-dims I,J,T]: the sizes of the three modes (default: the largest index seen in either file)\n"
               << "  [-t N]: host threads (accepted; the column loop runs on the GPU)\n"
               << "\n"
               << "Matrix formats (by extension, optionally .gz):\n"
@@ -770,6 +783,102 @@ void rank_main(Job &J, int rank, std::ostream &os)
 
 }  // namespace
 
+// --tensor: the Gibbs loop of the tensor model (bpmf_amd.tensor_gibbs is the same loop): per iteration every mode, last mode first --
+// the hyper-parameters of the mode at counter `it` from its cov, bpmf_hip_tensor_sample, cov from the sums -- then the test entries.
+static int run_tensor(const std::string &file, const std::string &test_file, const std::string &dims_text, bool dims_given, int K, int nsims, int burnin,
+               double alpha, const std::string &odir)
+{
+    using bpmf::io::Tns;
+    Tns A, T;
+    try {
+        A = bpmf::io::read_tns(file);
+        if (!test_file.empty()) T = bpmf::io::read_tns(test_file);
+    } catch (const std::exception &e) { die(e.what()); }
+    int64_t dims[3];
+    for (int m = 0; m < 3; ++m) dims[m] = std::max(A.dims[m], T.dims[m]);
+    if (dims_given) {
+        long long d[3] = {0, 0, 0};
+        char tail = 0;
+        if (sscanf(dims_text.c_str(), "%lld,%lld,%lld%c", &d[0], &d[1], &d[2], &tail) != 3 || d[0] < 1 || d[1] < 1 || d[2] < 1)
+            die("--tensor-dims expects I,J,T, three sizes >= 1, not '" + dims_text + "'");
+        for (int m = 0; m < 3; ++m) {
+            if (d[m] < dims[m])
+                die("--tensor-dims " + dims_text + ": mode " + std::to_string(m + 1) + " has size " + std::to_string(d[m]) + ", the files hold the index " + std::to_string(dims[m]));
+            dims[m] = d[m];
+        }
+    }
+    const int64_t nnz = (int64_t)A.vals.size(), nnzt = (int64_t)T.vals.size();
+    if (nnz == 0) die("the training tensor is empty");
+    double mean = 0.0;
+    for (double v : A.vals) mean += v;
+    mean /= (double)nnz;
+    std::ostream &os = std::cout;
+    os << "tensor: " << dims[0] << " x " << dims[1] << " x " << dims[2] << ", " << nnz << " ratings, " << nnzt << " test" << std::endl;
+    os << "num_latent: " << K << "\n" << "mean rating: " << mean << "\n" << "alpha: " << alpha << std::endl;
+
+    bpmf_hip_ctx *ctx = nullptr;
+    bpmf_hip_tensor *tensor = nullptr;
+    bpmf_hip_tensor_test *tt = nullptr;
+    check(bpmf_hip_ctx_create(0, K, nullptr, &ctx));
+    check(bpmf_hip_tensor_create(ctx, 3, dims, nnz, A.idx[0].data(), A.idx[1].data(), A.idx[2].data(), A.vals.data(), mean, &tensor));
+    if (nnzt > 0) check(bpmf_hip_tensor_test_create(tensor, nnzt, T.idx[0].data(), T.idx[1].data(), T.idx[2].data(), T.vals.data(), &tt));
+    const size_t kk = (size_t)K * K;
+    std::vector<double> cov[3], mu((size_t)K), LU(kk), LF(kk), sum((size_t)K), prod(kk);
+    for (auto &c : cov) c.assign(kk, 0.0);
+    double rmse = 0.0, rmse_avg = 0.0, items_sec_sum = 0.0;
+    int kept = 0;
+    for (int it = 0; it < nsims; ++it) {
+        const double t0 = tick();
+        double norm[3] = {0, 0, 0};
+        for (int m = 2; m >= 0; --m) {
+            if (bpmf_hyper_sample(K, dims[m], cov[m].data(), nullptr, (uint32_t)it, mu.data(), LU.data(), LF.data())) die("the hyper-parameter draw failed");
+            check(bpmf_hip_tensor_sample(tensor, m, it, alpha, mu.data(), LF.data(), sum.data(), prod.data(), &norm[m]));
+            bpmf_cov_from_sums(K, dims[m], sum.data(), prod.data(), cov[m].data());
+        }
+        if (tt) {
+            double se = 0.0, se_avg = 0.0;
+            int64_t count = 0;
+            check(bpmf_hip_tensor_predict(tt, it < burnin ? 0 : it - burnin, &se, &se_avg, &count));
+            rmse = std::sqrt(se / (double)count); rmse_avg = std::sqrt(se_avg / (double)count);
+        }
+        if (it >= burnin && !odir.empty()) {
+            for (int m = 0; m < 3; ++m) check(bpmf_hip_side_aggr_add(bpmf_hip_tensor_side(tensor, m)));
+            ++kept;
+        }
+        const double items_per_sec = (double)(dims[0] + dims[1] + dims[2]) / (tick() - t0);
+        items_sec_sum += items_per_sec;
+        char buf[512];
+        snprintf(buf, sizeof buf, "0: %s iteration %d:\t RMSE: %3.4f\tavg RMSE: %3.4f\tF1(%6.2f)\tF2(%6.2f)\tF3(%6.2f)\titems/sec: %6.2f",
+                 (it < burnin) ? "Burnin" : "Sampling", it, rmse, rmse_avg, std::sqrt(norm[0]), std::sqrt(norm[1]), std::sqrt(norm[2]), items_per_sec);
+        os << buf << "\n" << std::flush;
+    }
+    if (!odir.empty()) {
+        try {
+            for (int m = 0; m < 3 && kept > 0; ++m) {
+                Dense d;
+                d.nrows = K; d.ncols = dims[m]; d.data.resize((size_t)K * (size_t)dims[m]);
+                std::vector<double> lambda(kk * (size_t)dims[m]);
+                check(bpmf_hip_side_aggr_finalize(bpmf_hip_tensor_side(tensor, m), kept, d.data.data(), lambda.data()));
+                bpmf::io::write_dense(odir + "/mode" + std::to_string(m + 1) + "-mu.ddm", d);
+            }
+            if (tt) {
+                Tns P = T;
+                std::vector<double> pm2((size_t)nnzt);
+                check(bpmf_hip_tensor_test_get(tt, P.vals.data(), pm2.data()));
+                bpmf::io::write_tns(odir + "/Pavg.tns", P);
+                P.vals = pm2;
+                bpmf::io::write_tns(odir + "/Pm2.tns", P);
+            }
+        } catch (const std::exception &e) { die(e.what()); }
+    }
+    os << "Final Avg RMSE: " << rmse_avg << std::endl;
+    os << "Average items/sec: " << items_sec_sum / std::max(nsims, 1) << std::endl;
+    check(bpmf_hip_tensor_test_destroy(tt));
+    check(bpmf_hip_tensor_destroy(tensor));
+    check(bpmf_hip_ctx_destroy(ctx));
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     Job J;
@@ -793,11 +902,15 @@ int main(int argc, char *argv[])
                                               {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
                                               {"topn-threshold", required_argument, nullptr, 1019},
                                               {"fold-in-rows", required_argument, nullptr, 1020}, {"fold-in-cols", required_argument, nullptr, 1021},
+                                              {"tensor", required_argument, nullptr, 1040}, {"tensor-test", required_argument, nullptr, 1041},
+                                              {"tensor-dims", required_argument, nullptr, 1042},
                                               {nullptr, 0, nullptr, 0}};
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
     bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
+    std::string tensor_file, tensor_test, tensor_dims;
+    bool tensor_given = false, tensor_test_given = false, tensor_dims_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
         switch (ch) {
@@ -825,6 +938,9 @@ int main(int argc, char *argv[])
         case 1019: topn_threshold = optarg; topn_threshold_given = true; break;
         case 1020: fold_in_rows = optarg; break;
         case 1021: fold_in_cols = optarg; break;
+        case 1040: tensor_file = optarg; tensor_given = true; break;
+        case 1041: tensor_test = optarg; tensor_test_given = true; break;
+        case 1042: tensor_dims = optarg; tensor_dims_given = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -842,6 +958,30 @@ int main(int argc, char *argv[])
         case 'v': J.verbose = true; break;
         default: usage(); return 1;
         }
+    }
+    // --tensor: refused before anything touches a GPU, then a loop of its own (run_tensor)
+    if ((tensor_test_given || tensor_dims_given) && !tensor_given) die(std::string(tensor_test_given ? "--tensor-test" : "--tensor-dims") + " needs --tensor FILE.tns");
+    if (tensor_given) {
+        if (tensor_file.empty()) die("--tensor expects a file");
+        if (!fname.empty() || !probename.empty()) die("--tensor takes the place of the matrix files: -n / -p do not go together with it");
+        if (ngpu >= 1) die("--tensor runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (a mode's side is not sharded)");
+        if (fp32) die("--tensor does not go together with --fp32 (the Khatri-Rao rows and their samplers are fp64)");
+        if (!mname.empty() || !lname.empty()) die("--tensor does not go together with a propagated posterior (-m / -l)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--tensor does not go together with BPMF_REDUCE=1");
+        if (J.probit || threshold_given) die("--tensor does not go together with --probit");
+        if (J.censored) die("--tensor does not go together with --censored");
+        if (J.weighted) die("--tensor does not go together with --weights");
+        if (J.robust) die("--tensor does not go together with --robust");
+        if (noise != "fixed" || !alpha_prior.empty() || !alpha_max.empty()) die("--tensor does not go together with --noise adaptive");
+        if (!row_features.empty() || !col_features.empty() || !new_row_features.empty() || !new_col_features.empty() || !lambda_beta.empty() ||
+            !lambda_beta_prior.empty() || !link_tol.empty() || !link_max_iter.empty())
+            die("--tensor does not go together with --row-features / --col-features");
+        if (J.topn > 0 || topn_score != "mean" || topn_kappa_given || topn_threshold_given) die("--tensor does not go together with --topn");
+        if (!fold_in_rows.empty() || !fold_in_cols.empty()) die("--tensor does not go together with --fold-in-rows / --fold-in-cols");
+        if (J.verbose) die("--tensor does not go together with -v");
+        if (!bpmf_hip_supports(K, BPMF_HIP_F64)) die("unsupported number of latent dimensions " + std::to_string(K) + " (1 .. 128)");
+        if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--tensor needs a noise precision -a F > 0");
+        return run_tensor(tensor_file, tensor_test, tensor_dims, tensor_dims_given, K, J.nsims, J.burnin, J.alpha, J.odirname);
     }
     if (fname.empty() || probename.empty()) { usage(); return 1; }
     // --topn: checked before anything touches a GPU

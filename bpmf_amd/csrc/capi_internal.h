@@ -13,6 +13,7 @@
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
 //   capi_robust.hip    Student-t noise: the weights of a side redrawn on the device ahead of every sampler launch, their posterior mean
+//   capi_tensor.hip    sparse tensor factorisation (CP, order 3): a side per mode behind the Khatri-Rao rows of the other two, test entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)

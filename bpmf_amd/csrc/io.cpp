@@ -12,6 +12,9 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -408,6 +411,77 @@ void write_dense(const std::string &path, const Dense &d)
     spill(path, t.gz, out);
 }
 
+// ---- FROSTT .tns: one entry per line, "i j t value", 1-based indices, whitespace-separated, # comment lines -----------------------
+Tns read_tns(const std::string &path)
+{
+    const bool gz = ends_with(path, ".gz");
+    const std::string stem = gz ? path.substr(0, path.size() - 3) : path;
+    if (!ends_with(stem, ".tns")) throw IoError("Unknown tensor file type (.tns or .tns.gz expected): " + path);
+    const std::string bytes = slurp(path, gz);
+    Lines in{bytes};
+    Tns t;
+    std::string line;
+    int64_t lineno = 0;
+    while (in.next(line)) {
+        ++lineno;
+        const char *p = line.c_str();
+        while (*p && isspace((unsigned char)*p)) ++p;
+        if (!*p || *p == '#') continue;
+        const std::string at = path + ", line " + std::to_string(lineno) + ": ";
+        long long ix[3];
+        for (int m = 0; m < 3; ++m) {
+            char *end = nullptr;
+            errno = 0;
+            ix[m] = strtoll(p, &end, 10);
+            if (end == p || (*end && !isspace((unsigned char)*end))) throw IoError(at + "three indices and a value expected (i j t value)");
+            if (errno || ix[m] > (long long)INT32_MAX) throw IoError(at + "an index does not fit 32 bits");
+            if (ix[m] < 1) throw IoError(at + "index " + std::to_string(ix[m]) + " in mode " + std::to_string(m + 1) + ": the indices of a .tns file are 1-based");
+            p = end;
+        }
+        char *end = nullptr;
+        const double v = strtod(p, &end);
+        if (end == p) throw IoError(at + "three indices and a value expected (i j t value)");
+        p = end;
+        while (*p && isspace((unsigned char)*p)) ++p;
+        if (*p) throw IoError(at + "more than three indices: tensors of order 3 only");
+        if (!std::isfinite(v)) throw IoError(at + "the value is not finite");
+        for (int m = 0; m < 3; ++m) { t.idx[m].push_back((int32_t)(ix[m] - 1)); t.dims[m] = std::max<int64_t>(t.dims[m], ix[m]); }
+        t.vals.push_back(v);
+        t.line.push_back(lineno);
+    }
+    // no cell twice
+    std::vector<int64_t> o(t.vals.size());
+    for (size_t e = 0; e < o.size(); ++e) o[e] = (int64_t)e;
+    auto cell_less = [&](int64_t x, int64_t y) {
+        for (int m = 0; m < 3; ++m) if (t.idx[m][x] != t.idx[m][y]) return t.idx[m][x] < t.idx[m][y];
+        return x < y;
+    };
+    std::sort(o.begin(), o.end(), cell_less);
+    int64_t first = -1, other = -1;
+    for (size_t q = 1; q < o.size(); ++q) {
+        const int64_t x = o[q - 1], y = o[q];
+        if (t.idx[0][x] == t.idx[0][y] && t.idx[1][x] == t.idx[1][y] && t.idx[2][x] == t.idx[2][y] && (first < 0 || y < first)) { first = y; other = x; }
+    }
+    if (first >= 0)
+        throw IoError(path + ": cell (" + std::to_string(t.idx[0][first] + 1) + ", " + std::to_string(t.idx[1][first] + 1) + ", " + std::to_string(t.idx[2][first] + 1) +
+                      ") is listed twice (lines " + std::to_string(t.line[other]) + " and " + std::to_string(t.line[first]) + ")");
+    return t;
+}
+
+void write_tns(const std::string &path, const Tns &t)
+{
+    const bool gz = ends_with(path, ".gz");
+    const std::string stem = gz ? path.substr(0, path.size() - 3) : path;
+    if (!ends_with(stem, ".tns")) throw IoError("Unknown tensor file type (.tns or .tns.gz expected): " + path);
+    std::string out;
+    char buf[128];
+    for (size_t e = 0; e < t.vals.size(); ++e) {
+        snprintf(buf, sizeof buf, "%lld %lld %lld %.17g\n", (long long)t.idx[0][e] + 1, (long long)t.idx[1][e] + 1, (long long)t.idx[2][e] + 1, t.vals[e]);
+        out += buf;
+    }
+    spill(path, gz, out);
+}
+
 }  // namespace io
 }  // namespace bpmf
 
@@ -470,5 +544,26 @@ extern "C" int bpmf_io_write_dense(const char *path, int64_t nrows, int64_t ncol
         d.nrows = nrows; d.ncols = ncols;
         d.data.assign(data, data + (size_t)nrows * (size_t)ncols);
         bpmf::io::write_dense(path, d);
+    });
+}
+
+extern "C" int bpmf_io_read_tns(const char *path, int64_t *nnz, int64_t *dims, int32_t **idx0, int32_t **idx1, int32_t **idx2, double **vals)
+{
+    return guarded([&] {
+        const bpmf::io::Tns t = bpmf::io::read_tns(path);
+        *nnz = (int64_t)t.vals.size();
+        for (int m = 0; m < 3; ++m) dims[m] = t.dims[m];
+        *idx0 = dup(t.idx[0]); *idx1 = dup(t.idx[1]); *idx2 = dup(t.idx[2]); *vals = dup(t.vals);
+    });
+}
+
+extern "C" int bpmf_io_write_tns(const char *path, int64_t nnz, const int32_t *idx0, const int32_t *idx1, const int32_t *idx2, const double *vals)
+{
+    return guarded([&] {
+        bpmf::io::Tns t;
+        const int32_t *idx[3] = {idx0, idx1, idx2};
+        for (int m = 0; m < 3; ++m) t.idx[m].assign(idx[m], idx[m] + nnz);
+        t.vals.assign(vals, vals + nnz);
+        bpmf::io::write_tns(path, t);
     });
 }

@@ -42,5 +42,18 @@ Dense read_dense(const std::string &path);
 void write_sparse(const std::string &path, const Csc &m);
 void write_dense(const std::string &path, const Dense &m);
 
+// a sparse tensor of order 3 in the FROSTT .tns format (optionally .gz): one entry per line, "i j t value", 1-based indices,
+// whitespace-separated, # comment lines.  Entries in file order, indices 0-based here; dims: the largest index seen per mode.
+struct Tns {
+    int64_t dims[3] = {0, 0, 0};
+    std::vector<int32_t> idx[3];
+    std::vector<double> vals;
+    std::vector<int64_t> line;     // the line of every entry (read_tns; for messages)
+};
+// refuses (IoError naming the line): fewer or more than three indices, an index < 1 or past 32 bits, a value that is not finite,
+// a cell listed twice
+Tns read_tns(const std::string &path);
+void write_tns(const std::string &path, const Tns &t);      // values as %.17g: a round trip is exact
+
 }  // namespace io
 }  // namespace bpmf

@@ -234,6 +234,16 @@ struct RobustWeightsLaunch {
 int robust_weights(const RobustWeightsLaunch &p, hipStream_t st);        // -1: unsupported K (nothing launched)
 void robust_accumulate(const double *sw, int64_t nnz, double *wsum, hipStream_t st);   // wsum[p] += sw[p]^2
 
+// sparse tensor factorisation (kernels_tensor.h, ktensor.hip): fp64 factors only
+struct KhatriRaoLaunch {                                   // P[:, e] = A[:, ia[e]] o B[:, ib[e]], e < n; rows kt .. ld - 1 of P zero
+    const double *A, *B;                                   // the two other modes' factor matrices (leading dimension ld)
+    const int32_t *ia, *ib; int64_t n;                     // per entry its column of A and of B
+    int ld, kt;                                            // the context's leading dimension and the caller's num_latent
+    double *P;                                             // ld x n
+    hipEvent_t ev_start, ev_stop;                          // optional: recorded by the dispatch packet itself (bpmf_hip_tensor_last_ms)
+};
+int khatri_rao(const KhatriRaoLaunch &p, hipStream_t st);  // -1: unsupported ld (nothing launched); n = 0: nothing launched
+
 // side information (kernels_link.h, klink.hip): fp64, row-major operands
 struct LinkTnLaunch {                                      // C (D x n, leading dimension ldc) = A^T (B - 1 bvec^T)
     const double *A; int64_t lda;                          // N x D

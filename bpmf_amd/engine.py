@@ -22,6 +22,13 @@ class _Side:
         self._keep = keep          # arrays / tensors that must outlive the handle
 
 
+class _Tensor:
+    def __init__(self, handle, dims, nnz, mean_rating, sides):
+        self.handle, self.dims, self.nnz, self.mean_rating = handle, dims, nnz, mean_rating
+        self.sides = sides         # the three modes as sides (owned by the tensor: get_items / set_items / aggr_add / kernel_name ...)
+        self.tests = []            # [handle, entries] of its live test sets
+
+
 class HipEngine:
     """One context = one GPU + one stream.  `stream` is an integer hipStream_t or None."""
 
@@ -48,6 +55,8 @@ class HipEngine:
                 if t[0]:
                     self.lib.bpmf_hip_test_destroy(t[0])
                     t[0] = None
+            for t in getattr(self, "_tensors", []):
+                self.tensor_destroy(t)
             for s in self._sides:
                 if s.handle:
                     self.lib.bpmf_hip_side_destroy(s.handle)
@@ -588,6 +597,107 @@ class HipEngine:
         n, nu = C.c_int(), C.c_double()
         _lib.check(self.lib.bpmf_hip_side_robust_get(side.handle, _ptr(w), C.byref(n), C.byref(nu)))
         return w, n.value, nu.value
+
+    # -- sparse tensor factorisation -----------------------------------------------
+    @staticmethod
+    def _tensor_entries(who, idx, vals):
+        idx = np.asarray(idx)
+        if idx.ndim != 2 or idx.shape[1] != 3:
+            raise ValueError("%s: idx must be [nnz, 3], one 0-based index per mode" % who)
+        if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise ValueError("%s: an index does not fit 32 bits" % who)
+        vals = np.ascontiguousarray(vals, np.float64)
+        if vals.shape != (idx.shape[0],):
+            raise ValueError("%s: %d entries with %s values" % (who, idx.shape[0], vals.shape))
+        cols = [np.ascontiguousarray(idx[:, m], np.int32) for m in range(3)]
+        if idx.shape[0] == 0:
+            cols, vals = [np.zeros(1, np.int32)] * 3, np.zeros(1)
+        return cols, vals, int(idx.shape[0])
+
+    def tensor_create(self, idx, vals, dims, mean_rating):
+        """A sparse tensor of order 3 for Bayesian CP factorisation (include/bpmf_hip.h): idx [nnz, 3] holds the
+        0-based indices of every entry, vals its value, dims the three sizes.  Every mode becomes a side (tensor.sides[m]) behind the
+        Khatri-Rao rows of the other two modes.  fp64 engines, one GPU."""
+        cols, v, nnz = self._tensor_entries("tensor_create", idx, vals)
+        d = np.ascontiguousarray(dims, np.int64)
+        if d.shape != (3,):
+            raise ValueError("tensor_create: dims must hold three sizes (tensors of order 3 only)")
+        h = C.c_void_p()
+        _lib.check(self.lib.bpmf_hip_tensor_create(self.ctx, 3, _ptr(d), nnz, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(v),
+                                                   float(mean_rating), C.byref(h)))
+        sides = []
+        for m in range(3):
+            sd = _Side(C.c_void_p(self.lib.bpmf_hip_tensor_side(h, m)), self.K, int(d[m]), max(nnz, 1), 0, int(d[m]), None)
+            sd.nnz = nnz
+            sides.append(sd)
+        t = _Tensor(h, tuple(int(x) for x in d), nnz, float(mean_rating), sides)
+        if not hasattr(self, "_tensors"):
+            self._tensors = []
+        self._tensors.append(t)
+        return t
+
+    def tensor_destroy(self, tensor):
+        if tensor.handle:
+            for tt in tensor.tests:
+                self.tensor_test_destroy(tt)
+            _lib.check(self.lib.bpmf_hip_tensor_destroy(tensor.handle))
+            tensor.handle = None
+            for sd in tensor.sides:
+                sd.handle = None
+
+    def tensor_sample(self, tensor, mode, it, alpha, mu, LambdaF):
+        """One blocking half-iteration of a mode: its Khatri-Rao rows, then its sampler.  Returns (sum[K], prod[K,K], norm)."""
+        K = self.K
+        mu = np.ascontiguousarray(mu, np.float64)
+        LF = np.asfortranarray(LambdaF, np.float64)
+        s = np.empty(K); prod = np.empty((K, K), order="F"); nrm = np.empty(1)
+        _lib.check(self.lib.bpmf_hip_tensor_sample(tensor.handle, int(mode), int(it), float(alpha), _ptr(mu), _ptr(LF), _ptr(s), _ptr(prod),
+                                                   _ptr(nrm)))
+        return s, prod, float(nrm[0])
+
+    def tensor_product(self, tensor, mode):
+        """[nnz, ld] array: row e holds the Khatri-Rao row of the entry at position e of the mode's order (the entries sorted stably
+        by their index in that mode), as the mode's next sampler launch would read it; columns K .. ld - 1 are the zero padding."""
+        out = np.empty((max(tensor.nnz, 1), self.ld()), np.float64)
+        _lib.check(self.lib.bpmf_hip_tensor_product(tensor.handle, int(mode), _ptr(out)))
+        return out[:tensor.nnz]
+
+    def tensor_product_run(self, tensor, mode):
+        """Runs the Khatri-Rao kernel of a mode and waits, without the copy to the host (measurements)."""
+        _lib.check(self.lib.bpmf_hip_tensor_product(tensor.handle, int(mode), None))
+
+    def tensor_last_ms(self, tensor):
+        """Device time in ms of the newest Khatri-Rao launch of a mode of the tensor (waits for it)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_tensor_last_ms(tensor.handle, C.byref(ms)))
+        return ms.value
+
+    def tensor_test(self, tensor, idx, vals):
+        """The test entries of a tensor (idx [n, 3] 0-based, vals [n]) for tensor_predict."""
+        cols, v, n = self._tensor_entries("tensor_test", idx, vals)
+        h = C.c_void_p()
+        _lib.check(self.lib.bpmf_hip_tensor_test_create(tensor.handle, n, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(v), C.byref(h)))
+        tt = [h, n, tensor]
+        tensor.tests.append(tt)
+        return tt
+
+    def tensor_test_destroy(self, test):
+        if test[0]:
+            _lib.check(self.lib.bpmf_hip_tensor_test_destroy(test[0]))
+            test[0] = None
+
+    def tensor_predict(self, test, n):
+        """(se, se_avg, count) of the test entries against the current factors; n as in predict (0 during burn-in, then the number
+        of samples already averaged)."""
+        se = C.c_double(); sea = C.c_double(); cnt = C.c_int64()
+        _lib.check(self.lib.bpmf_hip_tensor_predict(test[0], int(n), C.byref(se), C.byref(sea), C.byref(cnt)))
+        return se.value, sea.value, cnt.value
+
+    def tensor_test_get(self, test):
+        """(Pavg, Pm2) of the test entries, in the order they were passed."""
+        pavg = np.empty(max(test[1], 1)); pm2 = np.empty(max(test[1], 1))
+        _lib.check(self.lib.bpmf_hip_tensor_test_get(test[0], _ptr(pavg), _ptr(pm2)))
+        return pavg[:test[1]], pm2[:test[1]]
 
     # -- side information ---------------------------------------------------------
     def set_features(self, side, F, lambda_beta=5.0, tag=3):

@@ -532,6 +532,57 @@ BPMF_API int bpmf_hip_side_robust_add(bpmf_hip_side *side);
  * nothing added: BPMF_HIP_EINVAL. */
 BPMF_API int bpmf_hip_side_robust_get(bpmf_hip_side *side, double *wmean_host, int *count, double *nu);
 
+/* ---- sparse tensor factorisation: Bayesian CP of order 3 -------------------------------
+ * A tensor of ratings r(i, j, t) -- compound x target x assay type, user x movie x time -- is modelled as
+ *     r(i, j, t) ~ N(mean_rating + sum_k a_ik b_jk c_tk, 1 / alpha),   a Normal-Wishart prior per mode.
+ * The conditional of one factor row of a mode is the column update of the matrix model with the other side's row replaced by the
+ * Hadamard product of the other two modes' rows, p_e = b_j o c_t: Lambda* = Lambda + alpha sum_e p_e p_e^T,
+ * b = Lambda mu + alpha sum_e (r_e - mean_rating) p_e.  So every mode is an ordinary side whose ratings are the tensor's entries in
+ * the order of the mode's index, entry e rating row e of a matrix P (ld x nnz fp64, ld = bpmf_hip_ctx_ld) that k_khatri_rao rebuilds
+ * ahead of every one of the mode's sampler launches; the samplers are the matrix model's.  DESIGN.md section 22 has the layout and
+ * what it costs.
+ *
+ * bpmf_hip_tensor_create takes nnz entries as three 0-based index arrays and their values, in any order.  Per mode m it sorts the
+ * entries stably by their mode-m index (ties keep the caller's order: that fixes the samplers' summation order) and creates a side
+ * with dims[m] columns and nnz rows, schedule, chunks and gather stream as for any side.  Device memory: ld * nnz * 8 bytes for P
+ * (one buffer, shared by the three modes), per mode 2 * 4 * nnz bytes of indices, 8 * nnz of values and 4 * nnz of row ids, the
+ * mode's two factor copies and, at ld <= 32, its gather stream (16 bytes per entry).
+ * BPMF_HIP_EINVAL, before anything is enqueued: nmodes != 3, a size outside 1 .. 2^31-1, nnz outside 0 .. 2^31-1 (the samplers' row
+ * ids are 32-bit), an index out of range or a value that is not finite (the first such entry is named, 1-based), a cell listed twice
+ * (named in 1-based indices, with the two entries), an fp32 context, a context with a communicator.
+ * A mode's side (bpmf_hip_tensor_side) serves bpmf_hip_side_get_items / _set_items, the sample ring, _aggr_add / _aggr_finalize,
+ * _kernel_name and _schedule_info; it belongs to the tensor and is not destroyed by the caller.  A mode that was given a probit
+ * likelihood, censored ratings, weights, Student-t noise, features, propagated priors or the BPMF_REDUCE formulation is refused by
+ * bpmf_hip_tensor_sample.  Destroy a tensor's test sets before the tensor. */
+typedef struct bpmf_hip_tensor bpmf_hip_tensor;
+typedef struct bpmf_hip_tensor_test bpmf_hip_tensor_test;
+BPMF_API int bpmf_hip_tensor_create(bpmf_hip_ctx *ctx, int nmodes, const int64_t *dims, int64_t nnz, const int32_t *idx0, const int32_t *idx1,
+                                    const int32_t *idx2, const double *vals, double mean_rating, bpmf_hip_tensor **out);
+BPMF_API int bpmf_hip_tensor_destroy(bpmf_hip_tensor *tensor);
+BPMF_API bpmf_hip_side *bpmf_hip_tensor_side(bpmf_hip_tensor *tensor, int mode);
+/* One blocking half-iteration of mode `mode` (0 .. 2): k_khatri_rao writes the mode's rows of P from the current factors of the two
+ * other modes, then the mode's sampler runs behind it in the same queue, as bpmf_hip_sample_side (same arguments, same sums, same
+ * error codes: BPMF_HIP_ECHOL with bpmf_hip_failed_column of the mode's side).  `iter` is the iteration number, the same value for
+ * every mode of an iteration, as the matrix loop passes it for both sides. */
+BPMF_API int bpmf_hip_tensor_sample(bpmf_hip_tensor *tensor, int mode, int iter, double alpha, const double *mu, const double *LambdaF,
+                                    double *sum_out, double *prod_out, double *norm_out);
+/* The rows of P the next sampler launch of `mode` would read: runs k_khatri_rao and copies ld x nnz doubles (column e: the entry at
+ * position e of the mode's order; rows num_latent .. ld - 1 zero) to the host; out_host = NULL: runs the kernel and waits, no copy.
+ * For tests, debugging and measurements. */
+BPMF_API int bpmf_hip_tensor_product(bpmf_hip_tensor *tensor, int mode, double *out_host);
+/* Device time of the newest k_khatri_rao launch of a mode (bpmf_hip_tensor_sample, _product), from events on its dispatch packet;
+ * waits for it.  0 before the first launch.  The sampler behind it: bpmf_hip_side_last_kernel_ms of the mode's side. */
+BPMF_API int bpmf_hip_tensor_last_ms(bpmf_hip_tensor *tensor, float *khatri_rao_ms);
+/* Test entries of a tensor: entry q is predicted as mean_rating + c_t . (a_i o b_j).  bpmf_hip_tensor_predict writes the entries'
+ * Khatri-Rao rows over the first two modes with k_khatri_rao and evaluates them against the last mode with the evaluation kernel of
+ * bpmf_hip_predict: Pavg / Pm2 / n and the returned sums are that call's.  bpmf_hip_tensor_test_get returns Pavg and Pm2 in the
+ * order the entries were passed (either pointer may be NULL). */
+BPMF_API int bpmf_hip_tensor_test_create(bpmf_hip_tensor *tensor, int64_t nnz, const int32_t *idx0, const int32_t *idx1, const int32_t *idx2,
+                                         const double *vals, bpmf_hip_tensor_test **out);
+BPMF_API int bpmf_hip_tensor_test_destroy(bpmf_hip_tensor_test *test);
+BPMF_API int bpmf_hip_tensor_predict(bpmf_hip_tensor_test *test, int n, double *se, double *se_avg, int64_t *count);
+BPMF_API int bpmf_hip_tensor_test_get(bpmf_hip_tensor_test *test, double *pavg, double *pm2);
+
 /* ---- side information: row / column features linked to the factor priors -----------
  * A side with N columns may carry a dense feature matrix F (N x D, fp64), a link matrix beta (D x K) and a fixed
  * lambda_beta > 0:

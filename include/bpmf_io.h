@@ -36,6 +36,13 @@ BPMF_IO_API int bpmf_io_write_sparse(const char *path, int64_t nrows, int64_t nc
 BPMF_IO_API int bpmf_io_read_dense(const char *path, int64_t *nrows, int64_t *ncols, double **data);
 BPMF_IO_API int bpmf_io_write_dense(const char *path, int64_t nrows, int64_t ncols, const double *data);
 BPMF_IO_API void bpmf_io_free(void *p);
+/* Sparse tensors of order 3 in the FROSTT .tns format (optionally .tns.gz): one entry per line, "i j t value", 1-based indices,
+ * whitespace-separated, lines starting with # are comments.  _read_tns returns the entries in file order with 0-based indices and
+ * dims[3] = the largest index seen per mode; it refuses a line with fewer or more than three indices, an index < 1, a value that is
+ * not finite and a cell listed twice (the message names the line(s); the cell in 1-based indices).  _write_tns writes the values as
+ * %.17g, so that a round trip is exact. */
+BPMF_IO_API int bpmf_io_read_tns(const char *path, int64_t *nnz, int64_t *dims, int32_t **idx0, int32_t **idx1, int32_t **idx2, double **vals);
+BPMF_IO_API int bpmf_io_write_tns(const char *path, int64_t nnz, const int32_t *idx0, const int32_t *idx1, const int32_t *idx2, const double *vals);
 
 /* Assignment of the columns of a side to `nparts` ranks (host; bpmf_amd/csrc/assign.cpp).
  * _greedy: Sys::assign of the reference (c++/assign.cpp:52-201, default weights): least-loaded rank on work = 10 + nnz,
