@@ -15,6 +15,7 @@ _SIGNATURES = {
     "bpmf_hip_last_error": (C.c_char_p, []),
     "bpmf_hip_abi_version": (C.c_int, []),
     "bpmf_hip_live_device_bytes": (C.c_int64, []),
+    "bpmf_hip_stream_drains": (C.c_int64, []),
     "bpmf_hip_supports_k": (C.c_int, [C.c_int]),
     "bpmf_hip_supports": (C.c_int, [C.c_int, C.c_int]),
     "bpmf_hip_kernel_k": (C.c_int, [C.c_int, C.c_int]),
@@ -93,6 +94,15 @@ _SIGNATURES = {
     "bpmf_hip_test_probit_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_test_probit_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "bpmf_hip_auc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_ordinal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
+    "bpmf_hip_side_ordinal_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int64)]),
+    "bpmf_hip_side_ordinal_latent": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_ordinal_cut_get": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_ordinal_cut_set": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_ordinal_loglik": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_ordinal_cut_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int)]),
+    "bpmf_hip_test_ordinal_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_test_ordinal_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bpmf_hip_side_set_censored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
     "bpmf_hip_side_censored_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bpmf_hip_side_censored_latent": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -25,6 +25,11 @@
 // likelihood: mean rating 0, alpha 1, latent scores redrawn on the device ahead of every sampler launch.
 // After "Final Avg RMSE" the run prints "Final AUC" and "Final Brier" of the posterior-mean probabilities of the test entries,
 // and -o DIR also gets DIR/probit.csv (row,col,label,prob).  Without these flags nothing changes.
+// --ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F] (one GPU, no -g): the ratings are ordered
+// categories under the ordinal probit likelihood: mean rating 0, alpha 1, latent scores between the cutpoints
+// of their level redrawn on the device ahead of every sampler launch, the cutpoints sampled by one Metropolis-Hastings step per
+// iteration (or fixed).  After "Final Avg RMSE" the run prints "Final ordinal RMSE", "Final accuracy" and "Final log-prob" over the
+// test entries, and -o DIR also gets DIR/ordinal.csv (row,col,value,expected,p1..pC) and DIR/cutpoints.csv (iteration,accepted,step,g1..).
 // --new-row-features FILE / --new-col-features FILE (with the matching --row-features / --col-features, -o DIR, -i > -b): users /
 // movies that are NOT in the training matrix, predicted from their features alone: DIR/new-rows-mean.ddm,
 // new-rows-std.ddm (new x movies), new-cols-mean.ddm, new-cols-std.ddm (users x new); with --topn N also DIR/new-rows-topn.csv /
@@ -96,7 +101,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--censored FILE] [--weights FILE] [--robust NU] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "       bpmf --tensor <TNS> [--tensor-test <TNS>] [--tensor-dims I,J,T] [-o DIR/] [-i N] [-b N] [-a F] [-d K]\n"
               << "\n"
               << "Parameters:\n"
@@ -160,6 +165,16 @@ void usage()
               << "              first draws are large (the chain starts at beta = 0): give the burn-in (-b) some tens of iterations.  With\n"
               << "              -o DIR the value every iteration used goes to DIR/lambda_beta.csv (iteration,lambda_rows,lambda_cols)\n"
               << "  [--probit-threshold F]: the threshold between negative and positive labels (0.5)\n"
+              << "  [--ordinal]: ordinal probit likelihood for ordered categories (star ratings): the ratings take one of 2 .. 16 levels, a\n"
+              << "              rating at level c has a latent score between the cutpoints g_{c-1} and g_c, which are sampled too (Metropolis-\n"
+              << "              Hastings, one pass over the ratings per iteration); mean rating 0, alpha 1; prints Final ordinal RMSE / Final\n"
+              << "              accuracy / Final log-prob over the test matrix, -o DIR also gets DIR/ordinal.csv and DIR/cutpoints.csv (one GPU,\n"
+              << "              no -g; not with --probit, --tensor, --weights, --robust, --censored, --fold-in-*, --noise adaptive, --row-features /\n"
+              << "              --col-features, -m / -l or BPMF_REDUCE=1)\n"
+              << "  [--ordinal-levels a,b,..]: the level values, increasing (default: the distinct training values)\n"
+              << "  [--ordinal-cutpoints g1,..]: fixed cutpoints, one fewer than the levels (default: sampled, from Phi^-1 of the level frequencies)\n"
+              << "  [--ordinal-step F]: the proposal step of the cutpoints (default: 1 / sqrt(nnz), adapted towards 35 % acceptance in the burn-in;\n"
+              << "              start, target and schedule are defaults, not tuned numbers)\n"
               << "  [--censored FILE]: training cells whose value is only a bound: a sparse matrix of the training matrix's shape (.sdm,\n"
               << "              coordinate .mtx, .sbm = all lower bounds; optional .gz), an entry > 0 = the true value is at least the recorded\n"
               << "              one, < 0 = at most; every entry must be a cell of the training matrix.  The latent values of these cells are\n"
@@ -326,6 +341,12 @@ struct Job {
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
     bool probit = false;                                             // --probit
     double probit_threshold = 0.5;                                   // --probit-threshold F
+    bool ordinal = false, ord_fixed = false, ord_step_given = false; // --ordinal, --ordinal-cutpoints (fixed), --ordinal-step F
+    std::vector<double> ord_levels, ord_cut0;                        // the C level values; the C - 1 initial cutpoints (empty: the library's default)
+    double ord_step = 0.0;                                           // the proposal step of the cutpoints (0: 1 / sqrt(nnz), adapted in the burn-in)
+    std::vector<double> ord_trace, ord_step_trace, cat_prob;         // per iteration its C - 1 cutpoints and its step; test entries x C probabilities
+    std::vector<int> ord_accepted;                                   // per iteration: was its proposal accepted
+    double ord_rmse = NAN, ord_accuracy = NAN, ord_logp = NAN;
     bool censored = false;                                           // --censored FILE
     std::vector<int8_t> cens_m, cens_u;                              // the flags of every rating of M / Mt (0, +1 lower bound, -1 upper bound)
     int64_t cens_right = 0, cens_left = 0;
@@ -402,6 +423,13 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.probit) {                                                  // (streams: tag 1 = movies, 2 = users)
         check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
         check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
+    }
+    if (J.ordinal) {                                                 // (streams: tag 11 = movies, 12 = users); both sides hold the same cutpoints
+        const int C = (int)J.ord_levels.size();
+        check(bpmf_hip_side_set_ordinal(movies, J.ord_levels.data(), C, J.ord_fixed ? J.ord_cut0.data() : nullptr, 11));
+        J.ord_cut0.resize((size_t)C - 1);
+        check(bpmf_hip_side_ordinal_cut_get(movies, J.ord_cut0.data()));
+        check(bpmf_hip_side_set_ordinal(users, J.ord_levels.data(), C, J.ord_cut0.data(), 12));
     }
     if (J.censored) {                                                // (streams: tag 5 = movies, 6 = users)
         check(bpmf_hip_side_set_censored(movies, J.cens_m.data(), 5));
@@ -510,6 +538,14 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.probit)
         os << "likelihood: probit, a rating > " << J.probit_threshold << " is a positive label; the RMSE columns compare the latent score "
               "with the raw label and are not an error measure" << std::endl;
+    if (J.ordinal) {
+        os << "likelihood: ordinal probit, " << J.ord_levels.size() << " levels ";
+        for (size_t k = 0; k < J.ord_levels.size(); ++k) os << (k ? "," : "") << J.ord_levels[k];
+        os << "; cutpoints ";
+        for (size_t k = 0; k < J.ord_cut0.size(); ++k) os << (k ? "," : "") << J.ord_cut0[k];
+        os << (J.ord_fixed ? " (fixed)" : " (sampled)") << "; the RMSE columns compare the latent score with the raw value and are not an error measure"
+           << std::endl;
+    }
     if (J.censored)
         os << "censored: " << J.cens_right << " lower bounds, " << J.cens_left << " upper bounds of " << J.M.nnz() << " training ratings" << std::endl;
     if (J.weighted)
@@ -566,6 +602,24 @@ void rank_main(Job &J, int rank, std::ostream &os)
         J.train_rmse.push_back(std::sqrt(sse / (double)n));
         if (i + 1 < nsims) check(bpmf_hip_noise_sample(J.a0, J.b0, sse, n, i, J.alpha_max, &alpha));
     };
+    // --ordinal, after both sides of iteration i: the Metropolis-Hastings step of the cutpoints of iteration i + 1 (one pass over the
+    // training ratings on the device, the rest on the host; the pipelined loop waits here once per iteration, as adapt does).  The
+    // step size follows log s += (accepted - 0.35) / sqrt(iter + 1) during the burn-in unless --ordinal-step gave it.
+    const bool ordinal_eval = J.ordinal && J.T.nnz() > 0;
+    double ord_s = J.ord_step_given ? J.ord_step : 1.0 / std::sqrt((double)std::max<int64_t>(J.M.nnz(), 1));
+    std::vector<double> ord_cut = J.ord_cut0;
+    if (J.ordinal && nsims > 0) { J.ord_trace = ord_cut; J.ord_accepted.push_back(0); J.ord_step_trace.push_back(ord_s); }
+    auto cut = [&](int i) {
+        if (i + 1 >= nsims) return;
+        int acc = 0;
+        if (!J.ord_fixed) {
+            check(bpmf_hip_ordinal_cut_step(movies, users, i + 1, ord_s, &acc));
+            if (acc) check(bpmf_hip_side_ordinal_cut_get(movies, ord_cut.data()));
+        }
+        J.ord_accepted.push_back(acc); J.ord_step_trace.push_back(ord_s);
+        J.ord_trace.insert(J.ord_trace.end(), ord_cut.begin(), ord_cut.end());
+        if (!J.ord_fixed && !J.ord_step_given && i + 1 < burnin) ord_s = std::exp(std::log(ord_s) + ((acc ? 1.0 : 0.0) - 0.35) / std::sqrt((double)(i + 2)));
+    };
     // a model with side information steps both sides through the blocking half-iteration
     auto sample = [&](bpmf_hip_side *a, bpmf_hip_side *b) { check(linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha)); };
     if (J.odirname.empty() && !J.verbose && !linked) {
@@ -579,6 +633,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_sys_sample(users, movies, alpha));   // users.sample(movies)
             if (J.adaptive) adapt(i);
             if (probit_eval && i >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
+            if (ordinal_eval && i >= burnin) check(bpmf_hip_test_ordinal_add(test, movies, users));
+            if (J.ordinal) cut(i);
             if (i > 0) {
                 // norms of iteration i-1 (bpmf_hip_sys_norm waits for THAT half-iteration's sums only: asking bpmf_hip_sys_state
                 // here drained each side's pipeline once per iteration -- 83 M against the 100 M samples/s of the same loop
@@ -611,6 +667,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
         sample(movies, users);                                  // movies.sample(users)
         sample(users, movies);                                  // users.sample(movies)
         if (J.adaptive) adapt(i);
+        if (ordinal_eval && i >= burnin) check(bpmf_hip_test_ordinal_add(test, movies, users));
+        if (J.ordinal) cut(i);
         iter = i;
         const int n = (iter < burnin) ? 0 : (iter - burnin);
         check(bpmf_hip_predict_launch(test, movies, users, n));
@@ -705,6 +763,27 @@ void rank_main(Job &J, int rank, std::ostream &os)
         }
         check(bpmf_hip_auc(J.prob.data(), label.data(), (int64_t)label.size(), 0.5, &J.auc));
         J.brier = sq / (double)label.size();
+    }
+    if (ordinal_eval && nsims > burnin) {                            // one rank (main refuses -g)
+        const size_t C = J.ord_levels.size(), n = (size_t)J.T.nnz();
+        J.cat_prob.resize(n * C);
+        check(bpmf_hip_test_ordinal_get(test, J.cat_prob.data(), nullptr, nullptr));
+        double sq = 0.0, lp = 0.0;
+        size_t hit = 0;
+        for (size_t q = 0; q < n; ++q) {
+            const double *p = &J.cat_prob[q * C];
+            double e = 0.0;
+            size_t best = 0, truth = 0;
+            for (size_t k = 0; k < C; ++k) {
+                e += J.ord_levels[k] * p[k];
+                if (p[k] > p[best]) best = k;
+                if (J.ord_levels[k] == J.T.vals[q]) truth = k;
+            }
+            sq += (e - J.T.vals[q]) * (e - J.T.vals[q]);
+            hit += best == truth;
+            lp += std::log(p[truth]);
+        }
+        J.ord_rmse = std::sqrt(sq / (double)n); J.ord_accuracy = (double)hit / (double)n; J.ord_logp = lp / (double)n;
     }
     if (J.topn > 0) {                                                // one rank (main refuses -g > 1)
         const double t0 = tick();
@@ -902,6 +981,8 @@ int main(int argc, char *argv[])
                                               {"topn-score", required_argument, nullptr, 1017}, {"topn-kappa", required_argument, nullptr, 1018},
                                               {"topn-threshold", required_argument, nullptr, 1019},
                                               {"fold-in-rows", required_argument, nullptr, 1020}, {"fold-in-cols", required_argument, nullptr, 1021},
+                                              {"ordinal", no_argument, nullptr, 1050}, {"ordinal-levels", required_argument, nullptr, 1051},
+                                              {"ordinal-cutpoints", required_argument, nullptr, 1052}, {"ordinal-step", required_argument, nullptr, 1053},
                                               {"tensor", required_argument, nullptr, 1040}, {"tensor-test", required_argument, nullptr, 1041},
                                               {"tensor-dims", required_argument, nullptr, 1042},
                                               {nullptr, 0, nullptr, 0}};
@@ -910,6 +991,8 @@ int main(int argc, char *argv[])
     bool topn_kappa_given = false, topn_threshold_given = false;
     bool alpha_given = false, threshold_given = false;
     std::string tensor_file, tensor_test, tensor_dims;
+    std::string ordinal_levels, ordinal_cutpoints, ordinal_step;
+    bool ordinal_levels_given = false, ordinal_cutpoints_given = false;
     bool tensor_given = false, tensor_test_given = false, tensor_dims_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
@@ -938,6 +1021,10 @@ int main(int argc, char *argv[])
         case 1019: topn_threshold = optarg; topn_threshold_given = true; break;
         case 1020: fold_in_rows = optarg; break;
         case 1021: fold_in_cols = optarg; break;
+        case 1050: J.ordinal = true; break;
+        case 1051: ordinal_levels = optarg; ordinal_levels_given = true; break;
+        case 1052: ordinal_cutpoints = optarg; ordinal_cutpoints_given = true; break;
+        case 1053: ordinal_step = optarg; J.ord_step_given = true; break;
         case 1040: tensor_file = optarg; tensor_given = true; break;
         case 1041: tensor_test = optarg; tensor_test_given = true; break;
         case 1042: tensor_dims = optarg; tensor_dims_given = true; break;
@@ -969,6 +1056,7 @@ int main(int argc, char *argv[])
         if (!mname.empty() || !lname.empty()) die("--tensor does not go together with a propagated posterior (-m / -l)");
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--tensor does not go together with BPMF_REDUCE=1");
         if (J.probit || threshold_given) die("--tensor does not go together with --probit");
+        if (J.ordinal || ordinal_levels_given || ordinal_cutpoints_given || J.ord_step_given) die("--tensor does not go together with --ordinal");
         if (J.censored) die("--tensor does not go together with --censored");
         if (J.weighted) die("--tensor does not go together with --weights");
         if (J.robust) die("--tensor does not go together with --robust");
@@ -1018,8 +1106,8 @@ int main(int argc, char *argv[])
         if (thr) {
             J.topn_kind = topn_score == "prob" ? BPMF_HIP_SCORE_PROB : BPMF_HIP_SCORE_EI;
             J.topn_param = number(topn_threshold, "--topn-threshold");
-            if (!J.probit && !(J.alpha > 0.0 && std::isfinite(J.alpha))) die("--topn-score " + topn_score + " needs a finite -a > 0 (sigma = 1 / sqrt(alpha))");
-            J.topn_sigma = J.probit ? 1.0 : 1.0 / std::sqrt(J.alpha);
+            if (!J.probit && !J.ordinal && !(J.alpha > 0.0 && std::isfinite(J.alpha))) die("--topn-score " + topn_score + " needs a finite -a > 0 (sigma = 1 / sqrt(alpha))");
+            J.topn_sigma = (J.probit || J.ordinal) ? 1.0 : 1.0 / std::sqrt(J.alpha);
         }
     }
     if (!J.adaptive && (!alpha_prior.empty() || !alpha_max.empty())) die("--alpha-prior and --alpha-max need --noise adaptive");
@@ -1058,6 +1146,57 @@ int main(int argc, char *argv[])
                            "sharded side are not drawn)");
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--probit does not go together with BPMF_REDUCE=1");
         if (alpha_given && J.alpha != 1.0) die("--probit runs with alpha = 1: -a " + std::to_string(J.alpha) + " is not supported");
+        J.alpha = 1.0;
+    }
+    // --ordinal / --ordinal-levels / --ordinal-cutpoints / --ordinal-step: checked before anything touches a GPU (the values of the
+    // matrices below, once they are read)
+    if ((ordinal_levels_given || ordinal_cutpoints_given || J.ord_step_given) && !J.ordinal)
+        die(std::string(ordinal_levels_given ? "--ordinal-levels" : ordinal_cutpoints_given ? "--ordinal-cutpoints" : "--ordinal-step") + " needs --ordinal");
+    if (J.ordinal) {
+        auto number_list = [&](const std::string &text, const char *flag) {
+            std::vector<double> v;
+            const char *p = text.c_str();
+            for (;;) {
+                char *e = nullptr;
+                const double x = strtod(p, &e);
+                if (e == p || !std::isfinite(x) || (*e != ',' && *e != '\0')) die(std::string(flag) + " expects finite numbers separated by commas, not '" + text + "'");
+                v.push_back(x);
+                if (*e == '\0') break;
+                p = e + 1;
+            }
+            for (size_t k = 1; k < v.size(); ++k) if (!(v[k] > v[k - 1])) die(std::string(flag) + " expects strictly increasing numbers, not '" + text + "'");
+            return v;
+        };
+        if (ordinal_levels_given) {
+            J.ord_levels = number_list(ordinal_levels, "--ordinal-levels");
+            if (J.ord_levels.size() < 2 || J.ord_levels.size() > 16) die("--ordinal-levels expects 2 .. 16 levels, not " + std::to_string(J.ord_levels.size()));
+        }
+        if (ordinal_cutpoints_given) {
+            J.ord_cut0 = number_list(ordinal_cutpoints, "--ordinal-cutpoints");
+            J.ord_fixed = true;
+            if (ordinal_levels_given && J.ord_cut0.size() + 1 != J.ord_levels.size())
+                die("--ordinal-cutpoints expects " + std::to_string(J.ord_levels.size() - 1) + " cutpoints for " + std::to_string(J.ord_levels.size()) + " levels");
+        }
+        if (J.ord_step_given) {
+            char *e = nullptr;
+            J.ord_step = strtod(ordinal_step.c_str(), &e);
+            if (e == ordinal_step.c_str() || *e != '\0' || !std::isfinite(J.ord_step) || !(J.ord_step > 0.0))
+                die("--ordinal-step expects a number F > 0, not '" + ordinal_step + "'");
+            if (J.ord_fixed) die("--ordinal-step does not go together with --ordinal-cutpoints (fixed cutpoints are not proposed)");
+        }
+        if (J.probit || threshold_given) die("--ordinal does not go together with --probit (a side has one likelihood)");
+        if (J.adaptive) die("--ordinal does not go together with --noise adaptive (the latent scores have unit variance)");
+        if (ngpu >= 1) die("--ordinal runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the latent scores of a "
+                           "sharded side are not drawn)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--ordinal does not go together with BPMF_REDUCE=1");
+        if (alpha_given && J.alpha != 1.0) die("--ordinal runs with alpha = 1: -a " + std::to_string(J.alpha) + " is not supported");
+        if (!mname.empty() || !lname.empty()) die("--ordinal does not go together with a propagated posterior (-m / -l)");
+        if (!row_features.empty() || !col_features.empty()) die("--ordinal does not go together with --row-features / --col-features");
+        if (J.censored) die("--ordinal does not go together with --censored (levels have no bounds)");
+        if (J.weighted) die("--ordinal does not go together with --weights (the latent scores have unit variance)");
+        if (J.robust) die("--ordinal does not go together with --robust (the latent scores have unit variance)");
+        if (!fold_in_rows.empty() || !fold_in_cols.empty())
+            die("--ordinal does not go together with --fold-in-rows / --fold-in-cols (levels would need a latent iteration of their own)");
         J.alpha = 1.0;
     }
     // --row-features / --col-features / --lambda-beta: checked before anything touches a GPU
@@ -1265,6 +1404,24 @@ int main(int argc, char *argv[])
     for (double v : J.Mt.vals) usum += v;
     J.mean_m = msum / (double)J.M.nnz(); J.mean_u = usum / (double)J.Mt.nnz();
     if (J.probit) J.mean_m = J.mean_u = 0.0;                    // labels, not measurements: the latent scores are centred at 0
+    if (J.ordinal) {                                            // levels, not measurements; still before anything touches a GPU
+        J.mean_m = J.mean_u = 0.0;
+        if (J.ord_levels.empty()) {                             // the distinct training values
+            std::vector<double> v(J.M.vals);
+            std::sort(v.begin(), v.end());
+            v.erase(std::unique(v.begin(), v.end()), v.end());
+            if (v.size() < 2 || v.size() > 16)
+                die("--ordinal: the training matrix has " + std::to_string(v.size()) + " distinct values (2 .. 16 levels are supported; --ordinal-levels names them)");
+            for (double x : v) if (!std::isfinite(x)) die("--ordinal: a training value is not finite");
+            J.ord_levels = v;
+        }
+        if (J.ord_fixed && J.ord_cut0.size() + 1 != J.ord_levels.size())
+            die("--ordinal-cutpoints expects " + std::to_string(J.ord_levels.size() - 1) + " cutpoints for " + std::to_string(J.ord_levels.size()) + " levels");
+        for (double x : J.M.vals)
+            if (!std::binary_search(J.ord_levels.begin(), J.ord_levels.end(), x)) die("--ordinal: the training value " + std::to_string(x) + " is not one of the levels");
+        for (double x : J.T.vals)
+            if (!std::binary_search(J.ord_levels.begin(), J.ord_levels.end(), x)) die("--ordinal: the test value " + std::to_string(x) + " is not one of the levels");
+    }
 
     auto read_features = [&](const std::string &name, int64_t n, const char *what, Dense &F) {
         if (name.empty()) return;
@@ -1607,8 +1764,47 @@ int main(int argc, char *argv[])
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/probit.csv");
     }
 
+    if (J.ordinal && !J.odirname.empty()) {
+        const size_t C = J.ord_levels.size();
+        if (!J.cat_prob.empty()) {                                   // test-set order of T, 1-based ids in the ORIGINAL numbering
+            FILE *f = fopen((J.odirname + "/ordinal.csv").c_str(), "w");
+            if (!f) die("cannot write " + J.odirname + "/ordinal.csv");
+            fprintf(f, "row,col,value,expected");
+            for (size_t k = 0; k < C; ++k) fprintf(f, ",p%zu", k + 1);
+            fprintf(f, "\n");
+            for (int64_t c = 0; c < J.T.ncols; ++c)
+                for (int64_t q = J.T.colptr[(size_t)c]; q < J.T.colptr[(size_t)c + 1]; ++q) {
+                    const int64_t r = J.T.rowidx[(size_t)q];
+                    const double *p = &J.cat_prob[(size_t)q * C];
+                    double e = 0.0;
+                    for (size_t k = 0; k < C; ++k) e += J.ord_levels[k] * p[k];
+                    fprintf(f, "%lld,%lld,%.17g,%.17g", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                            (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.T.vals[(size_t)q], e);
+                    for (size_t k = 0; k < C; ++k) fprintf(f, ",%.17g", p[k]);
+                    fprintf(f, "\n");
+                }
+            if (fclose(f) != 0) die("cannot write " + J.odirname + "/ordinal.csv");
+        }
+        FILE *f = fopen((J.odirname + "/cutpoints.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/cutpoints.csv");
+        fprintf(f, "iteration,accepted,step");
+        for (size_t k = 1; k < C; ++k) fprintf(f, ",g%zu", k);
+        fprintf(f, "\n");
+        for (size_t i = 0; i < J.ord_accepted.size(); ++i) {
+            fprintf(f, "%zu,%d,%.17g", i, J.ord_accepted[i], J.ord_step_trace[i]);
+            for (size_t k = 0; k + 1 < C; ++k) fprintf(f, ",%.17g", J.ord_trace[i * (C - 1) + k]);
+            fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/cutpoints.csv");
+    }
+
     os << "Total time: " << J.elapsed << std::endl;
     os << "Final Avg RMSE: " << J.rmse_avg << std::endl;
+    if (J.ordinal && !J.cat_prob.empty()) {
+        os << "Final ordinal RMSE: " << J.ord_rmse << std::endl;
+        os << "Final accuracy: " << J.ord_accuracy << std::endl;
+        os << "Final log-prob: " << J.ord_logp << std::endl;
+    }
     if (J.probit && !J.prob.empty()) {
         os << "Final AUC: " << J.auc << std::endl;
         os << "Final Brier: " << J.brier << std::endl;

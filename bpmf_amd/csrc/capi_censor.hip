@@ -38,6 +38,7 @@ extern "C" int bpmf_hip_side_set_censored(bpmf_hip_side *s, const int8_t *flags,
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
     if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with propagated priors");
+    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_censored: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     int rc = require_single_gpu("side_set_censored", c, s);
     if (rc) return rc;

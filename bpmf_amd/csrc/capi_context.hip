@@ -89,6 +89,7 @@ int comm_abort(bpmf_hip_ctx *c, const std::string &what)
 // hipStreamSynchronize for a stream that may carry a collective: a poll with a deadline instead of a wait without one
 int bounded_stream_sync(bpmf_hip_ctx *c, hipStream_t st, const char *what)
 {
+    if (st == c->stream) g_stream_drains.fetch_add(1, std::memory_order_relaxed);
     if (!c->comm) { HIP_TRY(hipStreamSynchronize(st)); return 0; }
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 0;; ++spins) {

@@ -10,6 +10,7 @@
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
+//   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
 //   capi_robust.hip    Student-t noise: the weights of a side redrawn on the device ahead of every sampler launch, their posterior mean
@@ -61,10 +62,13 @@ int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
 int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a censored side
 // Student-t noise (capi_robust.hip)
 int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a robust side
-// the latent kernel of a probit, a censored or a robust side, whichever `self` is (a side is at most one of them)
+// ordinal probit likelihood (capi_ordinal.hip)
+int ordinal_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);  // ahead of the sampler of an ordinal side
+// the latent kernel of a probit, an ordinal, a censored or a robust side, whichever `self` is (a side is at most one of them)
 inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
 {
     return self->probit ? probit_latent_enqueue(self, other, iter, alpha, st)
+           : self->ordinal ? ordinal_latent_enqueue(self, other, iter, alpha, st)
            : self->censor ? censor_latent_enqueue(self, other, iter, alpha, st) : robust_latent_enqueue(self, other, iter, alpha, st);
 }
 

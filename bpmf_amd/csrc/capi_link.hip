@@ -144,6 +144,7 @@ int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, 
     if (rc) return rc;
     if (s->reduce_on) return fail(BPMF_HIP_EINVAL, w + ": not together with the BPMF_REDUCE formulation");
     if (s->probit) return fail(BPMF_HIP_EINVAL, w + ": not on a probit side");
+    if (s->ordinal) return fail(BPMF_HIP_EINVAL, w + ": not on an ordinal side");
     if (s->censor) return fail(BPMF_HIP_EINVAL, w + ": not on a censored side (the residuals would have to be formed from the latent values)");
     if (s->robust) return fail(BPMF_HIP_EINVAL, w + ": not on a side with Student-t noise (bpmf_hip_side_set_robust)");
     if (s->weights) return fail(BPMF_HIP_EINVAL, w + ": not on a side with per-rating weights (bpmf_hip_side_set_weights)");

@@ -35,6 +35,7 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
     if (!s) return fail(BPMF_HIP_EINVAL, "side_set_probit: NULL");
     bpmf_hip_ctx *c = s->ctx;
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
+    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with features (bpmf_hip_side_set_features)");
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a censored side (bpmf_hip_side_set_censored)");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a side with Student-t noise (bpmf_hip_side_set_robust)");

@@ -48,6 +48,7 @@ extern "C" int bpmf_hip_side_set_robust(bpmf_hip_side *s, double nu, unsigned ta
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a probit side (bpmf_hip_side_set_probit)");
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a censored side (bpmf_hip_side_set_censored)");
+    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with features (bpmf_hip_side_set_features)");
     if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with propagated priors");
     if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with the BPMF_REDUCE formulation");

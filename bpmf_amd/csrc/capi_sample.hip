@@ -28,7 +28,7 @@ int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, do
     // stateful path has enqueued the kernel already, ahead of its wait for the gate kernel (bpmf_hip_sys_sample).
     // censored side: the same for the latent values of its censored entries (capi_censor.hip).
     // robust side: the same for its per-rating weights (capi_robust.hip).
-    if ((self->probit || self->censor || self->robust) && !self->probit_latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
+    if ((self->probit || self->ordinal || self->censor || self->robust) && !self->probit_latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
     int rc = claim_second_copy(self, st);
@@ -289,6 +289,7 @@ int read_result_blob(bpmf_hip_side *s, double *h_out, double *sum_out, double *p
     const int K = s->ctx->K, Kt = s->ctx->Kt;
     int rc = check_timeout(h_out, K, msg);
     if (!rc) rc = check_probit(s, msg);                   // (the latent kernel ran ahead of the sampler whose sums these are)
+    if (!rc) rc = check_ordinal(s, msg);
     if (!rc) rc = check_censor(s, msg);
     if (!rc) rc = check_robust(s, msg);
     if (rc) return rc;
@@ -760,7 +761,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     // before, directly ahead of the sampler launch that carries its own gate.  The latent kernel of a censored side and the weight
     // kernel of a robust side: likewise.
     self->probit_latent_queued = false;
-    if (self->probit || self->censor || self->robust) {
+    if (self->probit || self->ordinal || self->censor || self->robust) {
         if ((rc = latent_enqueue(self, other, iter, alpha, s0))) return rc;
         self->probit_latent_queued = true;
     }

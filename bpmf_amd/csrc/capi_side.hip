@@ -359,7 +359,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     if (s->own_items && s->d_items) (void)hipFree(s->d_items);
     if (s->d_items_alt) (void)hipFree(s->d_items_alt);
     if (s->d_prop) (void)hipFree(s->d_prop);
-    s->probit.reset(); s->censor.reset(); s->weights.reset(); s->robust.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
+    s->probit.reset(); s->ordinal.reset(); s->censor.reset(); s->weights.reset(); s->robust.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
     if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
     if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
     void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,
@@ -388,6 +388,7 @@ int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_si
 int ensure_colptr(bpmf_hip_side *s) { return s->d_colptr ? 0 : s->d_colptr.upload(s->h_colptr.data(), s->h_colptr.size()); }
 
 extern "C" int64_t bpmf_hip_live_device_bytes(void) { return g_live_bytes.load(std::memory_order_relaxed); }
+extern "C" int64_t bpmf_hip_stream_drains(void) { return g_stream_drains.load(std::memory_order_relaxed); }
 
 // ---- padded num_latent (ctx->Kt < ctx->K) -----------------------------------------------------
 // Everything that crosses the C ABI has the caller's size Kt; the device side has the instantiated size K.
@@ -412,6 +413,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
     (void)mu;
     if (Lambda && s->robust) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
     if (Lambda && s->weights) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
+    if (Lambda && s->ordinal) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }

@@ -15,6 +15,7 @@ extern "C" int bpmf_hip_side_set_weights(bpmf_hip_side *s, const double *w)
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a side with Student-t noise (bpmf_hip_side_set_robust redraws the weights itself)");
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a probit side (bpmf_hip_side_set_probit)");
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a censored side (bpmf_hip_side_set_censored)");
+    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with features (bpmf_hip_side_set_features)");
     if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with propagated priors");
     if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with the BPMF_REDUCE formulation");

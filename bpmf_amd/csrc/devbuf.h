@@ -7,6 +7,9 @@
 // live DevBuf / Pinned allocations of the process and the device bytes of the former (bpmf_hip_live_device_bytes): hipMemGetInfo
 // counts the whole card, other processes included
 inline std::atomic<int64_t> g_live_allocs{0}, g_live_bytes{0};
+// host waits for a context's main stream so far in this process (bounded_stream_sync; bpmf_hip_stream_drains): what a loop that
+// claims not to drain must leave unchanged
+inline std::atomic<int64_t> g_stream_drains{0};
 
 template <typename T>
 class DevBuf {

@@ -37,6 +37,17 @@ struct CgWork {
 // place), the sign of every rating, and a word the latent kernel raises to a rating position when a draw runs into its attempt cap
 struct bpmf_probit { DevBuf<double> z; DevBuf<int8_t> sign; Pinned<unsigned long long> fail; uint32_t tag = 0; };
 
+// ordinal probit likelihood (capi_ordinal.hip): the latent scores (layout of d_vals; the samplers read them in
+// its place), the level 0 .. C - 1 of every rating, the C level values, the cutpoint table -inf, g_1 .. g_{C-1}, +inf on the host and
+// two tables on the device (the current one and a proposal), the partials of the log-likelihood pass (2 x blocks, then the two sums),
+// and the word the latent kernel raises to a rating position whose dot product is not finite
+struct bpmf_ordinal {
+    DevBuf<double> z; DevBuf<uint8_t> level; DevBuf<double> g, g_prop, part;
+    Pinned<unsigned long long> fail; uint32_t tag = 0; int nlev = 0;
+    std::vector<double> levels, cut;                        // C values; C + 1 table entries
+    int64_t loglik_launches = 0;                            // log-likelihood passes enqueued so far (bpmf_hip_side_ordinal_info)
+};
+
 // censored ratings (capi_censor.hip): the censored entries of the side as compact lists (position in the CSC,
 // column, row, +1 = the rating is a lower bound / -1 = an upper bound), the latent values (layout of d_vals: a copy of the ratings
 // of which only the censored positions are ever rewritten; the samplers read it in place of d_vals), and the word the latent kernel

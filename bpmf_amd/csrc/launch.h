@@ -208,6 +208,34 @@ void probit_sign(const double *vals, int64_t nnz, double threshold, int8_t *sign
 int probit_latent(const ProbitLatentLaunch &p, hipStream_t st);  // -1: unsupported K (nothing launched)
 int probit_prob(const ProbitProbLaunch &p, hipStream_t st);
 
+// ordinal probit likelihood (kernels_ordinal.h, kordinal.hip)
+struct OrdinalLatentLaunch {
+    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
+    const int32_t *rowidx; const uint8_t *level; int64_t nnz;   // level: 0 .. nlev - 1 per rating
+    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    uint32_t iter, tag;
+    const double *g; int nlev;                             // the cutpoint table on the device: -inf, g_1 .. g_{C-1}, +inf (nlev + 1 doubles)
+    double *z;                                             // the latent scores, layout of the side's ratings
+    unsigned long long *fail;                              // raised (rating position) when a dot product is not finite
+};
+struct OrdinalLoglikLaunch {
+    const int64_t *colptr; int64_t ncols;
+    const int32_t *rowidx; const uint8_t *level; int64_t nnz;
+    const void *items, *other; bool f32; int K, kt;
+    const double *g0, *g1; int nlev;                       // two cutpoint tables
+    double *partial;                                       // 2 x ordinal_blocks(nnz) partials, then the two sums
+};
+struct OrdinalProbLaunch {
+    const int32_t *tcol, *trow; int64_t nnz;               // column and row of every test entry
+    const void *items, *other; bool f32; int K, kt;
+    const double *g; int nlev;
+    double *sum;                                           // nlev x nnz running sums of the level probabilities
+};
+int64_t ordinal_blocks(int64_t nnz);                       // workgroups of the three kernels: one tile of ratings each
+int ordinal_latent(const OrdinalLatentLaunch &p, hipStream_t st);   // -1: unsupported K (nothing launched)
+int ordinal_loglik(const OrdinalLoglikLaunch &p, hipStream_t st);   // nnz = 0: the final kernel alone (two zeros)
+int ordinal_prob(const OrdinalProbLaunch &p, hipStream_t st);
+
 // censored ratings (kernels_censor.h, kcensor.hip)
 struct CensorLatentLaunch {
     const int64_t *pos; const int32_t *col, *row; const int8_t *sign; int64_t n;   // the censored entries: position in the CSC, column, row, +-1

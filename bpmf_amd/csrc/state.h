@@ -213,6 +213,7 @@ struct bpmf_hip_side {
     // the add-ons (ext_state.h), each NULL until its entry point attaches it; released in bpmf_hip_side_destroy
     std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
     std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
+    std::unique_ptr<bpmf_ordinal> ordinal; // ordinal probit likelihood (bpmf_hip_side_set_ordinal)
     std::unique_ptr<bpmf_weights> weights; // per-rating precision weights (bpmf_hip_side_set_weights)
     std::unique_ptr<bpmf_robust> robust;   // Student-t noise: the weights are redrawn per launch (bpmf_hip_side_set_robust)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
@@ -345,7 +346,7 @@ struct bpmf_hip_side {
 // never reads it either: a record has no room for sqrt(w) (k_sample1w, the weighted index-block form).
 inline bool uses_gather_stream(const bpmf_hip_side *s)
 {
-    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->censor && !s->link && !s->weights && !(s->ctx->ablate & 4u);
+    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->ordinal && !s->censor && !s->link && !s->weights && !(s->ctx->ablate & 4u);
 }
 
 struct bpmf_hip_test {
@@ -373,6 +374,7 @@ struct bpmf_hip_test {
     int32_t *d_twin_perm = nullptr;
     std::vector<int32_t> h_col, h_row;   // global column / row of every entry (kept for the matching)
     double *d_prob_sum = nullptr; int prob_n = 0;        // probit: running sums of Phi(x . y) per entry and the samples added (capi_probit.hip)
+    DevBuf<double> ord_sum; int ord_n = 0, ord_nlev = 0; // ordinal: running sums of the level probabilities, level-major (nlev x nnz), and the samples added (capi_ordinal.hip)
 };
 
 // did a device-side wait of the pass that wrote this result blob time out?  (the word is sticky: cleared here)
@@ -395,6 +397,18 @@ inline int check_probit(bpmf_hip_side *s, std::string *msg)
     if (v == ~0ull) return 0;
     __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
     *msg = "probit: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
+    return BPMF_HIP_ENUM;
+}
+
+// ordinal probit: did the latent kernel of this side meet a dot product that is not finite?
+inline int check_ordinal(bpmf_hip_side *s, std::string *msg)
+{
+    if (!s->ordinal) return 0;
+    unsigned long long *word = s->ordinal->fail.host();
+    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (v == ~0ull) return 0;
+    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
+    *msg = "ordinal: the score of rating " + std::to_string(v) + " is not finite (non-finite factors?)";
     return BPMF_HIP_ENUM;
 }
 

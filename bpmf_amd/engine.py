@@ -519,6 +519,78 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_test_probit_get(test[0], _ptr(prob), C.byref(n)))
         return prob, n.value
 
+    # -- ordinal probit likelihood -------------------------------------------------
+    def set_ordinal(self, side, levels, cutpoints=None, tag=11):
+        """Turns `side` (created with mean_rating 0) into an ordinal side (include/bpmf_hip.h): its ratings
+        take one of the C = len(levels) values `levels` (strictly increasing, 2 <= C <= 16), and every sampler launch of the side is
+        preceded by the draw of its latent scores, truncated to the interval of each rating's level at the side's current
+        cutpoints.  cutpoints: the C - 1 initial cutpoints, or None for Phi^-1 of the cumulative level frequencies.  tag >= 1 names
+        the side's random streams (gibbs: 11 = movies, 12 = users).  Such a side is sampled with alpha = 1."""
+        lv = np.ascontiguousarray(levels, np.float64)
+        if lv.ndim != 1:
+            raise ValueError("set_ordinal: the levels must be one array")
+        cp = None
+        if cutpoints is not None:
+            cp = np.ascontiguousarray(cutpoints, np.float64)
+            if cp.ndim != 1 or len(cp) != len(lv) - 1:
+                raise ValueError("set_ordinal: %d levels need %d cutpoints" % (len(lv), len(lv) - 1))
+        _lib.check(self.lib.bpmf_hip_side_set_ordinal(side.handle, _ptr(lv), len(lv), _ptr(cp), int(tag)))
+
+    def ordinal_info(self, side):
+        """(levels, log-likelihood passes enqueued so far) of an ordinal side."""
+        n, runs = C.c_int(), C.c_int64()
+        lv = np.zeros(16)
+        _lib.check(self.lib.bpmf_hip_side_ordinal_info(side.handle, C.byref(n), _ptr(lv), C.byref(runs)))
+        return lv[:n.value].copy(), runs.value
+
+    def ordinal_latent(self, side, nnz):
+        """The latent scores the side's newest sampler launch read, in the order of its ratings (waits)."""
+        z = np.empty(int(nnz))
+        _lib.check(self.lib.bpmf_hip_side_ordinal_latent(side.handle, _ptr(z)))
+        return z
+
+    def ordinal_cut_get(self, side):
+        """The side's C - 1 cutpoints."""
+        cp = np.zeros(15)
+        _lib.check(self.lib.bpmf_hip_side_ordinal_cut_get(side.handle, _ptr(cp)))
+        return cp[:len(self.ordinal_info(side)[0]) - 1].copy()
+
+    def ordinal_cut_set(self, side, cutpoints):
+        """Replaces the side's cutpoints (waits for the work in flight first)."""
+        cp = np.ascontiguousarray(cutpoints, np.float64)
+        if cp.ndim != 1 or len(cp) != len(self.ordinal_info(side)[0]) - 1:
+            raise ValueError("ordinal_cut_set: the side has %d cutpoints" % (len(self.ordinal_info(side)[0]) - 1))
+        _lib.check(self.lib.bpmf_hip_side_ordinal_cut_set(side.handle, _ptr(cp)))
+
+    def ordinal_loglik(self, side, other, cutpoints_prop):
+        """(l(g), l(g')): the log-likelihood of the side's ratings at its cutpoints g and at `cutpoints_prop`, the latent scores
+        integrated out, from one pass over the ratings at the newest factors of both sides (waits)."""
+        cp = np.ascontiguousarray(cutpoints_prop, np.float64)
+        if cp.ndim != 1 or len(cp) != len(self.ordinal_info(side)[0]) - 1:
+            raise ValueError("ordinal_loglik: the side has %d cutpoints" % (len(self.ordinal_info(side)[0]) - 1))
+        out = np.zeros(2)
+        _lib.check(self.lib.bpmf_hip_ordinal_loglik(side.handle, other.handle, _ptr(cp), _ptr(out)))
+        return float(out[0]), float(out[1])
+
+    def ordinal_cut_step(self, movies, users, it, step):
+        """One Metropolis-Hastings step of the cutpoints of both sides given their factors (Cowles 1996; include/bpmf_hip.h has
+        the proposal, the acceptance ratio and the random streams).  Returns whether the proposal was accepted (waits)."""
+        acc = C.c_int()
+        _lib.check(self.lib.bpmf_hip_ordinal_cut_step(movies.handle, users.handle, int(it), float(step), C.byref(acc)))
+        return bool(acc.value)
+
+    def ordinal_add(self, test, side, other):
+        """Adds the level probabilities of the current factors and cutpoints to the running sums of the test matrix' entries
+        (enqueue only)."""
+        _lib.check(self.lib.bpmf_hip_test_ordinal_add(test[0], side.handle, other.handle))
+
+    def ordinal_get(self, test):
+        """(prob [entries, C], nsamples): the mean probability of every level per test entry, in the order given to test_create."""
+        buf = np.empty(test[1] * 16)                 # (room for the largest C: the library says how many levels it wrote)
+        n, c = C.c_int(), C.c_int()
+        _lib.check(self.lib.bpmf_hip_test_ordinal_get(test[0], _ptr(buf), C.byref(c), C.byref(n)))
+        return buf[:test[1] * c.value].reshape(test[1], c.value).copy(), n.value
+
     # -- censored ratings ----------------------------------------------------------
     def set_censored(self, side, flags, tag):
         """Marks ratings of `side` as bounds: flags holds one int8 per rating in the side's order, 0 = the value is the measurement,

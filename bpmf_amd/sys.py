@@ -188,7 +188,8 @@ class Sys:
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
-          new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None):
+          new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
+          ordinal=None, cutpoints=None, ordinal_step=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -288,7 +289,64 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     rating in M's CSC order (zeros without a kept sample), kept=the samples in it).  With or without topn, foldin (a folded-in
     row's own ratings are Gaussian with weight 1) and topn_score ("ucb" only: the sigma = 1 / sqrt(alpha) of "prob" and "ei"
     assumes Gaussian noise).  weights, probit=True, censored, noise="adaptive", features and an fp32 engine are refused with
-    robust.  None (the default): nothing changes."""
+    robust.  None (the default): nothing changes.
+
+    ordinal=True | levels: the ratings are ordered categories under the ordinal probit likelihood with sampled cutpoints (DESIGN.md
+    section 23).  The training values take one of C levels (True: the distinct training values; or the 2 <= C <= 16 level values,
+    increasing, of which some may be absent from the training set); a rating at level c has a latent score between the cutpoints
+    g_{c-1} and g_c.  Both sides are created with mean rating 0 and turned into ordinal sides (engine.set_ordinal, tags 11 =
+    movies, 12 = users), alpha is 1.  Every iteration but the first starts with a Metropolis-Hastings step of all cutpoints given
+    the factors (engine.ordinal_cut_step: one pass over the training ratings on the device, the pipelined loop drains once per
+    iteration for it, as noise="adaptive" does).  Its proposal step s starts at 1 / sqrt(nnz) and follows log s += (accepted -
+    0.35) / sqrt(iter + 1) during the burn-in, frozen afterwards: start, target and schedule are defaults, not tuned numbers.
+    ordinal_step=F fixes s = F and disables the adaptation.  cutpoints=[g_1 .. g_{C-1}]: the cutpoints are fixed at these values,
+    there is no step and no drain (None: they start at Phi^-1 of the cumulative level frequencies and are sampled).  Every
+    post-burn-in sample adds the level probabilities of the test entries (engine.ordinal_add, enqueue only).  res["ordinal"] =
+    dict(levels, cutpoints = the cutpoints every iteration ran with [nsims, C - 1], accepted = per iteration whether its proposal
+    was accepted, step = the s of every iteration); res["cat_prob"] [ntest, C]: the posterior-mean probability of every level,
+    res["expected"] = sum_c l_c p_c, res["logp"]: the mean log probability of the true level (a test value that is not a level is
+    refused).  The RMSE columns of the trace compare the latent score u . v with the raw value and are not an error measure.  topn
+    ranks by the latent score, and the thresholds of topn_score "prob" / "ei" are on that scale.  foldin, features,
+    noise="adaptive", censored, weights, robust and probit=True are refused with ordinal.  None / False (the default): nothing
+    changes."""
+    ordinal_on = ordinal is not None and ordinal is not False
+    if ordinal_on:                                   # (refused before the engine is used)
+        for on, what, why in ((probit, "probit=True", "a side has one likelihood"),
+                              (foldin, "foldin=True", "levels would need a latent iteration of their own"),
+                              (noise == "adaptive", "noise='adaptive'", "the latent scores have unit variance"),
+                              (censored is not None, "censored", "levels have no bounds"),
+                              (weights is not None, "weights", "the latent scores have unit variance"),
+                              (robust is not None, "robust", "the latent scores have unit variance"),
+                              (row_features is not None or col_features is not None, "row_features / col_features",
+                               "the residuals would have to be formed from the latent scores")):
+            if on:
+                raise ValueError("ordinal does not go together with %s (%s)" % (what, why))
+        if alpha is not None and float(alpha) != 1.0:
+            raise ValueError("ordinal runs with alpha = 1, not %r" % (alpha,))
+        ord_levels = np.unique(np.asarray(M[2], np.float64)) if ordinal is True else np.array(ordinal, np.float64)
+        if ord_levels.ndim != 1 or not (2 <= len(ord_levels) <= 16):
+            raise ValueError("ordinal: %d levels (2 .. 16 are supported)" % (ord_levels.size if ord_levels.ndim == 1 else -1,))
+        if not (np.all(np.isfinite(ord_levels)) and np.all(np.diff(ord_levels) > 0)):
+            raise ValueError("ordinal: the levels must be finite and strictly increasing")
+        if not np.all(np.isin(np.asarray(M[2], np.float64), ord_levels)):
+            raise ValueError("ordinal: a training value is not one of the levels %s" % (ord_levels.tolist(),))
+        if T is not None and not np.all(np.isin(np.asarray(T[2], np.float64), ord_levels)):
+            raise ValueError("ordinal: a test value is not one of the levels %s" % (ord_levels.tolist(),))
+        if cutpoints is not None:
+            cutpoints = np.array(cutpoints, np.float64)
+            if cutpoints.ndim != 1 or len(cutpoints) != len(ord_levels) - 1:
+                raise ValueError("ordinal: %d levels need %d cutpoints" % (len(ord_levels), len(ord_levels) - 1))
+            if not (np.all(np.isfinite(cutpoints)) and np.all(np.diff(cutpoints) > 0)):
+                raise ValueError("ordinal: the cutpoints must be finite and strictly increasing")
+        elif len(M[2]) == 0:
+            raise ValueError("ordinal: a training matrix without ratings has no default cutpoints")
+        if ordinal_step is not None:
+            ordinal_step = float(ordinal_step)
+            if not (ordinal_step > 0 and math.isfinite(ordinal_step)):
+                raise ValueError("ordinal_step must be positive and finite")
+        alpha = 1.0
+    elif cutpoints is not None or ordinal_step is not None:
+        raise ValueError("cutpoints / ordinal_step need ordinal")
     if robust is not None:                           # (refused before the engine is used)
         try:
             robust = float(robust)
@@ -418,8 +476,13 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if weights is not None:                          # (checked before a side is created)
         wts = (rating_weights(M, weights), rating_weights(Mt, transpose_csc(weights, nusers)))
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
-    movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit else None)
-    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit else None)
+    movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit or ordinal_on else None)
+    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit or ordinal_on else None)
+    if ordinal_on:
+        engine.set_ordinal(movies.side, ord_levels, cutpoints, ORDINAL_TAGS[0])
+        engine.set_ordinal(users.side, ord_levels, engine.ordinal_cut_get(movies.side), ORDINAL_TAGS[1])   # (the same bits on both sides)
+        ord_sampled = cutpoints is None
+        ord_s = ordinal_step if ordinal_step is not None else 1.0 / math.sqrt(max(len(M[2]), 1))
     if probit:
         engine.set_probit(movies.side, threshold, 1)
         engine.set_probit(users.side, threshold, 2)
@@ -486,6 +549,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             engine.robust_add(movies.side)
         if probit and i >= burnin and movies.test is not None:
             engine.probit_add(movies.test, movies.side, users.side)
+        if ordinal_on and i >= burnin and movies.test is not None:
+            engine.ordinal_add(movies.test, movies.side, users.side)
         if linked and i >= burnin:
             if col_features is not None:
                 engine.link_add(movies.side)
@@ -503,6 +568,21 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
 
     if adaptive:
         res["alpha"], res["train_rmse"] = [], []
+    if ordinal_on:
+        res["ordinal"] = dict(levels=ord_levels.copy(), cutpoints=[engine.ordinal_cut_get(movies.side)], accepted=[False], step=[ord_s])
+
+    def cut(i):                                      # after both sides of iteration i: the cutpoints of iteration i + 1
+        nonlocal ord_s
+        if not ordinal_on or i + 1 >= nsims:
+            return
+        acc = False
+        if ord_sampled:
+            acc = engine.ordinal_cut_step(movies.side, users.side, i + 1, ord_s)
+        o = res["ordinal"]
+        o["accepted"].append(acc); o["step"].append(ord_s)
+        o["cutpoints"].append(engine.ordinal_cut_get(movies.side) if acc else o["cutpoints"][-1])
+        if ord_sampled and ordinal_step is None and i + 1 < burnin:
+            ord_s = math.exp(math.log(ord_s) + ((1.0 if acc else 0.0) - 0.35) / math.sqrt(i + 2))
 
     def adapt(i):                                    # after both sides of iteration i: the alpha of iteration i + 1
         if not adaptive:
@@ -531,6 +611,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             users.sample(movies)
             keep(i)
             adapt(i)
+            cut(i)
             if i > 0:
                 norm_m = engine.sys_norm(movies.side, i - 1)
                 norm_u = engine.sys_norm(users.side, i - 1)
@@ -554,6 +635,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             users.sample(movies)
             keep(i)
             adapt(i)
+            cut(i)
             movies.predict(users)
             if Tt is not None:
                 users.predict(movies)                # c++/bpmf.cpp:190 (nothing reads its results; Tt = None leaves it out)
@@ -580,6 +662,18 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         label = (np.asarray(T[2]) > threshold).astype(np.float64) if have else np.zeros(0)
         res["auc"] = _engine.auc(res["prob"], label, 0.5) if have else float("nan")
         res["brier"] = float(np.mean((res["prob"] - label) ** 2)) if have else float("nan")
+    if ordinal_on:
+        o = res["ordinal"]
+        o["cutpoints"] = np.array(o["cutpoints"][:max(nsims, 1)]).reshape(-1, len(ord_levels) - 1)
+        have = movies.test is not None and movies.T_nnz > 0 and nsims > burnin
+        res["cat_prob"] = engine.ordinal_get(movies.test)[0] if have else np.zeros((0, len(ord_levels)))
+        res["expected"] = res["cat_prob"] @ ord_levels
+        if have:
+            true = np.searchsorted(ord_levels, np.asarray(T[2], np.float64))
+            with np.errstate(divide="ignore"):
+                res["logp"] = float(np.mean(np.log(res["cat_prob"][np.arange(len(true)), true])))
+        else:
+            res["logp"] = float("nan")
     if censored is not None:
         res["censored"] = engine.censored_count(movies.side)
     if weights is not None:
@@ -610,6 +704,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
 
 
 FOLDIN_TAGS = {"rows": 7, "cols": 8}                 # the random streams of folded-in users / movies (1 .. 6 and 9, 10 are taken: gibbs)
+ORDINAL_TAGS = (11, 12)                              # the random streams of the latent scores of ordinal sides: movies, users
 ROBUST_TAGS = (9, 10)                                # the random streams of the weights of Student-t noise: movies, users
 
 

@@ -61,6 +61,9 @@ BPMF_API int bpmf_hip_abi_version(void);
 /* diagnostic: device bytes the add-ons of all sides of this process own right now (probit, features, sample rings, residual partials,
  * the temporaries of their calls): hipMemGetInfo counts the whole card, other processes included */
 BPMF_API int64_t bpmf_hip_live_device_bytes(void);
+/* diagnostic: how often this process has waited on the host for the main stream of a context (the waits of the entry points that say
+ * "waits": bpmf_hip_train_sse, bpmf_hip_ordinal_cut_step, the _get calls ...).  A loop that does not drain leaves it unchanged. */
+BPMF_API int64_t bpmf_hip_stream_drains(void);
 /* 1 if a context of num_latent K (BPMF_NUMLATENT, c++/bpmf.h:22-24,53: the reference ships bpmf-8 ... bpmf-128 incl. 10, 20 ... 100,
  * ci/multilatent.sh:5) can be created in fp64: 1 <= K <= 128.  The kernels are instantiated for 8, 16, 32, 64, 128; any other K
  * runs on the next instantiated size (bpmf_hip_kernel_k) with zero factor rows and an identity block of the prior precision in
@@ -445,6 +448,54 @@ BPMF_API int bpmf_hip_test_probit_get(bpmf_hip_test *test, double *prob_host, in
  * pairs that the score orders correctly, ties counted half (average ranks).  *auc = NaN when one class is empty (n = 0
  * included).  BPMF_HIP_EINVAL for NULL arguments, n < 0 or a NaN score. */
 BPMF_API int bpmf_hip_auc(const double *score, const double *value, int64_t n, double threshold, double *auc);
+
+/* ---- ordinal probit likelihood with sampled cutpoints -----------------------------
+ * The ratings of an ordinal side take one of C levels l_1 < ... < l_C (2 <= C <= 16).  A rating at level c carries a latent
+ * score z with g_{c-1} < z <= g_c, z ~ N(u . v, 1), g_0 = -inf, g_C = +inf: the probit model above with C - 1 cutpoints in
+ * place of the threshold.  The column samplers read the scores in place of the ratings, with mean 0 and alpha = 1.  DESIGN.md
+ * section 23 has the model, the draw and the keying.
+ *
+ * bpmf_hip_side_set_ordinal turns `side` into an ordinal side: `levels` are the nlevels level values, strictly increasing;
+ * `cutpoints` the nlevels - 1 initial cutpoints, strictly increasing, or NULL for Phi^-1 of the cumulative frequencies of the
+ * side's ratings (every level counted half a rating higher when one of them has no rating).  From then on every sampler launch of
+ * the side is preceded on the same stream by the latent step
+ *     m = x_c . y_r,   z_p ~ N(m, 1) truncated to the interval of the level of rating p at the side's current cutpoints,
+ * by inversion from ONE Philox4x32-10 block per rating (counter = p low, p high, iter, 0; key = 42, tag): no rejection, no host
+ * wait, ahead of the wait for the hyper-parameters in the queue.  tag >= 1 as for a probit side (bpmf_amd.gibbs uses 11 =
+ * movies, 12 = users; 1 .. 10 are taken).  Give both sides of a model the same levels and cutpoints.  A score that is not finite
+ * makes the sampling call that collects the half-iteration fail with BPMF_HIP_ENUM.
+ * BPMF_HIP_EINVAL: NULL, nlevels outside 2 .. 16, levels or cutpoints not finite or not strictly increasing, a rating that is not
+ * a level, tag = 0, mean_rating != 0 (and, at a launch, alpha != 1), a side that is ordinal already, a probit, censored, weighted
+ * or robust side, features, propagated priors, the BPMF_REDUCE formulation, a communicator or a sharded side.  In turn
+ * bpmf_hip_side_set_probit, _set_censored, _set_weights, _set_robust, _set_features[_sparse], _set_prop_posterior,
+ * bpmf_hip_sys_set_reduce, bpmf_hip_train_sse, the fold-in and a tensor mode refuse an ordinal side. */
+BPMF_API int bpmf_hip_side_set_ordinal(bpmf_hip_side *side, const double *levels, int nlevels, const double *cutpoints, unsigned tag);
+/* The number of levels, the level values (16 doubles of room) and the log-likelihood passes enqueued so far; each may be NULL. */
+BPMF_API int bpmf_hip_side_ordinal_info(bpmf_hip_side *side, int *nlevels, double *levels, int64_t *loglik_launches);
+/* The side's latent scores as the newest sampler launch read them, nnz doubles in the order of the side's ratings (waits). */
+BPMF_API int bpmf_hip_side_ordinal_latent(bpmf_hip_side *side, double *z_host);
+/* The side's nlevels - 1 cutpoints.  _cut_set waits for the work in flight (a latent kernel reads the table), then replaces them. */
+BPMF_API int bpmf_hip_side_ordinal_cut_get(bpmf_hip_side *side, double *cutpoints);
+BPMF_API int bpmf_hip_side_ordinal_cut_set(bpmf_hip_side *side, const double *cutpoints);
+/* out[0] = sum over the ratings of `self` of log[Phi(g_y - m) - Phi(g_{y-1} - m)] at the side's cutpoints, out[1] the same at
+ * `cutpoints_prop`, m = x_c . y_r of the newest factors of both sides; one pass over the ratings, no atomics, the same bits for
+ * the same inputs.  Enqueues behind the newest samplers on the context stream and waits. */
+BPMF_API int bpmf_hip_ordinal_loglik(bpmf_hip_side *self, bpmf_hip_side *other, const double *cutpoints_prop, double *out);
+/* One Metropolis-Hastings step of all cutpoints given the factors (Cowles 1996), the scores integrated out.  For c = 1 .. C - 1
+ * in turn g'_c ~ N(g_c, step^2) truncated to (g'_{c-1}, g_{c+1}); accepted with log-ratio l(g') - l(g) + sum_c (log[Phi((g_{c+1}
+ * - g_c) / step) - Phi((g'_{c-1} - g_c) / step)] - log[Phi((g'_{c+1} - g'_c) / step) - Phi((g_{c-1} - g'_c) / step)]), both l from
+ * one bpmf_hip_ordinal_loglik pass over the ratings of `movies`.  Random numbers: the Philox4x32-10 blocks (counter =
+ * BPMF_ORDINAL_COUNTER(iter), c, 0, attempt; key = 42, 0); an attempt is one Box-Muller pair (u1 = 1 - canonical53(w3, w2), u2 =
+ * canonical53(w1, w0); g_c + step sqrt(-2 ln u1) cos(2 pi u2), then ... sin(2 pi u2): the first inside the bounds), after 64
+ * attempts g'_c = g_c; the accept uniform is u1 of the block c = 0, attempt 0.  *accepted = 1: both sides hold g' now.  Waits. */
+#define BPMF_ORDINAL_COUNTER(iter) (0x40000000u + (uint32_t)(iter))
+BPMF_API int bpmf_hip_ordinal_cut_step(bpmf_hip_side *movies, bpmf_hip_side *users, int iter, double step, int *accepted);
+/* Adds the C level probabilities Phi(g_c - m) - Phi(g_{c-1} - m) of the current factors and cutpoints of `self` (the side of
+ * `test`) to the running sums of every entry of the test matrix.  Enqueue only, as bpmf_hip_test_probit_add. */
+BPMF_API int bpmf_hip_test_ordinal_add(bpmf_hip_test *test, bpmf_hip_side *self, bpmf_hip_side *other);
+/* The mean of the added probabilities, nnz x C row-major (entry-major) in the order of the test matrix, the number of levels and
+ * of samples added (either may be NULL).  Waits.  BPMF_HIP_EINVAL when nothing was added. */
+BPMF_API int bpmf_hip_test_ordinal_get(bpmf_hip_test *test, double *prob_host, int *nlevels, int *nsamples);
 
 /* ---- censored ratings (Tobit) ----------------------------------------------------
  * A training rating may be a bound on the measurement instead of the measurement.  Every rating p of a side (position in the
