@@ -10,7 +10,8 @@ from .engine import HipEngine, auc, hyper_sample, link_lambda_sample  # noqa: F4
 from .sys import Sys, HyperParams, gibbs, fold_in  # noqa: F401
 from .censor import censor_flags  # noqa: F401
 from .weights import rating_weights  # noqa: F401
+from .rank import held_out_lists, rank_metrics  # noqa: F401
 from .io import read_tns, write_tns  # noqa: F401
 from .tensor import tensor_gibbs  # noqa: F401
 
-__all__ = ["load_library", "library_path", "BpmfHipError", "HipEngine", "auc", "hyper_sample", "Sys", "HyperParams", "gibbs", "fold_in", "censor_flags", "rating_weights", "read_tns", "write_tns", "tensor_gibbs"]
+__all__ = ["load_library", "library_path", "BpmfHipError", "HipEngine", "auc", "hyper_sample", "Sys", "HyperParams", "gibbs", "fold_in", "censor_flags", "rating_weights", "held_out_lists", "rank_metrics", "read_tns", "write_tns", "tensor_gibbs"]

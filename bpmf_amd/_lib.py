@@ -62,6 +62,12 @@ _SIGNATURES = {
     "bpmf_hip_side_samples_count": (C.c_int, [C.c_void_p]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_rank_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_set_implicit": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "bpmf_hip_side_implicit_w0": (C.c_double, [C.c_void_p]),
+    "bpmf_hip_side_implicit_gram": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_implicit_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     "bpmf_hip_topn_scored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double,
                                        C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_predict_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -58,6 +58,14 @@
 // sides redraw a precision weight per rating on the device ahead of every sampler launch (bpmf_hip_side_set_robust); one more header
 // line names NU, -o DIR also writes DIR/robust-weights.sdm (the posterior-mean weight of every training cell), everything else keeps
 // its format.
+// --implicit W0 [--weights FILE] (one GPU, no -g): implicit feedback: every cell the training matrix does not
+// store is a zero of weight W0, a stored cell has its value and the confidence 1 (or its entry of --weights FILE, > W0); mean rating 0.
+// Both sides become implicit sides (bpmf_hip_side_set_implicit) and step through the blocking bpmf_hip_implicit_sample; one more header
+// line, everything else keeps its format (the RMSE columns are over the -p cells as given).
+// --rank-eval N [--rank-by rows|cols] [--rank-threshold F] (-i > -b, one GPU): after the chain every test cell with a value > F (default:
+// every test cell, or value > 0 under --implicit) is ranked among the candidates its query has not rated in the training matrix, by the
+// posterior-mean score of the kept samples (bpmf_hip_rank_eval).  After "Final Avg RMSE" the run prints "Final recall@N", "Final NDCG@N",
+// "Final MRR", "Final MPR" and "Final rank AUC"; -o DIR also gets DIR/ranks.csv (query,candidate,rank,ncand).
 // --tensor FILE.tns [--tensor-test FILE.tns] [--tensor-dims I,J,T] (one GPU, no -g): Bayesian CP factorisation of a sparse tensor of
 // order 3 in the place of -n / -p.  FROSTT .tns files (one entry per line, "i j t value", 1-based, # comments,
 // optional .gz); the sizes default to the largest index of either file.  -i, -b, -a, -d and -o apply.  stdout: the header line
@@ -101,7 +109,7 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--implicit W0] [--rank-eval N [--rank-by rows|cols] [--rank-threshold F]] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "       bpmf --tensor <TNS> [--tensor-test <TNS>] [--tensor-dims I,J,T] [-o DIR/] [-i N] [-b N] [-a F] [-d K]\n"
               << "\n"
               << "Parameters:\n"
@@ -189,6 +197,16 @@ void usage()
               << "              stops dragging its factors; -o DIR also gets robust-weights.sdm, the posterior-mean weight of every training\n"
               << "              cell (one GPU, no -g; not with --weights, --probit, --censored, --noise adaptive, --row-features /\n"
               << "              --col-features, -m / -l, --fp32, --topn-score prob|ei or BPMF_REDUCE=1)\n"
+              << "  [--implicit W0]: implicit feedback: every cell the training matrix does not store is a zero of weight W0 > 0, a stored cell has\n"
+              << "              its value and the confidence 1, or its entry of --weights FILE, which must be > W0; mean rating 0; both sides step\n"
+              << "              through a blocking half-iteration that forms the Gram matrix of the other side (one GPU, no -g; not with --fp32,\n"
+              << "              --probit, --ordinal, --robust, --censored, --noise adaptive, --row-features / --col-features, -m / -l,\n"
+              << "              --fold-in-*, --tensor, --topn-score prob|ei or BPMF_REDUCE=1)\n"
+              << "  [--rank-eval N]: after the chain rank every held-out test cell among the candidates its query has not rated (1 <= N <= 1000;\n"
+              << "              -i > -b, one GPU) and print recall@N, NDCG@N, MRR, the mean percentile rank and the rank AUC; -o DIR also gets\n"
+              << "              ranks.csv (query,candidate,rank,ncand)\n"
+              << "  [--rank-by rows|cols]: the queries of --rank-eval: rows (users, the default) or columns\n"
+              << "  [--rank-threshold F]: the held-out items are the test cells with a value > F (default: every test cell; > 0 under --implicit)\n"
               << "  [--tensor FILE.tns]: factorise a sparse tensor of order 3 (Bayesian CP) instead of a matrix: FILE takes the place of -n / -p;\n"
               << "              FROSTT format, one entry per line, i j t value, 1-based indices, # comments, optional .gz (one GPU, no -g; -i, -b,\n"
               << "              -a, -d and -o apply; not with --fp32, -m / -l, --probit, --censored, --weights, --robust, --noise adaptive,\n"
@@ -324,6 +342,48 @@ void permute_columns(std::vector<double> &d, int64_t rows, const std::vector<int
     d.swap(o);
 }
 
+// bpmf_amd.rank_metrics at list length n: rank[p] of held-out entry p among the ncand[q] candidates its query q has not rated, the
+// entries of query q at tptr[q] .. tptr[q + 1].  Means over what is named, NaN when that is empty:
+//   recall   over the queries with entries: entries with rank <= n / min(n, entries)
+//   ndcg     over the same: sum of 1 / log2(1 + rank) over the entries with rank <= n, over sum_{i = 1 .. min(n, entries)} 1 / log2(1 + i)
+//   mrr      over the same: 1 / the smallest rank
+//   mpr      over the ENTRIES with ncand > 1: (rank - 1) / (ncand - 1)
+//   auc      over the queries with entries and other candidates: 1 - sum_i (r_(i) - i) / (entries (ncand - entries)), ranks ascending
+struct RankMetrics { double recall = NAN, ndcg = NAN, mrr = NAN, mpr = NAN, auc = NAN; int64_t queries = 0, entries = 0; };
+RankMetrics rank_metrics(const std::vector<int32_t> &rank, const std::vector<int64_t> &tptr, const std::vector<int32_t> &ncand, int n)
+{
+    RankMetrics m;
+    double recall = 0.0, ndcg = 0.0, mrr = 0.0, auc = 0.0, mpr = 0.0;
+    int64_t nauc = 0, nmpr = 0;
+    const int64_t nq = (int64_t)tptr.size() - 1;
+    std::vector<int32_t> r;
+    for (int64_t q = 0; q < nq; ++q) {
+        r.assign(rank.begin() + tptr[(size_t)q], rank.begin() + tptr[(size_t)q + 1]);
+        const int64_t h = (int64_t)r.size();
+        if (h == 0) continue;
+        std::sort(r.begin(), r.end());
+        int64_t hits = 0, before = 0;
+        double dcg = 0.0, idcg = 0.0;
+        for (int64_t i = 0; i < h; ++i) {
+            if (r[(size_t)i] <= n) { ++hits; dcg += 1.0 / std::log2(1.0 + (double)r[(size_t)i]); }
+            if (i < n) idcg += 1.0 / std::log2(2.0 + (double)i);
+            before += (int64_t)r[(size_t)i] - (i + 1);
+            if (ncand[(size_t)q] > 1) { mpr += (double)(r[(size_t)i] - 1) / (double)(ncand[(size_t)q] - 1); ++nmpr; }
+        }
+        recall += (double)hits / (double)std::min<int64_t>(n, h);
+        ndcg += dcg / idcg;
+        mrr += 1.0 / (double)r[0];
+        const int64_t others = (int64_t)ncand[(size_t)q] - h;
+        if (others > 0) { auc += 1.0 - (double)before / ((double)h * (double)others); ++nauc; }
+        ++m.queries;
+        m.entries += h;
+    }
+    if (m.queries > 0) { m.recall = recall / (double)m.queries; m.ndcg = ndcg / (double)m.queries; m.mrr = mrr / (double)m.queries; }
+    if (nmpr > 0) m.mpr = mpr / (double)nmpr;
+    if (nauc > 0) m.auc = auc / (double)nauc;
+    return m;
+}
+
 struct Job {
     // inputs (read-only for the ranks)
     Csc M, Mt, T, Tt;                                                // Tt: the test entries by user (users.predict(movies), c++/bpmf.cpp:190)
@@ -354,6 +414,12 @@ struct Job {
     std::vector<double> w_m, w_u;                                    // the weight of every rating of M / Mt
     int64_t w_count = 0; double w_min = 1.0, w_max = 1.0;            // listed cells whose weight is not 1; the smallest / largest weight
     bool robust = false; double robust_nu = 0.0;                     // --robust NU
+    bool implicit = false; double implicit_w0 = 0.0;                 // --implicit W0
+    int rank_eval = 0;                                               // --rank-eval N (0: off)
+    bool rank_by_cols = false, rank_thr_given = false;               // --rank-by cols, --rank-threshold F
+    double rank_thr = 0.0;
+    std::vector<int64_t> rank_tptr;                                  // per query of the run's numbering: its held-out entries
+    std::vector<int32_t> rank_tcand, rank_rank, rank_ncand;          // their candidates (ascending) and ranks; the candidates left per query
     std::vector<double> robust_w;                                    // the posterior-mean weight of every rating of M
     std::vector<double> prob;                                        // posterior-mean probability of a positive, test-set order of T
     double auc = NAN, brier = NAN;
@@ -435,7 +501,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(bpmf_hip_side_set_censored(movies, J.cens_m.data(), 5));
         check(bpmf_hip_side_set_censored(users, J.cens_u.data(), 6));
     }
-    if (J.weighted) {
+    if (J.implicit) {                                                // (--weights FILE: the confidences)
+        check(bpmf_hip_side_set_implicit(movies, J.implicit_w0, J.weighted ? J.w_m.data() : nullptr));
+        check(bpmf_hip_side_set_implicit(users, J.implicit_w0, J.weighted ? J.w_u.data() : nullptr));
+    } else if (J.weighted) {
         check(bpmf_hip_side_set_weights(movies, J.w_m.data()));
         check(bpmf_hip_side_set_weights(users, J.w_u.data()));
     }
@@ -461,7 +530,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.has_feat_u()) check(bpmf_hip_side_link_lambda_prior(users, J.lb_a0, J.lb_b0));
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0;
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -551,6 +620,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.weighted)
         os << "weights: " << J.w_count << " of " << J.M.nnz() << " training ratings weighted, min " << J.w_min << ", max " << J.w_max << std::endl;
     if (J.robust) os << "robust: Student-t noise, nu = " << J.robust_nu << std::endl;
+    if (J.implicit)
+        os << "implicit: w0 " << J.implicit_w0 << ", " << J.M.nnz() << " observed of " << nusers << " x " << nmovies << " cells" << std::endl;
     if (linked) {
         os << "side information:";
         if (J.sfeat_u_d > 0) os << " row features sparse D = " << J.sfeat_u_d << " nnz = " << J.sfeat_u.nnz() << ",";
@@ -621,8 +692,12 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (!J.ord_fixed && !J.ord_step_given && i + 1 < burnin) ord_s = std::exp(std::log(ord_s) + ((acc ? 1.0 : 0.0) - 0.35) / std::sqrt((double)(i + 2)));
     };
     // a model with side information steps both sides through the blocking half-iteration
-    auto sample = [&](bpmf_hip_side *a, bpmf_hip_side *b) { check(linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha)); };
-    if (J.odirname.empty() && !J.verbose && !linked) {
+    // (an implicit model too: bpmf_hip_implicit_sample forms the Gram matrix of the other side first)
+    auto sample = [&](bpmf_hip_side *a, bpmf_hip_side *b) {
+        check(J.implicit ? bpmf_hip_implicit_sample(a, b, alpha) : linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha));
+    };
+    // (--rank-eval keeps the samples in the rings, which the loop below fills)
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -802,6 +877,17 @@ void rank_main(Job &J, int rank, std::ostream &os)
         }
         std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
                   << (tick() - t0) * 1e3 << " ms" << std::endl;
+    }
+    if (J.rank_eval > 0) {                                           // one rank (main refuses -g > 1)
+        const double t0 = tick();
+        bpmf_hip_side *q = J.rank_by_cols ? movies : users, *cand = J.rank_by_cols ? users : movies;
+        const int64_t nq = J.rank_by_cols ? nmovies : nusers;
+        J.rank_rank.assign(std::max<size_t>(J.rank_tcand.size(), 1), 0); J.rank_ncand.assign((size_t)std::max<int64_t>(nq, 1), 0);
+        static const int32_t none = 0;
+        check(bpmf_hip_rank_eval(q, cand, J.mean_m, 0, nq, 1, J.rank_tptr.data(), J.rank_tcand.empty() ? &none : J.rank_tcand.data(),
+                                 J.rank_rank.data(), J.rank_ncand.data()));
+        J.rank_rank.resize(J.rank_tcand.size());
+        std::cerr << "rank-eval: " << J.rank_tcand.size() << " held-out entries of " << nq << " queries, " << (tick() - t0) * 1e3 << " ms" << std::endl;
     }
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
@@ -985,6 +1071,8 @@ int main(int argc, char *argv[])
                                               {"ordinal-cutpoints", required_argument, nullptr, 1052}, {"ordinal-step", required_argument, nullptr, 1053},
                                               {"tensor", required_argument, nullptr, 1040}, {"tensor-test", required_argument, nullptr, 1041},
                                               {"tensor-dims", required_argument, nullptr, 1042},
+                                              {"implicit", required_argument, nullptr, 1060}, {"rank-eval", required_argument, nullptr, 1061},
+                                              {"rank-by", required_argument, nullptr, 1062}, {"rank-threshold", required_argument, nullptr, 1063},
                                               {nullptr, 0, nullptr, 0}};
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
@@ -992,6 +1080,8 @@ int main(int argc, char *argv[])
     bool alpha_given = false, threshold_given = false;
     std::string tensor_file, tensor_test, tensor_dims;
     std::string ordinal_levels, ordinal_cutpoints, ordinal_step;
+    std::string implicit_w0, rank_eval_n, rank_by = "rows", rank_threshold;
+    bool rank_eval_given = false, rank_by_given = false;
     bool ordinal_levels_given = false, ordinal_cutpoints_given = false;
     bool tensor_given = false, tensor_test_given = false, tensor_dims_given = false;
     int ch;
@@ -1028,6 +1118,10 @@ int main(int argc, char *argv[])
         case 1040: tensor_file = optarg; tensor_given = true; break;
         case 1041: tensor_test = optarg; tensor_test_given = true; break;
         case 1042: tensor_dims = optarg; tensor_dims_given = true; break;
+        case 1060: implicit_w0 = optarg; J.implicit = true; break;
+        case 1061: rank_eval_n = optarg; rank_eval_given = true; break;
+        case 1062: rank_by = optarg; rank_by_given = true; break;
+        case 1063: rank_threshold = optarg; J.rank_thr_given = true; break;
         case 'i': J.nsims = atoi(optarg); break;
         case 'b': J.burnin = atoi(optarg); break;
         case 'f': J.update_freq = atoi(optarg); break;
@@ -1060,6 +1154,8 @@ int main(int argc, char *argv[])
         if (J.censored) die("--tensor does not go together with --censored");
         if (J.weighted) die("--tensor does not go together with --weights");
         if (J.robust) die("--tensor does not go together with --robust");
+        if (J.implicit) die("--implicit does not go together with --tensor (a mode's side is a plain Gaussian side)");
+        if (rank_eval_given || rank_by_given || J.rank_thr_given) die("--tensor does not go together with --rank-eval");
         if (noise != "fixed" || !alpha_prior.empty() || !alpha_max.empty()) die("--tensor does not go together with --noise adaptive");
         if (!row_features.empty() || !col_features.empty() || !new_row_features.empty() || !new_col_features.empty() || !lambda_beta.empty() ||
             !lambda_beta_prior.empty() || !link_tol.empty() || !link_max_iter.empty())
@@ -1307,6 +1403,44 @@ int main(int argc, char *argv[])
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--robust does not go together with BPMF_REDUCE=1");
         if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--robust needs a noise precision -a F > 0");
     }
+    // --implicit: checked before anything touches a GPU (the confidences below, once --weights FILE is read)
+    if (J.implicit) {
+        char *end = nullptr;
+        J.implicit_w0 = implicit_w0.empty() ? NAN : strtod(implicit_w0.c_str(), &end);
+        if (implicit_w0.empty() || *end != '\0' || !std::isfinite(J.implicit_w0) || !(J.implicit_w0 > 0.0))
+            die("--implicit expects the weight W0 of an unobserved cell, a finite number > 0, not '" + implicit_w0 + "'");
+        if (ngpu >= 1) die("--implicit runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the Gram matrix needs the other side whole)");
+        if (fp32) die("--implicit does not go together with --fp32 (the weighted samplers are fp64)");
+        if (J.probit) die("--implicit does not go together with --probit (a side has one likelihood)");
+        if (J.ordinal) die("--implicit does not go together with --ordinal (a side has one likelihood)");
+        if (J.robust) die("--implicit does not go together with --robust (the weights of Student-t noise are redrawn in every half-iteration)");
+        if (J.censored) die("--implicit does not go together with --censored (the latent draw would need the confidence of its cell)");
+        if (J.adaptive) die("--implicit does not go together with --noise adaptive (alpha | r would need the residuals of every cell)");
+        if (linked) die("--implicit does not go together with --row-features / --col-features (the link matrix would need the weighted residuals)");
+        if (!mname.empty() || !lname.empty()) die("--implicit does not go together with a propagated posterior (-m / -l)");
+        if (!fold_in_rows.empty() || !fold_in_cols.empty()) die("--implicit does not go together with --fold-in-rows / --fold-in-cols (a folded-in row would need the Gram matrix)");
+        if (topn_score == "prob" || topn_score == "ei")
+            die("--implicit does not go together with --topn-score " + topn_score + " (its sigma = 1 / sqrt(alpha) is not the noise of a cell; mean and ucb are fine)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--implicit does not go together with BPMF_REDUCE=1");
+        if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--implicit needs a noise precision -a F > 0");
+        if (!J.weighted && !(1.0 > J.implicit_w0)) die("--implicit " + implicit_w0 + ": without --weights every observed cell has the confidence 1, which is not > W0");
+    }
+    // --rank-eval / --rank-by / --rank-threshold: checked before anything touches a GPU
+    if ((rank_by_given || J.rank_thr_given) && !rank_eval_given) die(std::string(rank_by_given ? "--rank-by" : "--rank-threshold") + " needs --rank-eval N");
+    if (rank_eval_given) {
+        char *end = nullptr;
+        const long n = rank_eval_n.empty() ? 0 : strtol(rank_eval_n.c_str(), &end, 10);
+        if (rank_eval_n.empty() || *end != '\0' || n < 1 || n > 1000) die("--rank-eval expects 1 <= N <= 1000, not '" + rank_eval_n + "'");
+        J.rank_eval = (int)n;
+        if (rank_by != "rows" && rank_by != "cols") die("--rank-by expects rows or cols, not '" + rank_by + "'");
+        J.rank_by_cols = rank_by == "cols";
+        if (J.rank_thr_given) {
+            J.rank_thr = rank_threshold.empty() ? NAN : strtod(rank_threshold.c_str(), &end);
+            if (rank_threshold.empty() || *end != '\0' || !std::isfinite(J.rank_thr)) die("--rank-threshold expects a finite number, not '" + rank_threshold + "'");
+        } else if (J.implicit) { J.rank_thr_given = true; J.rank_thr = 0.0; }
+        if (ngpu > 1) die("--rank-eval runs on one GPU: -g " + std::to_string(ngpu) + " is not supported (the sharded replicas are not complete on every rank)");
+        if (J.nsims <= J.burnin) die("--rank-eval needs at least one post-burn-in sample (-i > -b)");
+    }
     // --fold-in-rows / --fold-in-cols: checked before anything touches a GPU (the files themselves below, once the shape is known)
     for (int which = 0; which < 2; ++which) {
         const std::string &name = which ? fold_in_cols : fold_in_rows;
@@ -1390,6 +1524,15 @@ int main(int argc, char *argv[])
                 first = false;
             }
         if ((int64_t)W.vals.size() < J.M.nnz()) { J.w_min = std::min(J.w_min, 1.0); J.w_max = std::max(J.w_max, 1.0); }   // (the unlisted cells)
+        if (J.implicit)                                              // the weights are the confidences: every one above W0
+            for (int64_t c = 0; c < WF.ncols; ++c)
+                for (int64_t q = WF.colptr[(size_t)c]; q < WF.colptr[(size_t)c + 1]; ++q)
+                    if (!(WF.vals[(size_t)q] > J.implicit_w0)) {
+                        char v[32];
+                        snprintf(v, sizeof v, "%g", WF.vals[(size_t)q]);
+                        die("--implicit " + implicit_w0 + ": the confidence " + v + " of cell (" + std::to_string((long long)WF.rowidx[(size_t)q] + 1) + ", " +
+                            std::to_string((long long)c + 1) + ") is not > W0");
+                    }
     }
     const int64_t rows = std::max(J.M.nrows, J.T.nrows), cols = std::max(J.M.ncols, J.T.ncols);
     if (J.censored) bpmf::io::resize(CF, rows, cols);
@@ -1404,6 +1547,7 @@ int main(int argc, char *argv[])
     for (double v : J.Mt.vals) usum += v;
     J.mean_m = msum / (double)J.M.nnz(); J.mean_u = usum / (double)J.Mt.nnz();
     if (J.probit) J.mean_m = J.mean_u = 0.0;                    // labels, not measurements: the latent scores are centred at 0
+    if (J.implicit) J.mean_m = J.mean_u = 0.0;                  // every cell is observed, most of them as zeros: the model has mean 0
     if (J.ordinal) {                                            // levels, not measurements; still before anything touches a GPU
         J.mean_m = J.mean_u = 0.0;
         if (J.ord_levels.empty()) {                             // the distinct training values
@@ -1583,6 +1727,18 @@ int main(int argc, char *argv[])
         if (J.w_m.empty()) { J.w_m.assign(1, 1.0); J.w_u.assign(1, 1.0); }
     }
     J.Tt = bpmf::io::transpose(J.T);
+    if (J.rank_eval > 0) {                                           // the held-out candidates of every query, ascending (the run's numbering)
+        const Csc &Q = J.rank_by_cols ? J.T : J.Tt;                  // one column per query
+        J.rank_tptr.assign((size_t)Q.ncols + 1, 0);
+        for (int64_t q = 0; q < Q.ncols; ++q) {
+            std::vector<int32_t> c;
+            for (int64_t p = Q.colptr[(size_t)q]; p < Q.colptr[(size_t)q + 1]; ++p)
+                if (!J.rank_thr_given || Q.vals[(size_t)p] > J.rank_thr) c.push_back(Q.rowidx[(size_t)p]);
+            std::sort(c.begin(), c.end());
+            J.rank_tcand.insert(J.rank_tcand.end(), c.begin(), c.end());
+            J.rank_tptr[(size_t)q + 1] = (int64_t)J.rank_tcand.size();
+        }
+    }
     if (J.sharded) check(bpmf_hip_comm_unique_id(J.rccl_id));      // (also loads RCCL before the rank threads start)
     if (!J.odirname.empty()) {
         J.pavg.assign(J.T.vals.size(), 0.0); J.pm2.assign(J.T.vals.size(), 0.0);
@@ -1684,6 +1840,29 @@ int main(int argc, char *argv[])
                 else fprintf(f, "%lld,%d,%lld,%.17g,%.17g,%.17g\n", qid, r + 1, cid, J.topn_score[at], J.topn_mean[at], J.topn_std[at]);
             }
         if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
+    }
+
+    // --rank-eval: the metrics (the arithmetic of bpmf_amd.rank_metrics), and with -o DIR the rank of every held-out entry
+    RankMetrics rkm;
+    if (J.rank_eval > 0) {
+        rkm = rank_metrics(J.rank_rank, J.rank_tptr, J.rank_ncand, J.rank_eval);
+        if (!J.odirname.empty()) {                                   // 1-based ids in the ORIGINAL numbering, the queries in their order
+            const std::vector<int64_t> &pq = J.rank_by_cols ? J.perm_m : J.perm_u, &pc = J.rank_by_cols ? J.perm_u : J.perm_m;
+            const int64_t nq = (int64_t)J.rank_tptr.size() - 1;
+            std::vector<int64_t> order((size_t)nq);
+            for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
+            if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
+            FILE *f = fopen((J.odirname + "/ranks.csv").c_str(), "w");
+            if (!f) die("cannot write " + J.odirname + "/ranks.csv");
+            fprintf(f, "query,candidate,rank,ncand\n");
+            for (int64_t q : order)
+                for (int64_t p = J.rank_tptr[(size_t)q]; p < J.rank_tptr[(size_t)q + 1]; ++p) {
+                    const int32_t c = J.rank_tcand[(size_t)p];
+                    fprintf(f, "%lld,%lld,%d,%d\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), (long long)((pc.empty() ? c : pc[(size_t)c]) + 1),
+                            J.rank_rank[(size_t)p], J.rank_ncand[(size_t)q]);
+                }
+            if (fclose(f) != 0) die("cannot write " + J.odirname + "/ranks.csv");
+        }
     }
 
     // the new entities: new x movies as it is computed; users x new = the transpose of what is computed (row-major new x users IS
@@ -1808,6 +1987,13 @@ int main(int argc, char *argv[])
     if (J.probit && !J.prob.empty()) {
         os << "Final AUC: " << J.auc << std::endl;
         os << "Final Brier: " << J.brier << std::endl;
+    }
+    if (J.rank_eval > 0) {
+        os << "Final recall@" << J.rank_eval << ": " << rkm.recall << std::endl;
+        os << "Final NDCG@" << J.rank_eval << ": " << rkm.ndcg << std::endl;
+        os << "Final MRR: " << rkm.mrr << std::endl;
+        os << "Final MPR: " << rkm.mpr << std::endl;
+        os << "Final rank AUC: " << rkm.auc << std::endl;
     }
     os << "  computed on " << J.num_predict << " items (" << (J.T.nnz() ? int(100. * (double)J.num_predict / (double)J.T.nnz()) : 0)
        << "% of total items in test set)" << std::endl;

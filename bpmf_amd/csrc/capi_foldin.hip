@@ -76,6 +76,7 @@ TopnRings foldin_rings(const bpmf_foldin *f, const bpmf_ring *cr)
 extern "C" int bpmf_hip_side_hyper_reserve(bpmf_hip_side *s, int max_samples)
 {
     if (!s || max_samples < 0) return fail(BPMF_HIP_EINVAL, "side_hyper_reserve: bad argument");
+    if (max_samples > 0 && s->implicit) return fail(BPMF_HIP_EINVAL, "side_hyper_reserve: not on an implicit side (fold-in under the implicit model would need G)");
     if (max_samples == 0) {
         if (s->foldin) {
             bpmf_foldin *f = s->foldin.get();

@@ -13,6 +13,7 @@
 //   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities
 //   capi_censor.hip    censored ratings: the bounded latent values ahead of every sampler launch of a side with censored entries
 //   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
+//   capi_implicit.hip  implicit feedback: unobserved cells as zeros of weight w0 behind the weighted samplers, the blocking half-iteration bpmf_hip_implicit_sample
 //   capi_robust.hip    Student-t noise: the weights of a side redrawn on the device ahead of every sampler launch, their posterior mean
 //   capi_tensor.hip    sparse tensor factorisation (CP, order 3): a side per mode behind the Khatri-Rao rows of the other two, test entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample

@@ -223,6 +223,8 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
     bpmf_hip_ctx *c = self->ctx;
     { const int rc = require_single_gpu("link_sample", c, self, other); if (rc) return rc; }
     bpmf_link *L = self->link.get();
+    if (self->implicit || other->implicit)
+        return fail(BPMF_HIP_EINVAL, "link_sample: the model is implicit: step BOTH sides with bpmf_hip_implicit_sample");
     if (L && (self->reduce_on || self->probit || self->d_prop))
         return fail(BPMF_HIP_EINVAL, "link_sample: features do not go together with BPMF_REDUCE, a probit side or propagated priors");
     HIP_TRY(hipSetDevice(c->device));

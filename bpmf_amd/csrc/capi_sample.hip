@@ -254,6 +254,8 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     if (self->pending) return fail(BPMF_HIP_EINVAL, "sample_side_launch: previous launch not finished");
     if (self->link && !self->link->in_call)
         return fail(BPMF_HIP_EINVAL, "sample_side: the side has features: step it with bpmf_hip_link_sample");
+    if (self->implicit && !self->implicit->in_call)
+        return fail(BPMF_HIP_EINVAL, "sample_side: the side is implicit: step it with bpmf_hip_implicit_sample");
     self->probit_latent_queued = false;                               // (a stateful call that failed half-way may have left it set)
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sample_side: the communicator of this context was aborted (a collective timed out)");
     const int K = c->K;
@@ -261,6 +263,15 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     { const int rs = settle_async(self); if (rs) return rs; }
     if (self->saux) { const int rs_ = bounded_stream_sync(self->ctx, self->saux, __func__); if (rs_) return rs_; }
     fill_blob_ctx(c, mu, LambdaF, c->h_in, K == 64 && c->dtype == BPMF_HIP_F64 && self->lr_n > 0);
+    if (self->implicit) {
+        // implicit side: the prior precision becomes Lambda + alpha w0 G in the leading Kt x Kt block, behind Lmu = Lambda mu (which
+        // keeps the plain Lambda); a weighted side never launches the product form, so the factor tail of the blob goes unread
+        const int Kt = c->Kt;
+        const double *g = self->implicit->prior.data();
+        double *lf = c->h_in + blob::par_LambdaF(K);
+        for (int j = 0; j < Kt; ++j)
+            for (int i = 0; i < Kt; ++i) lf[(size_t)j * K + i] += g[(size_t)j * Kt + i];
+    }
     bpmf_launch::stage(c->h_in_dev, c->d_in, (int)c->in_words, c->stream);
     if (lf32_words(c)) bpmf_launch::lf32_tiles(c->d_in, reinterpret_cast<float *>(c->d_in + c->in_words), K, c->stream);
     HIP_TRY(hipEventRecord(c->ev[0], c->stream));
@@ -694,6 +705,8 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "sys_sample: other side has the wrong number of columns");
     if (self->link)
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side has features: step BOTH sides of the model with bpmf_hip_link_sample");
+    if (self->implicit || other->implicit)
+        return fail(BPMF_HIP_EINVAL, "sys_sample: the model is implicit: step BOTH sides with bpmf_hip_implicit_sample");
     if (self->to - self->from != self->ncols && !(c->comm && !self->bounds.empty()))
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side is a shard: give the context a communicator "
                                      "(bpmf_hip_ctx_comm_init) and the side its ranges (bpmf_hip_side_set_ranges), "

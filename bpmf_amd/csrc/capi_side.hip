@@ -359,7 +359,7 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
     if (s->own_items && s->d_items) (void)hipFree(s->d_items);
     if (s->d_items_alt) (void)hipFree(s->d_items_alt);
     if (s->d_prop) (void)hipFree(s->d_prop);
-    s->probit.reset(); s->ordinal.reset(); s->censor.reset(); s->weights.reset(); s->robust.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
+    s->probit.reset(); s->ordinal.reset(); s->censor.reset(); s->weights.reset(); s->implicit.reset(); s->robust.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
     if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
     if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
     void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,

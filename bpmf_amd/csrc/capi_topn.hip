@@ -1,4 +1,5 @@
-// capi_topn.hip -- sample rings of the sides and the posterior top-N ranking (bpmf_hip_topn; kernels in kernels_topn.h)
+// capi_topn.hip -- sample rings of the sides, the posterior top-N ranking (bpmf_hip_topn; kernels in kernels_topn.h) and the ranks of
+// held-out candidates (bpmf_hip_rank_eval; kernels in kernels_rank.h)
 // (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
 #include "capi_internal.h"
 
@@ -48,21 +49,31 @@ extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
 
 extern "C" int bpmf_hip_side_samples_count(const bpmf_hip_side *s) { return s && s->ring ? s->ring->count : 0; }
 
-// the rated candidates of every column of the side, sorted: read back from the device ratings once
-static int build_exclusion(bpmf_hip_side *s)
+// the rated candidates of every column of the side, sorted, on the host: read back from the device ratings
+static int sorted_rows(bpmf_hip_side *s, std::vector<int32_t> &rows)
 {
-    if (s->ring->ex_ptr) return 0;
     if (s->from != 0 || s->to != s->ncols)
         return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs a query side that holds all its columns (this rank has " +
                     std::to_string((long long)s->from) + " .. " + std::to_string((long long)s->to) + ")");
     bpmf_hip_ctx *c = s->ctx;
     { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
     const std::vector<int64_t> &cp = s->h_colptr;
-    std::vector<int32_t> rows((size_t)std::max<int64_t>(s->nnz, 1));
+    rows.assign((size_t)std::max<int64_t>(s->nnz, 1), 0);
     if (s->nnz > 0) HIP_TRY(hipMemcpy(rows.data(), s->d_rowidx, (size_t)s->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int64_t q = 0; q < s->ncols; ++q) std::sort(rows.begin() + cp[(size_t)q], rows.begin() + cp[(size_t)q + 1]);
+    return 0;
+}
+
+// the exclusion lists of the side's ring, built on the first ranking that excludes the rated candidates.  host_rows: also wanted on the host
+static int build_exclusion(bpmf_hip_side *s, std::vector<int32_t> *host_rows = nullptr)
+{
+    if (s->ring->ex_ptr) return host_rows ? sorted_rows(s, *host_rows) : 0;
+    std::vector<int32_t> local;
+    std::vector<int32_t> &rows = host_rows ? *host_rows : local;
+    int rc = sorted_rows(s, rows);
+    if (rc) return rc;
+    const std::vector<int64_t> &cp = s->h_colptr;
     DevBuf<int64_t> ptr; DevBuf<int32_t> sorted;
-    int rc;
     if ((rc = ptr.upload(cp.data(), cp.size())) || (rc = sorted.upload(rows.data(), rows.size()))) return rc;
     s->ring->ex_ptr = std::move(ptr); s->ring->ex_rows = std::move(sorted);
     return 0;
@@ -200,5 +211,86 @@ extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, d
         hipMemcpy(std_out, out.get() + 2 * pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(BPMF_HIP_ENODEV, "topn_scored: copying the results back failed");
+    return BPMF_HIP_OK;
+}
+
+// rank of every held-out (query, candidate) among the candidates the query has not rated, by bpmf_hip_topn's score and order
+// (kernels_rank.h)
+extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                  int exclude_rated, const int64_t *tptr, const int32_t *tcand, int32_t *rank_out, int32_t *ncand_out)
+{
+    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL side");
+    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "rank_eval: the two sides belong to different contexts");
+    if (!std::isfinite(mean_rating)) return fail(BPMF_HIP_EINVAL, "rank_eval: mean_rating is not finite");
+    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "rank_eval: query range out of bounds");
+    const int64_t nq = q_to - q_from, nc = cand->ncols;
+    if (!tptr) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL held-out pointer array");
+    if (tptr[0] != 0) return fail(BPMF_HIP_EINVAL, "rank_eval: tptr[0] must be 0");
+    for (int64_t q = 0; q < nq; ++q)
+        if (tptr[q + 1] < tptr[q]) return fail(BPMF_HIP_EINVAL, "rank_eval: tptr decreases at query " + std::to_string((long long)(q_from + q)));
+    const int64_t nt = tptr[nq];
+    if (nt > 0 && (!tcand || !rank_out)) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL held-out array");
+    if (nq > 0 && !ncand_out) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL output");
+    if (nc > std::numeric_limits<int32_t>::max()) return fail(BPMF_HIP_EINVAL, "rank_eval: too many candidates");
+    for (int64_t q = 0; q < nq; ++q)
+        for (int64_t p = tptr[q]; p < tptr[q + 1]; ++p) {
+            if (tcand[p] < 0 || tcand[p] >= nc)
+                return fail(BPMF_HIP_EINVAL, "rank_eval: held-out candidate " + std::to_string(tcand[p]) + " of query " +
+                            std::to_string((long long)(q_from + q)) + " is out of range");
+            if (p > tptr[q] && tcand[p] <= tcand[p - 1])
+                return fail(BPMF_HIP_EINVAL, "rank_eval: the held-out candidates of query " + std::to_string((long long)(q_from + q)) +
+                            " are not ascending and distinct (" + std::to_string(tcand[p - 1]) + ", " + std::to_string(tcand[p]) + ")");
+        }
+    bpmf_hip_ctx *c = query->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(query); if (rc) return rc; }
+    { const int rc = settle_async(cand); if (rc) return rc; }
+    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "rank_eval: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
+    const int S = qr->count;
+    if (S < 1 || cr->count != S)
+        return fail(BPMF_HIP_EINVAL, "rank_eval: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
+                    std::to_string(cr->count));
+    if (exclude_rated && query->nrows != cand->ncols)
+        return fail(BPMF_HIP_EINVAL, "rank_eval: exclude_rated needs the query side's rows to be the candidate side's columns");
+    if (nq == 0) return BPMF_HIP_OK;
+    if (exclude_rated) {
+        // a held-out entry that is a rated cell would be scored -inf: refused while the lists are on the host
+        std::vector<int32_t> rows;
+        { const int rc = build_exclusion(query, &rows); if (rc) return rc; }
+        const std::vector<int64_t> &cp = query->h_colptr;
+        for (int64_t q = 0; q < nq; ++q) {
+            const auto b = rows.begin() + cp[(size_t)(q_from + q)], e = rows.begin() + cp[(size_t)(q_from + q) + 1];
+            for (int64_t p = tptr[q]; p < tptr[q + 1]; ++p)
+                if (std::binary_search(b, e, tcand[p]))
+                    return fail(BPMF_HIP_EINVAL, "rank_eval: the held-out cell (query " + std::to_string((long long)(q_from + q)) + ", candidate " +
+                                std::to_string(tcand[p]) + ") is a rated cell of the query side");
+        }
+    }
+    int64_t nsplit, cspan;
+    topn_splits(c, nq, nc, &nsplit, &cspan);
+    DevBuf<int64_t> d_tptr;
+    DevBuf<int32_t> d_tcand, part_cnt, part_ncand, d_rank, d_ncand;
+    DevBuf<double> tscore;
+    const size_t ntz = (size_t)std::max<int64_t>(nt, 1);
+    int rc;
+    if ((rc = d_tptr.upload(tptr, (size_t)nq + 1)) || (rc = d_tcand.upload(nt > 0 ? tcand : nullptr, (size_t)nt)) || (rc = tscore.alloc(ntz)) ||
+        (rc = part_cnt.alloc((size_t)nsplit * ntz)) || (rc = part_ncand.alloc((size_t)nsplit * (size_t)nq)) || (rc = d_rank.alloc(ntz)) ||
+        (rc = d_ncand.alloc((size_t)nq)))
+        return rc;
+    bpmf_launch::RankLaunch p{};
+    p.qring = qr->samples.get(); p.cring = cr->samples.get();
+    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
+    p.Kp = qr->kp; p.S = S; p.mean_rating = mean_rating;
+    p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
+    p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
+    p.tptr = d_tptr.get(); p.tcand = d_tcand.get(); p.nt = nt; p.tscore = tscore.get();
+    p.part_cnt = part_cnt.get(); p.part_ncand = part_ncand.get(); p.rank = d_rank.get(); p.ncand = d_ncand.get();
+    bpmf_launch::rank_eval(p, c->stream);
+    if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "rank_eval: kernel launch failed");
+    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    if ((nt > 0 && hipMemcpy(rank_out, d_rank.get(), (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) ||
+        hipMemcpy(ncand_out, d_ncand.get(), (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(BPMF_HIP_ENODEV, "rank_eval: copying the results back failed");
     return BPMF_HIP_OK;
 }

@@ -12,6 +12,7 @@ extern "C" int bpmf_hip_side_set_weights(bpmf_hip_side *s, const double *w)
     if (!s || !w) return fail(BPMF_HIP_EINVAL, "side_set_weights: NULL argument");
     bpmf_hip_ctx *c = s->ctx;
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an fp32 context");
+    if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an implicit side (bpmf_hip_side_set_implicit takes the confidences itself)");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a side with Student-t noise (bpmf_hip_side_set_robust redraws the weights itself)");
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a probit side (bpmf_hip_side_set_probit)");
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a censored side (bpmf_hip_side_set_censored)");

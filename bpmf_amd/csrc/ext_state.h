@@ -62,6 +62,13 @@ struct bpmf_censor {
 // (layout of d_vals).  The weighted forms of the samplers read zw in place of d_vals with mean 0 and multiply every gathered row by sw.
 struct bpmf_weights { DevBuf<double> sw, zw; int64_t nweighted = 0; double wmin = 1.0, wmax = 1.0; };
 
+// implicit feedback (capi_implicit.hip): every cell of the matrix is observed, an unobserved one as r = 0 with
+// weight w0.  The side's bpmf_weights hold sw = sqrt(w - w0) and zw = w r / sqrt(w - w0); gram: G = sum over ALL columns of the other
+// side of u u^T (Kt x Kt), formed on the device ahead of every half-iteration, part: the chunk partials of that product; prior: alpha
+// w0 G on the host, added to the LambdaF of the parameter blob behind Lmu.  in_call: bpmf_hip_implicit_sample is driving the
+// stateless half-iteration of this side.
+struct bpmf_implicit { double w0 = 0.0; bool in_call = false; DevBuf<double> gram, part; std::vector<double> prior; };
+
 // Student-t noise (capi_robust.hip): the side's bpmf_weights are redrawn on the device ahead of every sampler
 // launch.  nu: the degrees of freedom; wsum: the running sum of w over the kept samples (layout of d_vals), `kept` of them; the word
 // the weight kernel raises to a rating position when a draw runs into its attempt cap or meets a residual that is not finite

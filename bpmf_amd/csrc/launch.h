@@ -141,6 +141,19 @@ struct TopnLaunch {
 };
 void topn(const TopnLaunch &p, hipStream_t st);             // score + select, merge of the splits, std of the selected pairs
 
+// ranks of held-out candidates among the candidates a query has not rated (kernels_rank.h, krank.hip)
+struct RankLaunch {
+    const double *qring, *cring; int64_t qstride, cstride;
+    int Kp, S; double mean_rating;
+    int64_t q_from, nq, nc, cspan; int nsplit;
+    const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
+    const int64_t *tptr; const int32_t *tcand; int64_t nt; // held-out entries of query q: tcand[tptr[q] .. tptr[q + 1]), ascending; nt = tptr[nq]
+    double *tscore;                                        // nt
+    int32_t *part_cnt, *part_ncand;                        // nsplit x nt, nsplit x nq
+    int32_t *rank, *ncand;                                 // nt, nq
+};
+void rank_eval(const RankLaunch &p, hipStream_t st);        // the scores of the entries, the counts, the sum of the splits
+
 // posterior top-N by an acquisition score (kernels_topn_score.h, ktopnscore.hip)
 struct TopnScoredLaunch {
     const double *qring, *cring; int64_t qstride, cstride;

@@ -215,6 +215,7 @@ struct bpmf_hip_side {
     std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
     std::unique_ptr<bpmf_ordinal> ordinal; // ordinal probit likelihood (bpmf_hip_side_set_ordinal)
     std::unique_ptr<bpmf_weights> weights; // per-rating precision weights (bpmf_hip_side_set_weights)
+    std::unique_ptr<bpmf_implicit> implicit; // implicit feedback: unobserved cells are zeros of weight w0 (bpmf_hip_side_set_implicit)
     std::unique_ptr<bpmf_robust> robust;   // Student-t noise: the weights are redrawn per launch (bpmf_hip_side_set_robust)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)

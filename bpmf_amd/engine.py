@@ -276,6 +276,28 @@ class HipEngine:
                                           1 if exclude_rated else 0, _ptr(idx), _ptr(mean), _ptr(std)))
         return idx, mean, std
 
+    def rank_eval(self, query, cand, tptr, tcand, mean_rating=0.0, q_from=0, q_to=None, exclude_rated=True):
+        """Ranks of held-out candidates by topn's score and order.  Query q_from + q holds out the candidates
+        tcand[tptr[q] : tptr[q + 1]], ascending and distinct.  Returns (rank int32[len(tcand)], ncand int32[nq]): rank is 1 + the
+        number of other candidates the query has not rated (exclude_rated) that come before the entry, ncand the number of
+        candidates the query has not rated.  A held-out entry that is a rated cell of the query is refused."""
+        q_to = query.ncols if q_to is None else int(q_to)
+        nq = max(0, q_to - int(q_from))
+        tptr = np.ascontiguousarray(tptr, np.int64)
+        tcand = np.ascontiguousarray(tcand, np.int32)
+        if tptr.ndim != 1 or len(tptr) != nq + 1:
+            raise ValueError("rank_eval: tptr must hold %d entries (one per query, plus one), not %s" % (nq + 1, tptr.shape))
+        if tcand.ndim != 1 or len(tcand) != int(tptr[-1]):
+            raise ValueError("rank_eval: tcand holds %d entries, tptr ends at %d" % (tcand.size, int(tptr[-1])))
+        rank = np.empty(len(tcand), dtype=np.int32)
+        ncand = np.empty(nq, dtype=np.int32)
+        tc = tcand if len(tcand) else np.zeros(1, np.int32)
+        rk = rank if len(rank) else np.zeros(1, np.int32)
+        nc = ncand if nq else np.zeros(1, np.int32)
+        _lib.check(self.lib.bpmf_hip_rank_eval(query.handle, cand.handle, float(mean_rating), int(q_from), int(q_to),
+                                               1 if exclude_rated else 0, _ptr(tptr), _ptr(tc), _ptr(rk), _ptr(nc)))
+        return rank, ncand
+
     SCORE_KINDS = {"ucb": 0, "prob": 1, "ei": 2}     # BPMF_HIP_SCORE_*
 
     def topn_scored(self, query, cand, mean_rating, n, kind, param, sigma=0.0, q_from=0, q_to=None, exclude_rated=True):
@@ -638,6 +660,36 @@ class HipEngine:
         if len(w) == 0:
             w = np.ones(1)
         _lib.check(self.lib.bpmf_hip_side_set_weights(side.handle, _ptr(w)))
+
+    # -- implicit feedback ----------------------------------------------------------
+    def set_implicit(self, side, w0, w=None):
+        """Makes `side` an implicit side: every cell of the matrix is observed, an unobserved one as a zero
+        of weight w0, rating p with its value and the confidence w[p] > w0 (None: every confidence is 1, which needs w0 < 1).  The
+        side's mean rating must be 0.  Both sides of a model are implicit and are stepped with implicit_sample.  weights_get
+        returns sqrt(w - w0) and w r / sqrt(w - w0).  fp64 contexts, one GPU; not with weights, Student-t noise, a probit, ordinal
+        or censored likelihood, features, propagated priors, BPMF_REDUCE or fold-in."""
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            if w.ndim != 1 or len(w) != side.nnz:
+                raise ValueError("set_implicit: %s confidences for a side of %d ratings" % (w.shape, side.nnz))
+            if len(w) == 0:
+                w = None
+        _lib.check(self.lib.bpmf_hip_side_set_implicit(side.handle, float(w0), _ptr(w) if w is not None else None))
+
+    def implicit_w0(self, side):
+        """w0 of an implicit side, 0.0 for any other side."""
+        return float(self.lib.bpmf_hip_side_implicit_w0(side.handle))
+
+    def implicit_gram(self, side):
+        """G (K x K) of the side's newest implicit_sample: the sum of u u^T over every column of the other side."""
+        G = np.empty((self.K, self.K))
+        _lib.check(self.lib.bpmf_hip_side_implicit_gram(side.handle, _ptr(G)))
+        return G
+
+    def implicit_sample(self, side, other, alpha):
+        """One blocking half-iteration of an implicit side: hyper-parameters, G of `other` on the device, the weighted samplers
+        under the prior precision Lambda + alpha w0 G (bpmf_hip_implicit_sample)."""
+        _lib.check(self.lib.bpmf_hip_implicit_sample(side.handle, other.handle, float(alpha)))
 
     def weights_get(self, side):
         """(sw, zw) of a side with weights as the device holds them: sqrt(w) and sqrt(w) (r - mean_rating), in the ratings' order."""

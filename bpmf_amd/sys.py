@@ -15,6 +15,7 @@ import numpy as np
 from . import engine as _engine
 from .censor import censor_flags, transpose_csc
 from .weights import rating_weights
+from .rank import held_out_lists, rank_metrics
 
 
 class HyperParams:
@@ -110,6 +111,12 @@ class Sys:
 
     # -- Sys::sample(Sys&), c++/sample.cpp:341-385 ------------------------------
     def sample(self, other):
+        if getattr(self, "implicit", False):
+            # an implicit model: BOTH sides take the blocking half-iteration that forms G
+            self.engine.implicit_sample(self.side, other.side, Sys.alpha)
+            self.iter += 1
+            self._stale = True
+            return
         if getattr(self, "linked", False):
             # a model with side information: BOTH sides take the blocking half-iteration
             self.engine.link_sample(self.side, other.side, Sys.alpha)
@@ -189,7 +196,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
-          ordinal=None, cutpoints=None, ordinal_step=None):
+          ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -308,7 +315,66 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     refused).  The RMSE columns of the trace compare the latent score u . v with the raw value and are not an error measure.  topn
     ranks by the latent score, and the thresholds of topn_score "prob" / "ei" are on that scale.  foldin, features,
     noise="adaptive", censored, weights, robust and probit=True are refused with ordinal.  None / False (the default): nothing
-    changes."""
+    changes.
+
+    implicit=W0: implicit feedback.  EVERY cell of the matrix is observed with precision alpha w: a cell that
+    M does not store as r = 0 with w = W0 (finite, > 0), a stored cell with its value and the confidence w = 1 -- or, with weights=W,
+    the listed entry of W, which must be > W0 (as must 1 when a stored cell is not listed).  Both sides are created with mean
+    rating 0, become implicit sides (engine.set_implicit) and are stepped with engine.implicit_sample, the blocking half-iteration
+    that forms G = sum of u u^T over all columns of the other side on the device and samples under the prior precision Lambda +
+    alpha W0 G; the column samplers are the weighted ones, unchanged.  With or without topn, topn_score "ucb" and rank_eval; the
+    RMSE columns are over the test cells as given.  pipelined=True, probit=True, ordinal, robust, censored, noise="adaptive",
+    features, foldin, topn_score "prob" / "ei" and an fp32 engine are refused with implicit.  res["implicit"] = dict(w0, observed =
+    the stored cells, cells = nusers * nmovies, weights = (confidences that are not 1, smallest, largest)).  None (the default):
+    nothing changes.
+
+    rank_eval=N (1 .. 1000): ranked evaluation of the test cells after the chain.  Needs nsims > burnin; the
+    sample rings are reserved as for topn.  rank_by="rows": the users are the queries and the movies the candidates ("cols": the
+    other way round).  The held-out items are the test cells with a value > rank_threshold (None: every test cell, or value > 0
+    under implicit); engine.rank_eval gives each its rank among the candidates its query has not rated in M, by topn's score.
+    res["rank"] = bpmf_amd.rank_metrics(...) at N (recall, ndcg, mrr, mpr, auc, queries, entries) plus n = N, by, rank = the
+    rank per test cell in T's order (0 for a cell the threshold left out) and ncand = the candidates left per query.  A test cell
+    that is also a training cell is refused.  Works with every likelihood topn works with.  None (the default): nothing changes."""
+    if implicit is not None:                         # (refused before the engine is used)
+        try:
+            implicit = float(implicit)
+        except (TypeError, ValueError):
+            raise ValueError("implicit must be a number: the weight w0 of an unobserved cell")
+        if not (math.isfinite(implicit) and implicit > 0.0):
+            raise ValueError("implicit = %r: w0 must be finite and > 0" % (implicit,))
+        for on, what, why in ((pipelined, "pipelined=True", "the implicit loop is blocking: G of the other side is formed ahead of every half-iteration"),
+                              (probit, "probit=True", "a side has one likelihood"),
+                              (ordinal is not None and ordinal is not False, "ordinal", "a side has one likelihood"),
+                              (robust is not None, "robust", "the weights of a robust side are redrawn in every half-iteration"),
+                              (censored is not None, "censored", "the latent draw would need the confidence of its cell"),
+                              (noise == "adaptive", "noise='adaptive'", "alpha | r would need the residuals of every cell"),
+                              (row_features is not None or col_features is not None, "row_features / col_features",
+                               "the link matrix would need the weighted residuals"),
+                              (foldin, "foldin=True", "a folded-in row would need G"),
+                              (isinstance(topn_score, (tuple, list)) and len(topn_score) > 0 and topn_score[0] in ("prob", "ei"),
+                               "topn_score 'prob' / 'ei'", "their sigma = 1 / sqrt(alpha) is not the noise of a cell; 'ucb' is fine"),
+                              (getattr(engine, "dtype", "f64") == "f32", "an fp32 engine", "the weighted samplers are fp64")):
+            if on:
+                raise ValueError("implicit does not go together with %s (%s)" % (what, why))
+        if alpha is not None and not (float(alpha) > 0 and math.isfinite(float(alpha))):
+            raise ValueError("implicit needs a finite alpha > 0")
+    if rank_eval is not None:                        # (refused before the engine is used)
+        if isinstance(rank_eval, bool) or int(rank_eval) != rank_eval or not (1 <= int(rank_eval) <= 1000):
+            raise ValueError("rank_eval = %r: the list length N must be an integer 1 .. 1000" % (rank_eval,))
+        rank_eval = int(rank_eval)
+        if rank_by not in ("rows", "cols"):
+            raise ValueError("rank_by must be 'rows' or 'cols', not %r" % (rank_by,))
+        if rank_threshold is not None and not math.isfinite(float(rank_threshold)):
+            raise ValueError("rank_threshold must be finite")
+        if nsims - burnin < 1:
+            raise ValueError("rank_eval needs at least one post-burn-in sample (nsims > burnin)")
+        if T is None:
+            raise ValueError("rank_eval needs a test matrix")
+        if rank_threshold is None and implicit is not None:
+            rank_threshold = 0.0
+        rk_tptr, rk_tcand, rk_cell = held_out_lists(T, nusers if rank_by == "rows" else nmovies, rank_by, rank_threshold)
+    elif rank_by != "rows" or rank_threshold is not None:
+        raise ValueError("rank_by / rank_threshold need rank_eval=N")
     ordinal_on = ordinal is not None and ordinal is not False
     if ordinal_on:                                   # (refused before the engine is used)
         for on, what, why in ((probit, "probit=True", "a side has one likelihood"),
@@ -371,7 +437,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
                              "'ucb' is fine)" % (topn_score[0],))
         if alpha is not None and not (float(alpha) > 0 and math.isfinite(float(alpha))):
             raise ValueError("robust needs a finite alpha > 0")
-    if weights is not None:                          # (refused before the engine is used)
+    if weights is not None and implicit is None:     # (refused before the engine is used)
         if probit:
             raise ValueError("weights does not go together with probit=True (the latent scores have unit variance)")
         if censored is not None:
@@ -475,9 +541,15 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         cflags = (censor_flags(M, censored), censor_flags(Mt, transpose_csc(censored, nusers)))
     if weights is not None:                          # (checked before a side is created)
         wts = (rating_weights(M, weights), rating_weights(Mt, transpose_csc(weights, nusers)))
+    if implicit is not None:
+        if weights is None:
+            wts = (np.ones(len(M[2])), np.ones(len(Mt[2])))
+        low = ~(wts[0] > implicit)
+        if low.any():
+            raise ValueError("implicit: the confidence %r of training rating %d is not > w0 = %r" % (float(wts[0][int(np.argmax(low))]), int(np.argmax(low)), implicit))
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
-    movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit or ordinal_on else None)
-    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit or ordinal_on else None)
+    movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit or ordinal_on or implicit is not None else None)
+    users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit or ordinal_on or implicit is not None else None)
     if ordinal_on:
         engine.set_ordinal(movies.side, ord_levels, cutpoints, ORDINAL_TAGS[0])
         engine.set_ordinal(users.side, ord_levels, engine.ordinal_cut_get(movies.side), ORDINAL_TAGS[1])   # (the same bits on both sides)
@@ -489,7 +561,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if censored is not None:
         engine.set_censored(movies.side, cflags[0], 5)
         engine.set_censored(users.side, cflags[1], 6)
-    if weights is not None:
+    if implicit is not None:
+        engine.set_implicit(movies.side, implicit, wts[0])
+        engine.set_implicit(users.side, implicit, wts[1])
+        movies.implicit = users.implicit = True
+    elif weights is not None:
         engine.set_weights(movies.side, wts[0])
         engine.set_weights(users.side, wts[1])
     if robust is not None:
@@ -512,8 +588,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if foldin and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -676,7 +752,15 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             res["logp"] = float("nan")
     if censored is not None:
         res["censored"] = engine.censored_count(movies.side)
-    if weights is not None:
+    if rank_eval is not None:
+        qs, cs = (users, movies) if rank_by == "rows" else (movies, users)
+        rk, ncand = engine.rank_eval(qs.side, cs.side, rk_tptr, rk_tcand, movies.mean_rating)
+        per_cell = np.zeros(len(T[2]), np.int32)
+        per_cell[rk_cell] = rk
+        res["rank"] = dict(rank_metrics(rk, rk_tptr, ncand, rank_eval), n=rank_eval, by=rank_by, rank=per_cell, ncand=ncand)
+    if implicit is not None:
+        res["implicit"] = dict(w0=implicit, observed=len(M[2]), cells=int(nusers) * int(nmovies), weights=engine.weights_count(movies.side))
+    elif weights is not None:
         res["weights"] = engine.weights_count(movies.side)
     if robust is not None:
         kept = max(nsims - burnin, 0)

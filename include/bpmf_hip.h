@@ -289,6 +289,19 @@ BPMF_API int bpmf_hip_side_samples_count(const bpmf_hip_side *side);
 BPMF_API int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                            int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out);
 
+/* Ranks of held-out candidates.  Query q_from + q (q = 0 .. q_to - q_from - 1) has the held-out candidates
+ * tcand[tptr[q] .. tptr[q + 1]), ascending and distinct.  With the score and the order of bpmf_hip_topn -- the same device code, the
+ * same bits --
+ *   rank_out[p]  = 1 + the number of candidates c' != tcand[p] in [0, cand's columns) that the query has not rated (exclude_rated != 0)
+ *                  and that come before tcand[p] (higher score, or the same score and a lower index)
+ *   ncand_out[q] = the number of candidates the query has not rated.
+ * Other held-out candidates of the query count as ordinary candidates.  Two sweeps over the products of bpmf_hip_topn: the scores of
+ * the held-out entries, then the counts; integer partials per candidate split, no atomics, no nq x nc buffer, no cap on the entries
+ * of a query.  Waits.  BPMF_HIP_EINVAL: no or unequal sample rings, a query range or candidate out of bounds, candidates of a query
+ * not ascending and distinct, and -- with exclude_rated -- a held-out entry that is a rated cell of the query (named). */
+BPMF_API int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
+                                int exclude_rated, const int64_t *tptr, const int32_t *tcand, int32_t *rank_out, int32_t *ncand_out);
+
 /* The n best candidates by an ACQUISITION SCORE of the per-sample predictions p_s instead of their mean.
  * With mean and std as bpmf_hip_predict_block computes them (w = NULL), Phi / phi the standard normal cdf / pdf and
  * z_s = (p_s - t) / sigma:
@@ -554,6 +567,35 @@ BPMF_API int bpmf_hip_side_set_weights(bpmf_hip_side *side, const double *w_host
 BPMF_API int bpmf_hip_side_weights_get(bpmf_hip_side *side, double *sw_host, double *zw_host);
 /* The number of ratings whose weight is not 1, the smallest and the largest weight of a side with weights. */
 BPMF_API int bpmf_hip_side_weights_count(bpmf_hip_side *side, int64_t *nweighted, double *wmin, double *wmax);
+
+/* ---- implicit feedback ----------------------------------------------------------------------------------
+ * Every cell (i, j) of the matrix is observed with precision alpha w_ij: an unobserved cell as r = 0 with w = w0, a stored cell with
+ * its value and a confidence w_ij > w0; the mean rating is 0 (Hu, Koren & Volinsky's confidence model as a Gibbs conditional).  The
+ * conditional of column j is the weighted column update with sw = sqrt(w - w0), zw = w r / sqrt(w - w0) under the prior precision
+ * Lambda + alpha w0 G, G = sum over ALL columns u of the other side of u u^T, with the right-hand side Lambda mu unchanged.
+ *
+ * bpmf_hip_side_set_implicit takes w0 and nnz confidences in the order of the side's ratings (NULL: every confidence is 1), forms sw
+ * and zw on the host in IEEE arithmetic and installs them as the side's weights (bpmf_hip_side_weights_get returns them), so every
+ * launch of the side runs the weighted form of its sampler -- at K = 64 the slab form only.
+ * BPMF_HIP_EINVAL: w0 not finite and > 0; a confidence not finite and > w0 (the first one is named); a side whose mean_rating is not
+ * exactly 0; an fp32 context; a communicator or a sharded side; a side with Student-t noise, weights, a probit, ordinal or censored
+ * likelihood, features, propagated priors, the BPMF_REDUCE formulation or a hyper ring (fold-in).  In turn bpmf_hip_side_set_weights,
+ * _set_robust, _set_probit, _set_ordinal, _set_censored, _set_features[_sparse], _set_prop_posterior, bpmf_hip_sys_set_reduce,
+ * bpmf_hip_side_hyper_reserve and bpmf_hip_tensor_sample refuse an implicit side (it is a side with weights).
+ *
+ * bpmf_hip_implicit_sample is the blocking half-iteration of an implicit side, modelled on bpmf_hip_link_sample: iter++, the
+ * hyper-parameters at counter iter from the side's own cov, G of `other`'s current factors on the device (every column, those without
+ * ratings too; k_link_gemm_tn: fp64, fixed order, no floating-point atomics -- the same bits at every call), alpha w0 G added to the
+ * LambdaF of the parameter blob after Lmu = Lambda mu was formed (padded num_latent: into the leading block), the stateless weighted
+ * launch, cov from the sums.  Both sides of a model are implicit, with one w0, or neither: anything else is BPMF_HIP_EINVAL, and so
+ * are bpmf_hip_sys_sample, bpmf_hip_link_sample and bpmf_hip_sample_side on an implicit side.  bpmf_hip_sys_state, the sample rings,
+ * the -o aggregates, bpmf_hip_topn[_scored], bpmf_hip_rank_eval and the evaluation work on top as they do for a side with features. */
+BPMF_API int bpmf_hip_side_set_implicit(bpmf_hip_side *side, double w0, const double *w_host);
+/* w0 of an implicit side; 0 for any other side. */
+BPMF_API double bpmf_hip_side_implicit_w0(const bpmf_hip_side *side);
+/* G of the side's newest bpmf_hip_implicit_sample, Kt x Kt doubles (waits). */
+BPMF_API int bpmf_hip_side_implicit_gram(bpmf_hip_side *side, double *G_host);
+BPMF_API int bpmf_hip_implicit_sample(bpmf_hip_side *self, bpmf_hip_side *other, double alpha);
 
 /* ---- Student-t noise: the weights redrawn on the device ------------------------------
  * r_p ~ Student-t with nu degrees of freedom, location mean_rating + x_c . y_r, scale 1 / sqrt(alpha), as a scale mixture:
