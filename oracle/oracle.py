@@ -176,10 +176,11 @@ class Oracle:
             raise RuntimeError("Cholesky failed in column %d" % (-rc - 1))
         return s, prod, float(nrm[0])
 
-    def gibbs_reduce(self, K, M, Mt, T, alpha=2.0, nsims=4, burnin=0, bounds_m=None, bounds_u=None):
+    def gibbs_reduce(self, K, M, Mt, T, alpha=2.0, nsims=4, burnin=0, bounds_m=None, bounds_u=None, no_covariance=False):
         """The Gibbs loop of the BPMF_REDUCE build for `nranks` simulated ranks (bounds_*: column ranges per rank; None: one
         rank): per half-iteration the parts of all ranks are summed in rank order (MPI_Reduce), the owners sample their
-        ranges, every rank precomputes the other side's parts from its own fresh columns.  Returns U, V, rmse per iteration."""
+        ranges, every rank precomputes the other side's parts from its own fresh columns.  Returns U, V, rmse per iteration.
+        no_covariance: the BPMF_NO_COVARIANCE build on top (only the diagonal of Lambda* is factorised)."""
         nmovies, nusers = len(M[0]) - 1, len(Mt[0]) - 1
         bounds_m = [0, nmovies] if bounds_m is None else list(bounds_m)
         bounds_u = [0, nusers] if bounds_u is None else list(bounds_u)
@@ -198,7 +199,7 @@ class Oracle:
                 tot = (sum(p[0] for p in prec), sum(p[1] for p in prec))                   # the reduction onto the owners
                 s = np.zeros(K); prod = np.zeros((K, K))
                 for r in range(nr):
-                    sr, pr, _ = self.sample_side_prec(K, alpha, tot, X, it, mu, LF, b[r], b[r + 1])
+                    sr, pr, _ = self.sample_side_prec(K, alpha, tot, X, it, mu, LF, b[r], b[r + 1], no_covariance=no_covariance)
                     s += sr; prod += pr
                 for r in range(nr):                                                         # other.preComputeMuLambda(*this)
                     prec_o[r] = self.precompute(K, csc_o, mean_o, alpha, X, b[r], b[r + 1])
