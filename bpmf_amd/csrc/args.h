@@ -32,7 +32,9 @@ struct Geo {
 // block (g, g') of the Gram; lane (k, b, x) feeds rating slot s = 4 k + b with the latent index
 // idx(g, x) = 8 (g / 2) + 2 x + (g & 1)  (so that one 16-byte load per lane brings the operands of
 // two groups).  The NB = NG (NG + 1) / 2 upper blocks are NB accumulator registers per lane, each
-// holding the contribution of the lane's b; the four b are added once per column (DPP row rotates).
+// holding the contribution of the lane's b; the four b are added once per column (DPP row rotates): at K = 32 as a
+// reduce-scatter that packs four registers into one, each total in ONE of the four b and computed once (assemble44_packed
+// in kernels.h); at K = 8 and 16, whose 5 and 14 registers do not fill groups of four, in every lane.
 template <int K>
 struct Geo44 {
     static constexpr int NG = K / 4;                      // groups of 4 latent indices

@@ -650,16 +650,131 @@ __device__ __forceinline__ void gram_stream44(const GatherRec *__restrict__ rec,
     }
 }
 
+// DPP move of the lanes whose bank (the b of lane = 16 i + 4 b + j) is in BANKS; the other lanes keep `old`
+template <int CTRL, int BANKS>
+__device__ __forceinline__ double dpp_merge(double old, double src)
+{
+    const long long o = __builtin_bit_cast(long long, old), v = __builtin_bit_cast(long long, src);
+    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)v, CTRL, 0xF, BANKS, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(v >> 32), CTRL, 0xF, BANKS, false);
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+
+// The bank totals of four registers in one: bank 0 of the result holds the total of x0, bank 1 of x1, bank 2 of y0, bank 3 of
+// y1 -- a reduce-scatter over the four b.  Level 1 (row_ror:8, bank b reads bank b ^ 2) merges (x, y) into one register with
+// x_b + x_{b+2} in the banks 0, 1 and y_{b-2} + y_b in the banks 2, 3; level 2 merges two of those (row_ror:12: bank b reads
+// bank b + 1, row_ror:4: bank b - 1).  Every addition pairs the two operands the all-lanes form pairs, (v_b + v_{b^2}) +
+// (v_{b^1} + v_{b^3}): the totals have the same bits.  12 DPP moves, 3 additions and 3 register copies (a merge overwrites
+// its `old`, which the partner merge still reads) where summing the four registers in every lane takes 16 moves and 8
+// additions, and each total exists once.
+__device__ __forceinline__ double bank_totals4(double x0, double x1, double y0, double y1)
+{
+    const double u0 = dpp_merge<0x128, 0x3>(y0, x0), v0 = dpp_merge<0x128, 0xC>(x0, y0);
+    const double z0 = v0 + u0;
+    const double u1 = dpp_merge<0x128, 0x3>(y1, x1), v1 = dpp_merge<0x128, 0xC>(x1, y1);
+    const double z1 = v1 + u1;
+    const double p = dpp_merge<0x12C, 0x5>(z1, z0), q = dpp_merge<0x124, 0xA>(z0, z1);
+    return q + p;
+}
+
+// a + b of the two registers the row swap leaves: the rows (16 lanes) 1, 3 of x change places with the rows 0, 2 of y
+// (WIDE: the rows 2, 3 of x with the rows 0, 1 of y)
+template <bool WIDE>
+__device__ __forceinline__ double row_swap_add(double x, double y)
+{
+    const unsigned long long a = __builtin_bit_cast(unsigned long long, x), b = __builtin_bit_cast(unsigned long long, y);
+    unsigned alo, blo, ahi, bhi;
+    if constexpr (WIDE) {
+        const auto l = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap((unsigned)(a >> 32), (unsigned)(b >> 32), false, false);
+        alo = l[0]; blo = l[1]; ahi = h[0]; bhi = h[1];
+    } else {
+        const auto l = __builtin_amdgcn_permlane16_swap((unsigned)a, (unsigned)b, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap((unsigned)(a >> 32), (unsigned)(b >> 32), false, false);
+        alo = l[0]; blo = l[1]; ahi = h[0]; bhi = h[1];
+    }
+    return __builtin_bit_cast(double, ((unsigned long long)ahi << 32) | alo) + __builtin_bit_cast(double, ((unsigned long long)bhi << 32) | blo);
+}
+
+// K = 32: the four b of every accumulator are added ONCE (bank_totals4: four registers become one that holds each total in
+// one bank), so every store below is a full-wave 8-byte store of 64 different entries -- no exec regions.  Which block goes
+// to which bank is chosen so that a lane's store address is a per-lane term (computed once from b) plus a compile-time
+// constant per register, and so that a register is mirrored as a whole or not at all:
+//   2 registers  diagonal blocks (b, b) and (4 + b, 4 + b)
+//   4 registers  block row g = 0..3 against the columns 4 + b
+//   3 registers  the blocks inside the block quads 0..3 and 4..7: (g, g2), (g', g2') in the banks 0, 1 and the same + (4, 4) in 2, 3
+//   2 registers  rhs sums b and 4 + b: their rows i are then added by two row swaps (the operand pairs of xor 16, xor 32);
+//                after the first the two registers are one
+// 9 + 7 stores of G and one of the rhs sums; a group of four accumulators is dead once it is merged.
+template <int K>
+__device__ __forceinline__ void assemble44_packed(double (&acc)[Geo44<K>::NB], double (&rr)[Geo44<K>::NG], double *sA, double *sb,
+                                                  int LD, int lane)
+{
+    using G = Geo44<K>;
+    constexpr int NG = G::NG;
+    static_assert(NG == 8, "the packing is the one of K = 32");
+    const int i = lane >> 4, b = (lane >> 2) & 3, j = lane & 3;
+    auto blk = [](int g, int g2) constexpr { return g * NG - (g * (g - 1)) / 2 + (g2 - g); };
+    const int ib = G::idx(b, 0), b1 = b & 1;
+    const int quad = (b >> 1) * (G::idx(4, 0) * LD + G::idx(4, 0));              // banks 2, 3: the block + (4, 4)
+    double *up = sA + (2 * i) * LD + 2 * j;      // entry (idx(g, i), idx(g2, j)) of block (g, g2): lane base + block offset
+    double *lo = sA + (2 * j) * LD + 2 * i;      // its mirror image (idx(g2, j), idx(g, i))
+    // inside the two quads: (0, 2) | (0, 3), (1, 2) | (1, 3) -- neighbours in a row -- and (0, 1) | (2, 3)
+    {
+        double *pu = up + quad + b1, *pl = lo + quad + b1 * LD;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const double v = bank_totals4(acc[blk(g, 2)], acc[blk(g, 3)], acc[blk(g + 4, 6)], acc[blk(g + 4, 7)]);
+            pu[G::idx(g, 0) * LD + G::idx(2, 0)] = v;
+            pl[G::idx(2, 0) * LD + G::idx(g, 0)] = v;
+        }
+        const int d = b1 * (G::idx(2, 0) * LD + G::idx(2, 0));                    // (0, 1) -> (2, 3)
+        const double v = bank_totals4(acc[blk(0, 1)], acc[blk(2, 3)], acc[blk(4, 5)], acc[blk(6, 7)]);
+        up[quad + d + G::idx(0, 0) * LD + G::idx(1, 0)] = v;
+        lo[quad + d + G::idx(1, 0) * LD + G::idx(0, 0)] = v;
+    }
+    // block rows 0..3 x block columns 4..7
+    {
+        double *pu = up + ib, *pl = lo + ib * LD;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const double v = bank_totals4(acc[blk(g, 4)], acc[blk(g, 5)], acc[blk(g, 6)], acc[blk(g, 7)]);
+            pu[G::idx(g, 0) * LD + G::idx(4, 0)] = v;
+            pl[G::idx(4, 0) * LD + G::idx(g, 0)] = v;
+        }
+    }
+    // diagonal blocks
+    {
+        double *p = up + ib * (LD + 1);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            p[G::idx(4 * h, 0) * (LD + 1)] = bank_totals4(acc[blk(4 * h, 4 * h)], acc[blk(4 * h + 1, 4 * h + 1)],
+                                                          acc[blk(4 * h + 2, 4 * h + 2)], acc[blk(4 * h + 3, 4 * h + 3)]);
+    }
+    // rhs sums: row i & 1 ends up with the totals of the groups 4 (i & 1) + b
+    {
+        const double w0 = bank_totals4(rr[0], rr[1], rr[2], rr[3]), w1 = bank_totals4(rr[4], rr[5], rr[6], rr[7]);
+        const double s = row_swap_add<false>(w0, w1);                             // rows 0, 2: w0 of i + i ^ 1; rows 1, 3: w1
+        const double t = row_swap_add<true>(s, s);                                // + the same of i ^ 2
+        sb[G::idx(4 * (i & 1), 0) + G::idx(b, j)] = t;
+    }
+}
+
 // The four b of every accumulator are added (fixed order: (b + b^2) + the same of b^1; every lane ends up with the
 // total), then the full symmetric G goes into the K x LD LDS matrix finish_single reads: the lanes b = 0 write the
 // upper blocks, the lanes b = 1 their mirror images, two block rows (g, g + 1) at a time -- two exec regions per row
 // pair instead of one per block, 16-byte stores wherever two blocks are neighbours in a row (idx(g, x) and
-// idx(g + 1, x) are adjacent for even g: 36 LDS stores for K = 32 instead of 64), and the accumulators of a row pair
-// are dead once it is written (all 36 sums live at once spill).  The rhs sums (also over the four k) go into sb.
+// idx(g + 1, x) are adjacent for even g).  The rhs sums (also over the four k) go into sb.
+// K = 32 takes the packed form above (the same bits in LDS); this one serves K = 8 and 16, whose 5 and 14 registers
+// do not fill groups of four.
 template <int K>
 __device__ __forceinline__ void assemble44(double (&acc)[Geo44<K>::NB], double (&rr)[Geo44<K>::NG], double *sA, double *sb,
                                            int LD, int lane)
 {
+    if constexpr (K == 32) {
+        assemble44_packed<K>(acc, rr, sA, sb, LD, lane);
+        return;
+    }
     using G = Geo44<K>;
     constexpr int NG = G::NG;
     static_assert(NG % 2 == 0, "block rows are written in pairs");
