@@ -177,6 +177,7 @@ _SIGNATURES = {
     "bpmf_hip_side_kernel_name": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "bpmf_hip_side_kernel_resources": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "bpmf_hip_side_schedule_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "bpmf_hip_side_stat_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "bpmf_hip_side_schedule_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "bpmf_hip_side_kernel_ms_sum": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "bpmf_hip_side_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -824,6 +824,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     c->last_sampler_done = ev[1];
     if (carry) {                                                      // P's statistics are inside this launch: complete behind ev[1]
         P->stats_ev[c->pending_evset].store(ev[1], std::memory_order_release);
+        ++P->stat_rider_passes;
         c->pending_stats = nullptr;
         c->pending_riders = false;
     }

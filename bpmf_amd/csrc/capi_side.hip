@@ -613,6 +613,28 @@ extern "C" int bpmf_hip_side_schedule_info(const bpmf_hip_side *s, int64_t *out,
     return BPMF_HIP_OK;
 }
 
+// The statistics pass of a side in numbers (build_schedule and the kernels' own slicing), for tests: out[0..7] =
+//   0 form: 0 one wave per slice of columns (k_colstats, also as riders), 1 four-wave workgroups (k_colstats_wg), 2 one wave
+//     per (slice, tile) (k_colstats_f32, also as riders)
+//   1 waves / workgroups / slices   2 columns per wave or slice: per = roundup4(ceil(local columns / waves)); form 1: per wave
+//   3 waves or slices whose range [w per, (w + 1) per) begins at or behind the last local column (form 1: of the 4 x workgroups waves)
+//   4 passes enqueued as riders of a sampler launch   5 passes enqueued as kernels of their own   6, 7 zero
+extern "C" int bpmf_hip_side_stat_info(const bpmf_hip_side *s, int64_t *out, int n)
+{
+    if (!s || !out || n < 8) return fail(BPMF_HIP_EINVAL, "side_stat_info: bad argument (8 words)");
+    for (int i = 0; i < n; ++i) out[i] = 0;
+    const int64_t nloc = s->to - s->from;
+    const int form = s->ctx->K == 128 ? 2 : (s->nstat_wg > 0 ? 1 : 0);
+    const int64_t units = form == 1 ? s->nstat_wg : s->nstat_waves;
+    const int64_t nw = form == 1 ? 4 * units : units;                 // the ranges are per wave in every form
+    const int64_t per = nw > 0 ? ((nloc + nw - 1) / nw + 3) / 4 * 4 : 0;
+    int64_t empty = 0;
+    for (int64_t w = 0; w < nw; ++w) empty += (w * per >= nloc) ? 1 : 0;
+    out[0] = form; out[1] = units; out[2] = per; out[3] = empty;
+    out[4] = s->stat_rider_passes; out[5] = s->stat_alone_passes;
+    return BPMF_HIP_OK;
+}
+
 extern "C" int bpmf_hip_side_schedule_items(const bpmf_hip_side *s, int32_t *col, int32_t *len, int32_t *heavy, int64_t n, int64_t *nitems)
 {
     if (!s || n < 0) return fail(BPMF_HIP_EINVAL, "side_schedule_items: bad argument");

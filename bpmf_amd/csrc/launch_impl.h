@@ -242,6 +242,7 @@ int stats(bpmf_hip_side *self, hipStream_t st, const StatPass &p, hipEvent_t ev_
     unsigned *flag = dist ? p.ticket + 8 : p.flag;
     const unsigned seq = dist ? 0u : p.seq;
     if (dist) ev_done = nullptr;
+    ++self->stat_alone_passes;
     if constexpr (K == 128) {                           // one wave per (slice of columns, 16 x 16 tile): fp32 or fp64 factors, fp64 sums
         typedef typename std::conditional<F32, float, double>::type T;
         hipLaunchKernelGGL((k_colstats_f32<K, T>), dim3(p.nwaves * (K / 16) * (K / 16 + 1) / 2), dim3(64), 0, st, reinterpret_cast<const T *>(p.items),

@@ -250,6 +250,7 @@ struct bpmf_hip_side {
     int nstat_wg = 0;                    // > 0: the side's stand-alone statistics pass runs as this many four-wave workgroups (k_colstats_wg: big sides)
     hipEvent_t ev_stat_go = nullptr;     // big side: S0 continues only once S1 has reached the statistics kernel (head start for its workgroups)
     double *d_stat_partials = nullptr;
+    int64_t stat_rider_passes = 0, stat_alone_passes = 0;   // statistics passes of this side enqueued as riders / as kernels of their own (bpmf_hip_side_stat_info)
     std::vector<int64_t> bounds;         // multi-GPU: column range of every rank (nranks + 1 entries)
     // overlap of exchange and sampling (bpmf_hip_side_set_overlap): every rank's range is cut into nsub parts of
     // equal work; part c of every rank is exchanged on the stream `sx` while part c + 1 is being sampled

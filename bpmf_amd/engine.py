@@ -951,6 +951,14 @@ class HipEngine:
                 "lr_columns", "parts", "local_columns", "local_ratings", "pf_ratings", "pf_ratings_sq", "chunk")
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def stat_info(self, side):
+        """The side's column statistics pass (bpmf_hip_side_stat_info): form "waves" / "workgroups" / "tiles", units (waves,
+        workgroups or slices), columns per wave or slice, empty ranges, passes enqueued as riders / stand-alone."""
+        out = np.zeros(8, np.int64)
+        _lib.check(self.lib.bpmf_hip_side_stat_info(side.handle, _ptr(out), 8))
+        return {"form": ("waves", "workgroups", "tiles")[int(out[0])], "units": int(out[1]), "per": int(out[2]), "empty": int(out[3]),
+                "rider_passes": int(out[4]), "alone_passes": int(out[5])}
+
     def schedule_items(self, side):
         """The side's work items in launch order: (local column, ratings, heavy-column ordinal or -1) arrays."""
         n = C.c_int64()

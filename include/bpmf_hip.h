@@ -860,6 +860,10 @@ BPMF_API int bpmf_hip_side_kernel_name(const bpmf_hip_side *side, char *buf, int
  * launch sites spell them, ';'-separated.  Returns the number of kernels (<= max_kernels) or a negative error.  Launches nothing. */
 BPMF_API int bpmf_hip_side_kernel_resources(bpmf_hip_side *side, int64_t *out, int max_kernels, char *names, int names_len);
 BPMF_API int bpmf_hip_side_schedule_info(const bpmf_hip_side *side, int64_t *out16, int n);
+/* the side's column statistics pass in numbers (8 words, see capi_side.hip): form (0 waves, 1 four-wave workgroups, 2 tiles),
+ * waves / workgroups / slices, columns per wave or slice, waves or slices with an empty range, passes enqueued so far as
+ * riders of a sampler launch and as kernels of their own.  Launches nothing, waits for nothing. */
+BPMF_API int bpmf_hip_side_stat_info(const bpmf_hip_side *side, int64_t *out8, int n);
 /* the side's work items in launch order (what replaces the `#pragma omp parallel for schedule(guided)` over the columns,
  * c++/sample.cpp:353-356): local column, number of ratings, and the ordinal of the item's heavy column (-1: the item is
  * a whole column).  Copies min(n, work items) entries; returns the number of work items through *nitems. */

@@ -25,6 +25,7 @@ def test_library_exports_every_declared_symbol():
     lib = C.CDLL(bpmf_amd.library_path())
     names = header_symbols()
     assert len(names) >= 25
+    assert "bpmf_hip_side_schedule_info" in names and "bpmf_hip_side_stat_info" in names
     for n in names:
         assert hasattr(lib, n), "missing export " + n
     # and the binding covers exactly the header
