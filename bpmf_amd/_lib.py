@@ -15,6 +15,7 @@ _SIGNATURES = {
     "bpmf_hip_last_error": (C.c_char_p, []),
     "bpmf_hip_abi_version": (C.c_int, []),
     "bpmf_hip_live_device_bytes": (C.c_int64, []),
+    "bpmf_hip_live_core_bytes": (C.c_int64, []),
     "bpmf_hip_stream_drains": (C.c_int64, []),
     "bpmf_hip_supports_k": (C.c_int, [C.c_int]),
     "bpmf_hip_supports": (C.c_int, [C.c_int, C.c_int]),

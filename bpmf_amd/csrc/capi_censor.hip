@@ -49,7 +49,7 @@ extern "C" int bpmf_hip_side_set_censored(bpmf_hip_side *s, const int8_t *flags,
     auto cs = std::make_unique<bpmf_censor>();                        // (freed with everything it holds on every return below)
     // z starts as the ratings; only the censored positions are ever rewritten
     if ((rc = cs->z.alloc((size_t)s->nnz)) || (rc = cs->fail.alloc(1))) return rc;
-    if (s->nnz > 0) HIP_TRY(hipMemcpyAsync(cs->z.get(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (s->nnz > 0) HIP_TRY(hipMemcpyAsync(cs->z.get(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream.get()));
     // the lists of the censored entries in the order of the CSC, in one pass over the flags: positions ascend, columns come from
     // the host column pointers, rows from the side's row indices (on the device since the side was created)
     std::vector<int32_t> rowidx((size_t)s->nnz);
@@ -92,7 +92,7 @@ extern "C" int bpmf_hip_side_censored_latent(bpmf_hip_side *s, double *z_host)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     { std::string m; if (check_censor(s, &m)) return fail(BPMF_HIP_ENUM, m); }
     if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->censor->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;

@@ -99,10 +99,8 @@ static int reduce_prepare(bpmf_hip_side *s, const bpmf_hip_side *o)
 {
     bpmf_hip_ctx *c = s->ctx;
     const size_t part = (size_t)bpmf_launch::reduce_part_words(c->K);
-    if (!s->d_prec) {
-        HIP_TRY(hipMalloc((void **)&s->d_prec, std::max<size_t>(1, (size_t)s->ncols * part) * sizeof(double)));
-    }
-    HIP_TRY(hipMemset(s->d_prec, 0, std::max<size_t>(1, (size_t)s->ncols * part) * sizeof(double)));
+    if (!s->d_prec) { const int ra = s->d_prec.alloc((size_t)s->ncols * part); if (ra) return ra; }
+    { const int rz = s->d_prec.zero(); if (rz) return rz; }
     if (s->d_t_colptr) return 0;
     // transpose of the local block: for every column j of the other side, the local columns of this side (global
     // ids, ascending) with a rating in row j
@@ -127,8 +125,8 @@ static int reduce_prepare(bpmf_hip_side *s, const bpmf_hip_side *o)
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return tp[(size_t)x + 1] - tp[(size_t)x] > tp[(size_t)y + 1] - tp[(size_t)y]; });
     int rc;
-    if ((rc = dev_upload(&s->d_t_colptr, tp.data(), tp.size())) || (rc = dev_upload(&s->d_t_rowidx, tr.data(), (size_t)nnz)) ||
-        (rc = dev_upload(&s->d_t_vals, tv.data(), (size_t)nnz)) || (rc = dev_upload(&s->d_t_order, order.data(), order.size()))) return rc;
+    if ((rc = s->d_t_colptr.upload(tp.data(), tp.size())) || (rc = s->d_t_rowidx.upload(tr.data(), (size_t)nnz)) ||
+        (rc = s->d_t_vals.upload(tv.data(), (size_t)nnz)) || (rc = s->d_t_order.upload(order.data(), order.size()))) return rc;
     (void)o;
     return 0;
 }
@@ -143,7 +141,7 @@ extern "C" int bpmf_hip_sys_set_reduce(bpmf_hip_side *a, bpmf_hip_side *b, int o
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if ((rc = settle_async(a)) || (rc = settle_async(b))) return rc;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if (!on) { a->reduce_on = b->reduce_on = false; return BPMF_HIP_OK; }
     if (a->probit || b->probit) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with the probit likelihood (bpmf_hip_side_set_probit)");
     if (a->censor || b->censor) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with censored ratings (bpmf_hip_side_set_censored)");
@@ -166,8 +164,8 @@ extern "C" int bpmf_hip_side_set_overlap(bpmf_hip_side *s, int nparts)
     int rc;
     if ((rc = settle_async(s))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    if (s->saux) { const int rs_ = bounded_stream_sync(s->ctx, s->saux, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
+    if (s->saux) { const int rs_ = bounded_stream_sync(s->ctx, s->saux.get(), __func__); if (rs_) return rs_; }
     Rccl *R = rccl();
     if (nparts > 1 && (!R->AllGather || !R->Send || !R->Recv)) nparts = 1;          // (old RCCL: no parts)
     const int64_t nloc = s->to - s->from;
@@ -187,17 +185,14 @@ extern "C" int bpmf_hip_side_set_overlap(bpmf_hip_side *s, int nparts)
     // ... of every rank: one small all-gather (device buffers; once per side)
     std::vector<int64_t> all((size_t)c->nranks * (nparts + 1));
     if (nparts > 1) {
-        int64_t *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, all.size() * sizeof(int64_t)));
+        CoreBuf<int64_t> dbuf;
+        { const int ra = dbuf.alloc(all.size()); if (ra) return ra; }
+        int64_t *d = dbuf.get();
         HIP_TRY(hipMemcpy(d + (size_t)c->rank * (nparts + 1), mine.data(), mine.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        ncclResult_t nr = R->AllGather(d + (size_t)c->rank * (nparts + 1), d, (size_t)nparts + 1, ncclInt64, c->comm, c->stream);
+        ncclResult_t nr = R->AllGather(d + (size_t)c->rank * (nparts + 1), d, (size_t)nparts + 1, ncclInt64, c->comm, c->stream.get());
         hipError_t he = hipSuccess;
-        if (nr == ncclSuccess && bounded_stream_sync(c, c->stream, "side_set_overlap: all-gather of the parts") != 0) {
-            (void)hipFree(d);
-            return BPMF_HIP_ENODEV;
-        }
+        if (nr == ncclSuccess && bounded_stream_sync(c, c->stream.get(), "side_set_overlap: all-gather of the parts") != 0) return BPMF_HIP_ENODEV;
         if (nr == ncclSuccess && he == hipSuccess) he = hipMemcpy(all.data(), d, all.size() * sizeof(int64_t), hipMemcpyDeviceToHost);
-        (void)hipFree(d);
         if (nr != ncclSuccess) return fail(BPMF_HIP_ENODEV, "side_set_overlap: ncclAllGather failed");
         if (he != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_set_overlap: HIP error");
         for (int r = 0; r < c->nranks; ++r)
@@ -205,9 +200,10 @@ extern "C" int bpmf_hip_side_set_overlap(bpmf_hip_side *s, int nparts)
                 return fail(BPMF_HIP_EINVAL, "side_set_overlap: the ranks disagree about the ranges or the number of parts");
     }
     if (nparts > 1 && !s->sx) {
-        HIP_TRY(hipStreamCreateWithFlags(&s->sx, hipStreamNonBlocking));
-        for (hipEvent_t &e : s->sub_ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s->sx_done, hipEventDisableTiming));
+        int re = s->sx.create(hipStreamNonBlocking);
+        for (Event &e : s->sub_ev) if (!re) re = e.create(hipEventDisableTiming);
+        if (!re) re = s->sx_done.create(hipEventDisableTiming);
+        if (re) { s->sx.reset(); return re; }                           // (the next call builds the stream and all its events again)
     }
     s->nsub = nparts;
     s->sub_bounds = nparts > 1 ? all : std::vector<int64_t>();
@@ -247,10 +243,8 @@ extern "C" int bpmf_hip_side_set_conn(bpmf_hip_side *s, const int64_t *send_ptr,
     int rc;
     if ((rc = settle_async(s))) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    for (void *p : {(void *)s->d_conn_send, (void *)s->d_conn_recv, (void *)s->d_conn_sbuf, (void *)s->d_conn_rbuf})
-        if (p) HIP_TRY(hipFree(p));
-    s->d_conn_send = s->d_conn_recv = nullptr; s->d_conn_sbuf = s->d_conn_rbuf = nullptr;
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
+    s->d_conn_send.reset(); s->d_conn_recv.reset(); s->d_conn_sbuf.reset(); s->d_conn_rbuf.reset();
     s->conn_send_ptr.clear(); s->conn_recv_ptr.clear();
     if (!send_ptr && !recv_ptr) return BPMF_HIP_OK;                     // back to the all-gather form
     if (!send_ptr || !recv_ptr) return fail(BPMF_HIP_EINVAL, "side_set_conn: both lists or none");
@@ -269,10 +263,10 @@ extern "C" int bpmf_hip_side_set_conn(bpmf_hip_side *s, const int64_t *send_ptr,
         for (int64_t i = recv_ptr[r]; i < recv_ptr[r + 1]; ++i)
             if (recv_cols[i] < s->bounds[(size_t)r] || recv_cols[i] >= s->bounds[(size_t)r + 1])
                 return fail(BPMF_HIP_EINVAL, "side_set_conn: receive list names a column outside the sender's range");
-    if ((rc = dev_upload<int32_t>(&s->d_conn_send, send_cols, (size_t)std::max<int64_t>(ns, 1)))) return rc;
-    if ((rc = dev_upload<int32_t>(&s->d_conn_recv, recv_cols, (size_t)std::max<int64_t>(nr, 1)))) return rc;
-    if ((rc = dev_upload<double>(&s->d_conn_sbuf, nullptr, (size_t)std::max<int64_t>(ns, 1) * c->K))) return rc;
-    if ((rc = dev_upload<double>(&s->d_conn_rbuf, nullptr, (size_t)std::max<int64_t>(nr, 1) * c->K))) return rc;
+    if ((rc = s->d_conn_send.upload(send_cols, (size_t)std::max<int64_t>(ns, 1)))) return rc;
+    if ((rc = s->d_conn_recv.upload(recv_cols, (size_t)std::max<int64_t>(nr, 1)))) return rc;
+    if ((rc = s->d_conn_sbuf.alloc((size_t)std::max<int64_t>(ns, 1) * c->K))) return rc;
+    if ((rc = s->d_conn_rbuf.alloc((size_t)std::max<int64_t>(nr, 1) * c->K))) return rc;
     s->conn_send_ptr.assign(send_ptr, send_ptr + n + 1);
     s->conn_recv_ptr.assign(recv_ptr, recv_ptr + n + 1);
     return BPMF_HIP_OK;
@@ -288,9 +282,9 @@ extern "C" int bpmf_hip_side_exchange(bpmf_hip_side *s)
     if ((rc = settle_async(s))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     c->last_sampler_done = nullptr;
-    rc = BPMF_DISPATCH_K(c->K, (bpmf_launch::exchange<KK, FF>(s, c->stream, -1)));
+    rc = BPMF_DISPATCH_K(c->K, (bpmf_launch::exchange<KK, FF>(s, c->stream.get(), -1)));
     if (rc) return rc;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     return BPMF_HIP_OK;
 }
 

@@ -89,7 +89,7 @@ int comm_abort(bpmf_hip_ctx *c, const std::string &what)
 // hipStreamSynchronize for a stream that may carry a collective: a poll with a deadline instead of a wait without one
 int bounded_stream_sync(bpmf_hip_ctx *c, hipStream_t st, const char *what)
 {
-    if (st == c->stream) g_stream_drains.fetch_add(1, std::memory_order_relaxed);
+    if (st == c->stream.get()) g_stream_drains.fetch_add(1, std::memory_order_relaxed);
     if (!c->comm) { HIP_TRY(hipStreamSynchronize(st)); return 0; }
     const auto t0 = std::chrono::steady_clock::now();
     for (unsigned spins = 0;; ++spins) {
@@ -130,10 +130,10 @@ int bounded_event_sync(bpmf_hip_ctx *c, hipEvent_t ev, const char *what)
 // half-iteration) on a path whose device work is only tens of microseconds.
 int wait_host(bpmf_hip_ctx *c)
 {
-    unsigned *flag = blob::res_flag_word(c->h_out, c->K);
+    unsigned *flag = blob::res_flag_word(c->h_out.host(), c->K);
     if (spin_for_seq(flag, c->seq)) return 0;
     // long kernel (big matrix) or an error: fall back to a blocking wait
-    { const int rc = bounded_stream_sync(c, c->stream, "sampler + exchange + all-reduce of a half-iteration"); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), "sampler + exchange + all-reduce of a half-iteration"); if (rc) return rc; }
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != c->seq) return fail(BPMF_HIP_ENODEV, "device did not publish its results");
     return 0;
 }
@@ -189,7 +189,7 @@ static int ctx_create_impl(int device, int Ktrue, int dtype, void *stream, bpmf_
         return fail(BPMF_HIP_ENODEV, "no HIP device available (the BPMF hot path has no CPU fallback)");
     if (device < 0 || device >= ndev) return fail(BPMF_HIP_EINVAL, "ctx_create: bad device index");
     HIP_TRY(hipSetDevice(device));
-    bpmf_hip_ctx *c = new (std::nothrow) bpmf_hip_ctx();
+    std::unique_ptr<bpmf_hip_ctx> c(new (std::nothrow) bpmf_hip_ctx());      // (a failure below releases what was built so far)
     if (!c) return fail(BPMF_HIP_ENOMEM, "ctx_create: out of host memory");
     c->device = device; c->K = K; c->Kt = Ktrue; c->dtype = dtype;
     hipDeviceProp_t prop;
@@ -199,32 +199,24 @@ static int ctx_create_impl(int device, int Ktrue, int dtype, void *stream, bpmf_
     c->ablate = (unsigned)env_int("BPMF_HIP_ABLATE", 0);
 #else
     // the product build has no profiling hooks in its kernels (kernels.h: kProfiling): asking for them must not pass silently
-    if (env_int("BPMF_HIP_ABLATE", 0) || env_int("BPMF_HIP_STAMPS", 0)) {
-        delete c;
+    if (env_int("BPMF_HIP_ABLATE", 0) || env_int("BPMF_HIP_STAMPS", 0))
         return fail(BPMF_HIP_EINVAL, "BPMF_HIP_ABLATE / BPMF_HIP_STAMPS need the profiling build of the library "
                                      "(make -C bpmf_amd/csrc prof; BPMF_HIP_LIBRARY=<repo>/bpmf_amd/libbpmf_hip_prof.so)");
-    }
 #endif
-    if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
-    else { HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); c->own_stream = true; }
+    int rc;
+    if (stream) c->stream.borrow((hipStream_t)stream);
+    else if ((rc = c->stream.create(hipStreamNonBlocking))) return rc;
     c->in_words = (K == 64 && dtype == BPMF_HIP_F64) ? blob::par_words_pf(K) : blob::par_words(K);
     c->out_words = blob::res_words(K);
-    HIP_TRY(hipHostMalloc((void **)&c->h_in, c->in_words * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostMalloc((void **)&c->h_out, c->out_words * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&c->h_in_dev, c->h_in, 0));
-    HIP_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out, 0));
-    memset(c->h_out, 0, c->out_words * sizeof(double));
-    HIP_TRY(hipMalloc((void **)&c->d_in, (c->in_words + lf32_words(c)) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->d_red, (size_t)blob::red_words(K) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&c->d_ticket, 64));
-    HIP_TRY(hipMemset(c->d_ticket, 0, 64));
-    HIP_TRY(hipMalloc((void **)&c->d_zero, 1024));
-    HIP_TRY(hipMemset(c->d_zero, 0, 1024));
+    if ((rc = c->h_in.alloc(c->in_words)) || (rc = c->h_out.alloc(c->out_words))) return rc;
+    memset(c->h_out.host(), 0, c->out_words * sizeof(double));
+    if ((rc = c->d_in.alloc(c->in_words + lf32_words(c.get()))) || (rc = c->d_red.alloc((size_t)blob::red_words(K))) ||
+        (rc = c->d_ticket.alloc(16)) || (rc = c->d_ticket.zero()) || (rc = c->d_zero.alloc(128)) || (rc = c->d_zero.zero())) return rc;
 #if defined(BPMF_PROFILING) && BPMF_PROFILING
-    if (env_int("BPMF_HIP_STAMPS", 0)) { HIP_TRY(hipMalloc((void **)&c->d_stamps, 4096)); HIP_TRY(hipMemset(c->d_stamps, 0, 4096)); }
+    if (env_int("BPMF_HIP_STAMPS", 0) && ((rc = c->d_stamps.alloc(512)) || (rc = c->d_stamps.zero()))) return rc;
 #endif
-    for (auto &e : c->ev) HIP_TRY(hipEventCreate(&e));
-    *out = c;
+    for (Event &e : c->ev) if ((rc = e.create())) return rc;
+    *out = c.release();
     return BPMF_HIP_OK;
 }
 
@@ -241,31 +233,22 @@ extern "C" int bpmf_hip_ctx_destroy(bpmf_hip_ctx *c)
     if (!c) return BPMF_HIP_OK;
     if (g_trace_on) trace_dump();
     (void)hipSetDevice(c->device);
-    (void)bounded_stream_sync(c, c->stream, __func__);
+    (void)bounded_stream_sync(c, c->stream.get(), __func__);
     if (c->d_stamps) {                                              // the last launch's stamps of the two probe items
         unsigned long long h[512];
-        if (hipMemcpy(h, c->d_stamps, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
+        if (hipMemcpy(h, c->d_stamps.get(), sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
             for (int probe = 0; probe < 2; ++probe) {
                 fprintf(stderr, "[bpmf_hip] stamps of probe item %d (100 MHz ticks since its start):", probe);
                 for (int i = 1; i < 64; ++i) if (h[probe * 64 + i]) fprintf(stderr, " %d:%lld", i, (long long)(h[probe * 64 + i] - h[probe * 64]));
                 fprintf(stderr, "\n");
             }
         if (h[129]) fprintf(stderr, "[bpmf_hip] all launches: %llu items, mean life of wave 0 %.1f us\n", h[129], (double)h[128] / (double)h[129] / 100.0);
-        (void)hipFree(c->d_stamps);
     }
-    for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->d_in) (void)hipFree(c->d_in);
-    if (c->d_ticket) (void)hipFree(c->d_ticket);
-    if (c->d_zero) (void)hipFree(c->d_zero);
-    if (c->d_red) (void)hipFree(c->d_red);
     if (!c->comm_dead.load()) {                                      // (aborted communicators are gone already)
         if (c->comm2 && rccl()) (void)rccl()->CommDestroy(c->comm2);
         if (c->comm && rccl()) (void)rccl()->CommDestroy(c->comm);
     }
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                                       // (events and buffers, then the stream if it is the context's own)
     return BPMF_HIP_OK;
 }
 
@@ -288,24 +271,23 @@ extern "C" int bpmf_hip_ctx_sync(bpmf_hip_ctx *c)
         (void)hipGetLastError();                                      // ("not ready" is no error: do not leave it for a later hipGetLastError())
         return bounded_stream_sync(c, st, "ctx_sync");
     };
-    { const int r = sync_stream(c->stream); if (r) return r; }
-    for (bpmf_hip_side *s : sides) { const int r = sync_stream(s->saux); if (r) return r; }
+    { const int r = sync_stream(c->stream.get()); if (r) return r; }
+    for (bpmf_hip_side *s : sides) { const int r = sync_stream(s->saux.get()); if (r) return r; }
     trace("ctx_sync: done", nullptr, 0);
     return rc;
 }
 
-extern "C" void *bpmf_hip_ctx_stream(bpmf_hip_ctx *c) { return c ? (void *)c->stream : nullptr; }
+extern "C" void *bpmf_hip_ctx_stream(bpmf_hip_ctx *c) { return c ? (void *)c->stream.get() : nullptr; }
 
 extern "C" int bpmf_hip_randn_stream(bpmf_hip_ctx *c, uint32_t counter, int n, double *out)
 {
     if (!c || !out || n < 0 || n > 128) return fail(BPMF_HIP_EINVAL, "randn_stream: bad argument");
     HIP_TRY(hipSetDevice(c->device));
-    double *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 128 * sizeof(double)));
-    bpmf_launch::randn_probe(counter, n, d, c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
+    CoreBuf<double> d;
+    { const int rc = d.alloc(128); if (rc) return rc; }
+    bpmf_launch::randn_probe(counter, n, d.get(), c->stream.get());
+    hipError_t e = hipStreamSynchronize(c->stream.get());
+    if (e == hipSuccess) e = hipMemcpy(out, d.get(), n * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(BPMF_HIP_ENODEV, std::string("randn_stream: ") + hipGetErrorString(e));
     return BPMF_HIP_OK;
 }

@@ -24,22 +24,15 @@ extern "C" int bpmf_hip_test_create(bpmf_hip_side *side, const int64_t *tcolptr,
             tcol[p] = (int32_t)c;
         }
     }
-    bpmf_hip_test *t = new (std::nothrow) bpmf_hip_test();
+    std::unique_ptr<bpmf_hip_test> own(new (std::nothrow) bpmf_hip_test());      // (nothing below registers it: a failure just releases it)
+    bpmf_hip_test *t = own.get();
     if (!t) return fail(BPMF_HIP_ENOMEM, "test_create: out of host memory");
     t->side = side; t->nnz = nnz;
     t->h_col.resize((size_t)nnz); t->h_row.assign(trowidx, trowidx + nnz);
     for (int64_t p = 0; p < nnz; ++p) t->h_col[(size_t)p] = (int32_t)(side->from + tcol[(size_t)p]);
-    if (hipHostMalloc((void **)&t->h_res, 4 * sizeof(double), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&t->h_res_dev, t->h_res, 0) != hipSuccess) {
-        delete t;
-        return fail(BPMF_HIP_ENOMEM, "test_create: pinned result allocation failed");
-    }
-    memset(t->h_res, 0, 4 * sizeof(double));
-    if (hipMalloc((void **)&t->d_ticket, 64) != hipSuccess || hipMemset(t->d_ticket, 0, 64) != hipSuccess) {
-        (void)hipHostFree(t->h_res);
-        delete t;
-        return fail(BPMF_HIP_ENOMEM, "test_create: device allocation failed");
-    }
+    if (t->h_res.alloc(4)) return fail(BPMF_HIP_ENOMEM, "test_create: pinned result allocation failed");
+    memset(t->h_res.host(), 0, 4 * sizeof(double));
+    if (t->d_ticket.alloc(16) || t->d_ticket.zero()) return fail(BPMF_HIP_ENOMEM, "test_create: device allocation failed");
     // one lane per test rating, four-wave workgroups; BPMF_HIP_PREDICT_WG=64: single-wave workgroups (up to 4 M ratings, fp64
     // contexts), which find wave slots beside a sampler launch that refills every slot with single-wave workgroups
     // (MEASURED, ML-1M shape: 64-thread workgroups make the evaluation compete with the sampler's items for every slot -- the
@@ -49,22 +42,18 @@ extern "C" int bpmf_hip_test_create(bpmf_hip_side *side, const int64_t *tcolptr,
     t->nblocks = std::max<int64_t>(1, (nnz + t->wg - 1) / t->wg);
     const int64_t nw = t->nblocks;
     int rc;
-    if ((rc = dev_upload(&t->d_tcol, tcol.data(), (size_t)nnz)) || (rc = dev_upload(&t->d_trow, trowidx, (size_t)nnz)) ||
-        (rc = dev_upload(&t->d_tval, tvals, (size_t)nnz)) || (rc = dev_upload(&t->d_pavg, tvals, (size_t)nnz)) ||
-        (rc = dev_upload(&t->d_pm2, tvals, (size_t)nnz)) || (rc = dev_upload<double>(&t->d_partial, nullptr, (size_t)nw * 2))) {
-        bpmf_hip_test_destroy(t);
-        return rc;
-    }
-    // events for an evaluation that runs beside the samplers of the next iteration (launch_predict)
+    if ((rc = t->d_tcol.upload(tcol.data(), (size_t)nnz)) || (rc = t->d_trow.upload(trowidx, (size_t)nnz)) ||
+        (rc = t->d_tval.upload(tvals, (size_t)nnz)) || (rc = t->d_pavg.upload(tvals, (size_t)nnz)) ||
+        (rc = t->d_pm2.upload(tvals, (size_t)nnz)) || (rc = t->d_partial.alloc((size_t)nw * 2))) return rc;
+    // events for an evaluation that runs beside the samplers of the next iteration (launch_predict): all three, or none
     if (env_int("BPMF_HIP_DBUF", 1) != 0) {
-        bool ok = hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-        for (auto &e : t->ev_done) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-        if (!ok) {
+        const unsigned flags = hipEventDisableTiming | hipEventDisableSystemFence;
+        if (t->ev_in.create(flags) || t->ev_done[0].create(flags) || t->ev_done[1].create(flags)) {
             (void)hipGetLastError();
-            if (t->ev_in) { (void)hipEventDestroy(t->ev_in); t->ev_in = nullptr; }
+            t->ev_in.reset(); t->ev_done[0].reset(); t->ev_done[1].reset();
         }
     }
-    *out = t;
+    *out = own.release();
     return BPMF_HIP_OK;
 }
 
@@ -72,10 +61,10 @@ extern "C" int bpmf_hip_test_create(bpmf_hip_side *side, const int64_t *tcolptr,
 static hipStream_t live_pstream(bpmf_hip_test *t)
 {
     bpmf_hip_ctx *c = t->side->ctx;
-    if (!t->pstream || t->pstream == c->stream) return c->stream;
+    if (!t->pstream || t->pstream == c->stream.get()) return c->stream.get();
     std::lock_guard<std::mutex> lk(c->launch_mutex);
-    for (bpmf_hip_side *sd : c->sides) if (sd->saux == t->pstream) return t->pstream;
-    return c->stream;
+    for (bpmf_hip_side *sd : c->sides) if (sd->saux.get() == t->pstream) return t->pstream;
+    return c->stream.get();
 }
 
 extern "C" int bpmf_hip_test_destroy(bpmf_hip_test *t)
@@ -86,7 +75,7 @@ extern "C" int bpmf_hip_test_destroy(bpmf_hip_test *t)
     if (t->owner) {                                                   // a twin: its owner's evaluation in flight reads its arrays
         flush_deferred(t->owner);
         (void)bounded_stream_sync(t->owner->side->ctx, live_pstream(t->owner), __func__);
-        if (t->owner->d_twin_perm) { (void)hipFree(t->owner->d_twin_perm); t->owner->d_twin_perm = nullptr; }
+        t->owner->d_twin_perm.reset();
         t->owner->twin = nullptr; t->owner = nullptr;
     }
     if (t->twin) { flush_deferred(t); t->twin->owner = nullptr; t->twin->launched = false; t->twin = nullptr; }
@@ -95,7 +84,7 @@ extern "C" int bpmf_hip_test_destroy(bpmf_hip_test *t)
         std::lock_guard<std::mutex> lk(c->launch_mutex);
         for (bpmf_hip_side *sd : c->sides) if (sd->deferred_eval == t) sd->deferred_eval = nullptr;
     }
-    (void)bounded_stream_sync(c, c->stream, __func__);
+    (void)bounded_stream_sync(c, c->stream.get(), __func__);
     (void)bounded_stream_sync(t->side->ctx, live_pstream(t), __func__);
     {   // no side may wait for this evaluation any more
         std::lock_guard<std::mutex> lk(c->launch_mutex);
@@ -103,11 +92,6 @@ extern "C" int bpmf_hip_test_destroy(bpmf_hip_test *t)
             for (auto &rd : sd->readers) if (rd.t == t) rd.t = nullptr;
         for (auto &rd : t->side->readers) if (rd.t == t) rd.t = nullptr;
     }
-    if (t->ev_in) (void)hipEventDestroy(t->ev_in);
-    for (hipEvent_t e : t->ev_done) if (e) (void)hipEventDestroy(e);
-    void *ptrs[] = {t->d_tcol, t->d_trow, t->d_tval, t->d_pavg, t->d_pm2, t->d_partial, t->d_ticket, t->d_twin_perm, t->d_prob_sum};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (t->h_res) (void)hipHostFree(t->h_res);
     delete t;
     return BPMF_HIP_OK;
 }
@@ -145,7 +129,7 @@ void flush_deferred(bpmf_hip_test *t, bool on_main)
     (void)hipSetDevice(t->side->ctx->device);
     // (on_main: the end of a run -- behind the last sampler on its own stream, no cross-queue hop)
     if (on_main) t->side->ctx->last_sampler_done = nullptr;
-    dispatch_predict(t, t->side, t->def_self_items, t->def_other_items, t->def_n, on_main ? t->side->ctx->stream : o->saux, true);
+    dispatch_predict(t, t->side, t->def_self_items, t->def_other_items, t->def_n, on_main ? t->side->ctx->stream.get() : o->saux.get(), true);
     trace("predict: enqueued", t->side, t->def_n);
 }
 
@@ -161,7 +145,7 @@ extern "C" int bpmf_hip_test_set_twin(bpmf_hip_test *t, bpmf_hip_test *twin)
         return fail(BPMF_HIP_EINVAL, "test_set_twin: the twin must sit on the other side of the same pair");
     HIP_TRY(hipSetDevice(t->side->ctx->device));
     if (t->twin) t->twin->owner = nullptr;
-    if (t->d_twin_perm) { (void)hipFree(t->d_twin_perm); t->d_twin_perm = nullptr; }
+    t->d_twin_perm.reset();
     t->twin = twin;
     if (!twin) return BPMF_HIP_OK;
     twin->owner = t;
@@ -213,11 +197,10 @@ extern "C" int bpmf_hip_test_set_twin(bpmf_hip_test *t, bpmf_hip_test *twin)
         }
         if (ok) {
             int rc;
-            if ((rc = dev_upload(&t->d_twin_perm, perm.data(), perm.size()))) return rc;
+            if ((rc = t->d_twin_perm.upload(perm.data(), perm.size()))) return rc;
             // the fused kernel writes the twin's block partials with the OWNER's grid
             if (twin->nblocks < t->nblocks) {
-                if (twin->d_partial) (void)hipFree(twin->d_partial);
-                if ((rc = dev_upload<double>(&twin->d_partial, nullptr, (size_t)t->nblocks * 2))) return rc;
+                if ((rc = twin->d_partial.alloc((size_t)t->nblocks * 2))) return rc;
             }
         }
     }
@@ -250,21 +233,21 @@ extern "C" int bpmf_hip_predict_launch(bpmf_hip_test *t, const bpmf_hip_side *se
         // the samplers this evaluation is about: the stop event of the newest one if nothing else
         // went to the main stream since, else a marker (a packet between two samplers)
         if (c->last_sampler_done) t->in_ev = c->last_sampler_done;
-        else { HIP_TRY(hipEventRecord(t->ev_in, c->stream)); t->in_ev = t->ev_in; }
+        else { HIP_TRY(hipEventRecord(t->ev_in.get(), c->stream.get())); t->in_ev = t->ev_in.get(); }
         t->deferred = true; t->def_n = n; t->def_other = other;
         t->def_self_items = self->d_items; t->def_other_items = other->d_items;
         other->deferred_eval = t;
         bpmf_hip_side *sm = t->side;
         sm->readers[sm->cur_buf].t = t; sm->readers[sm->cur_buf].seq = t->seq + 1;
         other->readers[other->cur_buf].t = t; other->readers[other->cur_buf].seq = t->seq + 1;
-        t->pstream = other->saux;
+        t->pstream = other->saux.get();
         t->launched = true;
         if (t->twin) t->twin->launched = true;                        // (enqueued with this one: flush_deferred)
         trace("predict: deferred", self, n);
         return BPMF_HIP_OK;
     }
     c->last_sampler_done = nullptr;
-    dispatch_predict(t, self, self->d_items, other->d_items, n, c->stream, false);
+    dispatch_predict(t, self, self->d_items, other->d_items, n, c->stream.get(), false);
     HIP_TRY(hipGetLastError());
     t->launched = true;
     trace("predict: enqueued", self, n);
@@ -292,24 +275,24 @@ extern "C" int bpmf_hip_predict_finish(bpmf_hip_test *t, double *se, double *se_
     HIP_TRY(hipSetDevice(c->device));
     const bool dist = c->comm && !self->bounds.empty();
     if (t->nnz == 0 && !dist) { *se = 0.0; *se_avg = 0.0; *count = 0; return BPMF_HIP_OK; }
-    unsigned *flag = reinterpret_cast<unsigned *>(t->h_res + 2);     // the sequence number published behind the two sums
+    unsigned *flag = reinterpret_cast<unsigned *>(t->h_res.host() + 2);     // the sequence number published behind the two sums
     if (!spin_for_seq(flag, t->seq)) {
         { const int rs_ = bounded_stream_sync(t->side->ctx, live_pstream(t), __func__); if (rs_) return rs_; }
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != t->seq) return fail(BPMF_HIP_ENODEV, "device did not publish its results");
     }
     t->done_seq = t->seq;                                           // every block has read its factors
     trace("predict: sums landed", self, 0);
-    *se = t->h_res[0];
-    *se_avg = t->h_res[1];
+    *se = t->h_res.host()[0];
+    *se_avg = t->h_res.host()[1];
     *count = t->nnz;
     if (dist) {
         if (t->global_nnz < 0) {                                   // once: number of test ratings over all ranks
             COMM_ALIVE_OR_FAIL(c, "predict_finish");
-            long long v = (long long)t->nnz, *d = reinterpret_cast<long long *>(c->d_red + blob::red_count(c->K));
-            HIP_TRY(hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
-            NCCL_TRY(rccl()->AllReduce(d, d, 1, ncclInt64, ncclSum, c->comm, c->stream));
-            HIP_TRY(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, c->stream));
-            { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+            long long v = (long long)t->nnz, *d = reinterpret_cast<long long *>(c->d_red.get() + blob::red_count(c->K));
+            HIP_TRY(hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, c->stream.get()));
+            NCCL_TRY(rccl()->AllReduce(d, d, 1, ncclInt64, ncclSum, c->comm, c->stream.get()));
+            HIP_TRY(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, c->stream.get()));
+            { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
             t->global_nnz = v;
         }
         *count = t->global_nnz;
@@ -330,11 +313,11 @@ extern "C" int bpmf_hip_test_get(bpmf_hip_test *t, double *pavg, double *pm2)
 {
     if (!t) return fail(BPMF_HIP_EINVAL, "test_get: NULL");
     HIP_TRY(hipSetDevice(t->side->ctx->device));
-    { const int rs_ = bounded_stream_sync(t->side->ctx, t->side->ctx->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(t->side->ctx, t->side->ctx->stream.get(), __func__); if (rs_) return rs_; }
     flush_deferred(t);
     { const int rs_ = bounded_stream_sync(t->side->ctx, live_pstream(t), __func__); if (rs_) return rs_; }
-    if (pavg) HIP_TRY(hipMemcpy(pavg, t->d_pavg, (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
-    if (pm2) HIP_TRY(hipMemcpy(pm2, t->d_pm2, (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (pavg) HIP_TRY(hipMemcpy(pavg, t->d_pavg.get(), (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    if (pm2) HIP_TRY(hipMemcpy(pm2, t->d_pm2.get(), (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
 

@@ -39,7 +39,7 @@ int foldin_free_set(bpmf_hip_side *s)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
     f->rowptr.reset(); f->colidx.reset(); f->ring.reset();
     f->n = 0; f->S = 0;
     if (f->hmax == 0) s->foldin.reset();
@@ -195,7 +195,7 @@ extern "C" int bpmf_hip_foldin(bpmf_hip_side *side, bpmf_hip_side *cand, double 
     int rc;
     if ((rc = settle_async(side)) || (rc = settle_async(cand))) return rc;
     if (f->ring) {                                                      // an earlier set: nothing on the stream may still read it
-        if ((rc = bounded_stream_sync(c, c->stream, __func__))) return rc;
+        if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;
         f->rowptr.reset(); f->colidx.reset(); f->ring.reset(); f->n = 0; f->S = 0;
     }
     const size_t ring_words = (size_t)n_new * (size_t)S * (size_t)kp;
@@ -215,15 +215,15 @@ extern "C" int bpmf_hip_foldin(bpmf_hip_side *side, bpmf_hip_side *cand, double 
     p.alpha = d_alpha.get(); p.lam = d_lam.get(); p.lmu = d_lmu.get(); p.S = S;
     p.K = c->K; p.kt = c->Kt; p.kp = kp; p.mean_rating = mean_rating; p.tag = tag; p.draw = draw ? 1 : 0;
     p.out = d_ring.get(); p.fail = f->fail.dev();
-    for (hipEvent_t &e : f->timed) if (!e) HIP_TRY(hipEventCreate(&e));
+    for (Event &e : f->timed) if (!e) { const int re = e.create(); if (re) return re; }
     f->last_ms = -1.f;
-    HIP_TRY(hipEventRecord(f->timed[0], c->stream));
-    if (bpmf_launch::foldin(p, c->stream)) return fail(BPMF_HIP_EINVAL, "foldin: unsupported shape");
+    HIP_TRY(hipEventRecord(f->timed[0].get(), c->stream.get()));
+    if (bpmf_launch::foldin(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "foldin: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "foldin: kernel launch failed");
-    HIP_TRY(hipEventRecord(f->timed[1], c->stream));
+    HIP_TRY(hipEventRecord(f->timed[1].get(), c->stream.get()));
     c->last_sampler_done = nullptr;
-    if ((rc = bounded_stream_sync(c, c->stream, "foldin"))) return rc;
-    if (hipEventElapsedTime(&f->last_ms, f->timed[0], f->timed[1]) != hipSuccess) { (void)hipGetLastError(); f->last_ms = -1.f; }
+    if ((rc = bounded_stream_sync(c, c->stream.get(), "foldin"))) return rc;
+    if (hipEventElapsedTime(&f->last_ms, f->timed[0].get(), f->timed[1].get()) != hipSuccess) { (void)hipGetLastError(); f->last_ms = -1.f; }
     f->rowptr = std::move(d_ptr); f->colidx = std::move(d_idx); f->ring = std::move(d_ring);
     f->n = n_new; f->S = S; f->kp = kp;
     const unsigned long long bad = __atomic_load_n(f->fail.host(), __ATOMIC_ACQUIRE);
@@ -244,7 +244,7 @@ extern "C" int bpmf_hip_foldin_get(bpmf_hip_side *s, double *E_host)
     if (!f || !f->ring) return fail(BPMF_HIP_EINVAL, "foldin_get: the side has no folded-in rows (bpmf_hip_foldin)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rc = bounded_stream_sync(c, c->stream, "foldin_get"); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), "foldin_get"); if (rc) return rc; }
     const size_t kt = (size_t)c->Kt, kp = (size_t)f->kp, rows = (size_t)f->n * (size_t)f->S;
     HIP_TRY(hipMemcpy2D(E_host, kt * sizeof(double), f->ring.get(), kp * sizeof(double), kt * sizeof(double), rows, hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
@@ -257,7 +257,7 @@ extern "C" int bpmf_hip_foldin_get_padded(bpmf_hip_side *s, double *E_host)
     if (!f || !f->ring) return fail(BPMF_HIP_EINVAL, "foldin_get_padded: the side has no folded-in rows (bpmf_hip_foldin)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rc = bounded_stream_sync(c, c->stream, "foldin_get_padded"); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), "foldin_get_padded"); if (rc) return rc; }
     HIP_TRY(hipMemcpy(E_host, f->ring.get(), (size_t)f->n * (size_t)f->S * (size_t)f->kp * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }

@@ -46,7 +46,7 @@ extern "C" int bpmf_hip_side_set_implicit(bpmf_hip_side *s, double w0, const dou
     if (!w && !(1.0 > w0)) return fail(BPMF_HIP_EINVAL, "side_set_implicit: without confidences every rating has w = 1, which needs w0 < 1");
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     // sw = sqrt(w - w0) and zw = w r / sw are formed on the host in IEEE arithmetic, as side_set_weights forms its arrays (the
     // ratings come back from the device: a side keeps no host copy of them)
     const size_t n = (size_t)s->nnz;
@@ -84,7 +84,7 @@ extern "C" int bpmf_hip_side_implicit_gram(bpmf_hip_side *s, double *G_host)
     if (!s->implicit) return fail(BPMF_HIP_EINVAL, "side_implicit_gram: the side is not implicit (bpmf_hip_side_set_implicit)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     HIP_TRY(hipMemcpy(G_host, s->implicit->gram.get(), (size_t)c->Kt * c->Kt * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
@@ -111,7 +111,7 @@ extern "C" int bpmf_hip_implicit_sample(bpmf_hip_side *self, bpmf_hip_side *othe
     const int K = c->K, Kt = c->Kt;
     const int64_t N = self->ncols;
     const int iter = self->iter + 1;
-    hipStream_t st = c->stream;
+    hipStream_t st = c->stream.get();
     bpmf_implicit *im = self->implicit.get();
     std::vector<double> mu((size_t)Kt), LU((size_t)Kt * Kt), LF((size_t)Kt * Kt);
 

@@ -19,7 +19,9 @@
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// The device memory of the last ten (probit, censoring, weights, Student-t noise, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h.
+// The device memory of the last ten (probit, censoring, weights, Student-t noise, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h
+// and counted by bpmf_hip_live_device_bytes; the core state of a context, a side and a test set (state.h) is owned the same way -- DevBuf / Pinned / Event / Stream members
+// (devbuf.h), released by `delete` -- and counted by bpmf_hip_live_core_bytes.  No file but devbuf.h allocates or releases device memory, pinned memory, events or streams.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>

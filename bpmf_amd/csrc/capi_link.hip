@@ -79,7 +79,7 @@ int offsets_update(bpmf_hip_side *s)
     const bpmf_hip_ctx *c = s->ctx;
     const bpmf_link *L = s->link.get();
     if (L->sparse) return link_sparse_offsets(s);
-    return nn_product(L->dense->F.get(), L->D, L->beta.get(), c->K, s->ncols, L->D, c->Kt, L->m.get(), c->K, c->K, c->stream);
+    return nn_product(L->dense->F.get(), L->D, L->beta.get(), c->K, s->ncols, L->D, c->Kt, L->m.get(), c->K, c->K, c->stream.get());
 }
 
 int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
@@ -88,7 +88,7 @@ int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
     bpmf_launch::LinkResidualLaunch p{};
     p.colptr = s->d_colptr.get(); p.ncols = s->ncols; p.rowidx = s->d_rowidx; p.vals = s->d_vals; p.nnz = s->nnz;
     p.offs = s->link->m.get(); p.other = other->d_items; p.K = c->K; p.kt = c->Kt; p.out = out;
-    if (bpmf_launch::link_residual(p, c->stream)) return fail(BPMF_HIP_EINVAL, "link: unsupported K " + std::to_string(c->K));
+    if (bpmf_launch::link_residual(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "link: unsupported K " + std::to_string(c->K));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -97,11 +97,11 @@ int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
 int shift_and_norm(bpmf_hip_side *s, double *items, const double *offs, int64_t total, double *norm)
 {
     bpmf_hip_ctx *c = s->ctx;
-    bpmf_launch::link_shift(items, offs, total, s->link->norm.get(), c->stream);
+    bpmf_launch::link_shift(items, offs, total, s->link->norm.get(), c->stream.get());
     HIP_TRY(hipGetLastError());
     const int nb = bpmf_launch::link_shift_blocks(total);
     std::vector<double> part((size_t)std::max(nb, 1), 0.0);
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if (nb > 0) HIP_TRY(hipMemcpy(part.data(), s->link->norm.get(), (size_t)nb * sizeof(double), hipMemcpyDeviceToHost));
     double nn = 0.0;
     for (int b = 0; b < nb; ++b) nn += part[(size_t)b];
@@ -159,9 +159,9 @@ int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, 
         (rc = L->r.alloc((size_t)s->nnz)) || (rc = L->part.alloc(part_words)) || (rc = L->mu.alloc(ld)) || (rc = L->btb.alloc(Kt * Kt)) ||
         (rc = L->norm.alloc((size_t)nblk)) || (rc = ensure_colptr(s)))
         return rc;
-    if ((rc = L->beta.zero_async(c->stream)) || (rc = L->beta_sum.zero_async(c->stream)) || (rc = L->m.zero_async(c->stream))) return rc;
+    if ((rc = L->beta.zero_async(c->stream.get())) || (rc = L->beta_sum.zero_async(c->stream.get())) || (rc = L->m.zero_async(c->stream.get()))) return rc;
     // (the residuals of M = 0 are the ratings: a sampler that ran before the first link_sample would still read ratings)
-    if (s->nnz > 0) HIP_TRY(hipMemcpyAsync(L->r.get(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (s->nnz > 0) HIP_TRY(hipMemcpyAsync(L->r.get(), s->d_vals, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToDevice, c->stream.get()));
     *out = std::move(L);
     return 0;
 }
@@ -200,8 +200,8 @@ extern "C" int bpmf_hip_side_set_features(bpmf_hip_side *s, const double *F_host
     {   // G = F^T F on the device, factored and inverted on the host
         DevBuf<double> d_G, d_part0;
         if ((rc = d_G.alloc(DD)) || (rc = d_part0.alloc(bpmf_launch::link_tn_part_words(N, D, std::min(D, 128))))) return rc;
-        if ((rc = tn_product(dn->F.get(), D, dn->F.get(), D, nullptr, N, D, D, d_G.get(), D, d_part0.get(), c->stream))) return rc;
-        if ((rc = bounded_stream_sync(c, c->stream, __func__))) return rc;
+        if ((rc = tn_product(dn->F.get(), D, dn->F.get(), D, nullptr, N, D, D, d_G.get(), D, d_part0.get(), c->stream.get()))) return rc;
+        if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;
         if (hipMemcpy(G.data(), d_G.get(), DD * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_set_features: copy of G failed");
     }
     for (int d = 0; d < D; ++d) G[(size_t)d * D + d] += lambda_beta;
@@ -211,7 +211,7 @@ extern "C" int bpmf_hip_side_set_features(bpmf_hip_side *s, const double *F_host
         memcpy(&W[(size_t)a * 2 * D], &Ginv[(size_t)a * D], sizeof(double) * D);
         memcpy(&W[(size_t)a * 2 * D + D], &T[(size_t)a * D], sizeof(double) * D);
     }
-    if ((rc = dn->W.upload(W.data(), 2 * DD)) || (rc = dn->PE.alloc(2 * (size_t)D * K)) || (rc = dn->PE.zero_async(c->stream))) return rc;
+    if ((rc = dn->W.upload(W.data(), 2 * DD)) || (rc = dn->PE.alloc(2 * (size_t)D * K)) || (rc = dn->PE.zero_async(c->stream.get()))) return rc;
     L->dense = std::move(dn);
     s->link = std::move(L);
     return BPMF_HIP_OK;
@@ -236,7 +236,7 @@ extern "C" int bpmf_hip_link_sample(bpmf_hip_side *self, bpmf_hip_side *other, d
     const int64_t N = self->ncols;
     const int iter = self->iter + 1;
     const bool link = L != nullptr;
-    hipStream_t st = c->stream;
+    hipStream_t st = c->stream.get();
     std::vector<double> mu((size_t)Kt), LU((size_t)Kt * Kt), LF((size_t)Kt * Kt), scatter;
 
     // 1. hyper-parameters: the link's scatter lambda_beta beta^T beta (K x K, formed on the device) and its D degrees of freedom.
@@ -309,7 +309,7 @@ extern "C" int bpmf_hip_side_link_get(bpmf_hip_side *s, double *beta_host, doubl
     if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_get: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     const size_t K = (size_t)c->K, Kt = (size_t)c->Kt;
     if (beta_host) HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->link->beta.get(), K * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyDeviceToHost));
     if (offsets_host && s->ncols > 0)
@@ -327,7 +327,7 @@ extern "C" int bpmf_hip_side_link_set(bpmf_hip_side *s, const double *beta_host)
         if (!std::isfinite(beta_host[q])) return fail(BPMF_HIP_EINVAL, "side_link_set: beta is not finite");
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     HIP_TRY(hipMemcpy2D(s->link->beta.get(), K * sizeof(double), beta_host, Kt * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyHostToDevice));
     return offsets_update(s);
 }
@@ -338,7 +338,7 @@ extern "C" int bpmf_hip_side_link_add(bpmf_hip_side *s)
     if (!s->link) return fail(BPMF_HIP_EINVAL, "side_link_add: the side has no features (bpmf_hip_side_set_features)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    bpmf_launch::link_shift(s->link->beta_sum.get(), s->link->beta.get(), (int64_t)s->link->D * c->K, s->link->norm.get(), c->stream);   // (sum += beta; the norm goes unused)
+    bpmf_launch::link_shift(s->link->beta_sum.get(), s->link->beta.get(), (int64_t)s->link->D * c->K, s->link->norm.get(), c->stream.get());   // (sum += beta; the norm goes unused)
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
     ++s->link->nsum;
@@ -353,7 +353,7 @@ extern "C" int bpmf_hip_side_link_mean(bpmf_hip_side *s, double *beta_host, int 
     if (s->link->nsum == 0) return fail(BPMF_HIP_EINVAL, "side_link_mean: nothing added (bpmf_hip_side_link_add)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     const size_t K = (size_t)c->K, Kt = (size_t)c->Kt;
     HIP_TRY(hipMemcpy2D(beta_host, Kt * sizeof(double), s->link->beta_sum.get(), K * sizeof(double), Kt * sizeof(double), (size_t)s->link->D, hipMemcpyDeviceToHost));
     const double n = (double)s->link->nsum;
@@ -370,7 +370,7 @@ extern "C" int bpmf_hip_side_link_residual(bpmf_hip_side *s, const bpmf_hip_side
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rc = residual_enqueue(s, other, s->link->r.get()); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if (s->nnz > 0) HIP_TRY(hipMemcpy(r_host, s->link->r.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }

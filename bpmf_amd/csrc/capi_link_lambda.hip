@@ -62,10 +62,10 @@ int link_chol_enter(bpmf_hip_side *s)
     if ((rc = settle_async(s))) return rc;
     DevBuf<double> part0;
     if ((rc = dn->FtF.alloc((size_t)D * D)) || (rc = part0.alloc(bpmf_launch::link_tn_part_words(N, D, std::min(D, 128)))) ||
-        (rc = chol_alloc(D, dn->Lp, dn->Linv, dn->LinvT, dn->Xp, dn->Ep, dn->flag, c->stream)))
+        (rc = chol_alloc(D, dn->Lp, dn->Linv, dn->LinvT, dn->Xp, dn->Ep, dn->flag, c->stream.get())))
         return rc;
-    if ((rc = link_tn_product(dn->F.get(), D, dn->F.get(), D, nullptr, N, D, D, dn->FtF.get(), D, part0.get(), c->stream))) return rc;
-    if ((rc = bounded_stream_sync(c, c->stream, __func__))) return rc;     // (part0 goes out of use here)
+    if ((rc = link_tn_product(dn->F.get(), D, dn->F.get(), D, nullptr, N, D, D, dn->FtF.get(), D, part0.get(), c->stream.get()))) return rc;
+    if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;     // (part0 goes out of use here)
     dn->W.reset();
     dn->devfac = true;
     dn->fact_lambda = 0.0;                                                 // (no factor yet: lambda_beta > 0 always differs)
@@ -82,16 +82,16 @@ int link_chol_draw(bpmf_hip_side *s)
         bpmf_launch::LinkCholLaunch f{};
         f.FtF = dn->FtF.get(); f.D = D; f.lambda = L->lambda; f.Lp = dn->Lp.get(); f.Linv = dn->Linv.get(); f.LinvT = dn->LinvT.get();
         f.flag = dn->flag.get();
-        if (bpmf_launch::link_chol_factor(f, c->stream)) return fail(BPMF_HIP_EINVAL, "link: unsupported shape of the device factorisation");
+        if (bpmf_launch::link_chol_factor(f, c->stream.get())) return fail(BPMF_HIP_EINVAL, "link: unsupported shape of the device factorisation");
         dn->fact_lambda = 0.0;                                             // (valid only once the flag has been collected)
     }
     bpmf_launch::LinkCholSolveLaunch q{};
     q.Lp = dn->Lp.get(); q.Linv = dn->Linv.get(); q.LinvT = dn->LinvT.get(); q.D = D;
     q.P = dn->PE.get(); q.ldp = K; q.E = dn->PE.get() + (size_t)D * K; q.lde = K; q.n = Kt;
     q.Xp = dn->Xp.get(); q.Ep = dn->Ep.get(); q.out = L->beta.get(); q.ldo = K; q.ncw = K;
-    if (bpmf_launch::link_chol_solve(q, c->stream)) return fail(BPMF_HIP_EINVAL, "link: unsupported shape of the device solves");
+    if (bpmf_launch::link_chol_solve(q, c->stream.get())) return fail(BPMF_HIP_EINVAL, "link: unsupported shape of the device solves");
     HIP_TRY(hipGetLastError());
-    const int rc = chol_collect(dn->flag.get(), c->stream, "link_sample: F^T F + lambda_beta I");
+    const int rc = chol_collect(dn->flag.get(), c->stream.get(), "link_sample: F^T F + lambda_beta I");
     if (rc) return rc;
     dn->fact_lambda = L->lambda;
     return 0;

@@ -76,7 +76,7 @@ int link_sparse_offsets(bpmf_hip_side *s)
 {
     const bpmf_hip_ctx *c = s->ctx;
     const bpmf_link *L = s->link.get();
-    if (bpmf_launch::sp_product(L->sparse->F, L->beta.get(), c->K, c->Kt, c->K, L->m.get(), c->K, 0.0, nullptr, 0, c->stream))
+    if (bpmf_launch::sp_product(L->sparse->F, L->beta.get(), c->K, c->Kt, c->K, L->m.get(), c->K, 0.0, nullptr, 0, c->stream.get()))
         return fail(BPMF_HIP_EINVAL, "link: unsupported shape of the sparse product");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -89,7 +89,7 @@ int link_sparse_draw(bpmf_hip_side *s, const double *mu, const double *LU, int i
     bpmf_link_sparse *sp = L->sparse.get();
     const int K = c->K, Kt = c->Kt, D = L->D;
     const int64_t N = s->ncols;
-    hipStream_t st = c->stream;
+    hipStream_t st = c->stream.get();
     // R^-1 (upper triangular, row-major) of Lambda = R^T R, R = LambdaU (upper, column-major): K^3 on the host
     std::vector<double> Rinv((size_t)Kt * Kt, 0.0), pad((size_t)K, 0.0);
     for (int col = 0; col < Kt; ++col)
@@ -132,8 +132,8 @@ extern "C" int bpmf_hip_side_set_features_sparse(bpmf_hip_side *s, int D, const 
     if ((rc = link_attach_common("side_set_features_sparse", s, D, lambda_beta, tag, bpmf_launch::link_tn_part_words(D, Kt, Kt), &L))) return rc;
     auto sp = std::make_unique<bpmf_link_sparse>();
     if ((rc = upload_both(sp->F, sp->Ft, N, D, rowptr, colidx, vals, Kt)) || (rc = bpmf_launch::cg_alloc(sp->cg, N, D, K, true)) ||
-        (rc = sp->rhs.alloc((size_t)D * K)) || (rc = sp->rinv.alloc((size_t)Kt * Kt)) || (rc = sp->rhs.zero_async(c->stream)) ||
-        (rc = sp->cg.t.zero_async(c->stream)))
+        (rc = sp->rhs.alloc((size_t)D * K)) || (rc = sp->rinv.alloc((size_t)Kt * Kt)) || (rc = sp->rhs.zero_async(c->stream.get())) ||
+        (rc = sp->cg.t.zero_async(c->stream.get())))
         return rc;
     L->sparse = std::move(sp);
     s->link = std::move(L);

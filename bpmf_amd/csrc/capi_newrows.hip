@@ -29,7 +29,7 @@ int newrows_attach(const char *who, bpmf_hip_side *s, int64_t n_new, int max_sam
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     if (s->newrows) {
-        if ((rc = bounded_stream_sync(c, c->stream, __func__))) return rc;
+        if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;
         s->newrows.reset();
     }
     auto nr = std::make_unique<bpmf_newrows>();
@@ -40,9 +40,9 @@ int newrows_attach(const char *who, bpmf_hip_side *s, int64_t n_new, int max_sam
         return fail(BPMF_HIP_ENOMEM, w + ": " + std::to_string(max_samples) + " samples of " + std::to_string((long long)n_new) + " new rows x " +
                     std::to_string(nr->kp) + " doubles (" + mib(ring_words) + ") and " + std::to_string((long long)nr->nw) + " x " +
                     std::to_string(nr->kp) + " doubles of work (" + mib(y_words) + ") do not fit in device memory");
-    if ((rc = nr->ring.zero_async(c->stream)) || (rc = nr->w.zero_async(c->stream))) return rc;
+    if ((rc = nr->ring.zero_async(c->stream.get())) || (rc = nr->w.zero_async(c->stream.get()))) return rc;
     if ((rc = nr->stage.alloc(2 * ((size_t)c->Kt * c->Kt + c->Kt)))) return rc;
-    for (hipEvent_t &e : nr->staged) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event &e : nr->staged) { const int re = e.create(hipEventDisableTiming); if (re) return re; }
     *out = std::move(nr);
     return 0;
 }
@@ -53,7 +53,7 @@ int newrows_free(bpmf_hip_side *s)
     if (!s->newrows) return BPMF_HIP_OK;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
     s->newrows.reset();
     return BPMF_HIP_OK;
 }
@@ -91,9 +91,9 @@ int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t 
     p.qring = r.qring; p.cring = r.cring; p.qstride = r.qstride; p.cstride = r.cstride; p.Kp = r.kp; p.S = r.S; p.mean_rating = mean_rating;
     p.q_from = q_from; p.nq = nq; p.c_from = c_from; p.nc = nc; p.w = w;
     p.mean = in_place ? mean_out : out.get(); p.std = in_place ? std_out : out.get() + cells;
-    if (bpmf_launch::predict_block(p, c->stream)) return fail(BPMF_HIP_EINVAL, ws + ": unsupported shape of the block");
+    if (bpmf_launch::predict_block(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, ws + ": unsupported shape of the block");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, ws + ": kernel launch failed");
-    { const int rc = bounded_stream_sync(c, c->stream, who); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), who); if (rc) return rc; }
     if (!in_place && (hipMemcpy(mean_out, out.get(), cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
                       hipMemcpy(std_out, out.get() + cells, cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
         return fail(BPMF_HIP_ENODEV, ws + ": copying the results back failed");
@@ -183,7 +183,7 @@ extern "C" int bpmf_hip_side_newrows_add(bpmf_hip_side *s, bpmf_hip_side *other)
         return fail(BPMF_HIP_EINVAL, "side_newrows_add: the side has no hyper-parameters yet (after a bpmf_hip_link_sample)");
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s)) || (rc = settle_async(other))) return rc;
-    hipStream_t st = c->stream;
+    hipStream_t st = c->stream.get();
     const bpmf_link *L = s->link.get();
     const int slot = nr->count;
     const int64_t stride = (int64_t)nr->max * kp;
@@ -191,7 +191,7 @@ extern "C" int bpmf_hip_side_newrows_add(bpmf_hip_side *s, bpmf_hip_side *other)
     // pinned halves (R^-1 | mu) taken in turn; the event of a half says that the copies which read it two calls ago are done
     const std::vector<double> &LU = s->hp_LambdaU;
     const int half = slot & 1;
-    if (slot >= 2) HIP_TRY(hipEventSynchronize(nr->staged[half]));
+    if (slot >= 2) HIP_TRY(hipEventSynchronize(nr->staged[half].get()));
     double *Rinv = nr->stage.host() + (size_t)half * ((size_t)Kt * Kt + Kt), *mu = Rinv + (size_t)Kt * Kt;
     std::fill(Rinv, Rinv + (size_t)Kt * Kt, 0.0);
     for (int col = 0; col < Kt; ++col)
@@ -205,7 +205,7 @@ extern "C" int bpmf_hip_side_newrows_add(bpmf_hip_side *s, bpmf_hip_side *other)
     memcpy(mu, s->hp_mu.data(), sizeof(double) * Kt);
     HIP_TRY(hipMemcpyAsync(nr->mu.get(), mu, sizeof(double) * Kt, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(nr->rinv.get(), Rinv, sizeof(double) * Kt * Kt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(nr->staged[half], st));
+    HIP_TRY(hipEventRecord(nr->staged[half].get(), st));
     // E[:, slot, :] = F_new beta (pad rows zero) + 1 mu^T
     double *E = nr->ring.get() + (size_t)slot * kp;
     if (nr->sp) {
@@ -234,7 +234,7 @@ static int newrows_ring_to_host(const char *who, bpmf_hip_side *s, std::vector<d
     if (nr->count < 1) return fail(BPMF_HIP_EINVAL, w + ": nothing added (bpmf_hip_side_newrows_add)");
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, who); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), who); if (rs_) return rs_; }
     if (!out) return BPMF_HIP_OK;
     const size_t kp = (size_t)nr->kp, S = (size_t)nr->count;
     out->resize((size_t)nr->n * S * kp);

@@ -35,10 +35,10 @@ extern "C" int bpmf_hip_train_sse(bpmf_hip_side *self, bpmf_hip_side *other, dou
     p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.vals = self->d_vals; p.nnz = self->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
     p.mean = self->mean_rating; p.partial = self->sse->part.get(); p.nblk = self->sse->nblk;
-    if (bpmf_launch::train_sse(p, c->stream)) return fail(BPMF_HIP_EINVAL, "train_sse: unsupported K " + std::to_string(c->K));
+    if (bpmf_launch::train_sse(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "train_sse: unsupported K " + std::to_string(c->K));
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "train_sse: kernel launch failed");
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     HIP_TRY(hipMemcpy(sse, self->sse->part.get() + self->sse->nblk, sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }

@@ -95,11 +95,11 @@ int loglik_pass(const char *who, bpmf_hip_side *self, bpmf_hip_side *other, cons
     p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.level = o->level.get(); p.nnz = self->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
     p.g0 = o->g.get(); p.g1 = o->g_prop.get(); p.nlev = o->nlev; p.partial = o->part.get();
-    if (bpmf_launch::ordinal_loglik(p, c->stream)) return fail(BPMF_HIP_EINVAL, std::string(who) + ": unsupported K " + std::to_string(c->K));
+    if (bpmf_launch::ordinal_loglik(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, std::string(who) + ": unsupported K " + std::to_string(c->K));
     ++o->loglik_launches;
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, std::string(who) + ": kernel launch failed");
-    { const int rs_ = bounded_stream_sync(c, c->stream, who); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), who); if (rs_) return rs_; }
     HIP_TRY(hipMemcpy(out, o->part.get() + 2 * bpmf_launch::ordinal_blocks(self->nnz), 2 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -184,7 +184,7 @@ extern "C" int bpmf_hip_side_set_ordinal(bpmf_hip_side *s, const double *levels,
     const size_t nblk = (size_t)bpmf_launch::ordinal_blocks(s->nnz);
     if ((rc = o->z.alloc((size_t)s->nnz)) || (rc = o->level.upload(lev.data(), (size_t)s->nnz)) || (rc = ensure_colptr(s)) ||
         (rc = o->g.alloc((size_t)nlevels + 1)) || (rc = o->g_prop.alloc((size_t)nlevels + 1)) || (rc = o->part.alloc(2 * nblk + 2)) ||
-        (rc = o->fail.alloc(1)) || (rc = o->z.zero_async(c->stream)))
+        (rc = o->fail.alloc(1)) || (rc = o->z.zero_async(c->stream.get())))
         return rc;
     *o->fail.host() = ~0ull;
     s->ordinal = std::move(o);
@@ -209,7 +209,7 @@ extern "C" int bpmf_hip_side_ordinal_latent(bpmf_hip_side *s, double *z_host)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     { std::string m; if (check_ordinal(s, &m)) return fail(BPMF_HIP_ENUM, m); }
     if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->ordinal->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
@@ -231,7 +231,7 @@ extern "C" int bpmf_hip_side_ordinal_cut_set(bpmf_hip_side *s, const double *cut
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }     // (a latent kernel in flight reads the old table)
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }     // (a latent kernel in flight reads the old table)
     return store_cutpoints(s, cutpoints);
 }
 
@@ -306,16 +306,16 @@ extern "C" int bpmf_hip_test_ordinal_add(bpmf_hip_test *t, bpmf_hip_side *self, 
     HIP_TRY(hipSetDevice(c->device));
     if (!t->ord_sum) {
         int rc = t->ord_sum.alloc((size_t)t->nnz * (size_t)o->nlev);
-        if (!rc) rc = t->ord_sum.zero_async(c->stream);
+        if (!rc) rc = t->ord_sum.zero_async(c->stream.get());
         if (rc) return rc;
         t->ord_nlev = o->nlev; t->ord_n = 0;
     }
     if (t->ord_nlev != o->nlev) return fail(BPMF_HIP_EINVAL, "test_ordinal_add: the number of levels changed");
     bpmf_launch::OrdinalProbLaunch p{};
-    p.tcol = t->d_tcol; p.trow = t->d_trow; p.nnz = t->nnz;
+    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
     p.g = o->g.get(); p.nlev = o->nlev; p.sum = t->ord_sum.get();
-    if (bpmf_launch::ordinal_prob(p, c->stream)) return fail(BPMF_HIP_EINVAL, "test_ordinal_add: unsupported K " + std::to_string(c->K));
+    if (bpmf_launch::ordinal_prob(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "test_ordinal_add: unsupported K " + std::to_string(c->K));
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "test_ordinal_add: kernel launch failed");
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     ++t->ord_n;
@@ -330,7 +330,7 @@ extern "C" int bpmf_hip_test_ordinal_get(bpmf_hip_test *t, double *prob_host, in
     if (!t->ord_sum || t->ord_n == 0) return fail(BPMF_HIP_EINVAL, "test_ordinal_get: nothing added (bpmf_hip_test_ordinal_add)");
     bpmf_hip_ctx *c = t->side->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     const size_t n = (size_t)t->nnz, C = (size_t)t->ord_nlev;
     std::vector<double> sum(n * C);
     if (n > 0) HIP_TRY(hipMemcpy(sum.data(), t->ord_sum.get(), n * C * sizeof(double), hipMemcpyDeviceToHost));

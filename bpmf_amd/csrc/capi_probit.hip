@@ -50,11 +50,11 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
     if ((rc = settle_async(s))) return rc;
     auto pb = std::make_unique<bpmf_probit>();
     if ((rc = pb->z.alloc((size_t)s->nnz)) || (rc = pb->sign.alloc((size_t)s->nnz)) || (rc = ensure_colptr(s)) || (rc = pb->fail.alloc(1)) ||
-        (rc = pb->z.zero_async(c->stream)))
+        (rc = pb->z.zero_async(c->stream.get())))
         return rc;
     *pb->fail.host() = ~0ull;
     pb->tag = (uint32_t)tag;
-    bpmf_launch::probit_sign(s->d_vals, s->nnz, threshold, pb->sign.get(), c->stream);
+    bpmf_launch::probit_sign(s->d_vals, s->nnz, threshold, pb->sign.get(), c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_set_probit: kernel launch failed");
     s->probit = std::move(pb);
     return BPMF_HIP_OK;
@@ -67,7 +67,7 @@ extern "C" int bpmf_hip_side_probit_latent(bpmf_hip_side *s, double *z_host)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     { std::string m; if (check_probit(s, &m)) return fail(BPMF_HIP_ENUM, m); }
     if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->probit->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
@@ -82,17 +82,17 @@ extern "C" int bpmf_hip_test_probit_add(bpmf_hip_test *t, bpmf_hip_side *self, b
     { const int rc = require_single_gpu("test_probit_add", c, self, other); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
     if (!t->d_prob_sum) {
-        const int rc = dev_upload<double>(&t->d_prob_sum, nullptr, (size_t)t->nnz);
+        int rc = t->d_prob_sum.alloc((size_t)t->nnz);
+        if (!rc) rc = t->d_prob_sum.zero_async(c->stream.get());
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(t->d_prob_sum, 0, std::max<size_t>((size_t)t->nnz, 1) * sizeof(double), c->stream));
     }
     // S0 holds the newest sampler of both sides and d_items is the copy it writes (as in bpmf_hip_train_sse); whichever
     // sampler rewrites one of these copies later is behind this kernel in the same queue.  Enqueue only: nothing waits.
     bpmf_launch::ProbitProbLaunch p{};
-    p.tcol = t->d_tcol; p.trow = t->d_trow; p.nnz = t->nnz;
+    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz;
     p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
-    p.sum = t->d_prob_sum;
-    if (bpmf_launch::probit_prob(p, c->stream)) return fail(BPMF_HIP_EINVAL, "test_probit_add: unsupported K " + std::to_string(c->K));
+    p.sum = t->d_prob_sum.get();
+    if (bpmf_launch::probit_prob(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "test_probit_add: unsupported K " + std::to_string(c->K));
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "test_probit_add: kernel launch failed");
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     ++t->prob_n;
@@ -106,8 +106,8 @@ extern "C" int bpmf_hip_test_probit_get(bpmf_hip_test *t, double *prob_host, int
     if (!t->d_prob_sum || t->prob_n == 0) return fail(BPMF_HIP_EINVAL, "test_probit_get: nothing added (bpmf_hip_test_probit_add)");
     bpmf_hip_ctx *c = t->side->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    if (t->nnz > 0) HIP_TRY(hipMemcpy(prob_host, t->d_prob_sum, (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
+    if (t->nnz > 0) HIP_TRY(hipMemcpy(prob_host, t->d_prob_sum.get(), (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
     const double inv = (double)t->prob_n;
     for (int64_t q = 0; q < t->nnz; ++q) prob_host[q] /= inv;
     return BPMF_HIP_OK;

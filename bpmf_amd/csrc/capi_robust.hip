@@ -56,7 +56,7 @@ extern "C" int bpmf_hip_side_set_robust(bpmf_hip_side *s, double nu, unsigned ta
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     // w = 1 until the first launch: sw = 1 and zw = r - mean, the fp64 subtraction bpmf_hip_side_set_weights does (the ratings come
     // back from the device: a side keeps no host copy of them)
     const size_t n = (size_t)s->nnz;
@@ -66,7 +66,7 @@ extern "C" int bpmf_hip_side_set_robust(bpmf_hip_side *s, double nu, unsigned ta
     auto ws = std::make_unique<bpmf_weights>();                       // (both freed with everything they hold on every return below)
     auto rb = std::make_unique<bpmf_robust>();
     if ((rc = ws->sw.upload(sw.data(), n)) || (rc = ws->zw.upload(zw.data(), n)) || (rc = rb->wsum.alloc(n)) || (rc = rb->fail.alloc(1)) ||
-        (rc = ensure_colptr(s)) || (rc = rb->wsum.zero_async(c->stream)))
+        (rc = ensure_colptr(s)) || (rc = rb->wsum.zero_async(c->stream.get())))
         return rc;
     *rb->fail.host() = ~0ull;
     rb->nu = nu; rb->tag = (uint32_t)tag;
@@ -83,7 +83,7 @@ extern "C" int bpmf_hip_side_robust_add(bpmf_hip_side *s)
     HIP_TRY(hipSetDevice(c->device));
     // S0 holds the side's newest weight kernel and sampler; the next weight kernel is behind this one in the same queue.  Enqueue
     // only: nothing waits.
-    bpmf_launch::robust_accumulate(s->weights->sw.get(), s->nnz, s->robust->wsum.get(), c->stream);
+    bpmf_launch::robust_accumulate(s->weights->sw.get(), s->nnz, s->robust->wsum.get(), c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "side_robust_add: kernel launch failed");
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     ++s->robust->kept;
@@ -102,7 +102,7 @@ extern "C" int bpmf_hip_side_robust_get(bpmf_hip_side *s, double *wmean_host, in
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     { std::string m; if (check_robust(s, &m)) return fail(BPMF_HIP_ENUM, m); }
     if (s->nnz > 0) HIP_TRY(hipMemcpy(wmean_host, rb->wsum.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
     const double k = (double)rb->kept;

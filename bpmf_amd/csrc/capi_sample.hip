@@ -13,7 +13,7 @@ int claim_second_copy(bpmf_hip_side *s, hipStream_t st)
     bpmf_hip_side::Reader &rd = s->readers[s->cur_buf ^ 1];
     if (rd.t) {
         if (rd.t->deferred && rd.seq == rd.t->seq + 1) flush_deferred(rd.t);      // (the one that reads this copy, not a later one)
-        if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u], 0));
+        if (rd.t->done_seq < rd.seq) HIP_TRY(hipStreamWaitEvent(st, rd.t->ev_done[rd.seq & 1u].get(), 0));
     }
     rd.t = nullptr;
     return 0;
@@ -66,7 +66,7 @@ int reduce_half_iteration(bpmf_hip_side *self, const bpmf_hip_side *other, int i
         for (int r = 0; r < c->nranks; ++r) {
             const int64_t lo = self->bounds[(size_t)r], hi = self->bounds[(size_t)r + 1];
             if (hi > lo) {
-                double *p = self->d_prec + (size_t)lo * part;
+                double *p = self->d_prec.get() + (size_t)lo * part;
                 NCCL_TRY(R->Reduce(p, p, (size_t)(hi - lo) * part, ncclDouble, ncclSum, r, c->comm, st));
             }
         }
@@ -84,13 +84,13 @@ int reduce_half_iteration(bpmf_hip_side *self, const bpmf_hip_side *other, int i
     const int resident = c->num_cu * 4 * bpmf_launch::reduce_waves_per_simd(K);
     const int C = 64 / K;
     const int grid = std::max(1, std::min((a.nwork + C - 1) / C, resident));
-    bpmf_launch::reduce_sample(K, grid, st, ev_start, nullptr, a, self->d_prec);
+    bpmf_launch::reduce_sample(K, grid, st, ev_start, nullptr, a, self->d_prec.get());
     if (a.nwork <= 0 && ev_start) HIP_TRY(hipEventRecord(ev_start, st));
     if (swap) { std::swap(self->d_items, self->d_items_alt); self->cur_buf ^= 1; }
 
     bpmf::PrecArgs p{};
-    p.t_colptr = self->d_t_colptr; p.t_rowidx = self->d_t_rowidx; p.t_vals = self->d_t_vals; p.order = self->d_t_order;
-    p.ncols = other->ncols; p.s_items = self->d_items; p.zero_row = c->d_zero; p.prec = other->d_prec;
+    p.t_colptr = self->d_t_colptr.get(); p.t_rowidx = self->d_t_rowidx.get(); p.t_vals = self->d_t_vals.get(); p.order = self->d_t_order.get();
+    p.ncols = other->ncols; p.s_items = self->d_items; p.zero_row = c->d_zero.get(); p.prec = other->d_prec.get();
     p.mean_rating = other->mean_rating; p.alpha = alpha;
     bpmf_launch::reduce_precompute(K, st, nullptr, ev_stop, p);
     HIP_TRY(hipGetLastError());
@@ -143,15 +143,15 @@ int sample_and_exchange(bpmf_hip_side *self, const bpmf_hip_side *other, int ite
         if (rc) break;
         hipError_t he = hipSuccess;
         if (p == self->nsub - 1 && ev_stop) he = hipEventRecord(ev_stop, st);
-        if (he == hipSuccess) he = hipEventRecord(self->sub_ev[p], st);
-        if (he == hipSuccess) he = hipStreamWaitEvent(self->sx, self->sub_ev[p], 0);
+        if (he == hipSuccess) he = hipEventRecord(self->sub_ev[p].get(), st);
+        if (he == hipSuccess) he = hipStreamWaitEvent(self->sx.get(), self->sub_ev[p].get(), 0);
         if (he != hipSuccess) { rc = fail(BPMF_HIP_ENODEV, std::string("sample_and_exchange: ") + hipGetErrorString(he)); break; }
-        if (travels(p)) rc = bpmf_launch::exchange<K, F32>(self, self->sx, p);
+        if (travels(p)) rc = bpmf_launch::exchange<K, F32>(self, self->sx.get(), p);
     }
     self->item_off = 0; self->item_n = -1;                           // (whatever happened: later launches see the whole item list again)
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(self->sx_done, self->sx));
-    HIP_TRY(hipStreamWaitEvent(st, self->sx_done, 0));
+    HIP_TRY(hipEventRecord(self->sx_done.get(), self->sx.get()));
+    HIP_TRY(hipStreamWaitEvent(st, self->sx_done.get(), 0));
     return 0;
 }
 
@@ -261,28 +261,28 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
     const int K = c->K;
     HIP_TRY(hipSetDevice(c->device));
     { const int rs = settle_async(self); if (rs) return rs; }
-    if (self->saux) { const int rs_ = bounded_stream_sync(self->ctx, self->saux, __func__); if (rs_) return rs_; }
-    fill_blob_ctx(c, mu, LambdaF, c->h_in, K == 64 && c->dtype == BPMF_HIP_F64 && self->lr_n > 0);
+    if (self->saux) { const int rs_ = bounded_stream_sync(self->ctx, self->saux.get(), __func__); if (rs_) return rs_; }
+    fill_blob_ctx(c, mu, LambdaF, c->h_in.host(), K == 64 && c->dtype == BPMF_HIP_F64 && self->lr_n > 0);
     if (self->implicit) {
         // implicit side: the prior precision becomes Lambda + alpha w0 G in the leading Kt x Kt block, behind Lmu = Lambda mu (which
         // keeps the plain Lambda); a weighted side never launches the product form, so the factor tail of the blob goes unread
         const int Kt = c->Kt;
         const double *g = self->implicit->prior.data();
-        double *lf = c->h_in + blob::par_LambdaF(K);
+        double *lf = c->h_in.host() + blob::par_LambdaF(K);
         for (int j = 0; j < Kt; ++j)
             for (int i = 0; i < Kt; ++i) lf[(size_t)j * K + i] += g[(size_t)j * Kt + i];
     }
-    bpmf_launch::stage(c->h_in_dev, c->d_in, (int)c->in_words, c->stream);
-    if (lf32_words(c)) bpmf_launch::lf32_tiles(c->d_in, reinterpret_cast<float *>(c->d_in + c->in_words), K, c->stream);
-    HIP_TRY(hipEventRecord(c->ev[0], c->stream));
+    bpmf_launch::stage(c->h_in.dev(), c->d_in.get(), (int)c->in_words, c->stream.get());
+    if (lf32_words(c)) bpmf_launch::lf32_tiles(c->d_in.get(), reinterpret_cast<float *>(c->d_in.get() + c->in_words), K, c->stream.get());
+    HIP_TRY(hipEventRecord(c->ev[0].get(), c->stream.get()));
     c->last_sampler_done = nullptr;
-    int rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, c->d_in, c->stream, nullptr, nullptr));
+    int rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, c->d_in.get(), c->stream.get(), nullptr, nullptr));
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev[1], c->stream));
-    const bpmf_launch::StatPass sp = bpmf_launch::stat_pass(self, c->d_in, c->h_out_dev, c->d_ticket, ++c->seq);
-    rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, c->stream, sp));
+    HIP_TRY(hipEventRecord(c->ev[1].get(), c->stream.get()));
+    const bpmf_launch::StatPass sp = bpmf_launch::stat_pass(self, c->d_in.get(), c->h_out.dev(), c->d_ticket.get(), ++c->seq);
+    rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, c->stream.get(), sp));
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(c->ev[2], c->stream));
+    HIP_TRY(hipEventRecord(c->ev[2].get(), c->stream.get()));
     // the sums and the fail word land in the pinned result blob; the last wave of k_colstats
     // publishes the sequence number behind them
     HIP_TRY(hipGetLastError());
@@ -338,7 +338,7 @@ extern "C" int bpmf_hip_sample_side_finish(bpmf_hip_side *self, double *sum_out,
     self->pending = false;
     { const int rcw = wait_host(c); if (rcw) return rcw; }
     std::string m;
-    const int rc = read_result_blob(self, c->h_out, sum_out, prod_out, norm_out, &m);
+    const int rc = read_result_blob(self, c->h_out.host(), sum_out, prod_out, norm_out, &m);
     if (rc != BPMF_HIP_ENODEV && rc != BPMF_HIP_ENUM) self->timing_valid = false;     // (the blob was read)
     return rc ? fail(rc, m) : BPMF_HIP_OK;
 }
@@ -363,18 +363,14 @@ extern "C" int bpmf_hip_side_aggr_add(bpmf_hip_side *s)
     { const int rc = settle_async(s); if (rc) return rc; }
     const size_t K = (size_t)c->Kt, nloc = (size_t)(s->to - s->from);      // (aggrMu / aggrLambda have the caller's size)
     if (!s->d_aggr_mu || !s->d_aggr_lambda) {
-        if (s->d_aggr_mu) { (void)hipFree(s->d_aggr_mu); s->d_aggr_mu = nullptr; }
-        if (hipMalloc((void **)&s->d_aggr_mu, std::max<size_t>(K * nloc, 1) * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&s->d_aggr_lambda, std::max<size_t>(K * K * nloc, 1) * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (s->d_aggr_mu) { (void)hipFree(s->d_aggr_mu); s->d_aggr_mu = nullptr; }
-            s->d_aggr_lambda = nullptr;
+        if (s->d_aggr_mu.alloc(K * nloc) || s->d_aggr_lambda.alloc(K * K * nloc)) {
+            s->d_aggr_mu.reset(); s->d_aggr_lambda.reset();
             return fail(BPMF_HIP_ENOMEM, "aggr_add: K*K doubles per column do not fit in device memory");
         }
-        HIP_TRY(hipMemsetAsync(s->d_aggr_mu, 0, K * nloc * sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(s->d_aggr_lambda, 0, K * K * nloc * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(s->d_aggr_mu.get(), 0, K * nloc * sizeof(double), c->stream.get()));
+        HIP_TRY(hipMemsetAsync(s->d_aggr_lambda.get(), 0, K * K * nloc * sizeof(double), c->stream.get()));
     }
-    bpmf_launch::aggr_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, s->from, (int64_t)nloc, s->d_aggr_mu, s->d_aggr_lambda, c->stream);
+    bpmf_launch::aggr_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, s->from, (int64_t)nloc, s->d_aggr_mu.get(), s->d_aggr_lambda.get(), c->stream.get());
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
     return BPMF_HIP_OK;
@@ -388,12 +384,11 @@ extern "C" int bpmf_hip_side_aggr_finalize(bpmf_hip_side *s, int nsamples, doubl
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const size_t K = (size_t)c->Kt, nloc = (size_t)(s->to - s->from);
-    bpmf_launch::aggr_finalize(c->Kt, nsamples, (int64_t)nloc, s->d_aggr_mu, s->d_aggr_lambda, c->stream);
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
-    HIP_TRY(hipMemcpy(mu_host, s->d_aggr_mu, K * nloc * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(lambda_host, s->d_aggr_lambda, K * K * nloc * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(s->d_aggr_mu); (void)hipFree(s->d_aggr_lambda);
-    s->d_aggr_mu = s->d_aggr_lambda = nullptr;
+    bpmf_launch::aggr_finalize(c->Kt, nsamples, (int64_t)nloc, s->d_aggr_mu.get(), s->d_aggr_lambda.get(), c->stream.get());
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
+    HIP_TRY(hipMemcpy(mu_host, s->d_aggr_mu.get(), K * nloc * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lambda_host, s->d_aggr_lambda.get(), K * K * nloc * sizeof(double), hipMemcpyDeviceToHost));
+    s->d_aggr_mu.reset(); s->d_aggr_lambda.reset();
     return BPMF_HIP_OK;
 }
 
@@ -403,9 +398,9 @@ extern "C" int bpmf_hip_side_last_kernel_ms(bpmf_hip_side *s, float *sample_ms, 
     { const int rc = settle_async(s); if (rc) return rc; }      // stateful path: the worker has stored the times
     if (!s->timing_valid) {          // stateless path: the events of the last launch on this context
         bpmf_hip_ctx *c = s->ctx;
-        { const int re_ = bounded_event_sync(c, c->ev[2], "last_kernel_ms"); if (re_) return re_; }
-        if (hipEventElapsedTime(&s->last_sample_ms, c->ev[0], c->ev[1]) != hipSuccess ||
-            hipEventElapsedTime(&s->last_reduce_ms, c->ev[1], c->ev[2]) != hipSuccess) {
+        { const int re_ = bounded_event_sync(c, c->ev[2].get(), "last_kernel_ms"); if (re_) return re_; }
+        if (hipEventElapsedTime(&s->last_sample_ms, c->ev[0].get(), c->ev[1].get()) != hipSuccess ||
+            hipEventElapsedTime(&s->last_reduce_ms, c->ev[1].get(), c->ev[2].get()) != hipSuccess) {
             (void)hipGetLastError();                                  // nothing was launched (or timed) yet
             s->last_sample_ms = s->last_reduce_ms = 0.f;
         }
@@ -440,25 +435,19 @@ int ensure_state(bpmf_hip_side *s)
     bpmf_hip_ctx *c = s->ctx;
     const size_t K = (size_t)c->Kt;                                  // (the Sys state -- cov, hp -- has the caller's size)
     if (s->cov.size() == K * K) return 0;
-    HIP_TRY(hipHostMalloc((void **)&s->a_h_in, c->in_words * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostMalloc((void **)&s->a_h_out, c->out_words * sizeof(double), hipHostMallocMapped));
-    HIP_TRY(hipHostMalloc((void **)&s->a_gate, 64, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->a_h_in_dev, s->a_h_in, 0));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->a_h_out_dev, s->a_h_out, 0));
-    HIP_TRY(hipHostGetDevicePointer((void **)&s->a_gate_dev, s->a_gate, 0));
-    memset(s->a_h_out, 0, c->out_words * sizeof(double));
-    memset(s->a_gate, 0, 64);
-    HIP_TRY(hipMalloc((void **)&s->a_d_in, (c->in_words + lf32_words(c)) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&s->a_ticket, 256));                 // [0], [1] statistics tickets (+ spare words)
-    HIP_TRY(hipMemset(s->a_ticket, 0, 256));
-    HIP_TRY(hipMalloc((void **)&s->a_dflag, 64));
-    HIP_TRY(hipMemset(s->a_dflag, 0, 64));
-    HIP_TRY(hipMalloc((void **)&s->a_d_red, (size_t)blob::red_words(c->K) * sizeof(double)));
-    static const unsigned evflags = hipEventDisableSystemFence;
-    for (auto &set : s->evs) for (hipEvent_t &e : set) HIP_TRY(hipEventCreateWithFlags(&e, evflags));
+    // (every owner releases what it held before it allocates: a call that fails half way leaks nothing, and the next one starts over)
+    int rc;
+    if ((rc = s->a_h_in.alloc(c->in_words)) || (rc = s->a_h_out.alloc(c->out_words)) || (rc = s->a_gate.alloc(16))) return rc;
+    memset(s->a_h_out.host(), 0, c->out_words * sizeof(double));
+    memset(s->a_gate.host(), 0, 64);
+    if ((rc = s->a_d_in.alloc(c->in_words + lf32_words(c))) ||
+        (rc = s->a_ticket.alloc(64)) || (rc = s->a_ticket.zero()) ||     // [0], [1] statistics tickets (+ spare words)
+        (rc = s->a_dflag.alloc(16)) || (rc = s->a_dflag.zero()) ||
+        (rc = s->a_d_red.alloc((size_t)blob::red_words(c->K)))) return rc;
+    for (auto &set : s->evs) for (Event &e : set) if ((rc = e.create(hipEventDisableSystemFence))) return rc;
     int lo = 0, hi = 0;                                              // numerically lowest = most urgent
     HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIP_TRY(hipStreamCreateWithPriority(&s->saux, hipStreamNonBlocking, hi));
+    if ((rc = s->saux.create(hipStreamNonBlocking, hi))) return rc;
     { std::lock_guard<std::mutex> lk(c->launch_mutex); c->sides.push_back(s); }
     s->hp_mu.assign(K, 0.0); s->hp_LambdaU.assign(K * K, 0.0); s->hp_LambdaF.assign(K * K, 0.0);
     s->nx_mu.assign(K, 0.0); s->nx_LambdaU.assign(K * K, 0.0); s->nx_LambdaF.assign(K * K, 0.0);
@@ -539,14 +528,14 @@ int draw_and_release(bpmf_hip_side *s, int iter, double *mu, double *LU, double 
     int rc = 0;
     if (s->rd_iter != iter) rc = predraw_get(s, iter);
     if (!rc) rc = bpmf_hyper_finish(K, s->ncols, s->cov.data(), nullptr, s->rd_au.data(), s->rd_z.data(), mu, LU, LF);
-    if (!rc) fill_blob_ctx(c, mu, LF, s->a_h_in, c->K == 64 && c->dtype == BPMF_HIP_F64 && s->lr_n > 0, LU);   // (R0, R0^-1: only the low-rank forms read them)
+    if (!rc) fill_blob_ctx(c, mu, LF, s->a_h_in.host(), c->K == 64 && c->dtype == BPMF_HIP_F64 && s->lr_n > 0, LU);   // (R0, R0^-1: only the low-rank forms read them)
     // the gate is opened even after an error: a sampler may already be queued behind it and must
     // not be left spinning (its results are never looked at: the error is reported first)
     {   // test hook: a host worker that is descheduled for a while (SIGSTOP, debugger, oversubscription)
         static const int stall_ms = env_int("BPMF_HIP_TEST_STALL_WORKER_MS", 0);
         if (stall_ms > 0 && iter > 0) std::this_thread::sleep_for(std::chrono::milliseconds(stall_ms));
     }
-    __atomic_store_n(s->a_gate, (unsigned)(iter + 1), __ATOMIC_RELEASE);
+    __atomic_store_n(s->a_gate.host(), (unsigned)(iter + 1), __ATOMIC_RELEASE);
     s->gate_iter = iter;
     return rc;
 }
@@ -557,7 +546,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
     bpmf_hip_ctx *c = s->ctx;
     const int K = c->K;
     trace("collect: start", s, job.iter);
-    unsigned *flag = blob::res_flag_word(s->a_h_out, K);
+    unsigned *flag = blob::res_flag_word(s->a_h_out.host(), K);
     // while the device is still sampling: the random part of the next draw (gamma / normal stream
     // of WishartUnitChol and MvNormalChol_prec), which needs no result of this half-iteration
     if (s->nx_iter == job.iter) {                                     // the parameters this half-iteration ran with
@@ -568,7 +557,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
     const bool seen = spin_for_seq(flag, job.seq);
     trace("collect: sums landed", s, job.iter);
     (void)hipSetDevice(c->device);
-    hipEvent_t *ev = s->evs[job.evset];
+    const hipEvent_t ev[4] = {s->evs[job.evset][0].get(), s->evs[job.evset][1].get(), s->evs[job.evset][2].get(), s->evs[job.evset][3].get()};
     int rc = 0;
     std::string msg;
     if (!seen) {                                                      // long kernel or an error: blocking wait
@@ -589,7 +578,7 @@ void collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
             rc = BPMF_HIP_ENODEV;
         }
     }
-    if (!rc) rc = read_result_blob(s, s->a_h_out, nullptr, nullptr, &s->norm, &msg);
+    if (!rc) rc = read_result_blob(s, s->a_h_out.host(), nullptr, nullptr, &s->norm, &msg);
     if (!rc) {
         { std::lock_guard<std::mutex> lk(s->wm); s->norm_hist[job.iter & 7] = s->norm; s->collected_iter = job.iter; }
         s->wcv.notify_all();
@@ -643,7 +632,7 @@ void post_collect(bpmf_hip_side *s, const bpmf_hip_side::Job &job)
 // the statistics pass of a stateful side, sequence number `seq`: the side's own parameter / result blobs and tickets
 static bpmf_launch::StatPass own_stat_pass(const bpmf_hip_side *P, unsigned seq)
 {
-    return bpmf_launch::stat_pass(P, P->a_d_in, P->a_h_out_dev, P->a_ticket, seq);
+    return bpmf_launch::stat_pass(P, P->a_d_in.get(), P->a_h_out.dev(), P->a_ticket.get(), seq);
 }
 
 // fused stateful path: the statistics of the newest half-iteration ride in the NEXT sampler launch;
@@ -658,8 +647,8 @@ int flush_pending_stats(bpmf_hip_ctx *c, bool on_main)
     c->pending_riders = false;
     const int K = c->K;
     HIP_TRY(hipSetDevice(c->device));
-    hipEvent_t *ev = P->evs[c->pending_evset];
-    hipStream_t sst = on_main ? c->stream : P->saux;
+    const hipEvent_t ev[4] = {P->evs[c->pending_evset][0].get(), P->evs[c->pending_evset][1].get(), P->evs[c->pending_evset][2].get(), P->evs[c->pending_evset][3].get()};
+    hipStream_t sst = on_main ? c->stream.get() : P->saux.get();
     if (!on_main) HIP_TRY(hipStreamWaitEvent(sst, ev[1], 0));        // (ev[1]: recorded with / behind P's sampler)
     else c->last_sampler_done = nullptr;                              // (the newest thing on S0 is no longer a sampler)
     const int rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(P, sst, own_stat_pass(P, c->pending_seq)));
@@ -731,10 +720,10 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     }
     self->iter = iter;
 
-    hipStream_t s0 = c->stream, s1 = (c->comm && !c->comm2) ? c->stream : self->saux;   // one stream when there is one communicator only
+    hipStream_t s0 = c->stream.get(), s1 = (c->comm && !c->comm2) ? c->stream.get() : self->saux.get();   // one stream when there is one communicator only
     const unsigned seq = ++self->a_seq;
     const int evset = (int)(seq & 1u);
-    hipEvent_t *ev = self->evs[evset];
+    const hipEvent_t ev[4] = {self->evs[evset][0].get(), self->evs[evset][1].get(), self->evs[evset][2].get(), self->evs[evset][3].get()};
     // Fused form (single GPU, K <= 32 in fp64, one item per workgroup): ONE launch on S0 per
     // half-iteration carries the gate + staging of its own parameters (workgroup 0) and the column
     // statistics of the previous launch's side (the next workgroups) -- see FusedArgs in kernels.h.
@@ -779,17 +768,17 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
         self->probit_latent_queued = true;
     }
     if (fused) {
-        fz.gate_host = self->a_gate_dev; fz.gate_want = (unsigned)(iter + 1); fz.src_host = self->a_h_in_dev;
-        fz.dst = self->a_d_in; fz.n = (int)stage_words; fz.dflag = self->a_dflag; fz.dval = seq;
+        fz.gate_host = self->a_gate.dev(); fz.gate_want = (unsigned)(iter + 1); fz.src_host = self->a_h_in.dev();
+        fz.dst = self->a_d_in.get(); fz.n = (int)stage_words; fz.dflag = self->a_dflag.get(); fz.dval = seq;
         if (carry && !ride_f32) {
             fz.nstat = sp.nwaves; fz.st_items = static_cast<const double *>(sp.items); fz.st_c0 = sp.c0; fz.st_c1 = sp.c1;
             fz.st_partials = sp.partials; fz.st_fail = sp.fail_in; fz.st_out = sp.out; fz.st_ticket = sp.ticket;
             fz.st_flag = sp.flag; fz.st_seq = sp.seq; fz.st_tmo = sp.tmo;
         }
     } else {
-        bpmf_launch::gate_stage(c->in_words > 8192 ? 16 : 1, self->a_gate_dev, (unsigned)(iter + 1), self->a_h_in_dev, self->a_d_in, (int)c->in_words,
-                                blob::tmo_word(self->a_h_out_dev, K), wait_ticks(), s1);
-        if (lf32_words(c)) bpmf_launch::lf32_tiles(self->a_d_in, reinterpret_cast<float *>(self->a_d_in + c->in_words), K, s1);
+        bpmf_launch::gate_stage(c->in_words > 8192 ? 16 : 1, self->a_gate.dev(), (unsigned)(iter + 1), self->a_h_in.dev(), self->a_d_in.get(), (int)c->in_words,
+                                blob::tmo_word(self->a_h_out.dev(), K), wait_ticks(), s1);
+        if (lf32_words(c)) bpmf_launch::lf32_tiles(self->a_d_in.get(), reinterpret_cast<float *>(self->a_d_in.get() + c->in_words), K, s1);
         if (s1 != s0) {
             HIP_TRY(hipEventRecord(ev[3], s1));
             HIP_TRY(hipStreamWaitEvent(s0, ev[3], 0));
@@ -810,8 +799,8 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     if (timed && !ride) HIP_TRY(hipEventRecord(ev[0], s0));
     self->cur_fused = fz;
     self->cur_riders = riders;
-    self->cur_gate_flag = fused ? self->a_dflag : nullptr; self->cur_gate_want = seq;
-    rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, self->a_d_in, s0, (ride && timed) ? ev[0] : nullptr,
+    self->cur_gate_flag = fused ? self->a_dflag.get() : nullptr; self->cur_gate_want = seq;
+    rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, self->a_d_in.get(), s0, (ride && timed) ? ev[0] : nullptr,
                                                     ride ? ev[1] : nullptr));
     self->cur_gate_flag = nullptr;
     self->probit_latent_queued = false;
@@ -859,9 +848,9 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
         // (fp32 path: 1 152 single-wave tile workgroups, same reasoning: 0.84 -> 0.81 ms.  NOT the fp64 form of K = 128 -- round 4,
         //  interleaved: 1.383 / 1.392 ms without the head start against 1.404 / 1.408 with it: its 22-us pass finds room anyway)
         if (head_start && sst != s0 && !dist && (self->nstat_wg > 0 || (K == 128 && c->dtype == BPMF_HIP_F32))) {
-            if (!self->ev_stat_go) HIP_TRY(hipEventCreateWithFlags(&self->ev_stat_go, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(self->ev_stat_go, sst));
-            HIP_TRY(hipStreamWaitEvent(s0, self->ev_stat_go, 0));
+            if (!self->ev_stat_go) { const int re = self->ev_stat_go.create(hipEventDisableTiming); if (re) return re; }
+            HIP_TRY(hipEventRecord(self->ev_stat_go.get(), sst));
+            HIP_TRY(hipStreamWaitEvent(s0, self->ev_stat_go.get(), 0));
         }
         rc = BPMF_DISPATCH_K(K, bpmf_launch::stats<KK, FF>(self, sst, own_stat_pass(self, seq)));
         if (rc) return rc;

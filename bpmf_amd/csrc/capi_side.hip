@@ -43,9 +43,9 @@ static int build_gather_stream(bpmf_hip_side *s, const std::vector<int64_t> &wp0
         g += ng[i];
     }
     int rc;
-    if ((rc = dev_upload(&s->d_gs_rec, rec.data(), rec.size()))) return rc;
-    if ((rc = dev_upload(&s->d_gs_g0, g0.data(), nw))) return rc;
-    if ((rc = dev_upload(&s->d_gs_ng, ng.data(), nw))) return rc;
+    if ((rc = s->d_gs_rec.upload(rec.data(), rec.size()))) return rc;
+    if ((rc = s->d_gs_g0.upload(g0.data(), nw))) return rc;
+    if ((rc = s->d_gs_ng.upload(ng.data(), nw))) return rc;
     s->gs_groups = groups;
     return 0;
 }
@@ -205,36 +205,36 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
             if (!(it.mc < 0 && it.len <= nlr)) { hc.push_back(it.col); hl.push_back(it.len); hm.push_back(it.mc); hk.push_back(it.chunk); hp.push_back(it.p0); }
         if (nlr > 0 && (int64_t)lc.size() * 2 >= nloc && !lc.empty()) {
             s->lr_n = (int)lc.size(); s->hv_nwork = (int)hc.size();
-            if (s->pf_class[3] > 0 && (rc = dev_upload<double>(&s->d_pf_q, nullptr, (size_t)s->nrows * K))) return rc;
-            if ((rc = dev_upload(&s->d_lr_col, lc.data(), lc.size())) || (rc = dev_upload(&s->d_lr_len, ll.data(), ll.size())) ||
-                (rc = dev_upload(&s->d_lr_p0, lp.data(), lp.size())) || (rc = dev_upload(&s->d_hv_col, hc.data(), hc.size())) ||
-                (rc = dev_upload(&s->d_hv_len, hl.data(), hl.size())) || (rc = dev_upload(&s->d_hv_mc, hm.data(), hm.size())) ||
-                (rc = dev_upload(&s->d_hv_chunk, hk.data(), hk.size())) || (rc = dev_upload(&s->d_hv_p0, hp.data(), hp.size())))
+            if (s->pf_class[3] > 0 && (rc = s->d_pf_q.alloc((size_t)s->nrows * K))) return rc;
+            if ((rc = s->d_lr_col.upload(lc.data(), lc.size())) || (rc = s->d_lr_len.upload(ll.data(), ll.size())) ||
+                (rc = s->d_lr_p0.upload(lp.data(), lp.size())) || (rc = s->d_hv_col.upload(hc.data(), hc.size())) ||
+                (rc = s->d_hv_len.upload(hl.data(), hl.size())) || (rc = s->d_hv_mc.upload(hm.data(), hm.size())) ||
+                (rc = s->d_hv_chunk.upload(hk.data(), hk.size())) || (rc = s->d_hv_p0.upload(hp.data(), hp.size())))
                 return rc;
         }
     }
-    if ((rc = dev_upload(&s->d_wi_col, wcol.data(), nw))) return rc;
-    if ((rc = dev_upload(&s->d_wi_len, wlen.data(), nw))) return rc;
-    if ((rc = dev_upload(&s->d_wi_mc, wmc.data(), nw))) return rc;
-    if ((rc = dev_upload(&s->d_wi_chunk, wchunk.data(), nw))) return rc;
-    if ((rc = dev_upload(&s->d_wi_p0, wp0.data(), nw))) return rc;
+    if ((rc = s->d_wi_col.upload(wcol.data(), nw))) return rc;
+    if ((rc = s->d_wi_len.upload(wlen.data(), nw))) return rc;
+    if ((rc = s->d_wi_mc.upload(wmc.data(), nw))) return rc;
+    if ((rc = s->d_wi_chunk.upload(wchunk.data(), nw))) return rc;
+    if ((rc = s->d_wi_p0.upload(wp0.data(), nw))) return rc;
     if ((rc = build_gather_stream(s, wp0, wlen))) return rc;
-    if ((rc = dev_upload(&s->d_mc_slot0, mc_slot0.data(), mc_slot0.size()))) return rc;
-    if ((rc = dev_upload(&s->d_mc_nch, mc_nch.data(), mc_nch.size()))) return rc;
+    if ((rc = s->d_mc_slot0.upload(mc_slot0.data(), mc_slot0.size()))) return rc;
+    if ((rc = s->d_mc_nch.upload(mc_nch.data(), mc_nch.size()))) return rc;
     {
         std::vector<unsigned> zeros(std::max<size_t>(mc_slot0.size(), 8 * 32), 0u);
-        if ((rc = dev_upload(&s->d_mc_count, zeros.data(), std::max<size_t>(mc_slot0.size(), 1)))) return rc;
+        if ((rc = s->d_mc_count.upload(zeros.data(), std::max<size_t>(mc_slot0.size(), 1)))) return rc;
     }
     if (big) {
         // column statistics: <= 32 slices of columns x 36 tiles (k_colstats_f32), one partial (tiles | sum) per slice
         // (128 partials of 132 KB were 17 MB written and read back per half-iteration: the two kernels took 55 us alone)
         s->nstat_waves = (int)std::max<int64_t>(1, std::min<int64_t>((nloc + 63) / 64, 32));
-        if ((rc = dev_upload<double>(&s->d_stat_partials, nullptr, (size_t)s->nstat_waves * blob::stat_partial_words(K)))) return rc;
-        if ((rc = dev_upload<double>(&s->d_partials, nullptr, (size_t)slots * part_words_rt(K, f32)))) return rc;     // chunks of heavy columns
+        if ((rc = s->d_stat_partials.alloc((size_t)s->nstat_waves * blob::stat_partial_words(K)))) return rc;
+        if ((rc = s->d_partials.alloc((size_t)slots * part_words_rt(K, f32)))) return rc;     // chunks of heavy columns
         return 0;
     }
     const size_t pw = part_words_rt(K, false);
-    if ((rc = dev_upload<double>(&s->d_partials, nullptr, (size_t)slots * pw))) return rc;
+    if ((rc = s->d_partials.alloc((size_t)slots * pw))) return rc;
     // column statistics: one wave per 64+ columns, at most 2 waves per CU
     // (sides with hundreds of thousands of columns: the pass is a 8 K-byte-per-column stream, four times the waves)
     s->nstat_waves = (int)std::max<int64_t>(1, std::min<int64_t>((nloc + 31) / 32, (int64_t)s->ctx->num_cu * (nloc > 100000 ? 8 : 2)));
@@ -244,19 +244,18 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr)
     if (nloc < 20000) s->nstat_waves = (int)std::max<int64_t>(1, std::min<int64_t>(s->nstat_waves, std::max<int64_t>((nloc + 159) / 160, 24)));
     // big sides: four-wave workgroups with a finisher that reads the partials contiguously (k_colstats_wg)
     s->nstat_wg = (nloc > 100000) ? (int)std::min<int64_t>((nloc + 127) / 128, (int64_t)s->ctx->num_cu * 2) : 0;
-    if ((rc = dev_upload<double>(&s->d_stat_partials, nullptr, (size_t)std::max(s->nstat_waves, 2 * s->nstat_wg) * pw))) return rc;
+    if ((rc = s->d_stat_partials.alloc((size_t)std::max(s->nstat_waves, 2 * s->nstat_wg) * pw))) return rc;
     return 0;
 }
 
 // the device arrays build_schedule made (the schedule is rebuilt when the parts of the side change)
 void free_schedule(bpmf_hip_side *s)
 {
-    void **ptrs[] = {(void **)&s->d_wi_col, (void **)&s->d_wi_len, (void **)&s->d_wi_mc, (void **)&s->d_wi_chunk, (void **)&s->d_wi_p0,
-                     (void **)&s->d_mc_slot0, (void **)&s->d_mc_nch, (void **)&s->d_mc_count, (void **)&s->d_partials, (void **)&s->d_stat_partials,
-                     (void **)&s->d_lr_col, (void **)&s->d_lr_len, (void **)&s->d_lr_p0, (void **)&s->d_hv_col, (void **)&s->d_hv_len,
-                     (void **)&s->d_hv_mc, (void **)&s->d_hv_chunk, (void **)&s->d_hv_p0, (void **)&s->d_pf_q,
-                     (void **)&s->d_gs_rec, (void **)&s->d_gs_g0, (void **)&s->d_gs_ng};
-    for (void **p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->d_wi_col.reset(); s->d_wi_len.reset(); s->d_wi_mc.reset(); s->d_wi_chunk.reset(); s->d_wi_p0.reset();
+    s->d_mc_slot0.reset(); s->d_mc_nch.reset(); s->d_mc_count.reset(); s->d_partials.reset(); s->d_stat_partials.reset();
+    s->d_lr_col.reset(); s->d_lr_len.reset(); s->d_lr_p0.reset(); s->d_hv_col.reset(); s->d_hv_len.reset();
+    s->d_hv_mc.reset(); s->d_hv_chunk.reset(); s->d_hv_p0.reset(); s->d_pf_q.reset();
+    s->d_gs_rec.reset(); s->d_gs_g0.reset(); s->d_gs_ng.reset();
     s->lr_n = s->hv_nwork = 0; s->gs_groups = 0;
 }
 
@@ -280,30 +279,32 @@ static int side_create_common(bpmf_hip_ctx *ctx, int64_t ncols, int64_t nrows, i
         for (int64_t p = 0; p < nnz; ++p)
             if (rowidx[p] < 0 || rowidx[p] >= nrows) return fail(BPMF_HIP_EINVAL, "side_create: row index out of range");
     }
-    bpmf_hip_side *s = new (std::nothrow) bpmf_hip_side();
+    std::unique_ptr<bpmf_hip_side> own(new (std::nothrow) bpmf_hip_side());      // (nothing below starts a worker or registers the side: a failure just releases it)
+    bpmf_hip_side *s = own.get();
     if (!s) return fail(BPMF_HIP_ENOMEM, "side_create: out of host memory");
     s->ctx = ctx; s->ncols = ncols; s->nrows = nrows; s->from = from; s->to = to; s->nnz = nnz; s->mean_rating = mean_rating;
     int rc = 0;
     if (dev_arrays) {
-        s->d_rowidx = const_cast<int32_t *>(rowidx); s->d_vals = const_cast<double *>(vals); s->own_csc = false;
+        s->d_rowidx = const_cast<int32_t *>(rowidx); s->d_vals = const_cast<double *>(vals);
     } else {
-        if ((rc = dev_upload(&s->d_rowidx, rowidx, (size_t)nnz)) || (rc = dev_upload(&s->d_vals, vals, (size_t)nnz))) { bpmf_hip_side_destroy(s); return rc; }
+        if ((rc = s->own_rowidx.upload(rowidx, (size_t)nnz)) || (rc = s->own_vals.upload(vals, (size_t)nnz))) return rc;
+        s->d_rowidx = s->own_rowidx.get(); s->d_vals = s->own_vals.get();
     }
     const size_t words = (size_t)ctx->K * (size_t)ncols;
     const size_t esz = ctx->dtype == BPMF_HIP_F32 ? sizeof(float) : sizeof(double);
-    hipError_t e = hipMalloc((void **)&s->d_items, words * esz);
-    if (e != hipSuccess) { bpmf_hip_side_destroy(s); return fail(BPMF_HIP_ENOMEM, "side_create: factor matrix allocation failed"); }
-    e = hipMemset(s->d_items, 0, words * esz);                      // items().setZero(), c++/sample.cpp:185
-    if (e != hipSuccess) { bpmf_hip_side_destroy(s); return fail(BPMF_HIP_ENODEV, "side_create: memset failed"); }
-    if (env_int("BPMF_HIP_DBUF", 1) != 0 && hipMalloc((void **)&s->d_items_alt, words * esz) == hipSuccess) {
-        if (hipMemset(s->d_items_alt, 0, words * esz) != hipSuccess) { (void)hipFree(s->d_items_alt); s->d_items_alt = nullptr; }
-    } else {
-        (void)hipGetLastError();                                    // no second copy: samplers write in place
-        s->d_items_alt = nullptr;
+    const size_t dwords = (words * esz + sizeof(double) - 1) / sizeof(double);      // (fp32 factors behind the double pointers)
+    if (s->items_buf[0].alloc(dwords)) return fail(BPMF_HIP_ENOMEM, "side_create: factor matrix allocation failed");
+    s->d_items = s->items_buf[0].get();
+    if (hipMemset(s->d_items, 0, words * esz) != hipSuccess)       // items().setZero(), c++/sample.cpp:185
+        return fail(BPMF_HIP_ENODEV, "side_create: memset failed");
+    if (env_int("BPMF_HIP_DBUF", 1) != 0 && (s->items_buf[1].alloc(dwords) || hipMemset(s->items_buf[1].get(), 0, words * esz) != hipSuccess)) {
+        (void)hipGetLastError();                                    // no second copy: the samplers write in place
+        s->items_buf[1].reset();
     }
+    s->d_items_alt = s->items_buf[1].get();
     s->h_colptr.assign(colptr, colptr + nloc + 1);
-    if ((rc = build_schedule(s, colptr))) { bpmf_hip_side_destroy(s); return rc; }
-    *out = s;
+    if ((rc = build_schedule(s, colptr))) return rc;
+    *out = own.release();
     return BPMF_HIP_OK;
 }
 
@@ -344,37 +345,14 @@ extern "C" int bpmf_hip_side_destroy(bpmf_hip_side *s)
             }
     }
     flush_deferred(s->deferred_eval);                               // (it would go to this side's stream)
-    (void)bounded_stream_sync(s->ctx, s->ctx->stream, __func__);
+    (void)bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__);
     if (s->saux) {
-        (void)bounded_stream_sync(s->ctx, s->saux, __func__); (void)hipStreamDestroy(s->saux);
+        (void)bounded_stream_sync(s->ctx, s->saux.get(), __func__);
         std::lock_guard<std::mutex> lk(s->ctx->launch_mutex);
         auto &v = s->ctx->sides;
         v.erase(std::remove(v.begin(), v.end(), s), v.end());
     }
-    if (s->sx) { (void)bounded_stream_sync(s->ctx, s->sx, __func__); (void)hipStreamDestroy(s->sx); }
-    for (hipEvent_t e : s->sub_ev) if (e) (void)hipEventDestroy(e);
-    if (s->sx_done) (void)hipEventDestroy(s->sx_done);
-    if (s->ev_stat_go) (void)hipEventDestroy(s->ev_stat_go);
-    if (s->own_csc) { if (s->d_rowidx) (void)hipFree(s->d_rowidx); if (s->d_vals) (void)hipFree(s->d_vals); }
-    if (s->own_items && s->d_items) (void)hipFree(s->d_items);
-    if (s->d_items_alt) (void)hipFree(s->d_items_alt);
-    if (s->d_prop) (void)hipFree(s->d_prop);
-    s->probit.reset(); s->ordinal.reset(); s->censor.reset(); s->weights.reset(); s->implicit.reset(); s->robust.reset(); s->link.reset(); s->ring.reset(); s->newrows.reset(); s->foldin.reset(); s->sse.reset(); s->d_colptr.reset();
-    if (s->d_aggr_mu) (void)hipFree(s->d_aggr_mu);
-    if (s->d_aggr_lambda) (void)hipFree(s->d_aggr_lambda);
-    void *ptrs[] = {s->d_wi_col, s->d_wi_len, s->d_wi_mc, s->d_wi_chunk, s->d_wi_p0, s->d_mc_slot0, s->d_mc_nch, s->d_mc_count, s->d_partials,
-                    s->d_stat_partials, s->a_d_in,
-                    s->d_lr_col, s->d_lr_len, s->d_lr_p0, s->d_hv_col, s->d_hv_len, s->d_hv_mc, s->d_hv_chunk, s->d_hv_p0,
-                    s->d_conn_send, s->d_conn_recv, s->d_conn_sbuf, s->d_conn_rbuf, s->d_pf_q,
-                    s->d_prec, s->d_t_colptr, s->d_t_rowidx, s->d_t_vals, s->d_t_order, s->d_gs_rec, s->d_gs_g0, s->d_gs_ng};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (s->a_h_in) (void)hipHostFree(s->a_h_in);
-    if (s->a_h_out) (void)hipHostFree(s->a_h_out);
-    for (auto &set : s->evs) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
-    if (s->a_gate) (void)hipHostFree(s->a_gate);
-    if (s->a_ticket) (void)hipFree(s->a_ticket);
-    if (s->a_dflag) (void)hipFree(s->a_dflag);
-    if (s->a_d_red) (void)hipFree(s->a_d_red);
+    if (s->sx) (void)bounded_stream_sync(s->ctx, s->sx.get(), __func__);
     delete s;
     return BPMF_HIP_OK;
 }
@@ -388,6 +366,7 @@ int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_si
 int ensure_colptr(bpmf_hip_side *s) { return s->d_colptr ? 0 : s->d_colptr.upload(s->h_colptr.data(), s->h_colptr.size()); }
 
 extern "C" int64_t bpmf_hip_live_device_bytes(void) { return g_live_bytes.load(std::memory_order_relaxed); }
+extern "C" int64_t bpmf_hip_live_core_bytes(void) { return g_core_bytes.load(std::memory_order_relaxed); }
 extern "C" int64_t bpmf_hip_stream_drains(void) { return g_stream_drains.load(std::memory_order_relaxed); }
 
 // ---- padded num_latent (ctx->Kt < ctx->K) -----------------------------------------------------
@@ -416,15 +395,15 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
     if (Lambda && s->ordinal) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on an ordinal side (bpmf_hip_side_set_ordinal)");
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }
-    if (s->d_prop) { (void)hipFree(s->d_prop); s->d_prop = nullptr; }
+    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }
+    s->d_prop.reset();
     if (!Lambda) return BPMF_HIP_OK;
     const int K = s->ctx->K, Kt = s->ctx->Kt;
     const size_t nloc = (size_t)(s->to - s->from), words = (size_t)K * K * nloc;
-    if (hipMalloc((void **)&s->d_prop, std::max<size_t>(words, 1) * sizeof(double)) != hipSuccess)
+    if (s->d_prop.alloc(words))
         return fail(BPMF_HIP_ENOMEM, "set_prop_posterior: device allocation failed");
     if (Kt == K) {
-        HIP_TRY(hipMemcpy(s->d_prop, Lambda, words * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_prop.get(), Lambda, words * sizeof(double), hipMemcpyHostToDevice));
         return BPMF_HIP_OK;
     }
     // padded num_latent: identity in the extra dimensions of every column's prior, a few thousand columns at a time
@@ -433,7 +412,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
     for (size_t c0 = 0; c0 < nloc; c0 += per) {
         const size_t n = std::min(per, nloc - c0);
         for (size_t c = 0; c < n; ++c) pad_square(Kt, K, Lambda + (c0 + c) * (size_t)Kt * Kt, buf.data() + c * (size_t)K * K, 1.0);
-        HIP_TRY(hipMemcpy(s->d_prop + c0 * (size_t)K * K, buf.data(), n * (size_t)K * K * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_prop.get() + c0 * (size_t)K * K, buf.data(), n * (size_t)K * K * sizeof(double), hipMemcpyHostToDevice));
     }
     return BPMF_HIP_OK;
 }
@@ -460,7 +439,7 @@ static int drop_second_copy(bpmf_hip_side *s)
     (void)settle_async(s);
     HIP_TRY(hipSetDevice(s->ctx->device));
     HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(s->d_items_alt);
+    s->items_buf[s->cur_buf ^ 1].reset();                          // (the owner behind d_items_alt: the views swap, the owners do not)
     s->d_items_alt = nullptr;
     return 0;
 }
@@ -486,11 +465,11 @@ extern "C" int bpmf_hip_side_bind_items(bpmf_hip_side *s, double *items_dev, int
                     std::to_string(sizeof(double) * (size_t)s->ctx->K * (size_t)s->ncols) + " needed");
     HIP_TRY(hipSetDevice(s->ctx->device));
     (void)settle_async(s);
-    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }
-    if (s->saux) { const int rs_ = bounded_stream_sync(s->ctx, s->saux, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }
+    if (s->saux) { const int rs_ = bounded_stream_sync(s->ctx, s->saux.get(), __func__); if (rs_) return rs_; }
     { const int rc = drop_second_copy(s); if (rc) return rc; }
-    if (s->own_items && s->d_items) (void)hipFree(s->d_items);
-    s->d_items = items_dev; s->own_items = false;
+    s->items_buf[s->cur_buf].reset();                              // (empty from here on: the factors are the caller's)
+    s->d_items = items_dev;
     return BPMF_HIP_OK;
 }
 
@@ -498,7 +477,7 @@ extern "C" int bpmf_hip_side_get_items(bpmf_hip_side *s, double *h)
 {
     if (!s || !h) return fail(BPMF_HIP_EINVAL, "get_items: NULL");
     HIP_TRY(hipSetDevice(s->ctx->device));
-    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }
     const size_t K = (size_t)s->ctx->K, Kt = (size_t)s->ctx->Kt, n = (size_t)s->ncols;     // (device leading dimension K, the caller's rows Kt)
     const size_t words = K * n;
     if (s->ctx->dtype == BPMF_HIP_F32) {                            // fp32 factors: widen on the host
@@ -578,7 +557,7 @@ extern "C" int bpmf_hip_side_kernel_resources(bpmf_hip_side *s, int64_t *out, in
     bpmf_launch::Probe pr;
     bpmf_launch::probe() = &pr;
     // (every kernel of sampler_into goes through BPMF_LAUNCH, which records instead of launching while the probe is installed)
-    const int rc = BPMF_DISPATCH_K(c->K, (bpmf_launch::sampler_into<KK, FF>(s, s->d_items, s, 0, 1.0, c->d_in, c->stream, nullptr, nullptr)));
+    const int rc = BPMF_DISPATCH_K(c->K, (bpmf_launch::sampler_into<KK, FF>(s, s->d_items, s, 0, 1.0, c->d_in.get(), c->stream.get(), nullptr, nullptr)));
     bpmf_launch::probe() = nullptr;
     if (rc) return rc;
     std::string all;
@@ -642,9 +621,9 @@ extern "C" int bpmf_hip_side_schedule_items(const bpmf_hip_side *s, int32_t *col
     const size_t m = (size_t)std::min<int64_t>(n, s->nwork);
     if (m == 0) return BPMF_HIP_OK;
     HIP_TRY(hipSetDevice(s->ctx->device));
-    if (col) HIP_TRY(hipMemcpy(col, s->d_wi_col, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (len) HIP_TRY(hipMemcpy(len, s->d_wi_len, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (heavy) HIP_TRY(hipMemcpy(heavy, s->d_wi_mc, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (col) HIP_TRY(hipMemcpy(col, s->d_wi_col.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (len) HIP_TRY(hipMemcpy(len, s->d_wi_len.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (heavy) HIP_TRY(hipMemcpy(heavy, s->d_wi_mc.get(), m * sizeof(int32_t), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
 

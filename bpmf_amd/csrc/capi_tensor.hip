@@ -18,7 +18,7 @@ static bpmf_hip_side *carrier(bpmf_hip_ctx *c, int64_t ncols, int64_t nrows, dou
     bpmf_hip_side *s = new (std::nothrow) bpmf_hip_side();
     if (!s) return nullptr;
     s->ctx = c; s->ncols = ncols; s->nrows = nrows; s->from = 0; s->to = ncols; s->mean_rating = mean;
-    s->d_items = items; s->own_items = false; s->own_csc = false;
+    s->d_items = items;                                             // (a view: the side's owners stay empty)
     return s;
 }
 
@@ -31,7 +31,7 @@ struct bpmf_hip_tensor {
     DevBuf<double> P;                                                  // ld x nnz, shared by the three modes
     bpmf_hip_side *pcar = nullptr;                                     // P as "the other side"
     int ntests = 0;                                                    // live test sets (they read the sides)
-    hipEvent_t kr_ev[2] = {nullptr, nullptr};                          // start / stop of the newest k_khatri_rao of a mode (bpmf_hip_tensor_last_ms)
+    Event kr_ev[2];                                                    // start / stop of the newest k_khatri_rao of a mode (bpmf_hip_tensor_last_ms)
     bool kr_timed = false;
 };
 
@@ -77,7 +77,7 @@ static int enqueue_khatri_rao(bpmf_hip_ctx *c, const double *A, const double *B,
 {
     bpmf_launch::KhatriRaoLaunch p{};
     p.A = A; p.B = B; p.ia = ia; p.ib = ib; p.n = n; p.ld = c->K; p.kt = c->Kt; p.P = P; p.ev_start = ev_start; p.ev_stop = ev_stop;
-    if (bpmf_launch::khatri_rao(p, c->stream)) return fail(BPMF_HIP_EINVAL, "tensor: unsupported K " + std::to_string(c->K));
+    if (bpmf_launch::khatri_rao(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "tensor: unsupported K " + std::to_string(c->K));
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)
     return 0;
@@ -89,7 +89,7 @@ static int build_product(bpmf_hip_tensor *t, int m)
     int a, b;
     others(m, &a, &b);
     t->kr_timed = t->nnz > 0;
-    return enqueue_khatri_rao(t->ctx, t->side[a]->d_items, t->side[b]->d_items, t->ia[m].get(), t->ib[m].get(), t->nnz, t->P.get(), t->kr_ev[0], t->kr_ev[1]);
+    return enqueue_khatri_rao(t->ctx, t->side[a]->d_items, t->side[b]->d_items, t->ia[m].get(), t->ib[m].get(), t->nnz, t->P.get(), t->kr_ev[0].get(), t->kr_ev[1].get());
 }
 
 extern "C" int bpmf_hip_tensor_destroy(bpmf_hip_tensor *t)
@@ -98,7 +98,6 @@ extern "C" int bpmf_hip_tensor_destroy(bpmf_hip_tensor *t)
     if (t->ntests > 0) return fail(BPMF_HIP_EINVAL, "tensor_destroy: destroy the tensor's test sets first (bpmf_hip_tensor_test_destroy)");
     if (t->ctx) (void)hipSetDevice(t->ctx->device);
     for (bpmf_hip_side *s : t->side) if (s) (void)bpmf_hip_side_destroy(s);      // (waits for S0: nothing reads P after this)
-    for (hipEvent_t e : t->kr_ev) if (e) (void)hipEventDestroy(e);
     delete t->pcar;
     delete t;
     return BPMF_HIP_OK;
@@ -165,10 +164,10 @@ extern "C" int bpmf_hip_tensor_create(bpmf_hip_ctx *ctx, int nmodes, const int64
         if ((rc = t->ia[m].upload(ha.data(), (size_t)nnz)) || (rc = t->ib[m].upload(hb.data(), (size_t)nnz))) break;
         rc = bpmf_hip_side_create(ctx, dims[m], (int64_t)n1, 0, dims[m], colptr[m].data(), rowidx.data(), v.data(), mean_rating, &t->side[m]);
     }
-    for (hipEvent_t &e : t->kr_ev)
-        if (!rc && hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; rc = fail(BPMF_HIP_ENODEV, "tensor_create: hipEventCreate failed"); }
+    for (Event &e : t->kr_ev)
+        if (!rc && e.create()) { (void)hipGetLastError(); rc = fail(BPMF_HIP_ENODEV, "tensor_create: hipEventCreate failed"); }
     if (!rc) rc = t->P.alloc((size_t)ctx->K * n1);
-    if (!rc) rc = t->P.zero_async(ctx->stream);
+    if (!rc) rc = t->P.zero_async(ctx->stream.get());
     if (!rc && !(t->pcar = carrier(ctx, (int64_t)n1, 0, mean_rating, t->P.get()))) rc = fail(BPMF_HIP_ENOMEM, "tensor_create: out of host memory");
     if (rc) {
         const std::string keep = bpmf_hip_last_error();              // (the destructor's calls may not replace the reason)
@@ -189,7 +188,7 @@ extern "C" bpmf_hip_side *bpmf_hip_tensor_side(bpmf_hip_tensor *t, int m)
 static int check_plain_mode(const char *who, const bpmf_hip_side *s)
 {
     const char *what = s->probit ? "a probit likelihood" : s->ordinal ? "an ordinal likelihood" : s->censor ? "censored ratings" : s->robust ? "Student-t noise" : s->weights ? "per-rating weights"
-                       : s->link ? "features" : s->d_prop ? "propagated priors" : s->reduce_on ? "the BPMF_REDUCE formulation" : nullptr;
+                       : s->link ? "features" : s->d_prop.get() ? "propagated priors" : s->reduce_on ? "the BPMF_REDUCE formulation" : nullptr;
     if (what) return fail(BPMF_HIP_EINVAL, std::string(who) + ": not together with " + what + " on a mode of a tensor");
     if (s->ctx->comm || sharded(s)) return fail(BPMF_HIP_EINVAL, std::string(who) + ": needs the tensor whole on one GPU, on a context without a communicator");
     return 0;
@@ -218,7 +217,7 @@ extern "C" int bpmf_hip_tensor_product(bpmf_hip_tensor *t, int m, double *out_ho
     HIP_TRY(hipSetDevice(c->device));
     int rc = build_product(t, m);
     if (rc) return rc;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if (t->nnz > 0 && out_host) HIP_TRY(hipMemcpy(out_host, t->P.get(), (size_t)c->K * (size_t)t->nnz * sizeof(double), hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
@@ -229,8 +228,8 @@ extern "C" int bpmf_hip_tensor_last_ms(bpmf_hip_tensor *t, float *khatri_rao_ms)
     *khatri_rao_ms = 0.f;
     if (!t->kr_timed) return BPMF_HIP_OK;                            // (nothing launched yet, or a tensor without entries)
     HIP_TRY(hipSetDevice(t->ctx->device));
-    { const int re_ = bounded_event_sync(t->ctx, t->kr_ev[1], "tensor_last_ms"); if (re_) return re_; }
-    HIP_TRY(hipEventElapsedTime(khatri_rao_ms, t->kr_ev[0], t->kr_ev[1]));
+    { const int re_ = bounded_event_sync(t->ctx, t->kr_ev[1].get(), "tensor_last_ms"); if (re_) return re_; }
+    HIP_TRY(hipEventElapsedTime(khatri_rao_ms, t->kr_ev[0].get(), t->kr_ev[1].get()));
     return BPMF_HIP_OK;
 }
 
@@ -273,7 +272,7 @@ extern "C" int bpmf_hip_tensor_test_create(bpmf_hip_tensor *t, int64_t nnz, cons
         rowidx[(size_t)p] = (int32_t)p; ha[(size_t)p] = idx0[e]; hb[(size_t)p] = idx1[e]; v[(size_t)p] = vals[e];
     }
     if (!(rc = tt->qa.upload(ha.data(), (size_t)nnz)) && !(rc = tt->qb.upload(hb.data(), (size_t)nnz)) && !(rc = tt->Q.alloc((size_t)c->K * n1)) &&
-        !(rc = tt->Q.zero_async(c->stream))) {
+        !(rc = tt->Q.zero_async(c->stream.get()))) {
         tt->tside = carrier(c, t->dims[2], (int64_t)n1, t->mean_rating, t->side[2]->d_items);
         tt->qcar = carrier(c, (int64_t)n1, 0, t->mean_rating, tt->Q.get());
         if (!tt->tside || !tt->qcar) rc = fail(BPMF_HIP_ENOMEM, "tensor_test_create: out of host memory");

@@ -14,7 +14,7 @@ extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     if (s->ring) {
-        { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+        { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
         s->ring.reset();
     }
     if (max_samples == 0) return BPMF_HIP_OK;
@@ -24,7 +24,7 @@ extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
     if (ring->samples.alloc(words))
         return fail(BPMF_HIP_ENOMEM, "samples_reserve: " + std::to_string(max_samples) + " samples of " + std::to_string((long long)s->ncols) +
                     " columns x " + std::to_string(ring->kp) + " doubles (" + std::to_string(words * sizeof(double) >> 20) + " MiB) do not fit in device memory");
-    { const int rc = ring->samples.zero_async(c->stream); if (rc) return rc; }
+    { const int rc = ring->samples.zero_async(c->stream.get()); if (rc) return rc; }
     s->ring = std::move(ring);
     return BPMF_HIP_OK;
 }
@@ -40,7 +40,7 @@ extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, ring->kp, s->ncols, ring->samples.get(),
-                             (int64_t)ring->max * ring->kp, ring->count, c->stream);
+                             (int64_t)ring->max * ring->kp, ring->count, c->stream.get());
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
     ++ring->count;
@@ -56,7 +56,7 @@ static int sorted_rows(bpmf_hip_side *s, std::vector<int32_t> &rows)
         return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs a query side that holds all its columns (this rank has " +
                     std::to_string((long long)s->from) + " .. " + std::to_string((long long)s->to) + ")");
     bpmf_hip_ctx *c = s->ctx;
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     const std::vector<int64_t> &cp = s->h_colptr;
     rows.assign((size_t)std::max<int64_t>(s->nnz, 1), 0);
     if (s->nnz > 0) HIP_TRY(hipMemcpy(rows.data(), s->d_rowidx, (size_t)s->nnz * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -110,9 +110,9 @@ int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, i
     p.ex_ptr = ex_ptr; p.ex_rows = ex_rows;
     p.part_mean = part_mean.get(); p.part_idx = part_idx.get();
     p.out_mean = out.get(); p.out_std = out.get() + pn; p.out_idx = out_idx.get();
-    bpmf_launch::topn(p, c->stream);
+    bpmf_launch::topn(p, c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
-    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
     if (hipMemcpy(mean_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(std_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
@@ -201,11 +201,11 @@ extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, d
     p.part_score = part.get(); p.part_mean = part.get() + (size_t)nsplit * pn; p.part_std = part.get() + 2 * (size_t)nsplit * pn;
     p.part_idx = part_idx.get();
     p.out_score = out.get(); p.out_mean = out.get() + pn; p.out_std = out.get() + 2 * pn; p.out_idx = out_idx.get();
-    const int lrc = bpmf_launch::topn_scored(p, c->stream);
+    const int lrc = bpmf_launch::topn_scored(p, c->stream.get());
     if (lrc == -2) return fail(BPMF_HIP_ENODEV, "topn_scored: the device refused the LDS of lists of " + std::to_string(n));
     if (lrc) return fail(BPMF_HIP_EINVAL, "topn_scored: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn_scored: kernel launch failed");
-    { const int rc = bounded_stream_sync(c, c->stream, __func__); if (rc) return rc; }
+    { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
     if (hipMemcpy(score_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(mean_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(std_out, out.get() + 2 * pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -286,9 +286,9 @@ extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, dou
     p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
     p.tptr = d_tptr.get(); p.tcand = d_tcand.get(); p.nt = nt; p.tscore = tscore.get();
     p.part_cnt = part_cnt.get(); p.part_ncand = part_ncand.get(); p.rank = d_rank.get(); p.ncand = d_ncand.get();
-    bpmf_launch::rank_eval(p, c->stream);
+    bpmf_launch::rank_eval(p, c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "rank_eval: kernel launch failed");
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if ((nt > 0 && hipMemcpy(rank_out, d_rank.get(), (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) ||
         hipMemcpy(ncand_out, d_ncand.get(), (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return fail(BPMF_HIP_ENODEV, "rank_eval: copying the results back failed");

@@ -32,7 +32,7 @@ extern "C" int bpmf_hip_side_set_weights(bpmf_hip_side *s, const double *w)
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     // (a launch of the side that still reads the arrays being replaced; an evaluation reads neither)
-    { const int rs_ = bounded_stream_sync(c, c->stream, __func__); if (rs_) return rs_; }
+    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     // sqrt(w) and sqrt(w) (r - mean) are formed on the host: the IEEE square root and product, correctly rounded, whatever the
     // device's sqrt sequence would give (the ratings come back from the device: a side keeps no host copy of them)
     const size_t n = (size_t)s->nnz;
@@ -60,7 +60,7 @@ extern "C" int bpmf_hip_side_weights_get(bpmf_hip_side *s, double *sw_host, doub
     HIP_TRY(hipSetDevice(s->ctx->device));
     if (s->robust) {                                                  // (redrawn per launch: the arrays the side's newest launch read)
         { const int rc = settle_async(s); if (rc) return rc; }
-        { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream, __func__); if (rs_) return rs_; }
+        { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }
         { std::string m; if (check_robust(s, &m)) return fail(BPMF_HIP_ENUM, m); }
     }
     const size_t n = (size_t)s->nnz;

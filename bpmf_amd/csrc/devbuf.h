@@ -1,20 +1,25 @@
-// devbuf.h -- owning device and pinned allocations of the add-ons of a side (ext_state.h): freed when they go out of scope, counted
-// while they live.  Included by state.h behind fail() and HIP_TRY, which report the errors (BPMF_HIP_ENOMEM / BPMF_HIP_ENODEV, as
-// dev_upload).  The caller has set the device.
+// devbuf.h -- the owners of everything the library holds on the device: device buffers (DevBuf), mapped pinned host memory (Pinned),
+// events (Event) and streams (Stream), each released when it goes out of scope.  The add-ons of a side (ext_state.h) and the core
+// state behind the handles (state.h: context, side, test set) are owned the same way; no other file allocates or releases.
+// Device bytes are counted while they live, in two counters: the add-ons' DevBuf<T> into g_live_bytes (bpmf_hip_live_device_bytes),
+// the core state's DevBuf<T, true> into g_core_bytes (bpmf_hip_live_core_bytes) -- the core state of a side is built lazily by
+// its first bpmf_hip_sys_sample, which must not move the add-ons' counter.  Included by state.h behind fail() and HIP_TRY, which
+// report the errors (BPMF_HIP_ENOMEM / BPMF_HIP_ENODEV).  The caller has set the device.
 #pragma once
 #include <utility>
 
-// live DevBuf / Pinned allocations of the process and the device bytes of the former (bpmf_hip_live_device_bytes): hipMemGetInfo
-// counts the whole card, other processes included
-inline std::atomic<int64_t> g_live_allocs{0}, g_live_bytes{0};
+// device bytes of the live DevBuf allocations of the process, add-ons / core state: hipMemGetInfo counts the whole card, other
+// processes included
+inline std::atomic<int64_t> g_live_bytes{0}, g_core_bytes{0};
 // host waits for a context's main stream so far in this process (bounded_stream_sync; bpmf_hip_stream_drains): what a loop that
 // claims not to drain must leave unchanged
 inline std::atomic<int64_t> g_stream_drains{0};
 
-template <typename T>
+template <typename T, bool Core = false>
 class DevBuf {
     T *p_ = nullptr;
     size_t bytes_ = 0;
+    static std::atomic<int64_t> &counter() { return Core ? g_core_bytes : g_live_bytes; }
 
 public:
     DevBuf() = default;
@@ -28,8 +33,7 @@ public:
     {
         if (!p_) return;
         (void)hipFree(p_);
-        g_live_allocs.fetch_sub(1, std::memory_order_relaxed);
-        g_live_bytes.fetch_sub((int64_t)bytes_, std::memory_order_relaxed);
+        counter().fetch_sub((int64_t)bytes_, std::memory_order_relaxed);
         p_ = nullptr; bytes_ = 0;
     }
     // n elements, uninitialised (n = 0: one element, so that a live buffer is never NULL)
@@ -45,8 +49,7 @@ public:
                         "hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
         }
         bytes_ = bytes;
-        g_live_allocs.fetch_add(1, std::memory_order_relaxed);
-        g_live_bytes.fetch_add((int64_t)bytes, std::memory_order_relaxed);
+        counter().fetch_add((int64_t)bytes, std::memory_order_relaxed);
         return 0;
     }
     int upload(const T *src, size_t n)
@@ -56,10 +59,11 @@ public:
         if (src && n) HIP_TRY(hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice));
         return 0;
     }
+    int zero() { HIP_TRY(hipMemset(p_, 0, bytes_)); return 0; }
     int zero_async(hipStream_t st) { HIP_TRY(hipMemsetAsync(p_, 0, bytes_, st)); return 0; }
 };
 
-// n elements of mapped pinned host memory and their address on the device (host memory: no part of the live bytes)
+// n elements of mapped pinned host memory and their address on the device (host memory: counted by neither counter)
 template <typename T>
 class Pinned {
     T *h_ = nullptr, *d_ = nullptr;
@@ -77,15 +81,76 @@ public:
     {
         if (!h_) return;
         (void)hipHostFree(h_);
-        g_live_allocs.fetch_sub(1, std::memory_order_relaxed);
         h_ = d_ = nullptr;
     }
     int alloc(size_t n)
     {
         reset();
         HIP_TRY(hipHostMalloc((void **)&h_, n * sizeof(T), hipHostMallocMapped));
-        g_live_allocs.fetch_add(1, std::memory_order_relaxed);
         HIP_TRY(hipHostGetDevicePointer((void **)&d_, h_, 0));
+        return 0;
+    }
+};
+
+// the core state's device buffers (state.h)
+template <typename T>
+using CoreBuf = DevBuf<T, true>;
+
+class Event {
+    hipEvent_t ev_ = nullptr;
+
+public:
+    Event() = default;
+    Event(Event &&o) noexcept : ev_(std::exchange(o.ev_, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { std::swap(ev_, o.ev_); return *this; }
+    ~Event() { reset(); }
+
+    hipEvent_t get() const { return ev_; }
+    explicit operator bool() const { return ev_ != nullptr; }
+    void reset()
+    {
+        if (ev_) (void)hipEventDestroy(ev_);
+        ev_ = nullptr;
+    }
+    int create(unsigned flags = hipEventDefault)
+    {
+        reset();
+        HIP_TRY(hipEventCreateWithFlags(&ev_, flags));
+        return 0;
+    }
+};
+
+// a stream of the library's own, or the caller's (borrow: never destroyed here)
+class Stream {
+    hipStream_t s_ = nullptr;
+    bool owned_ = false;
+
+public:
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s_(std::exchange(o.s_, nullptr)), owned_(std::exchange(o.owned_, false)) {}
+    Stream &operator=(Stream &&o) noexcept { std::swap(s_, o.s_); std::swap(owned_, o.owned_); return *this; }
+    ~Stream() { reset(); }
+
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+    void reset()
+    {
+        if (s_ && owned_) (void)hipStreamDestroy(s_);
+        s_ = nullptr; owned_ = false;
+    }
+    void borrow(hipStream_t s) { reset(); s_ = s; }
+    int create(unsigned flags)
+    {
+        reset();
+        HIP_TRY(hipStreamCreateWithFlags(&s_, flags));
+        owned_ = true;
+        return 0;
+    }
+    int create(unsigned flags, int priority)
+    {
+        reset();
+        HIP_TRY(hipStreamCreateWithPriority(&s_, flags, priority));
+        owned_ = true;
         return 0;
     }
 };

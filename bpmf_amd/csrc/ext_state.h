@@ -120,11 +120,7 @@ struct bpmf_newrows {
     int64_t n = 0, nw = 0; int D = 0, max = 0, count = 0, kp = 0;
     DevBuf<double> F; std::unique_ptr<bpmf_launch::SpMat> sp;
     DevBuf<double> ring, w, y, rinv, mu;
-    Pinned<double> stage; hipEvent_t staged[2] = {nullptr, nullptr};
-    bpmf_newrows() = default;
-    bpmf_newrows(const bpmf_newrows &) = delete;
-    bpmf_newrows &operator=(const bpmf_newrows &) = delete;
-    ~bpmf_newrows() { for (hipEvent_t e : staged) if (e) (void)hipEventDestroy(e); }
+    Pinned<double> stage; Event staged[2];
 };
 
 // fold-in (capi_foldin.hip): the hyper ring of the side -- alpha_s, mu_s (kt), Lambda_s (kt x kt) and Lambda_s mu_s
@@ -137,11 +133,7 @@ struct bpmf_foldin {
     int64_t n = 0; int S = 0, kp = 0;
     DevBuf<int64_t> rowptr; DevBuf<int32_t> colidx; DevBuf<double> ring;
     Pinned<unsigned long long> fail;
-    hipEvent_t timed[2] = {nullptr, nullptr}; float last_ms = -1.f;   // around the newest launch of k_foldin (bpmf_hip_foldin_last_ms)
-    bpmf_foldin() = default;
-    bpmf_foldin(const bpmf_foldin &) = delete;
-    bpmf_foldin &operator=(const bpmf_foldin &) = delete;
-    ~bpmf_foldin() { for (hipEvent_t e : timed) if (e) (void)hipEventDestroy(e); }
+    Event timed[2]; float last_ms = -1.f;   // around the newest launch of k_foldin (bpmf_hip_foldin_last_ms)
 };
 
 // adaptive noise (capi_noise.hip): the block partials | sum of bpmf_hip_train_sse

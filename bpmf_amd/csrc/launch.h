@@ -56,7 +56,7 @@ inline bpmf::SampleArgs blob_args(const bpmf_hip_side *self, double *out_items, 
     bpmf::SampleArgs a{};
     a.items = out_items; a.col_from = self->from;
     a.LambdaF = d_in + blob::par_LambdaF(K); a.Lmu = d_in + blob::par_Lmu(K); a.fail = blob::par_fail_word(d_in, K);
-    a.mu = d_in + blob::par_mu(K); a.prop_lambda = self->d_prop; a.diag_only = c->diag_only;
+    a.mu = d_in + blob::par_mu(K); a.prop_lambda = self->d_prop.get(); a.diag_only = c->diag_only;
     a.mean_rating = self->mean_rating; a.alpha = alpha; a.iter_plus_1 = (uint32_t)(iter + 1); a.ktrue = c->Kt;
     return a;
 }
@@ -71,7 +71,7 @@ struct StatPass {
 inline StatPass stat_pass(const bpmf_hip_side *P, const double *d_in, double *out_host_dev, unsigned *ticket, unsigned seq)
 {
     const int K = P->ctx->K;
-    return {P->d_items, P->from, P->to, P->nstat_waves, P->d_stat_partials, blob::par_fail_word(d_in, K),
+    return {P->d_items, P->from, P->to, P->nstat_waves, P->d_stat_partials.get(), blob::par_fail_word(d_in, K),
             out_host_dev, ticket, blob::res_flag_word(out_host_dev, K), seq, blob::tmo_word(out_host_dev, K)};
 }
 

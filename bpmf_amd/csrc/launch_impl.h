@@ -42,15 +42,15 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     }
     // (item window: the whole list, or the items of one part of the columns -- bpmf_hip_side_set_overlap)
     const int w0 = self->item_n >= 0 ? self->item_off : 0, nwork = self->item_n >= 0 ? self->item_n : self->nwork;
-    a.wi_col = self->d_wi_col + w0; a.wi_p0 = self->d_wi_p0 + w0; a.wi_len = self->d_wi_len + w0; a.wi_mc = self->d_wi_mc + w0; a.wi_chunk = self->d_wi_chunk + w0;
-    a.mc_slot0 = self->d_mc_slot0; a.mc_nchunks = self->d_mc_nch; a.mc_count = self->d_mc_count;
-    a.partials = self->d_partials; a.nwork = nwork;
+    a.wi_col = self->d_wi_col.get() + w0; a.wi_p0 = self->d_wi_p0.get() + w0; a.wi_len = self->d_wi_len.get() + w0; a.wi_mc = self->d_wi_mc.get() + w0; a.wi_chunk = self->d_wi_chunk.get() + w0;
+    a.mc_slot0 = self->d_mc_slot0.get(); a.mc_nchunks = self->d_mc_nch.get(); a.mc_count = self->d_mc_count.get();
+    a.partials = self->d_partials.get(); a.nwork = nwork;
     a.other_items = other->d_items;
-    a.ablate = c->ablate; a.stamps = c->d_stamps;
+    a.ablate = c->ablate; a.stamps = c->d_stamps.get();
     a.gate_flag = self->cur_gate_flag; a.gate_want = self->cur_gate_want;
-    a.tmo = self->cur_gate_flag ? blob::tmo_word(self->a_h_out_dev, K) : nullptr; a.wait_ticks = wait_ticks();
-    a.zero_row = c->d_zero;
-    a.lf32 = (lf32_words(c) && !self->d_prop) ? reinterpret_cast<const float *>(d_in + c->in_words) : nullptr;
+    a.tmo = self->cur_gate_flag ? blob::tmo_word(self->a_h_out.dev(), K) : nullptr; a.wait_ticks = wait_ticks();
+    a.zero_row = c->d_zero.get();
+    a.lf32 = (lf32_words(c) && !self->d_prop.get()) ? reinterpret_cast<const float *>(d_in + c->in_words) : nullptr;
     const bpmf::StatRiders &rr = self->cur_riders;                   // (K = 128 fp32 only)
     if constexpr (F32) {                                             // fp32 factors (items / other_items are float arrays): kernels_wg2.h, T = float
         if (nwork > 0) k128_wg2(nwork, st, ev_start, ev_stop, a, rr);
@@ -72,24 +72,24 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
         if (self->lr_n > 0 && !self->d_prop && !c->diag_only && !(c->ablate & 3u) && !wt) {
             // light columns (<= 16 ratings): product form over the shared factor of LambdaF (k_sample_pf); the others in the slab form
             if (self->hv_nwork > 0) {
-                a.wi_col = self->d_hv_col; a.wi_p0 = self->d_hv_p0; a.wi_len = self->d_hv_len; a.wi_mc = self->d_hv_mc;
-                a.wi_chunk = self->d_hv_chunk; a.nwork = self->hv_nwork;
+                a.wi_col = self->d_hv_col.get(); a.wi_p0 = self->d_hv_p0.get(); a.wi_len = self->d_hv_len.get(); a.wi_mc = self->d_hv_mc.get();
+                a.wi_chunk = self->d_hv_chunk.get(); a.nwork = self->hv_nwork;
                 k64_slab(self->hv_nwork, st, ev_start, nullptr, a);
             }
             LrArgs l;
-            l.rowidx = self->d_rowidx; l.vals = vals; l.col = self->d_lr_col; l.p0 = self->d_lr_p0; l.len = self->d_lr_len;
+            l.rowidx = self->d_rowidx; l.vals = vals; l.col = self->d_lr_col.get(); l.p0 = self->d_lr_p0.get(); l.len = self->d_lr_len.get();
             l.nitems = self->lr_n; l.other_items = other->d_items; l.items = out_items; l.col_from = self->from;
             l.R0 = d_in + blob::par_R0(K); l.S0t = d_in + blob::par_S0t(K); l.y0 = d_in + blob::par_y0(K);
             l.Lmu = a.Lmu; l.fail = a.fail;
             l.mean_rating = self->mean_rating; l.alpha = alpha; l.sqrt_alpha = std::sqrt(alpha); l.iter_plus_1 = (uint32_t)(iter + 1); l.ktrue = c->Kt;
             // three instantiations (<= 3, <= 6, <= 16 ratings), persistent workgroups of eight waves with R0^-1 in LDS
             // (the events ride on the first / last launch of the side)
-            l.Q = self->d_pf_q;
+            l.Q = self->d_pf_q.get();
             bool started = self->hv_nwork > 0;
             if (self->pf_class[3] > self->pf_class[0] && self->d_pf_q) {
                 // Q = U_other R0^-1 once per half-iteration (k_pf_prepare), ahead of the product-form launches
                 const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((self->nrows + 7) / 8, (int64_t)c->num_cu * 4));
-                k64_pf_prepare(grid, st, started ? nullptr : ev_start, l.S0t, other->d_items, self->nrows, self->d_pf_q);
+                k64_pf_prepare(grid, st, started ? nullptr : ev_start, l.S0t, other->d_items, self->nrows, self->d_pf_q.get());
                 started = true;
             }
             int last_pf = -1;
@@ -126,7 +126,7 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
         if (wt) {                                                    // weighted index blocks (never the gather stream)
             sample1w<K>((int)grid.x, st, ev_start, ev_stop, a, f);
         } else if (uses_gather_stream(self) && vals == self->d_vals) {      // the Gram reads the side's gather stream (build_schedule)
-            a.gs_rec = self->d_gs_rec; a.gs_g0 = self->d_gs_g0 + w0; a.gs_ng = self->d_gs_ng + w0;
+            a.gs_rec = self->d_gs_rec.get(); a.gs_g0 = self->d_gs_g0.get() + w0; a.gs_ng = self->d_gs_ng.get() + w0;
             BPMF_LAUNCH(k_sample1<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
         } else {                                                     // other values than the side's own ratings: index blocks
             BPMF_LAUNCH(k_sample1i<K>, grid, dim3(64), st, ev_start, ev_stop, a, f);
@@ -164,19 +164,19 @@ int exchange(bpmf_hip_side *self, hipStream_t st, int sub)
         constexpr int P = K / 2;                                   // 16-byte pieces per column
         if (ns > 0)
             hipLaunchKernelGGL(bpmf::k_pack_cols<K>, dim3((unsigned)((ns * P + 255) / 256)), dim3(256), 0, st,
-                               (const double *)self->d_items, (const int32_t *)self->d_conn_send, ns, self->d_conn_sbuf);
+                               (const double *)self->d_items, (const int32_t *)self->d_conn_send.get(), ns, self->d_conn_sbuf.get());
         NcclGroup group(R);
         NCCL_TRY(group.start());
         for (int r = 0; r < c->nranks; ++r) {
             const int64_t s0 = self->conn_send_ptr[(size_t)r], s1 = self->conn_send_ptr[(size_t)r + 1];
             const int64_t r0 = self->conn_recv_ptr[(size_t)r], r1 = self->conn_recv_ptr[(size_t)r + 1];
-            if (s1 > s0) NCCL_TRY(R->Send(self->d_conn_sbuf + (size_t)s0 * K, (size_t)(s1 - s0) * K, ncclDouble, r, c->comm, st));
-            if (r1 > r0) NCCL_TRY(R->Recv(self->d_conn_rbuf + (size_t)r0 * K, (size_t)(r1 - r0) * K, ncclDouble, r, c->comm, st));
+            if (s1 > s0) NCCL_TRY(R->Send(self->d_conn_sbuf.get() + (size_t)s0 * K, (size_t)(s1 - s0) * K, ncclDouble, r, c->comm, st));
+            if (r1 > r0) NCCL_TRY(R->Recv(self->d_conn_rbuf.get() + (size_t)r0 * K, (size_t)(r1 - r0) * K, ncclDouble, r, c->comm, st));
         }
         NCCL_TRY(group.end());
         if (nr > 0)
             hipLaunchKernelGGL(bpmf::k_unpack_cols<K>, dim3((unsigned)((nr * P + 255) / 256)), dim3(256), 0, st,
-                               (const double *)self->d_conn_rbuf, (const int32_t *)self->d_conn_recv, nr, self->d_items);
+                               (const double *)self->d_conn_rbuf.get(), (const int32_t *)self->d_conn_recv.get(), nr, self->d_items);
         HIP_TRY(hipGetLastError());
         return 0;
         }
@@ -235,9 +235,9 @@ int stats(bpmf_hip_side *self, hipStream_t st, const StatPass &p, hipEvent_t ev_
     // formed once from the GLOBAL sums: SURVEY Q19) together with the failed-column word, then published to the host -- on
     // the side's own stream: its own reduction blob and the second communicator
     const bool dist = c->comm != nullptr && !self->bounds.empty();
-    const bool own = st != c->stream && c->comm2 && self->a_d_red;
+    const bool own = st != c->stream.get() && c->comm2 && self->a_d_red;
     if (dist) COMM_ALIVE_OR_FAIL(c, "statistics all-reduce");
-    double *red = own ? self->a_d_red : c->d_red;
+    double *red = own ? self->a_d_red.get() : c->d_red.get();
     double *out = dist ? red : p.out;
     unsigned *flag = dist ? p.ticket + 8 : p.flag;
     const unsigned seq = dist ? 0u : p.seq;
@@ -269,7 +269,7 @@ void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items
 {
     typedef typename std::conditional<F32, float, double>::type T;
     bpmf_hip_ctx *c = self->ctx;
-    unsigned *flag = reinterpret_cast<unsigned *>(t->h_res_dev + 2);
+    unsigned *flag = reinterpret_cast<unsigned *>(t->h_res.dev() + 2);
     const bool dist = c->comm && !self->bounds.empty();
     t->pstream = ps;
     if (beside) (void)hipStreamWaitEvent(ps, t->in_ev, 0);
@@ -282,22 +282,22 @@ void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items
         t->twin->launched = true;
     }
     // se | se_avg of this rank's test ratings: straight to the host, or -> all-reduce -> host
-    double *red = c->d_red + (t->owner ? blob::red_twin(K) : blob::red_eval(K));
+    double *red = c->d_red.get() + (t->owner ? blob::red_twin(K) : blob::red_eval(K));
     // one kernel, both copies of the test entries.  fp32 too (round 4: k_predict<K, 256, float>) -- as two kernels the second
     // one started when the partner's sampler had filled the chip and ended with it (347 us for 20 us of work), and the
     // host loop, which collects both sums before it enqueues the next iteration, came 45 us late every iteration
     bpmf::TwinArgs tw{};
     if (fused_twin) {
         bpmf_hip_test *u = t->twin;
-        tw.perm = t->d_twin_perm; tw.pavg = u->d_pavg; tw.pm2 = u->d_pm2; tw.mean = u->side->mean_rating;
-        tw.partial = u->d_partial; tw.out = u->h_res_dev; tw.flag = reinterpret_cast<unsigned *>(u->h_res_dev + 2); tw.seq = ++u->seq;
+        tw.perm = t->d_twin_perm.get(); tw.pavg = u->d_pavg.get(); tw.pm2 = u->d_pm2.get(); tw.mean = u->side->mean_rating;
+        tw.partial = u->d_partial.get(); tw.out = u->h_res.dev(); tw.flag = reinterpret_cast<unsigned *>(u->h_res.dev() + 2); tw.seq = ++u->seq;
         u->pstream = ps; u->launched = true;
     }
     const unsigned pseq = dist ? 0u : ++t->seq;
     auto run = [&](auto kernel, unsigned wg, auto... twin) {          // (k_predict takes the twin's arguments, k_predict_f32 has none)
-        launch_ev(kernel, dim3((unsigned)t->nblocks), dim3(wg), ps, nullptr, t->d_tcol, t->d_trow, t->d_tval, t->nnz,
+        launch_ev(kernel, dim3((unsigned)t->nblocks), dim3(wg), ps, nullptr, t->d_tcol.get(), t->d_trow.get(), t->d_tval.get(), t->nnz,
                   reinterpret_cast<const T *>(self_items), reinterpret_cast<const T *>(other_items), self->from, self->mean_rating, n,
-                  t->d_pavg, t->d_pm2, t->d_partial, dist ? red : t->h_res_dev, t->d_ticket, dist ? t->d_ticket + 8 : flag, pseq, twin...);
+                  t->d_pavg.get(), t->d_pm2.get(), t->d_partial.get(), dist ? red : t->h_res.dev(), t->d_ticket.get(), dist ? t->d_ticket.get() + 8 : flag, pseq, twin...);
     };
     if constexpr (F32) {
         if (fused_twin) run(bpmf::k_predict<K, 256, float>, 256u, tw);
@@ -307,10 +307,10 @@ void predict(bpmf_hip_test *t, const bpmf_hip_side *self, const void *self_items
         else run(bpmf::k_predict<K, 256>, 256u, tw);
     }
     if (dist) {
-        if (rccl()->AllReduce(red, red, 2, ncclDouble, ncclSum, c->comm, c->stream) != ncclSuccess) return;
-        publish(red, t->h_res_dev, 2, flag, ++t->seq, -1, c->stream);
+        if (rccl()->AllReduce(red, red, 2, ncclDouble, ncclSum, c->comm, c->stream.get()) != ncclSuccess) return;
+        publish(red, t->h_res.dev(), 2, flag, ++t->seq, -1, c->stream.get());
     }
-    if (beside) (void)hipEventRecord(t->ev_done[t->seq & 1u], ps);
+    if (beside) (void)hipEventRecord(t->ev_done[t->seq & 1u].get(), ps);
 }
 
 }  // namespace bpmf_launch

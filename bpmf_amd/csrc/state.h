@@ -41,17 +41,7 @@ inline int fail(int code, const std::string &msg)
                         std::string(#expr) + ": " + hipGetErrorString(e_));                            \
     } while (0)
 
-template <typename T>
-inline int dev_upload(T **dst, const T *src, size_t n)
-{
-    *dst = nullptr;
-    // (an empty array still gets one element of storage; nothing is read from src then: the caller's array has none)
-    HIP_TRY(hipMalloc((void **)dst, std::max<size_t>(n, 1) * sizeof(T)));
-    if (src && n) HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
-#include "ext_state.h"      // DevBuf and the owned state of the add-ons (uses fail / HIP_TRY above)
+#include "ext_state.h"      // the owners (devbuf.h) and the owned state of the add-ons (uses fail / HIP_TRY above)
 
 namespace blob = bpmf::blob;      // the layouts of the parameter / result / reduction blobs (blob.h)
 
@@ -153,7 +143,7 @@ struct bpmf_hip_ctx {
     // normals and stay exactly zero; RNG stream ids use Kt (c++/sample.cpp:266).
     int K = 0, Kt = 0;
     int dtype = BPMF_HIP_F64;            // arithmetic of the column loop and storage of the factors (BPMF_HIP_F32: K = 128)
-    hipStream_t stream = nullptr;        // S0: samplers, exchange, predict
+    Stream stream;                       // S0: samplers, exchange, predict (its own, or the caller's: borrowed).  Declared first: released last
     hipEvent_t last_sampler_done = nullptr;   // stop event of the newest thing on S0 when that is a stateful sampler (+ exchange), else NULL
     // fused stateful path: the side whose newest half-iteration still has its statistics to run (they
     // ride in the next k_sample1 launch; flush_pending_stats launches them alone if none comes)
@@ -163,14 +153,13 @@ struct bpmf_hip_ctx {
     // ... or, fp32 path: as rider workgroups at the head of the next k_sample_wg2 launch (StatRiders, args.h)
     bool pending_riders = false;
     std::vector<bpmf_hip_side *> sides;  // stateful sides with a statistics stream of their own (for ctx_sync)
-    bool own_stream = false;
     int num_cu = 256;
     unsigned ablate = 0;
     unsigned diag_only = 0;              // BPMF_NO_COVARIANCE variant (bpmf_hip_ctx_set_no_covariance)
     // per-call parameter blob (blob.h): pinned host copy + device copy
-    double *h_in = nullptr, *h_in_dev = nullptr, *d_in = nullptr;
+    Pinned<double> h_in; CoreBuf<double> d_in;
     // result blob (blob.h) in pinned host memory the kernels write directly (zero-copy)
-    double *h_out = nullptr, *h_out_dev = nullptr;
+    Pinned<double> h_out;
     size_t in_words = 0, out_words = 0;  // their sizes: blob::par_words / par_words_pf (K = 64 in fp64), blob::res_words
     std::mutex launch_mutex;             // kernel launches come from the caller's thread and from the sides' workers
     // multi-GPU: RCCL communicator (one rank per process / GPU) and the reduction blob (blob.h) for the all-reduced sums
@@ -187,30 +176,36 @@ struct bpmf_hip_ctx {
     std::atomic<bool> comm_dead{false};
     std::mutex abort_mutex;
     int nranks = 1, rank = 0;
-    double *d_red = nullptr;
+    CoreBuf<double> d_red;
     unsigned seq = 0;                    // value the next publishing kernel writes behind its results
-    unsigned *d_ticket = nullptr;        // arrival counters of k_colstats' waves (stateless path)
-    unsigned long long *d_stamps = nullptr;   // BPMF_HIP_STAMPS=1: phase time stamps of two probe work items (printed when the context dies)
-    double *d_zero = nullptr;            // K zeros: the row padding slots of a ragged rating group gather from
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    CoreBuf<unsigned> d_ticket;          // arrival counters of k_colstats' waves (stateless path)
+    CoreBuf<unsigned long long> d_stamps;     // BPMF_HIP_STAMPS=1: phase time stamps of two probe work items (printed when the context dies)
+    CoreBuf<double> d_zero;              // K zeros: the row padding slots of a ragged rating group gather from
+    Event ev[3];
 };
 
 struct bpmf_hip_side {
     bpmf_hip_ctx *ctx = nullptr;
     int64_t ncols = 0, nrows = 0, from = 0, to = 0, nnz = 0;
     double mean_rating = 0.0;
-    int32_t *d_rowidx = nullptr; double *d_vals = nullptr; bool own_csc = true;
-    double *d_items = nullptr; bool own_items = true;
+    // the ratings and the factors as every launch reads them: views.  Their storage is in the owners below unless the caller
+    // lent it (bpmf_hip_side_create_dev, bpmf_hip_side_bind_items, the tensor sides): an empty owner means borrowed
+    int32_t *d_rowidx = nullptr; double *d_vals = nullptr;
+    CoreBuf<int32_t> own_rowidx; CoreBuf<double> own_vals;
+    double *d_items = nullptr;
     // Second copy of the factor matrix: a sampler writes the copy that is NOT current and the two swap
     // roles behind it, so that an evaluation of the previous iteration (k_predict on its own stream)
     // can still read the factors the sampler replaces.  Only while the library owns the storage, the
     // raw pointer was never handed out, and this rank's launches rewrite or receive every column.
+    // The swap exchanges the views d_items / d_items_alt; the two owners (fp32 contexts: floats behind them, sized in doubles)
+    // stay where they are.
     double *d_items_alt = nullptr; bool items_exposed = false; int cur_buf = 0;
+    CoreBuf<double> items_buf[2];
     struct Reader { struct bpmf_hip_test *t = nullptr; unsigned seq = 0; } readers[2];   // last evaluation that read buffer 0 / 1
     struct bpmf_hip_test *deferred_eval = nullptr;      // evaluation waiting for this side's next gate kernel (flush_deferred)
-    double *d_aggr_mu = nullptr, *d_aggr_lambda = nullptr;   // -o: aggrMu (K x nloc) / aggrLambda (K*K x nloc) of the local columns
-    double *d_prop = nullptr;            // propagated posterior (-m / -l): K x K prior precision per local column, or NULL
-    // the add-ons (ext_state.h), each NULL until its entry point attaches it; released in bpmf_hip_side_destroy
+    CoreBuf<double> d_aggr_mu, d_aggr_lambda;                // -o: aggrMu (K x nloc) / aggrLambda (K*K x nloc) of the local columns
+    CoreBuf<double> d_prop;              // propagated posterior (-m / -l): K x K prior precision per local column, or NULL
+    // the add-ons (ext_state.h), each NULL until its entry point attaches it; released with the side
     std::unique_ptr<bpmf_probit> probit;   // probit likelihood (bpmf_hip_side_set_probit)
     std::unique_ptr<bpmf_censor> censor;   // censored ratings (bpmf_hip_side_set_censored)
     std::unique_ptr<bpmf_ordinal> ordinal; // ordinal probit likelihood (bpmf_hip_side_set_ordinal)
@@ -233,23 +228,23 @@ struct bpmf_hip_side {
     int64_t pf_ratings2 = 0;
     int64_t pf_ratings = 0;                // ratings of the product-form columns (bpmf_hip_side_schedule_info)
     int pf_class[4] = {0, 0, 0, 0};        // the light items by class: <= 3 ratings, 4..6, 7..16 -- class c is [pf_class[c], pf_class[c+1])
-    double *d_pf_q = nullptr;              // product form: R0^-T u_row for every row of the other side (nrows x K), per half-iteration
-    int32_t *d_lr_col = nullptr, *d_lr_len = nullptr; int64_t *d_lr_p0 = nullptr;
-    int32_t *d_hv_col = nullptr, *d_hv_len = nullptr, *d_hv_mc = nullptr, *d_hv_chunk = nullptr; int64_t *d_hv_p0 = nullptr;
-    int32_t *d_wi_col = nullptr, *d_wi_len = nullptr, *d_wi_mc = nullptr, *d_wi_chunk = nullptr;
-    int64_t *d_wi_p0 = nullptr;
+    CoreBuf<double> d_pf_q;                // product form: R0^-T u_row for every row of the other side (nrows x K), per half-iteration
+    CoreBuf<int32_t> d_lr_col, d_lr_len; CoreBuf<int64_t> d_lr_p0;
+    CoreBuf<int32_t> d_hv_col, d_hv_len, d_hv_mc, d_hv_chunk; CoreBuf<int64_t> d_hv_p0;
+    CoreBuf<int32_t> d_wi_col, d_wi_len, d_wi_mc, d_wi_chunk;
+    CoreBuf<int64_t> d_wi_p0;
     // gather stream (mode 1, K <= 32; build_schedule): one 16-byte record per rating in item order, per item its first
-    // group of 16 records and its number of groups.  NULL: not built (BPMF_HIP_GATHER_STREAM=0, another form of the sampler)
-    bpmf::GatherRec *d_gs_rec = nullptr;
-    int32_t *d_gs_g0 = nullptr, *d_gs_ng = nullptr;
+    // group of 16 records and its number of groups.  Empty: not built (BPMF_HIP_GATHER_STREAM=0, another form of the sampler)
+    CoreBuf<bpmf::GatherRec> d_gs_rec;
+    CoreBuf<int32_t> d_gs_g0, d_gs_ng;
     int64_t gs_groups = 0;                 // groups of 16 records in the stream, the padding groups behind the last item included
-    int32_t *d_mc_slot0 = nullptr, *d_mc_nch = nullptr;
-    unsigned *d_mc_count = nullptr;
-    double *d_partials = nullptr;
+    CoreBuf<int32_t> d_mc_slot0, d_mc_nch;
+    CoreBuf<unsigned> d_mc_count;
+    CoreBuf<double> d_partials;
     int nstat_waves = 0;
     int nstat_wg = 0;                    // > 0: the side's stand-alone statistics pass runs as this many four-wave workgroups (k_colstats_wg: big sides)
-    hipEvent_t ev_stat_go = nullptr;     // big side: S0 continues only once S1 has reached the statistics kernel (head start for its workgroups)
-    double *d_stat_partials = nullptr;
+    Event ev_stat_go;                    // big side: S0 continues only once S1 has reached the statistics kernel (head start for its workgroups)
+    CoreBuf<double> d_stat_partials;
     int64_t stat_rider_passes = 0, stat_alone_passes = 0;   // statistics passes of this side enqueued as riders / as kernels of their own (bpmf_hip_side_stat_info)
     std::vector<int64_t> bounds;         // multi-GPU: column range of every rank (nranks + 1 entries)
     // overlap of exchange and sampling (bpmf_hip_side_set_overlap): every rank's range is cut into nsub parts of
@@ -263,44 +258,51 @@ struct bpmf_hip_side {
     std::vector<int64_t> sub_bounds;     // nranks x (nsub + 1): global column bounds of the parts of every rank
     std::vector<int> sub_item_off;       // nsub + 1: the work items of part c are [off[c], off[c+1]) of the item arrays
     int item_off = 0, item_n = -1;       // item window of the launch being enqueued (-1: the whole list)
-    hipStream_t sx = nullptr;            // exchange stream
-    hipEvent_t sub_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, sx_done = nullptr;
+    Stream sx;                           // exchange stream
+    Event sub_ev[8], sx_done;
     // BPMF_REDUCE formulation (bpmf_hip_sys_set_reduce, kernels_reduce.h): this side's precomputed Gram parts
     // (ncols x part words, every column -- not only the local ones) and the transpose of this rank's block of
     // ratings (for every column of the OTHER side: the local columns of this side that rate it), longest first
     bool reduce_on = false;
-    double *d_prec = nullptr;
-    int64_t *d_t_colptr = nullptr; int32_t *d_t_rowidx = nullptr; double *d_t_vals = nullptr; int32_t *d_t_order = nullptr;
+    CoreBuf<double> d_prec;
+    CoreBuf<int64_t> d_t_colptr; CoreBuf<int32_t> d_t_rowidx; CoreBuf<double> d_t_vals; CoreBuf<int32_t> d_t_order;
     std::vector<int64_t> h_colptr;       // host copy of the local column pointers (schedules are rebuilt when the parts change)
     // connectivity-aware exchange (bpmf_hip_side_set_conn): per peer, the columns of this rank's range the
     // peer reads (send) and the columns of the peer's range this rank reads (recv), as global column ids
     std::vector<int64_t> conn_send_ptr, conn_recv_ptr;
-    int32_t *d_conn_send = nullptr, *d_conn_recv = nullptr;
-    double *d_conn_sbuf = nullptr, *d_conn_rbuf = nullptr;
-    int64_t failed_column = -1;
-    bool pending = false;
-    float last_sample_ms = 0.f, last_reduce_ms = 0.f;
-    bool timing_valid = true;
-    // asynchronous (stateful) path: own parameter / result blobs, gate word, events
-    double *a_h_in = nullptr, *a_h_in_dev = nullptr, *a_d_in = nullptr;
-    double *a_h_out = nullptr, *a_h_out_dev = nullptr;
-    bpmf::FusedArgs cur_fused{};         // gate + statistics riders of the k_sample1 launch being enqueued (fused stateful path)
+    CoreBuf<int32_t> d_conn_send, d_conn_recv;
+    CoreBuf<double> d_conn_sbuf, d_conn_rbuf;
+    // asynchronous (stateful) path: own parameter / result blobs, gate word, events -- set once (ensure_state), then read by both threads
+    Pinned<double> a_h_in; CoreBuf<double> a_d_in;
+    Pinned<double> a_h_out;
+    CoreBuf<unsigned> a_dflag;           // device word k_gate_stage sets when the parameters are staged (in-kernel gate of the sampler)
+    Pinned<unsigned> a_gate;                             // pinned word the host sets to iter + 1 when a_h_in holds that iteration's parameters
+    CoreBuf<unsigned> a_ticket;                          // arrival counters of this side's k_colstats waves
+    CoreBuf<double> a_d_red;                             // multi-GPU: this side's device blob for the all-reduced sums
+    Event evs[2][4];                     // (start, sampled, stats, staged) of the two half-iterations that may be in flight
+    Stream saux;                         // this side's statistics stream (high priority: its few blocks must not queue behind the other side's sampler)
+    // What the caller's thread writes with every launch, on cache lines of its own: the side's worker reads the members above
+    // and writes the ones below while the caller enqueues, and a line the two threads share travels between their cores on
+    // the path from "sums landed" to "gate open".  (ML-1M shape, K = 32, alternating processes against the layout before the
+    // owning members: with those simply in declaration order the iteration took 0.35 % longer, seven pairs, every one slower;
+    // grouped like this 0.1 % less, four pairs.)
+    alignas(64) bpmf::FusedArgs cur_fused{};   // gate + statistics riders of the k_sample1 launch being enqueued (fused stateful path)
     bpmf::StatRiders cur_riders{};       // fp32 path: statistics riders of the k_sample_wg2 launch being enqueued
+    const unsigned *cur_gate_flag = nullptr; unsigned cur_gate_want = 0;   // what the launch being enqueued polls (NULL: ordered by the queue)
+    unsigned a_seq = 0;
+    int iter = -1;                       // state of the reference's Sys (c++/bpmf.h:139,221-226) for bpmf_hip_sys_sample
+    bool pending = false;
+    hipEvent_t last_stop = nullptr;      // stop event of this side's newest sampler (diagnostic: boundary to the next launch)
     // the event behind which this side's statistics of the job with event set 0 / 1 are complete, once they
     // have been enqueued (inside the next sampler launch, or as a kernel of their own): the collector's blocking wait
     std::atomic<hipEvent_t> stats_ev[2] = {{nullptr}, {nullptr}};
-    unsigned *a_dflag = nullptr;         // device word k_gate_stage sets when the parameters are staged (in-kernel gate of the sampler)
-    const unsigned *cur_gate_flag = nullptr; unsigned cur_gate_want = 0;   // what the launch being enqueued polls (NULL: ordered by the queue)
-    unsigned *a_gate = nullptr, *a_gate_dev = nullptr;   // pinned word the host sets to iter + 1 when a_h_in holds that iteration's parameters
-    unsigned *a_ticket = nullptr;                        // arrival counters of this side's k_colstats waves
-    double *a_d_red = nullptr;                           // multi-GPU: this side's device blob for the all-reduced sums
-    unsigned a_seq = 0;
-    hipEvent_t evs[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // (start, sampled, stats, staged) of the two half-iterations that may be in flight
-    hipStream_t saux = nullptr;          // this side's statistics stream (high priority: its few blocks must not queue behind the other side's sampler)
     // host worker of this side: collects its sums when they land, forms cov, draws its next
-    // hyper-parameters and releases the gate of its next sampler, all while the GPU samples the other side
+    // hyper-parameters and releases the gate of its next sampler, all while the GPU samples the other side.
+    // From here on: what the worker writes (in the stateless path, the caller at collection).
     struct Job { int iter; unsigned seq; int evset; bool timed; hipEvent_t prev_stop; };
-    hipEvent_t last_stop = nullptr;      // stop event of this side's newest sampler (diagnostic: boundary to the next launch)
+    alignas(64) int64_t failed_column = -1;
+    float last_sample_ms = 0.f, last_reduce_ms = 0.f;
+    bool timing_valid = true;
     double tot_gap_ms = 0.0; int64_t n_gap = 0;
     std::thread worker;
     std::mutex wm;
@@ -313,8 +315,6 @@ struct bpmf_hip_side {
     int gate_iter = -2;                  // iteration whose parameters the gate has been opened for
     double tot_sample_ms = 0.0, tot_reduce_ms = 0.0;
     long long n_launches = 0;
-    // state of the reference's Sys (c++/bpmf.h:139,221-226) for bpmf_hip_sys_sample
-    int iter = -1;
     double norm = 0.0;
     // norm of the last few collected half-iterations (bpmf_hip_sys_norm: the line of iteration i - 1 is printed after iteration i
     // has been enqueued; asking bpmf_hip_sys_state for it would drain the side's pipeline first).  Guarded by `wm`.
@@ -354,16 +354,16 @@ inline bool uses_gather_stream(const bpmf_hip_side *s)
 struct bpmf_hip_test {
     bpmf_hip_side *side = nullptr;
     int64_t nnz = 0;
-    int32_t *d_tcol = nullptr, *d_trow = nullptr;
-    double *d_tval = nullptr, *d_pavg = nullptr, *d_pm2 = nullptr, *d_partial = nullptr;
+    CoreBuf<int32_t> d_tcol, d_trow;
+    CoreBuf<double> d_tval, d_pavg, d_pm2, d_partial;
     int64_t nblocks = 0;
     int wg = 256;                        // threads per workgroup of k_predict (64: single-wave workgroups, small test sets)
     int64_t global_nnz = -1;             // multi-GPU: test ratings over all ranks (all-reduced once)
-    double *h_res = nullptr, *h_res_dev = nullptr;       // pinned: se | se_avg | flag
-    unsigned *d_ticket = nullptr;                        // arrival counter of k_predict's blocks
+    Pinned<double> h_res;                                // pinned: se | se_avg | flag
+    CoreBuf<unsigned> d_ticket;                          // arrival counter of k_predict's blocks
     unsigned seq = 0, done_seq = 0;
     bool launched = false;
-    hipEvent_t ev_in = nullptr, ev_done[2] = {nullptr, nullptr}, in_ev = nullptr;
+    Event ev_in, ev_done[2]; hipEvent_t in_ev = nullptr;
     hipStream_t pstream = nullptr;       // where the launch in flight was enqueued (the main stream, or the other side's)
     // requested, not yet enqueued (flush_deferred): the factor copies it reads, captured at the request
     bool deferred = false, cancelled = false; int def_n = 0; struct bpmf_hip_side *def_other = nullptr;
@@ -372,10 +372,10 @@ struct bpmf_hip_test {
     // the roles swapped whenever this one is (bpmf_hip_test_set_twin); owner: the test matrix this one is the twin of
     struct bpmf_hip_test *twin = nullptr, *owner = nullptr;
     // single GPU, fp64: the twin's entries are this matrix's, transposed -- entry q here is entry twin_perm[q] there, and
-    // ONE kernel writes both copies (k_predict's TwinArgs).  NULL: the twin runs as a kernel of its own (sharded, fp32).
-    int32_t *d_twin_perm = nullptr;
+    // ONE kernel writes both copies (k_predict's TwinArgs).  Empty: the twin runs as a kernel of its own (sharded, fp32).
+    CoreBuf<int32_t> d_twin_perm;
     std::vector<int32_t> h_col, h_row;   // global column / row of every entry (kept for the matching)
-    double *d_prob_sum = nullptr; int prob_n = 0;        // probit: running sums of Phi(x . y) per entry and the samples added (capi_probit.hip)
+    DevBuf<double> d_prob_sum; int prob_n = 0;       // probit: running sums of Phi(x . y) per entry and the samples added (capi_probit.hip)
     DevBuf<double> ord_sum; int ord_n = 0, ord_nlev = 0; // ordinal: running sums of the level probabilities, level-major (nlev x nnz), and the samples added (capi_ordinal.hip)
 };
 
@@ -468,7 +468,7 @@ inline size_t lf32_words(const bpmf_hip_ctx *c) { return c->dtype == BPMF_HIP_F3
 // be produced by this launch or arrive through the exchange that follows it.
 inline bool second_copy_usable(const bpmf_hip_side *s)
 {
-    if (!s->d_items_alt || !s->own_items || s->items_exposed || s->nwork <= 0) return false;
+    if (!s->d_items_alt || !s->items_buf[s->cur_buf] || s->items_exposed || s->nwork <= 0) return false;
     // bounded staleness: a part that does not travel must keep the value the peer LAST RECEIVED, and that sits in the
     // current copy only -- with two copies a skipped part would fall back to what the other copy held two
     // half-iterations earlier: the samplers of such a side write in place

@@ -61,6 +61,10 @@ BPMF_API int bpmf_hip_abi_version(void);
 /* diagnostic: device bytes the add-ons of all sides of this process own right now (probit, features, sample rings, residual partials,
  * the temporaries of their calls): hipMemGetInfo counts the whole card, other processes included */
 BPMF_API int64_t bpmf_hip_live_device_bytes(void);
+/* diagnostic: the same for the core state of all contexts, sides and test sets of this process -- blobs, ratings, factors, schedules,
+ * posterior aggregates, per-column priors, test entries.  (Memory a caller lent -- bpmf_hip_side_create_dev, bpmf_hip_side_bind_items
+ * -- is the caller's and not counted.)  A side's first bpmf_hip_sys_sample allocates here, never in the add-ons' counter. */
+BPMF_API int64_t bpmf_hip_live_core_bytes(void);
 /* diagnostic: how often this process has waited on the host for the main stream of a context (the waits of the entry points that say
  * "waits": bpmf_hip_train_sse, bpmf_hip_ordinal_cut_step, the _get calls ...).  A loop that does not drain leaves it unchanged. */
 BPMF_API int64_t bpmf_hip_stream_drains(void);

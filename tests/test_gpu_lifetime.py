@@ -1,6 +1,8 @@
 """Ownership of the device memory of a side's add-ons (probit, side information, sample ring, training residuals):
 bpmf_hip_live_device_bytes counts what they hold, so what an entry point allocates and what a destroy or a refused call leaves
-behind can be stated in bytes.  (hipMemGetInfo counts the whole card, other processes included.)
+behind can be stated in bytes.  (hipMemGetInfo counts the whole card, other processes included.)  The core state of a context, a
+side and a test set (blobs, ratings, factors, schedules, aggregates, priors, test entries) is counted on its own by
+bpmf_hip_live_core_bytes: the second half of this file.
 
 Shapes: 48 users x 40 movies, about 300 ratings; K = 8 (a kernel size) and K = 20 (runs padded to 32)."""
 import numpy as np
@@ -19,6 +21,10 @@ def live():
     return int(bpmf_amd.load_library().bpmf_hip_live_device_bytes())
 
 
+def core():
+    return int(bpmf_amd.load_library().bpmf_hip_live_core_bytes())
+
+
 @pytest.fixture(scope="module")
 def data():
     rng = np.random.default_rng(5)
@@ -30,7 +36,7 @@ def data():
     Fm = rng.standard_normal((NM, 5))
     Fu = sp.random(NU, 70, density=0.1, random_state=7, format="csr")
     Fu.sort_indices()
-    return dict(M=util.csc_arrays(A), Mt=util.csc_arrays(A.T), T=util.csc_arrays(T), Fm=Fm, Fu=Fu)
+    return dict(M=util.csc_arrays(A), Mt=util.csc_arrays(A.T), T=util.csc_arrays(T), Tt=util.csc_arrays(T.T), Fm=Fm, Fu=Fu)
 
 
 def attach_everything(eng, d):
@@ -158,3 +164,169 @@ def test_colptr_is_shared(data, K):
         assert live() - before == others + (NM + 1) * 8                 # ... and the column pointers once
     finally:
         eng.close()
+
+
+# ---- the core state: bpmf_hip_live_core_bytes ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("K,dtype", [(8, "f64"), (20, "f64"), (65, "f32")])
+def test_core_state_returns_to_base(data, K, dtype):
+    """Everything the core state can hold at once -- the lazily built state of the stateful path, a test set with its twin and
+    evaluations in flight, posterior aggregates, a propagated posterior, the BPMF_REDUCE storage of a second pair (fp64 only: the
+    fp32 context refuses it) -- goes with the handle that holds it, and none of it is an add-on."""
+    base, addons = core(), live()
+    eng = bpmf_amd.HipEngine(K, dtype=dtype)
+    try:
+        assert core() > base and live() == addons                      # the context's blobs
+        movies = eng.side_create(NM, NU, *data["M"], 3.0)
+        users = eng.side_create(NU, NM, *data["Mt"], 3.0)
+        assert live() == addons
+        test = eng.test_create(movies, *data["T"])
+        twin = eng.test_create(users, *data["Tt"])
+        eng.test_set_twin(test, twin)
+        assert live() == addons
+        for i in range(3):                                             # the pipelined loop: the line of i - 1 is collected behind iteration i
+            eng.sys_sample(movies, users, 2.0)
+            eng.sys_sample(users, movies, 2.0)
+            if i > 0:
+                assert eng.predict_finish(test)[2] == 30 and eng.predict_finish(twin)[2] == 30
+            eng.predict_launch(test, movies, users, i)
+            assert live() == addons
+        assert eng.predict_finish(test)[2] == 30 and eng.predict_finish(twin)[2] == 30
+        eng.aggr_add(movies)
+        eng.aggr_add(users)
+        assert live() == addons
+        eng.set_prop_posterior(users, np.tile(np.eye(K).ravel(order="F"), (NU, 1)))
+        assert live() == addons
+        sides = [movies, users]
+        if dtype == "f64":
+            sides += [eng.side_create(NM, NU, *data["M"], 3.0), eng.side_create(NU, NM, *data["Mt"], 3.0)]
+            eng.sys_set_reduce(sides[2], sides[3])
+            assert live() == addons
+        eng.sync()
+        assert live() == addons
+        held = core()
+        for t in (twin, test):
+            eng.test_destroy(t)
+            assert core() < held and live() == addons
+            held = core()
+        for s in sides:
+            eng.side_destroy(s)
+            assert core() < held and live() == addons
+            held = core()
+    finally:
+        eng.close()
+    assert core() == base and live() == addons
+
+
+_BIND_CHILD = """
+import sys
+import torch                                                           # (first: the library then runs on the HIP runtime torch brought)
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import bpmf_amd
+NU, NM = 48, 40
+lib = bpmf_amd.load_library()
+core, live = lib.bpmf_hip_live_core_bytes, lib.bpmf_hip_live_device_bytes
+rng = np.random.default_rng(5)
+rows = np.stack([np.sort(rng.choice(NU, size=7, replace=False)) for _ in range(NM)])      # 7 ratings per movie
+colptr = np.arange(NM + 1, dtype=np.int64) * 7
+M = (colptr, np.ascontiguousarray(rows.ravel(), np.int32), rng.integers(1, 6, size=NM * 7).astype(np.float64))
+for K in (8, 20):
+    base = core()
+    eng = bpmf_amd.HipEngine(K)
+    movies = eng.side_create(NM, NU, *M, 3.0)
+    ld = eng.ld()
+    assert ld == (8 if K == 8 else 32)
+    addons, before = live(), core()
+    buf = torch.full((NM, ld), 0.25, dtype=torch.float64, device="cuda:0")
+    eng.bind_items(movies, buf.data_ptr(), keep=buf, ld=ld, nbytes=buf.numel() * 8)
+    assert before - core() == 2 * ld * NM * 8, (K, before - core())
+    assert live() == addons
+    held = core()
+    eng.side_destroy(movies)
+    assert core() < held and live() == addons
+    torch.cuda.synchronize()
+    assert bool((buf.cpu() == 0.25).all())                             # the caller's storage was not freed with the side
+    assert live() == addons
+    eng.close()
+    assert core() == base
+    print("BOUND K=%d" % K)
+"""
+
+
+def test_bind_items_releases_the_two_factor_copies():
+    """The caller's buffer is a torch tensor, so this runs in a process of its own, which imports torch ahead of the library."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("BPMF_HIP_DBUF", None)                                     # (the default: a side keeps two copies of its factors)
+    r = subprocess.run([sys.executable, "-c", _BIND_CHILD, root], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    assert "BOUND K=8" in r.stdout and "BOUND K=20" in r.stdout, r.stdout
+
+
+@pytest.mark.parametrize("K", [8, 20])
+def test_prop_posterior_is_exact_in_both_directions(data, K):
+    eng = bpmf_amd.HipEngine(K)
+    try:
+        users = eng.side_create(NU, NM, *data["Mt"], 3.0)
+        ld = eng.ld()
+        addons, before = live(), core()
+        eng.set_prop_posterior(users, np.tile(np.eye(K).ravel(order="F"), (NU, 1)))
+        assert core() - before == ld * ld * NU * 8 and live() == addons
+        eng.set_prop_posterior(users, None)
+        assert core() == before and live() == addons
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("K", [8, 20])
+def test_aggr_finalize_returns_what_aggr_add_took(data, K):
+    eng = bpmf_amd.HipEngine(K)
+    try:
+        movies = eng.side_create(NM, NU, *data["M"], 3.0)
+        users = eng.side_create(NU, NM, *data["Mt"], 3.0)
+        for _ in range(3):
+            eng.sys_sample(movies, users, 2.0)
+            eng.sys_sample(users, movies, 2.0)
+        eng.sync()
+        addons, before = live(), core()                                # (behind the first sys_sample: it builds core state of its own)
+        eng.aggr_add(movies)
+        assert core() - before == (K + K * K) * NM * 8                 # aggrMu, aggrLambda: the caller's num_latent
+        assert live() == addons
+        eng.aggr_add(movies)
+        assert core() - before == (K + K * K) * NM * 8 and live() == addons
+        mu, lam = eng.aggr_finalize(movies, 2)
+        assert mu.shape == (NM, K) and lam.shape == (NM, K * K)
+        assert core() == before and live() == addons
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("K", [8, 20])
+def test_create_dev_borrows_the_ratings(data, K):
+    from tests.test_gpu_probit import _from_device, _hip_runtime, _to_device
+    colptr, rowidx, vals = data["M"]
+    nnz = int(colptr[-1])
+    hip = _hip_runtime()
+    d_rows, d_vals = _to_device(hip, rowidx), _to_device(hip, vals)
+    eng = bpmf_amd.HipEngine(K)
+    try:
+        addons, c0 = live(), core()
+        own = eng.side_create(NM, NU, colptr, rowidx, vals, 3.0)
+        c1 = core()
+        assert live() == addons
+        lent = eng.side_create_dev(NM, NU, colptr, d_rows.value, d_vals.value, 3.0)
+        c2 = core()
+        assert live() == addons
+        assert (c1 - c0) - (c2 - c1) == nnz * (4 + 8)                  # the same side but for its copies of rowidx and vals
+        eng.side_destroy(lent)
+        assert core() == c1 and live() == addons
+        assert np.array_equal(_from_device(hip, d_rows, rowidx), rowidx) and np.array_equal(_from_device(hip, d_vals, vals), vals)
+        eng.side_destroy(own)
+        assert core() == c0 and live() == addons
+    finally:
+        eng.close()
+        hip.hipFree(d_rows); hip.hipFree(d_vals)
