@@ -61,6 +61,11 @@ _SIGNATURES = {
     "bpmf_hip_side_samples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "bpmf_hip_side_samples_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_samples_count": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_samples_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "bpmf_hip_side_samples_set": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "bpmf_hip_predict_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_predict_cells_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_rank_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
@@ -193,6 +198,9 @@ _SIGNATURES = {
     "bpmf_io_read_tns": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(c_i32p), C.POINTER(c_i32p), C.POINTER(c_i32p),
                                    C.POINTER(c_f64p)]),
     "bpmf_io_write_tns": (C.c_int, [C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_io_write_model": (C.c_int, [C.c_char_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_io_read_model": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(c_f64p), C.POINTER(c_f64p), C.POINTER(c_f64p), C.POINTER(c_f64p)]),
     "bpmf_assign_greedy": (C.c_int, [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bpmf_assign_contiguous": (C.c_int, [C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
 }

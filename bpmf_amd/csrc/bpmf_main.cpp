@@ -40,6 +40,15 @@
 // other side (bpmf_hip_foldin): DIR/foldin-rows-mean.ddm, foldin-rows-std.ddm (new x movies), foldin-cols-mean.ddm, foldin-cols-std.ddm
 // (users x new); with --topn N also DIR/foldin-rows-topn.csv / foldin-cols-topn.csv, the new entities as the queries, their own
 // ratings excluded.  One more header line names the counts; everything else keeps its format.
+// --save-model DIR (-i > -b; one GPU, no -g): the run keeps the sample rings of both sides and, unless --probit, both hyper rings, and
+// writes them after the chain as a model directory, format version 1 (include/bpmf_io.h): model.txt,
+// U-samples.ddm, V-samples.ddm, U-hyper.ddm, V-hyper.ddm, in the numbering of the input.  One more header line, `save-model: DIR`.
+// --model DIR -o OUT [-n TRAIN] [-p TEST]: no chain runs (run_model).  The model is loaded into a fp64 context and serves --predict FILE
+// [--predict-threshold F] (OUT/predict.csv: row,col,mean,std[,prob] for the cells FILE lists, 1-based, in the reader's order; prob with
+// sigma = 1 / sqrt(alpha), always there for a probit model with t = 0 unless given and sigma = 1), --topn N with its --topn-* flags and
+// --rank-eval N -p TEST (both need -n TRAIN: the rated cells are what they exclude) and --fold-in-rows / --fold-in-cols FILE (a Gaussian
+// model with hyper files), each with exactly the files of a training run.  stdout: one line `model: DIR, R x C, num_latent K, S samples,
+// LIKELIHOOD` (and the Final rank lines of --rank-eval); times go to stderr.
 // --row-features FILE / --col-features FILE [--lambda-beta F] (one GPU, no -g): side information.  FILE is a
 // dense matrix (.ddm / .csv) with one row per user / movie; both sides then step through the blocking bpmf_hip_link_sample and
 // -o DIR also gets DIR/U-link.ddm / DIR/V-link.ddm, the posterior mean of the link matrix (D x num_latent).  A sparse FILE (.sdm / .sbm /
@@ -109,7 +118,8 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--implicit W0] [--rank-eval N [--rank-by rows|cols] [--rank-threshold F]] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--implicit W0] [--rank-eval N [--rank-by rows|cols] [--rank-threshold F]] [--fold-in-rows FILE] [--fold-in-cols FILE] [--save-model DIR]\n"
+              << "   or: bpmf --model DIR -o OUT [-n <train_matrix>] [-p <test_matrix>] [--predict FILE [--predict-threshold F]] [--topn N ...] [--rank-eval N ...] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "       bpmf --tensor <TNS> [--tensor-test <TNS>] [--tensor-dims I,J,T] [-o DIR/] [-i N] [-b N] [-a F] [-d K]\n"
               << "\n"
               << "Parameters:\n"
@@ -165,6 +175,14 @@ void usage()
               << "              (users x new); std leaves the observation noise 1 / alpha out.  With --topn N also DIR/foldin-rows-topn.csv /\n"
               << "              foldin-cols-topn.csv: the best N for every new entity, its own ratings excluded; files of more than 2^28 cells\n"
               << "              need --topn\n"
+              << "  [--save-model DIR]: keep the post-burn-in samples of both sides and (unless --probit) their hyper-parameters, and write\n"
+              << "              them after the chain as a model directory (model.txt, U-samples.ddm, V-samples.ddm, U-hyper.ddm, V-hyper.ddm;\n"
+              << "              needs -i > -b; one GPU, no -g; not with BPMF_REDUCE=1, --tensor, --ordinal, --implicit, features, -m / -l)\n"
+              << "  --model DIR: serve a saved model without a chain (needs -o OUT; not with -i, -b, -a, -g, --save-model or any flag of the\n"
+              << "              likelihood or the chain; -d must be the model's).  --predict FILE [--predict-threshold F]: OUT/predict.csv with\n"
+              << "              row,col,mean,std[,prob] for the cells the sparse matrix FILE lists (its values are ignored); --topn N and\n"
+              << "              --rank-eval N -p TEST with their flags and files (both need -n TRAIN: the rated cells are excluded);\n"
+              << "              --fold-in-rows / --fold-in-cols FILE with their files (a Gaussian model saved with hyper files)\n"
               << "  [--link-tol F] [--link-max-iter N]: the stopping rule of that CG draw: relative residual (1e-6), most iterations (1000);\n"
               << "              need a sparse feature file\n"
               << "  [--lambda-beta F]: the fixed precision scale of the rows of beta, for both sides (5: a default, not a tuned number)\n"
@@ -444,6 +462,7 @@ struct Job {
     bool has_feat_m() const { return !feat_m.data.empty() || sfeat_m_d > 0; }
     std::vector<double> beta_u, beta_m;                              // posterior mean of the link matrices, D x K row-major
     std::string odirname;
+    std::string save_model;                                          // --save-model DIR (empty: off)
     Dense prop_m_mu, prop_m_lambda, prop_u_mu, prop_u_lambda;       // -m / -l (empty: none)
     std::vector<int64_t> bm, bu;                                     // column ranges of the ranks
     std::vector<int64_t> perm_m, perm_u;                             // greedy assignment: new column id -> original (empty: none)
@@ -457,6 +476,203 @@ struct Job {
     long double average_items_sec = 0, average_ratings_sec = 0;
     std::vector<std::string> errors;                                 // per rank
 };
+
+// --topn and --rank-eval over the sample rings of the two sides: after the chain (rank_main) or from a loaded model (run_model)
+void serve_rank(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies)
+{
+    const int64_t nmovies = J.M.ncols, nusers = J.M.nrows;
+    if (J.topn > 0) {                                                // one rank (main refuses -g > 1)
+        const double t0 = tick();
+        bpmf_hip_side *q = J.topn_by_cols ? movies : users, *cand = J.topn_by_cols ? users : movies;
+        const int64_t nq = J.topn_by_cols ? nmovies : nusers;
+        J.topn_idx.resize((size_t)nq * J.topn); J.topn_mean.resize(J.topn_idx.size()); J.topn_std.resize(J.topn_idx.size());
+        if (J.topn_kind < 0) {
+            check(bpmf_hip_topn(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_idx.data(), J.topn_mean.data(), J.topn_std.data()));
+        } else {
+            J.topn_score.resize(J.topn_idx.size());
+            check(bpmf_hip_topn_scored(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_kind, J.topn_param, J.topn_sigma, J.topn_idx.data(),
+                                       J.topn_score.data(), J.topn_mean.data(), J.topn_std.data()));
+            if (J.topn_kind == BPMF_HIP_SCORE_UCB) std::cerr << "topn score: ucb, kappa = " << J.topn_param << std::endl;
+            else std::cerr << "topn score: " << (J.topn_kind == BPMF_HIP_SCORE_PROB ? "prob" : "ei") << ", threshold = " << J.topn_param
+                           << ", sigma = " << J.topn_sigma << std::endl;
+        }
+        std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
+                  << (tick() - t0) * 1e3 << " ms" << std::endl;
+    }
+    if (J.rank_eval > 0) {                                           // one rank (main refuses -g > 1)
+        const double t0 = tick();
+        bpmf_hip_side *q = J.rank_by_cols ? movies : users, *cand = J.rank_by_cols ? users : movies;
+        const int64_t nq = J.rank_by_cols ? nmovies : nusers;
+        J.rank_rank.assign(std::max<size_t>(J.rank_tcand.size(), 1), 0); J.rank_ncand.assign((size_t)std::max<int64_t>(nq, 1), 0);
+        static const int32_t none = 0;
+        check(bpmf_hip_rank_eval(q, cand, J.mean_m, 0, nq, 1, J.rank_tptr.data(), J.rank_tcand.empty() ? &none : J.rank_tcand.data(),
+                                 J.rank_rank.data(), J.rank_ncand.data()));
+        J.rank_rank.resize(J.rank_tcand.size());
+        std::cerr << "rank-eval: " << J.rank_tcand.size() << " held-out entries of " << nq << " queries, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+    }
+}
+
+// --fold-in-rows / --fold-in-cols against the sample ring of the other side and the side's hyper ring: after the chain or from a loaded model
+void serve_fold(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies)
+{
+    const int64_t nmovies = J.M.ncols, nusers = J.M.nrows;
+    // fold-in (streams: tag 7 = new users, 8 = new movies): one launch over every (new entity, kept sample), then the block and the lists
+    auto fold_in = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, unsigned tag) {
+        if (N.n == 0) return;
+        const double t0 = tick();
+        static const int32_t none = 0; static const double zero = 0.0;
+        check(bpmf_hip_foldin(side, cand, J.mean_m, N.n, N.Fr.colptr.data(), N.Fr.rowidx.empty() ? &none : N.Fr.rowidx.data(),
+                              N.Fr.vals.empty() ? &zero : N.Fr.vals.data(), tag, 1));
+        if (N.dense_out) {
+            N.mean.resize((size_t)N.n * (size_t)nc); N.std.resize(N.mean.size());
+            const int64_t step = std::max<int64_t>(64, ((int64_t)1 << 24) / std::max<int64_t>(nc, 1) / 64 * 64);
+            for (int64_t q0 = 0; q0 < N.n; q0 += step) {
+                const int64_t q1 = std::min(N.n, q0 + step);
+                check(bpmf_hip_foldin_predict(side, cand, J.mean_m, q0, q1, 0, nc, N.mean.data() + (size_t)q0 * nc, N.std.data() + (size_t)q0 * nc));
+            }
+        }
+        if (J.topn > 0) {
+            N.new_are_queries = true;
+            N.topn_idx.resize((size_t)N.n * J.topn); N.topn_mean.resize(N.topn_idx.size()); N.topn_std.resize(N.topn_idx.size());
+            check(bpmf_hip_foldin_topn(side, cand, J.mean_m, J.topn, 1, N.topn_idx.data(), N.topn_mean.data(), N.topn_std.data()));
+        }
+        std::cerr << "fold-in " << (side == users ? "rows" : "columns") << ": " << N.n << " x " << nc << " predictions, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+    };
+    fold_in(users, movies, J.fold_u, nmovies, 7);
+    fold_in(movies, users, J.fold_m, nusers, 8);
+}
+
+// DIR/topn.csv
+void write_topn(const Job &J)
+{
+    if (J.topn > 0) {                                                // 1-based ids in the ORIGINAL numbering, like the -o writers
+        const std::vector<int64_t> &pq = J.topn_by_cols ? J.perm_m : J.perm_u, &pc = J.topn_by_cols ? J.perm_u : J.perm_m;
+        const int64_t nq = (int64_t)(J.topn_idx.size() / (size_t)J.topn);
+        std::vector<int64_t> order((size_t)nq);                      // queries in original order
+        for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
+        if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
+        FILE *f = fopen((J.odirname + "/topn.csv").c_str(), "w");
+        if (!f) die("cannot write " + J.odirname + "/topn.csv");
+        fprintf(f, J.topn_kind < 0 ? "query,rank,candidate,mean,std\n" : "query,rank,candidate,score,mean,std\n");
+        for (int64_t q : order)
+            for (int r = 0; r < J.topn; ++r) {
+                const size_t at = (size_t)q * J.topn + r;
+                const int32_t c = J.topn_idx[at];
+                if (c < 0) break;                                      // (padding slots are not written)
+                const long long qid = (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), cid = (long long)((pc.empty() ? c : pc[(size_t)c]) + 1);
+                if (J.topn_kind < 0) fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", qid, r + 1, cid, J.topn_mean[at], J.topn_std[at]);
+                else fprintf(f, "%lld,%d,%lld,%.17g,%.17g,%.17g\n", qid, r + 1, cid, J.topn_score[at], J.topn_mean[at], J.topn_std[at]);
+            }
+        if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
+    }
+}
+
+// --rank-eval: the metrics (the arithmetic of bpmf_amd.rank_metrics), and with -o DIR the rank of every held-out entry in DIR/ranks.csv
+RankMetrics write_ranks(const Job &J)
+{
+    RankMetrics rkm;
+    if (J.rank_eval > 0) {
+        rkm = rank_metrics(J.rank_rank, J.rank_tptr, J.rank_ncand, J.rank_eval);
+        if (!J.odirname.empty()) {                                   // 1-based ids in the ORIGINAL numbering, the queries in their order
+            const std::vector<int64_t> &pq = J.rank_by_cols ? J.perm_m : J.perm_u, &pc = J.rank_by_cols ? J.perm_u : J.perm_m;
+            const int64_t nq = (int64_t)J.rank_tptr.size() - 1;
+            std::vector<int64_t> order((size_t)nq);
+            for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
+            if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
+            FILE *f = fopen((J.odirname + "/ranks.csv").c_str(), "w");
+            if (!f) die("cannot write " + J.odirname + "/ranks.csv");
+            fprintf(f, "query,candidate,rank,ncand\n");
+            for (int64_t q : order)
+                for (int64_t p = J.rank_tptr[(size_t)q]; p < J.rank_tptr[(size_t)q + 1]; ++p) {
+                    const int32_t c = J.rank_tcand[(size_t)p];
+                    fprintf(f, "%lld,%lld,%d,%d\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), (long long)((pc.empty() ? c : pc[(size_t)c]) + 1),
+                            J.rank_rank[(size_t)p], J.rank_ncand[(size_t)q]);
+                }
+            if (fclose(f) != 0) die("cannot write " + J.odirname + "/ranks.csv");
+        }
+    }
+    return rkm;
+}
+
+// the new entities: new x movies as it is computed; users x new = the transpose of what is computed (row-major new x users IS
+// column-major users x new).  Lists: 1-based ids, the new entities numbered by their row in the feature file.
+void write_new(const Job &J, Job::NewRows &N, bool rows, int64_t nother, const char *stem)
+{
+    if (N.n == 0) return;
+    const std::string base = J.odirname + "/" + stem + (rows ? "-rows" : "-cols");
+    try {
+        if (N.dense_out) {
+            for (int which = 0; which < 2; ++which) {
+                std::vector<double> &src = which ? N.std : N.mean;
+                Dense d;
+                if (rows) {                                        // row-major new x movies -> column-major
+                    d.nrows = N.n; d.ncols = nother; d.data.resize(src.size());
+                    for (int64_t i = 0; i < N.n; ++i)
+                        for (int64_t c = 0; c < nother; ++c) d.data[(size_t)c * (size_t)N.n + (size_t)i] = src[(size_t)i * (size_t)nother + (size_t)c];
+                } else { d.nrows = nother; d.ncols = N.n; d.data.swap(src); }
+                bpmf::io::write_dense(base + (which ? "-std.ddm" : "-mean.ddm"), d);
+            }
+        }
+    } catch (const std::exception &e) { die(e.what()); }
+    if (J.topn > 0) {
+        const std::string name = base + "-topn.csv";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) die("cannot write " + name);
+        fprintf(f, "query,rank,candidate,mean,std\n");
+        const int64_t nq = (int64_t)(N.topn_idx.size() / (size_t)J.topn);
+        for (int64_t q = 0; q < nq; ++q)
+            for (int r = 0; r < J.topn; ++r) {
+                const size_t at = (size_t)q * J.topn + r;
+                if (N.topn_idx[at] < 0) break;                     // (padding slots are not written)
+                fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", (long long)(q + 1), r + 1, (long long)(N.topn_idx[at] + 1), N.topn_mean[at], N.topn_std[at]);
+            }
+        if (fclose(f) != 0) die("cannot write " + name);
+    }
+}
+
+// the ratings of the entities to fold in: new users x movies / users x new movies; every cell once, finite; stored by new entity
+void read_fold(const Job &J, const std::string &name, bool rows, Job::NewRows &N)
+{
+    if (name.empty()) return;
+    const int64_t nmovies = J.M.ncols, nusers = J.M.nrows;
+    const std::string w = rows ? "--fold-in-rows" : "--fold-in-cols";
+    const int64_t nother = rows ? nmovies : nusers;
+    Csc F;
+    try { F = bpmf::io::read_sparse(name); } catch (const std::exception &e) { die(e.what()); }
+    if ((rows ? F.ncols : F.nrows) != nother)
+        die(w + ": " + name + " is " + std::to_string(F.nrows) + " x " + std::to_string(F.ncols) + ", the training matrix has " + std::to_string(nother) +
+            (rows ? " columns" : " rows"));
+    const int64_t n = rows ? F.nrows : F.ncols;
+    if (n < 1) die(w + ": " + name + (rows ? " has no rows" : " has no columns"));
+    if (F.dup_row >= 0)
+        die(w + ": " + name + " lists cell (" + std::to_string((long long)F.dup_row + 1) + ", " + std::to_string((long long)F.dup_col + 1) + ") twice");
+    for (double v : F.vals) if (!std::isfinite(v)) die(w + ": " + name + " holds a value that is not finite");
+    N.n = n;
+    if (n > ((int64_t)1 << 28) / std::max<int64_t>(nother, 1)) {
+        const std::string cells = std::to_string(n) + " x " + std::to_string(nother) + " predictions are more than 2^28 cells per file";
+        if (J.topn < 1) die(w + ": " + cells + ": ask for the best N of every query with --topn N instead");
+        std::cerr << w << ": " << cells << ": the dense mean / std files are skipped, the --topn lists are written" << std::endl;
+        N.dense_out = false;
+    }
+    N.Fr = rows ? bpmf::io::transpose(F) : F;                     // column i = new entity i, its row ids ascending
+}
+
+// --rank-eval: the held-out candidates of every query from the test matrix, ascending (the run's numbering)
+void build_rank_lists(Job &J)
+{
+    if (J.rank_eval > 0) {                                           // the held-out candidates of every query, ascending (the run's numbering)
+        const Csc &Q = J.rank_by_cols ? J.T : J.Tt;                  // one column per query
+        J.rank_tptr.assign((size_t)Q.ncols + 1, 0);
+        for (int64_t q = 0; q < Q.ncols; ++q) {
+            std::vector<int32_t> c;
+            for (int64_t p = Q.colptr[(size_t)q]; p < Q.colptr[(size_t)q + 1]; ++p)
+                if (!J.rank_thr_given || Q.vals[(size_t)p] > J.rank_thr) c.push_back(Q.rowidx[(size_t)p]);
+            std::sort(c.begin(), c.end());
+            J.rank_tcand.insert(J.rank_tcand.end(), c.begin(), c.end());
+            J.rank_tptr[(size_t)q + 1] = (int64_t)J.rank_tcand.size();
+        }
+    }
+}
 
 // one rank = one GPU: Sys::Sys + init (its shard), the Gibbs loop of c++/bpmf.cpp:180-253
 void rank_main(Job &J, int rank, std::ostream &os)
@@ -530,12 +746,15 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.has_feat_u()) check(bpmf_hip_side_link_lambda_prior(users, J.lb_a0, J.lb_b0));
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0;
+    const bool saving = !J.save_model.empty();
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
-    if (J.fold_u.n > 0) check(bpmf_hip_side_hyper_reserve(users, J.nsims - J.burnin));
-    if (J.fold_m.n > 0) check(bpmf_hip_side_hyper_reserve(movies, J.nsims - J.burnin));
+    // (--save-model keeps them for both sides, unless the model is a probit one: fold-in is refused there anyway)
+    const bool hyper_u = J.fold_u.n > 0 || (saving && !J.probit), hyper_m = J.fold_m.n > 0 || (saving && !J.probit);
+    if (hyper_u) check(bpmf_hip_side_hyper_reserve(users, J.nsims - J.burnin));
+    if (hyper_m) check(bpmf_hip_side_hyper_reserve(movies, J.nsims - J.burnin));
     auto set_new = [&](bpmf_hip_side *side, const Job::NewRows &N) {
         if (N.n == 0) return;
         if (N.F.empty()) {
@@ -638,6 +857,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.new_m.n > 0) os << "new columns: " << J.new_m.n << " (--new-col-features), predicted from their features over the kept samples" << std::endl;
     if (J.fold_u.n > 0) os << "fold-in rows: " << J.fold_u.n << " (--fold-in-rows), " << J.fold_u.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (J.fold_m.n > 0) os << "fold-in columns: " << J.fold_m.n << " (--fold-in-cols), " << J.fold_m.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
+    if (saving) os << "save-model: " << J.save_model << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -697,7 +917,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(J.implicit ? bpmf_hip_implicit_sample(a, b, alpha) : linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha));
     };
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0) {
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -761,8 +981,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
         if (J.robust && aggregate && iter >= burnin) check(bpmf_hip_side_robust_add(movies));
         if (ring_u && iter >= burnin) check(bpmf_hip_side_samples_add(users));
         if (ring_m && iter >= burnin) check(bpmf_hip_side_samples_add(movies));
-        if (J.fold_u.n > 0 && iter >= burnin) check(bpmf_hip_side_hyper_add(users, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
-        if (J.fold_m.n > 0 && iter >= burnin) check(bpmf_hip_side_hyper_add(movies, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
+        if (hyper_u && iter >= burnin) check(bpmf_hip_side_hyper_add(users, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
+        if (hyper_m && iter >= burnin) check(bpmf_hip_side_hyper_add(movies, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
         if (J.new_u.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(users, movies));
         if (J.new_m.n > 0 && iter >= burnin) check(bpmf_hip_side_newrows_add(movies, users));
         if (probit_eval && iter >= burnin) check(bpmf_hip_test_probit_add(test, movies, users));
@@ -860,35 +1080,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         }
         J.ord_rmse = std::sqrt(sq / (double)n); J.ord_accuracy = (double)hit / (double)n; J.ord_logp = lp / (double)n;
     }
-    if (J.topn > 0) {                                                // one rank (main refuses -g > 1)
-        const double t0 = tick();
-        bpmf_hip_side *q = J.topn_by_cols ? movies : users, *cand = J.topn_by_cols ? users : movies;
-        const int64_t nq = J.topn_by_cols ? nmovies : nusers;
-        J.topn_idx.resize((size_t)nq * J.topn); J.topn_mean.resize(J.topn_idx.size()); J.topn_std.resize(J.topn_idx.size());
-        if (J.topn_kind < 0) {
-            check(bpmf_hip_topn(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_idx.data(), J.topn_mean.data(), J.topn_std.data()));
-        } else {
-            J.topn_score.resize(J.topn_idx.size());
-            check(bpmf_hip_topn_scored(q, cand, J.mean_m, J.topn, 0, nq, 1, J.topn_kind, J.topn_param, J.topn_sigma, J.topn_idx.data(),
-                                       J.topn_score.data(), J.topn_mean.data(), J.topn_std.data()));
-            if (J.topn_kind == BPMF_HIP_SCORE_UCB) std::cerr << "topn score: ucb, kappa = " << J.topn_param << std::endl;
-            else std::cerr << "topn score: " << (J.topn_kind == BPMF_HIP_SCORE_PROB ? "prob" : "ei") << ", threshold = " << J.topn_param
-                           << ", sigma = " << J.topn_sigma << std::endl;
-        }
-        std::cerr << "topn: " << J.topn << " per " << (J.topn_by_cols ? "column" : "row") << " for " << nq << " queries, "
-                  << (tick() - t0) * 1e3 << " ms" << std::endl;
-    }
-    if (J.rank_eval > 0) {                                           // one rank (main refuses -g > 1)
-        const double t0 = tick();
-        bpmf_hip_side *q = J.rank_by_cols ? movies : users, *cand = J.rank_by_cols ? users : movies;
-        const int64_t nq = J.rank_by_cols ? nmovies : nusers;
-        J.rank_rank.assign(std::max<size_t>(J.rank_tcand.size(), 1), 0); J.rank_ncand.assign((size_t)std::max<int64_t>(nq, 1), 0);
-        static const int32_t none = 0;
-        check(bpmf_hip_rank_eval(q, cand, J.mean_m, 0, nq, 1, J.rank_tptr.data(), J.rank_tcand.empty() ? &none : J.rank_tcand.data(),
-                                 J.rank_rank.data(), J.rank_ncand.data()));
-        J.rank_rank.resize(J.rank_tcand.size());
-        std::cerr << "rank-eval: " << J.rank_tcand.size() << " held-out entries of " << nq << " queries, " << (tick() - t0) * 1e3 << " ms" << std::endl;
-    }
+    serve_rank(J, users, movies);                                    // --topn, --rank-eval: one rank (main refuses -g > 1)
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
         if (N.n == 0) return;
@@ -911,30 +1103,31 @@ void rank_main(Job &J, int rank, std::ostream &os)
     };
     predict_new(users, movies, J.new_u, nmovies, !J.topn_by_cols);   // --topn-by rows: the new rows are the queries
     predict_new(movies, users, J.new_m, nusers, J.topn_by_cols);     // --topn-by cols: the new columns are the queries
-    // fold-in (streams: tag 7 = new users, 8 = new movies): one launch over every (new entity, kept sample), then the block and the lists
-    auto fold_in = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, unsigned tag) {
-        if (N.n == 0) return;
+    serve_fold(J, users, movies);
+    if (saving) {                                                    // one rank (main refuses -g); the ORIGINAL numbering, as the -o writers
         const double t0 = tick();
-        static const int32_t none = 0; static const double zero = 0.0;
-        check(bpmf_hip_foldin(side, cand, J.mean_m, N.n, N.Fr.colptr.data(), N.Fr.rowidx.empty() ? &none : N.Fr.rowidx.data(),
-                              N.Fr.vals.empty() ? &zero : N.Fr.vals.data(), tag, 1));
-        if (N.dense_out) {
-            N.mean.resize((size_t)N.n * (size_t)nc); N.std.resize(N.mean.size());
-            const int64_t step = std::max<int64_t>(64, ((int64_t)1 << 24) / std::max<int64_t>(nc, 1) / 64 * 64);
-            for (int64_t q0 = 0; q0 < N.n; q0 += step) {
-                const int64_t q1 = std::min(N.n, q0 + step);
-                check(bpmf_hip_foldin_predict(side, cand, J.mean_m, q0, q1, 0, nc, N.mean.data() + (size_t)q0 * nc, N.std.data() + (size_t)q0 * nc));
+        bpmf::io::Model m;
+        m.K = K; m.S = nsims - burnin; m.rows = nusers; m.cols = nmovies; m.mean_rating = J.mean_m; m.alpha = J.alpha;
+        m.probit = J.probit; m.probit_threshold = J.probit ? J.probit_threshold : 0.0; m.f32 = J.dtype == BPMF_HIP_F32; m.hyper = hyper_u && hyper_m;
+        const size_t sk = (size_t)m.S * (size_t)K, h = 1 + (size_t)K + (size_t)K * K;
+        m.U.resize(sk * (size_t)nusers); m.V.resize(sk * (size_t)nmovies);
+        check(bpmf_hip_side_samples_get(users, 0, m.S, m.U.data()));
+        check(bpmf_hip_side_samples_get(movies, 0, m.S, m.V.data()));
+        if (!J.perm_u.empty()) { permute_columns(m.U, (int64_t)sk, inverse(J.perm_u)); permute_columns(m.V, (int64_t)sk, inverse(J.perm_m)); }
+        auto hyper = [&](bpmf_hip_side *side, std::vector<double> &out) {      // column s = alpha_s, mu_s, Lambda_s
+            std::vector<double> a((size_t)m.S), mu((size_t)m.S * K), lam((size_t)m.S * K * K);
+            check(bpmf_hip_side_hyper_get(side, a.data(), mu.data(), lam.data()));
+            out.resize(h * (size_t)m.S);
+            for (size_t sm = 0; sm < (size_t)m.S; ++sm) {
+                out[sm * h] = a[sm];
+                memcpy(&out[sm * h + 1], &mu[sm * K], sizeof(double) * (size_t)K);
+                memcpy(&out[sm * h + 1 + K], &lam[sm * K * K], sizeof(double) * (size_t)K * K);
             }
-        }
-        if (J.topn > 0) {
-            N.new_are_queries = true;
-            N.topn_idx.resize((size_t)N.n * J.topn); N.topn_mean.resize(N.topn_idx.size()); N.topn_std.resize(N.topn_idx.size());
-            check(bpmf_hip_foldin_topn(side, cand, J.mean_m, J.topn, 1, N.topn_idx.data(), N.topn_mean.data(), N.topn_std.data()));
-        }
-        std::cerr << "fold-in " << (side == users ? "rows" : "columns") << ": " << N.n << " x " << nc << " predictions, " << (tick() - t0) * 1e3 << " ms" << std::endl;
-    };
-    fold_in(users, movies, J.fold_u, nmovies, 7);
-    fold_in(movies, users, J.fold_m, nusers, 8);
+        };
+        if (m.hyper) { hyper(users, m.Uh); hyper(movies, m.Vh); }
+        try { bpmf::io::write_model(J.save_model, m); } catch (const std::exception &e) { die(e.what()); }
+        std::cerr << "save-model: " << m.S << " samples of " << nusers << " + " << nmovies << " columns, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+    }
     if (rank == 0) {
         J.elapsed = elapsed; J.rmse_avg = rmse_avg; J.num_predict = num_predict;
         J.average_items_sec = average_items_sec; J.average_ratings_sec = average_ratings_sec;
@@ -1044,6 +1237,129 @@ static int run_tensor(const std::string &file, const std::string &test_file, con
     return 0;
 }
 
+// --model DIR: serves a saved model (bpmf --save-model, bpmf_amd.save_model) without a chain.  The model is read
+// and everything that can be refused is refused before a GPU is touched; then a fp64 context with the model's num_latent, both sides
+// from the training matrix (-n: the cells the rankings exclude) or from empty matrices, the sample rings and the hyper rings loaded,
+// and what was asked for -- --predict, --topn, --rank-eval, --fold-in-rows / -cols -- through the code a training run serves them with.
+static int run_model(Job &J, const std::string &dir, const std::string &fname, const std::string &probename, const std::string &predict_file,
+                     bool thr_given, double thr, const std::string &fold_in_rows, const std::string &fold_in_cols, bool d_given, int d)
+{
+    bpmf::io::Model m;
+    try { m = bpmf::io::read_model(dir); } catch (const std::exception &e) { die(e.what()); }
+    const int K = m.K;
+    if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
+    for (const std::string *f : {&fold_in_rows, &fold_in_cols}) {
+        if (f->empty()) continue;
+        const std::string w = f == &fold_in_rows ? "--fold-in-rows" : "--fold-in-cols";
+        if (m.probit) die(w + ": " + dir + " is a probit model, which is saved without hyper files: labels would need a latent iteration of their own");
+        if (!m.hyper) die(w + ": " + dir + " was saved without hyper files (model.txt: hyper 0)");
+    }
+    if (J.topn_kind == BPMF_HIP_SCORE_PROB || J.topn_kind == BPMF_HIP_SCORE_EI) {
+        if (!m.probit && !(m.alpha > 0.0)) die("--topn-score needs a model with alpha > 0 (sigma = 1 / sqrt(alpha))");
+        J.topn_sigma = m.probit ? 1.0 : 1.0 / std::sqrt(m.alpha);
+    }
+    const int64_t nusers = m.rows, nmovies = m.cols;
+    try {
+        if (!fname.empty()) J.M = bpmf::io::read_sparse(fname);
+        if (!probename.empty()) J.T = bpmf::io::read_sparse(probename);
+    } catch (const std::exception &e) { die(e.what()); }
+    if (!fname.empty()) {                                            // the shape a training run gives both: the larger of the two files
+        const int64_t r = std::max(J.M.nrows, J.T.nrows), c = std::max(J.M.ncols, J.T.ncols);
+        if (r != nusers || c != nmovies)
+            die("-n " + fname + (probename.empty() ? "" : " with -p " + probename) + " is " + std::to_string(r) + " x " + std::to_string(c) + ", the model " + dir +
+                " is " + std::to_string(nusers) + " x " + std::to_string(nmovies));
+    } else {
+        J.M.colptr.assign((size_t)nmovies + 1, 0);
+    }
+    bpmf::io::resize(J.M, nusers, nmovies);
+    if (!probename.empty()) {
+        if (J.T.nrows > nusers || J.T.ncols > nmovies) die("-p " + probename + " is larger than the model " + dir);
+        bpmf::io::resize(J.T, nusers, nmovies);
+    } else {
+        J.T.colptr.assign((size_t)nmovies + 1, 0); J.T.nrows = nusers; J.T.ncols = nmovies;
+    }
+    J.Mt = bpmf::io::transpose(J.M);
+    J.Tt = bpmf::io::transpose(J.T);
+    J.K = K; J.dtype = BPMF_HIP_F64; J.mean_m = J.mean_u = m.mean_rating; J.alpha = m.alpha; J.probit = m.probit;
+    build_rank_lists(J);
+    read_fold(J, fold_in_rows, true, J.fold_u);
+    read_fold(J, fold_in_cols, false, J.fold_m);
+    Csc P;                                                           // --predict FILE: the cells, in the reader's order
+    if (!predict_file.empty()) {
+        try { P = bpmf::io::read_sparse(predict_file); } catch (const std::exception &e) { die(e.what()); }
+        if (P.nrows > nusers || P.ncols > nmovies)
+            die("--predict: " + predict_file + " is " + std::to_string(P.nrows) + " x " + std::to_string(P.ncols) + ", the model " + dir + " is " +
+                std::to_string(nusers) + " x " + std::to_string(nmovies));
+    }
+    const bool want_prob = m.probit || thr_given;
+    const double pt = thr_given ? thr : 0.0, psigma = m.probit ? 1.0 : (m.alpha > 0.0 ? 1.0 / std::sqrt(m.alpha) : 0.0);
+    if (!predict_file.empty() && thr_given && !m.probit && !(m.alpha > 0.0)) die("--predict-threshold needs a model with alpha > 0 (sigma = 1 / sqrt(alpha))");
+
+    std::cout << "model: " << dir << ", " << nusers << " x " << nmovies << ", num_latent " << K << ", " << m.S << " samples, " << (m.probit ? "probit" : "gaussian")
+              << std::endl;
+    int device = 0;
+    if (const char *e = getenv("BPMF_HIP_DEVICES")) device = atoi(e);
+    bpmf_hip_ctx *ctx = nullptr;
+    bpmf_hip_side *movies = nullptr, *users = nullptr;
+    const double t0 = tick();
+    static const int32_t none = 0; static const double zero = 0.0;
+    check(bpmf_hip_ctx_create_ex(device, K, BPMF_HIP_F64, nullptr, &ctx));
+    check(bpmf_hip_side_create(ctx, nmovies, nusers, 0, nmovies, J.M.colptr.data(), J.M.rowidx.empty() ? &none : J.M.rowidx.data(),
+                               J.M.vals.empty() ? &zero : J.M.vals.data(), J.mean_m, &movies));
+    check(bpmf_hip_side_create(ctx, nusers, nmovies, 0, nusers, J.Mt.colptr.data(), J.Mt.rowidx.empty() ? &none : J.Mt.rowidx.data(),
+                               J.Mt.vals.empty() ? &zero : J.Mt.vals.data(), J.mean_u, &users));
+    check(bpmf_hip_side_samples_reserve(users, m.S)); check(bpmf_hip_side_samples_set(users, m.S, m.U.data()));
+    check(bpmf_hip_side_samples_reserve(movies, m.S)); check(bpmf_hip_side_samples_set(movies, m.S, m.V.data()));
+    if (m.hyper && !m.probit) {
+        const size_t h = 1 + (size_t)K + (size_t)K * K;
+        for (int which = 0; which < 2; ++which) {
+            bpmf_hip_side *side = which ? movies : users;
+            const std::vector<double> &H = which ? m.Vh : m.Uh;
+            check(bpmf_hip_side_hyper_reserve(side, m.S));
+            for (size_t sm = 0; sm < (size_t)m.S; ++sm) check(bpmf_hip_side_hyper_add(side, H[sm * h], &H[sm * h + 1], &H[sm * h + 1 + K]));
+        }
+    }
+    std::cerr << "model: loaded in " << (tick() - t0) * 1e3 << " ms" << std::endl;
+
+    if (!predict_file.empty()) {
+        const double t1 = tick();
+        const size_t n = (size_t)P.nnz();
+        std::vector<int32_t> q(std::max<size_t>(n, 1)), c(std::max<size_t>(n, 1));
+        for (int64_t col = 0; col < P.ncols; ++col)
+            for (int64_t at = P.colptr[(size_t)col]; at < P.colptr[(size_t)col + 1]; ++at) { q[(size_t)at] = P.rowidx[(size_t)at]; c[(size_t)at] = (int32_t)col; }
+        std::vector<double> mean(std::max<size_t>(n, 1)), sd(std::max<size_t>(n, 1)), prob(std::max<size_t>(n, 1));
+        check(bpmf_hip_predict_cells(users, movies, J.mean_m, (int64_t)n, q.data(), c.data(), want_prob ? 1 : 0, pt, psigma, mean.data(), sd.data(), prob.data()));
+        const std::string name = J.odirname + "/predict.csv";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) die("cannot write " + name);
+        fprintf(f, want_prob ? "row,col,mean,std,prob\n" : "row,col,mean,std\n");
+        for (size_t i = 0; i < n; ++i) {
+            if (want_prob) fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g\n", (long long)q[i] + 1, (long long)c[i] + 1, mean[i], sd[i], prob[i]);
+            else fprintf(f, "%lld,%lld,%.17g,%.17g\n", (long long)q[i] + 1, (long long)c[i] + 1, mean[i], sd[i]);
+        }
+        if (fclose(f) != 0) die("cannot write " + name);
+        std::cerr << "predict: " << n << " cells, " << (tick() - t1) * 1e3 << " ms" << std::endl;
+    }
+    serve_rank(J, users, movies);
+    serve_fold(J, users, movies);
+    bpmf_hip_side_destroy(movies);
+    bpmf_hip_side_destroy(users);
+    bpmf_hip_ctx_destroy(ctx);
+
+    write_topn(J);
+    const RankMetrics rkm = write_ranks(J);
+    write_new(J, J.fold_u, true, nmovies, "foldin");
+    write_new(J, J.fold_m, false, nusers, "foldin");
+    if (J.rank_eval > 0) {
+        std::cout << "Final recall@" << J.rank_eval << ": " << rkm.recall << std::endl;
+        std::cout << "Final NDCG@" << J.rank_eval << ": " << rkm.ndcg << std::endl;
+        std::cout << "Final MRR: " << rkm.mrr << std::endl;
+        std::cout << "Final MPR: " << rkm.mpr << std::endl;
+        std::cout << "Final rank AUC: " << rkm.auc << std::endl;
+    }
+    return 0;
+}
+
 int main(int argc, char *argv[])
 {
     Job J;
@@ -1073,6 +1389,8 @@ int main(int argc, char *argv[])
                                               {"tensor-dims", required_argument, nullptr, 1042},
                                               {"implicit", required_argument, nullptr, 1060}, {"rank-eval", required_argument, nullptr, 1061},
                                               {"rank-by", required_argument, nullptr, 1062}, {"rank-threshold", required_argument, nullptr, 1063},
+                                              {"save-model", required_argument, nullptr, 1070}, {"model", required_argument, nullptr, 1071},
+                                              {"predict", required_argument, nullptr, 1072}, {"predict-threshold", required_argument, nullptr, 1073},
                                               {nullptr, 0, nullptr, 0}};
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
@@ -1082,63 +1400,108 @@ int main(int argc, char *argv[])
     std::string ordinal_levels, ordinal_cutpoints, ordinal_step;
     std::string implicit_w0, rank_eval_n, rank_by = "rows", rank_threshold;
     bool rank_eval_given = false, rank_by_given = false;
+    std::string model_dir, predict_file, predict_threshold;
+    bool save_model_given = false, model_given = false, predict_given = false, predict_threshold_given = false;
+    bool nsims_given = false, burnin_given = false, d_given = false, g_given = false;
+    std::string training_flag;                                       // the first flag of the likelihood / the chain (refused with --model)
+    auto training = [&](const char *flag) { if (training_flag.empty()) training_flag = flag; };
     bool ordinal_levels_given = false, ordinal_cutpoints_given = false;
     bool tensor_given = false, tensor_test_given = false, tensor_dims_given = false;
     int ch;
     while ((ch = getopt_long(argc, argv, "krvn:t:p:i:b:f:o:m:l:a:d:g:h", long_opts, nullptr)) != -1) {
         switch (ch) {
-        case 1000: fp32 = true; break;
+        case 1000: training("--fp32"); fp32 = true; break;
         case 1001: J.topn = atoi(optarg); if (J.topn < 1) die("--topn expects N >= 1"); break;
         case 1002: topn_by = optarg; break;
-        case 1003: noise = optarg; break;
-        case 1004: alpha_prior = optarg; break;
-        case 1005: alpha_max = optarg; break;
-        case 1006: J.probit = true; break;
-        case 1007: probit_threshold = optarg; threshold_given = true; break;
-        case 1008: row_features = optarg; break;
-        case 1009: col_features = optarg; break;
-        case 1010: lambda_beta = optarg; break;
-        case 1011: link_tol = optarg; break;
-        case 1012: link_max_iter = optarg; break;
-        case 1013: lambda_beta_prior = optarg; J.lb_sampled = true; break;
-        case 1014: censored_file = optarg; J.censored = true; break;
-        case 1030: weights_file = optarg; J.weighted = true; break;
-        case 1031: robust_nu = optarg; J.robust = true; break;
-        case 1015: new_row_features = optarg; break;
-        case 1016: new_col_features = optarg; break;
+        case 1003: training("--noise"); noise = optarg; break;
+        case 1004: training("--alpha-prior"); alpha_prior = optarg; break;
+        case 1005: training("--alpha-max"); alpha_max = optarg; break;
+        case 1006: training("--probit"); J.probit = true; break;
+        case 1007: training("--probit-threshold"); probit_threshold = optarg; threshold_given = true; break;
+        case 1008: training("--row-features"); row_features = optarg; break;
+        case 1009: training("--col-features"); col_features = optarg; break;
+        case 1010: training("--lambda-beta"); lambda_beta = optarg; break;
+        case 1011: training("--link-tol"); link_tol = optarg; break;
+        case 1012: training("--link-max-iter"); link_max_iter = optarg; break;
+        case 1013: training("--lambda-beta-prior"); lambda_beta_prior = optarg; J.lb_sampled = true; break;
+        case 1014: training("--censored"); censored_file = optarg; J.censored = true; break;
+        case 1030: training("--weights"); weights_file = optarg; J.weighted = true; break;
+        case 1031: training("--robust"); robust_nu = optarg; J.robust = true; break;
+        case 1015: training("--new-row-features"); new_row_features = optarg; break;
+        case 1016: training("--new-col-features"); new_col_features = optarg; break;
         case 1017: topn_score = optarg; break;
         case 1018: topn_kappa = optarg; topn_kappa_given = true; break;
         case 1019: topn_threshold = optarg; topn_threshold_given = true; break;
         case 1020: fold_in_rows = optarg; break;
         case 1021: fold_in_cols = optarg; break;
-        case 1050: J.ordinal = true; break;
-        case 1051: ordinal_levels = optarg; ordinal_levels_given = true; break;
-        case 1052: ordinal_cutpoints = optarg; ordinal_cutpoints_given = true; break;
-        case 1053: ordinal_step = optarg; J.ord_step_given = true; break;
-        case 1040: tensor_file = optarg; tensor_given = true; break;
-        case 1041: tensor_test = optarg; tensor_test_given = true; break;
-        case 1042: tensor_dims = optarg; tensor_dims_given = true; break;
-        case 1060: implicit_w0 = optarg; J.implicit = true; break;
+        case 1050: training("--ordinal"); J.ordinal = true; break;
+        case 1051: training("--ordinal-levels"); ordinal_levels = optarg; ordinal_levels_given = true; break;
+        case 1052: training("--ordinal-cutpoints"); ordinal_cutpoints = optarg; ordinal_cutpoints_given = true; break;
+        case 1053: training("--ordinal-step"); ordinal_step = optarg; J.ord_step_given = true; break;
+        case 1040: training("--tensor"); tensor_file = optarg; tensor_given = true; break;
+        case 1041: training("--tensor-test"); tensor_test = optarg; tensor_test_given = true; break;
+        case 1042: training("--tensor-dims"); tensor_dims = optarg; tensor_dims_given = true; break;
+        case 1060: training("--implicit"); implicit_w0 = optarg; J.implicit = true; break;
         case 1061: rank_eval_n = optarg; rank_eval_given = true; break;
         case 1062: rank_by = optarg; rank_by_given = true; break;
         case 1063: rank_threshold = optarg; J.rank_thr_given = true; break;
-        case 'i': J.nsims = atoi(optarg); break;
-        case 'b': J.burnin = atoi(optarg); break;
-        case 'f': J.update_freq = atoi(optarg); break;
-        case 't': J.nthrds = atoi(optarg); break;
+        case 1070: J.save_model = optarg; save_model_given = true; break;
+        case 1071: model_dir = optarg; model_given = true; break;
+        case 1072: predict_file = optarg; predict_given = true; break;
+        case 1073: predict_threshold = optarg; predict_threshold_given = true; break;
+        case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
+        case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
+        case 'f': training("-f"); J.update_freq = atoi(optarg); break;
+        case 't': training("-t"); J.nthrds = atoi(optarg); break;
         case 'a': J.alpha = atof(optarg); alpha_given = true; break;
-        case 'd': K = atoi(optarg); break;
-        case 'g': ngpu = atoi(optarg); break;
+        case 'd': K = atoi(optarg); d_given = true; break;
+        case 'g': ngpu = atoi(optarg); g_given = true; break;
         case 'n': fname = optarg; break;
         case 'p': probename = optarg; break;
         case 'o': J.odirname = optarg; break;
-        case 'm': mname = optarg; break;
-        case 'l': lname = optarg; break;
-        case 'r': J.redirect = true; break;
-        case 'k': balance = false; break;
-        case 'v': J.verbose = true; break;
+        case 'm': training("-m"); mname = optarg; break;
+        case 'l': training("-l"); lname = optarg; break;
+        case 'r': training("-r"); J.redirect = true; break;
+        case 'k': training("-k"); balance = false; break;
+        case 'v': training("-v"); J.verbose = true; break;
         default: usage(); return 1;
         }
+    }
+    // --model / --predict / --save-model: refused before anything touches a GPU
+    if (predict_given && !model_given) die("--predict needs --model DIR (cells are predicted from a saved model)");
+    if (predict_threshold_given && !predict_given) die("--predict-threshold needs --predict FILE");
+    double predict_thr = 0.0;
+    if (predict_threshold_given) {
+        char *e = nullptr;
+        predict_thr = strtod(predict_threshold.c_str(), &e);
+        if (e == predict_threshold.c_str() || *e != '\0' || !std::isfinite(predict_thr)) die("--predict-threshold expects a finite number, not '" + predict_threshold + "'");
+    }
+    if (model_given) {
+        if (model_dir.empty()) die("--model expects a directory");
+        if (save_model_given) die("--model does not go together with --save-model (no chain runs)");
+        if (nsims_given || burnin_given) die(std::string("--model does not go together with ") + (nsims_given ? "-i" : "-b") + " (no chain runs)");
+        if (alpha_given) die("--model does not go together with -a (the model has its alpha)");
+        if (g_given || ngpu >= 1) die("--model runs on one GPU without -g");
+        if (!training_flag.empty()) die("--model does not go together with " + training_flag + " (no chain runs; the likelihood is the model's)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--model does not go together with BPMF_REDUCE=1");
+        if (predict_given && predict_file.empty()) die("--predict expects a file");
+        if (J.topn > 0 && fname.empty()) die("--topn with --model needs -n TRAIN (the rated cells are what the lists exclude)");
+        if (rank_eval_given && fname.empty()) die("--rank-eval with --model needs -n TRAIN (the rated cells are what the ranks exclude)");
+        if (rank_eval_given && probename.empty()) die("--rank-eval with --model needs -p TEST (the held-out cells)");
+        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty())
+            die("--model: nothing to do (--predict FILE, --topn N, --rank-eval N, --fold-in-rows FILE or --fold-in-cols FILE)");
+        if (J.odirname.empty()) die("--model needs -o DIR (the results go to files in DIR)");
+    }
+    if (save_model_given) {
+        if (J.save_model.empty()) die("--save-model expects a directory");
+        if (tensor_given) die("--save-model does not go together with --tensor (model format 1 stores two sides)");
+        if (g_given || ngpu >= 1) die("--save-model runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample rings of a sharded side are not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--save-model does not go together with BPMF_REDUCE=1");
+        if (J.ordinal) die("--save-model does not go together with --ordinal (model format 1 does not store the cutpoints)");
+        if (J.implicit) die("--save-model does not go together with --implicit (model format 1 does not store the Gram matrix)");
+        if (!row_features.empty() || !col_features.empty()) die("--save-model does not go together with --row-features / --col-features (model format 1 does not store the link matrix per sample)");
+        if (!mname.empty() || !lname.empty()) die("--save-model does not go together with a propagated posterior (-m / -l)");
+        if (J.nsims <= J.burnin) die("--save-model needs at least one post-burn-in sample (-i > -b)");
     }
     // --tensor: refused before anything touches a GPU, then a loop of its own (run_tensor)
     if ((tensor_test_given || tensor_dims_given) && !tensor_given) die(std::string(tensor_test_given ? "--tensor-test" : "--tensor-dims") + " needs --tensor FILE.tns");
@@ -1167,7 +1530,7 @@ int main(int argc, char *argv[])
         if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--tensor needs a noise precision -a F > 0");
         return run_tensor(tensor_file, tensor_test, tensor_dims, tensor_dims_given, K, J.nsims, J.burnin, J.alpha, J.odirname);
     }
-    if (fname.empty() || probename.empty()) { usage(); return 1; }
+    if (!model_given && (fname.empty() || probename.empty())) { usage(); return 1; }
     // --topn: checked before anything touches a GPU
     if (topn_by != "rows" && topn_by != "cols") die("--topn-by expects rows or cols, not '" + topn_by + "'");
     J.topn_by_cols = topn_by == "cols";
@@ -1458,6 +1821,8 @@ int main(int argc, char *argv[])
         if (topn_score != "mean") die(w + " does not go together with --topn-score " + topn_score + " (its lists are ranked by the mean)");
         if (!sparse_file(name)) die(w + ": " + name + " is not a sparse matrix file (.sdm, .sbm or a coordinate .mtx)");
     }
+    if (model_given)
+        return run_model(J, model_dir, fname, probename, predict_file, predict_threshold_given, predict_thr, fold_in_rows, fold_in_cols, d_given, K);
     // fp64 like the reference (c++/bpmf.h:55-58) for every num_latent; the fp32 large-K path only when asked for
     J.K = K;
     J.dtype = fp32 ? BPMF_HIP_F32 : BPMF_HIP_F64;
@@ -1622,32 +1987,8 @@ int main(int argc, char *argv[])
     read_new(new_row_features, sparse_u, sparse_u ? J.sfeat_u_d : J.feat_u.ncols, nmovies, "new-row-features", "row-features", J.new_u);
     read_new(new_col_features, sparse_m, sparse_m ? J.sfeat_m_d : J.feat_m.ncols, nusers, "new-col-features", "col-features", J.new_m);
 
-    // the ratings of the entities to fold in: new users x movies / users x new movies; every cell once, finite; stored by new entity
-    auto read_fold = [&](const std::string &name, bool rows, Job::NewRows &N) {
-        if (name.empty()) return;
-        const std::string w = rows ? "--fold-in-rows" : "--fold-in-cols";
-        const int64_t nother = rows ? nmovies : nusers;
-        Csc F;
-        try { F = bpmf::io::read_sparse(name); } catch (const std::exception &e) { die(e.what()); }
-        if ((rows ? F.ncols : F.nrows) != nother)
-            die(w + ": " + name + " is " + std::to_string(F.nrows) + " x " + std::to_string(F.ncols) + ", the training matrix has " + std::to_string(nother) +
-                (rows ? " columns" : " rows"));
-        const int64_t n = rows ? F.nrows : F.ncols;
-        if (n < 1) die(w + ": " + name + (rows ? " has no rows" : " has no columns"));
-        if (F.dup_row >= 0)
-            die(w + ": " + name + " lists cell (" + std::to_string((long long)F.dup_row + 1) + ", " + std::to_string((long long)F.dup_col + 1) + ") twice");
-        for (double v : F.vals) if (!std::isfinite(v)) die(w + ": " + name + " holds a value that is not finite");
-        N.n = n;
-        if (n > ((int64_t)1 << 28) / std::max<int64_t>(nother, 1)) {
-            const std::string cells = std::to_string(n) + " x " + std::to_string(nother) + " predictions are more than 2^28 cells per file";
-            if (J.topn < 1) die(w + ": " + cells + ": ask for the best N of every query with --topn N instead");
-            std::cerr << w << ": " << cells << ": the dense mean / std files are skipped, the --topn lists are written" << std::endl;
-            N.dense_out = false;
-        }
-        N.Fr = rows ? bpmf::io::transpose(F) : F;                     // column i = new entity i, its row ids ascending
-    };
-    read_fold(fold_in_rows, true, J.fold_u);
-    read_fold(fold_in_cols, false, J.fold_m);
+    read_fold(J, fold_in_rows, true, J.fold_u);
+    read_fold(J, fold_in_cols, false, J.fold_m);
 
     // Sys::add_prop_posterior (c++/sample.cpp:157-174): "mu_file,lambda_file"; K x N and K*K x N dense matrices
     auto read_prop = [&](const std::string &fnames, int64_t n, const char *what, Dense &mu, Dense &lambda) {
@@ -1727,18 +2068,7 @@ int main(int argc, char *argv[])
         if (J.w_m.empty()) { J.w_m.assign(1, 1.0); J.w_u.assign(1, 1.0); }
     }
     J.Tt = bpmf::io::transpose(J.T);
-    if (J.rank_eval > 0) {                                           // the held-out candidates of every query, ascending (the run's numbering)
-        const Csc &Q = J.rank_by_cols ? J.T : J.Tt;                  // one column per query
-        J.rank_tptr.assign((size_t)Q.ncols + 1, 0);
-        for (int64_t q = 0; q < Q.ncols; ++q) {
-            std::vector<int32_t> c;
-            for (int64_t p = Q.colptr[(size_t)q]; p < Q.colptr[(size_t)q + 1]; ++p)
-                if (!J.rank_thr_given || Q.vals[(size_t)p] > J.rank_thr) c.push_back(Q.rowidx[(size_t)p]);
-            std::sort(c.begin(), c.end());
-            J.rank_tcand.insert(J.rank_tcand.end(), c.begin(), c.end());
-            J.rank_tptr[(size_t)q + 1] = (int64_t)J.rank_tcand.size();
-        }
-    }
+    build_rank_lists(J);
     if (J.sharded) check(bpmf_hip_comm_unique_id(J.rccl_id));      // (also loads RCCL before the rank threads start)
     if (!J.odirname.empty()) {
         J.pavg.assign(J.T.vals.size(), 0.0); J.pm2.assign(J.T.vals.size(), 0.0);
@@ -1821,90 +2151,16 @@ int main(int argc, char *argv[])
         } catch (const std::exception &e) { die(e.what()); }
     }
 
-    if (J.topn > 0) {                                                // 1-based ids in the ORIGINAL numbering, like the -o writers
-        const std::vector<int64_t> &pq = J.topn_by_cols ? J.perm_m : J.perm_u, &pc = J.topn_by_cols ? J.perm_u : J.perm_m;
-        const int64_t nq = (int64_t)(J.topn_idx.size() / (size_t)J.topn);
-        std::vector<int64_t> order((size_t)nq);                      // queries in original order
-        for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
-        if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
-        FILE *f = fopen((J.odirname + "/topn.csv").c_str(), "w");
-        if (!f) die("cannot write " + J.odirname + "/topn.csv");
-        fprintf(f, J.topn_kind < 0 ? "query,rank,candidate,mean,std\n" : "query,rank,candidate,score,mean,std\n");
-        for (int64_t q : order)
-            for (int r = 0; r < J.topn; ++r) {
-                const size_t at = (size_t)q * J.topn + r;
-                const int32_t c = J.topn_idx[at];
-                if (c < 0) break;                                      // (padding slots are not written)
-                const long long qid = (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), cid = (long long)((pc.empty() ? c : pc[(size_t)c]) + 1);
-                if (J.topn_kind < 0) fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", qid, r + 1, cid, J.topn_mean[at], J.topn_std[at]);
-                else fprintf(f, "%lld,%d,%lld,%.17g,%.17g,%.17g\n", qid, r + 1, cid, J.topn_score[at], J.topn_mean[at], J.topn_std[at]);
-            }
-        if (fclose(f) != 0) die("cannot write " + J.odirname + "/topn.csv");
-    }
+    write_topn(J);
 
-    // --rank-eval: the metrics (the arithmetic of bpmf_amd.rank_metrics), and with -o DIR the rank of every held-out entry
-    RankMetrics rkm;
-    if (J.rank_eval > 0) {
-        rkm = rank_metrics(J.rank_rank, J.rank_tptr, J.rank_ncand, J.rank_eval);
-        if (!J.odirname.empty()) {                                   // 1-based ids in the ORIGINAL numbering, the queries in their order
-            const std::vector<int64_t> &pq = J.rank_by_cols ? J.perm_m : J.perm_u, &pc = J.rank_by_cols ? J.perm_u : J.perm_m;
-            const int64_t nq = (int64_t)J.rank_tptr.size() - 1;
-            std::vector<int64_t> order((size_t)nq);
-            for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
-            if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
-            FILE *f = fopen((J.odirname + "/ranks.csv").c_str(), "w");
-            if (!f) die("cannot write " + J.odirname + "/ranks.csv");
-            fprintf(f, "query,candidate,rank,ncand\n");
-            for (int64_t q : order)
-                for (int64_t p = J.rank_tptr[(size_t)q]; p < J.rank_tptr[(size_t)q + 1]; ++p) {
-                    const int32_t c = J.rank_tcand[(size_t)p];
-                    fprintf(f, "%lld,%lld,%d,%d\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), (long long)((pc.empty() ? c : pc[(size_t)c]) + 1),
-                            J.rank_rank[(size_t)p], J.rank_ncand[(size_t)q]);
-                }
-            if (fclose(f) != 0) die("cannot write " + J.odirname + "/ranks.csv");
-        }
-    }
+    const RankMetrics rkm = write_ranks(J);
 
-    // the new entities: new x movies as it is computed; users x new = the transpose of what is computed (row-major new x users IS
-    // column-major users x new).  Lists: 1-based ids, the new entities numbered by their row in the feature file.
-    auto write_new = [&](Job::NewRows &N, bool rows, int64_t nother, const char *stem) {
-        if (N.n == 0) return;
-        const std::string base = J.odirname + "/" + stem + (rows ? "-rows" : "-cols");
-        try {
-            if (N.dense_out) {
-                for (int which = 0; which < 2; ++which) {
-                    std::vector<double> &src = which ? N.std : N.mean;
-                    Dense d;
-                    if (rows) {                                        // row-major new x movies -> column-major
-                        d.nrows = N.n; d.ncols = nother; d.data.resize(src.size());
-                        for (int64_t i = 0; i < N.n; ++i)
-                            for (int64_t c = 0; c < nother; ++c) d.data[(size_t)c * (size_t)N.n + (size_t)i] = src[(size_t)i * (size_t)nother + (size_t)c];
-                    } else { d.nrows = nother; d.ncols = N.n; d.data.swap(src); }
-                    bpmf::io::write_dense(base + (which ? "-std.ddm" : "-mean.ddm"), d);
-                }
-            }
-        } catch (const std::exception &e) { die(e.what()); }
-        if (J.topn > 0) {
-            const std::string name = base + "-topn.csv";
-            FILE *f = fopen(name.c_str(), "w");
-            if (!f) die("cannot write " + name);
-            fprintf(f, "query,rank,candidate,mean,std\n");
-            const int64_t nq = (int64_t)(N.topn_idx.size() / (size_t)J.topn);
-            for (int64_t q = 0; q < nq; ++q)
-                for (int r = 0; r < J.topn; ++r) {
-                    const size_t at = (size_t)q * J.topn + r;
-                    if (N.topn_idx[at] < 0) break;                     // (padding slots are not written)
-                    fprintf(f, "%lld,%d,%lld,%.17g,%.17g\n", (long long)(q + 1), r + 1, (long long)(N.topn_idx[at] + 1), N.topn_mean[at], N.topn_std[at]);
-                }
-            if (fclose(f) != 0) die("cannot write " + name);
-        }
-    };
-    write_new(J.new_u, true, nmovies, "new");
-    write_new(J.new_m, false, nusers, "new");
+    write_new(J, J.new_u, true, nmovies, "new");
+    write_new(J, J.new_m, false, nusers, "new");
 
     // the folded-in entities: the same layout, queries numbered by their row (column) in FILE
-    write_new(J.fold_u, true, nmovies, "foldin");
-    write_new(J.fold_m, false, nusers, "foldin");
+    write_new(J, J.fold_u, true, nmovies, "foldin");
+    write_new(J, J.fold_m, false, nusers, "foldin");
 
     if (J.lb_sampled && !J.odirname.empty()) {                       // a cell is empty where a side has no features
         FILE *f = fopen((J.odirname + "/lambda_beta.csv").c_str(), "w");

@@ -109,7 +109,10 @@ struct bpmf_link {
 
 // posterior top-N (capi_topn.hip): ring of kept samples, fp64, column c / sample s / row k at c * max * kp + s * kp + k, and the
 // sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
-struct bpmf_ring { DevBuf<double> samples; int max = 0, count = 0, kp = 0; DevBuf<int64_t> ex_ptr; DevBuf<int32_t> ex_rows; };
+struct bpmf_ring {
+    DevBuf<double> samples; int max = 0, count = 0, kp = 0; DevBuf<int64_t> ex_ptr; DevBuf<int32_t> ex_rows;
+    Event timed[2]; float cells_ms = -1.f;   // around the newest launch of k_predict_cells with the side as the queries (bpmf_hip_predict_cells_last_ms)
+};
 
 // rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as
 // exactly one of dense (n x D, row-major) / sparse; the ring of their projected factors E[i, s, :] = mu_s + beta_s^T f_i (layout

@@ -8,6 +8,7 @@
 // "File '...' not found" (:117), 6 significant digits in text output (:697-718).
 #include "io.h"
 
+#include <sys/stat.h>
 #include <zlib.h>
 
 #include <algorithm>
@@ -482,6 +483,128 @@ void write_tns(const std::string &path, const Tns &t)
     spill(path, gz, out);
 }
 
+// ---- saved models, format version 1 -----------------------------------------------------------------------------------------------
+void write_model(const std::string &dir, const Model &m)
+{
+    const size_t K = (size_t)m.K, S = (size_t)m.S, H = 1 + K + K * K;
+    if (m.K < 1 || m.S < 1 || m.rows < 1 || m.cols < 1) throw IoError("write_model: num_latent, samples, rows and cols must be >= 1");
+    if (m.U.size() != S * K * (size_t)m.rows || m.V.size() != S * K * (size_t)m.cols)
+        throw IoError("write_model: the sample matrices must be (samples x num_latent) x rows and (samples x num_latent) x cols");
+    if (m.hyper && (m.Uh.size() != H * S || m.Vh.size() != H * S))
+        throw IoError("write_model: the hyper matrices must be (1 + num_latent + num_latent^2) x samples");
+    for (const std::vector<double> *v : {&m.U, &m.V, &m.Uh, &m.Vh})
+        for (double x : *v) if (!std::isfinite(x)) throw IoError("write_model: a value is not finite");
+    if (!std::isfinite(m.mean_rating) || !std::isfinite(m.alpha) || !std::isfinite(m.probit_threshold))
+        throw IoError("write_model: mean_rating, alpha and probit_threshold must be finite");
+    if (mkdir(dir.c_str(), 0777) != 0 && errno != EEXIST) throw IoError("cannot create the directory " + dir);
+    char num[3][64];
+    snprintf(num[0], sizeof num[0], "%.17g", m.mean_rating);
+    snprintf(num[1], sizeof num[1], "%.17g", m.alpha);
+    snprintf(num[2], sizeof num[2], "%.17g", m.probit_threshold);
+    std::string t = "bpmf_model 1\n";
+    t += "num_latent " + std::to_string(m.K) + "\nrows " + std::to_string(m.rows) + "\ncols " + std::to_string(m.cols) + "\nsamples " + std::to_string(m.S) + "\n";
+    t += std::string("mean_rating ") + num[0] + "\nalpha " + num[1] + "\nlikelihood " + (m.probit ? "probit" : "gaussian") + "\nprobit_threshold " + num[2] + "\n";
+    t += std::string("dtype ") + (m.f32 ? "f32" : "f64") + "\nhyper " + (m.hyper ? "1" : "0") + "\n";
+    spill(dir + "/model.txt", false, t);
+    Dense d;
+    d.nrows = (int64_t)(S * K); d.ncols = m.rows; d.data = m.U;
+    write_dense(dir + "/U-samples.ddm", d);
+    d.ncols = m.cols; d.data = m.V;
+    write_dense(dir + "/V-samples.ddm", d);
+    if (m.hyper) {
+        d.nrows = (int64_t)H; d.ncols = m.S; d.data = m.Uh;
+        write_dense(dir + "/U-hyper.ddm", d);
+        d.data = m.Vh;
+        write_dense(dir + "/V-hyper.ddm", d);
+    }
+}
+
+Model read_model(const std::string &dir)
+{
+    const std::string txt = dir + "/model.txt";
+    std::istringstream in(slurp(txt, false));
+    Model m;
+    std::string line, like, dtype;
+    bool first = true;
+    unsigned seen = 0;
+    static const char *keys[] = {"num_latent", "rows", "cols", "samples", "mean_rating", "alpha", "likelihood", "probit_threshold", "dtype", "hyper"};
+    auto number = [&](const std::string &key, const std::string &val) {
+        char *e = nullptr;
+        const double v = strtod(val.c_str(), &e);
+        if (val.empty() || *e != '\0') throw IoError(txt + ": the value of " + key + " is not a number: '" + val + "'");
+        if (!std::isfinite(v)) throw IoError(txt + ": the value of " + key + " is not finite");
+        return v;
+    };
+    auto count = [&](const std::string &key, const std::string &val, double lo, double hi) {
+        const double v = number(key, val);
+        if (v != std::floor(v) || v < lo || v > hi) throw IoError(txt + ": " + key + " " + val + " is out of range");
+        return (int64_t)v;
+    };
+    while (std::getline(in, line)) {
+        while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+        if (line.empty()) continue;
+        const size_t sp = line.find(' ');
+        const std::string key = line.substr(0, sp), val = sp == std::string::npos ? "" : line.substr(sp + 1);
+        if (first) {
+            if (key != "bpmf_model") throw IoError(txt + ": not a saved model (the first line must be 'bpmf_model 1')");
+            if (val != "1") throw IoError(txt + ": unknown format version '" + val + "' (this build reads version 1)");
+            first = false;
+            continue;
+        }
+        size_t k = 0;
+        while (k < 10 && key != keys[k]) ++k;
+        if (k == 10) throw IoError(txt + ": unknown key '" + key + "'");
+        seen |= 1u << k;
+        switch (k) {
+        case 0: m.K = (int)count(key, val, 1, 128); break;
+        case 1: m.rows = count(key, val, 1, 2147483647.0); break;
+        case 2: m.cols = count(key, val, 1, 2147483647.0); break;
+        case 3: m.S = (int)count(key, val, 1, 2147483647.0); break;
+        case 4: m.mean_rating = number(key, val); break;
+        case 5: m.alpha = number(key, val); break;
+        case 6: like = val; break;
+        case 7: m.probit_threshold = number(key, val); break;
+        case 8: dtype = val; break;
+        default: m.hyper = count(key, val, 0, 1) != 0; break;
+        }
+    }
+    if (first) throw IoError(txt + ": not a saved model (the first line must be 'bpmf_model 1')");
+    for (size_t k = 0; k < 10; ++k)
+        if (!(seen >> k & 1u)) throw IoError(txt + ": the key '" + keys[k] + "' is missing");
+    if (like != "gaussian" && like != "probit") throw IoError(txt + ": likelihood '" + like + "' is not gaussian or probit");
+    if (dtype != "f64" && dtype != "f32") throw IoError(txt + ": dtype '" + dtype + "' is not f64 or f32");
+    m.probit = like == "probit"; m.f32 = dtype == "f32";
+    const int64_t K = m.K, S = m.S, H = 1 + K + K * K;
+    auto load = [&](const char *name, int64_t ncols, bool hyper, std::vector<double> &out) {
+        const std::string path = dir + "/" + name;
+        Dense d;
+        try { d = read_dense(path); }
+        catch (const IoError &e) {
+            const std::string what = e.what();
+            throw IoError(what.find(path) != std::string::npos ? what : path + ": " + what);
+        }
+        if (hyper) {
+            if (d.nrows != H) throw IoError(path + ": " + std::to_string(d.nrows) + " rows, not 1 + num_latent + num_latent^2 = " + std::to_string(H));
+            if (d.ncols != S) throw IoError(path + ": holds " + std::to_string(d.ncols) + " samples, " + txt + " says " + std::to_string(S));
+        } else {
+            if (d.nrows % K != 0) throw IoError(path + ": " + std::to_string(d.nrows) + " rows are not samples x num_latent (num_latent " + std::to_string(K) + ")");
+            if (d.nrows / K != S) throw IoError(path + ": holds " + std::to_string(d.nrows / K) + " samples, " + txt + " says " + std::to_string(S));
+            if (d.ncols != ncols) throw IoError(path + ": " + std::to_string(d.ncols) + " columns, " + txt + " says " + std::to_string(ncols));
+        }
+        for (size_t i = 0; i < d.data.size(); ++i)
+            if (!std::isfinite(d.data[i]))
+                throw IoError(path + ": the value of row " + std::to_string(i % (size_t)d.nrows + 1) + ", column " + std::to_string(i / (size_t)d.nrows + 1) + " is not finite");
+        out.swap(d.data);
+    };
+    load("U-samples.ddm", m.rows, false, m.U);
+    load("V-samples.ddm", m.cols, false, m.V);
+    if (m.hyper) {
+        load("U-hyper.ddm", S, true, m.Uh);
+        load("V-hyper.ddm", S, true, m.Vh);
+    }
+    return m;
+}
+
 }  // namespace io
 }  // namespace bpmf
 
@@ -565,5 +688,32 @@ extern "C" int bpmf_io_write_tns(const char *path, int64_t nnz, const int32_t *i
         for (int m = 0; m < 3; ++m) t.idx[m].assign(idx[m], idx[m] + nnz);
         t.vals.assign(vals, vals + nnz);
         bpmf::io::write_tns(path, t);
+    });
+}
+
+extern "C" int bpmf_io_write_model(const char *dir, int num_latent, int64_t rows, int64_t cols, int samples, double mean_rating, double alpha,
+                                   int probit, double probit_threshold, int f32, const double *U, const double *V, const double *Uh, const double *Vh)
+{
+    return guarded([&] {
+        if (num_latent < 1 || samples < 1 || rows < 1 || cols < 1 || !U || !V || ((Uh == nullptr) != (Vh == nullptr)))
+            throw bpmf::io::IoError("write_model: bad argument");
+        bpmf::io::Model m;
+        m.K = num_latent; m.S = samples; m.rows = rows; m.cols = cols; m.mean_rating = mean_rating; m.alpha = alpha;
+        m.probit = probit != 0; m.probit_threshold = probit_threshold; m.f32 = f32 != 0; m.hyper = Uh != nullptr;
+        const size_t sk = (size_t)samples * (size_t)num_latent, h = (1 + (size_t)num_latent + (size_t)num_latent * num_latent) * (size_t)samples;
+        m.U.assign(U, U + sk * (size_t)rows); m.V.assign(V, V + sk * (size_t)cols);
+        if (m.hyper) { m.Uh.assign(Uh, Uh + h); m.Vh.assign(Vh, Vh + h); }
+        bpmf::io::write_model(dir, m);
+    });
+}
+
+extern "C" int bpmf_io_read_model(const char *dir, int64_t *ints, double *reals, double **U, double **V, double **Uh, double **Vh)
+{
+    return guarded([&] {
+        const bpmf::io::Model m = bpmf::io::read_model(dir);
+        ints[0] = m.K; ints[1] = m.rows; ints[2] = m.cols; ints[3] = m.S; ints[4] = m.probit; ints[5] = m.f32; ints[6] = m.hyper;
+        reals[0] = m.mean_rating; reals[1] = m.alpha; reals[2] = m.probit_threshold;
+        *U = dup(m.U); *V = dup(m.V);
+        *Uh = m.hyper ? dup(m.Uh) : nullptr; *Vh = m.hyper ? dup(m.Vh) : nullptr;
     });
 }

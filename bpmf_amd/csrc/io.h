@@ -55,5 +55,21 @@ struct Tns {
 Tns read_tns(const std::string &path);
 void write_tns(const std::string &path, const Tns &t);      // values as %.17g: a round trip is exact
 
+// a saved model, format version 1: a directory with model.txt (`key value` lines, numbers as %.17g),
+// U-samples.ddm ((S K) x rows) and V-samples.ddm ((S K) x cols) -- column c holds sample 0's K values, then sample 1's ..., the
+// layout of bpmf_hip_side_samples_get -- and, with hyper, U-hyper.ddm and V-hyper.ddm ((1 + K + K^2) x S: column s holds alpha_s,
+// mu_s, Lambda_s as bpmf_hip_side_hyper_get gives them).  Everything in the numbering of the input files.
+struct Model {
+    int K = 0, S = 0;
+    int64_t rows = 0, cols = 0;                  // users, movies
+    double mean_rating = 0.0, alpha = 0.0, probit_threshold = 0.0;
+    bool probit = false, f32 = false, hyper = false;
+    std::vector<double> U, V, Uh, Vh;            // the four matrices, column-major (Uh, Vh empty without hyper)
+};
+void write_model(const std::string &dir, const Model &m);        // creates dir when it is missing
+// refuses (IoError, one line naming the file and the reason): an unknown version, a missing file or key, a row count that is not
+// S K (1 + K + K^2), a column count that is not rows / cols (S), a value that is not finite
+Model read_model(const std::string &dir);
+
 }  // namespace io
 }  // namespace bpmf

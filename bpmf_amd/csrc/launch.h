@@ -191,6 +191,22 @@ struct FoldinLaunch {
 int foldin_chunk();                                        // ratings staged per pass (kFoldinChunk)
 int foldin(const FoldinLaunch &p, hipStream_t st);         // -1: shape not supported (nothing launched)
 
+// predictions for a list of cells from two sample rings; the repacking of a ring for its read-back and load (kernels_predcells.h, kpredcells.hip)
+struct PredCellsLaunch {
+    const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column
+    int Kp, S; double mean_rating;
+    int want_prob; double t, sigma;                        // prob = (1/S) sum Phi((p_s - t) / sigma); sigma < DBL_MIN: the counting form
+    int64_t nseg;                                          // workgroups: runs of cells of one query, at most predict_cells_segment(Kp) each
+    const int32_t *seg_q, *seg_beg, *seg_cnt;              // per segment: the query, its first cell in the sorted list, its cells
+    const int32_t *cand, *orig;                            // per sorted cell: the candidate, the place in the caller's list
+    double *mean, *std, *prob;                             // caller's order, on the device; prob NULL without want_prob
+};
+int predict_cells_segment(int Kp);
+int predict_cells(const PredCellsLaunch &p, hipStream_t st);   // -1: shape not supported (nothing launched)
+// packed (nc x n x Kt doubles) <- slots [s_from, s_from + n) of columns [c_from, c_from + nc) of a ring; and packed -> slots [0, n), pad rows zero
+void samples_pack(const double *ring, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int s_from, int n, double *packed, hipStream_t st);
+void samples_unpack(const double *packed, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int n, double *ring, hipStream_t st);
+
 // training residuals for the adaptive noise precision (kernels_noise.h, knoise.hip)
 struct SseLaunch {
     const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)

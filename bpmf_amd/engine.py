@@ -264,6 +264,46 @@ class HipEngine:
     def samples_count(self, side):
         return int(self.lib.bpmf_hip_side_samples_count(side.handle))
 
+    def samples_get(self, side, s_from=0, s_to=None):
+        """Slots s_from .. s_to - 1 of the side's sample ring, [ncols, s_to - s_from, K] (the pad rows of the ring are left out): what
+        a saved model stores per side."""
+        s_to = self.samples_count(side) if s_to is None else int(s_to)
+        out = np.empty((side.ncols, max(0, s_to - int(s_from)), self.K))
+        _lib.check(self.lib.bpmf_hip_side_samples_get(side.handle, int(s_from), s_to, _ptr(out)))
+        return out
+
+    def samples_set(self, side, samples):
+        """The inverse of samples_get: samples [ncols, S, K] become slots 0 .. S - 1 of the side's ring (reserved with max_samples >= S),
+        which then counts S.  A value that is not finite is refused with its column and sample."""
+        samples = np.ascontiguousarray(samples, np.float64)
+        if samples.ndim != 3 or samples.shape[0] != side.ncols or samples.shape[2] != self.K:
+            raise ValueError("samples_set: samples must be [%d, S, %d], not %s" % (side.ncols, self.K, samples.shape))
+        _lib.check(self.lib.bpmf_hip_side_samples_set(side.handle, samples.shape[1], _ptr(samples)))
+
+    def predict_cells(self, query, cand, mean_rating, q, c, threshold=None, sigma=0.0):
+        """(mean, std) or, with a threshold t, (mean, std, prob) of the cells (q[i], c[i]) -- column q[i] of `query` against column c[i]
+        of `cand` -- over the samples of the two rings: mean and std as topn defines them (std leaves 1 / alpha
+        out), prob = the mean over the samples of Phi((p_s - t) / sigma) (sigma = 0: the share of samples with p_s > t).  Any order,
+        repeats allowed, an empty list allowed; an index out of range is refused naming the cell.  The bits of a cell do not depend on
+        the other cells or on its place in the list."""
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32)
+        if q.ndim != 1 or q.shape != c.shape:
+            raise ValueError("predict_cells: q and c must be one-dimensional and of the same length")
+        n = len(q)
+        mean = np.empty(n); std = np.empty(n); prob = np.empty(n) if threshold is not None else None
+        hold = np.zeros(1, np.int32)
+        _lib.check(self.lib.bpmf_hip_predict_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
+                                                   0 if threshold is None else 1, 0.0 if threshold is None else float(threshold), float(sigma),
+                                                   _ptr(mean if n else np.zeros(1)), _ptr(std if n else np.zeros(1)),
+                                                   _ptr(prob if n or prob is None else np.zeros(1))))
+        return (mean, std) if threshold is None else (mean, std, prob)
+
+    def predict_cells_last_ms(self, query):
+        """Device time of the newest launch of the cell kernel with `query` as the queries, between two events (tools/model_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_predict_cells_last_ms(query.handle, C.byref(ms)))
+        return ms.value
+
     def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
         """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
         (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""

@@ -1,0 +1,153 @@
+"""Saved models: the kept samples of a run as a directory, written after training and loaded into another
+process that serves top-N lists, ranked evaluation, blocks, fold-in and single cells without a chain.
+
+Format version 1 (written and read by the library: include/bpmf_io.h) -- everything in the numbering of the input:
+    model.txt        key value lines: bpmf_model 1, num_latent, rows, cols, samples, mean_rating, alpha, likelihood gaussian|probit,
+                     probit_threshold, dtype, hyper 0|1
+    U-samples.ddm    (S K) x rows,  V-samples.ddm  (S K) x cols: column c = sample 0's K values, then sample 1's, ...
+    U-hyper.ddm      (1 + K + K^2) x S, and V-hyper.ddm, with hyper 1: column s = alpha_s, mu_s, Lambda_s (column-major)
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from .io import BpmfIoError
+
+
+def write_model(path, model):
+    """Writes the dict `model` as a model directory: num_latent, rows, cols, samples, mean_rating, alpha, probit (bool),
+    probit_threshold, dtype ("f64" | "f32"), U [rows, S, K], V [cols, S, K] and, for hyper 1, U_hyper = (alpha [S], mu [S, K],
+    Lambda [S, K, K]) and V_hyper; U_hyper = V_hyper = None writes hyper 0."""
+    lib = _lib.load_library()
+    K, S, rows, cols = int(model["num_latent"]), int(model["samples"]), int(model["rows"]), int(model["cols"])
+    U = np.ascontiguousarray(model["U"], np.float64); V = np.ascontiguousarray(model["V"], np.float64)
+    if U.shape != (rows, S, K) or V.shape != (cols, S, K):
+        raise ValueError("write_model: U must be [%d, %d, %d] and V [%d, %d, %d]" % (rows, S, K, cols, S, K))
+    hyp = []
+    for key in ("U_hyper", "V_hyper"):
+        h = model.get(key)
+        if h is None:
+            hyp.append(None)
+            continue
+        alpha, mu, lam = (np.asarray(a, np.float64) for a in h)
+        if alpha.shape != (S,) or mu.shape != (S, K) or lam.shape != (S, K, K):
+            raise ValueError("write_model: %s must be (alpha [%d], mu [%d, %d], Lambda [%d, %d, %d])" % (key, S, S, K, S, K, K))
+        # one column per sample: alpha, mu, Lambda column-major
+        hyp.append(np.ascontiguousarray(np.concatenate([alpha[:, None], mu, np.transpose(lam, (0, 2, 1)).reshape(S, K * K)], axis=1)))
+    if (hyp[0] is None) != (hyp[1] is None):
+        raise ValueError("write_model: U_hyper and V_hyper are given together or not at all")
+    rc = lib.bpmf_io_write_model(str(path).encode(), K, rows, cols, S, float(model["mean_rating"]), float(model["alpha"]),
+                                 1 if model.get("probit") else 0, float(model.get("probit_threshold", 0.0)),
+                                 1 if model.get("dtype", "f64") == "f32" else 0, U.ctypes.data, V.ctypes.data,
+                                 hyp[0].ctypes.data if hyp[0] is not None else None, hyp[1].ctypes.data if hyp[1] is not None else None)
+    if rc:
+        raise BpmfIoError(lib.bpmf_io_last_error().decode("utf-8", "replace"))
+
+
+def read_model(path):
+    """The dict write_model takes, from a model directory.  Refused with BpmfIoError in one line that names the file and the reason: an
+    unknown version, a missing file, a row count that is not S K, unequal S between the files, a value that is not finite."""
+    lib = _lib.load_library()
+    ints = np.zeros(7, np.int64); reals = np.zeros(3)
+    ptr = [_lib.c_f64p() for _ in range(4)]
+    rc = lib.bpmf_io_read_model(str(path).encode(), ints.ctypes.data, reals.ctypes.data, *[C.byref(p) for p in ptr])
+    if rc:
+        raise BpmfIoError(lib.bpmf_io_last_error().decode("utf-8", "replace"))
+    K, rows, cols, S, probit, f32, hyper = (int(v) for v in ints)
+    try:
+        U = np.ctypeslib.as_array(ptr[0], shape=(rows, S, K)).copy()
+        V = np.ctypeslib.as_array(ptr[1], shape=(cols, S, K)).copy()
+        hyp = [None, None]
+        if hyper:
+            for i in (0, 1):
+                h = np.ctypeslib.as_array(ptr[2 + i], shape=(S, 1 + K + K * K)).copy()
+                hyp[i] = (h[:, 0].copy(), h[:, 1:1 + K].copy(), np.ascontiguousarray(np.transpose(h[:, 1 + K:].reshape(S, K, K), (0, 2, 1))))
+    finally:
+        for p in ptr:
+            if p:
+                lib.bpmf_io_free(p)
+    return dict(num_latent=K, rows=rows, cols=cols, samples=S, mean_rating=float(reals[0]), alpha=float(reals[1]), probit=bool(probit),
+                probit_threshold=float(reals[2]), dtype="f32" if f32 else "f64", U=U, V=V, U_hyper=hyp[0], V_hyper=hyp[1])
+
+
+def save_model(res, path):
+    """Writes the kept samples of the run `res` = gibbs(...) as a model directory.  The run must have kept the sample rings of both
+    sides (save_model=, topn=, foldin= or rank_eval=); the hyper-parameters are stored when both sides kept theirs (save_model= of a
+    Gaussian run, foldin=True without features).  The engine of the run must still be open."""
+    if not isinstance(res, dict) or "users" not in res or "movies" not in res:
+        raise ValueError("save_model needs the result of gibbs(...)")
+    users, movies = res["users"], res["movies"]
+    info = res.get("model_info")
+    if info is None:
+        raise ValueError("save_model: the result carries no model_info (it comes from gibbs or load_model)")
+    if not info.get("plain", True):
+        raise ValueError("save_model: %s" % info["why"])
+    engine = users.engine
+    S = engine.samples_count(users.side)
+    if S < 1 or engine.samples_count(movies.side) != S:
+        raise ValueError("save_model: the run kept no samples of both sides (gibbs(save_model=DIR), or topn / foldin / rank_eval)")
+    hyper = engine.hyper_count(users.side) == S and engine.hyper_count(movies.side) == S
+    write_model(path, dict(num_latent=engine.K, rows=users.num(), cols=movies.num(), samples=S, mean_rating=movies.mean_rating,
+                           alpha=info["alpha"], probit=info["probit"], probit_threshold=info["probit_threshold"],
+                           dtype=getattr(engine, "dtype", "f64"), U=engine.samples_get(users.side), V=engine.samples_get(movies.side),
+                           U_hyper=engine.hyper_get(users.side) if hyper else None, V_hyper=engine.hyper_get(movies.side) if hyper else None))
+
+
+def load_model(engine, path, M=None):
+    """Loads a model directory into `engine` (its num_latent must be the model's) and returns a dict with "users", "movies" and
+    "foldin" like gibbs's result: bpmf_amd.fold_in, engine.topn, topn_scored, rank_eval, predict_block and bpmf_amd.predict_cells
+    work on it unchanged, with res["movies"].mean_rating as the mean rating.  M: the training matrix as gibbs takes it (CSC, one
+    column per movie), whose cells the rankings exclude; None: no cell is excluded.  No chain runs."""
+    from scipy import sparse as sp
+    from .sys import Sys
+    m = read_model(path)
+    if engine.K != m["num_latent"]:
+        raise ValueError("load_model: the engine has num_latent %d, the model %d" % (engine.K, m["num_latent"]))
+    rows, cols, S = m["rows"], m["cols"], m["samples"]
+    if M is None:
+        M = (np.zeros(cols + 1, np.int64), np.zeros(0, np.int32), np.zeros(0))
+    M = (np.ascontiguousarray(M[0], np.int64), np.ascontiguousarray(M[1], np.int32), np.ascontiguousarray(M[2], np.float64))
+    if len(M[0]) != cols + 1 or (len(M[1]) and int(M[1].max()) >= rows):
+        raise ValueError("load_model: the training matrix does not have the model's shape %d x %d" % (rows, cols))
+    A = sp.csc_matrix((M[2], M[1], M[0]), shape=(rows, cols))
+    At = A.T.tocsc(); At.sort_indices()
+    Mt = (At.indptr.astype(np.int64), At.indices.astype(np.int32), At.data.astype(np.float64))
+    movies = Sys("movs", engine, M, cols, rows, mean_rating=m["mean_rating"])
+    users = Sys("users", engine, Mt, rows, cols, mean_rating=m["mean_rating"])
+    for sd, key in ((users, "U"), (movies, "V")):
+        engine.samples_reserve(sd.side, S)
+        engine.samples_set(sd.side, m[key])
+    foldin = m["U_hyper"] is not None and not m["probit"]
+    if foldin:
+        for sd, key in ((users, "U_hyper"), (movies, "V_hyper")):
+            alpha, mu, lam = m[key]
+            engine.hyper_reserve(sd.side, S)
+            for s in range(S):
+                engine.hyper_add(sd.side, alpha[s], mu[s], lam[s])
+    info = dict(alpha=m["alpha"], probit=m["probit"], probit_threshold=m["probit_threshold"], plain=True, dtype=m["dtype"], samples=S)
+    return dict(users=users, movies=movies, foldin=foldin, model_info=info)
+
+
+def predict_cells(res, rows, cols, threshold=None):
+    """Predictions for the cells (rows[i], cols[i]) -- user, movie, 0-based -- from the kept samples of `res` (gibbs with the rings kept,
+    or load_model): dict(mean, std), [n] each, std without the observation noise 1 / alpha.  threshold=t adds "prob", the posterior
+    probability that a rating exceeds t with sigma = 1 / sqrt(alpha); a probit model always has it, with t = 0 unless given and
+    sigma = 1 (the probability of a positive label)."""
+    users, movies = res["users"], res["movies"]
+    info = res.get("model_info") or {}
+    probit = bool(info.get("probit"))
+    if threshold is None and probit:
+        threshold = 0.0
+    if threshold is not None:
+        if not math.isfinite(float(threshold)):
+            raise ValueError("predict_cells: the threshold must be finite")
+        alpha = float(info.get("alpha", float("nan")))
+        if not probit and not (alpha > 0 and math.isfinite(alpha)):
+            raise ValueError("predict_cells: the threshold needs the alpha of the run (sigma = 1 / sqrt(alpha))")
+        sigma = 1.0 if probit else 1.0 / math.sqrt(alpha)
+        mean, std, prob = users.engine.predict_cells(users.side, movies.side, movies.mean_rating, rows, cols, float(threshold), sigma)
+        return dict(mean=mean, std=std, prob=prob)
+    mean, std = users.engine.predict_cells(users.side, movies.side, movies.mean_rating, rows, cols)
+    return dict(mean=mean, std=std)

@@ -196,7 +196,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
-          ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None):
+          ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -334,7 +334,21 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     under implicit); engine.rank_eval gives each its rank among the candidates its query has not rated in M, by topn's score.
     res["rank"] = bpmf_amd.rank_metrics(...) at N (recall, ndcg, mrr, mpr, auc, queries, entries) plus n = N, by, rank = the
     rank per test cell in T's order (0 for a cell the threshold left out) and ncand = the candidates left per query.  A test cell
-    that is also a training cell is refused.  Works with every likelihood topn works with.  None (the default): nothing changes."""
+    that is also a training cell is refused.  Works with every likelihood topn works with.  None (the default): nothing changes.
+
+    save_model=DIR: the run keeps the sample rings of both sides and, unless probit=True, the hyper-parameters of both sides (as
+    topn and foldin=True do), and writes them as a model directory after the chain (bpmf_amd.save_model): what
+    bpmf_amd.load_model and `bpmf --model DIR` serve top-N lists, ranked evaluation, blocks, fold-in and single cells from without a
+    chain.  Needs nsims > burnin.  Goes with plain Gaussian runs, any alpha, weights, robust, censored, probit=True, noise="adaptive"
+    and an fp32 engine; refused with ordinal, implicit and features (serving them would need state the format does not store).
+    None (the default): nothing changes."""
+    if save_model is not None:                       # (refused before the engine is used)
+        for on, what in ((ordinal is not None and ordinal is not False, "ordinal"), (implicit is not None, "implicit"),
+                         (row_features is not None or col_features is not None, "row_features / col_features")):
+            if on:
+                raise ValueError("save_model does not go together with %s (serving it would need state that model format 1 does not store)" % what)
+        if nsims - burnin < 1:
+            raise ValueError("save_model needs at least one post-burn-in sample (nsims > burnin)")
     if implicit is not None:                         # (refused before the engine is used)
         try:
             implicit = float(implicit)
@@ -588,9 +602,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None
-    hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if foldin and F is None]
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None
+    hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
     if ring_movies:
@@ -782,6 +796,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if foldin:
         res["foldin"] = True
     res["movies"], res["users"] = movies, users
+    plain = not ordinal_on and implicit is None and not linked      # what bpmf_amd.save_model can store of this run
+    res["model_info"] = dict(alpha=float(alpha), probit=bool(probit), probit_threshold=float(threshold) if probit else 0.0, plain=plain,
+                             why="ordinal, implicit and feature models are not stored by model format 1")
+    if save_model is not None:
+        from .model import save_model as _save_model
+        _save_model(res, save_model)
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res

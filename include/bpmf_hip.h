@@ -417,6 +417,29 @@ BPMF_API int bpmf_hip_foldin_topn(bpmf_hip_side *side, bpmf_hip_side *cand, doub
 BPMF_API int bpmf_hip_foldin_last_ms(const bpmf_hip_side *side, float *ms);   /* device time of the newest launch of the kernel, between two events */
 BPMF_API int bpmf_hip_foldin_chunk(void);
 
+/* ---- saved models: ring read-back and load, predictions for a list of cells ----
+ *   bpmf_hip_side_samples_get reads slots [s_from, s_to) of the side's sample ring without the pad rows:
+ * ncols x (s_to - s_from) x num_latent doubles, column c / sample s / row k at host[(c n + s) K + k], n = s_to - s_from.  It
+ * waits.  BPMF_HIP_EINVAL without a ring or for a range beyond bpmf_hip_side_samples_count.
+ * bpmf_hip_side_samples_set is the inverse: `nsamples` samples in the same layout (s_from = 0) into a ring reserved with
+ * max_samples >= nsamples; the pad rows are written as zeros (the ranking kernels rely on them); afterwards the ring counts
+ * nsamples.  A value that is not finite is refused with its column and sample, before the device is touched.
+ * Together with bpmf_hip_side_hyper_get / _hyper_reserve / _hyper_add this is all a process needs to serve bpmf_hip_topn*,
+ * _rank_eval, _predict_block and _foldin* from a model another process trained. */
+BPMF_API int bpmf_hip_side_samples_get(bpmf_hip_side *side, int s_from, int s_to, double *host);
+BPMF_API int bpmf_hip_side_samples_set(bpmf_hip_side *side, int nsamples, const double *host);
+/* For the n cells (q[i], c[i]) -- column q[i] of `query`, column c[i] of `cand`; any order, repeats allowed, n = 0 allowed --
+ * with p_s = mean_rating + u_s(q) . v_s(c) over the S >= 1 samples both rings hold: mean_out[i] and std_out[i] as bpmf_hip_topn
+ * defines them (std: 0 for S = 1; 1 / alpha is NOT included), and with want_prob prob_out[i] = (1/S) sum_s Phi((p_s - t) / sigma),
+ * the formula of BPMF_HIP_SCORE_PROB (sigma < DBL_MIN: the share of samples with p_s > t).  prob_out may be NULL without
+ * want_prob.  An index out of range is BPMF_HIP_EINVAL naming the cell, before the device is used.  The bits of a cell depend on
+ * the rings, (q, c), mean_rating, t and sigma alone: not on the other cells, its place in the list or the launch.  Works on
+ * fp32 contexts (the rings are fp64); needs both sides whole and no communicator.  Waits. */
+BPMF_API int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                    const int32_t *c, int want_prob, double t, double sigma, double *mean_out, double *std_out,
+                                    double *prob_out);
+BPMF_API int bpmf_hip_predict_cells_last_ms(const bpmf_hip_side *query, float *ms);   /* device time of the newest launch with `query` as the queries */
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout

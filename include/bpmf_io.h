@@ -44,6 +44,23 @@ BPMF_IO_API void bpmf_io_free(void *p);
 BPMF_IO_API int bpmf_io_read_tns(const char *path, int64_t *nnz, int64_t *dims, int32_t **idx0, int32_t **idx1, int32_t **idx2, double **vals);
 BPMF_IO_API int bpmf_io_write_tns(const char *path, int64_t nnz, const int32_t *idx0, const int32_t *idx1, const int32_t *idx2, const double *vals);
 
+/* Saved models, format version 1: a directory DIR that a training run writes (bpmf --save-model DIR, gibbs(save_model=DIR)) and a
+ * serving run loads (bpmf --model DIR, bpmf_amd.load_model).  Everything in the numbering of the input files.
+ *   model.txt        `key value` lines, numbers as %.17g: bpmf_model 1, num_latent, rows, cols, samples, mean_rating, alpha,
+ *                    likelihood gaussian|probit, probit_threshold, dtype f64|f32, hyper 0|1
+ *   U-samples.ddm    (samples x num_latent) x rows, V-samples.ddm the same x cols: column c holds sample 0's num_latent values, then
+ *                    sample 1's, ...: the layout of bpmf_hip_side_samples_get / _set
+ *   U-hyper.ddm      with hyper 1, and V-hyper.ddm: (1 + num_latent + num_latent^2) x samples, column s = alpha_s, mu_s, Lambda_s as
+ *                    bpmf_hip_side_hyper_get gives them
+ * _write_model: Uh = Vh = NULL writes hyper 0.  _read_model: ints[7] = num_latent, rows, cols, samples, probit, f32, hyper;
+ * reals[3] = mean_rating, alpha, probit_threshold; the four arrays are malloc'ed (Uh, Vh NULL with hyper 0).  It refuses, in one
+ * line that names the file and the reason: an unknown version, a missing file or key, a row count that is not samples x
+ * num_latent, sample counts that differ between the files, a value that is not finite. */
+BPMF_IO_API int bpmf_io_write_model(const char *dir, int num_latent, int64_t rows, int64_t cols, int samples, double mean_rating, double alpha,
+                                    int probit, double probit_threshold, int f32, const double *U, const double *V, const double *Uh,
+                                    const double *Vh);
+BPMF_IO_API int bpmf_io_read_model(const char *dir, int64_t *ints, double *reals, double **U, double **V, double **Uh, double **Vh);
+
 /* Assignment of the columns of a side to `nparts` ranks (host; bpmf_amd/csrc/assign.cpp).
  * _greedy: Sys::assign of the reference (c++/assign.cpp:52-201, default weights): least-loaded rank on work = 10 + nnz,
  *   three sweeps, then a renumbering that makes every rank's columns contiguous -- order[new] = old column, dom[p] .. dom[p+1]
