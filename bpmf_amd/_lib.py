@@ -76,6 +76,10 @@ _SIGNATURES = {
     "bpmf_hip_implicit_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double]),
     "bpmf_hip_topn_scored": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double,
                                        C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_similar": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "bpmf_hip_similar_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_similar_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bpmf_hip_predict_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "bpmf_hip_predict_block_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "bpmf_hip_side_newrows_set": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int]),

@@ -43,6 +43,10 @@
 // --save-model DIR (-i > -b; one GPU, no -g): the run keeps the sample rings of both sides and, unless --probit, both hyper rings, and
 // writes them after the chain as a model directory, format version 1 (include/bpmf_io.h): model.txt,
 // U-samples.ddm, V-samples.ddm, U-hyper.ddm, V-hyper.ddm, in the numbering of the input.  One more header line, `save-model: DIR`.
+// --similar N (with -o DIR, one GPU, no -g): the N nearest neighbours of every item (--similar-by cols, the default) or user (rows)
+// among the entities of the same side, by the posterior mean of the per-sample cosine (--similar-kind euclid: negative squared
+// distance) minus --similar-kappa times its spread, to DIR/similar-cols.csv / similar-rows.csv; entities with
+// fewer than --similar-min-ratings training ratings are not listed.  Also served from --model DIR.  stdout is the same as without it.
 // --model DIR -o OUT [-n TRAIN] [-p TEST]: no chain runs (run_model).  The model is loaded into a fp64 context and serves --predict FILE
 // [--predict-threshold F] (OUT/predict.csv: row,col,mean,std[,prob] for the cells FILE lists, 1-based, in the reader's order; prob with
 // sigma = 1 / sqrt(alpha), always there for a probit model with t = 0 unless given and sigma = 1), --topn N with its --topn-* flags and
@@ -118,8 +122,8 @@ double tick()
 void usage()
 {
     std::cout << "Usage: bpmf -n <MTX> -p <MTX> [-o DIR/] [-i N] [-b N] [-f N] [-a F] [-d K] [-krv] [-t N] [-m MTX,MTX] [-l MTX,MTX] [-g N] [--fp32] [--topn N [--topn-by rows|cols] [--topn-score mean|ucb|prob|ei] [--topn-kappa F] [--topn-threshold F]]"
-              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--implicit W0] [--rank-eval N [--rank-by rows|cols] [--rank-threshold F]] [--fold-in-rows FILE] [--fold-in-cols FILE] [--save-model DIR]\n"
-              << "   or: bpmf --model DIR -o OUT [-n <train_matrix>] [-p <test_matrix>] [--predict FILE [--predict-threshold F]] [--topn N ...] [--rank-eval N ...] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
+              << " [--noise fixed|adaptive [--alpha-prior A0,B0] [--alpha-max F]] [--probit [--probit-threshold F]] [--ordinal [--ordinal-levels a,b,..] [--ordinal-cutpoints g1,..] [--ordinal-step F]] [--censored FILE] [--weights FILE] [--robust NU] [--implicit W0] [--rank-eval N [--rank-by rows|cols] [--rank-threshold F]] [--fold-in-rows FILE] [--fold-in-cols FILE] [--save-model DIR] [--similar N [--similar-by cols|rows] [--similar-kind cosine|euclid] [--similar-kappa F] [--similar-min-ratings M]]\n"
+              << "   or: bpmf --model DIR -o OUT [-n <train_matrix>] [-p <test_matrix>] [--predict FILE [--predict-threshold F]] [--topn N ...] [--rank-eval N ...] [--similar N ...] [--fold-in-rows FILE] [--fold-in-cols FILE]\n"
               << "       bpmf --tensor <TNS> [--tensor-test <TNS>] [--tensor-dims I,J,T] [-o DIR/] [-i N] [-b N] [-a F] [-d K]\n"
               << "\n"
               << "Parameters:\n"
@@ -142,6 +146,13 @@ void usage()
               << "  [-v]: write every sample (U-<i>.ddm, V-<i>.ddm)\n"
               << "  [--topn N]: the N unrated items of every user with the highest posterior-mean prediction, with its standard\n"
               << "              deviation over the kept samples, to DIR/topn.csv (needs -o DIR; one GPU; 1 <= N <= 32)\n"
+              << "  [--similar N [--similar-by cols|rows] [--similar-kind cosine|euclid] [--similar-kappa F] [--similar-min-ratings M]]: the N\n"
+              << "              nearest neighbours of every item (cols, the default) or user (rows) among the entities of the same side, to\n"
+              << "              DIR/similar-cols.csv / similar-rows.csv (query,rank,neighbour,score,mean,std): per kept sample the cosine between\n"
+              << "              the two factor vectors (or, euclid, their negative squared distance) -- which no rotation of the latent space\n"
+              << "              changes -- then score = mean - kappa std over the samples (kappa >= 0, default 0); entities with fewer than M\n"
+              << "              training ratings are not listed (needs -o DIR and -i > -b; one GPU, no -g; 1 <= N <= 32; not with --tensor,\n"
+              << "              -m / -l or BPMF_REDUCE=1; also served from --model DIR, where --similar-min-ratings needs -n TRAIN)\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
               << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
@@ -414,6 +425,12 @@ struct Job {
     int topn_kind = -1;                                              // --topn-score: -1 mean, else BPMF_HIP_SCORE_*
     double topn_param = 0.0, topn_sigma = 0.0;                       // kappa or the threshold; the observation noise of prob / ei
     std::vector<double> topn_score;
+    int similar = 0;                                                 // --similar N (0: off): the N nearest neighbours of every column (item) or row (user)
+    bool similar_by_rows = false;                                    // --similar-by rows
+    int similar_kind = BPMF_HIP_SIM_COSINE;                          // --similar-kind cosine|euclid
+    double similar_kappa = 0.0;                                      // --similar-kappa F: score = mean - kappa std
+    long similar_min = 0;                                            // --similar-min-ratings M: entities with fewer training ratings are not listed
+    std::vector<int32_t> sim_idx; std::vector<double> sim_score, sim_mean, sim_std;   // queries x N, in the numbering of the run
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
@@ -510,6 +527,52 @@ void serve_rank(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies)
         J.rank_rank.resize(J.rank_tcand.size());
         std::cerr << "rank-eval: " << J.rank_tcand.size() << " held-out entries of " << nq << " queries, " << (tick() - t0) * 1e3 << " ms" << std::endl;
     }
+}
+
+// --similar over the sample ring of one side: after the chain or from a loaded model
+void serve_similar(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies)
+{
+    if (J.similar < 1) return;                                       // one rank (main refuses -g > 1)
+    const double t0 = tick();
+    bpmf_hip_side *side = J.similar_by_rows ? users : movies;
+    const Csc &A = J.similar_by_rows ? J.Mt : J.M;                   // one column per entity of the side, in the run's numbering
+    const int64_t nq = J.similar_by_rows ? J.M.nrows : J.M.ncols;
+    std::vector<uint8_t> ok;
+    if (J.similar_min > 0) {
+        ok.resize((size_t)std::max<int64_t>(nq, 1));
+        for (int64_t c = 0; c < nq; ++c) ok[(size_t)c] = A.colptr[(size_t)c + 1] - A.colptr[(size_t)c] >= (int64_t)J.similar_min ? 1 : 0;
+    }
+    J.sim_idx.resize((size_t)nq * J.similar); J.sim_score.resize(J.sim_idx.size()); J.sim_mean.resize(J.sim_idx.size()); J.sim_std.resize(J.sim_idx.size());
+    check(bpmf_hip_similar(side, J.similar_kind, J.similar_kappa, J.similar, 0, nq, ok.empty() ? nullptr : ok.data(), J.sim_idx.data(),
+                           J.sim_score.data(), J.sim_mean.data(), J.sim_std.data()));
+    std::cerr << "similar: " << J.similar << " per " << (J.similar_by_rows ? "row" : "column") << " for " << nq << " queries, "
+              << (tick() - t0) * 1e3 << " ms" << std::endl;
+}
+
+// DIR/similar-cols.csv / similar-rows.csv
+void write_similar(const Job &J)
+{
+    if (J.similar < 1) return;                                       // 1-based ids in the ORIGINAL numbering, like the -o writers
+    const std::vector<int64_t> &pq = J.similar_by_rows ? J.perm_u : J.perm_m;
+    const int64_t nq = (int64_t)(J.sim_idx.size() / (size_t)J.similar);
+    std::vector<int64_t> order((size_t)nq);                          // queries in original order
+    for (int64_t i = 0; i < nq; ++i) order[(size_t)i] = i;
+    if (!pq.empty()) std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return pq[(size_t)a] < pq[(size_t)b]; });
+    const std::string name = J.odirname + (J.similar_by_rows ? "/similar-rows.csv" : "/similar-cols.csv");
+    FILE *f = fopen(name.c_str(), "w");
+    if (!f) die("cannot write " + name);
+    fprintf(f, "# similar %d by %s kind %s kappa %.17g min-ratings %ld\n", J.similar, J.similar_by_rows ? "rows" : "cols",
+            J.similar_kind == BPMF_HIP_SIM_COSINE ? "cosine" : "euclid", J.similar_kappa, J.similar_min);
+    fprintf(f, "query,rank,neighbour,score,mean,std\n");
+    for (int64_t q : order)
+        for (int r = 0; r < J.similar; ++r) {
+            const size_t at = (size_t)q * J.similar + r;
+            const int32_t c = J.sim_idx[at];
+            if (c < 0) break;                                        // (padding slots are not written)
+            fprintf(f, "%lld,%d,%lld,%.17g,%.17g,%.17g\n", (long long)((pq.empty() ? q : pq[(size_t)q]) + 1), r + 1,
+                    (long long)((pq.empty() ? c : pq[(size_t)c]) + 1), J.sim_score[at], J.sim_mean[at], J.sim_std[at]);
+        }
+    if (fclose(f) != 0) die("cannot write " + name);
 }
 
 // --fold-in-rows / --fold-in-cols against the sample ring of the other side and the side's hyper ring: after the chain or from a loaded model
@@ -747,7 +810,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
     const bool saving = !J.save_model.empty();
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving;
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows), ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows);
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -1081,6 +1144,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         J.ord_rmse = std::sqrt(sq / (double)n); J.ord_accuracy = (double)hit / (double)n; J.ord_logp = lp / (double)n;
     }
     serve_rank(J, users, movies);                                    // --topn, --rank-eval: one rank (main refuses -g > 1)
+    serve_similar(J, users, movies);
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
         if (N.n == 0) return;
@@ -1341,12 +1405,14 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
         std::cerr << "predict: " << n << " cells, " << (tick() - t1) * 1e3 << " ms" << std::endl;
     }
     serve_rank(J, users, movies);
+    serve_similar(J, users, movies);
     serve_fold(J, users, movies);
     bpmf_hip_side_destroy(movies);
     bpmf_hip_side_destroy(users);
     bpmf_hip_ctx_destroy(ctx);
 
     write_topn(J);
+    write_similar(J);
     const RankMetrics rkm = write_ranks(J);
     write_new(J, J.fold_u, true, nmovies, "foldin");
     write_new(J, J.fold_m, false, nusers, "foldin");
@@ -1391,7 +1457,13 @@ int main(int argc, char *argv[])
                                               {"rank-by", required_argument, nullptr, 1062}, {"rank-threshold", required_argument, nullptr, 1063},
                                               {"save-model", required_argument, nullptr, 1070}, {"model", required_argument, nullptr, 1071},
                                               {"predict", required_argument, nullptr, 1072}, {"predict-threshold", required_argument, nullptr, 1073},
+                                              {"similar", required_argument, nullptr, 1080}, {"similar-by", required_argument, nullptr, 1081},
+                                              {"similar-kind", required_argument, nullptr, 1082}, {"similar-kappa", required_argument, nullptr, 1083},
+                                              {"similar-min-ratings", required_argument, nullptr, 1084},
                                               {nullptr, 0, nullptr, 0}};
+    std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
+    bool similar_given = false;
+    std::string similar_flag;                                        // the first --similar-* flag given
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
     std::string topn_score = "mean", topn_kappa, topn_threshold;
     bool topn_kappa_given = false, topn_threshold_given = false;
@@ -1449,6 +1521,11 @@ int main(int argc, char *argv[])
         case 1071: model_dir = optarg; model_given = true; break;
         case 1072: predict_file = optarg; predict_given = true; break;
         case 1073: predict_threshold = optarg; predict_threshold_given = true; break;
+        case 1080: similar_n = optarg; similar_given = true; break;
+        case 1081: similar_by = optarg; if (similar_flag.empty()) similar_flag = "--similar-by"; break;
+        case 1082: similar_kind = optarg; if (similar_flag.empty()) similar_flag = "--similar-kind"; break;
+        case 1083: similar_kappa = optarg; if (similar_flag.empty()) similar_flag = "--similar-kappa"; break;
+        case 1084: similar_min = optarg; if (similar_flag.empty()) similar_flag = "--similar-min-ratings"; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1466,6 +1543,34 @@ int main(int argc, char *argv[])
         case 'v': training("-v"); J.verbose = true; break;
         default: usage(); return 1;
         }
+    }
+    // --similar and its flags: refused before anything touches a GPU
+    if (!similar_flag.empty() && !similar_given) die(similar_flag + " needs --similar N");
+    if (similar_given) {
+        char *end = nullptr;
+        const long n = similar_n.empty() ? 0 : strtol(similar_n.c_str(), &end, 10);
+        if (similar_n.empty() || *end != '\0' || n < 1 || n > 32) die("--similar expects 1 <= N <= 32, not '" + similar_n + "'");
+        J.similar = (int)n;
+        if (similar_by != "cols" && similar_by != "rows") die("--similar-by expects cols or rows, not '" + similar_by + "'");
+        J.similar_by_rows = similar_by == "rows";
+        if (similar_kind != "cosine" && similar_kind != "euclid") die("--similar-kind expects cosine or euclid, not '" + similar_kind + "'");
+        J.similar_kind = similar_kind == "cosine" ? BPMF_HIP_SIM_COSINE : BPMF_HIP_SIM_EUCLID;
+        if (!similar_kappa.empty() || similar_flag == "--similar-kappa") {
+            J.similar_kappa = similar_kappa.empty() ? NAN : strtod(similar_kappa.c_str(), &end);
+            if (similar_kappa.empty() || *end != '\0' || !std::isfinite(J.similar_kappa) || J.similar_kappa < 0.0)
+                die("--similar-kappa expects a finite number >= 0, not '" + similar_kappa + "'");
+        }
+        if (!similar_min.empty() || similar_flag == "--similar-min-ratings") {
+            J.similar_min = similar_min.empty() ? -1 : strtol(similar_min.c_str(), &end, 10);
+            if (similar_min.empty() || *end != '\0' || J.similar_min < 0) die("--similar-min-ratings expects an integer >= 0, not '" + similar_min + "'");
+        }
+        if (tensor_given) die("--similar does not go together with --tensor (the similarity is between the columns of one side of a matrix)");
+        if (g_given || ngpu >= 1) die("--similar runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample ring of a sharded side is not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--similar does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--similar does not go together with a propagated posterior (-m / -l)");
+        if (J.odirname.empty()) die(std::string("--similar needs -o DIR (the lists go to DIR/similar-") + (J.similar_by_rows ? "rows" : "cols") + ".csv)");
+        if (!model_given && J.nsims <= J.burnin) die("--similar needs at least one post-burn-in sample (-i > -b)");
+        if (model_given && J.similar_min > 0 && fname.empty()) die("--similar-min-ratings with --model needs -n TRAIN (the training ratings are what it counts)");
     }
     // --model / --predict / --save-model: refused before anything touches a GPU
     if (predict_given && !model_given) die("--predict needs --model DIR (cells are predicted from a saved model)");
@@ -1488,8 +1593,8 @@ int main(int argc, char *argv[])
         if (J.topn > 0 && fname.empty()) die("--topn with --model needs -n TRAIN (the rated cells are what the lists exclude)");
         if (rank_eval_given && fname.empty()) die("--rank-eval with --model needs -n TRAIN (the rated cells are what the ranks exclude)");
         if (rank_eval_given && probename.empty()) die("--rank-eval with --model needs -p TEST (the held-out cells)");
-        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty())
-            die("--model: nothing to do (--predict FILE, --topn N, --rank-eval N, --fold-in-rows FILE or --fold-in-cols FILE)");
+        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty() && !similar_given)
+            die("--model: nothing to do (--predict FILE, --topn N, --rank-eval N, --similar N, --fold-in-rows FILE or --fold-in-cols FILE)");
         if (J.odirname.empty()) die("--model needs -o DIR (the results go to files in DIR)");
     }
     if (save_model_given) {
@@ -2152,6 +2257,7 @@ int main(int argc, char *argv[])
     }
 
     write_topn(J);
+    write_similar(J);
 
     const RankMetrics rkm = write_ranks(J);
 

@@ -6,6 +6,7 @@
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
 //   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn, bpmf_hip_topn_scored)
+//   capi_similar.hip   similar columns of one side by posterior cosine / distance over its ring (bpmf_hip_similar, bpmf_hip_similar_block)
 //   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells (bpmf_hip_predict_cells)

@@ -166,6 +166,25 @@ struct TopnScoredLaunch {
 };
 int topn_scored(const TopnScoredLaunch &p, hipStream_t st);    // score + select, merge of the splits.  -1: shape not supported, -2: the LDS of the lists was refused (nothing launched)
 
+// similar columns of one side by posterior cosine / distance (kernels_similar.h, ksimilar.hip).  -1: shape not supported (nothing launched)
+int ring_norms(const double *ring, int64_t stride, int Kp, int S, int64_t ncols, double *tab, hipStream_t st);   // tab: 2 S doubles per column
+struct SimilarLaunch {
+    const double *ring; int64_t stride; const double *tab;
+    int Kp, S, n; int kind; double kappa;                  // BPMF_HIP_SIM_*
+    int64_t q_from, nq, nc, cspan; int nsplit;             // nc: the side's columns, all of them candidates
+    const uint8_t *cand_ok;                                // device bytes, one per candidate, or NULL
+    double *part_score, *part_mean, *part_std; int32_t *part_idx;   // nsplit x nq x n
+    double *out_score, *out_mean, *out_std; int32_t *out_idx;       // nq x n
+};
+int similar_topn(const SimilarLaunch &p, hipStream_t st);  // score + select, merge of the splits.  -2: the LDS of the lists was refused
+struct SimilarBlockLaunch {
+    const double *ring; int64_t stride; const double *tab;
+    int Kp, S; int kind;
+    int64_t ncols, q_from, nq, c_from, nc;
+    double *mean, *std;                                    // nq x nc, row-major
+};
+int similar_block(const SimilarBlockLaunch &p, hipStream_t st);
+
 // dense blocks of predictions from two sample rings; rows unseen in training (kernels_predblock.h, kpredblock.hip)
 struct PredBlockLaunch {
     const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column

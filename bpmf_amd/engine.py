@@ -359,6 +359,51 @@ class HipEngine:
                                                  _ptr(idx), _ptr(score), _ptr(mean), _ptr(std)))
         return idx, score, mean, std
 
+    SIM_KINDS = {"cosine": 0, "euclid": 1}           # BPMF_HIP_SIM_*
+
+    def similar(self, side, n, kind="cosine", kappa=0.0, q_from=0, q_to=None, cand_ok=None):
+        """The n nearest neighbours of every column q_from .. q_to - 1 of `side` among the side's own columns, by a similarity no
+        rotation of the latent space changes: per kept sample the cosine between the two columns ("cosine")
+        or their negative squared distance ("euclid"), then score = mean - kappa std over the samples (kappa >= 0).  A query is
+        never its own neighbour; cand_ok (one truth value per column, None: all) says which columns may be listed.
+        (idx int32[nq, n], score, mean, std f64[nq, n]), score descending, lower index first; mean and std of a pick are
+        similar_block's, bit for bit; empty slots have idx -1 and zeros."""
+        if kind not in self.SIM_KINDS:
+            raise ValueError("similar: kind must be one of 'cosine', 'euclid', not %r" % (kind,))
+        q_to = side.ncols if q_to is None else int(q_to)
+        nq = max(0, q_to - int(q_from))
+        ok = None
+        if cand_ok is not None:
+            ok = np.ascontiguousarray(np.asarray(cand_ok) != 0, np.uint8)
+            if ok.shape != (side.ncols,):
+                raise ValueError("similar: cand_ok must hold one entry per column (%d), not %s" % (side.ncols, ok.shape))
+        idx = np.empty((nq, int(n)), dtype=np.int32)
+        score = np.empty((nq, int(n)))
+        mean = np.empty((nq, int(n)))
+        std = np.empty((nq, int(n)))
+        _lib.check(self.lib.bpmf_hip_similar(side.handle, self.SIM_KINDS[kind], float(kappa), int(n), int(q_from), int(q_to),
+                                             None if ok is None else _ptr(ok), _ptr(idx), _ptr(score), _ptr(mean), _ptr(std)))
+        return idx, score, mean, std
+
+    def similar_block(self, side, kind="cosine", q_from=0, q_to=None, c_from=0, c_to=None):
+        """(mean, std), [q_to - q_from, c_to - c_from] each: the posterior mean and spread of the similarity of every pair of
+        columns of the block, the diagonal included, with the bits `similar` lists."""
+        if kind not in self.SIM_KINDS:
+            raise ValueError("similar_block: kind must be one of 'cosine', 'euclid', not %r" % (kind,))
+        q_to = side.ncols if q_to is None else int(q_to)
+        c_to = side.ncols if c_to is None else int(c_to)
+        mean = np.empty((max(0, q_to - int(q_from)), max(0, c_to - int(c_from))))
+        std = np.empty_like(mean)
+        _lib.check(self.lib.bpmf_hip_similar_block(side.handle, self.SIM_KINDS[kind], int(q_from), int(q_to), int(c_from), int(c_to),
+                                                   _ptr(mean), _ptr(std)))
+        return mean, std
+
+    def similar_last_ms(self, side):
+        """Device time of the newest `similar` of the side, between two events (tools/similar_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_similar_last_ms(side.handle, C.byref(ms)))
+        return ms.value
+
     def predict_block(self, query, cand, mean_rating, q_from=0, q_to=None, c_from=0, c_to=None):
         """(mean, std), [q_to - q_from, c_to - c_from] each: the posterior-mean prediction and its spread over the samples of the
         two sides' rings for every pair of the block, in one kernel.  The bits of an element do not depend

@@ -196,7 +196,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
-          ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None):
+          ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -341,7 +342,28 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     bpmf_amd.load_model and `bpmf --model DIR` serve top-N lists, ranked evaluation, blocks, fold-in and single cells from without a
     chain.  Needs nsims > burnin.  Goes with plain Gaussian runs, any alpha, weights, robust, censored, probit=True, noise="adaptive"
     and an fp32 engine; refused with ordinal, implicit and features (serving them would need state the format does not store).
-    None (the default): nothing changes."""
+    None (the default): nothing changes.
+
+    similar=N: the sample rings are kept as for topn, and after the chain res["similar"] = dict(by, kind, kappa, idx, score, mean,
+    std) holds engine.similar's lists: the N nearest neighbours of every movie (similar_by="cols") or user
+    ("rows") among the entities of the same side, by the posterior mean of the per-sample cosine (similar_kind="cosine") or negative
+    squared distance ("euclid") minus similar_kappa >= 0 times its spread -- quantities no rotation of the latent space changes.
+    Entities with fewer than similar_min_ratings training ratings are not listed (their factors are close to prior draws); they are
+    still queries.  It reads only the ring, so it goes with every likelihood topn goes with, and is independent of topn.  Needs
+    nsims > burnin.  None (the default): nothing changes."""
+    if similar is not None:                          # (refused before the engine is used)
+        if not (isinstance(similar, (int, np.integer)) and 1 <= int(similar) <= 32):
+            raise ValueError("similar = %r: the list length must be an integer in 1 .. 32" % (similar,))
+        if similar_by not in ("cols", "rows"):
+            raise ValueError("similar_by must be 'cols' or 'rows', not %r" % (similar_by,))
+        if similar_kind not in ("cosine", "euclid"):
+            raise ValueError("similar_kind must be 'cosine' or 'euclid', not %r" % (similar_kind,))
+        if not (isinstance(similar_kappa, (int, float)) and math.isfinite(similar_kappa) and similar_kappa >= 0):
+            raise ValueError("similar_kappa = %r must be finite and >= 0" % (similar_kappa,))
+        if not (isinstance(similar_min_ratings, (int, np.integer)) and similar_min_ratings >= 0):
+            raise ValueError("similar_min_ratings = %r must be an integer >= 0" % (similar_min_ratings,))
+        if nsims - burnin < 1:
+            raise ValueError("similar needs at least one post-burn-in sample (nsims > burnin)")
     if save_model is not None:                       # (refused before the engine is used)
         for on, what in ((ordinal is not None and ordinal is not False, "ordinal"), (implicit is not None, "implicit"),
                          (row_features is not None or col_features is not None, "row_features / col_features")):
@@ -602,8 +624,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -740,6 +762,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     res["final_rmse_avg"] = movies.rmse_avg
     res["num_predict"] = movies.num_predict
     res["U"] = users.items(); res["V"] = movies.items()
+    if similar is not None:
+        sim_side, sim_M = (movies, M) if similar_by == "cols" else (users, Mt)
+        ok = np.diff(np.asarray(sim_M[0])) >= similar_min_ratings if similar_min_ratings > 0 else None
+        idx, score, mean, std = engine.similar(sim_side.side, int(similar), similar_kind, float(similar_kappa), cand_ok=ok)
+        res["similar"] = dict(by=similar_by, kind=similar_kind, kappa=float(similar_kappa), idx=idx, score=score, mean=mean, std=std)
     if topn is not None:
         if topn_score is None:
             res["topn"] = engine.topn(users.side, movies.side, movies.mean_rating, topn)

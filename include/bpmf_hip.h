@@ -323,6 +323,33 @@ BPMF_API int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, dou
                                   int exclude_rated, int kind, double param, double sigma, int32_t *idx_out, double *score_out,
                                   double *mean_out, double *std_out);
 
+/* SIMILAR COLUMNS of one side: the n nearest neighbours of every column q_from .. q_to - 1 of `side` among
+ * the side's own columns, by a similarity that no rotation of the latent space changes.  With v_s(c) column c of kept sample s
+ * (S >= 1 samples in the side's ring), d_s = v_s(q) . v_s(c), n_s(c) = |v_s(c)|^2, r_s(c) = 1 / sqrt(n_s(c)) (0 where n_s(c) = 0):
+ *   BPMF_HIP_SIM_COSINE  x_s = clamp(d_s * (r_s(q) * r_s(c)), -1, 1)      a column of norm zero has cosine 0 with everything
+ *   BPMF_HIP_SIM_EUCLID  x_s = -max((n_s(q) + n_s(c)) - 2 d_s, 0)         the negative squared distance
+ *   mean = (1/S) sum_s x_s,  std = sqrt(sum_s (x_s - mean)^2 / (S - 1)) (0 for S = 1),  score = mean - kappa std, kappa >= 0 finite
+ * (kappa = 0: the plain posterior-mean similarity; kappa > 0: neighbours the posterior is sure about).  The order is
+ * bpmf_hip_topn_scored's: score descending, lower column index first.  A query is never its own neighbour.  cand_ok: NULL, or one
+ * host byte per column of the side, != 0 meaning the column may be listed (it does not restrict the queries).  Empty slots have
+ * idx -1 and zeros.  1 <= n <= 32.  idx_out / score_out / mean_out / std_out: (q_to - q_from) x n row-major host arrays.
+ * x_s(q, c) and x_s(c, q) have the same bits, and the bits of a pair depend on its two columns alone: not on the ranges, the
+ * candidate splits, the mask or the call.  Supported range: every n_s(c) is 0 or within [2^-900, 2^900] (cosine) / [2^-500, 2^500] (euclid: its variance
+ * squares a squared norm); outside it nothing
+ * traps, and an element whose score is -inf or not a number is not listed.  Works on fp32 contexts (the ring is fp64).  Waits.
+ * BPMF_HIP_EINVAL: no ring or an empty one, an unknown kind, kappa negative or not finite, n outside 1 .. 32, a range out of
+ * bounds or with q_to < q_from, a side that does not hold all its columns or a context with a communicator.
+ *
+ * bpmf_hip_similar_block: mean_out / std_out ((q_to - q_from) x (c_to - c_from), row-major, host) of the dense block of pairs,
+ * the diagonal included, bit for bit the values the lists carry.
+ * bpmf_hip_similar_last_ms: device time between two events around the newest bpmf_hip_similar of the side (norm table, ranking, merge). */
+enum { BPMF_HIP_SIM_COSINE = 0, BPMF_HIP_SIM_EUCLID = 1 };
+BPMF_API int bpmf_hip_similar(bpmf_hip_side *side, int kind, double kappa, int n, int64_t q_from, int64_t q_to,
+                              const uint8_t *cand_ok, int32_t *idx_out, double *score_out, double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_similar_block(bpmf_hip_side *side, int kind, int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to,
+                                    double *mean_out, double *std_out);
+BPMF_API int bpmf_hip_similar_last_ms(const bpmf_hip_side *side, float *ms);
+
 /* ---- dense blocks of predictions; rows unseen in training ---------
  * bpmf_hip_predict_block: for every query column q in [q_from, q_to) of `query` and every candidate column c in [c_from, c_to)
  * of `cand`, from the sample rings of both sides (the same S >= 1 samples, bpmf_hip_side_samples_add): mean and std as
