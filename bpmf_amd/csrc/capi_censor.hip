@@ -18,7 +18,7 @@ int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
     const bpmf_censor *cs = self->censor.get();
     bpmf_launch::CensorLatentLaunch p{};
     p.pos = cs->pos.get(); p.col = cs->col.get(); p.row = cs->row.get(); p.sign = cs->sign.get(); p.n = cs->n; p.vals = self->d_vals;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.f = factor_pair(self, other);
     p.iter = (uint32_t)iter; p.tag = cs->tag; p.mean = self->mean_rating;
     p.sqrt_alpha = std::sqrt(alpha); p.inv_sqrt_alpha = 1.0 / p.sqrt_alpha;
     p.z = cs->z.get(); p.fail = cs->fail.dev();
@@ -33,16 +33,10 @@ extern "C" int bpmf_hip_side_set_censored(bpmf_hip_side *s, const int8_t *flags,
     if (!s || !flags) return fail(BPMF_HIP_EINVAL, "side_set_censored: NULL argument");
     bpmf_hip_ctx *c = s->ctx;
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_censored: the side is a censored side already");
-    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a probit side (bpmf_hip_side_set_probit)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with features (bpmf_hip_side_set_features)");
-    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
-    if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with propagated priors");
-    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_censored: not on an ordinal side (bpmf_hip_side_set_ordinal)");
-    if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_censored: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
-    int rc = require_single_gpu("side_set_censored", c, s);
+    int rc = refuse("side_set_censored", s, {Not::probit, Not::features, Not::robust, Not::weights, Not::prop_posterior, Not::ordinal});
     if (rc) return rc;
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_censored: not together with the BPMF_REDUCE formulation");
+    if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_censored: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
+    if ((rc = require_single_gpu("side_set_censored", c, s)) || (rc = refuse("side_set_censored", s, {Not::reduce}))) return rc;
     if ((int64_t)s->h_colptr.size() != s->ncols + 1) return fail(BPMF_HIP_EINVAL, "side_set_censored: the side has no host column pointers");
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
@@ -89,11 +83,5 @@ extern "C" int bpmf_hip_side_censored_latent(bpmf_hip_side *s, double *z_host)
 {
     if (!s || !z_host) return fail(BPMF_HIP_EINVAL, "side_censored_latent: NULL argument");
     if (!s->censor) return fail(BPMF_HIP_EINVAL, "side_censored_latent: not a censored side (bpmf_hip_side_set_censored)");
-    bpmf_hip_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
-    { std::string m; if (check_censor(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->censor->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
-    return BPMF_HIP_OK;
+    return latent_read_back(__func__, s, s->censor->z.get(), z_host);
 }

@@ -23,9 +23,10 @@ int foldin_refusals(const char *who, const bpmf_hip_side *side, const bpmf_hip_s
     if (rc) return rc;
     if (side->reduce_on || (cand && cand->reduce_on)) return fail(BPMF_HIP_EINVAL, w + ": does not go together with the BPMF_REDUCE formulation (bpmf_hip_sys_set_reduce)");
     if (side->d_prop) return fail(BPMF_HIP_EINVAL, w + ": the side has propagated priors (bpmf_hip_side_set_prop_posterior): a new row has none");
-    if (side->probit || (cand && cand->probit))
+    const auto either_is = [&](Likelihood k) { return likelihood(side) == k || (cand && likelihood(cand) == k); };
+    if (either_is(Likelihood::probit))
         return fail(BPMF_HIP_EINVAL, w + ": a probit side cannot be folded into (labels would need a latent iteration of their own)");
-    if (side->ordinal || (cand && cand->ordinal))
+    if (either_is(Likelihood::ordinal))
         return fail(BPMF_HIP_EINVAL, w + ": an ordinal side cannot be folded into (levels would need a latent iteration of their own)");
     if (side->link)
         return fail(BPMF_HIP_EINVAL, w + ": the side has features: the prior mean of a new row needs its features (bpmf_hip_side_newrows_set predicts such rows)");

@@ -20,22 +20,17 @@ extern "C" int bpmf_hip_side_set_implicit(bpmf_hip_side *s, double w0, const dou
     if (!(w0 > 0.0) || !std::isfinite(w0)) return fail(BPMF_HIP_EINVAL, "side_set_implicit: w0 must be finite and > 0");
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on an fp32 context");
     if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_implicit: the side is an implicit side already");
-    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
+    int rc = refuse("side_set_implicit", s, {Not::robust});
+    if (rc) return rc;
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on a side with per-rating weights (pass the confidences to this call)");
-    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on a probit side (bpmf_hip_side_set_probit)");
-    if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on a censored side (bpmf_hip_side_set_censored)");
-    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on an ordinal side (bpmf_hip_side_set_ordinal)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not together with features (bpmf_hip_side_set_features)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not together with propagated priors");
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not together with the BPMF_REDUCE formulation");
+    if ((rc = refuse("side_set_implicit", s, {Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce}))) return rc;
     if (s->foldin) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not together with fold-in on the side (the folded-in rows would need G)");
     if (s->mean_rating != 0.0) {
         char v[32];
         snprintf(v, sizeof v, "%g", s->mean_rating);
         return fail(BPMF_HIP_EINVAL, "side_set_implicit: the side's mean rating is " + std::string(v) + ", the implicit model needs exactly 0");
     }
-    int rc = require_single_gpu("side_set_implicit", c, s);
-    if (rc) return rc;
+    if ((rc = require_single_gpu("side_set_implicit", c, s))) return rc;
     for (int64_t p = 0; w && p < s->nnz; ++p)
         if (!(w[p] > w0) || !std::isfinite(w[p])) {
             char v[32], v0[32];

@@ -1,7 +1,8 @@
 // capi_internal.h -- what the translation units of the C ABI (capi_*.hip) share: the host-side helpers that cross the files.
 // Round 6 cut the former capi.hip (2 400 lines) into
 //   capi_context.hip   errors, RCCL entry points, host trace, bounded waits, context create / destroy / sync, normal stream
-//   capi_side.hip      static work schedule, side create / destroy, factor storage, priors, launch reports
+//   capi_side.hip      static work schedule, side create / destroy, factor storage, priors, launch reports; what the add-ons share: the
+//                      table of their mutual refusals (refuse) and the wait-check-copy of a latent step's read-back (latent_read_back)
 //   capi_sample.hip    sampler launches, stateless half-iteration, posterior aggregation, the stateful pipeline (bpmf_hip_sys_sample)
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
@@ -21,12 +22,17 @@
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
+// Four of the add-ons (probit, ordinal, censored, robust) run a latent kernel ahead of every sampler launch of their side: state.h names
+// the kind of a side (likelihood), checks its fail word (check_latent) and picks the values its samplers read (sampler_values); the launch
+// structs of launch.h share FactorPair / SideCsc, filled by factor_pair / side_csc below; their launchers share dispatch_k / dispatch_kt.
 // The device memory of the last ten (probit, censoring, weights, Student-t noise, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h
 // and counted by bpmf_hip_live_device_bytes; the core state of a context, a side and a test set (state.h) is owned the same way -- DevBuf / Pinned / Event / Stream members
 // (devbuf.h), released by `delete` -- and counted by bpmf_hip_live_core_bytes.  No file but devbuf.h allocates or releases device memory, pinned memory, events or streams.
 // Everything here lives in namespace bpmf_capi with hidden visibility (-fvisibility=hidden): not part of the ABI.
 #pragma once
 #include <dlfcn.h>
+
+#include <initializer_list>
 
 #include "launch.h"
 
@@ -60,22 +66,44 @@ int settle_async(bpmf_hip_side *s);                                    // waits 
 void predraw_stop(bpmf_hip_side *s);                                   // joins the side's pre-draw helper threads
 int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statistics without a launch to ride in: a kernel of their own
 
-// probit likelihood (capi_probit.hip)
-int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a probit side
-
-// censored ratings (capi_censor.hip)
-int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a censored side
-// Student-t noise (capi_robust.hip)
-int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);   // ahead of the sampler of a robust side
-// ordinal probit likelihood (capi_ordinal.hip)
-int ordinal_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);  // ahead of the sampler of an ordinal side
-// the latent kernel of a probit, an ordinal, a censored or a robust side, whichever `self` is (a side is at most one of them)
+// The latent step of a side (probit, ordinal, censored, robust: state.h has the kind): the kernel of the half-iteration being enqueued, on
+// the stream `st` its sampler goes on, ahead of it.  Each kind fills its launch struct and keeps its own refusals (capi_probit.hip,
+// capi_ordinal.hip, capi_censor.hip, capi_robust.hip); latent_enqueue picks the one `self` is and does nothing on a Gaussian side.
+int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
+int ordinal_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
+int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
+int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
 inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
 {
-    return self->probit ? probit_latent_enqueue(self, other, iter, alpha, st)
-           : self->ordinal ? ordinal_latent_enqueue(self, other, iter, alpha, st)
-           : self->censor ? censor_latent_enqueue(self, other, iter, alpha, st) : robust_latent_enqueue(self, other, iter, alpha, st);
+    switch (likelihood(self)) {
+    case Likelihood::probit: return probit_latent_enqueue(self, other, iter, alpha, st);
+    case Likelihood::ordinal: return ordinal_latent_enqueue(self, other, iter, alpha, st);
+    case Likelihood::censored: return censor_latent_enqueue(self, other, iter, alpha, st);
+    case Likelihood::robust: return robust_latent_enqueue(self, other, iter, alpha, st);
+    case Likelihood::gaussian: break;
+    }
+    return 0;
 }
+// the members the launch structs of the add-ons share (launch.h): the factors of the side being stepped and of its partner as the
+// newest launch on S0 left them, and the side's ratings by columns (ensure_colptr has run)
+inline bpmf_launch::FactorPair factor_pair(const bpmf_hip_side *self, const bpmf_hip_side *other)
+{
+    const bpmf_hip_ctx *c = self->ctx;
+    return {self->d_items, other->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt};
+}
+inline bpmf_launch::SideCsc side_csc(const bpmf_hip_side *self) { return {self->d_colptr.get(), self->ncols, self->d_rowidx, self->nnz}; }
+// (capi_side.hip) waits for the side's work in flight -- its worker, then S0, reported as `func` -- and reports a raised latent word
+// (check_latent: bpmf_hip_side_weights_get of a robust side); latent_read_back then copies the nnz doubles `z` to the host (the three
+// *_latent entry points, bpmf_hip_side_robust_get)
+int latent_settle(const char *func, bpmf_hip_side *s);
+int latent_read_back(const char *func, bpmf_hip_side *s, const double *z, double *z_host);
+
+// The refusals the setters of the add-ons give each other, in the standard wording "<who>: not on a probit side
+// (bpmf_hip_side_set_probit)" etc. (the table is in capi_side.hip): the first of `order` that holds for `s` is reported as
+// BPMF_HIP_EINVAL, 0 if none does.  The order decides what a side with two of the properties is told (a robust side has weights
+// too); a caller whose wording differs writes that line out at its place between two calls.
+enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce };
+int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> order);
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.

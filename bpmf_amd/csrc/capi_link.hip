@@ -86,7 +86,7 @@ int residual_enqueue(bpmf_hip_side *s, const bpmf_hip_side *other, double *out)
 {
     const bpmf_hip_ctx *c = s->ctx;
     bpmf_launch::LinkResidualLaunch p{};
-    p.colptr = s->d_colptr.get(); p.ncols = s->ncols; p.rowidx = s->d_rowidx; p.vals = s->d_vals; p.nnz = s->nnz;
+    p.m = side_csc(s); p.vals = s->d_vals;
     p.offs = s->link->m.get(); p.other = other->d_items; p.K = c->K; p.kt = c->Kt; p.out = out;
     if (bpmf_launch::link_residual(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "link: unsupported K " + std::to_string(c->K));
     HIP_TRY(hipGetLastError());
@@ -142,13 +142,11 @@ int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, 
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, w + ": not on an fp32 context");
     int rc = require_single_gpu(who, c, s);
     if (rc) return rc;
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, w + ": not together with the BPMF_REDUCE formulation");
+    if ((rc = refuse(who, s, {Not::reduce}))) return rc;
     if (s->probit) return fail(BPMF_HIP_EINVAL, w + ": not on a probit side");
     if (s->ordinal) return fail(BPMF_HIP_EINVAL, w + ": not on an ordinal side");
     if (s->censor) return fail(BPMF_HIP_EINVAL, w + ": not on a censored side (the residuals would have to be formed from the latent values)");
-    if (s->robust) return fail(BPMF_HIP_EINVAL, w + ": not on a side with Student-t noise (bpmf_hip_side_set_robust)");
-    if (s->weights) return fail(BPMF_HIP_EINVAL, w + ": not on a side with per-rating weights (bpmf_hip_side_set_weights)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, w + ": not together with propagated priors");
+    if ((rc = refuse(who, s, {Not::robust, Not::weights, Not::prop_posterior}))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     const size_t N = (size_t)s->ncols, ld = (size_t)c->K, Kt = (size_t)c->Kt;

@@ -32,8 +32,7 @@ extern "C" int bpmf_hip_train_sse(bpmf_hip_side *self, bpmf_hip_side *other, dou
     // the copy it writes: behind it in the queue, nothing else needed.  Nothing this waits for depends on a later enqueue:
     // statistics waiting for a rider and a deferred evaluation go to other launches, not to the samplers ahead of this one.
     bpmf_launch::SseLaunch p{};
-    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.vals = self->d_vals; p.nnz = self->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.m = side_csc(self); p.vals = self->d_vals; p.f = factor_pair(self, other);
     p.mean = self->mean_rating; p.partial = self->sse->part.get(); p.nblk = self->sse->nblk;
     if (bpmf_launch::train_sse(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "train_sse: unsupported K " + std::to_string(c->K));
     c->last_sampler_done = nullptr;                                   // (the newest thing on S0 is no longer a sampler)

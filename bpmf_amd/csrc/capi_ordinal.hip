@@ -92,8 +92,7 @@ int loglik_pass(const char *who, bpmf_hip_side *self, bpmf_hip_side *other, cons
     HIP_TRY(hipMemcpy(o->g_prop.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     // S0 holds the newest sampler of both sides and d_items is the copy it writes, as in bpmf_hip_train_sse
     bpmf_launch::OrdinalLoglikLaunch p{};
-    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.level = o->level.get(); p.nnz = self->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.m = side_csc(self); p.f = factor_pair(self, other); p.level = o->level.get();
     p.g0 = o->g.get(); p.g1 = o->g_prop.get(); p.nlev = o->nlev; p.partial = o->part.get();
     if (bpmf_launch::ordinal_loglik(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, std::string(who) + ": unsupported K " + std::to_string(c->K));
     ++o->loglik_launches;
@@ -119,8 +118,7 @@ int ordinal_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int 
         return fail(BPMF_HIP_EINVAL, "ordinal: needs the side whole on one GPU, without a communicator, BPMF_REDUCE or propagated priors");
     bpmf_launch::OrdinalLatentLaunch p{};
     const bpmf_ordinal *o = self->ordinal.get();
-    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.level = o->level.get(); p.nnz = self->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.m = side_csc(self); p.f = factor_pair(self, other); p.level = o->level.get();
     p.iter = (uint32_t)iter; p.tag = o->tag; p.g = o->g.get(); p.nlev = o->nlev; p.z = o->z.get(); p.fail = o->fail.dev();
     if (bpmf_launch::ordinal_latent(p, st)) return fail(BPMF_HIP_EINVAL, "ordinal: unsupported K " + std::to_string(c->K));
     return 0;
@@ -138,18 +136,12 @@ extern "C" int bpmf_hip_side_set_ordinal(bpmf_hip_side *s, const double *levels,
         if (i > 0 && !(levels[i] > levels[i - 1])) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the levels are not strictly increasing");
     }
     if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the side is an ordinal side already");
-    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not on a probit side (bpmf_hip_side_set_probit)");
-    if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not on a censored side (bpmf_hip_side_set_censored)");
-    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not on a side with Student-t noise (bpmf_hip_side_set_robust)");     // (it has weights too)
-    if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not together with features (bpmf_hip_side_set_features)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not together with propagated priors");
+    int rc = refuse("side_set_ordinal", s, {Not::probit, Not::censored, Not::robust, Not::weights, Not::features, Not::prop_posterior});
+    if (rc) return rc;
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if (cutpoints) { const int rk = check_cutpoints("side_set_ordinal", cutpoints, nlevels); if (rk) return rk; }
-    int rc = require_single_gpu("side_set_ordinal", c, s);
-    if (rc) return rc;
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: not together with the BPMF_REDUCE formulation");
+    if ((rc = require_single_gpu("side_set_ordinal", c, s)) || (rc = refuse("side_set_ordinal", s, {Not::reduce}))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     // the level of every rating, on the host: the ratings come back from the device once
@@ -206,13 +198,7 @@ extern "C" int bpmf_hip_side_ordinal_latent(bpmf_hip_side *s, double *z_host)
 {
     if (!s || !z_host) return fail(BPMF_HIP_EINVAL, "side_ordinal_latent: NULL argument");
     if (!s->ordinal) return fail(BPMF_HIP_EINVAL, "side_ordinal_latent: not an ordinal side (bpmf_hip_side_set_ordinal)");
-    bpmf_hip_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
-    { std::string m; if (check_ordinal(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->ordinal->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
-    return BPMF_HIP_OK;
+    return latent_read_back(__func__, s, s->ordinal->z.get(), z_host);
 }
 
 extern "C" int bpmf_hip_side_ordinal_cut_get(bpmf_hip_side *s, double *cutpoints)
@@ -312,8 +298,7 @@ extern "C" int bpmf_hip_test_ordinal_add(bpmf_hip_test *t, bpmf_hip_side *self, 
     }
     if (t->ord_nlev != o->nlev) return fail(BPMF_HIP_EINVAL, "test_ordinal_add: the number of levels changed");
     bpmf_launch::OrdinalProbLaunch p{};
-    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz; p.f = factor_pair(self, other);
     p.g = o->g.get(); p.nlev = o->nlev; p.sum = t->ord_sum.get();
     if (bpmf_launch::ordinal_prob(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "test_ordinal_add: unsupported K " + std::to_string(c->K));
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "test_ordinal_add: kernel launch failed");

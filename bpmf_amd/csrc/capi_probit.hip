@@ -21,8 +21,7 @@ int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
         return fail(BPMF_HIP_EINVAL, "probit: needs the side whole on one GPU, without a communicator and without BPMF_REDUCE");
     bpmf_launch::ProbitLatentLaunch p{};
     const bpmf_probit *pb = self->probit.get();
-    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.sign = pb->sign.get(); p.nnz = self->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.m = side_csc(self); p.f = factor_pair(self, other); p.sign = pb->sign.get();
     p.iter = (uint32_t)iter; p.tag = pb->tag; p.z = pb->z.get(); p.fail = pb->fail.dev();
     if (bpmf_launch::probit_latent(p, st)) return fail(BPMF_HIP_EINVAL, "probit: unsupported K " + std::to_string(c->K));
     return 0;
@@ -35,17 +34,12 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
     if (!s) return fail(BPMF_HIP_EINVAL, "side_set_probit: NULL");
     bpmf_hip_ctx *c = s->ctx;
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
-    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on an ordinal side (bpmf_hip_side_set_ordinal)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with features (bpmf_hip_side_set_features)");
-    if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a censored side (bpmf_hip_side_set_censored)");
-    if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
-    if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_probit: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
+    int rc = refuse("side_set_probit", s, {Not::ordinal, Not::features, Not::censored, Not::robust, Not::weights});
+    if (rc) return rc;
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_probit: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if (!std::isfinite(threshold)) return fail(BPMF_HIP_EINVAL, "side_set_probit: the threshold is not finite");
-    int rc = require_single_gpu("side_set_probit", c, s);
-    if (rc) return rc;
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_probit: not together with the BPMF_REDUCE formulation");
+    if ((rc = require_single_gpu("side_set_probit", c, s)) || (rc = refuse("side_set_probit", s, {Not::reduce}))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     auto pb = std::make_unique<bpmf_probit>();
@@ -64,13 +58,7 @@ extern "C" int bpmf_hip_side_probit_latent(bpmf_hip_side *s, double *z_host)
 {
     if (!s || !z_host) return fail(BPMF_HIP_EINVAL, "side_probit_latent: NULL argument");
     if (!s->probit) return fail(BPMF_HIP_EINVAL, "side_probit_latent: not a probit side (bpmf_hip_side_set_probit)");
-    bpmf_hip_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
-    { std::string m; if (check_probit(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, s->probit->z.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
-    return BPMF_HIP_OK;
+    return latent_read_back(__func__, s, s->probit->z.get(), z_host);
 }
 
 extern "C" int bpmf_hip_test_probit_add(bpmf_hip_test *t, bpmf_hip_side *self, bpmf_hip_side *other)
@@ -89,8 +77,7 @@ extern "C" int bpmf_hip_test_probit_add(bpmf_hip_test *t, bpmf_hip_side *self, b
     // S0 holds the newest sampler of both sides and d_items is the copy it writes (as in bpmf_hip_train_sse); whichever
     // sampler rewrites one of these copies later is behind this kernel in the same queue.  Enqueue only: nothing waits.
     bpmf_launch::ProbitProbLaunch p{};
-    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.f32 = c->dtype == BPMF_HIP_F32; p.K = c->K; p.kt = c->Kt;
+    p.tcol = t->d_tcol.get(); p.trow = t->d_trow.get(); p.nnz = t->nnz; p.f = factor_pair(self, other);
     p.sum = t->d_prob_sum.get();
     if (bpmf_launch::probit_prob(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "test_probit_add: unsupported K " + std::to_string(c->K));
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "test_probit_add: kernel launch failed");

@@ -19,8 +19,7 @@ int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
         return fail(BPMF_HIP_EINVAL, "robust: needs the side whole on one GPU in fp64, without a communicator, BPMF_REDUCE or propagated priors");
     const bpmf_robust *rb = self->robust.get();
     bpmf_launch::RobustWeightsLaunch p{};
-    p.colptr = self->d_colptr.get(); p.ncols = self->ncols; p.rowidx = self->d_rowidx; p.vals = self->d_vals; p.nnz = self->nnz;
-    p.items = self->d_items; p.other = other->d_items; p.K = c->K; p.kt = c->Kt;
+    p.m = side_csc(self); p.vals = self->d_vals; p.f = factor_pair(self, other);
     p.iter = (uint32_t)iter; p.tag = rb->tag; p.mean = self->mean_rating; p.sqrt_alpha = std::sqrt(alpha); p.nu = rb->nu;
     const double a = 0.5 * (rb->nu + 1.0);
     p.dd = a - 1.0 / 3.0;
@@ -45,15 +44,8 @@ extern "C" int bpmf_hip_side_set_robust(bpmf_hip_side *s, double nu, unsigned ta
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_robust: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on an fp32 context");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_robust: the side is a robust side already");
-    if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
-    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a probit side (bpmf_hip_side_set_probit)");
-    if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on a censored side (bpmf_hip_side_set_censored)");
-    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on an ordinal side (bpmf_hip_side_set_ordinal)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with features (bpmf_hip_side_set_features)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with propagated priors");
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_robust: not together with the BPMF_REDUCE formulation");
-    int rc = require_single_gpu("side_set_robust", c, s);
-    if (rc) return rc;
+    int rc = refuse("side_set_robust", s, {Not::weights, Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
+    if (rc || (rc = require_single_gpu("side_set_robust", c, s))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;
     { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
@@ -99,12 +91,7 @@ extern "C" int bpmf_hip_side_robust_get(bpmf_hip_side *s, double *wmean_host, in
     if (nu) *nu = rb->nu;
     if (!wmean_host) return BPMF_HIP_OK;
     if (rb->kept == 0) return fail(BPMF_HIP_EINVAL, "side_robust_get: nothing added (bpmf_hip_side_robust_add)");
-    bpmf_hip_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(s); if (rc) return rc; }
-    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
-    { std::string m; if (check_robust(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    if (s->nnz > 0) HIP_TRY(hipMemcpy(wmean_host, rb->wsum.get(), (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    { const int rc = latent_read_back(__func__, s, rb->wsum.get(), wmean_host); if (rc) return rc; }
     const double k = (double)rb->kept;
     for (int64_t p = 0; p < s->nnz; ++p) wmean_host[p] /= k;
     return BPMF_HIP_OK;

@@ -28,7 +28,7 @@ int launch_sampler(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, do
     // stateful path has enqueued the kernel already, ahead of its wait for the gate kernel (bpmf_hip_sys_sample).
     // censored side: the same for the latent values of its censored entries (capi_censor.hip).
     // robust side: the same for its per-rating weights (capi_robust.hip).
-    if ((self->probit || self->ordinal || self->censor || self->robust) && !self->probit_latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
+    if (!self->latent_queued) { const int rp = latent_enqueue(self, other, iter, alpha, st); if (rp) return rp; }
     if (!second_copy_usable(self)) return sampler_into<K, F32>(self, self->d_items, other, iter, alpha, d_in, st, ev_start, ev_stop);
     // the copy about to be overwritten may still be read by an evaluation that has not been collected
     int rc = claim_second_copy(self, st);
@@ -256,7 +256,7 @@ extern "C" int bpmf_hip_sample_side_launch(bpmf_hip_side *self, const bpmf_hip_s
         return fail(BPMF_HIP_EINVAL, "sample_side: the side has features: step it with bpmf_hip_link_sample");
     if (self->implicit && !self->implicit->in_call)
         return fail(BPMF_HIP_EINVAL, "sample_side: the side is implicit: step it with bpmf_hip_implicit_sample");
-    self->probit_latent_queued = false;                               // (a stateful call that failed half-way may have left it set)
+    self->latent_queued = false;                                      // (a stateful call that failed half-way may have left it set)
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sample_side: the communicator of this context was aborted (a collective timed out)");
     const int K = c->K;
     HIP_TRY(hipSetDevice(c->device));
@@ -299,10 +299,7 @@ int read_result_blob(bpmf_hip_side *s, double *h_out, double *sum_out, double *p
 {
     const int K = s->ctx->K, Kt = s->ctx->Kt;
     int rc = check_timeout(h_out, K, msg);
-    if (!rc) rc = check_probit(s, msg);                   // (the latent kernel ran ahead of the sampler whose sums these are)
-    if (!rc) rc = check_ordinal(s, msg);
-    if (!rc) rc = check_censor(s, msg);
-    if (!rc) rc = check_robust(s, msg);
+    if (!rc) rc = check_latent(s, msg);                   // (the latent kernel ran ahead of the sampler whose sums these are)
     if (rc) return rc;
     const double *prod = h_out + blob::res_prod(K), *sum = h_out + blob::res_sum(K);
     const unsigned long long f = *blob::res_fail_word(h_out, K);
@@ -762,10 +759,10 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     // host chain (sums -> cov -> Normal-Wishart -> staging) is still at work.  Fused form: the same place in the queue as
     // before, directly ahead of the sampler launch that carries its own gate.  The latent kernel of a censored side and the weight
     // kernel of a robust side: likewise.
-    self->probit_latent_queued = false;
-    if (self->probit || self->ordinal || self->censor || self->robust) {
+    self->latent_queued = false;
+    if (likelihood(self) != Likelihood::gaussian) {
         if ((rc = latent_enqueue(self, other, iter, alpha, s0))) return rc;
-        self->probit_latent_queued = true;
+        self->latent_queued = true;
     }
     if (fused) {
         fz.gate_host = self->a_gate.dev(); fz.gate_want = (unsigned)(iter + 1); fz.src_host = self->a_h_in.dev();
@@ -803,7 +800,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, self->a_d_in.get(), s0, (ride && timed) ? ev[0] : nullptr,
                                                     ride ? ev[1] : nullptr));
     self->cur_gate_flag = nullptr;
-    self->probit_latent_queued = false;
+    self->latent_queued = false;
     self->cur_fused = bpmf::FusedArgs{};
     self->cur_riders = bpmf::StatRiders{};
     bpmf_launch::next_flags() = 0;                                    // (a sampler sequence without a kernel leaves it pending)

@@ -1,4 +1,5 @@
-// capi_side.hip -- static work schedule of a side, side create / destroy, factor storage, priors, launch reports
+// capi_side.hip -- static work schedule of a side, side create / destroy, factor storage, priors, launch reports; the table of the
+// refusals the add-ons give each other and the read-back of a side's latent step (capi_internal.h: refuse, latent_read_back)
 // (one of the translation units of the C ABI of include/bpmf_hip.h: see capi_internal.h for the map)
 #include "capi_internal.h"
 
@@ -365,6 +366,41 @@ int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_si
 
 int ensure_colptr(bpmf_hip_side *s) { return s->d_colptr ? 0 : s->d_colptr.upload(s->h_colptr.data(), s->h_colptr.size()); }
 
+int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> order)
+{
+    static const char *const kSentence[] = {"not on a probit side (bpmf_hip_side_set_probit)",
+                                            "not on an ordinal side (bpmf_hip_side_set_ordinal)",
+                                            "not on a censored side (bpmf_hip_side_set_censored)",
+                                            "not on a side with Student-t noise (bpmf_hip_side_set_robust)",
+                                            "not on a side with per-rating weights (bpmf_hip_side_set_weights)",
+                                            "not together with features (bpmf_hip_side_set_features)",
+                                            "not together with propagated priors",
+                                            "not together with the BPMF_REDUCE formulation"};
+    const bool holds[] = {(bool)s->probit, (bool)s->ordinal, (bool)s->censor, (bool)s->robust, (bool)s->weights,
+                          (bool)s->link, (bool)s->d_prop, s->reduce_on};
+    for (const Not n : order)
+        if (holds[(int)n]) return fail(BPMF_HIP_EINVAL, std::string(who) + ": " + kSentence[(int)n]);
+    return 0;
+}
+
+int latent_settle(const char *func, bpmf_hip_side *s)
+{
+    bpmf_hip_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = settle_async(s); if (rc) return rc; }
+    { const int rs = bounded_stream_sync(c, c->stream.get(), func); if (rs) return rs; }
+    std::string m;
+    return check_latent(s, &m) ? fail(BPMF_HIP_ENUM, m) : 0;
+}
+
+int latent_read_back(const char *func, bpmf_hip_side *s, const double *z, double *z_host)
+{
+    const int rc = latent_settle(func, s);
+    if (rc) return rc;
+    if (s->nnz > 0) HIP_TRY(hipMemcpy(z_host, z, (size_t)s->nnz * sizeof(double), hipMemcpyDeviceToHost));
+    return BPMF_HIP_OK;
+}
+
 extern "C" int64_t bpmf_hip_live_device_bytes(void) { return g_live_bytes.load(std::memory_order_relaxed); }
 extern "C" int64_t bpmf_hip_live_core_bytes(void) { return g_core_bytes.load(std::memory_order_relaxed); }
 extern "C" int64_t bpmf_hip_stream_drains(void) { return g_stream_drains.load(std::memory_order_relaxed); }
@@ -390,9 +426,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: NULL");
     (void)mu;
-    if (Lambda && s->robust) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on a side with Student-t noise (bpmf_hip_side_set_robust)");
-    if (Lambda && s->weights) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on a side with per-rating weights (bpmf_hip_side_set_weights)");
-    if (Lambda && s->ordinal) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: not on an ordinal side (bpmf_hip_side_set_ordinal)");
+    if (Lambda) { const int rf = refuse("set_prop_posterior", s, {Not::robust, Not::weights, Not::ordinal}); if (rf) return rf; }
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }

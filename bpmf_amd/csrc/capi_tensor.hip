@@ -187,7 +187,8 @@ extern "C" bpmf_hip_side *bpmf_hip_tensor_side(bpmf_hip_tensor *t, int m)
 // a mode's side may carry the sample ring, the hyper ring and the -o aggregates; everything that changes what its sampler reads is refused
 static int check_plain_mode(const char *who, const bpmf_hip_side *s)
 {
-    const char *what = s->probit ? "a probit likelihood" : s->ordinal ? "an ordinal likelihood" : s->censor ? "censored ratings" : s->robust ? "Student-t noise" : s->weights ? "per-rating weights"
+    static const char *const kKind[] = {nullptr, "a probit likelihood", "an ordinal likelihood", "censored ratings", "Student-t noise"};
+    const char *what = latent_step(s) ? kKind[(int)likelihood(s)] : s->weights ? "per-rating weights"
                        : s->link ? "features" : s->d_prop.get() ? "propagated priors" : s->reduce_on ? "the BPMF_REDUCE formulation" : nullptr;
     if (what) return fail(BPMF_HIP_EINVAL, std::string(who) + ": not together with " + what + " on a mode of a tensor");
     if (s->ctx->comm || sharded(s)) return fail(BPMF_HIP_EINVAL, std::string(who) + ": needs the tensor whole on one GPU, on a context without a communicator");

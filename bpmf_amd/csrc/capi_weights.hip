@@ -14,14 +14,8 @@ extern "C" int bpmf_hip_side_set_weights(bpmf_hip_side *s, const double *w)
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an fp32 context");
     if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an implicit side (bpmf_hip_side_set_implicit takes the confidences itself)");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a side with Student-t noise (bpmf_hip_side_set_robust redraws the weights itself)");
-    if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a probit side (bpmf_hip_side_set_probit)");
-    if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a censored side (bpmf_hip_side_set_censored)");
-    if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an ordinal side (bpmf_hip_side_set_ordinal)");
-    if (s->link) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with features (bpmf_hip_side_set_features)");
-    if (s->d_prop) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with propagated priors");
-    if (s->reduce_on) return fail(BPMF_HIP_EINVAL, "side_set_weights: not together with the BPMF_REDUCE formulation");
-    int rc = require_single_gpu("side_set_weights", c, s);
-    if (rc) return rc;
+    int rc = refuse("side_set_weights", s, {Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
+    if (rc || (rc = require_single_gpu("side_set_weights", c, s))) return rc;
     for (int64_t p = 0; p < s->nnz; ++p)
         if (!(w[p] > 0.0) || !std::isfinite(w[p])) {
             char v[32];
@@ -58,11 +52,7 @@ extern "C" int bpmf_hip_side_weights_get(bpmf_hip_side *s, double *sw_host, doub
     if (!s) return fail(BPMF_HIP_EINVAL, "side_weights_get: NULL argument");
     if (!s->weights) return fail(BPMF_HIP_EINVAL, "side_weights_get: the side has no weights (bpmf_hip_side_set_weights)");
     HIP_TRY(hipSetDevice(s->ctx->device));
-    if (s->robust) {                                                  // (redrawn per launch: the arrays the side's newest launch read)
-        { const int rc = settle_async(s); if (rc) return rc; }
-        { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }
-        { std::string m; if (check_robust(s, &m)) return fail(BPMF_HIP_ENUM, m); }
-    }
+    if (s->robust) { const int rc = latent_settle(__func__, s); if (rc) return rc; }     // (redrawn per launch: the arrays the side's newest launch read)
     const size_t n = (size_t)s->nnz;
     if (sw_host && n > 0) HIP_TRY(hipMemcpy(sw_host, s->weights->sw.get(), n * sizeof(double), hipMemcpyDeviceToHost));
     if (zw_host && n > 0) HIP_TRY(hipMemcpy(zw_host, s->weights->zw.get(), n * sizeof(double), hipMemcpyDeviceToHost));

@@ -1,5 +1,6 @@
 // ext_state.h -- what the add-ons of a side own on the device (included by state.h): bpmf_hip_side holds one owning pointer per
-// add-on, NULL while the side has none; everything below is released when that pointer is reset.
+// add-on, NULL while the side has none; everything below is released when that pointer is reset.  The four add-ons with a latent
+// step (probit, ordinal, censored, robust) derive from bpmf_latent; state.h tells which of them a side is.
 #pragma once
 #include <limits>
 #include <memory>
@@ -33,29 +34,34 @@ struct CgWork {
 
 }  // namespace bpmf_launch
 
+// The latent step of a side: the kernel that a probit, an ordinal, a censored or a robust side runs ahead of every one of its sampler
+// launches (a side is at most one of the four: state.h has the kind and check_latent).  What the four share: the word the kernel raises
+// to a rating position it could not draw (~0: none; the kind says why), and the tag of the side's Philox streams.
+struct bpmf_latent { Pinned<unsigned long long> fail; uint32_t tag = 0; };
+
 // probit likelihood (capi_probit.hip): the latent scores (layout of d_vals; the samplers read them in its
-// place), the sign of every rating, and a word the latent kernel raises to a rating position when a draw runs into its attempt cap
-struct bpmf_probit { DevBuf<double> z; DevBuf<int8_t> sign; Pinned<unsigned long long> fail; uint32_t tag = 0; };
+// place) and the sign of every rating; the word is raised when a draw runs into its attempt cap
+struct bpmf_probit : bpmf_latent { DevBuf<double> z; DevBuf<int8_t> sign; };
 
 // ordinal probit likelihood (capi_ordinal.hip): the latent scores (layout of d_vals; the samplers read them in
 // its place), the level 0 .. C - 1 of every rating, the C level values, the cutpoint table -inf, g_1 .. g_{C-1}, +inf on the host and
-// two tables on the device (the current one and a proposal), the partials of the log-likelihood pass (2 x blocks, then the two sums),
-// and the word the latent kernel raises to a rating position whose dot product is not finite
-struct bpmf_ordinal {
+// two tables on the device (the current one and a proposal), the partials of the log-likelihood pass (2 x blocks, then the two sums);
+// the word is raised at a rating whose dot product is not finite
+struct bpmf_ordinal : bpmf_latent {
     DevBuf<double> z; DevBuf<uint8_t> level; DevBuf<double> g, g_prop, part;
-    Pinned<unsigned long long> fail; uint32_t tag = 0; int nlev = 0;
+    int nlev = 0;
     std::vector<double> levels, cut;                        // C values; C + 1 table entries
     int64_t loglik_launches = 0;                            // log-likelihood passes enqueued so far (bpmf_hip_side_ordinal_info)
 };
 
 // censored ratings (capi_censor.hip): the censored entries of the side as compact lists (position in the CSC,
-// column, row, +1 = the rating is a lower bound / -1 = an upper bound), the latent values (layout of d_vals: a copy of the ratings
-// of which only the censored positions are ever rewritten; the samplers read it in place of d_vals), and the word the latent kernel
-// raises to a rating position when a draw runs into its attempt cap
-struct bpmf_censor {
+// column, row, +1 = the rating is a lower bound / -1 = an upper bound) and the latent values (layout of d_vals: a copy of the ratings
+// of which only the censored positions are ever rewritten; the samplers read it in place of d_vals); the word is raised when a draw
+// runs into its attempt cap
+struct bpmf_censor : bpmf_latent {
     DevBuf<int64_t> pos; DevBuf<int32_t> col, row; DevBuf<int8_t> sign;
-    DevBuf<double> z; Pinned<unsigned long long> fail;
-    int64_t n = 0, nright = 0, nleft = 0; uint32_t tag = 0;
+    DevBuf<double> z;
+    int64_t n = 0, nright = 0, nleft = 0;
 };
 
 // per-rating precision weights (capi_weights.hip): sw = sqrt(w) and zw = sqrt(w) (r - mean_rating) of every rating
@@ -71,8 +77,8 @@ struct bpmf_implicit { double w0 = 0.0; bool in_call = false; DevBuf<double> gra
 
 // Student-t noise (capi_robust.hip): the side's bpmf_weights are redrawn on the device ahead of every sampler
 // launch.  nu: the degrees of freedom; wsum: the running sum of w over the kept samples (layout of d_vals), `kept` of them; the word
-// the weight kernel raises to a rating position when a draw runs into its attempt cap or meets a residual that is not finite
-struct bpmf_robust { double nu = 0.0; uint32_t tag = 0; DevBuf<double> wsum; int kept = 0; Pinned<unsigned long long> fail; };
+// is raised when a draw runs into its attempt cap or meets a residual that is not finite
+struct bpmf_robust : bpmf_latent { double nu = 0.0; DevBuf<double> wsum; int kept = 0; };
 
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
 struct bpmf_link_dense {

@@ -58,26 +58,14 @@ int link_gemm_nn(const LinkNnLaunch &p, hipStream_t st)
     return 0;
 }
 
-template <int K>
-static void residual_launch(const LinkResidualLaunch &p, unsigned grid, hipStream_t st)
-{
-    hipLaunchKernelGGL((bpmf::k_link_residual<K>), dim3(grid), dim3(bpmf::kProbitTile), 0, st, p.colptr, p.ncols, p.rowidx, p.vals, p.nnz,
-                       p.offs, p.other, p.kt, p.out);
-}
-
 int link_residual(const LinkResidualLaunch &p, hipStream_t st)
 {
-    if (p.nnz <= 0) return 0;
-    const unsigned grid = (unsigned)((p.nnz + bpmf::kProbitTile - 1) / bpmf::kProbitTile);
-    switch (p.K) {
-    case 8: residual_launch<8>(p, grid, st); break;
-    case 16: residual_launch<16>(p, grid, st); break;
-    case 32: residual_launch<32>(p, grid, st); break;
-    case 64: residual_launch<64>(p, grid, st); break;
-    case 128: residual_launch<128>(p, grid, st); break;
-    default: return -1;
-    }
-    return 0;
+    if (p.m.nnz <= 0) return 0;
+    const unsigned grid = (unsigned)((p.m.nnz + bpmf::kProbitTile - 1) / bpmf::kProbitTile);
+    return dispatch_k(p.K, [&](auto k) {
+        hipLaunchKernelGGL((bpmf::k_link_residual<decltype(k)::value>), dim3(grid), dim3(bpmf::kProbitTile), 0, st, p.m.colptr, p.m.ncols, p.m.rowidx,
+                           p.vals, p.m.nnz, p.offs, p.other, p.kt, p.out);
+    });
 }
 
 void link_shift(double *items, const double *offs, int64_t total, double *partial, hipStream_t st)

@@ -4,27 +4,15 @@
 
 namespace bpmf_launch {
 
-template <int K>
-static void weights_launch(const RobustWeightsLaunch &p, unsigned grid, hipStream_t st)
-{
-    hipLaunchKernelGGL((bpmf::k_robust_weights<K, double>), dim3(grid), dim3(bpmf::kProbitTile), 0, st, p.colptr, p.ncols, p.rowidx, p.vals,
-                       p.nnz, (const double *)p.items, (const double *)p.other, p.kt, p.iter, p.tag, p.mean, p.sqrt_alpha, p.nu, p.dd, p.c,
-                       p.sw, p.zw, p.fail);
-}
-
 int robust_weights(const RobustWeightsLaunch &p, hipStream_t st)
 {
-    if (p.nnz <= 0) return 0;
-    const unsigned grid = (unsigned)((p.nnz + bpmf::kProbitTile - 1) / bpmf::kProbitTile);     // one tile of ratings per workgroup
-    switch (p.K) {
-    case 8: weights_launch<8>(p, grid, st); break;
-    case 16: weights_launch<16>(p, grid, st); break;
-    case 32: weights_launch<32>(p, grid, st); break;
-    case 64: weights_launch<64>(p, grid, st); break;
-    case 128: weights_launch<128>(p, grid, st); break;
-    default: return -1;
-    }
-    return 0;
+    if (p.m.nnz <= 0) return 0;
+    const unsigned grid = (unsigned)((p.m.nnz + bpmf::kProbitTile - 1) / bpmf::kProbitTile);   // one tile of ratings per workgroup
+    return dispatch_k(p.f.K, [&](auto k) {
+        hipLaunchKernelGGL((bpmf::k_robust_weights<decltype(k)::value, double>), dim3(grid), dim3(bpmf::kProbitTile), 0, st, p.m.colptr, p.m.ncols,
+                           p.m.rowidx, p.vals, p.m.nnz, (const double *)p.f.items, (const double *)p.f.other, p.f.kt, p.iter, p.tag, p.mean,
+                           p.sqrt_alpha, p.nu, p.dd, p.c, p.sw, p.zw, p.fail);
+    });
 }
 
 void robust_accumulate(const double *sw, int64_t nnz, double *wsum, hipStream_t st)

@@ -4,6 +4,8 @@
 #pragma once
 #include "state.h"
 
+#include <type_traits>
+
 // one kernel launch of a sampler sequence: events ride on the dispatch packet when given, the pending launch flags are consumed
 // (EVERY kernel of a sampler sequence must be launched through this macro: bpmf_hip_side_kernel_resources runs the dispatch
 //  logic over live factor pointers with a probe installed, and only this macro knows not to launch then)
@@ -226,11 +228,40 @@ int predict_cells(const PredCellsLaunch &p, hipStream_t st);   // -1: shape not 
 void samples_pack(const double *ring, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int s_from, int n, double *packed, hipStream_t st);
 void samples_unpack(const double *packed, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int n, double *ring, hipStream_t st);
 
+// What the launch structs of the add-ons below share, filled by factor_pair / side_csc (capi_internal.h):
+struct FactorPair { const void *items, *other; bool f32; int K, kt; };   // both factor matrices (leading dimension K; floats if f32), the caller's num_latent kt
+struct SideCsc { const int64_t *colptr; int64_t ncols; const int32_t *rowidx; int64_t nnz; };   // a side's ratings: column pointers (ncols + 1) and row ids, on the device
+
+// The instantiated num_latent as a compile-time constant: fn(std::integral_constant<int, K>) for K = 8, 16, 32, 64, 128 -- the
+// launcher units with fp64 kernels only.  -1 for any other K: fn is not called, nothing is launched.
+template <typename Fn>
+inline int dispatch_k(int K, Fn &&fn)
+{
+    switch (K) {
+    case 8: fn(std::integral_constant<int, 8>{}); return 0;
+    case 16: fn(std::integral_constant<int, 16>{}); return 0;
+    case 32: fn(std::integral_constant<int, 32>{}); return 0;
+    case 64: fn(std::integral_constant<int, 64>{}); return 0;
+    case 128: fn(std::integral_constant<int, 128>{}); return 0;
+    }
+    return -1;
+}
+// ... and with the element type of the factors as a second argument (a value of it): double at every size, float at K = 128 alone
+template <typename Fn>
+inline int dispatch_kt(int K, bool f32, Fn &&fn)
+{
+    if (f32) {
+        if (K != 128) return -1;
+        fn(std::integral_constant<int, 128>{}, float{});
+        return 0;
+    }
+    return dispatch_k(K, [&](auto k) { fn(k, double{}); });
+}
+
 // training residuals for the adaptive noise precision (kernels_noise.h, knoise.hip)
 struct SseLaunch {
-    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
-    const int32_t *rowidx; const double *vals; int64_t nnz;
-    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    SideCsc m; const double *vals;
+    FactorPair f;
     double mean;
     double *partial; int nblk;                             // nblk partials, then the sum
 };
@@ -240,16 +271,15 @@ int train_sse(const SseLaunch &p, hipStream_t st);         // -1: unsupported K 
 
 // probit likelihood (kernels_probit.h, kprobit.hip)
 struct ProbitLatentLaunch {
-    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
-    const int32_t *rowidx; const int8_t *sign; int64_t nnz;
-    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    SideCsc m; const int8_t *sign;
+    FactorPair f;
     uint32_t iter, tag;
     double *z;                                             // the latent scores, layout of the side's ratings
     unsigned long long *fail;                              // raised (rating position) when a draw runs into the attempt cap
 };
 struct ProbitProbLaunch {
     const int32_t *tcol, *trow; int64_t nnz;               // column and row of every test entry
-    const void *items, *other; bool f32; int K, kt;
+    FactorPair f;
     double *sum;                                           // running sums of Phi(x . y) per test entry
 };
 void probit_sign(const double *vals, int64_t nnz, double threshold, int8_t *sign, hipStream_t st);
@@ -258,24 +288,22 @@ int probit_prob(const ProbitProbLaunch &p, hipStream_t st);
 
 // ordinal probit likelihood (kernels_ordinal.h, kordinal.hip)
 struct OrdinalLatentLaunch {
-    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
-    const int32_t *rowidx; const uint8_t *level; int64_t nnz;   // level: 0 .. nlev - 1 per rating
-    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    SideCsc m; const uint8_t *level;                       // level: 0 .. nlev - 1 per rating
+    FactorPair f;
     uint32_t iter, tag;
     const double *g; int nlev;                             // the cutpoint table on the device: -inf, g_1 .. g_{C-1}, +inf (nlev + 1 doubles)
     double *z;                                             // the latent scores, layout of the side's ratings
     unsigned long long *fail;                              // raised (rating position) when a dot product is not finite
 };
 struct OrdinalLoglikLaunch {
-    const int64_t *colptr; int64_t ncols;
-    const int32_t *rowidx; const uint8_t *level; int64_t nnz;
-    const void *items, *other; bool f32; int K, kt;
+    SideCsc m; const uint8_t *level;
+    FactorPair f;
     const double *g0, *g1; int nlev;                       // two cutpoint tables
     double *partial;                                       // 2 x ordinal_blocks(nnz) partials, then the two sums
 };
 struct OrdinalProbLaunch {
     const int32_t *tcol, *trow; int64_t nnz;               // column and row of every test entry
-    const void *items, *other; bool f32; int K, kt;
+    FactorPair f;
     const double *g; int nlev;
     double *sum;                                           // nlev x nnz running sums of the level probabilities
 };
@@ -288,7 +316,7 @@ int ordinal_prob(const OrdinalProbLaunch &p, hipStream_t st);
 struct CensorLatentLaunch {
     const int64_t *pos; const int32_t *col, *row; const int8_t *sign; int64_t n;   // the censored entries: position in the CSC, column, row, +-1
     const double *vals;                                    // the side's ratings: vals[pos] is the bound
-    const void *items, *other; bool f32; int K, kt;        // both factor matrices (leading dimension K), the caller's num_latent kt
+    FactorPair f;
     uint32_t iter, tag;
     double mean, sqrt_alpha, inv_sqrt_alpha;               // the side's mean rating; sqrt(alpha) and 1 / sqrt(alpha), formed on the host
     double *z;                                             // the latent values, layout of the side's ratings: z[pos] is written
@@ -298,9 +326,8 @@ int censor_latent(const CensorLatentLaunch &p, hipStream_t st);  // -1: unsuppor
 
 // Student-t noise (kernels_robust.h, krobust.hip): fp64 factors only
 struct RobustWeightsLaunch {
-    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
-    const int32_t *rowidx; const double *vals; int64_t nnz;
-    const void *items, *other; int K, kt;                  // both factor matrices (leading dimension K), the caller's num_latent kt
+    SideCsc m; const double *vals;
+    FactorPair f;                                          // (fp64 factors: f.f32 is not read)
     uint32_t iter, tag;
     double mean, sqrt_alpha, nu;                           // the side's mean rating; sqrt(alpha), formed on the host; the degrees of freedom
     double dd, c;                                          // a - 1 / 3 and 1 / sqrt(9 dd) of the shape a = (nu + 1) / 2, formed on the host
@@ -335,8 +362,7 @@ struct LinkNnLaunch {                                      // C (N x ncw, leadin
     double *C; int64_t ldc; int ncw;                       // n <= ncw <= 128
 };
 struct LinkResidualLaunch {
-    const int64_t *colptr; int64_t ncols;                  // the side's column pointers (ncols + 1, on the device)
-    const int32_t *rowidx; const double *vals; int64_t nnz;
+    SideCsc m; const double *vals;
     const double *offs, *other; int K, kt;                 // the side's offsets and the other side's factors (leading dimension K)
     double *out;                                           // vals - offs_c . other_r, layout of vals
 };

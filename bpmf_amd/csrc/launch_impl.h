@@ -26,17 +26,15 @@ int sampler_into(bpmf_hip_side *self, double *out_items, const bpmf_hip_side *ot
     using namespace bpmf;
     bpmf_hip_ctx *c = self->ctx;
     SampleArgs a = blob_args(self, out_items, d_in, iter, alpha);
-    // probit side: the latent scores stand in for the ratings; censored side: the ratings with a fresh draw at every censored
-    // position (capi_censor.hip); side with features: the residuals r - m_c . y_r (capi_link.hip)
-    // (an ordinal side: its latent scores, as a probit side)
-    const double *vals = self->probit ? self->probit->z.get() : self->ordinal ? self->ordinal->z.get() : self->censor ? self->censor->z.get() : self->link ? self->link->r.get() : self->d_vals;
+    // the ratings, or what stands in for them: latent scores / values, residuals (state.h)
+    const double *vals = sampler_values(self);
     a.rowidx = self->d_rowidx; a.vals = vals;
     // side with per-rating weights (capi_weights.hip): the weighted form of the side's family reads
     // zw = sqrt(w) (r - mean) as its values with mean 0 and multiplies every gathered row by sw = sqrt(w)
     const bool wt = self->weights != nullptr;
     if (wt) {
         if constexpr (F32) return fail(BPMF_HIP_EINVAL, "per-rating weights: not on an fp32 context");
-        if (self->probit || self->ordinal || self->censor || self->link || self->d_prop || self->reduce_on)
+        if (!reads_own_ratings(self) || self->d_prop || self->reduce_on)        // (a robust side has weights and passes)
             return fail(BPMF_HIP_EINVAL, "per-rating weights: not together with probit, censored ratings, features, propagated priors or BPMF_REDUCE");
         a.vals = self->weights->zw.get(); a.sw = self->weights->sw.get(); a.mean_rating = 0.0;
     }

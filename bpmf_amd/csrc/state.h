@@ -218,7 +218,7 @@ struct bpmf_hip_side {
     std::unique_ptr<bpmf_foldin> foldin;   // fold-in: the per-sample hyper-parameters and the folded-in rows (bpmf_hip_side_hyper_reserve, bpmf_hip_foldin)
     std::unique_ptr<bpmf_sse> sse;         // partials of the training residuals (bpmf_hip_train_sse)
     DevBuf<int64_t> d_colptr;              // the column pointers on the device, uploaded when an add-on first needs them (ensure_colptr)
-    bool probit_latent_queued = false;   // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
+    bool latent_queued = false;          // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
     int chunk = 0;                         // ratings per work item above which a column is cut (BPMF_HIP_CHUNK or the automatic value, rounded up to 16)
@@ -342,13 +342,51 @@ struct bpmf_hip_side {
     } predraw;
 };
 
+// The likelihood of a side's ratings: the setters see to it that a side is at most one of the four that are not Gaussian.
+enum class Likelihood { gaussian, probit, ordinal, censored, robust };
+inline Likelihood likelihood(const bpmf_hip_side *s)
+{
+    return s->probit ? Likelihood::probit : s->ordinal ? Likelihood::ordinal : s->censor ? Likelihood::censored
+           : s->robust ? Likelihood::robust : Likelihood::gaussian;
+}
+// the latent step of the side (ext_state.h), NULL on a Gaussian side
+inline bpmf_latent *latent_step(const bpmf_hip_side *s)
+{
+    switch (likelihood(s)) {
+    case Likelihood::probit: return s->probit.get();
+    case Likelihood::ordinal: return s->ordinal.get();
+    case Likelihood::censored: return s->censor.get();
+    case Likelihood::robust: return s->robust.get();
+    case Likelihood::gaussian: break;
+    }
+    return nullptr;
+}
+// what the samplers of the side read as its values (layout of d_vals): the latent scores of a probit or an ordinal side, the ratings
+// with a fresh draw at every censored position (capi_censor.hip), the residuals r - m_c . y_r of a side with features
+// (capi_link.hip), else the ratings themselves
+inline const double *sampler_values(const bpmf_hip_side *s)
+{
+    switch (likelihood(s)) {
+    case Likelihood::probit: return s->probit->z.get();
+    case Likelihood::ordinal: return s->ordinal->z.get();
+    case Likelihood::censored: return s->censor->z.get();
+    default: return s->link ? s->link->r.get() : s->d_vals;
+    }
+}
+// ... and whether those are the side's own ratings
+inline bool reads_own_ratings(const bpmf_hip_side *s)
+{
+    const Likelihood k = likelihood(s);
+    return (k == Likelihood::gaussian || k == Likelihood::robust) && !s->link;
+}
+
 // Does a k_sample1 launch of the side read its gather stream?  The stream holds r - mean_rating of the side's OWN ratings:
 // a probit, censored or side-information launch reads other values in their place and keeps the index-block form
 // (k_sample1i), and so does the hot-row profiling switch (BPMF_HIP_ABLATE & 4), which rewrites the row ids.  A weighted side
 // never reads it either: a record has no room for sqrt(w) (k_sample1w, the weighted index-block form).
 inline bool uses_gather_stream(const bpmf_hip_side *s)
 {
-    return s->d_gs_rec && s->mode == 1 && !s->probit && !s->ordinal && !s->censor && !s->link && !s->weights && !(s->ctx->ablate & 4u);
+    return s->d_gs_rec && s->mode == 1 && reads_own_ratings(s) && !s->weights && !(s->ctx->ablate & 4u);
 }
 
 struct bpmf_hip_test {
@@ -390,51 +428,23 @@ inline int check_timeout(double *h_blob, int K, std::string *msg)
     return BPMF_HIP_ENODEV;
 }
 
-// probit: did a latent draw of this side run into its attempt cap?  Checked where a half-iteration's results are collected.
-inline int check_probit(bpmf_hip_side *s, std::string *msg)
+// Did the latent kernel of this side (probit, ordinal, censored, robust) raise its word -- a draw that ran into its attempt cap, a
+// dot product or residual that is not finite?  Checked where a half-iteration's results are collected; the word is reset.
+inline int check_latent(bpmf_hip_side *s, std::string *msg)
 {
-    if (!s->probit) return 0;
-    unsigned long long *word = s->probit->fail.host();
+    static const char *const kBefore[] = {"", "probit: the truncated-normal draw of rating ", "ordinal: the score of rating ",
+                                          "censored: the truncated-normal draw of rating ", "robust: the weight of rating "};
+    static const char *const kAfter[] = {"", " was rejected 64 times (non-finite factors?)", " is not finite (non-finite factors?)",
+                                         " was rejected 64 times (non-finite factors?)",
+                                         " could not be drawn: 64 rejections, or a residual that is not finite (non-finite factors?)"};
+    bpmf_latent *l = latent_step(s);
+    if (!l) return 0;
+    unsigned long long *word = l->fail.host();
     const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
     if (v == ~0ull) return 0;
     __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
-    *msg = "probit: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
-    return BPMF_HIP_ENUM;
-}
-
-// ordinal probit: did the latent kernel of this side meet a dot product that is not finite?
-inline int check_ordinal(bpmf_hip_side *s, std::string *msg)
-{
-    if (!s->ordinal) return 0;
-    unsigned long long *word = s->ordinal->fail.host();
-    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    if (v == ~0ull) return 0;
-    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
-    *msg = "ordinal: the score of rating " + std::to_string(v) + " is not finite (non-finite factors?)";
-    return BPMF_HIP_ENUM;
-}
-
-// censored ratings: the same for the latent draw of a censored side
-inline int check_censor(bpmf_hip_side *s, std::string *msg)
-{
-    if (!s->censor) return 0;
-    unsigned long long *word = s->censor->fail.host();
-    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    if (v == ~0ull) return 0;
-    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
-    *msg = "censored: the truncated-normal draw of rating " + std::to_string(v) + " was rejected 64 times (non-finite factors?)";
-    return BPMF_HIP_ENUM;
-}
-
-// Student-t noise: the same for the Gamma draw of a robust side's weights
-inline int check_robust(bpmf_hip_side *s, std::string *msg)
-{
-    if (!s->robust) return 0;
-    unsigned long long *word = s->robust->fail.host();
-    const unsigned long long v = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    if (v == ~0ull) return 0;
-    __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
-    *msg = "robust: the weight of rating " + std::to_string(v) + " could not be drawn: 64 rejections, or a residual that is not finite (non-finite factors?)";
+    const int k = (int)likelihood(s);
+    *msg = kBefore[k] + std::to_string(v) + kAfter[k];
     return BPMF_HIP_ENUM;
 }
 
