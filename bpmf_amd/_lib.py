@@ -128,6 +128,14 @@ _SIGNATURES = {
     "bpmf_hip_side_set_robust": (C.c_int, [C.c_void_p, C.c_double, C.c_uint]),
     "bpmf_hip_side_robust_add": (C.c_int, [C.c_void_p]),
     "bpmf_hip_side_robust_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "bpmf_hip_side_set_bias": (C.c_int, [C.c_void_p, C.c_double, C.c_uint, C.c_int]),
+    "bpmf_hip_side_bias_get": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_bias_set": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_bias_latent": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bpmf_hip_side_bias_add": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_side_bias_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "bpmf_hip_side_bias_prior": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "bpmf_hip_side_bias_lambda_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bpmf_hip_tensor_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                                          C.POINTER(C.c_void_p)]),
     "bpmf_hip_tensor_destroy": (C.c_int, [C.c_void_p]),

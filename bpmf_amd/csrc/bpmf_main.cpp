@@ -226,6 +226,12 @@ void usage()
               << "              stops dragging its factors; -o DIR also gets robust-weights.sdm, the posterior-mean weight of every training\n"
               << "              cell (one GPU, no -g; not with --weights, --probit, --censored, --noise adaptive, --row-features /\n"
               << "              --col-features, -m / -l, --fp32, --topn-score prob|ei or BPMF_REDUCE=1)\n"
+              << "  [--bias] [--bias-lambda F] [--bias-prior A0,B0]: row and column offsets, r = mean + b_row + c_col + u . v with b, c ~ N(0, 1 / F)\n"
+              << "              (F = 1 unless given), redrawn on the device in every half-iteration; with --bias-prior F is sampled too, Gamma(A0,\n"
+              << "              rate B0) a priori, one per side.  The RMSE columns include the offsets and --topn / --rank-eval rank with them (-d <= 126);\n"
+              << "              -o DIR also gets row-bias.ddm and col-bias.ddm (their posterior means, 1 x rows / 1 x cols) and bias_lambda.csv (one\n"
+              << "              GPU, no -g; not with another likelihood, --weights, --noise adaptive, features, fold-in, --similar, --save-model /\n"
+              << "              --model, -m / -l, --fp32 or BPMF_REDUCE=1)\n"
               << "  [--implicit W0]: implicit feedback: every cell the training matrix does not store is a zero of weight W0 > 0, a stored cell has\n"
               << "              its value and the confidence 1, or its entry of --weights FILE, which must be > W0; mean rating 0; both sides step\n"
               << "              through a blocking half-iteration that forms the Gram matrix of the other side (one GPU, no -g; not with --fp32,\n"
@@ -450,6 +456,10 @@ struct Job {
     int64_t w_count = 0; double w_min = 1.0, w_max = 1.0;            // listed cells whose weight is not 1; the smallest / largest weight
     bool robust = false; double robust_nu = 0.0;                     // --robust NU
     bool implicit = false; double implicit_w0 = 0.0;                 // --implicit W0
+    bool bias = false; double bias_lambda = 1.0;                     // --bias [--bias-lambda F]
+    bool bias_sampled = false; double bias_a0 = 0.0, bias_b0 = 0.0;  // --bias-prior A0,B0
+    std::vector<double> bias_lam_u, bias_lam_m;                      // the precision every iteration's step ran with
+    std::vector<double> bias_u, bias_m;                              // the posterior-mean bias of every user / movie (the run's numbering)
     int rank_eval = 0;                                               // --rank-eval N (0: off)
     bool rank_by_cols = false, rank_thr_given = false;               // --rank-by cols, --rank-threshold F
     double rank_thr = 0.0;
@@ -787,6 +797,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(bpmf_hip_side_set_weights(movies, J.w_m.data()));
         check(bpmf_hip_side_set_weights(users, J.w_u.data()));
     }
+    if (J.bias) {                                            // (streams: tag 13 = movies, 14 = users; roles 0 / 1)
+        check(bpmf_hip_side_set_bias(movies, J.bias_lambda, 13, 0));
+        check(bpmf_hip_side_set_bias(users, J.bias_lambda, 14, 1));
+        if (J.bias_sampled) { check(bpmf_hip_side_bias_prior(movies, J.bias_a0, J.bias_b0)); check(bpmf_hip_side_bias_prior(users, J.bias_a0, J.bias_b0)); }
+    }
     if (J.robust) {                                          // (streams: tag 9 = movies, 10 = users; 7 and 8 are the fold-in's)
         check(bpmf_hip_side_set_robust(movies, J.robust_nu, 9));
         check(bpmf_hip_side_set_robust(users, J.robust_nu, 10));
@@ -902,6 +917,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.weighted)
         os << "weights: " << J.w_count << " of " << J.M.nnz() << " training ratings weighted, min " << J.w_min << ", max " << J.w_max << std::endl;
     if (J.robust) os << "robust: Student-t noise, nu = " << J.robust_nu << std::endl;
+    if (J.bias) {
+        os << "bias: row and column offsets, lambda " << J.bias_lambda;
+        if (J.bias_sampled) os << " sampled (" << J.bias_a0 << ", " << J.bias_b0 << ")" << std::endl;
+        else os << " fixed" << std::endl;
+    }
     if (J.implicit)
         os << "implicit: w0 " << J.implicit_w0 << ", " << J.M.nnz() << " observed of " << nusers << " x " << nmovies << " cells" << std::endl;
     if (linked) {
@@ -980,7 +1000,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(J.implicit ? bpmf_hip_implicit_sample(a, b, alpha) : linked ? bpmf_hip_link_sample(a, b, alpha) : bpmf_hip_sys_sample(a, b, alpha));
     };
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving) {
+    // (--bias: the evaluation of an iteration reads the bias vectors the next one overwrites -- the blocking loop)
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -1042,6 +1063,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
         if (J.robust && aggregate && iter >= burnin) check(bpmf_hip_side_robust_add(movies));
+        if (J.bias && aggregate && iter >= burnin) { check(bpmf_hip_side_bias_add(users)); check(bpmf_hip_side_bias_add(movies)); }
         if (ring_u && iter >= burnin) check(bpmf_hip_side_samples_add(users));
         if (ring_m && iter >= burnin) check(bpmf_hip_side_samples_add(movies));
         if (hyper_u && iter >= burnin) check(bpmf_hip_side_hyper_add(users, J.adaptive ? J.alpha_trace[(size_t)i] : alpha, nullptr, nullptr));
@@ -1100,6 +1122,18 @@ void rank_main(Job &J, int rank, std::ostream &os)
             check(bpmf_hip_side_aggr_finalize(users, nsamples, J.u_mu.data() + (size_t)K * u0, J.u_lambda.data() + (size_t)K * K * u0));
             check(bpmf_hip_side_aggr_finalize(movies, nsamples, J.m_mu.data() + (size_t)K * m0, J.m_lambda.data() + (size_t)K * K * m0));
         }
+    }
+    if (J.bias && aggregate && nsims > 0) {
+        double cur = 0.0;
+        J.bias_lam_u.resize((size_t)nsims); J.bias_lam_m.resize((size_t)nsims);
+        check(bpmf_hip_side_bias_lambda_get(users, &cur, J.bias_lam_u.data(), nsims, nullptr, nullptr));
+        check(bpmf_hip_side_bias_lambda_get(movies, &cur, J.bias_lam_m.data(), nsims, nullptr, nullptr));
+    }
+    if (J.bias && aggregate && nsims > burnin) {                     // one rank (main refuses -g)
+        J.bias_u.resize((size_t)std::max<int64_t>(nusers, 1)); J.bias_m.resize((size_t)std::max<int64_t>(nmovies, 1));
+        check(bpmf_hip_side_bias_mean(users, J.bias_u.data(), nullptr));
+        check(bpmf_hip_side_bias_mean(movies, J.bias_m.data(), nullptr));
+        J.bias_u.resize((size_t)nusers); J.bias_m.resize((size_t)nmovies);
     }
     if (J.robust && aggregate && nsims > burnin) {                   // one rank (main refuses -g)
         J.robust_w.resize((size_t)std::max<int64_t>(J.M.nnz(), 1));
@@ -1460,8 +1494,12 @@ int main(int argc, char *argv[])
                                               {"similar", required_argument, nullptr, 1080}, {"similar-by", required_argument, nullptr, 1081},
                                               {"similar-kind", required_argument, nullptr, 1082}, {"similar-kappa", required_argument, nullptr, 1083},
                                               {"similar-min-ratings", required_argument, nullptr, 1084},
+                                              {"bias", no_argument, nullptr, 1090}, {"bias-lambda", required_argument, nullptr, 1091},
+                                              {"bias-prior", required_argument, nullptr, 1092},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
+    std::string bias_lambda, bias_prior;
+    bool bias_lambda_given = false, bias_prior_given = false;
     bool similar_given = false;
     std::string similar_flag;                                        // the first --similar-* flag given
     std::string topn_by = "rows", noise = "fixed", alpha_prior, alpha_max, probit_threshold, row_features, col_features, lambda_beta, link_tol, link_max_iter, lambda_beta_prior, censored_file, weights_file, robust_nu, new_row_features, new_col_features, fold_in_rows, fold_in_cols;
@@ -1526,6 +1564,9 @@ int main(int argc, char *argv[])
         case 1082: similar_kind = optarg; if (similar_flag.empty()) similar_flag = "--similar-kind"; break;
         case 1083: similar_kappa = optarg; if (similar_flag.empty()) similar_flag = "--similar-kappa"; break;
         case 1084: similar_min = optarg; if (similar_flag.empty()) similar_flag = "--similar-min-ratings"; break;
+        case 1090: training("--bias"); J.bias = true; break;
+        case 1091: training("--bias-lambda"); bias_lambda = optarg; bias_lambda_given = true; break;
+        case 1092: training("--bias-prior"); bias_prior = optarg; bias_prior_given = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1622,6 +1663,7 @@ int main(int argc, char *argv[])
         if (J.censored) die("--tensor does not go together with --censored");
         if (J.weighted) die("--tensor does not go together with --weights");
         if (J.robust) die("--tensor does not go together with --robust");
+        if (J.bias) die("--tensor does not go together with --bias");
         if (J.implicit) die("--implicit does not go together with --tensor (a mode's side is a plain Gaussian side)");
         if (rank_eval_given || rank_by_given || J.rank_thr_given) die("--tensor does not go together with --rank-eval");
         if (noise != "fixed" || !alpha_prior.empty() || !alpha_max.empty()) die("--tensor does not go together with --noise adaptive");
@@ -1870,6 +1912,45 @@ int main(int argc, char *argv[])
             die("--robust does not go together with --topn-score " + topn_score + " (its sigma = 1 / sqrt(alpha) assumes Gaussian noise; mean and ucb are fine)");
         if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--robust does not go together with BPMF_REDUCE=1");
         if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--robust needs a noise precision -a F > 0");
+    }
+    // --bias: checked before anything touches a GPU
+    if ((bias_lambda_given || bias_prior_given) && !J.bias) die(std::string(bias_lambda_given ? "--bias-lambda" : "--bias-prior") + " needs --bias");
+    if (J.bias) {
+        if (bias_prior_given) {
+            char *e1 = nullptr, *e2 = nullptr;
+            const size_t comma = bias_prior.find(',');
+            const std::string sa = bias_prior.substr(0, comma), sb = comma == std::string::npos ? "" : bias_prior.substr(comma + 1);
+            J.bias_a0 = sa.empty() ? NAN : strtod(sa.c_str(), &e1);
+            J.bias_b0 = sb.empty() ? NAN : strtod(sb.c_str(), &e2);
+            if (sa.empty() || sb.empty() || *e1 != '\0' || *e2 != '\0' || !std::isfinite(J.bias_a0) || !(J.bias_a0 > 0.0) || !std::isfinite(J.bias_b0) || !(J.bias_b0 >= 0.0))
+                die("--bias-prior expects A0,B0 with a finite A0 > 0 and a finite B0 >= 0, not '" + bias_prior + "'");
+            J.bias_sampled = true;
+        }
+        if (bias_lambda_given) {
+            char *end = nullptr;
+            J.bias_lambda = bias_lambda.empty() ? NAN : strtod(bias_lambda.c_str(), &end);
+            if (bias_lambda.empty() || *end != '\0' || !std::isfinite(J.bias_lambda) || !(J.bias_lambda > 0.0))
+                die("--bias-lambda expects the precision of the bias prior, a finite number > 0, not '" + bias_lambda + "'");
+        }
+        if (ngpu >= 1) die("--bias runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the bias step needs both sides whole)");
+        if (J.probit) die("--bias does not go together with --probit (a side has one latent step)");
+        if (J.ordinal) die("--bias does not go together with --ordinal (a side has one latent step)");
+        if (J.censored) die("--bias does not go together with --censored (a side has one latent step)");
+        if (J.robust) die("--bias does not go together with --robust (a side has one latent step)");
+        if (J.weighted) die("--bias does not go together with --weights (the bias conditional is unweighted)");
+        if (J.implicit) die("--bias does not go together with --implicit (the bias conditional would run over every cell)");
+        if (tensor_given) die("--bias does not go together with --tensor");
+        if (J.adaptive) die("--bias does not go together with --noise adaptive (the training residuals leave the biases out)");
+        if (linked || !new_row_features.empty() || !new_col_features.empty())
+            die("--bias does not go together with --row-features / --col-features (the residuals would have to be formed from the bias-free values)");
+        if (!fold_in_rows.empty() || !fold_in_cols.empty()) die("--bias does not go together with --fold-in-rows / --fold-in-cols (a folded-in row would need a bias of its own)");
+        if (save_model_given || model_given) die("--bias does not go together with --save-model / --model (the model format stores no biases)");
+        if (similar_given) die("--bias does not go together with --similar (the two bias rows of the sample ring would enter the cosine)");
+        if ((J.topn > 0 || rank_eval_given) && K > 126) die("--bias with --topn / --rank-eval needs -d <= 126 (the sample rings keep two more rows per sample)");
+        if (!mname.empty() || !lname.empty()) die("--bias does not go together with a propagated posterior (-m / -l)");
+        if (fp32) die("--bias does not go together with --fp32 (the bias kernels are fp64)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--bias does not go together with BPMF_REDUCE=1");
+        if (!(J.alpha > 0.0) || !std::isfinite(J.alpha)) die("--bias needs a noise precision -a F > 0");
     }
     // --implicit: checked before anything touches a GPU (the confidences below, once --weights FILE is read)
     if (J.implicit) {
@@ -2228,6 +2309,19 @@ int main(int argc, char *argv[])
                 P = J.M; P.vals = J.robust_w;
                 if (!J.perm_m.empty()) P = permute(P, inverse(J.perm_m), J.perm_u);
                 bpmf::io::write_sparse(J.odirname + "/robust-weights.sdm", P);
+            }
+            if (J.bias) {
+                // row-bias.ddm / col-bias.ddm: the posterior-mean bias of every user / movie (1 x n; no kept sample: no file);
+                // bias_lambda.csv: the precision either side's step ran with, per iteration
+                if (!J.perm_m.empty()) { permute_columns(J.bias_u, 1, inverse(J.perm_u)); permute_columns(J.bias_m, 1, inverse(J.perm_m)); }
+                Dense b;
+                if (!J.bias_u.empty()) { b.nrows = 1; b.ncols = nusers; b.data = J.bias_u; bpmf::io::write_dense(J.odirname + "/row-bias.ddm", b); }
+                if (!J.bias_m.empty()) { b.nrows = 1; b.ncols = nmovies; b.data = J.bias_m; bpmf::io::write_dense(J.odirname + "/col-bias.ddm", b); }
+                std::ofstream csv(J.odirname + "/bias_lambda.csv");
+                csv << "iteration,lambda_rows,lambda_cols\n";
+                csv.precision(17);
+                for (size_t i = 0; i < J.bias_lam_u.size(); ++i) csv << i << "," << J.bias_lam_u[i] << "," << J.bias_lam_m[i] << "\n";
+                if (!csv) throw std::runtime_error("cannot write " + J.odirname + "/bias_lambda.csv");
             }
             if (!J.perm_m.empty()) {
                 const std::vector<int64_t> im = inverse(J.perm_m), iu = inverse(J.perm_u);

@@ -33,7 +33,7 @@ extern "C" int bpmf_hip_side_set_censored(bpmf_hip_side *s, const int8_t *flags,
     if (!s || !flags) return fail(BPMF_HIP_EINVAL, "side_set_censored: NULL argument");
     bpmf_hip_ctx *c = s->ctx;
     if (s->censor) return fail(BPMF_HIP_EINVAL, "side_set_censored: the side is a censored side already");
-    int rc = refuse("side_set_censored", s, {Not::probit, Not::features, Not::robust, Not::weights, Not::prop_posterior, Not::ordinal});
+    int rc = refuse("side_set_censored", s, {Not::bias, Not::probit, Not::features, Not::robust, Not::weights, Not::prop_posterior, Not::ordinal});
     if (rc) return rc;
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_censored: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if ((rc = require_single_gpu("side_set_censored", c, s)) || (rc = refuse("side_set_censored", s, {Not::reduce}))) return rc;

@@ -146,6 +146,7 @@ extern "C" int bpmf_hip_sys_set_reduce(bpmf_hip_side *a, bpmf_hip_side *b, int o
     if (a->probit || b->probit) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with the probit likelihood (bpmf_hip_side_set_probit)");
     if (a->censor || b->censor) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with censored ratings (bpmf_hip_side_set_censored)");
     if (a->ordinal || b->ordinal) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with the ordinal likelihood (bpmf_hip_side_set_ordinal)");
+    if (a->bias || b->bias) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with bias terms (bpmf_hip_side_set_bias)");
     if (a->robust || b->robust) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with Student-t noise (bpmf_hip_side_set_robust)");
     if (a->weights || b->weights) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with per-rating weights (bpmf_hip_side_set_weights)");
     if (!a->conn_send_ptr.empty() || !b->conn_send_ptr.empty())

@@ -227,6 +227,21 @@ extern "C" int bpmf_hip_predict_launch(bpmf_hip_test *t, const bpmf_hip_side *se
         return BPMF_HIP_OK;
     }
     if (c->K != 8 && c->K != 16 && c->K != 32 && c->K != 64 && c->K != 128) return fail(BPMF_HIP_EINVAL, "predict: unsupported K");
+    // A pair with bias terms (capi_bias.hip): k_predict_bias on the main stream, in order -- the evaluation of iteration i reads the
+    // bias vectors the step of iteration i + 1 overwrites in place, so it is never put off or moved to a second stream.
+    if (self->bias || other->bias) {
+        if (const int rb = bias_pair_check(self, other)) return rb;
+        if (dist || c->dtype != BPMF_HIP_F64 || sharded(self) || sharded(other))
+            return fail(BPMF_HIP_EINVAL, "predict: bias terms need both sides whole on one GPU in fp64");
+        if (other->ncols != self->nrows) return fail(BPMF_HIP_EINVAL, "predict: the other side has not one column per row of this side");
+        if (t->twin && (t->twin->side != other)) return fail(BPMF_HIP_EINVAL, "predict: the twin of a test matrix with bias terms belongs to the other side");
+        c->last_sampler_done = nullptr;
+        if (bpmf_launch::bias_predict(t, self, other, self->d_items, other->d_items, n, c->stream.get())) return fail(BPMF_HIP_EINVAL, "predict: unsupported K");
+        HIP_TRY(hipGetLastError());
+        t->launched = true;
+        trace("predict: enqueued (bias)", self, n);
+        return BPMF_HIP_OK;
+    }
     // (the all-reduce of the sharded form shares the main communicator: that form stays in order)
     const bool beside = t->ev_in && !dist && other->saux && !other->deferred_eval && second_copy_usable(self) && second_copy_usable(other);
     if (beside) {

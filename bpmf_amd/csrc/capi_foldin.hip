@@ -61,6 +61,7 @@ int foldin_pair(const char *who, bpmf_hip_side *side, bpmf_hip_side *cand)
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(side)) || (rc = settle_async(cand))) return rc;
     if (!cand->ring) return fail(BPMF_HIP_EINVAL, w + ": no sample ring on the candidate side (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse(w.c_str(), cand, {Not::bias}); if (rb) return rb; }      // (its ring has bias rows the folded-in rows have not)
     if (cand->ring->count != side->foldin->S)
         return fail(BPMF_HIP_EINVAL, w + ": the rows were folded in against " + std::to_string(side->foldin->S) + " samples, the candidate side holds " +
                     std::to_string(cand->ring->count));
@@ -78,6 +79,7 @@ extern "C" int bpmf_hip_side_hyper_reserve(bpmf_hip_side *s, int max_samples)
 {
     if (!s || max_samples < 0) return fail(BPMF_HIP_EINVAL, "side_hyper_reserve: bad argument");
     if (max_samples > 0 && s->implicit) return fail(BPMF_HIP_EINVAL, "side_hyper_reserve: not on an implicit side (fold-in under the implicit model would need G)");
+    if (max_samples > 0) { const int rb = refuse("side_hyper_reserve", s, {Not::bias}); if (rb) return rb; }
     if (max_samples == 0) {
         if (s->foldin) {
             bpmf_foldin *f = s->foldin.get();
@@ -183,6 +185,7 @@ extern "C" int bpmf_hip_foldin(bpmf_hip_side *side, bpmf_hip_side *cand, double 
     const int S = f ? f->hcount : 0;
     if (S < 1) return fail(BPMF_HIP_EINVAL, "foldin: the side holds no hyper-parameters (bpmf_hip_side_hyper_reserve, bpmf_hip_side_hyper_add)");
     if (!cand->ring) return fail(BPMF_HIP_EINVAL, "foldin: no sample ring on the candidate side (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse("foldin", cand, {Not::bias}); if (rb) return rb; }      // (a folded-in row would need a bias of its own)
     if (cand->ring->count != S)
         return fail(BPMF_HIP_EINVAL, "foldin: the side holds the hyper-parameters of " + std::to_string(S) + " samples, the candidate side's ring " +
                     std::to_string(cand->ring->count) + ": they must be the same samples");

@@ -18,11 +18,12 @@
 //   capi_weights.hip   per-rating precision weights: sqrt(w) and sqrt(w) (r - mean) of a side, which the weighted forms of the samplers read
 //   capi_implicit.hip  implicit feedback: unobserved cells as zeros of weight w0 behind the weighted samplers, the blocking half-iteration bpmf_hip_implicit_sample
 //   capi_robust.hip    Student-t noise: the weights of a side redrawn on the device ahead of every sampler launch, their posterior mean
+//   capi_bias.hip      row and column bias terms: the draw of a side's offsets ahead of every sampler launch, the values its samplers read, their posterior mean
 //   capi_tensor.hip    sparse tensor factorisation (CP, order 3): a side per mode behind the Khatri-Rao rows of the other two, test entries
 //   capi_link.hip      side information: features of a side, the link matrix beta, the blocking half-iteration bpmf_hip_link_sample
 //   capi_link_sparse.hip  side information with a sparse feature matrix: beta by conjugate gradients on the device (link_sparse.h)
 //   capi_link_lambda.hip  the sampled link precision lambda_beta; G(lambda_beta) factored and solved against on the device (link_lambda.h)
-// Four of the add-ons (probit, ordinal, censored, robust) run a latent kernel ahead of every sampler launch of their side: state.h names
+// Five of the add-ons (probit, ordinal, censored, robust, bias) run a latent kernel ahead of every sampler launch of their side: state.h names
 // the kind of a side (likelihood), checks its fail word (check_latent) and picks the values its samplers read (sampler_values); the launch
 // structs of launch.h share FactorPair / SideCsc, filled by factor_pair / side_csc below; their launchers share dispatch_k / dispatch_kt.
 // The device memory of the last ten (probit, censoring, weights, Student-t noise, features, sample ring, new rows, fold-in, residual partials) is owned by the structs of ext_state.h
@@ -66,13 +67,15 @@ int settle_async(bpmf_hip_side *s);                                    // waits 
 void predraw_stop(bpmf_hip_side *s);                                   // joins the side's pre-draw helper threads
 int flush_pending_stats(bpmf_hip_ctx *c, bool on_main = false);        // statistics without a launch to ride in: a kernel of their own
 
-// The latent step of a side (probit, ordinal, censored, robust: state.h has the kind): the kernel of the half-iteration being enqueued, on
+// The latent step of a side (probit, ordinal, censored, robust, bias: state.h has the kind): the kernel of the half-iteration being enqueued, on
 // the stream `st` its sampler goes on, ahead of it.  Each kind fills its launch struct and keeps its own refusals (capi_probit.hip,
 // capi_ordinal.hip, capi_censor.hip, capi_robust.hip); latent_enqueue picks the one `self` is and does nothing on a Gaussian side.
 int probit_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
 int ordinal_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
 int censor_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
 int robust_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
+int bias_latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st);
+int bias_pair_check(const bpmf_hip_side *self, const bpmf_hip_side *other);   // both sides of a pair carry biases, or neither does (capi_bias.hip)
 inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int iter, double alpha, hipStream_t st)
 {
     switch (likelihood(self)) {
@@ -80,9 +83,10 @@ inline int latent_enqueue(bpmf_hip_side *self, const bpmf_hip_side *other, int i
     case Likelihood::ordinal: return ordinal_latent_enqueue(self, other, iter, alpha, st);
     case Likelihood::censored: return censor_latent_enqueue(self, other, iter, alpha, st);
     case Likelihood::robust: return robust_latent_enqueue(self, other, iter, alpha, st);
+    case Likelihood::bias: return bias_latent_enqueue(self, other, iter, alpha, st);
     case Likelihood::gaussian: break;
     }
-    return 0;
+    return other->bias ? bias_pair_check(self, other) : 0;
 }
 // the members the launch structs of the add-ons share (launch.h): the factors of the side being stepped and of its partner as the
 // newest launch on S0 left them, and the side's ratings by columns (ensure_colptr has run)
@@ -102,8 +106,21 @@ int latent_read_back(const char *func, bpmf_hip_side *s, const double *z, double
 // (bpmf_hip_side_set_probit)" etc. (the table is in capi_side.hip): the first of `order` that holds for `s` is reported as
 // BPMF_HIP_EINVAL, 0 if none does.  The order decides what a side with two of the properties is told (a robust side has weights
 // too); a caller whose wording differs writes that line out at its place between two calls.
-enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce };
+enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce, bias };
 int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> order);
+
+// Two sample rings that meet in one dot product (capi_topn.hip, capi_newrows.hip, capi_model.hip): the same rows per sample, and, with
+// bias rows (capi_bias.hip), biases on both sides in opposite roles -- else the product is not mean + b + c + u . v
+inline int ring_pair_check(const std::string &who, const bpmf_hip_side *q, const bpmf_hip_side *c)
+{
+    if (q->ring->kp != c->ring->kp)
+        return fail(BPMF_HIP_EINVAL, who + ": the two sample rings hold " + std::to_string(q->ring->kp) + " and " + std::to_string(c->ring->kp) +
+                                     " rows per sample (bias terms on one side only?)");
+    if ((bool)q->bias != (bool)c->bias) return fail(BPMF_HIP_EINVAL, who + ": both sides of a pair carry bias terms or neither does (bpmf_hip_side_set_bias)");
+    if (q->bias && q->bias->role == c->bias->role)
+        return fail(BPMF_HIP_EINVAL, who + ": the two sides have the same bias role " + std::to_string(q->bias->role) + " (bpmf_hip_side_set_bias: 0 and 1)");
+    return 0;
+}
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.

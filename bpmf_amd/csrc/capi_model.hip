@@ -18,6 +18,7 @@ extern "C" int bpmf_hip_side_samples_get(bpmf_hip_side *s, int s_from, int s_to,
     if (!s) return fail(BPMF_HIP_EINVAL, "samples_get: NULL");
     bpmf_ring *ring = s->ring.get();
     if (!ring) return fail(BPMF_HIP_EINVAL, "samples_get: no sample ring (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse("samples_get", s, {Not::bias}); if (rb) return rb; }      // (the packed form has Kt rows per sample: no bias rows)
     if (s_from < 0 || s_to < s_from || s_to > ring->count)
         return fail(BPMF_HIP_EINVAL, "samples_get: samples " + std::to_string(s_from) + " .. " + std::to_string(s_to) + " are out of range (the ring holds " +
                     std::to_string(ring->count) + ")");
@@ -46,6 +47,7 @@ extern "C" int bpmf_hip_side_samples_set(bpmf_hip_side *s, int nsamples, const d
     if (!s) return fail(BPMF_HIP_EINVAL, "samples_set: NULL");
     bpmf_ring *ring = s->ring.get();
     if (!ring) return fail(BPMF_HIP_EINVAL, "samples_set: no sample ring (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse("samples_set", s, {Not::bias}); if (rb) return rb; }
     if (nsamples < 0 || nsamples > ring->max)
         return fail(BPMF_HIP_EINVAL, "samples_set: " + std::to_string(nsamples) + " samples do not fit the ring (reserved for " + std::to_string(ring->max) + ")");
     if (nsamples > 0 && s->ncols > 0 && !host) return fail(BPMF_HIP_EINVAL, "samples_set: NULL input");
@@ -100,6 +102,7 @@ extern "C" int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand,
     { const int rc = settle_async(query); if (rc) return rc; }
     { const int rc = settle_async(cand); if (rc) return rc; }
     if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "predict_cells: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check("predict_cells", query, cand); if (rb) return rb; }
     bpmf_ring *qr = query->ring.get();
     const bpmf_ring *cr = cand->ring.get();
     const int S = qr->count;

@@ -118,6 +118,7 @@ int newrows_pair(const char *who, bpmf_hip_side *side, bpmf_hip_side *cand)
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(side)) || (rc = settle_async(cand))) return rc;
     if (!cand->ring) return fail(BPMF_HIP_EINVAL, w + ": no sample ring on the candidate side (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse(w.c_str(), cand, {Not::bias}); if (rb) return rb; }      // (its ring has bias rows the new rows have not)
     const int S = side->newrows->count;
     if (S < 1 || cand->ring->count != S)
         return fail(BPMF_HIP_EINVAL, w + ": the new rows and the candidate side must hold the same number (>= 1) of samples: " + std::to_string(S) +
@@ -289,6 +290,7 @@ static int predict_block_of(const char *who, bpmf_hip_side *query, bpmf_hip_side
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(query)) || (rc = settle_async(cand))) return rc;
     if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, w + ": no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check(w, query, cand); if (rb) return rb; }
     const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
     const int S = qr->count;
     if (S < 1 || cr->count != S)

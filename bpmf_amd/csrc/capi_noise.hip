@@ -14,6 +14,7 @@ extern "C" int bpmf_hip_train_sse(bpmf_hip_side *self, bpmf_hip_side *other, dou
     int rc = require_single_gpu("train_sse", c, self, other, " (a sharded side or a communicator would need an all-reduce of the sum, which adaptive noise does not do)");
     if (rc) return rc;
     // (alpha | y needs a fresh draw of every censored y from the newest factors of BOTH sides ahead of the sum: DESIGN.md section 16)
+    if (self->bias || other->bias) return fail(BPMF_HIP_EINVAL, "train_sse: not with a side with bias terms (the residuals would leave the biases out)");
     if (self->censor || other->censor) return fail(BPMF_HIP_EINVAL, "train_sse: not with a censored side (the sum would take the bounds for measurements)");
     if (self->ordinal || other->ordinal) return fail(BPMF_HIP_EINVAL, "train_sse: not with an ordinal side (its ratings are levels and alpha is 1)");
     // (alpha | r of the weighted model takes sum w (r - mean - u . v)^2: not what this sums)

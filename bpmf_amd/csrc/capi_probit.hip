@@ -34,7 +34,7 @@ extern "C" int bpmf_hip_side_set_probit(bpmf_hip_side *s, double threshold, unsi
     if (!s) return fail(BPMF_HIP_EINVAL, "side_set_probit: NULL");
     bpmf_hip_ctx *c = s->ctx;
     if (s->probit) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side is a probit side already");
-    int rc = refuse("side_set_probit", s, {Not::ordinal, Not::features, Not::censored, Not::robust, Not::weights});
+    int rc = refuse("side_set_probit", s, {Not::bias, Not::ordinal, Not::features, Not::censored, Not::robust, Not::weights});
     if (rc) return rc;
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_probit: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_probit: tag must be >= 1 (key word 0 belongs to the samplers' streams)");

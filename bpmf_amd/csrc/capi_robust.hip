@@ -44,7 +44,7 @@ extern "C" int bpmf_hip_side_set_robust(bpmf_hip_side *s, double nu, unsigned ta
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_robust: tag must be >= 1 (key word 0 belongs to the samplers' streams)");
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_robust: not on an fp32 context");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_robust: the side is a robust side already");
-    int rc = refuse("side_set_robust", s, {Not::weights, Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
+    int rc = refuse("side_set_robust", s, {Not::bias, Not::weights, Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
     if (rc || (rc = require_single_gpu("side_set_robust", c, s))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = settle_async(s))) return rc;

@@ -375,9 +375,10 @@ int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> o
                                             "not on a side with per-rating weights (bpmf_hip_side_set_weights)",
                                             "not together with features (bpmf_hip_side_set_features)",
                                             "not together with propagated priors",
-                                            "not together with the BPMF_REDUCE formulation"};
+                                            "not together with the BPMF_REDUCE formulation",
+                                            "not on a side with bias terms (bpmf_hip_side_set_bias)"};
     const bool holds[] = {(bool)s->probit, (bool)s->ordinal, (bool)s->censor, (bool)s->robust, (bool)s->weights,
-                          (bool)s->link, (bool)s->d_prop, s->reduce_on};
+                          (bool)s->link, (bool)s->d_prop, s->reduce_on, (bool)s->bias};
     for (const Not n : order)
         if (holds[(int)n]) return fail(BPMF_HIP_EINVAL, std::string(who) + ": " + kSentence[(int)n]);
     return 0;
@@ -426,7 +427,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: NULL");
     (void)mu;
-    if (Lambda) { const int rf = refuse("set_prop_posterior", s, {Not::robust, Not::weights, Not::ordinal}); if (rf) return rf; }
+    if (Lambda) { const int rf = refuse("set_prop_posterior", s, {Not::bias, Not::robust, Not::weights, Not::ordinal}); if (rf) return rf; }
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }

@@ -21,6 +21,7 @@ int similar_prepare(const char *who, bpmf_hip_side *s, int kind, DevBuf<double> 
     if ((rc = settle_async(s))) return rc;
     const bpmf_ring *ring = s->ring.get();
     if (!ring) return fail(BPMF_HIP_EINVAL, w + ": no sample ring (bpmf_hip_side_samples_reserve)");
+    { const int rb = refuse(w.c_str(), s, {Not::bias}); if (rb) return rb; }      // (the two bias rows of its ring would enter the cosine)
     if (ring->count < 1) return fail(BPMF_HIP_EINVAL, w + ": the sample ring is empty");
     if (s->ncols > std::numeric_limits<int32_t>::max()) return fail(BPMF_HIP_EINVAL, w + ": too many columns");
     if (s->ncols < 1) return BPMF_HIP_OK;

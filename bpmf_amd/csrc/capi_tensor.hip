@@ -163,6 +163,7 @@ extern "C" int bpmf_hip_tensor_create(bpmf_hip_ctx *ctx, int nmodes, const int64
         }
         if ((rc = t->ia[m].upload(ha.data(), (size_t)nnz)) || (rc = t->ib[m].upload(hb.data(), (size_t)nnz))) break;
         rc = bpmf_hip_side_create(ctx, dims[m], (int64_t)n1, 0, dims[m], colptr[m].data(), rowidx.data(), v.data(), mean_rating, &t->side[m]);
+        if (!rc) t->side[m]->tensor_mode = true;
     }
     for (Event &e : t->kr_ev)
         if (!rc && e.create()) { (void)hipGetLastError(); rc = fail(BPMF_HIP_ENODEV, "tensor_create: hipEventCreate failed"); }
@@ -187,7 +188,7 @@ extern "C" bpmf_hip_side *bpmf_hip_tensor_side(bpmf_hip_tensor *t, int m)
 // a mode's side may carry the sample ring, the hyper ring and the -o aggregates; everything that changes what its sampler reads is refused
 static int check_plain_mode(const char *who, const bpmf_hip_side *s)
 {
-    static const char *const kKind[] = {nullptr, "a probit likelihood", "an ordinal likelihood", "censored ratings", "Student-t noise"};
+    static const char *const kKind[] = {nullptr, "a probit likelihood", "an ordinal likelihood", "censored ratings", "Student-t noise", "bias terms"};
     const char *what = latent_step(s) ? kKind[(int)likelihood(s)] : s->weights ? "per-rating weights"
                        : s->link ? "features" : s->d_prop.get() ? "propagated priors" : s->reduce_on ? "the BPMF_REDUCE formulation" : nullptr;
     if (what) return fail(BPMF_HIP_EINVAL, std::string(who) + ": not together with " + what + " on a mode of a tensor");

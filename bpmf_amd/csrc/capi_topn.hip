@@ -18,8 +18,11 @@ extern "C" int bpmf_hip_side_samples_reserve(bpmf_hip_side *s, int max_samples)
         s->ring.reset();
     }
     if (max_samples == 0) return BPMF_HIP_OK;
+    // a side with bias terms keeps two more rows per sample (capi_bias.hip); the ring kernels serve at most 128 rows
+    if (s->bias && c->Kt > 126)
+        return fail(BPMF_HIP_EINVAL, "samples_reserve: num_latent " + std::to_string(c->Kt) + " > 126 leaves no room for the two bias rows of a sample");
     auto ring = std::make_unique<bpmf_ring>();
-    ring->max = max_samples; ring->kp = ring_kp(c);
+    ring->max = max_samples; ring->kp = s->bias ? (c->Kt + 2 + 3) / 4 * 4 : ring_kp(c);
     const size_t words = (size_t)s->ncols * (size_t)max_samples * (size_t)ring->kp;
     if (ring->samples.alloc(words))
         return fail(BPMF_HIP_ENOMEM, "samples_reserve: " + std::to_string(max_samples) + " samples of " + std::to_string((long long)s->ncols) +
@@ -41,6 +44,9 @@ extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
     { const int rc = settle_async(s); if (rc) return rc; }
     bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, ring->kp, s->ncols, ring->samples.get(),
                              (int64_t)ring->max * ring->kp, ring->count, c->stream.get());
+    if (s->bias)                                                      // behind the factor rows: (b, 1) or (1, b), by the side's role
+        bpmf_launch::samples_add_bias(s->bias->b.get(), s->ncols, s->bias->role, c->Kt, ring->samples.get(), (int64_t)ring->max * ring->kp, ring->kp,
+                                      ring->count, c->stream.get());
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
     ++ring->count;
@@ -137,6 +143,7 @@ extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double m
     { const int rc = settle_async(query); if (rc) return rc; }        // every half-iteration in flight on both sides (as bpmf_hip_sys_state)
     { const int rc = settle_async(cand); if (rc) return rc; }
     if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check("topn", query, cand); if (rb) return rb; }
     const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
     const int S = qr->count;
     if (S < 1 || cr->count != S)
@@ -173,6 +180,7 @@ extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, d
     { const int rc = settle_async(query); if (rc) return rc; }
     { const int rc = settle_async(cand); if (rc) return rc; }
     if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn_scored: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check("topn_scored", query, cand); if (rb) return rb; }
     const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
     const int S = qr->count;
     if (S < 1 || cr->count != S)
@@ -246,6 +254,7 @@ extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, dou
     { const int rc = settle_async(query); if (rc) return rc; }
     { const int rc = settle_async(cand); if (rc) return rc; }
     if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "rank_eval: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check("rank_eval", query, cand); if (rb) return rb; }
     const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
     const int S = qr->count;
     if (S < 1 || cr->count != S)

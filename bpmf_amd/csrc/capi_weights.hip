@@ -14,7 +14,7 @@ extern "C" int bpmf_hip_side_set_weights(bpmf_hip_side *s, const double *w)
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an fp32 context");
     if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on an implicit side (bpmf_hip_side_set_implicit takes the confidences itself)");
     if (s->robust) return fail(BPMF_HIP_EINVAL, "side_set_weights: not on a side with Student-t noise (bpmf_hip_side_set_robust redraws the weights itself)");
-    int rc = refuse("side_set_weights", s, {Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
+    int rc = refuse("side_set_weights", s, {Not::bias, Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce});
     if (rc || (rc = require_single_gpu("side_set_weights", c, s))) return rc;
     for (int64_t p = 0; p < s->nnz; ++p)
         if (!(w[p] > 0.0) || !std::isfinite(w[p])) {

@@ -1,6 +1,6 @@
 // ext_state.h -- what the add-ons of a side own on the device (included by state.h): bpmf_hip_side holds one owning pointer per
-// add-on, NULL while the side has none; everything below is released when that pointer is reset.  The four add-ons with a latent
-// step (probit, ordinal, censored, robust) derive from bpmf_latent; state.h tells which of them a side is.
+// add-on, NULL while the side has none; everything below is released when that pointer is reset.  The five add-ons with a latent
+// step (probit, ordinal, censored, robust, bias) derive from bpmf_latent; state.h tells which of them a side is.
 #pragma once
 #include <limits>
 #include <memory>
@@ -34,8 +34,8 @@ struct CgWork {
 
 }  // namespace bpmf_launch
 
-// The latent step of a side: the kernel that a probit, an ordinal, a censored or a robust side runs ahead of every one of its sampler
-// launches (a side is at most one of the four: state.h has the kind and check_latent).  What the four share: the word the kernel raises
+// The latent step of a side: the kernel that a probit, an ordinal, a censored or a robust side or a side with biases runs ahead of every
+// one of its sampler launches (a side is at most one of the five: state.h has the kind and check_latent).  What they share: the word the kernel raises
 // to a rating position it could not draw (~0: none; the kind says why), and the tag of the side's Philox streams.
 struct bpmf_latent { Pinned<unsigned long long> fail; uint32_t tag = 0; };
 
@@ -79,6 +79,22 @@ struct bpmf_implicit { double w0 = 0.0; bool in_call = false; DevBuf<double> gra
 // launch.  nu: the degrees of freedom; wsum: the running sum of w over the kept samples (layout of d_vals), `kept` of them; the word
 // is raised when a draw runs into its attempt cap or meets a residual that is not finite
 struct bpmf_robust : bpmf_latent { double nu = 0.0; DevBuf<double> wsum; int kept = 0; };
+
+// row and column bias terms (capi_bias.hip): one offset per column of the side, b_a ~ N(0, 1 / lambda).  b: the
+// current biases; bsum: their running sum over the kept samples, `kept` of them; z: (r - b[col]) - c[row] (layout of d_vals; the
+// samplers read it in place of d_vals); e, part: the residuals and the piece partials of the newest step; pieceptr: the first piece of
+// every column (ncols + 1; npieces in all); lambda: the device word the draw reads its precision from (lambda_host: its value);
+// role: which of the two extra ring rows carries b (0: (b, 1), 1: (1, b)).  The word is raised at a rating whose residual is not finite
+struct bpmf_bias : bpmf_latent {
+    DevBuf<double> b, bsum, z, e, part, lambda;
+    DevBuf<int64_t> pieceptr; int64_t npieces = 0;
+    double lambda_host = 1.0; int role = 0, kept = 0;
+    int64_t steps = 0;                                      // bias steps enqueued so far
+    // a sampled precision (bpmf_hip_side_bias_prior): lambda ~ Gamma(a0 + N / 2, b0 + sum b^2 / 2) by k_bias_lambda at the start of every
+    // half-iteration of the side but its first; trace[iter] = the draw of that half-iteration (NaN where none was made), draws of them
+    bool sample_lambda = false; double a0 = 0.0, b0 = 0.0;
+    DevBuf<double> trace; int trace_cap = 0; int64_t draws = 0;
+};
 
 // dense features (capi_link.hip): F (ncols x D, row-major), W = [G^-1 | L_G^-T] (D x 2 D), the stacked right-hand side [P ; E] (2 D x ld)
 struct bpmf_link_dense {

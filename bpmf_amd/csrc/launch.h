@@ -337,6 +337,38 @@ struct RobustWeightsLaunch {
 int robust_weights(const RobustWeightsLaunch &p, hipStream_t st);        // -1: unsupported K (nothing launched)
 void robust_accumulate(const double *sw, int64_t nnz, double *wsum, hipStream_t st);   // wsum[p] += sw[p]^2
 
+// row and column bias terms (kernels_bias.h, kbias.hip): fp64 factors only
+struct BiasStepLaunch {
+    SideCsc m; const double *vals;
+    FactorPair f;                                          // (fp64 factors: f.f32 is not read)
+    const int64_t *pieceptr; int64_t npieces;              // the first piece of every column (ncols + 1), the pieces of the side
+    uint32_t iter, tag;
+    double mean, alpha;                                    // the side's mean rating; the noise precision
+    const double *lambda;                                  // the device word that holds the side's bias precision
+    const double *cbias;                                   // the other side's biases, one per row of this side
+    double *e, *part;                                      // work: nnz residuals, npieces piece partials
+    double *b, *z;                                         // the side's biases (ncols); the values its samplers read (layout of vals)
+    unsigned long long *fail;                              // raised (rating position) when a residual is not finite
+};
+struct BiasLambdaLaunch {
+    const double *b; int64_t ncols;                        // the side's current biases
+    double dd, c, b0;                                      // a - 1 / 3 and 1 / sqrt(9 dd) of the shape a = a0 + ncols / 2, formed on the host; the prior's rate
+    uint32_t iter, tag;
+    double *lambda; double *trace; int cap;                // the side's lambda word; trace[iter] gets the draw (iter < cap)
+    unsigned long long *fail;
+};
+void bias_lambda(const BiasLambdaLaunch &p, hipStream_t st);   // one workgroup
+// rows Kt, Kt + 1 of ring slot `slot` of every column: (b, 1) for role 0, (1, b) for role 1
+void samples_add_bias(const double *b, int64_t ncols, int role, int Kt, double *ring, int64_t stride, int Kp, int slot, hipStream_t st);
+int bias_light();                                          // ratings up to which a column has no piece (kBiasLight)
+int bias_piece();                                          // ratings of a column per piece (kBiasPiece)
+int bias_step(const BiasStepLaunch &p, hipStream_t st);    // residuals, piece sums, draw, values.  -1: unsupported K (nothing launched)
+void bias_accumulate(const double *b, int64_t ncols, double *bsum, hipStream_t st);   // bsum[a] += b[a]
+// k_predict_bias for the test matrix `t` of the biased side `self` against `other`, on `ps`, in order; the twin as bpmf_launch::predict
+// treats it (one kernel for both copies when the entries match, else a launch of its own ahead).  -1: unsupported K
+int bias_predict(bpmf_hip_test *t, const bpmf_hip_side *self, const bpmf_hip_side *other, const void *self_items, const void *other_items,
+                 int n, hipStream_t ps);
+
 // sparse tensor factorisation (kernels_tensor.h, ktensor.hip): fp64 factors only
 struct KhatriRaoLaunch {                                   // P[:, e] = A[:, ia[e]] o B[:, ib[e]], e < n; rows kt .. ld - 1 of P zero
     const double *A, *B;                                   // the two other modes' factor matrices (leading dimension ld)

@@ -212,12 +212,14 @@ struct bpmf_hip_side {
     std::unique_ptr<bpmf_weights> weights; // per-rating precision weights (bpmf_hip_side_set_weights)
     std::unique_ptr<bpmf_implicit> implicit; // implicit feedback: unobserved cells are zeros of weight w0 (bpmf_hip_side_set_implicit)
     std::unique_ptr<bpmf_robust> robust;   // Student-t noise: the weights are redrawn per launch (bpmf_hip_side_set_robust)
+    std::unique_ptr<bpmf_bias> bias;       // row / column bias terms: one offset per column, redrawn per launch (bpmf_hip_side_set_bias)
     std::unique_ptr<bpmf_link> link;       // side information, dense or sparse (bpmf_hip_side_set_features, _set_features_sparse)
     std::unique_ptr<bpmf_ring> ring;       // sample ring of the top-N ranking (bpmf_hip_side_samples_reserve)
     std::unique_ptr<bpmf_newrows> newrows; // rows unseen in training: their features and projected samples (bpmf_hip_side_newrows_set)
     std::unique_ptr<bpmf_foldin> foldin;   // fold-in: the per-sample hyper-parameters and the folded-in rows (bpmf_hip_side_hyper_reserve, bpmf_hip_foldin)
     std::unique_ptr<bpmf_sse> sse;         // partials of the training residuals (bpmf_hip_train_sse)
     DevBuf<int64_t> d_colptr;              // the column pointers on the device, uploaded when an add-on first needs them (ensure_colptr)
+    bool tensor_mode = false;            // the side is a mode of a tensor (capi_tensor.hip): its "rows" are Khatri-Rao rows, not the other side's columns
     bool latent_queued = false;          // bpmf_hip_sys_sample has enqueued the latent kernel of the launch it is building (launch_sampler then does not)
     // schedule
     int nwork = 0, nmulti = 0, nslots = 0, mode = 0;
@@ -342,12 +344,13 @@ struct bpmf_hip_side {
     } predraw;
 };
 
-// The likelihood of a side's ratings: the setters see to it that a side is at most one of the four that are not Gaussian.
-enum class Likelihood { gaussian, probit, ordinal, censored, robust };
+// The likelihood of a side's ratings: the setters see to it that a side is at most one of the five that are not plain Gaussian
+// (bias: Gaussian ratings around mean + b_col + c_row + x . y, a latent step all the same).
+enum class Likelihood { gaussian, probit, ordinal, censored, robust, bias };
 inline Likelihood likelihood(const bpmf_hip_side *s)
 {
     return s->probit ? Likelihood::probit : s->ordinal ? Likelihood::ordinal : s->censor ? Likelihood::censored
-           : s->robust ? Likelihood::robust : Likelihood::gaussian;
+           : s->robust ? Likelihood::robust : s->bias ? Likelihood::bias : Likelihood::gaussian;
 }
 // the latent step of the side (ext_state.h), NULL on a Gaussian side
 inline bpmf_latent *latent_step(const bpmf_hip_side *s)
@@ -357,19 +360,21 @@ inline bpmf_latent *latent_step(const bpmf_hip_side *s)
     case Likelihood::ordinal: return s->ordinal.get();
     case Likelihood::censored: return s->censor.get();
     case Likelihood::robust: return s->robust.get();
+    case Likelihood::bias: return s->bias.get();
     case Likelihood::gaussian: break;
     }
     return nullptr;
 }
 // what the samplers of the side read as its values (layout of d_vals): the latent scores of a probit or an ordinal side, the ratings
 // with a fresh draw at every censored position (capi_censor.hip), the residuals r - m_c . y_r of a side with features
-// (capi_link.hip), else the ratings themselves
+// (capi_link.hip), the ratings less both bias terms of a side with biases (capi_bias.hip), else the ratings themselves
 inline const double *sampler_values(const bpmf_hip_side *s)
 {
     switch (likelihood(s)) {
     case Likelihood::probit: return s->probit->z.get();
     case Likelihood::ordinal: return s->ordinal->z.get();
     case Likelihood::censored: return s->censor->z.get();
+    case Likelihood::bias: return s->bias->z.get();
     default: return s->link ? s->link->r.get() : s->d_vals;
     }
 }
@@ -428,15 +433,17 @@ inline int check_timeout(double *h_blob, int K, std::string *msg)
     return BPMF_HIP_ENODEV;
 }
 
-// Did the latent kernel of this side (probit, ordinal, censored, robust) raise its word -- a draw that ran into its attempt cap, a
+// Did the latent kernel of this side (probit, ordinal, censored, robust, bias) raise its word -- a draw that ran into its attempt cap, a
 // dot product or residual that is not finite?  Checked where a half-iteration's results are collected; the word is reset.
 inline int check_latent(bpmf_hip_side *s, std::string *msg)
 {
     static const char *const kBefore[] = {"", "probit: the truncated-normal draw of rating ", "ordinal: the score of rating ",
-                                          "censored: the truncated-normal draw of rating ", "robust: the weight of rating "};
+                                          "censored: the truncated-normal draw of rating ", "robust: the weight of rating ",
+                                          "bias: the residual of rating "};
     static const char *const kAfter[] = {"", " was rejected 64 times (non-finite factors?)", " is not finite (non-finite factors?)",
                                          " was rejected 64 times (non-finite factors?)",
-                                         " could not be drawn: 64 rejections, or a residual that is not finite (non-finite factors?)"};
+                                         " could not be drawn: 64 rejections, or a residual that is not finite (non-finite factors?)",
+                                         " is not finite (non-finite factors?)"};
     bpmf_latent *l = latent_step(s);
     if (!l) return 0;
     unsigned long long *word = l->fail.host();
@@ -444,6 +451,10 @@ inline int check_latent(bpmf_hip_side *s, std::string *msg)
     if (v == ~0ull) return 0;
     __atomic_store_n(word, ~0ull, __ATOMIC_RELEASE);
     const int k = (int)likelihood(s);
+    if (k == (int)Likelihood::bias && v == ~0ull - 1ull) {            // (kernels_bias.h: kBiasLambdaFailed)
+        *msg = "bias: the draw of lambda was rejected 64 times or met biases that are not finite";
+        return BPMF_HIP_ENUM;
+    }
     *msg = kBefore[k] + std::to_string(v) + kAfter[k];
     return BPMF_HIP_ENUM;
 }

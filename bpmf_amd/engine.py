@@ -807,6 +807,59 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_side_robust_get(side.handle, _ptr(w), C.byref(n), C.byref(nu)))
         return w, n.value, nu.value
 
+    # -- row and column bias terms ----------------------------------------------------
+    def set_bias(self, side, lam=1.0, tag=13, role=0):
+        """Gives `side` one bias per column, b_a ~ N(0, 1 / lam) (include/bpmf_hip.h): r = mean + b[col] + c[row]
+        + x . y.  The biases start at 0 and are redrawn on the device ahead of every sampler launch of the side, on the Philox
+        streams `tag` (>= 1; one per side, used by nothing else in the run); both sides of a pair carry biases or neither does, with
+        different roles (0 / 1).  fp64 contexts, one GPU; not with probit, ordinal, censored ratings, weights, Student-t noise,
+        features, propagated priors, BPMF_REDUCE, a sample ring or fold-in."""
+        _lib.check(self.lib.bpmf_hip_side_set_bias(side.handle, float(lam), int(tag), int(role)))
+
+    def bias_get(self, side):
+        """The current biases of the side, one per column (waits)."""
+        b = np.empty(side.ncols)
+        _lib.check(self.lib.bpmf_hip_side_bias_get(side.handle, _ptr(b)))
+        return b
+
+    def bias_set(self, side, b):
+        """Replaces the biases of the side (one finite value per column)."""
+        b = np.ascontiguousarray(b, np.float64)
+        if b.shape != (side.ncols,):
+            raise ValueError("bias_set: %r values for a side of %d columns" % (b.shape, side.ncols))
+        _lib.check(self.lib.bpmf_hip_side_bias_set(side.handle, _ptr(b)))
+
+    def bias_latent(self, side):
+        """The values the newest sampler launch of a side with biases read in place of its ratings: (r - b[col]) - c[row] (waits)."""
+        z = np.empty(side.nnz)
+        _lib.check(self.lib.bpmf_hip_side_bias_latent(side.handle, _ptr(z)))
+        return z
+
+    def bias_add(self, side):
+        """Adds the current biases to their running sums (enqueue only, no host wait)."""
+        _lib.check(self.lib.bpmf_hip_side_bias_add(side.handle))
+
+    def bias_mean(self, side):
+        """(posterior-mean bias per column, samples added)"""
+        m = np.empty(side.ncols)
+        n = C.c_int()
+        _lib.check(self.lib.bpmf_hip_side_bias_mean(side.handle, _ptr(m), C.byref(n)))
+        return m, n.value
+
+    def bias_prior(self, side, a0, b0):
+        """Samples the precision of the side's biases instead of fixing it: prior Gamma(a0, rate b0), drawn on the device at the start
+        of every half-iteration of the side but its first (include/bpmf_hip.h)."""
+        _lib.check(self.lib.bpmf_hip_side_bias_prior(side.handle, float(a0), float(b0)))
+
+    def bias_lambda(self, side, n=0):
+        """(current lambda of the side's biases, the lambda the steps of iterations 0 .. n - 1 ran with, bias steps enqueued so far,
+        lambda draws enqueued so far); waits."""
+        lam, steps, draws = C.c_double(), C.c_int64(), C.c_int64()
+        trace = np.empty(max(int(n), 0))
+        _lib.check(self.lib.bpmf_hip_side_bias_lambda_get(side.handle, C.byref(lam), _ptr(trace) if n > 0 else None, max(int(n), 0), C.byref(steps),
+                                                          C.byref(draws)))
+        return lam.value, trace, steps.value, draws.value
+
     # -- sparse tensor factorisation -----------------------------------------------
     @staticmethod
     def _tensor_entries(who, idx, vals):

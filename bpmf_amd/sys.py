@@ -197,7 +197,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -350,7 +350,56 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     squared distance ("euclid") minus similar_kappa >= 0 times its spread -- quantities no rotation of the latent space changes.
     Entities with fewer than similar_min_ratings training ratings are not listed (their factors are close to prior draws); they are
     still queries.  It reads only the ring, so it goes with every likelihood topn goes with, and is independent of topn.  Needs
-    nsims > burnin.  None (the default): nothing changes."""
+    nsims > burnin.  None (the default): nothing changes.
+
+    bias=True | LAMBDA: row and column bias terms, r = mean + b_user + c_movie + u . v with b, c ~ N(0, 1 / LAMBDA) (True: 1;
+    DESIGN.md section 28).  Both sides get their biases (engine.set_bias, tags 13 = movies, 14 = users, roles 0 / 1) and redraw them
+    on the device ahead of every sampler launch; the evaluation adds both to every prediction.  res["bias"] = dict(rows_mean,
+    cols_mean: the posterior means of the users' / movies' biases; lambda_rows, lambda_cols: the precision every iteration's step
+    ran with, nsims values each; kept).  bias_prior=(A0, B0): LAMBDA is sampled instead, Gamma(A0, rate B0) a priori, on the device at
+    the start of every half-iteration of a side but its first (engine.bias_prior); bias then gives the starting value.  topn (every
+    score), rank_eval and engine.predict_block / predict_cells work on top: the sample rings of both sides carry two more rows per
+    sample, (b, 1) and (1, c), so that the ring dot product is u . v + b + c.  Refused with every other likelihood and add-on (probit,
+    ordinal, censored, weights, robust, implicit, features, noise="adaptive"), with foldin, save_model and similar (a folded-in row has
+    no bias, the model format stores none, the bias rows would enter the cosine), with pipelined=True, an fp32 engine, a communicator,
+    and, together with a sample ring, num_latent > 126.  None / False (the default): nothing changes."""
+    bias_on = bias is not None and bias is not False
+    if bias_prior is not None and not bias_on:
+        raise ValueError("bias_prior needs bias")
+    if bias_on:                                      # (refused before the engine is used)
+        bias_lambda = 1.0 if bias is True else bias
+        try:
+            bias_lambda = float(bias_lambda)
+        except (TypeError, ValueError):
+            bias_lambda = float("nan")
+        if not (math.isfinite(bias_lambda) and bias_lambda > 0):
+            raise ValueError("bias = %r: True, or a finite lambda > 0" % (bias,))
+        if bias_prior is not None:
+            try:
+                bias_a0, bias_b0 = (float(v) for v in bias_prior)
+            except (TypeError, ValueError):
+                raise ValueError("bias_prior must be a pair (A0, B0)")
+            if not (bias_a0 > 0 and bias_b0 >= 0 and math.isfinite(bias_a0) and math.isfinite(bias_b0)):
+                raise ValueError("bias_prior = (A0, B0) needs a finite A0 > 0 and a finite B0 >= 0")
+        for on, what, why in ((pipelined, "pipelined=True", "the evaluation of an iteration reads the bias vectors the next one overwrites: the loop is blocking"),
+                              (probit, "probit=True", "a side has one latent step"),
+                              (ordinal is not None and ordinal is not False, "ordinal", "a side has one latent step"),
+                              (censored is not None, "censored", "a side has one latent step"),
+                              (robust is not None, "robust", "a side has one latent step"),
+                              (weights is not None, "weights", "the bias conditional is unweighted"),
+                              (implicit is not None, "implicit", "the bias conditional would run over every cell"),
+                              (row_features is not None or col_features is not None, "row_features / col_features", "the residuals would have to be formed from the bias-free values"),
+                              (new_row_features is not None or new_col_features is not None, "new_row_features / new_col_features", "they need features"),
+                              (noise == "adaptive", "noise='adaptive'", "the training residuals leave the biases out"),
+                              (foldin, "foldin=True", "a folded-in row would need a bias of its own"),
+                              (save_model is not None, "save_model", "the model format stores no biases"),
+                              (similar is not None, "similar", "the two bias rows of the sample ring would enter the cosine"),
+                              (getattr(engine, "dtype", "f64") == "f32", "an fp32 engine", "the bias kernels are fp64"),
+                              (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator", "the bias step needs both sides whole on one GPU")):
+            if on:
+                raise ValueError("bias does not go together with %s (%s)" % (what, why))
+        if alpha is not None and not (float(alpha) > 0 and math.isfinite(float(alpha))):
+            raise ValueError("bias needs a finite alpha > 0")
     if similar is not None:                          # (refused before the engine is used)
         if not (isinstance(similar, (int, np.integer)) and 1 <= int(similar) <= 32):
             raise ValueError("similar = %r: the list length must be an integer in 1 .. 32" % (similar,))
@@ -607,6 +656,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if robust is not None:
         engine.set_robust(movies.side, robust, ROBUST_TAGS[0])
         engine.set_robust(users.side, robust, ROBUST_TAGS[1])
+    if bias_on:
+        engine.set_bias(movies.side, bias_lambda, BIAS_TAGS[0], 0)
+        engine.set_bias(users.side, bias_lambda, BIAS_TAGS[1], 1)
+        if bias_prior is not None:
+            engine.bias_prior(movies.side, bias_a0, bias_b0)
+            engine.bias_prior(users.side, bias_a0, bias_b0)
     if linked:
         if col_features is not None:
             engine.set_features(movies.side, col_features, lambda_beta, 3)
@@ -659,6 +714,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             engine.newrows_add(movies.side, users.side)
         if robust is not None and i >= burnin:
             engine.robust_add(movies.side)
+        if bias_on and i >= burnin:
+            engine.bias_add(movies.side)
+            engine.bias_add(users.side)
         if probit and i >= burnin and movies.test is not None:
             engine.probit_add(movies.test, movies.side, users.side)
         if ordinal_on and i >= burnin and movies.test is not None:
@@ -807,6 +865,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         kept = max(nsims - burnin, 0)
         wm = engine.robust_get(movies.side)[0] if kept > 0 else np.zeros(len(M[2]))
         res["robust"] = dict(nu=robust, weight_mean=wm, kept=kept)
+    if bias_on:
+        kept = max(nsims - burnin, 0)
+        res["bias"] = dict(rows_mean=engine.bias_mean(users.side)[0] if kept > 0 else np.zeros(nusers),
+                           cols_mean=engine.bias_mean(movies.side)[0] if kept > 0 else np.zeros(nmovies),
+                           lambda_rows=engine.bias_lambda(users.side, nsims)[1], lambda_cols=engine.bias_lambda(movies.side, nsims)[1], kept=kept)
     if linked:
         res["beta_rows"] = engine.link_mean(users.side)[0] if row_features is not None and nsims > burnin else None
         res["beta_cols"] = engine.link_mean(movies.side)[0] if col_features is not None and nsims > burnin else None
@@ -836,6 +899,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
 
 FOLDIN_TAGS = {"rows": 7, "cols": 8}                 # the random streams of folded-in users / movies (1 .. 6 and 9, 10 are taken: gibbs)
 ORDINAL_TAGS = (11, 12)                              # the random streams of the latent scores of ordinal sides: movies, users
+BIAS_TAGS = (13, 14)                                 # the random streams of the bias draws: movies, users
 ROBUST_TAGS = (9, 10)                                # the random streams of the weights of Student-t noise: movies, users
 
 

@@ -679,6 +679,55 @@ BPMF_API int bpmf_hip_side_robust_add(bpmf_hip_side *side);
  * nothing added: BPMF_HIP_EINVAL. */
 BPMF_API int bpmf_hip_side_robust_get(bpmf_hip_side *side, double *wmean_host, int *count, double *nu);
 
+/* ---- row and column bias terms --------------------------------------------------------
+ * r_ij ~ N(mean_rating + b_i + c_j + u_i . v_j, 1 / alpha): one offset per column of either side, b_a ~ N(0, 1 / lambda), one
+ * lambda per side, fixed or sampled (bpmf_hip_side_bias_prior).  DESIGN.md section 28 has the model, the summation order, the sampled
+ * precision and the bias rows of the sample rings.
+ *
+ * bpmf_hip_side_set_bias gives a side its biases (all 0 at first).  Both sides of a pair carry them or neither does: a launch or an
+ * evaluation of one kind against the other is BPMF_HIP_EINVAL.  From then on every sampler launch of the side (bpmf_hip_sys_sample,
+ * bpmf_hip_sample_side[_launch]; iteration `iter`) is preceded on the same stream by the bias step over the factors x the side holds
+ * now, the other side's factors y and biases c:
+ *     S_a = sum_p ((r_p - mean_rating) - c[row p]) - x_a . y_row(p);   prec = lambda + alpha n_a;
+ *     b_a = (alpha S_a) / prec + xi_a / sqrt(prec),   xi_a ~ N(0, 1) from the Philox block (a lo, a hi, iter, 0; 42, tag)
+ * (a column without ratings draws from the prior), and the side's samplers read z_p = (r_p - b_a) - c[row p] in place of r_p, with
+ * the side's own mean_rating.  The sums have a fixed order (kernels_bias.h): the biases do not depend on the grid, and two launches
+ * of one iteration give the same bits.  A residual that is not finite (non-finite factors) makes the call that collects the
+ * half-iteration fail with BPMF_HIP_ENUM, naming the rating.  bpmf_hip_predict[_launch] of such a pair adds both biases to every
+ * prediction and always runs on the main stream, in order.  `role` (0 or 1; the two sides of a pair take different ones) lays out
+ * the bias rows of the side's sample ring: a ring reserved AFTER this call keeps roundup4(num_latent + 2) rows per sample, and
+ * bpmf_hip_side_samples_add writes (b, 1) (role 0) or (1, b) (role 1) behind the factor rows, so that the ring dot product of two
+ * sides of opposite roles is u . v + b + c and bpmf_hip_topn, _topn_scored, _rank_eval, _predict_block and _predict_cells serve the
+ * bias model unchanged.  Those five refuse two rings with different rows per sample, biases on one side only, and equal roles;
+ * bpmf_hip_side_samples_reserve refuses a side with biases at num_latent > 126 (the ring kernels serve 128 rows).
+ * BPMF_HIP_EINVAL: NULL, lambda not finite and > 0, tag 0, a role outside {0, 1}, an fp32 context, a side that has
+ * biases already, a probit, ordinal, censored, weighted, implicit or robust side, a mode of a tensor, features, propagated priors, the
+ * BPMF_REDUCE formulation, a sample ring reserved already or a hyper ring (fold-in), a context with a communicator or a sharded side.
+ * In turn those setters, bpmf_hip_side_hyper_reserve, bpmf_hip_sys_set_reduce, bpmf_hip_train_sse, bpmf_hip_similar[_block],
+ * bpmf_hip_side_samples_get / _set, and fold-in / new rows against such a candidate side refuse a side with biases. */
+BPMF_API int bpmf_hip_side_set_bias(bpmf_hip_side *side, double lambda, unsigned tag, int role);
+/* The current biases, ncols doubles (waits for the work in flight) / replaces them (every value finite). */
+BPMF_API int bpmf_hip_side_bias_get(bpmf_hip_side *side, double *b_host);
+BPMF_API int bpmf_hip_side_bias_set(bpmf_hip_side *side, const double *b_host);
+/* The array z as the side's newest sampler launch read it, nnz doubles in the order of the side's ratings (waits). */
+BPMF_API int bpmf_hip_side_bias_latent(bpmf_hip_side *side, double *z_host);
+/* Adds the current biases to their running sums (k_bias_accumulate behind the newest step: enqueue only). */
+BPMF_API int bpmf_hip_side_bias_add(bpmf_hip_side *side);
+/* The posterior mean of the biases (ncols doubles: the sums over the count of bpmf_hip_side_bias_add calls; waits) and that count.
+ * Either pointer may be NULL; mean_host given and nothing added: BPMF_HIP_EINVAL. */
+BPMF_API int bpmf_hip_side_bias_mean(bpmf_hip_side *side, double *mean_host, int *count);
+/* Samples the side's lambda instead of fixing it: prior Gamma(A0, rate B0), conditional Gamma(A0 + N / 2, B0 + sum_a b_a^2 / 2) with N
+ * the side's columns, drawn on the device (k_bias_lambda: the sum of squares in chunks of 256 columns added in chunk order, the
+ * Marsaglia-Tsang draw of the Student-t weights on the Philox blocks (~0, ~0, iter, attempt; 42, tag)) at the start of every
+ * half-iteration of the side but its first, into the device word the bias draw reads: no host round trip.  A draw that runs into its
+ * attempt cap, or biases that are not finite, make the call that collects the half-iteration fail with BPMF_HIP_ENUM.
+ * BPMF_HIP_EINVAL: no bias terms, A0 not finite and > 0, B0 not finite and >= 0, A0 + N / 2 < 1. */
+BPMF_API int bpmf_hip_side_bias_prior(bpmf_hip_side *side, double a0, double b0);
+/* The side's current lambda (waits for the work in flight); trace_host[i], i < ntrace: the lambda the bias step of iteration i ran
+ * with (the newest draw at or before i, the value of bpmf_hip_side_set_bias before the first; draws of the first 65 536 iterations are
+ * kept); the bias steps and the lambda draws enqueued so far.  trace_host (with ntrace = 0), steps and draws may be NULL. */
+BPMF_API int bpmf_hip_side_bias_lambda_get(bpmf_hip_side *side, double *lambda, double *trace_host, int ntrace, int64_t *steps, int64_t *draws);
+
 /* ---- sparse tensor factorisation: Bayesian CP of order 3 -------------------------------
  * A tensor of ratings r(i, j, t) -- compound x target x assay type, user x movie x time -- is modelled as
  *     r(i, j, t) ~ N(mean_rating + sum_k a_ik b_jk c_tk, 1 / alpha),   a Normal-Wishart prior per mode.
