@@ -66,6 +66,11 @@ _SIGNATURES = {
     "bpmf_hip_predict_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_predict_cells_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bpmf_hip_diag_traces": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_diag_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "bpmf_hip_diag_batch_cells": (C.c_int, [C.c_int]),
+    "bpmf_hip_diag_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_rank_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

@@ -47,6 +47,11 @@
 // among the entities of the same side, by the posterior mean of the per-sample cosine (--similar-kind euclid: negative squared
 // distance) minus --similar-kappa times its spread, to DIR/similar-cols.csv / similar-rows.csv; entities with
 // fewer than --similar-min-ratings training ratings are not listed.  Also served from --model DIR.  stdout is the same as without it.
+// --diagnose (-i - -b in 8 .. 4096; one GPU, no -g): convergence diagnostics of the test predictions.  The run keeps
+// the sample rings of both sides (the blocking loop) and after the chain bpmf_hip_diag_cells gives every test cell its split-Rhat and
+// effective sample size (ESS) over the kept samples; one more header line, four more Final lines (ESS, split-Rhat, MCSE/std, and the ESS
+// of the post-burn-in traces of RMSE, FU and FM), and with -o DIR also DIR/diagnostics.csv: row,col,mean,std,rhat,ess,mcse, 1-based
+// original ids in test-set order.  With --model DIR --predict FILE the same file is written for FILE's cells, without the trace line.
 // --model DIR -o OUT [-n TRAIN] [-p TEST]: no chain runs (run_model).  The model is loaded into a fp64 context and serves --predict FILE
 // [--predict-threshold F] (OUT/predict.csv: row,col,mean,std[,prob] for the cells FILE lists, 1-based, in the reader's order; prob with
 // sigma = 1 / sqrt(alpha), always there for a probit model with t = 0 unless given and sigma = 1), --topn N with its --topn-* flags and
@@ -153,6 +158,10 @@ void usage()
               << "              changes -- then score = mean - kappa std over the samples (kappa >= 0, default 0); entities with fewer than M\n"
               << "              training ratings are not listed (needs -o DIR and -i > -b; one GPU, no -g; 1 <= N <= 32; not with --tensor,\n"
               << "              -m / -l or BPMF_REDUCE=1; also served from --model DIR, where --similar-min-ratings needs -n TRAIN)\n"
+              << "  [--diagnose]: split-Rhat and the effective sample size (ESS) of every test prediction over the kept samples, and of the\n"
+              << "              post-burn-in traces of RMSE, FU and FM: four more Final lines and, with -o DIR, DIR/diagnostics.csv\n"
+              << "              (row,col,mean,std,rhat,ess,mcse; mcse = std / sqrt(ess)).  Needs 8 <= -i - -b <= 4096; one GPU, no -g; not with\n"
+              << "              --tensor, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE: the same file for FILE's cells\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
               << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
@@ -437,6 +446,12 @@ struct Job {
     double similar_kappa = 0.0;                                      // --similar-kappa F: score = mean - kappa std
     long similar_min = 0;                                            // --similar-min-ratings M: entities with fewer training ratings are not listed
     std::vector<int32_t> sim_idx; std::vector<double> sim_score, sim_mean, sim_std;   // queries x N, in the numbering of the run
+    bool diagnose = false;                                           // --diagnose: split-Rhat and ESS of the predictions of a list of cells
+    std::vector<int32_t> dg_q, dg_c;                                 // the cells (user, movie), in the numbering of the run
+    std::vector<double> dg_mean, dg_std, dg_rhat, dg_ess;            // per cell
+    int dg_samples = 0;                                              // the kept samples behind them
+    std::vector<double> dg_trace[3];                                 // the post-burn-in traces of RMSE, FU, FM
+    double dg_trace_ess[3] = {NAN, NAN, NAN};
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
@@ -583,6 +598,72 @@ void write_similar(const Job &J)
                     (long long)((pq.empty() ? c : pq[(size_t)c]) + 1), J.sim_score[at], J.sim_mean[at], J.sim_std[at]);
         }
     if (fclose(f) != 0) die("cannot write " + name);
+}
+
+// --diagnose over the sample rings of both sides: after the chain or from a loaded model, for the cells of
+// `cells` (one column per movie) in its order
+void serve_diag(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc &cells)
+{
+    if (!J.diagnose) return;                                         // one rank (main refuses -g)
+    const double t0 = tick();
+    const size_t n = (size_t)cells.nnz();
+    J.dg_q.resize(n); J.dg_c.resize(n);
+    for (int64_t col = 0; col < cells.ncols; ++col)
+        for (int64_t at = cells.colptr[(size_t)col]; at < cells.colptr[(size_t)col + 1]; ++at) {
+            J.dg_q[(size_t)at] = cells.rowidx[(size_t)at]; J.dg_c[(size_t)at] = (int32_t)col;
+        }
+    J.dg_mean.resize(std::max<size_t>(n, 1)); J.dg_std.resize(std::max<size_t>(n, 1)); J.dg_rhat.resize(std::max<size_t>(n, 1)); J.dg_ess.resize(std::max<size_t>(n, 1));
+    static const int32_t none = 0;
+    check(bpmf_hip_diag_cells(users, movies, J.mean_m, (int64_t)n, n ? J.dg_q.data() : &none, n ? J.dg_c.data() : &none, J.dg_mean.data(), J.dg_std.data(),
+                              J.dg_rhat.data(), J.dg_ess.data()));
+    J.dg_mean.resize(n); J.dg_std.resize(n); J.dg_rhat.resize(n); J.dg_ess.resize(n);
+    J.dg_samples = bpmf_hip_side_samples_count(users);
+    std::cerr << "diagnose: " << n << " cells over " << J.dg_samples << " samples, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+}
+
+// DIR/diagnostics.csv: test-set order, 1-based ids in the ORIGINAL numbering, like the -o writers
+void write_diag(const Job &J)
+{
+    if (!J.diagnose || J.odirname.empty()) return;
+    const std::string name = J.odirname + "/diagnostics.csv";
+    FILE *f = fopen(name.c_str(), "w");
+    if (!f) die("cannot write " + name);
+    fprintf(f, "row,col,mean,std,rhat,ess,mcse\n");
+    for (size_t i = 0; i < J.dg_q.size(); ++i) {
+        const int64_t r = J.dg_q[i], c = J.dg_c[i];
+        fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g,%.17g,%.17g\n", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.dg_mean[i], J.dg_std[i], J.dg_rhat[i], J.dg_ess[i],
+                J.dg_std[i] / std::sqrt(J.dg_ess[i]));
+    }
+    if (fclose(f) != 0) die("cannot write " + name);
+}
+
+// the Final lines of --diagnose (bpmf_amd.diag_summary computes the same figures): cells whose rhat or ess is NaN are left out
+void print_diag(std::ostream &os, const Job &J, bool traces)
+{
+    if (!J.diagnose) return;
+    std::vector<double> rh, es, ms;
+    for (size_t i = 0; i < J.dg_rhat.size(); ++i)
+        if (!std::isnan(J.dg_rhat[i]) && !std::isnan(J.dg_ess[i])) { rh.push_back(J.dg_rhat[i]); es.push_back(J.dg_ess[i]); ms.push_back(1.0 / std::sqrt(J.dg_ess[i])); }
+    auto median = [](std::vector<double> v) {
+        if (v.empty()) return (double)NAN;
+        std::sort(v.begin(), v.end());
+        return v.size() % 2 ? v[v.size() / 2] : 0.5 * (v[v.size() / 2 - 1] + v[v.size() / 2]);
+    };
+    size_t above = 0;
+    for (double r : rh) above += r > 1.01;
+    char buf[512];
+    snprintf(buf, sizeof buf, "Final ESS: min %.1f median %.1f of %d samples (%lld cells)", es.empty() ? NAN : *std::min_element(es.begin(), es.end()), median(es),
+             J.dg_samples, (long long)J.dg_rhat.size());
+    os << buf << std::endl;
+    snprintf(buf, sizeof buf, "Final split-Rhat: median %.4f max %.4f above 1.01: %.2f%%", median(rh), rh.empty() ? NAN : *std::max_element(rh.begin(), rh.end()),
+             rh.empty() ? NAN : 100.0 * (double)above / (double)rh.size());
+    os << buf << std::endl;
+    snprintf(buf, sizeof buf, "Final MCSE/std: median %.4f", median(ms));
+    os << buf << std::endl;
+    if (!traces) return;
+    snprintf(buf, sizeof buf, "Final trace ESS: RMSE %.1f FU %.1f FM %.1f", J.dg_trace_ess[0], J.dg_trace_ess[1], J.dg_trace_ess[2]);
+    os << buf << std::endl;
 }
 
 // --fold-in-rows / --fold-in-cols against the sample ring of the other side and the side's hyper ring: after the chain or from a loaded model
@@ -825,7 +906,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
     const bool saving = !J.save_model.empty();
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows), ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows);
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -941,6 +1022,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.fold_u.n > 0) os << "fold-in rows: " << J.fold_u.n << " (--fold-in-rows), " << J.fold_u.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (J.fold_m.n > 0) os << "fold-in columns: " << J.fold_m.n << " (--fold-in-cols), " << J.fold_m.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (saving) os << "save-model: " << J.save_model << std::endl;
+    if (J.diagnose) os << "diagnose: split-Rhat and ESS of the test predictions" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -1001,7 +1083,8 @@ void rank_main(Job &J, int rank, std::ostream &os)
     };
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
     // (--bias: the evaluation of an iteration reads the bias vectors the next one overwrites -- the blocking loop)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias) {
+    // (--diagnose keeps the samples in the rings too)
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -1059,6 +1142,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         check(bpmf_hip_sys_state(users, nullptr, &norm_u, nullptr, nullptr, nullptr, nullptr));
         check(bpmf_hip_sys_state(movies, nullptr, &norm_m, nullptr, nullptr, nullptr, nullptr));
         print_line(iter, rmse, rmse_avg, norm_u, norm_m, stop - start);
+        if (J.diagnose && iter >= burnin) { J.dg_trace[0].push_back(rmse); J.dg_trace[1].push_back(std::sqrt(norm_u)); J.dg_trace[2].push_back(std::sqrt(norm_m)); }
 
         // aggrMu / aggrLambda of this rank's columns, on the device (c++/sample.cpp:364-368)
         if (aggregate && iter >= burnin) { check(bpmf_hip_side_aggr_add(users)); check(bpmf_hip_side_aggr_add(movies)); }
@@ -1179,6 +1263,13 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     serve_rank(J, users, movies);                                    // --topn, --rank-eval: one rank (main refuses -g > 1)
     serve_similar(J, users, movies);
+    serve_diag(J, users, movies, J.T);
+    if (J.diagnose) {                                                // the scalar traces through the same estimator
+        const size_t S = J.dg_trace[0].size();
+        std::vector<double> tr, rh(3);
+        for (const std::vector<double> &t : J.dg_trace) tr.insert(tr.end(), t.begin(), t.end());
+        check(bpmf_hip_diag_traces(ctx, 3, (int)S, tr.data(), rh.data(), J.dg_trace_ess));
+    }
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
         if (N.n == 0) return;
@@ -1346,6 +1437,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     try { m = bpmf::io::read_model(dir); } catch (const std::exception &e) { die(e.what()); }
     const int K = m.K;
     if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
+    if (J.diagnose && (m.S < 8 || m.S > BPMF_HIP_DIAG_MAX_SAMPLES))
+        die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
     for (const std::string *f : {&fold_in_rows, &fold_in_cols}) {
         if (f->empty()) continue;
         const std::string w = f == &fold_in_rows ? "--fold-in-rows" : "--fold-in-cols";
@@ -1440,6 +1533,7 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     }
     serve_rank(J, users, movies);
     serve_similar(J, users, movies);
+    serve_diag(J, users, movies, P);                                 // --predict FILE --diagnose: FILE's cells
     serve_fold(J, users, movies);
     bpmf_hip_side_destroy(movies);
     bpmf_hip_side_destroy(users);
@@ -1447,6 +1541,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
 
     write_topn(J);
     write_similar(J);
+    write_diag(J);
+    print_diag(std::cout, J, false);
     const RankMetrics rkm = write_ranks(J);
     write_new(J, J.fold_u, true, nmovies, "foldin");
     write_new(J, J.fold_m, false, nusers, "foldin");
@@ -1496,6 +1592,7 @@ int main(int argc, char *argv[])
                                               {"similar-min-ratings", required_argument, nullptr, 1084},
                                               {"bias", no_argument, nullptr, 1090}, {"bias-lambda", required_argument, nullptr, 1091},
                                               {"bias-prior", required_argument, nullptr, 1092},
+                                              {"diagnose", no_argument, nullptr, 1100},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
     std::string bias_lambda, bias_prior;
@@ -1567,6 +1664,7 @@ int main(int argc, char *argv[])
         case 1090: training("--bias"); J.bias = true; break;
         case 1091: training("--bias-lambda"); bias_lambda = optarg; bias_lambda_given = true; break;
         case 1092: training("--bias-prior"); bias_prior = optarg; bias_prior_given = true; break;
+        case 1100: J.diagnose = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1612,6 +1710,16 @@ int main(int argc, char *argv[])
         if (J.odirname.empty()) die(std::string("--similar needs -o DIR (the lists go to DIR/similar-") + (J.similar_by_rows ? "rows" : "cols") + ".csv)");
         if (!model_given && J.nsims <= J.burnin) die("--similar needs at least one post-burn-in sample (-i > -b)");
         if (model_given && J.similar_min > 0 && fname.empty()) die("--similar-min-ratings with --model needs -n TRAIN (the training ratings are what it counts)");
+    }
+    // --diagnose: refused before anything touches a GPU
+    if (J.diagnose) {
+        if (tensor_given) die("--diagnose does not go together with --tensor (the diagnosed predictions are those of a matrix model)");
+        if (g_given || ngpu >= 1) die("--diagnose runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample ring of a sharded side is not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--diagnose does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--diagnose does not go together with a propagated posterior (-m / -l)");
+        if (model_given && !predict_given) die("--diagnose with --model needs --predict FILE (the cells whose predictions are diagnosed)");
+        if (!model_given && (J.nsims - J.burnin < 8 || J.nsims - J.burnin > BPMF_HIP_DIAG_MAX_SAMPLES))
+            die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
     }
     // --model / --predict / --save-model: refused before anything touches a GPU
     if (predict_given && !model_given) die("--predict needs --model DIR (cells are predicted from a saved model)");
@@ -2352,6 +2460,7 @@ int main(int argc, char *argv[])
 
     write_topn(J);
     write_similar(J);
+    write_diag(J);
 
     const RankMetrics rkm = write_ranks(J);
 
@@ -2435,6 +2544,7 @@ int main(int argc, char *argv[])
 
     os << "Total time: " << J.elapsed << std::endl;
     os << "Final Avg RMSE: " << J.rmse_avg << std::endl;
+    print_diag(os, J, true);
     if (J.ordinal && !J.cat_prob.empty()) {
         os << "Final ordinal RMSE: " << J.ord_rmse << std::endl;
         os << "Final accuracy: " << J.ord_accuracy << std::endl;

@@ -11,6 +11,7 @@
 //   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells (bpmf_hip_predict_cells)
+//   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities
@@ -121,6 +122,18 @@ inline int ring_pair_check(const std::string &who, const bpmf_hip_side *q, const
         return fail(BPMF_HIP_EINVAL, who + ": the two sides have the same bias role " + std::to_string(q->bias->role) + " (bpmf_hip_side_set_bias: 0 and 1)");
     return 0;
 }
+
+// A list of (query, candidate) cells over two rings (capi_model.hip): what bpmf_hip_predict_cells and bpmf_hip_diag_cells share.
+// cells_check_list refuses, as `who` and on the host alone, NULL or mismatched sides, a communicator or a shard, n, mean_rating, a NULL
+// list and a cell out of range; cells_check_rings then waits for the sides' work in flight and checks the ring pair; *S_out: the samples
+// both hold (>= 1).  cells_sort groups the list by query (stable counting sort); cells_segments cuts every query's run among the
+// sorted cells [b0, b1) into segments of at most `seg` cells and appends them, seg_beg counting from the start of the sorted list.
+struct CellsSorted { std::vector<int32_t> query, cand, orig; };       // per sorted cell: its query, its candidate, its place in the caller's list
+int cells_check_list(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q, const int32_t *cc);
+int cells_check_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, int *S_out);
+CellsSorted cells_sort(int64_t nq, int64_t n, const int32_t *q, const int32_t *cc);
+void cells_segments(const CellsSorted &s, int64_t b0, int64_t b1, int seg, std::vector<int32_t> *seg_q, std::vector<int32_t> *seg_beg,
+                    std::vector<int32_t> *seg_cnt);
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.

@@ -80,55 +80,85 @@ extern "C" int bpmf_hip_side_samples_set(bpmf_hip_side *s, int nsamples, const d
     return BPMF_HIP_OK;
 }
 
-extern "C" int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q, const int32_t *cc,
-                                      int want_prob, double t, double sigma, double *mean_out, double *std_out, double *prob_out)
+// What bpmf_hip_predict_cells and bpmf_hip_diag_cells (capi_diag.hip) refuse alike, reported as `who`.  cells_check_list: the sides and
+// the list, on the host alone; cells_check_rings: waits for the sides' work in flight, then the rings; *S_out: the samples both hold
+int bpmf_capi::cells_check_list(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                const int32_t *cc)
 {
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "predict_cells: NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "predict_cells: the two sides belong to different contexts");
-    bpmf_hip_ctx *c = query->ctx;
-    { const int rc = require_single_gpu("predict_cells", c, query, cand); if (rc) return rc; }
-    if (n < 0 || n > 0x7fffffff) return fail(BPMF_HIP_EINVAL, "predict_cells: n must be 0 .. 2^31 - 1");
-    if (!std::isfinite(mean_rating)) return fail(BPMF_HIP_EINVAL, "predict_cells: mean_rating is not finite");
-    if (want_prob && !std::isfinite(t)) return fail(BPMF_HIP_EINVAL, "predict_cells: the threshold is not finite");
-    if (want_prob && !(std::isfinite(sigma) && sigma >= 0.0)) return fail(BPMF_HIP_EINVAL, "predict_cells: sigma must be finite and >= 0");
-    if (n > 0 && (!q || !cc)) return fail(BPMF_HIP_EINVAL, "predict_cells: NULL cell list");
-    if (n > 0 && (!mean_out || !std_out || (want_prob && !prob_out))) return fail(BPMF_HIP_EINVAL, "predict_cells: NULL output");
+    if (!query || !cand) return fail(BPMF_HIP_EINVAL, who + ": NULL side");
+    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, who + ": the two sides belong to different contexts");
+    { const int rc = require_single_gpu(who.c_str(), query->ctx, query, cand); if (rc) return rc; }
+    if (n < 0 || n > 0x7fffffff) return fail(BPMF_HIP_EINVAL, who + ": n must be 0 .. 2^31 - 1");
+    if (!std::isfinite(mean_rating)) return fail(BPMF_HIP_EINVAL, who + ": mean_rating is not finite");
+    if (n > 0 && (!q || !cc)) return fail(BPMF_HIP_EINVAL, who + ": NULL cell list");
     const int64_t nq = query->ncols, nc = cand->ncols;
     for (int64_t i = 0; i < n; ++i)                                             // before the device is used
         if (q[i] < 0 || q[i] >= nq || cc[i] < 0 || cc[i] >= nc)
-            return fail(BPMF_HIP_EINVAL, "predict_cells: cell " + std::to_string((long long)i) + " (" + std::to_string(q[i]) + ", " + std::to_string(cc[i]) +
+            return fail(BPMF_HIP_EINVAL, who + ": cell " + std::to_string((long long)i) + " (" + std::to_string(q[i]) + ", " + std::to_string(cc[i]) +
                         ") is out of range (" + std::to_string((long long)nq) + " queries x " + std::to_string((long long)nc) + " candidates)");
-    HIP_TRY(hipSetDevice(c->device));
+    return BPMF_HIP_OK;
+}
+
+int bpmf_capi::cells_check_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, int *S_out)
+{
+    HIP_TRY(hipSetDevice(query->ctx->device));
     { const int rc = settle_async(query); if (rc) return rc; }
     { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "predict_cells: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check("predict_cells", query, cand); if (rb) return rb; }
+    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, who + ": no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check(who, query, cand); if (rb) return rb; }
+    const int S = query->ring->count;
+    if (S < 1 || cand->ring->count != S)
+        return fail(BPMF_HIP_EINVAL, who + ": both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
+                    std::to_string(cand->ring->count));
+    *S_out = S;
+    return BPMF_HIP_OK;
+}
+
+// the list grouped by query (stable counting sort)
+CellsSorted bpmf_capi::cells_sort(int64_t nq, int64_t n, const int32_t *q, const int32_t *cc)
+{
+    std::vector<int64_t> at((size_t)nq + 1, 0);
+    for (int64_t i = 0; i < n; ++i) ++at[(size_t)q[i] + 1];
+    for (int64_t j = 0; j < nq; ++j) at[(size_t)j + 1] += at[(size_t)j];
+    CellsSorted s;
+    s.query.resize((size_t)n); s.cand.resize((size_t)n); s.orig.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t p = at[(size_t)q[i]]++;
+        s.query[(size_t)p] = q[i]; s.cand[(size_t)p] = cc[i]; s.orig[(size_t)p] = (int32_t)i;
+    }
+    return s;
+}
+
+// every query's run among the sorted cells [b0, b1) cut into the segments a workgroup takes, appended to the three lists
+void bpmf_capi::cells_segments(const CellsSorted &s, int64_t b0, int64_t b1, int seg, std::vector<int32_t> *seg_q, std::vector<int32_t> *seg_beg,
+                               std::vector<int32_t> *seg_cnt)
+{
+    for (int64_t b = b0; b < b1;) {
+        int64_t e = b + 1;
+        while (e < b1 && e - b < seg && s.query[(size_t)e] == s.query[(size_t)b]) ++e;
+        seg_q->push_back(s.query[(size_t)b]); seg_beg->push_back((int32_t)b); seg_cnt->push_back((int32_t)(e - b));
+        b = e;
+    }
+}
+
+extern "C" int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q, const int32_t *cc,
+                                      int want_prob, double t, double sigma, double *mean_out, double *std_out, double *prob_out)
+{
+    { const int rc = cells_check_list("predict_cells", query, cand, mean_rating, n, q, cc); if (rc) return rc; }
+    if (want_prob && !std::isfinite(t)) return fail(BPMF_HIP_EINVAL, "predict_cells: the threshold is not finite");
+    if (want_prob && !(std::isfinite(sigma) && sigma >= 0.0)) return fail(BPMF_HIP_EINVAL, "predict_cells: sigma must be finite and >= 0");
+    if (n > 0 && (!mean_out || !std_out || (want_prob && !prob_out))) return fail(BPMF_HIP_EINVAL, "predict_cells: NULL output");
+    int S = 0;
+    { const int rc = cells_check_rings("predict_cells", query, cand, &S); if (rc) return rc; }
+    if (n == 0) return BPMF_HIP_OK;
+    bpmf_hip_ctx *c = query->ctx;
     bpmf_ring *qr = query->ring.get();
     const bpmf_ring *cr = cand->ring.get();
-    const int S = qr->count;
-    if (S < 1 || cr->count != S)
-        return fail(BPMF_HIP_EINVAL, "predict_cells: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cr->count));
-    if (n == 0) return BPMF_HIP_OK;
 
-    // the list grouped by query (stable counting sort), every query's run cut into the segments a workgroup takes
-    std::vector<int64_t> start((size_t)nq + 1, 0);
-    for (int64_t i = 0; i < n; ++i) ++start[(size_t)q[i] + 1];
-    for (int64_t j = 0; j < nq; ++j) start[(size_t)j + 1] += start[(size_t)j];
-    std::vector<int32_t> scand((size_t)n), orig((size_t)n), seg_q, seg_beg, seg_cnt;
-    {
-        std::vector<int64_t> at(start.begin(), start.end() - 1);
-        for (int64_t i = 0; i < n; ++i) {
-            const int64_t p = at[(size_t)q[i]]++;
-            scand[(size_t)p] = cc[i]; orig[(size_t)p] = (int32_t)i;
-        }
-    }
-    const int seg = bpmf_launch::predict_cells_segment(qr->kp);
-    for (int64_t j = 0; j < nq; ++j)
-        for (int64_t b = start[(size_t)j]; b < start[(size_t)j + 1]; b += seg) {
-            seg_q.push_back((int32_t)j); seg_beg.push_back((int32_t)b);
-            seg_cnt.push_back((int32_t)std::min<int64_t>(seg, start[(size_t)j + 1] - b));
-        }
+    const CellsSorted sorted = cells_sort(query->ncols, n, q, cc);
+    const std::vector<int32_t> &scand = sorted.cand, &orig = sorted.orig;
+    std::vector<int32_t> seg_q, seg_beg, seg_cnt;
+    cells_segments(sorted, 0, n, bpmf_launch::predict_cells_segment(qr->kp), &seg_q, &seg_beg, &seg_cnt);
     DevBuf<int32_t> d_segq, d_segb, d_segc, d_cand, d_orig;
     DevBuf<double> out;
     int rc;

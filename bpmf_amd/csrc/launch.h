@@ -228,6 +228,15 @@ int predict_cells(const PredCellsLaunch &p, hipStream_t st);   // -1: shape not 
 void samples_pack(const double *ring, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int s_from, int n, double *packed, hipStream_t st);
 void samples_unpack(const double *packed, int64_t stride, int Kp, int Kt, int64_t c_from, int64_t nc, int n, double *ring, hipStream_t st);
 
+// convergence diagnostics (kernels_diag.h, kdiag.hip).  cell_traces: predict_cells without the probability, which also stores every
+// cell's d_s at trace[(place among the sorted cells - tbase) * S + s]; the segments are those of one batch of sorted cells.
+// trace_diag: split-Rhat and ESS of ntr traces of S samples (row-major, on the device) to rhat / ess[orig[t]] (orig NULL: [t]).
+int diag_min_samples();
+int diag_max_samples();
+int cell_traces_segment(int Kp);                            // cells of a segment at most
+int cell_traces(const PredCellsLaunch &p, double *trace, int64_t tbase, hipStream_t st);          // -1: shape not supported (nothing launched)
+int trace_diag(const double *traces, int64_t ntr, int S, const int32_t *orig, double *rhat, double *ess, hipStream_t st);   // -1 likewise
+
 // What the launch structs of the add-ons below share, filled by factor_pair / side_csc (capi_internal.h):
 struct FactorPair { const void *items, *other; bool f32; int K, kt; };   // both factor matrices (leading dimension K; floats if f32), the caller's num_latent kt
 struct SideCsc { const int64_t *colptr; int64_t ncols; const int32_t *rowidx; int64_t nnz; };   // a side's ratings: column pointers (ncols + 1) and row ids, on the device

@@ -304,6 +304,48 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_predict_cells_last_ms(query.handle, C.byref(ms)))
         return ms.value
 
+    # -- convergence diagnostics ------------------------------------------------
+    DIAG_MIN_SAMPLES, DIAG_MAX_SAMPLES = 8, 4096
+
+    def diag_traces(self, X):
+        """(rhat, ess), [n] each: split-Rhat and the effective sample size of the n traces X [n, S] (one trace: [S]), every trace in
+        chronological order, 8 <= S <= 4096, by the split-chain estimator without rank normalisation.  A
+        constant trace and one with a value that is not finite give NaN for both."""
+        X = np.ascontiguousarray(X, np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        if X.ndim != 2:
+            raise ValueError("diag_traces: X must be [n, S]")
+        n, S = X.shape
+        rhat = np.empty(n); ess = np.empty(n)
+        hold = np.zeros(1)
+        _lib.check(self.lib.bpmf_hip_diag_traces(self.ctx, n, S, _ptr(X if n else hold), _ptr(rhat if n else hold), _ptr(ess if n else hold)))
+        return rhat, ess
+
+    def diag_cells(self, query, cand, mean_rating, q, c):
+        """dict(mean, std, rhat, ess), [n] each, of the cells (q[i], c[i]) over the samples of the two rings: mean and std are
+        predict_cells's, bit for bit; rhat and ess are diag_traces's of the cell's predictions in the order the samples were kept.
+        The list is as predict_cells takes it; the rings must hold 8 .. 4096 samples."""
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32)
+        if q.ndim != 1 or q.shape != c.shape:
+            raise ValueError("diag_cells: q and c must be one-dimensional and of the same length")
+        n = len(q)
+        out = [np.empty(n) for _ in range(4)]
+        hold = np.zeros(1, np.int32)
+        _lib.check(self.lib.bpmf_hip_diag_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
+                                                *[_ptr(a if n else np.zeros(1)) for a in out]))
+        return dict(mean=out[0], std=out[1], rhat=out[2], ess=out[3])
+
+    def diag_batch_cells(self, cells):
+        """Cells per batch of diag_cells (0: automatic, from the size of the trace buffer).  For tests: results do not depend on it."""
+        _lib.check(self.lib.bpmf_hip_diag_batch_cells(int(cells)))
+
+    def diag_last_ms(self, query):
+        """Device time of the kernels of the newest diag_cells with `query` as the queries, between two events (tools/diag_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_diag_last_ms(query.handle, C.byref(ms)))
+        return ms.value
+
     def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
         """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
         (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""

@@ -151,3 +151,36 @@ def predict_cells(res, rows, cols, threshold=None):
         return dict(mean=mean, std=std, prob=prob)
     mean, std = users.engine.predict_cells(users.side, movies.side, movies.mean_rating, rows, cols)
     return dict(mean=mean, std=std)
+
+
+def diag_summary(d):
+    """What one line says of the per-cell diagnostics `d` = dict(std, rhat, ess) (engine.diag_cells, res["diag"]): n (cells), n_nan
+    (cells whose rhat or ess is NaN: a constant trace), samples (d["samples"] if given, else None), ess_min, ess_median,
+    rhat_median, rhat_max, rhat_above (the share of cells with rhat > 1.01) and mcse_over_std_median, the median of
+    mcse / std = 1 / sqrt(ess) with mcse = std / sqrt(ess) the Monte-Carlo standard error of the mean.  NaNs are left out and
+    counted; without a cell left every figure is NaN."""
+    rhat = np.asarray(d["rhat"], np.float64); ess = np.asarray(d["ess"], np.float64)
+    ok = ~(np.isnan(rhat) | np.isnan(ess))
+    r, e = rhat[ok], ess[ok]
+    nan = float("nan")
+    have = len(r) > 0
+    return dict(n=int(len(rhat)), n_nan=int(len(rhat) - len(r)), samples=d.get("samples"),
+                ess_min=float(e.min()) if have else nan, ess_median=float(np.median(e)) if have else nan,
+                rhat_median=float(np.median(r)) if have else nan, rhat_max=float(r.max()) if have else nan,
+                rhat_above=float(np.mean(r > 1.01)) if have else nan,
+                mcse_over_std_median=float(np.median(1.0 / np.sqrt(e))) if have else nan)
+
+
+def diagnose(res, rows, cols):
+    """Convergence diagnostics of the predictions of the cells (rows[i], cols[i]) -- user, movie, 0-based -- over the kept samples of
+    `res` (gibbs with the rings kept, or load_model; 8 .. 4096 samples): dict(rows, cols, mean, std, rhat, ess, mcse, samples, summary)
+    with mean and std as predict_cells gives them, rhat and ess the split-Rhat and the effective sample size of the cell's trace
+    (DESIGN.md section 29), mcse = std / sqrt(ess) and summary = diag_summary of it."""
+    users, movies = res["users"], res["movies"]
+    rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
+    d = users.engine.diag_cells(users.side, movies.side, movies.mean_rating, rows, cols)
+    d.update(rows=rows, cols=cols, samples=users.engine.samples_count(users.side))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d["mcse"] = d["std"] / np.sqrt(d["ess"])
+    d["summary"] = diag_summary(d)
+    return d

@@ -197,7 +197,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -362,7 +362,34 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     sample, (b, 1) and (1, c), so that the ring dot product is u . v + b + c.  Refused with every other likelihood and add-on (probit,
     ordinal, censored, weights, robust, implicit, features, noise="adaptive"), with foldin, save_model and similar (a folded-in row has
     no bias, the model format stores none, the bias rows would enter the cosine), with pipelined=True, an fp32 engine, a communicator,
-    and, together with a sample ring, num_latent > 126.  None / False (the default): nothing changes."""
+    and, together with a sample ring, num_latent > 126.  None / False (the default): nothing changes.
+
+    diagnose=True | (rows, cols): convergence diagnostics of predictions.  The sample rings are kept as for
+    topn, and after the chain res["diag"] = bpmf_amd.diagnose's dict for the test cells in the order of T (True) or for the cells
+    (rows[i], cols[i]) -- user, movie, 0-based: per cell mean, std, the split-Rhat and the effective sample size (ESS) of the trace
+    of its prediction over the kept samples, mcse = std / sqrt(ess), and "summary" (bpmf_amd.diag_summary).  res["diag"]["scalars"] =
+    dict(rmse, norm_u, norm_m, and alpha under noise="adaptive"): (rhat, ess) of the post-burn-in per-iteration traces res[key],
+    through engine.diag_traces.  Predictions are identified where the factors are not (they rotate along the chain).  Needs 8 ..
+    4096 kept samples (nsims - burnin).  It reads only the rings, so it goes with every likelihood topn goes with, and with bias.
+    None (the default): nothing changes."""
+    diag_on = diagnose is not None and diagnose is not False
+    if diag_on:                                      # (refused before the engine is used)
+        kept = nsims - burnin
+        if not (_engine.HipEngine.DIAG_MIN_SAMPLES <= kept <= _engine.HipEngine.DIAG_MAX_SAMPLES):
+            raise ValueError("diagnose needs %d .. %d post-burn-in samples (nsims - burnin = %d)"
+                             % (_engine.HipEngine.DIAG_MIN_SAMPLES, _engine.HipEngine.DIAG_MAX_SAMPLES, kept))
+        if diagnose is True:
+            if T is None:
+                raise ValueError("diagnose=True needs a test matrix (or give the cells: diagnose=(rows, cols))")
+            diag_rows = np.ascontiguousarray(T[1], np.int32)
+            diag_cols = np.repeat(np.arange(len(T[0]) - 1, dtype=np.int32), np.diff(np.asarray(T[0], np.int64)))
+        else:
+            try:
+                diag_rows, diag_cols = (np.ascontiguousarray(v, np.int32) for v in diagnose)
+            except (TypeError, ValueError):
+                raise ValueError("diagnose must be True or a pair (rows, cols)")
+            if diag_rows.ndim != 1 or diag_rows.shape != diag_cols.shape:
+                raise ValueError("diagnose = (rows, cols): two one-dimensional arrays of the same length")
     bias_on = bias is not None and bias is not False
     if bias_prior is not None and not bias_on:
         raise ValueError("bias_prior needs bias")
@@ -679,8 +706,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -892,6 +919,12 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if save_model is not None:
         from .model import save_model as _save_model
         _save_model(res, save_model)
+    if diag_on:
+        from .model import diagnose as _diagnose
+        res["diag"] = _diagnose(res, diag_rows, diag_cols)
+        keys = ["rmse", "norm_u", "norm_m"] + (["alpha"] if adaptive else [])
+        rhat, ess = engine.diag_traces(np.array([res[k][burnin:nsims] for k in keys], np.float64))
+        res["diag"]["scalars"] = {k: (float(rhat[i]), float(ess[i])) for i, k in enumerate(keys)}
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res

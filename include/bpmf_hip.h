@@ -467,6 +467,29 @@ BPMF_API int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand, d
                                     double *prob_out);
 BPMF_API int bpmf_hip_predict_cells_last_ms(const bpmf_hip_side *query, float *ms);   /* device time of the newest launch with `query` as the queries */
 
+/* ---- convergence diagnostics: split-Rhat and ESS ----
+ *   For one trace x_0 .. x_{S-1} in chronological order, 8 <= S <= BPMF_HIP_DIAG_MAX_SAMPLES, with
+ * n = floor(S / 2), the halves A = x[0, n) and B = x[S - n, S), per half the mean m_h, d = x - m_h and
+ * c_h(t) = (1/n) sum_{i <= n-1-t} d_i d_{i+t}, c(t) = (c_A(t) + c_B(t)) / 2:
+ *     W = c(0) n / (n - 1),  var+ = c(0) + (m_A - m_B)^2 / 2,  rhat = sqrt(var+ / W),  rho_t = 1 - (W - c(t)) / var+,
+ *     P_0 = 1 + rho_1,  P_k = min(rho_2k + rho_2k+1, P_k-1) while 2k + 1 <= n - 3 and the pair sum is > 0,
+ *     tau = max(-1 + 2 sum_k P_k, 1 / log10(2n)),  ess = 2n / tau
+ * -- the split-chain estimator of Vehtari et al. (2021) without rank normalisation.  A trace with W not > 0 (constant, or holding
+ * a value that is not finite) gives NaN for both.  All fp64, also on fp32 contexts; the bits of a trace depend on the trace
+ * alone: not on its place, the batch or the launch.
+ * bpmf_hip_diag_traces: n >= 0 traces of S samples, row-major on the host.  BPMF_HIP_EINVAL: S outside the range, a NULL argument.
+ * bpmf_hip_diag_cells: the traces are p_s = mean_rating + u_s(q[i]) . v_s(c[i]) over the S samples both rings hold (mean_rating
+ * drops out of both figures); mean_out and std_out are those of bpmf_hip_predict_cells, bit for bit.  Its checks and refusals are
+ * those of bpmf_hip_predict_cells, and S outside the range.  The list is processed in batches of cells whose traces fit a fixed
+ * buffer; bpmf_hip_diag_batch_cells sets the cells per batch (0: automatic) for tests: results do not depend on it.  Waits.
+ * bpmf_hip_diag_last_ms: device time of the kernels of the newest bpmf_hip_diag_cells with `query` as the queries. */
+#define BPMF_HIP_DIAG_MAX_SAMPLES 4096
+BPMF_API int bpmf_hip_diag_traces(bpmf_hip_ctx *ctx, int64_t n, int S, const double *traces, double *rhat, double *ess);
+BPMF_API int bpmf_hip_diag_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                 const int32_t *c, double *mean_out, double *std_out, double *rhat_out, double *ess_out);
+BPMF_API int bpmf_hip_diag_batch_cells(int cells);
+BPMF_API int bpmf_hip_diag_last_ms(const bpmf_hip_side *query, float *ms);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
