@@ -52,6 +52,13 @@
 // effective sample size (ESS) over the kept samples; one more header line, four more Final lines (ESS, split-Rhat, MCSE/std, and the ESS
 // of the post-burn-in traces of RMSE, FU and FM), and with -o DIR also DIR/diagnostics.csv: row,col,mean,std,rhat,ess,mcse, 1-based
 // original ids in test-set order.  With --model DIR --predict FILE the same file is written for FILE's cells, without the trace line.
+// --score (-i - -b >= 2; one GPU, no -g): model comparison.  The run keeps the sample rings of both sides (the
+// blocking loop) and after the chain bpmf_hip_score_cells gives every test cell the log of its posterior predictive density at the
+// held-out value and every training cell the same with its WAIC correction, under the likelihood of the run (Gaussian with the
+// alpha of every kept iteration, the run's weights and censoring flags; Student-t under --robust; probit); one more header line, two
+// more Final lines (test log-density, WAIC), and with -o DIR also DIR/score.csv (row,col,value,lpd,mean,std; 1-based original ids in
+// test-set order) and DIR/waic-elpd.sdm (lpd - var of every training cell).  With --model DIR --predict FILE the values of FILE are
+// the observations (score.csv and the first line); with -n TRAIN also the WAIC of TRAIN's cells.
 // --model DIR -o OUT [-n TRAIN] [-p TEST]: no chain runs (run_model).  The model is loaded into a fp64 context and serves --predict FILE
 // [--predict-threshold F] (OUT/predict.csv: row,col,mean,std[,prob] for the cells FILE lists, 1-based, in the reader's order; prob with
 // sigma = 1 / sqrt(alpha), always there for a probit model with t = 0 unless given and sigma = 1), --topn N with its --topn-* flags and
@@ -162,6 +169,11 @@ void usage()
               << "              post-burn-in traces of RMSE, FU and FM: four more Final lines and, with -o DIR, DIR/diagnostics.csv\n"
               << "              (row,col,mean,std,rhat,ess,mcse; mcse = std / sqrt(ess)).  Needs 8 <= -i - -b <= 4096; one GPU, no -g; not with\n"
               << "              --tensor, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE: the same file for FILE's cells\n"
+              << "  [--score]: model comparison: the log posterior predictive density of every test cell (a proper score of held-out data) and\n"
+              << "              WAIC over the training cells, under the likelihood of the run: two more Final lines and, with -o DIR,\n"
+              << "              DIR/score.csv (row,col,value,lpd,mean,std) and DIR/waic-elpd.sdm.  Needs -i - -b >= 2; one GPU, no -g; not with\n"
+              << "              --tensor, --ordinal, --implicit, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE: FILE's values are\n"
+              << "              the observations, and -n TRAIN adds the WAIC of TRAIN's cells\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
               << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
@@ -452,6 +464,10 @@ struct Job {
     int dg_samples = 0;                                              // the kept samples behind them
     std::vector<double> dg_trace[3];                                 // the post-burn-in traces of RMSE, FU, FM
     double dg_trace_ess[3] = {NAN, NAN, NAN};
+    bool score = false;                                              // --score: log predictive density of the test cells, WAIC of the training cells
+    struct ScoreSet { bool have = false; std::vector<int32_t> q, c; std::vector<double> y, lpd, pw, mean, std; } sc_test, sc_train;   // cells (user, movie) in the numbering of the run
+    std::vector<double> sc_alpha;                                    // the alpha of every kept sample (one value: the same for all)
+    int sc_samples = 0;
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
@@ -664,6 +680,94 @@ void print_diag(std::ostream &os, const Job &J, bool traces)
     if (!traces) return;
     snprintf(buf, sizeof buf, "Final trace ESS: RMSE %.1f FU %.1f FM %.1f", J.dg_trace_ess[0], J.dg_trace_ess[1], J.dg_trace_ess[2]);
     os << buf << std::endl;
+}
+
+// --score over the sample rings of both sides: after the chain or from a loaded model.  `test` (NULL: none): the
+// held-out cells with their values; `train` (NULL: none): the training cells, with the weights and censoring flags of the run.  The
+// likelihood is the run's: probit, Student-t under --robust, else Gaussian; J.sc_alpha holds the alpha of the kept samples.
+void serve_score(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc *test, const Csc *train)
+{
+    if (!J.score) return;                                            // one rank (main refuses -g)
+    const double t0 = tick();
+    const int kind = J.probit ? BPMF_HIP_LOGDENS_PROBIT : J.robust ? BPMF_HIP_LOGDENS_STUDENT : BPMF_HIP_LOGDENS_GAUSSIAN;
+    auto run = [&](const Csc &cells, Job::ScoreSet &out, const double *w, const int8_t *flag) {
+        const size_t n = (size_t)cells.nnz(), n1 = std::max<size_t>(n, 1);
+        out.have = true;
+        out.q.resize(n1); out.c.resize(n1); out.y.resize(n1); out.lpd.resize(n1); out.pw.resize(n1); out.mean.resize(n1); out.std.resize(n1);
+        for (int64_t col = 0; col < cells.ncols; ++col)
+            for (int64_t at = cells.colptr[(size_t)col]; at < cells.colptr[(size_t)col + 1]; ++at) {
+                out.q[(size_t)at] = cells.rowidx[(size_t)at]; out.c[(size_t)at] = (int32_t)col;
+                out.y[(size_t)at] = J.probit ? (cells.vals[(size_t)at] > J.probit_threshold ? 1.0 : -1.0) : cells.vals[(size_t)at];
+            }
+        check(bpmf_hip_score_cells(users, movies, J.mean_m, (int64_t)n, out.q.data(), out.c.data(), out.y.data(), n ? w : nullptr, n ? flag : nullptr, kind,
+                                   J.robust_nu, (int)J.sc_alpha.size(), J.sc_alpha.data(), out.lpd.data(), out.pw.data(), out.mean.data(), out.std.data()));
+        out.q.resize(n); out.c.resize(n); out.y.resize(n); out.lpd.resize(n); out.pw.resize(n); out.mean.resize(n); out.std.resize(n);
+    };
+    if (test) run(*test, J.sc_test, nullptr, nullptr);
+    if (train) run(*train, J.sc_train, J.weighted && !J.implicit ? J.w_m.data() : nullptr, J.censored ? J.cens_m.data() : nullptr);
+    J.sc_samples = bpmf_hip_side_samples_count(users);
+    std::cerr << "score: " << (test ? J.sc_test.q.size() : 0) << " test and " << (train ? J.sc_train.q.size() : 0) << " training cells over " << J.sc_samples
+              << " samples, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+}
+
+// DIR/score.csv: the test cells in test-set order, 1-based ids in the ORIGINAL numbering, with the value as given; DIR/waic-elpd.sdm:
+// lpd - var of every training cell in the training matrix's original numbering (like robust-weights.sdm)
+void write_score(const Job &J, const Csc *test, const Csc *train)
+{
+    if (!J.score || J.odirname.empty()) return;
+    if (J.sc_test.have && test) {
+        const std::string name = J.odirname + "/score.csv";
+        FILE *f = fopen(name.c_str(), "w");
+        if (!f) die("cannot write " + name);
+        fprintf(f, "row,col,value,lpd,mean,std\n");
+        for (size_t i = 0; i < J.sc_test.q.size(); ++i) {
+            const int64_t r = J.sc_test.q[i], c = J.sc_test.c[i];
+            fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g,%.17g\n", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                    (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), test->vals[i], J.sc_test.lpd[i], J.sc_test.mean[i], J.sc_test.std[i]);
+        }
+        if (fclose(f) != 0) die("cannot write " + name);
+    }
+    if (J.sc_train.have && train && !J.sc_train.q.empty()) {
+        try {
+            Csc P = *train;
+            for (size_t i = 0; i < P.vals.size(); ++i) P.vals[i] = J.sc_train.lpd[i] - J.sc_train.pw[i];
+            if (!J.perm_m.empty()) P = permute(P, inverse(J.perm_m), J.perm_u);
+            bpmf::io::write_sparse(J.odirname + "/waic-elpd.sdm", P);
+        } catch (const std::exception &e) { die(e.what()); }
+    }
+}
+
+// the Final lines of --score (bpmf_amd.score_summary computes the same figures)
+void print_score(std::ostream &os, const Job &J)
+{
+    if (!J.score) return;
+    auto sum_se = [](const std::vector<double> &x, double *sum, double *se) {      // the sum and sqrt(n var), var with n - 1
+        const size_t n = x.size();
+        double s = 0.0, v = 0.0;
+        for (double e : x) s += e;
+        const double m = n ? s / (double)n : 0.0;
+        for (double e : x) v += (e - m) * (e - m);
+        *sum = s; *se = n > 1 ? std::sqrt((double)n * (v / (double)(n - 1))) : 0.0;
+    };
+    char buf[512];
+    if (J.sc_test.have) {
+        double s, se;
+        sum_se(J.sc_test.lpd, &s, &se);
+        const double n = (double)J.sc_test.lpd.size();
+        snprintf(buf, sizeof buf, "Final test log-density: mean %.6f se %.6f (%lld cells, %d samples)", n > 0 ? s / n : NAN, n > 0 ? se / n : NAN,
+                 (long long)J.sc_test.lpd.size(), J.sc_samples);
+        os << buf << std::endl;
+    }
+    if (J.sc_train.have) {
+        std::vector<double> e(J.sc_train.lpd.size());
+        double pw = 0.0; size_t above = 0;
+        for (size_t i = 0; i < e.size(); ++i) { e[i] = J.sc_train.lpd[i] - J.sc_train.pw[i]; pw += J.sc_train.pw[i]; above += J.sc_train.pw[i] > 0.4; }
+        double s, se;
+        sum_se(e, &s, &se);
+        snprintf(buf, sizeof buf, "Final WAIC: %.4f elpd %.4f p_waic %.4f se %.4f (%lld cells, %.2f%% with var > 0.4)", -2.0 * s, s, pw, se, (long long)e.size(),
+                 e.empty() ? NAN : 100.0 * (double)above / (double)e.size());
+        os << buf << std::endl;
+    }
 }
 
 // --fold-in-rows / --fold-in-cols against the sample ring of the other side and the side's hyper ring: after the chain or from a loaded model
@@ -906,7 +1010,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
     const bool saving = !J.save_model.empty();
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose;
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose || J.score, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose || J.score;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -1023,6 +1127,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.fold_m.n > 0) os << "fold-in columns: " << J.fold_m.n << " (--fold-in-cols), " << J.fold_m.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (saving) os << "save-model: " << J.save_model << std::endl;
     if (J.diagnose) os << "diagnose: split-Rhat and ESS of the test predictions" << std::endl;
+    if (J.score) os << "score: WAIC of the training cells and log density of the test cells" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -1084,7 +1189,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
     // (--bias: the evaluation of an iteration reads the bias vectors the next one overwrites -- the blocking loop)
     // (--diagnose keeps the samples in the rings too)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose) {
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose && !J.score) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -1270,6 +1375,12 @@ void rank_main(Job &J, int rank, std::ostream &os)
         for (const std::vector<double> &t : J.dg_trace) tr.insert(tr.end(), t.begin(), t.end());
         check(bpmf_hip_diag_traces(ctx, 3, (int)S, tr.data(), rh.data(), J.dg_trace_ess));
     }
+    if (J.score) {                                                   // the alpha every kept iteration ran with
+        J.sc_alpha.clear();
+        if (J.adaptive) for (int it = burnin; it < nsims; ++it) J.sc_alpha.push_back(J.alpha_trace[(size_t)it]);
+        else J.sc_alpha.push_back(J.probit ? 1.0 : J.alpha);
+        serve_score(J, users, movies, J.T.nnz() > 0 ? &J.T : nullptr, &J.M);     // (no test cell: no test line)
+    }
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
         if (N.n == 0) return;
@@ -1437,6 +1548,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     try { m = bpmf::io::read_model(dir); } catch (const std::exception &e) { die(e.what()); }
     const int K = m.K;
     if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
+    if (J.score && m.S < 2) die("--score needs at least 2 samples, the model " + dir + " holds " + std::to_string(m.S));
+    if (J.score && !m.probit && !(m.alpha > 0.0) && !m.hyper) die("--score needs a model with alpha > 0 (the noise precision of its likelihood)");
     if (J.diagnose && (m.S < 8 || m.S > BPMF_HIP_DIAG_MAX_SAMPLES))
         die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
     for (const std::string *f : {&fold_in_rows, &fold_in_cols}) {
@@ -1534,6 +1647,13 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     serve_rank(J, users, movies);
     serve_similar(J, users, movies);
     serve_diag(J, users, movies, P);                                 // --predict FILE --diagnose: FILE's cells
+    if (J.score) {                                                   // --predict FILE --score: FILE's values are the observations; -n TRAIN: its WAIC
+        J.probit_threshold = m.probit_threshold;
+        J.sc_alpha.clear();
+        if (m.hyper && !m.probit) for (size_t sm = 0; sm < (size_t)m.S; ++sm) J.sc_alpha.push_back(m.Uh[sm * (1 + (size_t)K + (size_t)K * K)]);
+        else J.sc_alpha.push_back(m.probit ? 1.0 : m.alpha);
+        serve_score(J, users, movies, predict_file.empty() ? nullptr : &P, fname.empty() ? nullptr : &J.M);
+    }
     serve_fold(J, users, movies);
     bpmf_hip_side_destroy(movies);
     bpmf_hip_side_destroy(users);
@@ -1543,6 +1663,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     write_similar(J);
     write_diag(J);
     print_diag(std::cout, J, false);
+    write_score(J, &P, &J.M);
+    print_score(std::cout, J);
     const RankMetrics rkm = write_ranks(J);
     write_new(J, J.fold_u, true, nmovies, "foldin");
     write_new(J, J.fold_m, false, nusers, "foldin");
@@ -1593,6 +1715,7 @@ int main(int argc, char *argv[])
                                               {"bias", no_argument, nullptr, 1090}, {"bias-lambda", required_argument, nullptr, 1091},
                                               {"bias-prior", required_argument, nullptr, 1092},
                                               {"diagnose", no_argument, nullptr, 1100},
+                                              {"score", no_argument, nullptr, 1101},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
     std::string bias_lambda, bias_prior;
@@ -1665,6 +1788,7 @@ int main(int argc, char *argv[])
         case 1091: training("--bias-lambda"); bias_lambda = optarg; bias_lambda_given = true; break;
         case 1092: training("--bias-prior"); bias_prior = optarg; bias_prior_given = true; break;
         case 1100: J.diagnose = true; break;
+        case 1101: J.score = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1721,6 +1845,17 @@ int main(int argc, char *argv[])
         if (!model_given && (J.nsims - J.burnin < 8 || J.nsims - J.burnin > BPMF_HIP_DIAG_MAX_SAMPLES))
             die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
     }
+    // --score: refused before anything touches a GPU
+    if (J.score) {
+        if (tensor_given) die("--score does not go together with --tensor (the scored likelihoods are those of a matrix model)");
+        if (J.ordinal) die("--score does not go together with --ordinal (its held-out log density is the `Final log-prob` line)");
+        if (J.implicit) die("--score does not go together with --implicit (its likelihood runs over every cell of the matrix)");
+        if (g_given || ngpu >= 1) die("--score runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample ring of a sharded side is not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--score does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--score does not go together with a propagated posterior (-m / -l)");
+        if (model_given && !predict_given && fname.empty()) die("--score with --model needs --predict FILE (held-out cells with their values) or -n TRAIN (the cells of WAIC)");
+        if (!model_given && J.nsims - J.burnin < 2) die("--score needs at least 2 post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
+    }
     // --model / --predict / --save-model: refused before anything touches a GPU
     if (predict_given && !model_given) die("--predict needs --model DIR (cells are predicted from a saved model)");
     if (predict_threshold_given && !predict_given) die("--predict-threshold needs --predict FILE");
@@ -1742,7 +1877,7 @@ int main(int argc, char *argv[])
         if (J.topn > 0 && fname.empty()) die("--topn with --model needs -n TRAIN (the rated cells are what the lists exclude)");
         if (rank_eval_given && fname.empty()) die("--rank-eval with --model needs -n TRAIN (the rated cells are what the ranks exclude)");
         if (rank_eval_given && probename.empty()) die("--rank-eval with --model needs -p TEST (the held-out cells)");
-        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty() && !similar_given)
+        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty() && !similar_given && !J.score)
             die("--model: nothing to do (--predict FILE, --topn N, --rank-eval N, --similar N, --fold-in-rows FILE or --fold-in-cols FILE)");
         if (J.odirname.empty()) die("--model needs -o DIR (the results go to files in DIR)");
     }
@@ -2461,6 +2596,7 @@ int main(int argc, char *argv[])
     write_topn(J);
     write_similar(J);
     write_diag(J);
+    write_score(J, &J.T, &J.M);
 
     const RankMetrics rkm = write_ranks(J);
 
@@ -2545,6 +2681,7 @@ int main(int argc, char *argv[])
     os << "Total time: " << J.elapsed << std::endl;
     os << "Final Avg RMSE: " << J.rmse_avg << std::endl;
     print_diag(os, J, true);
+    print_score(os, J);
     if (J.ordinal && !J.cat_prob.empty()) {
         os << "Final ordinal RMSE: " << J.ord_rmse << std::endl;
         os << "Final accuracy: " << J.ord_accuracy << std::endl;

@@ -12,6 +12,7 @@
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells (bpmf_hip_predict_cells)
 //   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
+//   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities

@@ -136,6 +136,7 @@ struct bpmf_ring {
     Event timed[2]; float cells_ms = -1.f;   // around the newest launch of k_predict_cells with the side as the queries (bpmf_hip_predict_cells_last_ms)
     Event sim_timed[2]; float sim_ms = -1.f; // around the newest bpmf_hip_similar of the side (bpmf_hip_similar_last_ms)
     Event diag_timed[2]; float diag_ms = -1.f;   // around the kernels of the newest bpmf_hip_diag_cells with the side as the queries (bpmf_hip_diag_last_ms)
+    Event score_timed[2]; float score_ms = -1.f; // around the kernels of the newest bpmf_hip_score_cells with the side as the queries (bpmf_hip_score_last_ms)
 };
 
 // rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as

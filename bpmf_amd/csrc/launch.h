@@ -237,6 +237,20 @@ int cell_traces_segment(int Kp);                            // cells of a segmen
 int cell_traces(const PredCellsLaunch &p, double *trace, int64_t tbase, hipStream_t st);          // -1: shape not supported (nothing launched)
 int trace_diag(const double *traces, int64_t ntr, int S, const int32_t *orig, double *rhat, double *ess, hipStream_t st);   // -1 likewise
 
+// model comparison (kernels_score.h, kscore.hip): predict_cells' walk of one batch of sorted cells (`cells`; want_prob, t, sigma and
+// prob are not read), which also turns every cell's S predictions into the log pointwise predictive density and the variance of the
+// log density.  kind: BPMF_HIP_LOGDENS_*; y, w (NULL: 1) and flag (NULL: none; probit: the sign of the label, never NULL) are in the
+// caller's order, c0 / as / sa are the per-sample constants of kernels_score.h (S doubles each; sa NULL without flags), on the device.
+struct ScoreCellsLaunch {
+    PredCellsLaunch cells;
+    int kind; double nu;
+    const double *y, *w; const int8_t *flag;
+    const double *c0, *as, *sa;
+    double *lpd, *pw;                                      // caller's order, on the device
+};
+int score_cells_segment(int Kp);                           // cells of a segment at most
+int score_cells(const ScoreCellsLaunch &p, hipStream_t st);   // -1: shape or kind not supported (nothing launched)
+
 // What the launch structs of the add-ons below share, filled by factor_pair / side_csc (capi_internal.h):
 struct FactorPair { const void *items, *other; bool f32; int K, kt; };   // both factor matrices (leading dimension K; floats if f32), the caller's num_latent kt
 struct SideCsc { const int64_t *colptr; int64_t ncols; const int32_t *rowidx; int64_t nnz; };   // a side's ratings: column pointers (ncols + 1) and row ids, on the device

@@ -346,6 +346,52 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_diag_last_ms(query.handle, C.byref(ms)))
         return ms.value
 
+    # -- model comparison ---------------------------------------------------------
+    LOGDENS_KINDS = {"gaussian": 0, "student": 1, "probit": 2}
+
+    def score_cells(self, query, cand, mean_rating, q, c, y, alpha, kind="gaussian", nu=0.0, w=None, flag=None):
+        """dict(lpd, pwaic, mean, std), [n] each, of the observed cells (q[i], c[i]) with the values y[i] over the S samples of the
+        two rings: lpd the log of the mean over the samples of the predictive density of y[i], pwaic the
+        variance over the samples of its log; mean and std are predict_cells's, bit for bit.  kind: "gaussian" (w: per-cell weights,
+        flag: int8 -1 / 0 / +1, a censored cell whose y is a bound), "student" (nu >= 1) or "probit" (y > 0: a positive label).
+        alpha: the noise precision, one number or S values in ring-slot order."""
+        if kind not in self.LOGDENS_KINDS:
+            raise ValueError("score_cells: kind must be one of %s, not %r" % (sorted(self.LOGDENS_KINDS), kind))
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32); y = np.ascontiguousarray(y, np.float64)
+        if q.ndim != 1 or q.shape != c.shape or y.shape != q.shape:
+            raise ValueError("score_cells: q, c and y must be one-dimensional and of the same length")
+        n = len(q)
+        alpha = np.ascontiguousarray(np.atleast_1d(alpha), np.float64)
+        if alpha.ndim != 1 or len(alpha) < 1:
+            raise ValueError("score_cells: alpha must be one number or one per sample")
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            if w.shape != q.shape:
+                raise ValueError("score_cells: w must have one weight per cell")
+        if flag is not None:
+            flag = np.ascontiguousarray(flag, np.int8)
+            if flag.shape != q.shape:
+                raise ValueError("score_cells: flag must have one flag per cell")
+        out = [np.empty(n) for _ in range(4)]
+        hold = np.zeros(1, np.int32)
+
+        def opt(a):
+            return None if a is None else _ptr(a if n else np.zeros(1, a.dtype))
+        _lib.check(self.lib.bpmf_hip_score_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
+                                                 _ptr(y if n else np.zeros(1)), opt(w), opt(flag), self.LOGDENS_KINDS[kind], float(nu), len(alpha),
+                                                 _ptr(alpha), *[_ptr(a if n else np.zeros(1)) for a in out]))
+        return dict(lpd=out[0], pwaic=out[1], mean=out[2], std=out[3])
+
+    def score_batch_cells(self, cells):
+        """Cells per launch of score_cells (0: automatic).  For tests: results do not depend on it."""
+        _lib.check(self.lib.bpmf_hip_score_batch_cells(int(cells)))
+
+    def score_last_ms(self, query):
+        """Device time of the kernels of the newest score_cells with `query` as the queries, between two events (tools/score_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_score_last_ms(query.handle, C.byref(ms)))
+        return ms.value
+
     def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
         """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
         (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""

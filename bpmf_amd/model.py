@@ -126,7 +126,8 @@ def load_model(engine, path, M=None):
             engine.hyper_reserve(sd.side, S)
             for s in range(S):
                 engine.hyper_add(sd.side, alpha[s], mu[s], lam[s])
-    info = dict(alpha=m["alpha"], probit=m["probit"], probit_threshold=m["probit_threshold"], plain=True, dtype=m["dtype"], samples=S)
+    info = dict(alpha=m["alpha"], probit=m["probit"], probit_threshold=m["probit_threshold"], plain=True, dtype=m["dtype"], samples=S,
+                nu=None, alpha_samples=[float(a) for a in m["U_hyper"][0]] if foldin else None)   # (score_cells: the format stores no nu)
     return dict(users=users, movies=movies, foldin=foldin, model_info=info)
 
 
@@ -183,4 +184,81 @@ def diagnose(res, rows, cols):
     with np.errstate(invalid="ignore", divide="ignore"):
         d["mcse"] = d["std"] / np.sqrt(d["ess"])
     d["summary"] = diag_summary(d)
+    return d
+
+
+def _sum_se(x):
+    """(sum, sqrt(n var)) of the per-cell values x, var with n - 1 in the denominator (0 for fewer than two cells)."""
+    x = np.asarray(x, np.float64)
+    n = len(x)
+    return float(x.sum()), float(math.sqrt(n * x.var(ddof=1))) if n > 1 else 0.0
+
+
+def score_summary(d):
+    """What one line says of the per-cell scores `d` = dict(lpd, pwaic) (engine.score_cells, bpmf_amd.score_cells): n (cells), lpd_sum
+    and lpd_mean (the log score: sum and mean of lpd_i), p_waic = sum pwaic_i (the effective number of parameters), elpd = sum (lpd_i -
+    pwaic_i), waic = -2 elpd, se = sqrt(n var_i elpd_i) and se_lpd = sqrt(n var_i lpd_i) (the standard errors of the two sums; var
+    with n - 1), pwaic_above = the share of cells with pwaic_i > 0.4 (where the WAIC correction is known to be unreliable: reported,
+    not asserted), samples (d["samples"] if given, else None).  Without a cell the sums are 0 and lpd_mean, pwaic_above are NaN."""
+    lpd = np.asarray(d["lpd"], np.float64); pw = np.asarray(d["pwaic"], np.float64)
+    n = len(lpd)
+    lpd_sum, se_lpd = _sum_se(lpd)
+    elpd, se = _sum_se(lpd - pw)
+    nan = float("nan")
+    return dict(n=int(n), samples=d.get("samples"), lpd_sum=lpd_sum, lpd_mean=lpd_sum / n if n else nan, p_waic=float(pw.sum()), elpd=elpd,
+                waic=-2.0 * elpd, se=se, se_lpd=se_lpd, pwaic_above=float(np.mean(pw > 0.4)) if n else nan)
+
+
+def score_compare(a, b):
+    """Two models scored on the same cells, `a` and `b` = dict(lpd, pwaic) in the same order: dict(n, elpd_diff, elpd_se, lpd_diff,
+    lpd_se) with the differences a - b of the sums and their paired standard errors sqrt(n var_i(a_i - b_i)).  A positive
+    difference of more than a few standard errors says that `a` predicts these cells better."""
+    la, lb = np.asarray(a["lpd"], np.float64), np.asarray(b["lpd"], np.float64)
+    if la.shape != lb.shape or la.ndim != 1:
+        raise ValueError("score_compare: the two results must cover the same cells")
+    ea, eb = la - np.asarray(a["pwaic"], np.float64), lb - np.asarray(b["pwaic"], np.float64)
+    elpd_diff, elpd_se = _sum_se(ea - eb)
+    lpd_diff, lpd_se = _sum_se(la - lb)
+    return dict(n=int(len(la)), elpd_diff=elpd_diff, elpd_se=elpd_se, lpd_diff=lpd_diff, lpd_se=lpd_se)
+
+
+def score_cells(res, rows, cols, values, weights=None, flags=None):
+    """The log pointwise predictive density of the observed cells (rows[i], cols[i]) -- user, movie, 0-based -- with the values
+    values[i], over the kept samples of `res` (gibbs with the rings kept, or load_model):
+    dict(rows, cols, lpd, pwaic, elpd, mean, std, samples, summary).  lpd_i = log mean_s p(y_i | sample s), pwaic_i = var_s log p(y_i |
+    sample s), elpd_i = lpd_i - pwaic_i; over held-out cells sum lpd_i is the log score, over training cells sum elpd_i is WAIC's
+    estimate of it; mean and std are predict_cells's; summary = score_summary of it.  The likelihood comes from
+    res["model_info"]: probit (values > probit_threshold is a positive label), Student-t with nu degrees of freedom after robust=nu
+    (the marginal density: the drawn weights are integrated out), else Gaussian; alpha is the precision every kept sample ran with
+    (model_info["alpha_samples"], one per sample, else model_info["alpha"]).  weights: per-cell precision weights as weights= of
+    gibbs gave them to the training cells; flags: int8, +-1 for a censored value (the value is then a bound, as censored= of gibbs);
+    both Gaussian only, None for held-out cells."""
+    users, movies = res["users"], res["movies"]
+    info = res.get("model_info")
+    if info is None:
+        raise ValueError("score_cells: the result carries no model_info (it comes from gibbs or load_model)")
+    if not info.get("scored", True):
+        raise ValueError("score_cells: ordinal and implicit runs are not scored")
+    engine = users.engine
+    S = engine.samples_count(users.side)
+    rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
+    y = np.ascontiguousarray(values, np.float64)
+    alpha = info.get("alpha_samples")
+    if alpha is None:
+        alpha = float(info.get("alpha", float("nan")))
+    elif len(alpha) != S:
+        raise ValueError("score_cells: model_info has %d values of alpha for %d kept samples" % (len(alpha), S))
+    nu = info.get("nu")
+    if info.get("probit"):
+        kind, nu, alpha = "probit", 0.0, 1.0
+        y = np.where(y > float(info.get("probit_threshold", 0.0)), 1.0, -1.0)
+    elif nu is not None:
+        kind = "student"
+    else:
+        kind, nu = "gaussian", 0.0
+    if kind != "gaussian" and (weights is not None or flags is not None):
+        raise ValueError("score_cells: weights and flags go with the Gaussian likelihood alone, this run is %s" % kind)
+    d = engine.score_cells(users.side, movies.side, movies.mean_rating, rows, cols, y, alpha, kind, nu, weights, flags)
+    d.update(rows=rows, cols=cols, samples=S, kind=kind, elpd=d["lpd"] - d["pwaic"])
+    d["summary"] = score_summary(d)
     return d

@@ -7,6 +7,7 @@ libbpmf_hip.so); this file only sequences the calls the way `Sys::sample(Sys&)`
 (c++/sample.cpp:341-385) and `main` (c++/bpmf.cpp:180-253) do.
 """
 import math
+import os as _os
 import sys as _sys
 import time
 
@@ -197,7 +198,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -371,7 +372,26 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     dict(rmse, norm_u, norm_m, and alpha under noise="adaptive"): (rhat, ess) of the post-burn-in per-iteration traces res[key],
     through engine.diag_traces.  Predictions are identified where the factors are not (they rotate along the chain).  Needs 8 ..
     4096 kept samples (nsims - burnin).  It reads only the rings, so it goes with every likelihood topn goes with, and with bias.
-    None (the default): nothing changes."""
+    None (the default): nothing changes.
+
+    score=True: model comparison.  The sample rings are kept as for topn, and after the chain res["score"] =
+    dict(train=, test=), each bpmf_amd.score_cells's dict.  "test": the log pointwise predictive density of the cells of T (the log
+    score of held-out data; absent without a test matrix).  "train": the same over every training cell in the order of M, with the
+    run's weights= and censored= flags, whose elpd = lpd - pwaic summed is WAIC's estimate of the out-of-sample log density
+    (summary["waic"] = -2 elpd).  The likelihood is the run's: Gaussian with the alpha every kept iteration ran with (noise="adaptive":
+    res["alpha"] of that iteration), Student-t with nu degrees of freedom under robust=nu (the marginal density, the weights integrated
+    out), probit under probit=True; bias terms are part of the rings.  Refused: ordinal (it has res["logp"]), implicit, a
+    communicator, BPMF_REDUCE, fewer than 2 kept samples.  False (the default): nothing changes."""
+    score_on = bool(score)
+    if score_on:                                     # (refused before the engine is used)
+        for on, what, why in ((ordinal is not None and ordinal is not False, "ordinal", "its held-out log density is res['logp']"),
+                              (implicit is not None, "implicit", "its likelihood runs over every cell of the matrix"),
+                              (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator", "the rings of both sides must be whole on one GPU"),
+                              (_os.environ.get("BPMF_REDUCE", "0") not in ("", "0"), "BPMF_REDUCE", "the rings of both sides must be whole on one GPU")):
+            if on:
+                raise ValueError("score does not go together with %s (%s)" % (what, why))
+        if nsims - burnin < 2:
+            raise ValueError("score needs at least 2 post-burn-in samples (nsims - burnin = %d)" % (nsims - burnin))
     diag_on = diagnose is not None and diagnose is not False
     if diag_on:                                      # (refused before the engine is used)
         kept = nsims - burnin
@@ -706,8 +726,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -915,7 +935,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     res["movies"], res["users"] = movies, users
     plain = not ordinal_on and implicit is None and not linked      # what bpmf_amd.save_model can store of this run
     res["model_info"] = dict(alpha=float(alpha), probit=bool(probit), probit_threshold=float(threshold) if probit else 0.0, plain=plain,
-                             why="ordinal, implicit and feature models are not stored by model format 1")
+                             why="ordinal, implicit and feature models are not stored by model format 1",
+                             nu=float(robust) if robust is not None else None,                       # (bpmf_amd.score_cells: the likelihood ..
+                             alpha_samples=[float(a) for a in res["alpha"][burnin:nsims]] if adaptive else None,   # .. and the alpha of every kept sample)
+                             scored=not ordinal_on and implicit is None)
     if save_model is not None:
         from .model import save_model as _save_model
         _save_model(res, save_model)
@@ -925,6 +948,15 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         keys = ["rmse", "norm_u", "norm_m"] + (["alpha"] if adaptive else [])
         rhat, ess = engine.diag_traces(np.array([res[k][burnin:nsims] for k in keys], np.float64))
         res["diag"]["scalars"] = {k: (float(rhat[i]), float(ess[i])) for i, k in enumerate(keys)}
+    if score_on:
+        from .model import score_cells as _score_cells
+        res["score"] = {}
+        if T is not None:
+            t_cols = np.repeat(np.arange(len(T[0]) - 1, dtype=np.int32), np.diff(np.asarray(T[0], np.int64)))
+            res["score"]["test"] = _score_cells(res, T[1], t_cols, T[2])
+        m_cols = np.repeat(np.arange(len(M[0]) - 1, dtype=np.int32), np.diff(np.asarray(M[0], np.int64)))
+        res["score"]["train"] = _score_cells(res, M[1], m_cols, M[2], weights=wts[0] if weights is not None else None,
+                                             flags=cflags[0] if censored is not None else None)
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res

@@ -490,6 +490,34 @@ BPMF_API int bpmf_hip_diag_cells(bpmf_hip_side *query, bpmf_hip_side *cand, doub
 BPMF_API int bpmf_hip_diag_batch_cells(int cells);
 BPMF_API int bpmf_hip_diag_last_ms(const bpmf_hip_side *query, float *ms);
 
+/* ---- model comparison: log pointwise predictive density and WAIC ----
+ *   For the observed cell i = (q[i], c[i]) with the value y[i], over the S samples both rings hold, with
+ * p_s = mean_rating + u_s(q[i]) . v_s(c[i]) and l_s = log p(y[i] | sample s):
+ *     lpd[i] = log((1/S) sum_s exp l_s),   pwaic[i] = sum_s (l_s - lbar)^2 / (S - 1)   (0 for S = 1)
+ * so that sum_i lpd[i] is the log score of held-out cells and sum_i (lpd[i] - pwaic[i]) the WAIC estimate of the expected log
+ * pointwise predictive density of training cells.  l_s by kind, with alpha_s the noise precision sample s ran with (alpha[0] for
+ * nalpha = 1, else alpha[s] in ring-slot order, nalpha = S) and w[i] the weight of the cell (NULL: 1):
+ *     BPMF_HIP_LOGDENS_GAUSSIAN   (1/2) log(alpha_s w_i / 2 pi) - (1/2) alpha_s w_i (y_i - p_s)^2
+ *         a cell with flag[i] = +-1 (a censored value: y_i is a bound; flag NULL: none): log Phi(flag sqrt(alpha_s) (p_s - y_i))
+ *     BPMF_HIP_LOGDENS_STUDENT    lgamma((nu+1)/2) - lgamma(nu/2) + (1/2) log(alpha_s / (nu pi)) - ((nu+1)/2) log1p(alpha_s (y_i - p_s)^2 / nu)
+ *     BPMF_HIP_LOGDENS_PROBIT     log Phi(p_s) for y_i > 0 (a positive label), log Phi(-p_s) otherwise
+ * All fp64, also on fp32 contexts.  The sum over s is a streaming log-sum-exp in s order and the variance a Welford recurrence; log Phi
+ * stays finite in both tails.  mean and std are those of bpmf_hip_predict_cells, bit for bit.  The bits of a cell depend on the cell,
+ * S and the kind alone: not on the other cells, its place in the list or the batches (bpmf_hip_score_batch_cells sets the cells per
+ * launch, 0: automatic, for tests).  Checked on the host before any launch, BPMF_HIP_EINVAL with a line that names the first
+ * offending cell: what bpmf_hip_predict_cells refuses, a NULL argument, nalpha that is neither 1 nor S, an alpha or w that is not
+ * finite and > 0, a y that is not finite, w or flags with a kind other than gaussian, a flag outside {-1, 0, +1}, nu not finite or
+ * < 1 for student.  n = 0 launches nothing.  Waits.
+ * bpmf_hip_score_last_ms: device time of the kernels of the newest bpmf_hip_score_cells with `query` as the queries. */
+#define BPMF_HIP_LOGDENS_GAUSSIAN 0
+#define BPMF_HIP_LOGDENS_STUDENT 1
+#define BPMF_HIP_LOGDENS_PROBIT 2
+BPMF_API int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                  const int32_t *c, const double *y, const double *w, const int8_t *flag, int kind, double nu,
+                                  int nalpha, const double *alpha, double *lpd, double *pwaic, double *mean, double *std);
+BPMF_API int bpmf_hip_score_batch_cells(int cells);
+BPMF_API int bpmf_hip_score_last_ms(const bpmf_hip_side *query, float *ms);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
