@@ -54,10 +54,9 @@ extern "C" int bpmf_hip_diag_traces(bpmf_hip_ctx *c, int64_t n, int S, const dou
         if (bpmf_launch::trace_diag(buf.get(), nb, S, nullptr, out.get(), out.get() + step, c->stream.get()))
             return fail(BPMF_HIP_EINVAL, "diag_traces: unsupported shape");
         if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "diag_traces: kernel launch failed");
-        if ((rc = bounded_stream_sync(c, c->stream.get(), "diag_traces"))) return rc;
-        if (hipMemcpy(rhat + b0, out.get(), (size_t)nb * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(ess + b0, out.get() + step, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(BPMF_HIP_ENODEV, "diag_traces: copying the results back failed");
+        if ((rc = bounded_stream_sync(c, c->stream.get(), "diag_traces")) ||
+            (rc = copy_back("diag_traces", {{rhat + b0, out.get(), (size_t)nb}, {ess + b0, out.get() + step, (size_t)nb}})))
+            return rc;
     }
     return BPMF_HIP_OK;
 }
@@ -67,67 +66,38 @@ extern "C" int bpmf_hip_diag_cells(bpmf_hip_side *query, bpmf_hip_side *cand, do
 {
     { const int rc = cells_check_list("diag_cells", query, cand, mean_rating, n, q, cc); if (rc) return rc; }
     if (n > 0 && (!mean_out || !std_out || !rhat_out || !ess_out)) return fail(BPMF_HIP_EINVAL, "diag_cells: NULL output");
-    int S = 0;
-    { const int rc = cells_check_rings("diag_cells", query, cand, &S); if (rc) return rc; }
-    { const int rb = refuse_samples("diag_cells", S); if (rb) return rb; }
+    bpmf_launch::PredCellsLaunch p{};
+    int rc;
+    if ((rc = pair_open_rings("diag_cells", query, cand, &p.r)) || (rc = refuse_samples("diag_cells", p.r.S))) return rc;
     if (n == 0) return BPMF_HIP_OK;
     bpmf_hip_ctx *c = query->ctx;
-    bpmf_ring *qr = query->ring.get();
-    const bpmf_ring *cr = cand->ring.get();
+    Timed &timed = query->ring->diag;
+    const int S = p.r.S;
 
-    const CellsSorted sorted = cells_sort(query->ncols, n, q, cc);
-    const int64_t step = std::min<int64_t>(n, batch_traces(S));
-    const int seg = bpmf_launch::cell_traces_segment(qr->kp);
     // batches of sorted cells: one trace buffer, filled by k_cell_traces and read by k_trace_diag of the batch, in stream order (no
-    // wait in between).  Segments do not cross a batch; a cell's results do not depend on where the batches are cut.
-    std::vector<int32_t> seg_q, seg_beg, seg_cnt;
-    std::vector<size_t> first;                                                 // per batch: its first segment
-    for (int64_t b0 = 0; b0 < n; b0 += step) {
-        first.push_back(seg_q.size());
-        cells_segments(sorted, b0, std::min<int64_t>(n, b0 + step), seg, &seg_q, &seg_beg, &seg_cnt);
-    }
-    first.push_back(seg_q.size());
-    DevBuf<int32_t> d_segq, d_segb, d_segc, d_cand, d_orig;
+    // wait in between)
+    const CellsSorted sorted = cells_sort(query->ncols, n, q, cc);
+    CellsPlan plan(sorted, n, std::min<int64_t>(n, batch_traces(S)), bpmf_launch::cell_traces_segment(p.r.Kp));
     DevBuf<double> out, trace;
-    int rc;
-    if ((rc = d_cand.upload(sorted.cand.data(), sorted.cand.size())) || (rc = d_orig.upload(sorted.orig.data(), sorted.orig.size())) ||
-        (rc = d_segq.upload(seg_q.data(), seg_q.size())) || (rc = d_segb.upload(seg_beg.data(), seg_beg.size())) ||
-        (rc = d_segc.upload(seg_cnt.data(), seg_cnt.size())) || (rc = out.alloc((size_t)4 * (size_t)n)) ||
-        (rc = trace.alloc((size_t)step * (size_t)S)))
-        return rc;
-    bpmf_launch::PredCellsLaunch p{};
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.mean_rating = mean_rating;
-    p.cand = d_cand.get(); p.orig = d_orig.get();
+    if ((rc = plan.upload()) || (rc = out.alloc((size_t)4 * (size_t)n)) || (rc = trace.alloc((size_t)plan.step * (size_t)S))) return rc;
+    p.mean_rating = mean_rating;
     p.mean = out.get(); p.std = out.get() + n;
-    for (Event &e : qr->diag_timed) if (!e) { const int re = e.create(); if (re) return re; }
-    qr->diag_ms = -1.f;
-    HIP_TRY(hipEventRecord(qr->diag_timed[0].get(), c->stream.get()));
-    for (size_t b = 0; b + 1 < first.size(); ++b) {
-        const int64_t b0 = (int64_t)b * step, nb = std::min<int64_t>(step, n - b0);
-        p.nseg = (int64_t)(first[b + 1] - first[b]);
-        p.seg_q = d_segq.get() + first[b]; p.seg_beg = d_segb.get() + first[b]; p.seg_cnt = d_segc.get() + first[b];
-        if (bpmf_launch::cell_traces(p, trace.get(), b0, c->stream.get()) ||
-            bpmf_launch::trace_diag(trace.get(), nb, S, d_orig.get() + b0, out.get() + 2 * n, out.get() + 3 * n, c->stream.get()))
+    if ((rc = timed.begin(c->stream.get()))) return rc;
+    for (size_t b = 0; b < plan.nbatches(); ++b) {
+        plan.bind(p, b);
+        if (bpmf_launch::cell_traces(p, trace.get(), plan.begin(b), c->stream.get()) ||
+            bpmf_launch::trace_diag(trace.get(), plan.cells(b), S, plan.orig() + plan.begin(b), out.get() + 2 * n, out.get() + 3 * n, c->stream.get()))
             return fail(BPMF_HIP_EINVAL, "diag_cells: unsupported shape");
         if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "diag_cells: kernel launch failed");
     }
-    HIP_TRY(hipEventRecord(qr->diag_timed[1].get(), c->stream.get()));
-    if ((rc = bounded_stream_sync(c, c->stream.get(), "diag_cells"))) return rc;
-    if (hipEventElapsedTime(&qr->diag_ms, qr->diag_timed[0].get(), qr->diag_timed[1].get()) != hipSuccess) { (void)hipGetLastError(); qr->diag_ms = -1.f; }
-    double *const dst[4] = {mean_out, std_out, rhat_out, ess_out};
-    for (int k = 0; k < 4; ++k)
-        if (hipMemcpy(dst[k], out.get() + (size_t)k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(BPMF_HIP_ENODEV, "diag_cells: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = timed.end(c->stream.get())) || (rc = bounded_stream_sync(c, c->stream.get(), "diag_cells"))) return rc;
+    timed.resolve();
+    return copy_back("diag_cells", {{mean_out, out.get(), (size_t)n}, {std_out, out.get() + n, (size_t)n}, {rhat_out, out.get() + 2 * n, (size_t)n},
+                                    {ess_out, out.get() + 3 * n, (size_t)n}});
 }
 
 extern "C" int bpmf_hip_diag_last_ms(const bpmf_hip_side *query, float *ms)
 {
-    if (!query || !ms) return fail(BPMF_HIP_EINVAL, "diag_last_ms: NULL argument");
-    if (!query->ring || query->ring->diag_ms < 0.f)
-        return fail(BPMF_HIP_EINVAL, "diag_last_ms: no diagnostics with the side as the queries have been timed (bpmf_hip_diag_cells)");
-    *ms = query->ring->diag_ms;
-    return BPMF_HIP_OK;
+    return last_ms("diag_last_ms", query, query && query->ring ? &query->ring->diag : nullptr, ms,
+                   "no diagnostics with the side as the queries have been timed (bpmf_hip_diag_cells)");
 }

@@ -68,11 +68,6 @@ int foldin_pair(const char *who, bpmf_hip_side *side, bpmf_hip_side *cand)
     return 0;
 }
 
-TopnRings foldin_rings(const bpmf_foldin *f, const bpmf_ring *cr)
-{
-    return TopnRings{f->ring.get(), cr->samples.get(), (int64_t)f->S * f->kp, (int64_t)cr->max * cr->kp, f->kp, f->S};
-}
-
 }  // namespace
 
 extern "C" int bpmf_hip_side_hyper_reserve(bpmf_hip_side *s, int max_samples)
@@ -215,19 +210,17 @@ extern "C" int bpmf_hip_foldin(bpmf_hip_side *side, bpmf_hip_side *cand, double 
     __atomic_store_n(f->fail.host(), ~0ull, __ATOMIC_RELEASE);
     bpmf_launch::FoldinLaunch p{};
     p.rowptr = d_ptr.get(); p.colidx = d_idx.get(); p.vals = d_vals.get(); p.n_new = n_new;
-    p.cring = cr->samples.get(); p.cstride = (int64_t)cr->max * cr->kp;
+    p.cring = cr->samples.get(); p.cstride = ring_view(cr).stride;
     p.alpha = d_alpha.get(); p.lam = d_lam.get(); p.lmu = d_lmu.get(); p.S = S;
     p.K = c->K; p.kt = c->Kt; p.kp = kp; p.mean_rating = mean_rating; p.tag = tag; p.draw = draw ? 1 : 0;
     p.out = d_ring.get(); p.fail = f->fail.dev();
-    for (Event &e : f->timed) if (!e) { const int re = e.create(); if (re) return re; }
-    f->last_ms = -1.f;
-    HIP_TRY(hipEventRecord(f->timed[0].get(), c->stream.get()));
+    if ((rc = f->timed.begin(c->stream.get()))) return rc;
     if (bpmf_launch::foldin(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "foldin: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "foldin: kernel launch failed");
-    HIP_TRY(hipEventRecord(f->timed[1].get(), c->stream.get()));
+    if ((rc = f->timed.end(c->stream.get()))) return rc;
     c->last_sampler_done = nullptr;
     if ((rc = bounded_stream_sync(c, c->stream.get(), "foldin"))) return rc;
-    if (hipEventElapsedTime(&f->last_ms, f->timed[0].get(), f->timed[1].get()) != hipSuccess) { (void)hipGetLastError(); f->last_ms = -1.f; }
+    f->timed.resolve();
     f->rowptr = std::move(d_ptr); f->colidx = std::move(d_idx); f->ring = std::move(d_ring);
     f->n = n_new; f->S = S; f->kp = kp;
     const unsigned long long bad = __atomic_load_n(f->fail.host(), __ATOMIC_ACQUIRE);
@@ -271,7 +264,7 @@ extern "C" int bpmf_hip_foldin_predict(bpmf_hip_side *side, bpmf_hip_side *cand,
 {
     { const int rc = foldin_pair("foldin_predict", side, cand); if (rc) return rc; }
     const bpmf_foldin *f = side->foldin.get();
-    return predict_rings("foldin_predict", side->ctx, foldin_rings(f, cand->ring.get()), f->n, cand->ncols, nullptr, mean_rating, q_from, q_to, c_from,
+    return predict_rings("foldin_predict", side->ctx, ring_pair(f, cand->ring.get()), f->n, cand->ncols, nullptr, mean_rating, q_from, q_to, c_from,
                          c_to, mean_out, std_out);
 }
 
@@ -279,21 +272,17 @@ extern "C" int bpmf_hip_foldin_topn(bpmf_hip_side *side, bpmf_hip_side *cand, do
                                     double *mean_out, double *std_out)
 {
     { const int rc = foldin_pair("foldin_topn", side, cand); if (rc) return rc; }
-    if (n < 1 || n > bpmf_launch::topn_max_n())
-        return fail(BPMF_HIP_EINVAL, "foldin_topn: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
+    { const int rc = refuse_topn_n("foldin_topn", n); if (rc) return rc; }
     if (!idx_out || !mean_out || !std_out) return fail(BPMF_HIP_EINVAL, "foldin_topn: NULL output");
     const bpmf_foldin *f = side->foldin.get();
     // the rows' own ratings are the exclusion lists: sorted columns of the candidate side per query, the format the ranking takes
-    return topn_rings(side->ctx, foldin_rings(f, cand->ring.get()), mean_rating, n, 0, f->n, cand->ncols, exclude_rated ? f->rowptr.get() : nullptr,
+    return topn_rings(side->ctx, ring_pair(f, cand->ring.get()), mean_rating, n, 0, f->n, cand->ncols, exclude_rated ? f->rowptr.get() : nullptr,
                       exclude_rated ? f->colidx.get() : nullptr, idx_out, mean_out, std_out);
 }
 
 extern "C" int bpmf_hip_foldin_last_ms(const bpmf_hip_side *s, float *ms)
 {
-    if (!s || !ms) return fail(BPMF_HIP_EINVAL, "foldin_last_ms: NULL argument");
-    if (!s->foldin || s->foldin->last_ms < 0.f) return fail(BPMF_HIP_EINVAL, "foldin_last_ms: no launch of the side has been timed (bpmf_hip_foldin)");
-    *ms = s->foldin->last_ms;
-    return BPMF_HIP_OK;
+    return last_ms("foldin_last_ms", s, s && s->foldin ? &s->foldin->timed : nullptr, ms, "no launch of the side has been timed (bpmf_hip_foldin)");
 }
 
 extern "C" int bpmf_hip_foldin_chunk(void) { return bpmf_launch::foldin_chunk(); }

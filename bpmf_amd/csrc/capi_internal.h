@@ -6,11 +6,14 @@
 //   capi_sample.hip    sampler launches, stateless half-iteration, posterior aggregation, the stateful pipeline (bpmf_hip_sys_sample)
 //   capi_comm.hip      communicator, ranges, parts, staleness, packed connectivity exchange, BPMF_REDUCE between ranks
 //   capi_eval.hip      test sets and Sys::predict
-//   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn, bpmf_hip_topn_scored)
+//   capi_topn.hip      sample rings and the posterior top-N ranking (bpmf_hip_topn, bpmf_hip_topn_scored, bpmf_hip_rank_eval); what every query
+//                      over two rings shares: the prologue (pair_check_sides, pair_open_rings), the refusals of n and of a range, the
+//                      lists of a ranking (TopnLists), the read-back (copy_back) and the *_last_ms entry points (last_ms)
 //   capi_similar.hip   similar columns of one side by posterior cosine / distance over its ring (bpmf_hip_similar, bpmf_hip_similar_block)
 //   capi_newrows.hip   dense blocks of predictions from two rings (bpmf_hip_predict_block); rows unseen in training (bpmf_hip_newrows_*)
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
-//   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells (bpmf_hip_predict_cells)
+//   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells
+//                      (bpmf_hip_predict_cells); what the cell lists share: their checks, their sort and their batches (CellsPlan)
 //   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
 //   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
@@ -111,30 +114,78 @@ int latent_read_back(const char *func, bpmf_hip_side *s, const double *z, double
 enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce, bias };
 int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> order);
 
-// Two sample rings that meet in one dot product (capi_topn.hip, capi_newrows.hip, capi_model.hip): the same rows per sample, and, with
-// bias rows (capi_bias.hip), biases on both sides in opposite roles -- else the product is not mean + b + c + u . v
-inline int ring_pair_check(const std::string &who, const bpmf_hip_side *q, const bpmf_hip_side *c)
+// ---- Ring queries: what the entry points that reduce mean + u_s . v_s over two rings share (defined in capi_topn.hip) ----
+// One ring as a launch reads it.  These three are the only places a ring stride is computed.
+struct RingView { const double *ring; int64_t stride; int kp, count; };   // doubles per column, rows per sample, samples held
+inline RingView ring_view(const bpmf_ring *r) { return {r->samples.get(), (int64_t)r->max * r->kp, r->kp, r->count}; }
+inline RingView ring_view(const bpmf_newrows *nr) { return {nr->ring.get(), (int64_t)nr->max * nr->kp, nr->kp, nr->count}; }
+inline RingView ring_view(const bpmf_foldin *f) { return {f->ring.get(), (int64_t)f->S * f->kp, f->kp, f->S}; }
+// queries of `q` against candidates of `c` (a sample ring, new rows or folded-in rows each: either order); the queries' count is S
+template <typename Q, typename Cn>
+inline bpmf_launch::RingPair ring_pair(const Q *q, const Cn *c)
 {
-    if (q->ring->kp != c->ring->kp)
-        return fail(BPMF_HIP_EINVAL, who + ": the two sample rings hold " + std::to_string(q->ring->kp) + " and " + std::to_string(c->ring->kp) +
-                                     " rows per sample (bias terms on one side only?)");
-    if ((bool)q->bias != (bool)c->bias) return fail(BPMF_HIP_EINVAL, who + ": both sides of a pair carry bias terms or neither does (bpmf_hip_side_set_bias)");
-    if (q->bias && q->bias->role == c->bias->role)
-        return fail(BPMF_HIP_EINVAL, who + ": the two sides have the same bias role " + std::to_string(q->bias->role) + " (bpmf_hip_side_set_bias: 0 and 1)");
-    return 0;
+    const RingView a = ring_view(q), b = ring_view(c);
+    return {a.ring, b.ring, a.stride, b.stride, a.kp, a.count};
 }
+// The prologue of a query over the sample rings of two sides, in two steps with the caller's own argument checks between them.
+// pair_check_sides, on the host alone: NULL sides, two contexts and, if asked, a communicator or a shard (require_single_gpu).
+// pair_open_rings: sets the device, waits for the sides' work in flight, then refuses a missing ring, rings that do not meet in one
+// dot product (rows per sample, bias roles) and counts that differ or are 0; *out: the pair.
+int pair_check_sides(const std::string &who, const bpmf_hip_side *query, const bpmf_hip_side *cand, bool single_gpu);
+int pair_open_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, bpmf_launch::RingPair *out);
+int refuse_topn_n(const char *who, int n);                             // "<who>: n = .. (1 .. topn_max_n)"
+int refuse_range(const char *who, const char *what, int64_t from, int64_t to, int64_t ncols);   // "<who>: <what> range out of bounds"
+// device -> host copies of results, skipping a NULL destination or an empty array: "<who>: copying the results back failed"
+struct CopyBack {
+    void *dst; const void *src; size_t bytes;
+    template <typename T>
+    CopyBack(T *d, const typename std::common_type<T>::type *s, size_t count) : dst(d), src(s), bytes(count * sizeof(T)) {}   // (T from d alone)
+};
+int copy_back(const std::string &who, std::initializer_list<CopyBack> list);
+// a *_last_ms entry point: NULL arguments, then `none_msg` while `t` (NULL: no state yet) has timed nothing
+int last_ms(const char *who, const bpmf_hip_side *s, const Timed *t, float *ms, const char *none_msg);
 
-// A list of (query, candidate) cells over two rings (capi_model.hip): what bpmf_hip_predict_cells and bpmf_hip_diag_cells share.
-// cells_check_list refuses, as `who` and on the host alone, NULL or mismatched sides, a communicator or a shard, n, mean_rating, a NULL
-// list and a cell out of range; cells_check_rings then waits for the sides' work in flight and checks the ring pair; *S_out: the samples
-// both hold (>= 1).  cells_sort groups the list by query (stable counting sort); cells_segments cuts every query's run among the
-// sorted cells [b0, b1) into segments of at most `seg` cells and appends them, seg_beg counting from the start of the sorted list.
+// The lists of a ranking of nq queries x n places over nsplit candidate splits: what the score + select kernel leaves per split
+// (part_*), what the merge leaves (out_*), and their read-back.  scored: the rankings by a score of their own keep score | mean | std
+// per split; the plain one keeps the mean per split and gets its std after the merge.
+struct TopnLists {
+    size_t pn = 0, nsplit = 0; bool scored = false;
+    DevBuf<double> part, out; DevBuf<int32_t> pidx, oidx;
+    int alloc(const char *who, int64_t nsplit_, int64_t nq, int n, bool scored_);
+    double *part_score() const { return part.get(); }
+    double *part_mean() const { return part.get() + (scored ? nsplit * pn : 0); }
+    double *part_std() const { return part.get() + 2 * nsplit * pn; }
+    int32_t *part_idx() const { return pidx.get(); }
+    double *out_score() const { return out.get(); }
+    double *out_mean() const { return out.get() + (scored ? pn : 0); }
+    double *out_std() const { return out_mean() + pn; }
+    int32_t *out_idx() const { return oidx.get(); }
+    int read_back(const char *who, int32_t *idx, double *score, double *mean, double *std) const;   // score NULL: not scored
+};
+
+// A list of (query, candidate) cells over two rings (capi_model.hip): what bpmf_hip_predict_cells, bpmf_hip_diag_cells and
+// bpmf_hip_score_cells share.  cells_check_list refuses, as `who` and on the host alone, what pair_check_sides does (single GPU), then
+// n, mean_rating, a NULL list and a cell out of range; pair_open_rings follows the caller's own checks.  cells_sort groups the list by
+// query (stable counting sort).
 struct CellsSorted { std::vector<int32_t> query, cand, orig; };       // per sorted cell: its query, its candidate, its place in the caller's list
 int cells_check_list(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q, const int32_t *cc);
-int cells_check_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, int *S_out);
 CellsSorted cells_sort(int64_t nq, int64_t n, const int32_t *q, const int32_t *cc);
-void cells_segments(const CellsSorted &s, int64_t b0, int64_t b1, int seg, std::vector<int32_t> *seg_q, std::vector<int32_t> *seg_beg,
-                    std::vector<int32_t> *seg_cnt);
+// The launches of a sorted list: batches of `step` sorted cells (the last one shorter), every query's run within a batch cut into the
+// segments of at most `seg` cells a workgroup takes.  Segments do not cross a batch; seg_beg counts from the start of the sorted
+// list, so a cell's results do not depend on where the batches are cut.
+struct CellsPlan {
+    const CellsSorted &sorted; int64_t n, step;
+    std::vector<int32_t> seg_q, seg_beg, seg_cnt;
+    std::vector<size_t> first;                                         // per batch: its first segment; then their number
+    DevBuf<int32_t> d_segq, d_segb, d_segc, d_cand, d_orig;
+    CellsPlan(const CellsSorted &s, int64_t n_, int64_t step_, int seg);
+    int upload();
+    size_t nbatches() const { return first.size() - 1; }
+    int64_t begin(size_t b) const { return (int64_t)b * step; }        // the first sorted cell of batch b
+    int64_t cells(size_t b) const { return std::min<int64_t>(step, n - begin(b)); }
+    const int32_t *orig() const { return d_orig.get(); }
+    void bind(bpmf_launch::PredCellsLaunch &p, size_t b) const;        // nseg, seg_q, seg_beg, seg_cnt of batch b; cand, orig
+};
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.
@@ -148,8 +199,7 @@ int link_check_csr(const char *who, int64_t N, int64_t D, const int64_t *rowptr,
 
 // posterior top-N over two rings of S samples (capi_topn.hip): what bpmf_hip_topn and bpmf_hip_newrows_topn share.  Queries
 // [q_from, q_from + nq) of qring against the candidates [0, nc) of cring; ex_ptr / ex_rows: the exclusion lists or NULL.  Waits.
-struct TopnRings { const double *qring, *cring; int64_t qstride, cstride; int kp, S; };
-int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
+int topn_rings(bpmf_hip_ctx *c, const bpmf_launch::RingPair &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
                const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out);
 // the candidate splits both rankings use: a split is a multiple of 64 candidates; they are used when the query blocks alone do not
 // fill the device
@@ -158,7 +208,7 @@ void topn_splits(const bpmf_hip_ctx *c, int64_t nq, int64_t nc, int64_t *nsplit,
 // mean / std (nq x nc each) of queries [q_from, q_to) against candidates [c_from, c_to) of two rings of S samples (capi_newrows.hip):
 // what bpmf_hip_predict_block, bpmf_hip_newrows_predict and bpmf_hip_foldin_predict share.  w: added to the variance as w[candidate] / S,
 // or NULL.  device_out: the outputs are device memory of the context's device and written in place, else host arrays.  Waits.
-int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
+int predict_rings(const char *who, bpmf_hip_ctx *c, const bpmf_launch::RingPair &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
                   int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to, double *mean_out, double *std_out, bool device_out = false);
 
 // evaluation (capi_eval.hip)

@@ -34,7 +34,7 @@ extern "C" int bpmf_hip_side_samples_get(bpmf_hip_side *s, int s_from, int s_to,
     { const int rc = packed.alloc((size_t)std::min<int64_t>(step, s->ncols) * (size_t)n * (size_t)kt); if (rc) return rc; }
     for (int64_t c0 = 0; c0 < s->ncols; c0 += step) {
         const int64_t nc = std::min<int64_t>(step, s->ncols - c0);
-        bpmf_launch::samples_pack(ring->samples.get(), (int64_t)ring->max * ring->kp, ring->kp, kt, c0, nc, s_from, n, packed.get(), c->stream.get());
+        bpmf_launch::samples_pack(ring->samples.get(), ring_view(ring).stride, ring->kp, kt, c0, nc, s_from, n, packed.get(), c->stream.get());
         if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "samples_get: kernel launch failed");
         { const int rc = bounded_stream_sync(c, c->stream.get(), "samples_get"); if (rc) return rc; }
         HIP_TRY(hipMemcpy(host + (size_t)c0 * (size_t)n * (size_t)kt, packed.get(), (size_t)nc * (size_t)n * (size_t)kt * sizeof(double), hipMemcpyDeviceToHost));
@@ -71,7 +71,7 @@ extern "C" int bpmf_hip_side_samples_set(bpmf_hip_side *s, int nsamples, const d
         for (int64_t c0 = 0; c0 < s->ncols; c0 += step) {
             const int64_t nc = std::min<int64_t>(step, s->ncols - c0);
             HIP_TRY(hipMemcpy(packed.get(), host + (size_t)c0 * (size_t)n * (size_t)kt, (size_t)nc * (size_t)n * (size_t)kt * sizeof(double), hipMemcpyHostToDevice));
-            bpmf_launch::samples_unpack(packed.get(), (int64_t)ring->max * ring->kp, ring->kp, kt, c0, nc, n, ring->samples.get(), c->stream.get());
+            bpmf_launch::samples_unpack(packed.get(), ring_view(ring).stride, ring->kp, kt, c0, nc, n, ring->samples.get(), c->stream.get());
             if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "samples_set: kernel launch failed");
             { const int rc = bounded_stream_sync(c, c->stream.get(), "samples_set"); if (rc) return rc; }
         }
@@ -80,14 +80,11 @@ extern "C" int bpmf_hip_side_samples_set(bpmf_hip_side *s, int nsamples, const d
     return BPMF_HIP_OK;
 }
 
-// What bpmf_hip_predict_cells and bpmf_hip_diag_cells (capi_diag.hip) refuse alike, reported as `who`.  cells_check_list: the sides and
-// the list, on the host alone; cells_check_rings: waits for the sides' work in flight, then the rings; *S_out: the samples both hold
+// What the cell lists (here, capi_diag.hip, capi_score.hip) refuse alike, reported as `who`, on the host alone: the sides and the list
 int bpmf_capi::cells_check_list(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
                                 const int32_t *cc)
 {
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, who + ": NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, who + ": the two sides belong to different contexts");
-    { const int rc = require_single_gpu(who.c_str(), query->ctx, query, cand); if (rc) return rc; }
+    { const int rc = pair_check_sides(who, query, cand, true); if (rc) return rc; }
     if (n < 0 || n > 0x7fffffff) return fail(BPMF_HIP_EINVAL, who + ": n must be 0 .. 2^31 - 1");
     if (!std::isfinite(mean_rating)) return fail(BPMF_HIP_EINVAL, who + ": mean_rating is not finite");
     if (n > 0 && (!q || !cc)) return fail(BPMF_HIP_EINVAL, who + ": NULL cell list");
@@ -96,21 +93,6 @@ int bpmf_capi::cells_check_list(const std::string &who, bpmf_hip_side *query, bp
         if (q[i] < 0 || q[i] >= nq || cc[i] < 0 || cc[i] >= nc)
             return fail(BPMF_HIP_EINVAL, who + ": cell " + std::to_string((long long)i) + " (" + std::to_string(q[i]) + ", " + std::to_string(cc[i]) +
                         ") is out of range (" + std::to_string((long long)nq) + " queries x " + std::to_string((long long)nc) + " candidates)");
-    return BPMF_HIP_OK;
-}
-
-int bpmf_capi::cells_check_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, int *S_out)
-{
-    HIP_TRY(hipSetDevice(query->ctx->device));
-    { const int rc = settle_async(query); if (rc) return rc; }
-    { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, who + ": no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check(who, query, cand); if (rb) return rb; }
-    const int S = query->ring->count;
-    if (S < 1 || cand->ring->count != S)
-        return fail(BPMF_HIP_EINVAL, who + ": both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cand->ring->count));
-    *S_out = S;
     return BPMF_HIP_OK;
 }
 
@@ -129,16 +111,37 @@ CellsSorted bpmf_capi::cells_sort(int64_t nq, int64_t n, const int32_t *q, const
     return s;
 }
 
-// every query's run among the sorted cells [b0, b1) cut into the segments a workgroup takes, appended to the three lists
-void bpmf_capi::cells_segments(const CellsSorted &s, int64_t b0, int64_t b1, int seg, std::vector<int32_t> *seg_q, std::vector<int32_t> *seg_beg,
-                               std::vector<int32_t> *seg_cnt)
+// every query's run among the sorted cells of a batch cut into the segments a workgroup takes
+bpmf_capi::CellsPlan::CellsPlan(const CellsSorted &s, int64_t n_, int64_t step_, int seg) : sorted(s), n(n_), step(step_)
 {
-    for (int64_t b = b0; b < b1;) {
-        int64_t e = b + 1;
-        while (e < b1 && e - b < seg && s.query[(size_t)e] == s.query[(size_t)b]) ++e;
-        seg_q->push_back(s.query[(size_t)b]); seg_beg->push_back((int32_t)b); seg_cnt->push_back((int32_t)(e - b));
-        b = e;
+    for (int64_t b0 = 0; b0 < n; b0 += step) {
+        first.push_back(seg_q.size());
+        const int64_t b1 = std::min<int64_t>(n, b0 + step);
+        for (int64_t b = b0; b < b1;) {
+            int64_t e = b + 1;
+            while (e < b1 && e - b < seg && s.query[(size_t)e] == s.query[(size_t)b]) ++e;
+            seg_q.push_back(s.query[(size_t)b]); seg_beg.push_back((int32_t)b); seg_cnt.push_back((int32_t)(e - b));
+            b = e;
+        }
     }
+    first.push_back(seg_q.size());
+}
+
+int bpmf_capi::CellsPlan::upload()
+{
+    int rc;
+    if ((rc = d_segq.upload(seg_q.data(), seg_q.size())) || (rc = d_segb.upload(seg_beg.data(), seg_beg.size())) ||
+        (rc = d_segc.upload(seg_cnt.data(), seg_cnt.size())) || (rc = d_cand.upload(sorted.cand.data(), sorted.cand.size())) ||
+        (rc = d_orig.upload(sorted.orig.data(), sorted.orig.size())))
+        return rc;
+    return 0;
+}
+
+void bpmf_capi::CellsPlan::bind(bpmf_launch::PredCellsLaunch &p, size_t b) const
+{
+    p.nseg = (int64_t)(first[b + 1] - first[b]);
+    p.seg_q = d_segq.get() + first[b]; p.seg_beg = d_segb.get() + first[b]; p.seg_cnt = d_segc.get() + first[b];
+    p.cand = d_cand.get(); p.orig = d_orig.get();
 }
 
 extern "C" int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q, const int32_t *cc,
@@ -148,52 +151,32 @@ extern "C" int bpmf_hip_predict_cells(bpmf_hip_side *query, bpmf_hip_side *cand,
     if (want_prob && !std::isfinite(t)) return fail(BPMF_HIP_EINVAL, "predict_cells: the threshold is not finite");
     if (want_prob && !(std::isfinite(sigma) && sigma >= 0.0)) return fail(BPMF_HIP_EINVAL, "predict_cells: sigma must be finite and >= 0");
     if (n > 0 && (!mean_out || !std_out || (want_prob && !prob_out))) return fail(BPMF_HIP_EINVAL, "predict_cells: NULL output");
-    int S = 0;
-    { const int rc = cells_check_rings("predict_cells", query, cand, &S); if (rc) return rc; }
+    bpmf_launch::PredCellsLaunch p{};
+    int rc;
+    if ((rc = pair_open_rings("predict_cells", query, cand, &p.r))) return rc;
     if (n == 0) return BPMF_HIP_OK;
     bpmf_hip_ctx *c = query->ctx;
-    bpmf_ring *qr = query->ring.get();
-    const bpmf_ring *cr = cand->ring.get();
+    Timed &timed = query->ring->cells;
 
     const CellsSorted sorted = cells_sort(query->ncols, n, q, cc);
-    const std::vector<int32_t> &scand = sorted.cand, &orig = sorted.orig;
-    std::vector<int32_t> seg_q, seg_beg, seg_cnt;
-    cells_segments(sorted, 0, n, bpmf_launch::predict_cells_segment(qr->kp), &seg_q, &seg_beg, &seg_cnt);
-    DevBuf<int32_t> d_segq, d_segb, d_segc, d_cand, d_orig;
+    CellsPlan plan(sorted, n, n, bpmf_launch::predict_cells_segment(p.r.Kp));      // one batch
     DevBuf<double> out;
-    int rc;
-    if ((rc = d_segq.upload(seg_q.data(), seg_q.size())) || (rc = d_segb.upload(seg_beg.data(), seg_beg.size())) ||
-        (rc = d_segc.upload(seg_cnt.data(), seg_cnt.size())) || (rc = d_cand.upload(scand.data(), scand.size())) ||
-        (rc = d_orig.upload(orig.data(), orig.size())) || (rc = out.alloc((size_t)(want_prob ? 3 : 2) * (size_t)n)))
-        return rc;
-    bpmf_launch::PredCellsLaunch p{};
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.mean_rating = mean_rating;
+    if ((rc = plan.upload()) || (rc = out.alloc((size_t)(want_prob ? 3 : 2) * (size_t)n))) return rc;
+    p.mean_rating = mean_rating;
     p.want_prob = want_prob ? 1 : 0; p.t = want_prob ? t : 0.0; p.sigma = want_prob ? sigma : 0.0;
-    p.nseg = (int64_t)seg_q.size();
-    p.seg_q = d_segq.get(); p.seg_beg = d_segb.get(); p.seg_cnt = d_segc.get(); p.cand = d_cand.get(); p.orig = d_orig.get();
+    plan.bind(p, 0);
     p.mean = out.get(); p.std = out.get() + n; p.prob = want_prob ? out.get() + 2 * n : nullptr;
-    for (Event &e : qr->timed) if (!e) { const int re = e.create(); if (re) return re; }
-    qr->cells_ms = -1.f;
-    HIP_TRY(hipEventRecord(qr->timed[0].get(), c->stream.get()));
+    if ((rc = timed.begin(c->stream.get()))) return rc;
     if (bpmf_launch::predict_cells(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, "predict_cells: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "predict_cells: kernel launch failed");
-    HIP_TRY(hipEventRecord(qr->timed[1].get(), c->stream.get()));
-    if ((rc = bounded_stream_sync(c, c->stream.get(), "predict_cells"))) return rc;
-    if (hipEventElapsedTime(&qr->cells_ms, qr->timed[0].get(), qr->timed[1].get()) != hipSuccess) { (void)hipGetLastError(); qr->cells_ms = -1.f; }
-    if (hipMemcpy(mean_out, out.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        (want_prob && hipMemcpy(prob_out, out.get() + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(BPMF_HIP_ENODEV, "predict_cells: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = timed.end(c->stream.get())) || (rc = bounded_stream_sync(c, c->stream.get(), "predict_cells"))) return rc;
+    timed.resolve();
+    return copy_back("predict_cells", {{mean_out, out.get(), (size_t)n}, {std_out, out.get() + n, (size_t)n},
+                                       {want_prob ? prob_out : nullptr, out.get() + 2 * n, (size_t)n}});
 }
 
 extern "C" int bpmf_hip_predict_cells_last_ms(const bpmf_hip_side *query, float *ms)
 {
-    if (!query || !ms) return fail(BPMF_HIP_EINVAL, "predict_cells_last_ms: NULL argument");
-    if (!query->ring || query->ring->cells_ms < 0.f)
-        return fail(BPMF_HIP_EINVAL, "predict_cells_last_ms: no launch with the side as the queries has been timed (bpmf_hip_predict_cells)");
-    *ms = query->ring->cells_ms;
-    return BPMF_HIP_OK;
+    return last_ms("predict_cells_last_ms", query, query && query->ring ? &query->ring->cells : nullptr, ms,
+                   "no launch with the side as the queries has been timed (bpmf_hip_predict_cells)");
 }

@@ -64,12 +64,12 @@ namespace bpmf_capi {
 
 // mean / std (nq x nc each) of queries [q_from, q_to) against candidates [c_from, c_to) of two rings of S samples; waits.
 // device_out: mean_out / std_out are device memory of the context's device and written in place, else host arrays
-int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
+int predict_rings(const char *who, bpmf_hip_ctx *c, const bpmf_launch::RingPair &r, int64_t nqcols, int64_t nccols, const double *w, double mean_rating,
                   int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to, double *mean_out, double *std_out, bool device_out)
 {
     const std::string ws(who);
-    if (q_from < 0 || q_to < q_from || q_to > nqcols) return fail(BPMF_HIP_EINVAL, ws + ": query range out of bounds");
-    if (c_from < 0 || c_to < c_from || c_to > nccols) return fail(BPMF_HIP_EINVAL, ws + ": candidate range out of bounds");
+    { const int rc = refuse_range(who, "query", q_from, q_to, nqcols); if (rc) return rc; }
+    { const int rc = refuse_range(who, "candidate", c_from, c_to, nccols); if (rc) return rc; }
     const int64_t nq = q_to - q_from, nc = c_to - c_from;
     if (nq == 0 || nc == 0) return BPMF_HIP_OK;
     if (!mean_out || !std_out) return fail(BPMF_HIP_EINVAL, ws + ": NULL output");
@@ -88,16 +88,13 @@ int predict_rings(const char *who, bpmf_hip_ctx *c, const TopnRings &r, int64_t 
         return fail(BPMF_HIP_ENOMEM, ws + ": a block of " + std::to_string((long long)nq) + " x " + std::to_string((long long)nc) + " means and deviations (" +
                     mib(2 * cells) + ") does not fit in device memory: predict in smaller ranges");
     bpmf_launch::PredBlockLaunch p{};
-    p.qring = r.qring; p.cring = r.cring; p.qstride = r.qstride; p.cstride = r.cstride; p.Kp = r.kp; p.S = r.S; p.mean_rating = mean_rating;
+    p.r = r; p.mean_rating = mean_rating;
     p.q_from = q_from; p.nq = nq; p.c_from = c_from; p.nc = nc; p.w = w;
     p.mean = in_place ? mean_out : out.get(); p.std = in_place ? std_out : out.get() + cells;
     if (bpmf_launch::predict_block(p, c->stream.get())) return fail(BPMF_HIP_EINVAL, ws + ": unsupported shape of the block");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, ws + ": kernel launch failed");
     { const int rc = bounded_stream_sync(c, c->stream.get(), who); if (rc) return rc; }
-    if (!in_place && (hipMemcpy(mean_out, out.get(), cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-                      hipMemcpy(std_out, out.get() + cells, cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(BPMF_HIP_ENODEV, ws + ": copying the results back failed");
-    return BPMF_HIP_OK;
+    return in_place ? BPMF_HIP_OK : copy_back(ws, {{mean_out, out.get(), cells}, {std_out, out.get() + cells, cells}});
 }
 
 }  // namespace bpmf_capi
@@ -187,7 +184,7 @@ extern "C" int bpmf_hip_side_newrows_add(bpmf_hip_side *s, bpmf_hip_side *other)
     hipStream_t st = c->stream.get();
     const bpmf_link *L = s->link.get();
     const int slot = nr->count;
-    const int64_t stride = (int64_t)nr->max * kp;
+    const int64_t stride = ring_view(nr).stride;
     // R^-1 (upper triangular, row-major) of Lambda = R^T R, R = LambdaU (upper, column-major): K^3 on the host, into one of two
     // pinned halves (R^-1 | mu) taken in turn; the event of a half says that the copies which read it two calls ago are done
     const std::vector<double> &LU = s->hp_LambdaU;
@@ -239,7 +236,7 @@ static int newrows_ring_to_host(const char *who, bpmf_hip_side *s, std::vector<d
     if (!out) return BPMF_HIP_OK;
     const size_t kp = (size_t)nr->kp, S = (size_t)nr->count;
     out->resize((size_t)nr->n * S * kp);
-    HIP_TRY(hipMemcpy2D(out->data(), S * kp * sizeof(double), nr->ring.get(), (size_t)nr->max * kp * sizeof(double), S * kp * sizeof(double),
+    HIP_TRY(hipMemcpy2D(out->data(), S * kp * sizeof(double), nr->ring.get(), (size_t)ring_view(nr).stride * sizeof(double), S * kp * sizeof(double),
                         (size_t)nr->n, hipMemcpyDeviceToHost));
     return BPMF_HIP_OK;
 }
@@ -273,31 +270,16 @@ extern "C" int bpmf_hip_newrows_predict(bpmf_hip_side *side, bpmf_hip_side *cand
 {
     { const int rc = newrows_pair("newrows_predict", side, cand); if (rc) return rc; }
     const bpmf_newrows *nr = side->newrows.get();
-    const bpmf_ring *cr = cand->ring.get();
-    const TopnRings r{nr->ring.get(), cr->samples.get(), (int64_t)nr->max * nr->kp, (int64_t)cr->max * cr->kp, nr->kp, nr->count};
-    return predict_rings("newrows_predict", side->ctx, r, nr->n, cand->ncols, nr->w.get(), mean_rating, q_from, q_to, c_from, c_to, mean_out, std_out);
+    return predict_rings("newrows_predict", side->ctx, ring_pair(nr, cand->ring.get()), nr->n, cand->ncols, nr->w.get(), mean_rating, q_from, q_to, c_from, c_to, mean_out, std_out);
 }
 
 static int predict_block_of(const char *who, bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to, int64_t c_from,
                             int64_t c_to, double *mean_out, double *std_out, bool device_out)
 {
-    const std::string w(who);
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, w + ": NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, w + ": the two sides belong to different contexts");
-    bpmf_hip_ctx *c = query->ctx;
-    int rc = require_single_gpu(who, c, query, cand);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = settle_async(query)) || (rc = settle_async(cand))) return rc;
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, w + ": no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check(w, query, cand); if (rb) return rb; }
-    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
-    const int S = qr->count;
-    if (S < 1 || cr->count != S)
-        return fail(BPMF_HIP_EINVAL, w + ": both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cr->count));
-    const TopnRings r{qr->samples.get(), cr->samples.get(), (int64_t)qr->max * qr->kp, (int64_t)cr->max * cr->kp, qr->kp, S};
-    return predict_rings(who, c, r, query->ncols, cand->ncols, nullptr, mean_rating, q_from, q_to, c_from, c_to, mean_out, std_out, device_out);
+    int rc;
+    bpmf_launch::RingPair r;
+    if ((rc = pair_check_sides(who, query, cand, true)) || (rc = pair_open_rings(who, query, cand, &r))) return rc;
+    return predict_rings(who, query->ctx, r, query->ncols, cand->ncols, nullptr, mean_rating, q_from, q_to, c_from, c_to, mean_out, std_out, device_out);
 }
 
 extern "C" int bpmf_hip_predict_block(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to, int64_t c_from,
@@ -316,18 +298,15 @@ extern "C" int bpmf_hip_newrows_topn(bpmf_hip_side *side, bpmf_hip_side *cand, d
                                      double *mean_out, double *std_out)
 {
     { const int rc = newrows_pair("newrows_topn", side, cand); if (rc) return rc; }
-    if (n < 1 || n > bpmf_launch::topn_max_n())
-        return fail(BPMF_HIP_EINVAL, "newrows_topn: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
+    { const int rc = refuse_topn_n("newrows_topn", n); if (rc) return rc; }
     if (!idx_out || !mean_out || !std_out) return fail(BPMF_HIP_EINVAL, "newrows_topn: NULL output");
     bpmf_hip_ctx *c = side->ctx;
     const bpmf_newrows *nr = side->newrows.get();
     const bpmf_ring *cr = cand->ring.get();
     const int S = nr->count;
-    const TopnRings fwd{nr->ring.get(), cr->samples.get(), (int64_t)nr->max * nr->kp, (int64_t)cr->max * cr->kp, nr->kp, S};
-    const TopnRings rev{fwd.cring, fwd.qring, fwd.cstride, fwd.qstride, nr->kp, S};
     const int64_t nq = new_are_queries ? nr->n : cand->ncols, nc = new_are_queries ? cand->ncols : nr->n;
     if (nq == 0) return BPMF_HIP_OK;
-    int rc = topn_rings(c, new_are_queries ? fwd : rev, mean_rating, n, 0, nq, nc, nullptr, nullptr, idx_out, mean_out, std_out);
+    int rc = topn_rings(c, new_are_queries ? ring_pair(nr, cr) : ring_pair(cr, nr), mean_rating, n, 0, nq, nc, nullptr, nullptr, idx_out, mean_out, std_out);
     if (rc) return rc;
     // the total deviation: the spread between the samples (k_topn_std) and w / S of the pair's in-matrix column, joined on the host
     std::vector<double> w((size_t)std::max<int64_t>(nr->nw, 1));

@@ -48,14 +48,16 @@ extern "C" int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, d
         if (flag && (flag[i] < -1 || flag[i] > 1))
             return fail(BPMF_HIP_EINVAL, "score_cells: the flag " + std::to_string((int)flag[i]) + " of " + cell_name(i, q, cc) + " is not -1, 0 or +1");
     }
-    int S = 0;
-    { const int rc = cells_check_rings("score_cells", query, cand, &S); if (rc) return rc; }
+    bpmf_launch::ScoreCellsLaunch sl{};
+    bpmf_launch::PredCellsLaunch &p = sl.cells;
+    int rc;
+    if ((rc = pair_open_rings("score_cells", query, cand, &p.r))) return rc;
+    const int S = p.r.S;
     if (nalpha != 1 && nalpha != S)
         return fail(BPMF_HIP_EINVAL, "score_cells: " + std::to_string(nalpha) + " values of alpha for " + std::to_string(S) + " samples (1 or as many)");
     if (n == 0) return BPMF_HIP_OK;
     bpmf_hip_ctx *c = query->ctx;
-    bpmf_ring *qr = query->ring.get();
-    const bpmf_ring *cr = cand->ring.get();
+    Timed &timed = query->ring->score;
 
     // the per-sample constants (kernels_score.h): c0 | as | sa
     std::vector<double> cst((size_t)3 * (size_t)S);
@@ -75,67 +77,38 @@ extern "C" int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, d
     bool any_flag = false;
     if (flag) for (int64_t i = 0; i < n && !any_flag; ++i) any_flag = flag[i] != 0;
 
+    // batches of sorted cells, one launch each, in stream order
     const CellsSorted sorted = cells_sort(query->ncols, n, q, cc);
     const int forced = g_batch_cells.load();
-    const int64_t step = std::min<int64_t>(n, forced > 0 ? forced : kBatchCells);
-    const int seg = bpmf_launch::score_cells_segment(qr->kp);
-    // batches of sorted cells, one launch each, in stream order.  Segments do not cross a batch; a cell's results do not depend on
-    // where the batches are cut.
-    std::vector<int32_t> seg_q, seg_beg, seg_cnt;
-    std::vector<size_t> first;                                                 // per batch: its first segment
-    for (int64_t b0 = 0; b0 < n; b0 += step) {
-        first.push_back(seg_q.size());
-        cells_segments(sorted, b0, std::min<int64_t>(n, b0 + step), seg, &seg_q, &seg_beg, &seg_cnt);
-    }
-    first.push_back(seg_q.size());
-    DevBuf<int32_t> d_segq, d_segb, d_segc, d_cand, d_orig;
+    CellsPlan plan(sorted, n, std::min<int64_t>(n, forced > 0 ? forced : kBatchCells), bpmf_launch::score_cells_segment(p.r.Kp));
     DevBuf<double> out, d_y, d_w, d_cst;
     DevBuf<int8_t> d_flag;
-    int rc;
-    if ((rc = d_cand.upload(sorted.cand.data(), sorted.cand.size())) || (rc = d_orig.upload(sorted.orig.data(), sorted.orig.size())) ||
-        (rc = d_segq.upload(seg_q.data(), seg_q.size())) || (rc = d_segb.upload(seg_beg.data(), seg_beg.size())) ||
-        (rc = d_segc.upload(seg_cnt.data(), seg_cnt.size())) || (rc = out.alloc((size_t)4 * (size_t)n)) ||
-        (rc = d_y.upload(y, (size_t)n)) || (rc = d_cst.upload(cst.data(), cst.size())))
+    if ((rc = plan.upload()) || (rc = out.alloc((size_t)4 * (size_t)n)) || (rc = d_y.upload(y, (size_t)n)) || (rc = d_cst.upload(cst.data(), cst.size())))
         return rc;
     if (w && (rc = d_w.upload(w, (size_t)n))) return rc;
     if (kind == BPMF_HIP_LOGDENS_PROBIT) { if ((rc = d_flag.upload(sign.data(), sign.size()))) return rc; }
     else if (any_flag && (rc = d_flag.upload(flag, (size_t)n))) return rc;
-    bpmf_launch::ScoreCellsLaunch sl{};
-    bpmf_launch::PredCellsLaunch &p = sl.cells;
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.mean_rating = mean_rating;
-    p.cand = d_cand.get(); p.orig = d_orig.get();
+    p.mean_rating = mean_rating;
     p.mean = out.get() + 2 * n; p.std = out.get() + 3 * n;
     sl.kind = kind; sl.nu = nu;
     sl.y = d_y.get(); sl.w = w ? d_w.get() : nullptr;
     sl.flag = (kind == BPMF_HIP_LOGDENS_PROBIT || any_flag) ? d_flag.get() : nullptr;      // without a censored cell: the plain form
     sl.c0 = d_cst.get(); sl.as = d_cst.get() + S; sl.sa = d_cst.get() + 2 * (size_t)S;
     sl.lpd = out.get(); sl.pw = out.get() + n;
-    for (Event &e : qr->score_timed) if (!e) { const int re = e.create(); if (re) return re; }
-    qr->score_ms = -1.f;
-    HIP_TRY(hipEventRecord(qr->score_timed[0].get(), c->stream.get()));
-    for (size_t b = 0; b + 1 < first.size(); ++b) {
-        p.nseg = (int64_t)(first[b + 1] - first[b]);
-        p.seg_q = d_segq.get() + first[b]; p.seg_beg = d_segb.get() + first[b]; p.seg_cnt = d_segc.get() + first[b];
+    if ((rc = timed.begin(c->stream.get()))) return rc;
+    for (size_t b = 0; b < plan.nbatches(); ++b) {
+        plan.bind(p, b);
         if (bpmf_launch::score_cells(sl, c->stream.get())) return fail(BPMF_HIP_EINVAL, "score_cells: unsupported shape");
         if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "score_cells: kernel launch failed");
     }
-    HIP_TRY(hipEventRecord(qr->score_timed[1].get(), c->stream.get()));
-    if ((rc = bounded_stream_sync(c, c->stream.get(), "score_cells"))) return rc;
-    if (hipEventElapsedTime(&qr->score_ms, qr->score_timed[0].get(), qr->score_timed[1].get()) != hipSuccess) { (void)hipGetLastError(); qr->score_ms = -1.f; }
-    double *const dst[4] = {lpd_out, pw_out, mean_out, std_out};
-    for (int k = 0; k < 4; ++k)
-        if (hipMemcpy(dst[k], out.get() + (size_t)k * (size_t)n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-            return fail(BPMF_HIP_ENODEV, "score_cells: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = timed.end(c->stream.get())) || (rc = bounded_stream_sync(c, c->stream.get(), "score_cells"))) return rc;
+    timed.resolve();
+    return copy_back("score_cells", {{lpd_out, out.get(), (size_t)n}, {pw_out, out.get() + n, (size_t)n}, {mean_out, out.get() + 2 * n, (size_t)n},
+                                     {std_out, out.get() + 3 * n, (size_t)n}});
 }
 
 extern "C" int bpmf_hip_score_last_ms(const bpmf_hip_side *query, float *ms)
 {
-    if (!query || !ms) return fail(BPMF_HIP_EINVAL, "score_last_ms: NULL argument");
-    if (!query->ring || query->ring->score_ms < 0.f)
-        return fail(BPMF_HIP_EINVAL, "score_last_ms: no scoring with the side as the queries has been timed (bpmf_hip_score_cells)");
-    *ms = query->ring->score_ms;
-    return BPMF_HIP_OK;
+    return last_ms("score_last_ms", query, query && query->ring ? &query->ring->score : nullptr, ms,
+                   "no scoring with the side as the queries has been timed (bpmf_hip_score_cells)");
 }

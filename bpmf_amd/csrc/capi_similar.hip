@@ -37,93 +37,73 @@ extern "C" int bpmf_hip_similar(bpmf_hip_side *side, int kind, double kappa, int
 {
     if (!side) return fail(BPMF_HIP_EINVAL, "similar: NULL side");
     if (!(std::isfinite(kappa) && kappa >= 0.0)) return fail(BPMF_HIP_EINVAL, "similar: kappa must be finite and >= 0");
-    if (n < 1 || n > bpmf_launch::topn_max_n())
-        return fail(BPMF_HIP_EINVAL, "similar: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
-    if (q_from < 0 || q_to < q_from || q_to > side->ncols) return fail(BPMF_HIP_EINVAL, "similar: query range out of bounds");
+    int rc;
+    if ((rc = refuse_topn_n("similar", n)) || (rc = refuse_range("similar", "query", q_from, q_to, side->ncols))) return rc;
     const int64_t nq = q_to - q_from, nc = side->ncols;
     if (nq > 0 && (!idx_out || !score_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "similar: NULL output");
     DevBuf<double> tab;
-    int rc = similar_prepare("similar", side, kind, tab);
-    if (rc) return rc;
+    if ((rc = similar_prepare("similar", side, kind, tab))) return rc;
     if (nq == 0) return BPMF_HIP_OK;
     bpmf_hip_ctx *c = side->ctx;
     bpmf_ring *ring = side->ring.get();
+    const RingView v = ring_view(ring);
 
     int64_t nsplit, cspan;
     topn_splits(c, nq, nc, &nsplit, &cspan);
-    const size_t pn = (size_t)nq * (size_t)n;
-    DevBuf<double> part, out;                                             // score | mean | std of the splits / of the result
-    DevBuf<int32_t> part_idx, out_idx;
+    TopnLists l;
     DevBuf<uint8_t> d_ok;
-    if (part.alloc(3 * (size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(3 * pn) || out_idx.alloc(pn))
-        return fail(BPMF_HIP_ENOMEM, "similar: device allocation of the result lists failed");
+    if ((rc = l.alloc("similar", nsplit, nq, n, true))) return rc;
     if (cand_ok && (rc = d_ok.upload(cand_ok, (size_t)nc))) return rc;
     bpmf_launch::SimilarLaunch p{};
-    p.ring = ring->samples.get(); p.stride = (int64_t)ring->max * ring->kp; p.tab = tab.get();
-    p.Kp = ring->kp; p.S = ring->count; p.n = n; p.kind = kind; p.kappa = kappa;
+    p.ring = v.ring; p.stride = v.stride; p.tab = tab.get();
+    p.Kp = v.kp; p.S = v.count; p.n = n; p.kind = kind; p.kappa = kappa;
     p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
     p.cand_ok = cand_ok ? d_ok.get() : nullptr;
-    p.part_score = part.get(); p.part_mean = part.get() + (size_t)nsplit * pn; p.part_std = part.get() + 2 * (size_t)nsplit * pn;
-    p.part_idx = part_idx.get();
-    p.out_score = out.get(); p.out_mean = out.get() + pn; p.out_std = out.get() + 2 * pn; p.out_idx = out_idx.get();
-    for (Event &e : ring->sim_timed) if (!e) { const int re = e.create(); if (re) return re; }
-    ring->sim_ms = -1.f;
-    HIP_TRY(hipEventRecord(ring->sim_timed[0].get(), c->stream.get()));
+    p.part_score = l.part_score(); p.part_mean = l.part_mean(); p.part_std = l.part_std(); p.part_idx = l.part_idx();
+    p.out_score = l.out_score(); p.out_mean = l.out_mean(); p.out_std = l.out_std(); p.out_idx = l.out_idx();
+    if ((rc = ring->sim.begin(c->stream.get()))) return rc;
     if (bpmf_launch::ring_norms(p.ring, p.stride, p.Kp, p.S, nc, tab.get(), c->stream.get())) return fail(BPMF_HIP_EINVAL, "similar: unsupported shape of the ring");
     const int lrc = bpmf_launch::similar_topn(p, c->stream.get());
     if (lrc == -2) return fail(BPMF_HIP_ENODEV, "similar: the device refused the LDS of lists of " + std::to_string(n));
     if (lrc) return fail(BPMF_HIP_EINVAL, "similar: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "similar: kernel launch failed");
-    HIP_TRY(hipEventRecord(ring->sim_timed[1].get(), c->stream.get()));
-    if ((rc = bounded_stream_sync(c, c->stream.get(), "similar"))) return rc;
-    if (hipEventElapsedTime(&ring->sim_ms, ring->sim_timed[0].get(), ring->sim_timed[1].get()) != hipSuccess) { (void)hipGetLastError(); ring->sim_ms = -1.f; }
-    if (hipMemcpy(score_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(mean_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + 2 * pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "similar: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = ring->sim.end(c->stream.get())) || (rc = bounded_stream_sync(c, c->stream.get(), "similar"))) return rc;
+    ring->sim.resolve();
+    return l.read_back("similar", idx_out, score_out, mean_out, std_out);
 }
 
 extern "C" int bpmf_hip_similar_block(bpmf_hip_side *side, int kind, int64_t q_from, int64_t q_to, int64_t c_from, int64_t c_to,
                                       double *mean_out, double *std_out)
 {
     if (!side) return fail(BPMF_HIP_EINVAL, "similar_block: NULL side");
-    if (q_from < 0 || q_to < q_from || q_to > side->ncols) return fail(BPMF_HIP_EINVAL, "similar_block: query range out of bounds");
-    if (c_from < 0 || c_to < c_from || c_to > side->ncols) return fail(BPMF_HIP_EINVAL, "similar_block: candidate range out of bounds");
+    int rc;
+    if ((rc = refuse_range("similar_block", "query", q_from, q_to, side->ncols)) || (rc = refuse_range("similar_block", "candidate", c_from, c_to, side->ncols)))
+        return rc;
     const int64_t nq = q_to - q_from, nc = c_to - c_from;
     if (nq > 0 && nc > 0 && (!mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "similar_block: NULL output");
     DevBuf<double> tab;
-    int rc = similar_prepare("similar_block", side, kind, tab);
-    if (rc) return rc;
+    if ((rc = similar_prepare("similar_block", side, kind, tab))) return rc;
     if (nq == 0 || nc == 0) return BPMF_HIP_OK;
     bpmf_hip_ctx *c = side->ctx;
-    const bpmf_ring *ring = side->ring.get();
+    const RingView v = ring_view(side->ring.get());
     const size_t cells = (size_t)nq * (size_t)nc;
     DevBuf<double> out;
     if (out.alloc(2 * cells))
         return fail(BPMF_HIP_ENOMEM, "similar_block: a block of " + std::to_string((long long)nq) + " x " + std::to_string((long long)nc) +
                     " means and deviations does not fit in device memory: ask for smaller ranges");
     bpmf_launch::SimilarBlockLaunch p{};
-    p.ring = ring->samples.get(); p.stride = (int64_t)ring->max * ring->kp; p.tab = tab.get();
-    p.Kp = ring->kp; p.S = ring->count; p.kind = kind;
+    p.ring = v.ring; p.stride = v.stride; p.tab = tab.get();
+    p.Kp = v.kp; p.S = v.count; p.kind = kind;
     p.ncols = side->ncols; p.q_from = q_from; p.nq = nq; p.c_from = c_from; p.nc = nc;
     p.mean = out.get(); p.std = out.get() + cells;
     if (bpmf_launch::ring_norms(p.ring, p.stride, p.Kp, p.S, side->ncols, tab.get(), c->stream.get()) || bpmf_launch::similar_block(p, c->stream.get()))
         return fail(BPMF_HIP_EINVAL, "similar_block: unsupported shape of the block");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "similar_block: kernel launch failed");
     if ((rc = bounded_stream_sync(c, c->stream.get(), "similar_block"))) return rc;
-    if (hipMemcpy(mean_out, out.get(), cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + cells, cells * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "similar_block: copying the results back failed");
-    return BPMF_HIP_OK;
+    return copy_back("similar_block", {{mean_out, out.get(), cells}, {std_out, out.get() + cells, cells}});
 }
 
 extern "C" int bpmf_hip_similar_last_ms(const bpmf_hip_side *side, float *ms)
 {
-    if (!side || !ms) return fail(BPMF_HIP_EINVAL, "similar_last_ms: NULL argument");
-    if (!side->ring || side->ring->sim_ms < 0.f)
-        return fail(BPMF_HIP_EINVAL, "similar_last_ms: no ranking of the side has been timed (bpmf_hip_similar)");
-    *ms = side->ring->sim_ms;
-    return BPMF_HIP_OK;
+    return last_ms("similar_last_ms", side, side && side->ring ? &side->ring->sim : nullptr, ms, "no ranking of the side has been timed (bpmf_hip_similar)");
 }

@@ -42,11 +42,10 @@ extern "C" int bpmf_hip_side_samples_add(bpmf_hip_side *s)
     bpmf_hip_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     { const int rc = settle_async(s); if (rc) return rc; }
-    bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, ring->kp, s->ncols, ring->samples.get(),
-                             (int64_t)ring->max * ring->kp, ring->count, c->stream.get());
+    const int64_t stride = ring_view(ring).stride;
+    bpmf_launch::samples_add(s->d_items, c->dtype == BPMF_HIP_F32, c->K, c->Kt, ring->kp, s->ncols, ring->samples.get(), stride, ring->count, c->stream.get());
     if (s->bias)                                                      // behind the factor rows: (b, 1) or (1, b), by the side's role
-        bpmf_launch::samples_add_bias(s->bias->b.get(), s->ncols, s->bias->role, c->Kt, ring->samples.get(), (int64_t)ring->max * ring->kp, ring->kp,
-                                      ring->count, c->stream.get());
+        bpmf_launch::samples_add_bias(s->bias->b.get(), s->ncols, s->bias->role, c->Kt, ring->samples.get(), stride, ring->kp, ring->count, c->stream.get());
     HIP_TRY(hipGetLastError());
     c->last_sampler_done = nullptr;
     ++ring->count;
@@ -97,64 +96,126 @@ void topn_splits(const bpmf_hip_ctx *c, int64_t nq, int64_t nc, int64_t *nsplit_
     *nsplit_out = nsplit; *cspan_out = cspan;
 }
 
-int topn_rings(bpmf_hip_ctx *c, const TopnRings &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc, const int64_t *ex_ptr,
-               const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out)
+static int ring_pair_check(const std::string &who, const bpmf_hip_side *q, const bpmf_hip_side *c)
+{
+    if (q->ring->kp != c->ring->kp)
+        return fail(BPMF_HIP_EINVAL, who + ": the two sample rings hold " + std::to_string(q->ring->kp) + " and " + std::to_string(c->ring->kp) +
+                                     " rows per sample (bias terms on one side only?)");
+    if ((bool)q->bias != (bool)c->bias) return fail(BPMF_HIP_EINVAL, who + ": both sides of a pair carry bias terms or neither does (bpmf_hip_side_set_bias)");
+    if (q->bias && q->bias->role == c->bias->role)
+        return fail(BPMF_HIP_EINVAL, who + ": the two sides have the same bias role " + std::to_string(q->bias->role) + " (bpmf_hip_side_set_bias: 0 and 1)");
+    return 0;
+}
+
+int pair_check_sides(const std::string &who, const bpmf_hip_side *query, const bpmf_hip_side *cand, bool single_gpu)
+{
+    if (!query || !cand) return fail(BPMF_HIP_EINVAL, who + ": NULL side");
+    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, who + ": the two sides belong to different contexts");
+    return single_gpu ? require_single_gpu(who.c_str(), query->ctx, query, cand) : 0;
+}
+
+// with bias rows (capi_bias.hip) both sides carry them, in opposite roles -- else the product is not mean + b + c + u . v
+int pair_open_rings(const std::string &who, bpmf_hip_side *query, bpmf_hip_side *cand, bpmf_launch::RingPair *out)
+{
+    HIP_TRY(hipSetDevice(query->ctx->device));
+    { const int rc = settle_async(query); if (rc) return rc; }        // every half-iteration in flight on both sides (as bpmf_hip_sys_state)
+    { const int rc = settle_async(cand); if (rc) return rc; }
+    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, who + ": no sample ring on both sides (bpmf_hip_side_samples_reserve)");
+    { const int rb = ring_pair_check(who, query, cand); if (rb) return rb; }
+    *out = ring_pair(query->ring.get(), cand->ring.get());
+    if (out->S < 1 || cand->ring->count != out->S)
+        return fail(BPMF_HIP_EINVAL, who + ": both sides must hold the same number (>= 1) of samples: " + std::to_string(out->S) + " and " +
+                    std::to_string(cand->ring->count));
+    return 0;
+}
+
+int refuse_topn_n(const char *who, int n)
+{
+    if (n >= 1 && n <= bpmf_launch::topn_max_n()) return 0;
+    return fail(BPMF_HIP_EINVAL, std::string(who) + ": n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
+}
+
+int refuse_range(const char *who, const char *what, int64_t from, int64_t to, int64_t ncols)
+{
+    if (from >= 0 && to >= from && to <= ncols) return 0;
+    return fail(BPMF_HIP_EINVAL, std::string(who) + ": " + what + " range out of bounds");
+}
+
+int copy_back(const std::string &who, std::initializer_list<CopyBack> list)
+{
+    for (const CopyBack &cb : list)
+        if (cb.dst && cb.bytes && hipMemcpy(cb.dst, cb.src, cb.bytes, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(BPMF_HIP_ENODEV, who + ": copying the results back failed");
+    return 0;
+}
+
+int last_ms(const char *who, const bpmf_hip_side *s, const Timed *t, float *ms, const char *none_msg)
+{
+    if (!s || !ms) return fail(BPMF_HIP_EINVAL, std::string(who) + ": NULL argument");
+    if (!t || t->ms < 0.f) return fail(BPMF_HIP_EINVAL, std::string(who) + ": " + none_msg);
+    *ms = t->ms;
+    return BPMF_HIP_OK;
+}
+
+int TopnLists::alloc(const char *who, int64_t nsplit_, int64_t nq, int n, bool scored_)
+{
+    pn = (size_t)nq * (size_t)n; nsplit = (size_t)nsplit_; scored = scored_;
+    if (part.alloc((scored ? 3 : 1) * nsplit * pn) || pidx.alloc(nsplit * pn) || out.alloc((scored ? 3 : 2) * pn) || oidx.alloc(pn))
+        return fail(BPMF_HIP_ENOMEM, std::string(who) + ": device allocation of the result lists failed");
+    return 0;
+}
+
+int TopnLists::read_back(const char *who, int32_t *idx, double *score, double *mean, double *std) const
+{
+    return copy_back(who, {{score, out_score(), pn}, {mean, out_mean(), pn}, {std, out_std(), pn}, {idx, out_idx(), pn}});
+}
+
+int topn_rings(bpmf_hip_ctx *c, const bpmf_launch::RingPair &r, double mean_rating, int n, int64_t q_from, int64_t nq, int64_t nc,
+               const int64_t *ex_ptr, const int32_t *ex_rows, int32_t *idx_out, double *mean_out, double *std_out)
 {
     int64_t nsplit, cspan;
     topn_splits(c, nq, nc, &nsplit, &cspan);
-
-    const size_t pn = (size_t)nq * (size_t)n;
-    DevBuf<double> part_mean, out;
-    DevBuf<int32_t> part_idx, out_idx;
-    if (part_mean.alloc((size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(2 * pn) || out_idx.alloc(pn))
-        return fail(BPMF_HIP_ENOMEM, "topn: device allocation of the result lists failed");
+    TopnLists l;
+    { const int rc = l.alloc("topn", nsplit, nq, n, false); if (rc) return rc; }
     bpmf_launch::TopnLaunch p{};
-    p.qring = r.qring; p.cring = r.cring;
-    p.qstride = r.qstride; p.cstride = r.cstride;
-    p.Kp = r.kp; p.S = r.S; p.n = n; p.mean_rating = mean_rating;
+    p.r = r; p.n = n; p.mean_rating = mean_rating;
     p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
     p.ex_ptr = ex_ptr; p.ex_rows = ex_rows;
-    p.part_mean = part_mean.get(); p.part_idx = part_idx.get();
-    p.out_mean = out.get(); p.out_std = out.get() + pn; p.out_idx = out_idx.get();
+    p.part_mean = l.part_mean(); p.part_idx = l.part_idx();
+    p.out_mean = l.out_mean(); p.out_std = l.out_std(); p.out_idx = l.out_idx();
     bpmf_launch::topn(p, c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn: kernel launch failed");
     { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
-    if (hipMemcpy(mean_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "topn: copying the results back failed");
-    return BPMF_HIP_OK;
+    return l.read_back("topn", idx_out, nullptr, mean_out, std_out);
 }
 
 }  // namespace bpmf_capi
 
+// what bpmf_hip_topn, bpmf_hip_topn_scored and bpmf_hip_rank_eval do between their own argument checks and their launches: the rings,
+// then exclude_rated against the shapes of the sides (a shard is served: only exclude_rated is refused on one, by sorted_rows)
+static int ranking_open(const char *who, bpmf_hip_side *query, bpmf_hip_side *cand, int exclude_rated, bpmf_launch::RingPair *r)
+{
+    { const int rc = pair_open_rings(who, query, cand, r); if (rc) return rc; }
+    if (exclude_rated && query->nrows != cand->ncols)
+        return fail(BPMF_HIP_EINVAL, std::string(who) + ": exclude_rated needs the query side's rows to be the candidate side's columns");
+    return 0;
+}
+
 extern "C" int bpmf_hip_topn(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int n, int64_t q_from, int64_t q_to,
                              int exclude_rated, int32_t *idx_out, double *mean_out, double *std_out)
 {
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "topn: NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "topn: the two sides belong to different contexts");
-    if (n < 1 || n > bpmf_launch::topn_max_n())
-        return fail(BPMF_HIP_EINVAL, "topn: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
-    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "topn: query range out of bounds");
+    int rc;
+    if ((rc = pair_check_sides("topn", query, cand, false)) || (rc = refuse_topn_n("topn", n)) ||
+        (rc = refuse_range("topn", "query", q_from, q_to, query->ncols)))
+        return rc;
     const int64_t nq = q_to - q_from;
     if (nq > 0 && (!idx_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "topn: NULL output");
-    bpmf_hip_ctx *c = query->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(query); if (rc) return rc; }        // every half-iteration in flight on both sides (as bpmf_hip_sys_state)
-    { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check("topn", query, cand); if (rb) return rb; }
-    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
-    const int S = qr->count;
-    if (S < 1 || cr->count != S)
-        return fail(BPMF_HIP_EINVAL, "topn: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cr->count));
-    if (exclude_rated && query->nrows != cand->ncols)
-        return fail(BPMF_HIP_EINVAL, "topn: exclude_rated needs the query side's rows to be the candidate side's columns");
+    bpmf_launch::RingPair r;
+    if ((rc = ranking_open("topn", query, cand, exclude_rated, &r))) return rc;
     if (nq == 0) return BPMF_HIP_OK;
-    if (exclude_rated) { const int rc = build_exclusion(query); if (rc) return rc; }
-    const TopnRings r{qr->samples.get(), cr->samples.get(), (int64_t)qr->max * qr->kp, (int64_t)cr->max * cr->kp, qr->kp, S};
-    return topn_rings(c, r, mean_rating, n, q_from, nq, cand->ncols, exclude_rated ? qr->ex_ptr.get() : nullptr,
+    if (exclude_rated && (rc = build_exclusion(query))) return rc;
+    const bpmf_ring *qr = query->ring.get();
+    return topn_rings(query->ctx, r, mean_rating, n, q_from, nq, cand->ncols, exclude_rated ? qr->ex_ptr.get() : nullptr,
                       exclude_rated ? qr->ex_rows.get() : nullptr, idx_out, mean_out, std_out);
 }
 
@@ -162,64 +223,41 @@ extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, d
                                     int exclude_rated, int kind, double param, double sigma, int32_t *idx_out, double *score_out,
                                     double *mean_out, double *std_out)
 {
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "topn_scored: NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "topn_scored: the two sides belong to different contexts");
+    int rc;
+    if ((rc = pair_check_sides("topn_scored", query, cand, false))) return rc;
     if (kind != BPMF_HIP_SCORE_UCB && kind != BPMF_HIP_SCORE_PROB && kind != BPMF_HIP_SCORE_EI)
         return fail(BPMF_HIP_EINVAL, "topn_scored: unknown score kind " + std::to_string(kind) + " (BPMF_HIP_SCORE_UCB, _PROB or _EI)");
     if (!std::isfinite(param))
         return fail(BPMF_HIP_EINVAL, std::string("topn_scored: ") + (kind == BPMF_HIP_SCORE_UCB ? "kappa" : "the threshold") + " is not finite");
     if (kind != BPMF_HIP_SCORE_UCB && !(std::isfinite(sigma) && sigma >= 0.0))
         return fail(BPMF_HIP_EINVAL, "topn_scored: sigma must be finite and >= 0");
-    if (n < 1 || n > bpmf_launch::topn_max_n())
-        return fail(BPMF_HIP_EINVAL, "topn_scored: n = " + std::to_string(n) + " (1 .. " + std::to_string(bpmf_launch::topn_max_n()) + ")");
-    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "topn_scored: query range out of bounds");
+    if ((rc = refuse_topn_n("topn_scored", n)) || (rc = refuse_range("topn_scored", "query", q_from, q_to, query->ncols))) return rc;
     const int64_t nq = q_to - q_from;
     if (nq > 0 && (!idx_out || !score_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "topn_scored: NULL output");
-    bpmf_hip_ctx *c = query->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(query); if (rc) return rc; }
-    { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "topn_scored: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check("topn_scored", query, cand); if (rb) return rb; }
-    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
-    const int S = qr->count;
-    if (S < 1 || cr->count != S)
-        return fail(BPMF_HIP_EINVAL, "topn_scored: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cr->count));
-    if (exclude_rated && query->nrows != cand->ncols)
-        return fail(BPMF_HIP_EINVAL, "topn_scored: exclude_rated needs the query side's rows to be the candidate side's columns");
+    bpmf_launch::TopnScoredLaunch p{};
+    if ((rc = ranking_open("topn_scored", query, cand, exclude_rated, &p.r))) return rc;
     if (nq == 0) return BPMF_HIP_OK;
-    if (exclude_rated) { const int rc = build_exclusion(query); if (rc) return rc; }
+    if (exclude_rated && (rc = build_exclusion(query))) return rc;
 
+    bpmf_hip_ctx *c = query->ctx;
+    const bpmf_ring *qr = query->ring.get();
     const int64_t nc = cand->ncols;
     int64_t nsplit, cspan;
     topn_splits(c, nq, nc, &nsplit, &cspan);
-    const size_t pn = (size_t)nq * (size_t)n;
-    DevBuf<double> part, out;                                             // score | mean | std of the splits / of the result
-    DevBuf<int32_t> part_idx, out_idx;
-    if (part.alloc(3 * (size_t)nsplit * pn) || part_idx.alloc((size_t)nsplit * pn) || out.alloc(3 * pn) || out_idx.alloc(pn))
-        return fail(BPMF_HIP_ENOMEM, "topn_scored: device allocation of the result lists failed");
-    bpmf_launch::TopnScoredLaunch p{};
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.n = n; p.mean_rating = mean_rating;
+    TopnLists l;
+    if ((rc = l.alloc("topn_scored", nsplit, nq, n, true))) return rc;
+    p.n = n; p.mean_rating = mean_rating;
     p.kind = kind; p.param = param; p.sigma = kind == BPMF_HIP_SCORE_UCB ? 0.0 : sigma;
     p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
     p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
-    p.part_score = part.get(); p.part_mean = part.get() + (size_t)nsplit * pn; p.part_std = part.get() + 2 * (size_t)nsplit * pn;
-    p.part_idx = part_idx.get();
-    p.out_score = out.get(); p.out_mean = out.get() + pn; p.out_std = out.get() + 2 * pn; p.out_idx = out_idx.get();
+    p.part_score = l.part_score(); p.part_mean = l.part_mean(); p.part_std = l.part_std(); p.part_idx = l.part_idx();
+    p.out_score = l.out_score(); p.out_mean = l.out_mean(); p.out_std = l.out_std(); p.out_idx = l.out_idx();
     const int lrc = bpmf_launch::topn_scored(p, c->stream.get());
     if (lrc == -2) return fail(BPMF_HIP_ENODEV, "topn_scored: the device refused the LDS of lists of " + std::to_string(n));
     if (lrc) return fail(BPMF_HIP_EINVAL, "topn_scored: unsupported shape");
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "topn_scored: kernel launch failed");
-    { const int rc = bounded_stream_sync(c, c->stream.get(), __func__); if (rc) return rc; }
-    if (hipMemcpy(score_out, out.get(), pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(mean_out, out.get() + pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(std_out, out.get() + 2 * pn, pn * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(idx_out, out_idx.get(), pn * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "topn_scored: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;
+    return l.read_back("topn_scored", idx_out, score_out, mean_out, std_out);
 }
 
 // rank of every held-out (query, candidate) among the candidates the query has not rated, by bpmf_hip_topn's score and order
@@ -227,10 +265,10 @@ extern "C" int bpmf_hip_topn_scored(bpmf_hip_side *query, bpmf_hip_side *cand, d
 extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t q_from, int64_t q_to,
                                   int exclude_rated, const int64_t *tptr, const int32_t *tcand, int32_t *rank_out, int32_t *ncand_out)
 {
-    if (!query || !cand) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL side");
-    if (query->ctx != cand->ctx) return fail(BPMF_HIP_EINVAL, "rank_eval: the two sides belong to different contexts");
+    int rc;
+    if ((rc = pair_check_sides("rank_eval", query, cand, false))) return rc;
     if (!std::isfinite(mean_rating)) return fail(BPMF_HIP_EINVAL, "rank_eval: mean_rating is not finite");
-    if (q_from < 0 || q_to < q_from || q_to > query->ncols) return fail(BPMF_HIP_EINVAL, "rank_eval: query range out of bounds");
+    if ((rc = refuse_range("rank_eval", "query", q_from, q_to, query->ncols))) return rc;
     const int64_t nq = q_to - q_from, nc = cand->ncols;
     if (!tptr) return fail(BPMF_HIP_EINVAL, "rank_eval: NULL held-out pointer array");
     if (tptr[0] != 0) return fail(BPMF_HIP_EINVAL, "rank_eval: tptr[0] must be 0");
@@ -249,24 +287,15 @@ extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, dou
                 return fail(BPMF_HIP_EINVAL, "rank_eval: the held-out candidates of query " + std::to_string((long long)(q_from + q)) +
                             " are not ascending and distinct (" + std::to_string(tcand[p - 1]) + ", " + std::to_string(tcand[p]) + ")");
         }
-    bpmf_hip_ctx *c = query->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    { const int rc = settle_async(query); if (rc) return rc; }
-    { const int rc = settle_async(cand); if (rc) return rc; }
-    if (!query->ring || !cand->ring) return fail(BPMF_HIP_EINVAL, "rank_eval: no sample ring on both sides (bpmf_hip_side_samples_reserve)");
-    { const int rb = ring_pair_check("rank_eval", query, cand); if (rb) return rb; }
-    const bpmf_ring *qr = query->ring.get(), *cr = cand->ring.get();
-    const int S = qr->count;
-    if (S < 1 || cr->count != S)
-        return fail(BPMF_HIP_EINVAL, "rank_eval: both sides must hold the same number (>= 1) of samples: " + std::to_string(S) + " and " +
-                    std::to_string(cr->count));
-    if (exclude_rated && query->nrows != cand->ncols)
-        return fail(BPMF_HIP_EINVAL, "rank_eval: exclude_rated needs the query side's rows to be the candidate side's columns");
+    bpmf_launch::RankLaunch p{};
+    if ((rc = ranking_open("rank_eval", query, cand, exclude_rated, &p.r))) return rc;
     if (nq == 0) return BPMF_HIP_OK;
+    bpmf_hip_ctx *c = query->ctx;
+    const bpmf_ring *qr = query->ring.get();
     if (exclude_rated) {
         // a held-out entry that is a rated cell would be scored -inf: refused while the lists are on the host
         std::vector<int32_t> rows;
-        { const int rc = build_exclusion(query, &rows); if (rc) return rc; }
+        if ((rc = build_exclusion(query, &rows))) return rc;
         const std::vector<int64_t> &cp = query->h_colptr;
         for (int64_t q = 0; q < nq; ++q) {
             const auto b = rows.begin() + cp[(size_t)(q_from + q)], e = rows.begin() + cp[(size_t)(q_from + q) + 1];
@@ -282,24 +311,17 @@ extern "C" int bpmf_hip_rank_eval(bpmf_hip_side *query, bpmf_hip_side *cand, dou
     DevBuf<int32_t> d_tcand, part_cnt, part_ncand, d_rank, d_ncand;
     DevBuf<double> tscore;
     const size_t ntz = (size_t)std::max<int64_t>(nt, 1);
-    int rc;
     if ((rc = d_tptr.upload(tptr, (size_t)nq + 1)) || (rc = d_tcand.upload(nt > 0 ? tcand : nullptr, (size_t)nt)) || (rc = tscore.alloc(ntz)) ||
         (rc = part_cnt.alloc((size_t)nsplit * ntz)) || (rc = part_ncand.alloc((size_t)nsplit * (size_t)nq)) || (rc = d_rank.alloc(ntz)) ||
         (rc = d_ncand.alloc((size_t)nq)))
         return rc;
-    bpmf_launch::RankLaunch p{};
-    p.qring = qr->samples.get(); p.cring = cr->samples.get();
-    p.qstride = (int64_t)qr->max * qr->kp; p.cstride = (int64_t)cr->max * cr->kp;
-    p.Kp = qr->kp; p.S = S; p.mean_rating = mean_rating;
+    p.mean_rating = mean_rating;
     p.q_from = q_from; p.nq = nq; p.nc = nc; p.cspan = cspan; p.nsplit = (int)nsplit;
     p.ex_ptr = exclude_rated ? qr->ex_ptr.get() : nullptr; p.ex_rows = exclude_rated ? qr->ex_rows.get() : nullptr;
     p.tptr = d_tptr.get(); p.tcand = d_tcand.get(); p.nt = nt; p.tscore = tscore.get();
     p.part_cnt = part_cnt.get(); p.part_ncand = part_ncand.get(); p.rank = d_rank.get(); p.ncand = d_ncand.get();
     bpmf_launch::rank_eval(p, c->stream.get());
     if (hipGetLastError() != hipSuccess) return fail(BPMF_HIP_ENODEV, "rank_eval: kernel launch failed");
-    { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
-    if ((nt > 0 && hipMemcpy(rank_out, d_rank.get(), (size_t)nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) ||
-        hipMemcpy(ncand_out, d_ncand.get(), (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(BPMF_HIP_ENODEV, "rank_eval: copying the results back failed");
-    return BPMF_HIP_OK;
+    if ((rc = bounded_stream_sync(c, c->stream.get(), __func__))) return rc;
+    return copy_back("rank_eval", {{rank_out, d_rank.get(), (size_t)nt}, {ncand_out, d_ncand.get(), (size_t)nq}});
 }

@@ -120,6 +120,25 @@ public:
     }
 };
 
+// The device time of a span of a stream between two events, created on first use.  begin / end record around the launches; resolve,
+// after the host has waited for the stream, reads the time.  ms < 0: nothing has been timed, or the time could not be read.
+struct Timed {
+    Event ev[2];
+    float ms = -1.f;
+    int begin(hipStream_t st)
+    {
+        for (Event &e : ev) if (!e) { const int rc = e.create(); if (rc) return rc; }
+        ms = -1.f;
+        HIP_TRY(hipEventRecord(ev[0].get(), st));
+        return 0;
+    }
+    int end(hipStream_t st) { HIP_TRY(hipEventRecord(ev[1].get(), st)); return 0; }
+    void resolve()
+    {
+        if (hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()) != hipSuccess) { (void)hipGetLastError(); ms = -1.f; }
+    }
+};
+
 // a stream of the library's own, or the caller's (borrow: never destroyed here)
 class Stream {
     hipStream_t s_ = nullptr;

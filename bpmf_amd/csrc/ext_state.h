@@ -133,10 +133,10 @@ struct bpmf_link {
 // sorted rated-candidate lists of every column (built on the first bpmf_hip_topn that excludes them)
 struct bpmf_ring {
     DevBuf<double> samples; int max = 0, count = 0, kp = 0; DevBuf<int64_t> ex_ptr; DevBuf<int32_t> ex_rows;
-    Event timed[2]; float cells_ms = -1.f;   // around the newest launch of k_predict_cells with the side as the queries (bpmf_hip_predict_cells_last_ms)
-    Event sim_timed[2]; float sim_ms = -1.f; // around the newest bpmf_hip_similar of the side (bpmf_hip_similar_last_ms)
-    Event diag_timed[2]; float diag_ms = -1.f;   // around the kernels of the newest bpmf_hip_diag_cells with the side as the queries (bpmf_hip_diag_last_ms)
-    Event score_timed[2]; float score_ms = -1.f; // around the kernels of the newest bpmf_hip_score_cells with the side as the queries (bpmf_hip_score_last_ms)
+    Timed cells;                             // around the newest launch of k_predict_cells with the side as the queries (bpmf_hip_predict_cells_last_ms)
+    Timed sim;                               // around the newest bpmf_hip_similar of the side (bpmf_hip_similar_last_ms)
+    Timed diag;                              // around the kernels of the newest bpmf_hip_diag_cells with the side as the queries (bpmf_hip_diag_last_ms)
+    Timed score;                             // around the kernels of the newest bpmf_hip_score_cells with the side as the queries (bpmf_hip_score_last_ms)
 };
 
 // rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as
@@ -161,7 +161,7 @@ struct bpmf_foldin {
     int64_t n = 0; int S = 0, kp = 0;
     DevBuf<int64_t> rowptr; DevBuf<int32_t> colidx; DevBuf<double> ring;
     Pinned<unsigned long long> fail;
-    Event timed[2]; float last_ms = -1.f;   // around the newest launch of k_foldin (bpmf_hip_foldin_last_ms)
+    Timed timed;                            // around the newest launch of k_foldin (bpmf_hip_foldin_last_ms)
 };
 
 // adaptive noise (capi_noise.hip): the block partials | sum of bpmf_hip_train_sse

@@ -10,19 +10,17 @@ int cell_traces_segment(int Kp) { return bpmf::ct_segment(Kp); }
 
 int cell_traces(const PredCellsLaunch &p, double *trace, int64_t tbase, hipStream_t st)
 {
-    if (p.Kp < 4 || p.Kp > 128 || p.Kp % 4 != 0 || p.S < 1 || p.nseg < 0 || p.nseg > 0x7fffffff || p.qstride < (int64_t)p.S * p.Kp ||
-        p.cstride < (int64_t)p.S * p.Kp || !trace)
-        return -1;
+    if (!ring_pair_ok(p.r) || p.nseg < 0 || p.nseg > 0x7fffffff || !trace) return -1;
     if (p.nseg == 0) return 0;
     bpmf::CellTracesArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride; a.Kp = p.Kp; a.S = p.S;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride; a.Kp = p.r.Kp; a.S = p.r.S;
     a.mean_rating = p.mean_rating;
     a.seg_q = p.seg_q; a.seg_beg = p.seg_beg; a.seg_cnt = p.seg_cnt; a.cand = p.cand; a.orig = p.orig;
     a.mean = p.mean; a.std = p.std;
     a.trace = trace; a.tbase = tbase;
     const dim3 grid((unsigned)p.nseg), block(256);
 #define BPMF_CT_LAUNCH(G_) case G_: hipLaunchKernelGGL((bpmf::k_cell_traces<G_>), grid, block, 0, st, a); break;
-    switch (bpmf::ct_group(p.Kp)) {
+    switch (bpmf::ct_group(p.r.Kp)) {
     BPMF_CT_LAUNCH(2) BPMF_CT_LAUNCH(4) BPMF_CT_LAUNCH(8) BPMF_CT_LAUNCH(16) BPMF_CT_LAUNCH(32) BPMF_CT_LAUNCH(64)
     default: return -1;
     }

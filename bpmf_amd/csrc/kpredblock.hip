@@ -6,14 +6,12 @@ namespace bpmf_launch {
 
 int predict_block(const PredBlockLaunch &p, hipStream_t st)
 {
-    if (p.Kp < 4 || p.Kp > 128 || p.Kp % 4 != 0 || p.S < 1 || p.nq < 0 || p.nc < 0 || p.qstride < (int64_t)p.S * p.Kp ||
-        p.cstride < (int64_t)p.S * p.Kp)
-        return -1;
+    if (!ring_pair_ok(p.r) || p.nq < 0 || p.nc < 0) return -1;
     if (p.nq == 0 || p.nc == 0) return 0;
     const int64_t gx = (p.nq + bpmf::kPredTile - 1) / bpmf::kPredTile, gy = (p.nc + bpmf::kPredTile - 1) / bpmf::kPredTile;
     if (gx > 0x7fffffff || gy > 65535) return -1;
     bpmf::PredBlockArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride; a.Kp = p.Kp; a.S = p.S;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride; a.Kp = p.r.Kp; a.S = p.r.S;
     a.mean_rating = p.mean_rating; a.q_from = p.q_from; a.nq = p.nq; a.c_from = p.c_from; a.nc = p.nc; a.w = p.w;
     a.mean = p.mean; a.std = p.std;
     hipLaunchKernelGGL(bpmf::k_predict_block, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, a);

@@ -8,12 +8,10 @@ int predict_cells_segment(int Kp) { return bpmf::pc_segment(Kp); }
 
 int predict_cells(const PredCellsLaunch &p, hipStream_t st)
 {
-    if (p.Kp < 4 || p.Kp > 128 || p.Kp % 4 != 0 || p.S < 1 || p.nseg < 0 || p.nseg > 0x7fffffff || p.qstride < (int64_t)p.S * p.Kp ||
-        p.cstride < (int64_t)p.S * p.Kp)
-        return -1;
+    if (!ring_pair_ok(p.r) || p.nseg < 0 || p.nseg > 0x7fffffff) return -1;
     if (p.nseg == 0) return 0;
     bpmf::PredCellsArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride; a.Kp = p.Kp; a.S = p.S;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride; a.Kp = p.r.Kp; a.S = p.r.S;
     a.mean_rating = p.mean_rating; a.t = p.t; a.sigma = p.sigma;
     a.seg_q = p.seg_q; a.seg_beg = p.seg_beg; a.seg_cnt = p.seg_cnt; a.cand = p.cand; a.orig = p.orig;
     a.mean = p.mean; a.std = p.std; a.prob = p.prob;
@@ -23,7 +21,7 @@ int predict_cells(const PredCellsLaunch &p, hipStream_t st)
         if (p.want_prob) hipLaunchKernelGGL((bpmf::k_predict_cells<G_, true>), grid, block, 0, st, a);                  \
         else hipLaunchKernelGGL((bpmf::k_predict_cells<G_, false>), grid, block, 0, st, a);                             \
         break;
-    switch (bpmf::pc_group(p.Kp)) {
+    switch (bpmf::pc_group(p.r.Kp)) {
     BPMF_PC_LAUNCH(2) BPMF_PC_LAUNCH(4) BPMF_PC_LAUNCH(8) BPMF_PC_LAUNCH(16) BPMF_PC_LAUNCH(32) BPMF_PC_LAUNCH(64)
     default: return -1;
     }

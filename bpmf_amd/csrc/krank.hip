@@ -7,8 +7,8 @@ namespace bpmf_launch {
 void rank_eval(const RankLaunch &p, hipStream_t st)
 {
     bpmf::RankArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride;
-    a.L = p.S * p.Kp; a.S = p.S; a.mean_rating = p.mean_rating;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride;
+    a.L = p.r.S * p.r.Kp; a.S = p.r.S; a.mean_rating = p.mean_rating;
     a.q_from = p.q_from; a.nq = p.nq; a.nc = p.nc; a.cspan = p.cspan;
     a.ex_ptr = p.ex_ptr; a.ex_rows = p.ex_rows; a.tptr = p.tptr; a.tcand = p.tcand; a.nt = p.nt;
     a.tscore = p.tscore; a.part_cnt = p.part_cnt; a.part_ncand = p.part_ncand;

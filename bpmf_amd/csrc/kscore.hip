@@ -10,9 +10,7 @@ int score_cells_segment(int Kp) { return bpmf::sc_segment(Kp); }
 int score_cells(const ScoreCellsLaunch &s, hipStream_t st)
 {
     const PredCellsLaunch &p = s.cells;
-    if (p.Kp < 4 || p.Kp > 128 || p.Kp % 4 != 0 || p.S < 1 || p.nseg < 0 || p.nseg > 0x7fffffff || p.qstride < (int64_t)p.S * p.Kp ||
-        p.cstride < (int64_t)p.S * p.Kp || !s.y || !s.c0 || !s.lpd || !s.pw)
-        return -1;
+    if (!ring_pair_ok(p.r) || p.nseg < 0 || p.nseg > 0x7fffffff || !s.y || !s.c0 || !s.lpd || !s.pw) return -1;
     int kind;
     switch (s.kind) {
     case BPMF_HIP_LOGDENS_GAUSSIAN: kind = s.flag ? bpmf::kScoreGaussFlags : bpmf::kScoreGauss; if (!s.as || (s.flag && !s.sa)) return -1; break;
@@ -22,7 +20,7 @@ int score_cells(const ScoreCellsLaunch &s, hipStream_t st)
     }
     if (p.nseg == 0) return 0;
     bpmf::ScoreCellsArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride; a.Kp = p.Kp; a.S = p.S;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride; a.Kp = p.r.Kp; a.S = p.r.S;
     a.mean_rating = p.mean_rating;
     a.seg_q = p.seg_q; a.seg_beg = p.seg_beg; a.seg_cnt = p.seg_cnt; a.cand = p.cand; a.orig = p.orig;
     a.y = s.y; a.w = s.w; a.flag = s.flag; a.c0 = s.c0; a.as = s.as; a.sa = s.sa; a.hnu1 = 0.5 * (s.nu + 1.0);
@@ -36,7 +34,7 @@ int score_cells(const ScoreCellsLaunch &s, hipStream_t st)
         BPMF_SC_KIND(G_, bpmf::kScoreProbit)                                                                                        \
         }                                                                                                                           \
         break;
-    switch (bpmf::sc_group(p.Kp)) {
+    switch (bpmf::sc_group(p.r.Kp)) {
     BPMF_SC_LAUNCH(2) BPMF_SC_LAUNCH(4) BPMF_SC_LAUNCH(8) BPMF_SC_LAUNCH(16) BPMF_SC_LAUNCH(32) BPMF_SC_LAUNCH(64)
     default: return -1;
     }

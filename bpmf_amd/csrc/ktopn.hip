@@ -18,8 +18,8 @@ int topn_max_n() { return bpmf::kTopnMaxN; }
 void topn(const TopnLaunch &p, hipStream_t st)
 {
     bpmf::TopnArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride;
-    a.L = p.S * p.Kp; a.S = p.S; a.n = p.n; a.mean_rating = p.mean_rating;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride;
+    a.L = p.r.S * p.r.Kp; a.S = p.r.S; a.n = p.n; a.mean_rating = p.mean_rating;
     a.q_from = p.q_from; a.nq = p.nq; a.nc = p.nc; a.cspan = p.cspan;
     a.ex_ptr = p.ex_ptr; a.ex_rows = p.ex_rows; a.part_mean = p.part_mean; a.part_idx = p.part_idx;
     const size_t lds = sizeof(double) * ((size_t)bpmf::kTopnQ * bpmf::kTopnScLd + (size_t)bpmf::kTopnQ * p.n + bpmf::kTopnQ) +
@@ -29,8 +29,8 @@ void topn(const TopnLaunch &p, hipStream_t st)
     hipLaunchKernelGGL(bpmf::k_topn_merge, dim3((unsigned)((p.nq + 255) / 256)), dim3(256), 0, st,
                        p.part_mean, p.part_idx, p.nsplit, p.nq, p.n, p.out_mean, p.out_idx);
     const int64_t npairs = p.nq * p.n;
-    hipLaunchKernelGGL(bpmf::k_topn_std, dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, st, p.qring, p.cring, p.qstride, p.cstride,
-                       p.Kp, p.S, p.mean_rating, p.q_from, npairs, p.n, p.out_mean, p.out_idx, p.out_std);
+    hipLaunchKernelGGL(bpmf::k_topn_std, dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, st, p.r.qring, p.r.cring, p.r.qstride, p.r.cstride,
+                       p.r.Kp, p.r.S, p.mean_rating, p.q_from, npairs, p.n, p.out_mean, p.out_idx, p.out_std);
 }
 
 }  // namespace bpmf_launch

@@ -26,12 +26,12 @@ int launch_scored(const bpmf::TopnScoredArgs &a, dim3 grid, size_t lds, hipStrea
 
 int topn_scored(const TopnScoredLaunch &p, hipStream_t st)
 {
-    if (p.Kp < 4 || p.Kp > 128 || p.Kp % 4 != 0 || p.S < 1 || p.n < 1 || p.n > bpmf::kTsMaxN || p.nq < 1 || p.nc < 1 || p.cspan < 1 ||
-        p.cspan % bpmf::kTsC != 0 || p.nsplit < 1 || p.nsplit > 65535 || p.qstride < (int64_t)p.S * p.Kp || p.cstride < (int64_t)p.S * p.Kp)
+    if (!ring_pair_ok(p.r) || p.n < 1 || p.n > bpmf::kTsMaxN || p.nq < 1 || p.nc < 1 || p.cspan < 1 || p.cspan % bpmf::kTsC != 0 || p.nsplit < 1 ||
+        p.nsplit > 65535)
         return -1;
     bpmf::TopnScoredArgs a;
-    a.qring = p.qring; a.cring = p.cring; a.qstride = p.qstride; a.cstride = p.cstride;
-    a.Kp = p.Kp; a.S = p.S; a.n = p.n; a.mean_rating = p.mean_rating; a.param = p.param; a.sigma = p.sigma;
+    a.qring = p.r.qring; a.cring = p.r.cring; a.qstride = p.r.qstride; a.cstride = p.r.cstride;
+    a.Kp = p.r.Kp; a.S = p.r.S; a.n = p.n; a.mean_rating = p.mean_rating; a.param = p.param; a.sigma = p.sigma;
     a.q_from = p.q_from; a.nq = p.nq; a.nc = p.nc; a.cspan = p.cspan;
     a.ex_ptr = p.ex_ptr; a.ex_rows = p.ex_rows;
     a.part_score = p.part_score; a.part_mean = p.part_mean; a.part_std = p.part_std; a.part_idx = p.part_idx;

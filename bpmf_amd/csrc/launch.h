@@ -1,6 +1,7 @@
 // launch.h -- what the C ABI (capi_*.hip) needs from the translation units that hold the kernels.  The templates
 // are defined in launch_impl.h and explicitly instantiated one K per file (k8.hip ... k128.hip), so
-// that the five instantiations of the sampler compile side by side (make -j).
+// that the five instantiations of the sampler compile side by side (make -j).  The launch structs of the kernels that read two sample
+// rings lead with one RingPair; those of the add-ons share FactorPair / SideCsc.
 #pragma once
 #include "state.h"
 
@@ -130,12 +131,21 @@ void randn_probe(uint32_t counter, int n, double *out_dev, hipStream_t st);
 void aggr_add(const void *items, bool f32, int ld, int K, int64_t c0, int64_t ncols, double *mu, double *lambda, hipStream_t st);   // ld: device leading dimension, K: the caller's num_latent
 void aggr_finalize(int K, int nsamples, int64_t ncols, double *mu, double *lambda, hipStream_t st);
 
+// Two sample rings that meet in one dot product, as a kernel reads them: S samples of Kp rows per column, a column of the queries'
+// ring every qstride doubles, of the candidates' every cstride.  Every launch struct of a ring query below leads with one (filled by
+// ring_pair, capi_internal.h); its launcher tests the shape with ring_pair_ok and copies the members into its kernel's arguments.
+struct RingPair { const double *qring, *cring; int64_t qstride, cstride; int Kp, S; };
+inline bool ring_pair_ok(const RingPair &r)
+{
+    return r.Kp >= 4 && r.Kp <= 128 && r.Kp % 4 == 0 && r.S >= 1 && r.qstride >= (int64_t)r.S * r.Kp && r.cstride >= (int64_t)r.S * r.Kp;
+}
+
 // posterior top-N (kernels_topn.h, ktopn.hip)
 void samples_add(const void *items, bool f32, int ld, int Kt, int Kp, int64_t ncols, double *ring, int64_t stride, int slot, hipStream_t st);
 int topn_max_n();
 struct TopnLaunch {
-    const double *qring, *cring; int64_t qstride, cstride;
-    int Kp, S, n; double mean_rating;
+    RingPair r;
+    int n; double mean_rating;
     int64_t q_from, nq, nc, cspan; int nsplit;
     const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
     double *part_mean; int32_t *part_idx;                  // nsplit x nq x n
@@ -145,8 +155,8 @@ void topn(const TopnLaunch &p, hipStream_t st);             // score + select, m
 
 // ranks of held-out candidates among the candidates a query has not rated (kernels_rank.h, krank.hip)
 struct RankLaunch {
-    const double *qring, *cring; int64_t qstride, cstride;
-    int Kp, S; double mean_rating;
+    RingPair r;
+    double mean_rating;
     int64_t q_from, nq, nc, cspan; int nsplit;
     const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
     const int64_t *tptr; const int32_t *tcand; int64_t nt; // held-out entries of query q: tcand[tptr[q] .. tptr[q + 1]), ascending; nt = tptr[nq]
@@ -158,8 +168,8 @@ void rank_eval(const RankLaunch &p, hipStream_t st);        // the scores of the
 
 // posterior top-N by an acquisition score (kernels_topn_score.h, ktopnscore.hip)
 struct TopnScoredLaunch {
-    const double *qring, *cring; int64_t qstride, cstride;
-    int Kp, S, n; double mean_rating;
+    RingPair r;
+    int n; double mean_rating;
     int kind; double param, sigma;                         // BPMF_HIP_SCORE_*; kappa or the threshold; sigma = 0: the noise-free forms
     int64_t q_from, nq, nc, cspan; int nsplit;
     const int64_t *ex_ptr; const int32_t *ex_rows;         // NULL: no exclusion
@@ -189,8 +199,8 @@ int similar_block(const SimilarBlockLaunch &p, hipStream_t st);
 
 // dense blocks of predictions from two sample rings; rows unseen in training (kernels_predblock.h, kpredblock.hip)
 struct PredBlockLaunch {
-    const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column
-    int Kp, S; double mean_rating;
+    RingPair r;
+    double mean_rating;
     int64_t q_from, nq, c_from, nc;                        // queries [q_from, q_from + nq), candidates [c_from, c_from + nc)
     const double *w;                                       // added to the variance as w[candidate id] / S, or NULL
     double *mean, *std;                                    // nq x nc, row-major
@@ -214,8 +224,8 @@ int foldin(const FoldinLaunch &p, hipStream_t st);         // -1: shape not supp
 
 // predictions for a list of cells from two sample rings; the repacking of a ring for its read-back and load (kernels_predcells.h, kpredcells.hip)
 struct PredCellsLaunch {
-    const double *qring, *cring; int64_t qstride, cstride; // rings of the queries / candidates, doubles per column
-    int Kp, S; double mean_rating;
+    RingPair r;
+    double mean_rating;
     int want_prob; double t, sigma;                        // prob = (1/S) sum Phi((p_s - t) / sigma); sigma < DBL_MIN: the counting form
     int64_t nseg;                                          // workgroups: runs of cells of one query, at most predict_cells_segment(Kp) each
     const int32_t *seg_q, *seg_beg, *seg_cnt;              // per segment: the query, its first cell in the sorted list, its cells
