@@ -15,6 +15,12 @@
 // --topn N (with -o DIR, one GPU): the N unrated items of every user with the highest posterior-mean prediction over the kept
 // samples, and its spread, to DIR/topn.csv (query,rank,candidate,mean,std; 1-based ids in the numbering of the input);
 // --topn-by cols ranks the users of every item instead.  stdout is the same as without it.
+// --intervals L1[,L2..] (1 <= -i - -b <= 4096, a test matrix; one GPU, no -g): predictive intervals and their calibration (DESIGN.md
+// section 31).  The run keeps the sample rings of both sides (the blocking loop) and after the chain bpmf_hip_interval_cells gives every
+// test cell the central intervals of its posterior predictive mixture at the 1 .. 4 levels and the probability integral transform of
+// its held-out value: two more Final lines (coverage, PIT) and, with -o DIR, DIR/intervals.csv (row,col,value,mean,std,pit,lo<L>,hi<L>,..;
+// 1-based original ids in test-set order).  With --model DIR --predict FILE the same file for FILE's cells, FILE's values being the
+// observations.
 // --topn-score ucb|prob|ei ranks by an acquisition score of the kept samples instead of their mean:
 // mean + kappa std (--topn-kappa), the posterior probability that a rating exceeds --topn-threshold, or the expected excess over
 // it, with sigma = 1 / sqrt(-a) (1 under --probit); topn.csv then has the columns query,rank,candidate,score,mean,std.
@@ -174,6 +180,13 @@ void usage()
               << "              DIR/score.csv (row,col,value,lpd,mean,std) and DIR/waic-elpd.sdm.  Needs -i - -b >= 2; one GPU, no -g; not with\n"
               << "              --tensor, --ordinal, --implicit, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE: FILE's values are\n"
               << "              the observations, and -n TRAIN adds the WAIC of TRAIN's cells\n"
+              << "  [--intervals L1[,L2..]]: predictive intervals: for every test cell the central intervals at the 1 .. 4 levels (in [0.01, 0.998],\n"
+              << "              e.g. 0.5,0.9) of its posterior predictive, the mixture over the kept samples of N(prediction, 1 / alpha), and\n"
+              << "              the probability integral transform (pit) of its held-out value: two more Final lines (the coverage and mean\n"
+              << "              width per level, the Kolmogorov distance of the pits from uniform) and, with -o DIR, DIR/intervals.csv\n"
+              << "              (row,col,value,mean,std,pit,lo<L>,hi<L>,..).  Needs 1 <= -i - -b <= 4096 and -p TEST; one GPU, no -g; not with\n"
+              << "              --tensor, --ordinal, --probit, --implicit, --robust, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE:\n"
+              << "              the same file for FILE's cells, FILE's values being the observations\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
               << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
@@ -468,6 +481,12 @@ struct Job {
     struct ScoreSet { bool have = false; std::vector<int32_t> q, c; std::vector<double> y, lpd, pw, mean, std; } sc_test, sc_train;   // cells (user, movie) in the numbering of the run
     std::vector<double> sc_alpha;                                    // the alpha of every kept sample (one value: the same for all)
     int sc_samples = 0;
+    std::vector<double> iv_levels;                                   // --intervals L1[,L2..]: the levels, as given; the quantile orders they need, increasing
+    std::vector<double> iv_tau;
+    std::vector<int> iv_lo, iv_hi;                                   // per level: the places of its two ends in iv_tau
+    std::vector<int32_t> iv_q, iv_c;                                 // cells (user, movie) in the numbering of the run
+    std::vector<double> iv_y, iv_pit, iv_quant, iv_mean, iv_std;     // iv_quant: cells x iv_tau.size()
+    int iv_samples = 0;
     bool adaptive = false;                                           // --noise adaptive
     double a0 = 1.0, b0 = 1.0, alpha_max = 0.0;                      // --alpha-prior A0,B0, --alpha-max F (0: no cap)
     std::vector<double> alpha_trace, train_rmse;                     // per iteration: the alpha it ran with, sqrt(SSE / n) after it
@@ -770,6 +789,86 @@ void print_score(std::ostream &os, const Job &J)
     }
 }
 
+// --intervals over the sample rings of both sides: after the chain or from a loaded model, for the cells of `cells`
+// (one column per movie) with their values as the observations, weight 1; J.sc_alpha holds the alpha of the kept samples.
+void serve_intervals(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc &cells)
+{
+    if (J.iv_levels.empty()) return;                                 // one rank (main refuses -g)
+    const double t0 = tick();
+    const size_t n = (size_t)cells.nnz(), n1 = std::max<size_t>(n, 1), nq = J.iv_tau.size();
+    J.iv_q.resize(n1); J.iv_c.resize(n1); J.iv_y.resize(n1); J.iv_pit.resize(n1); J.iv_quant.resize(n1 * nq); J.iv_mean.resize(n1); J.iv_std.resize(n1);
+    for (int64_t col = 0; col < cells.ncols; ++col)
+        for (int64_t at = cells.colptr[(size_t)col]; at < cells.colptr[(size_t)col + 1]; ++at) {
+            J.iv_q[(size_t)at] = cells.rowidx[(size_t)at]; J.iv_c[(size_t)at] = (int32_t)col; J.iv_y[(size_t)at] = cells.vals[(size_t)at];
+        }
+    check(bpmf_hip_interval_cells(users, movies, J.mean_m, (int64_t)n, J.iv_q.data(), J.iv_c.data(), J.iv_y.data(), nullptr, (int)J.sc_alpha.size(),
+                                  J.sc_alpha.data(), (int)nq, J.iv_tau.data(), J.iv_pit.data(), J.iv_quant.data(), J.iv_mean.data(), J.iv_std.data()));
+    J.iv_q.resize(n); J.iv_c.resize(n); J.iv_y.resize(n); J.iv_pit.resize(n); J.iv_quant.resize(n * nq); J.iv_mean.resize(n); J.iv_std.resize(n);
+    J.iv_samples = bpmf_hip_side_samples_count(users);
+    std::cerr << "intervals: " << n << " cells over " << J.iv_samples << " samples, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+}
+
+// the level as the column names of intervals.csv and the Final line carry it: its percentage in the shortest form (90, 99.8)
+std::string level_name(double level)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.10g", 100.0 * level);
+    return buf;
+}
+
+// DIR/intervals.csv: the cells in test-set order, 1-based ids in the ORIGINAL numbering, with the value as given
+void write_intervals(const Job &J)
+{
+    if (J.iv_levels.empty() || J.odirname.empty()) return;
+    const std::string name = J.odirname + "/intervals.csv";
+    FILE *f = fopen(name.c_str(), "w");
+    if (!f) die("cannot write " + name);
+    fprintf(f, "row,col,value,mean,std,pit");
+    for (double l : J.iv_levels) fprintf(f, ",lo%s,hi%s", level_name(l).c_str(), level_name(l).c_str());
+    fprintf(f, "\n");
+    const size_t nq = J.iv_tau.size();
+    for (size_t i = 0; i < J.iv_q.size(); ++i) {
+        const int64_t r = J.iv_q[i], c = J.iv_c[i];
+        fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g,%.17g", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.iv_y[i], J.iv_mean[i], J.iv_std[i], J.iv_pit[i]);
+        for (size_t k = 0; k < J.iv_levels.size(); ++k) fprintf(f, ",%.17g,%.17g", J.iv_quant[i * nq + (size_t)J.iv_lo[k]], J.iv_quant[i * nq + (size_t)J.iv_hi[k]]);
+        fprintf(f, "\n");
+    }
+    if (fclose(f) != 0) die("cannot write " + name);
+}
+
+// the Final lines of --intervals (bpmf_amd.calibration_summary computes the same figures): cells whose pit is NaN are left out
+void print_intervals(std::ostream &os, const Job &J)
+{
+    if (J.iv_levels.empty()) return;
+    const size_t nq = J.iv_tau.size();
+    std::vector<double> p;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < J.iv_pit.size(); ++i) if (!std::isnan(J.iv_pit[i])) { p.push_back(J.iv_pit[i]); at.push_back(i); }
+    const double n = (double)p.size();
+    std::string line = "Final coverage:";
+    char buf[256];
+    for (size_t k = 0; k < J.iv_levels.size(); ++k) {
+        const double l = J.iv_levels[k];
+        size_t inside = 0;
+        double width = 0.0;
+        for (size_t j = 0; j < p.size(); ++j) {
+            inside += std::fabs(p[j] - 0.5) <= 0.5 * l;
+            width += J.iv_quant[at[j] * nq + (size_t)J.iv_hi[k]] - J.iv_quant[at[j] * nq + (size_t)J.iv_lo[k]];
+        }
+        snprintf(buf, sizeof buf, " %s%%: %.3f (se %.3f, width %.2f)", level_name(l).c_str(), p.empty() ? NAN : (double)inside / n,
+                 p.empty() ? NAN : std::sqrt(l * (1.0 - l) / n), p.empty() ? NAN : width / n);
+        line += buf;
+    }
+    snprintf(buf, sizeof buf, " (%lld cells, %d samples)", (long long)p.size(), J.iv_samples);
+    os << line << buf << std::endl;
+    std::sort(p.begin(), p.end());
+    double ks = p.empty() ? NAN : 0.0;
+    for (size_t i = 0; i < p.size(); ++i) ks = std::max(ks, std::max((double)(i + 1) / n - p[i], p[i] - (double)i / n));
+    snprintf(buf, sizeof buf, "Final PIT: KS %.3f", ks);
+    os << buf << std::endl;
+}
+
 // --fold-in-rows / --fold-in-cols against the sample ring of the other side and the side's hyper ring: after the chain or from a loaded model
 void serve_fold(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies)
 {
@@ -1010,7 +1109,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
     const bool saving = !J.save_model.empty();
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose || J.score, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose || J.score;
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty(), ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty();
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -1128,6 +1227,11 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (saving) os << "save-model: " << J.save_model << std::endl;
     if (J.diagnose) os << "diagnose: split-Rhat and ESS of the test predictions" << std::endl;
     if (J.score) os << "score: WAIC of the training cells and log density of the test cells" << std::endl;
+    if (!J.iv_levels.empty()) {
+        os << "intervals: central predictive intervals of the test cells at";
+        for (double l : J.iv_levels) os << " " << level_name(l) << "%";
+        os << ", and the calibration of their held-out values" << std::endl;
+    }
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -1189,7 +1293,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
     // (--bias: the evaluation of an iteration reads the bias vectors the next one overwrites -- the blocking loop)
     // (--diagnose keeps the samples in the rings too)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose && !J.score) {
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose && !J.score && J.iv_levels.empty()) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -1375,11 +1479,12 @@ void rank_main(Job &J, int rank, std::ostream &os)
         for (const std::vector<double> &t : J.dg_trace) tr.insert(tr.end(), t.begin(), t.end());
         check(bpmf_hip_diag_traces(ctx, 3, (int)S, tr.data(), rh.data(), J.dg_trace_ess));
     }
-    if (J.score) {                                                   // the alpha every kept iteration ran with
+    if (J.score || !J.iv_levels.empty()) {                           // the alpha every kept iteration ran with
         J.sc_alpha.clear();
         if (J.adaptive) for (int it = burnin; it < nsims; ++it) J.sc_alpha.push_back(J.alpha_trace[(size_t)it]);
         else J.sc_alpha.push_back(J.probit ? 1.0 : J.alpha);
         serve_score(J, users, movies, J.T.nnz() > 0 ? &J.T : nullptr, &J.M);     // (no test cell: no test line)
+        serve_intervals(J, users, movies, J.T);
     }
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
@@ -1550,6 +1655,10 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
     if (J.score && m.S < 2) die("--score needs at least 2 samples, the model " + dir + " holds " + std::to_string(m.S));
     if (J.score && !m.probit && !(m.alpha > 0.0) && !m.hyper) die("--score needs a model with alpha > 0 (the noise precision of its likelihood)");
+    if (!J.iv_levels.empty() && m.probit) die("--intervals: " + dir + " is a probit model (its predictive is a probability, not an interval)");
+    if (!J.iv_levels.empty() && m.S > BPMF_HIP_INTERVAL_MAX_SAMPLES)
+        die("--intervals takes at most " + std::to_string(BPMF_HIP_INTERVAL_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
+    if (!J.iv_levels.empty() && !(m.alpha > 0.0) && !m.hyper) die("--intervals needs a model with alpha > 0 (the noise precision of its likelihood)");
     if (J.diagnose && (m.S < 8 || m.S > BPMF_HIP_DIAG_MAX_SAMPLES))
         die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
     for (const std::string *f : {&fold_in_rows, &fold_in_cols}) {
@@ -1647,12 +1756,13 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     serve_rank(J, users, movies);
     serve_similar(J, users, movies);
     serve_diag(J, users, movies, P);                                 // --predict FILE --diagnose: FILE's cells
-    if (J.score) {                                                   // --predict FILE --score: FILE's values are the observations; -n TRAIN: its WAIC
+    if (J.score || !J.iv_levels.empty()) {                           // --predict FILE --score / --intervals: FILE's values are the observations; -n TRAIN: its WAIC
         J.probit_threshold = m.probit_threshold;
         J.sc_alpha.clear();
         if (m.hyper && !m.probit) for (size_t sm = 0; sm < (size_t)m.S; ++sm) J.sc_alpha.push_back(m.Uh[sm * (1 + (size_t)K + (size_t)K * K)]);
         else J.sc_alpha.push_back(m.probit ? 1.0 : m.alpha);
         serve_score(J, users, movies, predict_file.empty() ? nullptr : &P, fname.empty() ? nullptr : &J.M);
+        serve_intervals(J, users, movies, P);
     }
     serve_fold(J, users, movies);
     bpmf_hip_side_destroy(movies);
@@ -1665,6 +1775,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     print_diag(std::cout, J, false);
     write_score(J, &P, &J.M);
     print_score(std::cout, J);
+    write_intervals(J);
+    print_intervals(std::cout, J);
     const RankMetrics rkm = write_ranks(J);
     write_new(J, J.fold_u, true, nmovies, "foldin");
     write_new(J, J.fold_m, false, nusers, "foldin");
@@ -1715,7 +1827,7 @@ int main(int argc, char *argv[])
                                               {"bias", no_argument, nullptr, 1090}, {"bias-lambda", required_argument, nullptr, 1091},
                                               {"bias-prior", required_argument, nullptr, 1092},
                                               {"diagnose", no_argument, nullptr, 1100},
-                                              {"score", no_argument, nullptr, 1101},
+                                              {"score", no_argument, nullptr, 1101}, {"intervals", required_argument, nullptr, 1102},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
     std::string bias_lambda, bias_prior;
@@ -1731,6 +1843,8 @@ int main(int argc, char *argv[])
     std::string implicit_w0, rank_eval_n, rank_by = "rows", rank_threshold;
     bool rank_eval_given = false, rank_by_given = false;
     std::string model_dir, predict_file, predict_threshold;
+    std::string intervals;
+    bool intervals_given = false;
     bool save_model_given = false, model_given = false, predict_given = false, predict_threshold_given = false;
     bool nsims_given = false, burnin_given = false, d_given = false, g_given = false;
     std::string training_flag;                                       // the first flag of the likelihood / the chain (refused with --model)
@@ -1789,6 +1903,7 @@ int main(int argc, char *argv[])
         case 1092: training("--bias-prior"); bias_prior = optarg; bias_prior_given = true; break;
         case 1100: J.diagnose = true; break;
         case 1101: J.score = true; break;
+        case 1102: intervals = optarg; intervals_given = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1855,6 +1970,38 @@ int main(int argc, char *argv[])
         if (!mname.empty() || !lname.empty()) die("--score does not go together with a propagated posterior (-m / -l)");
         if (model_given && !predict_given && fname.empty()) die("--score with --model needs --predict FILE (held-out cells with their values) or -n TRAIN (the cells of WAIC)");
         if (!model_given && J.nsims - J.burnin < 2) die("--score needs at least 2 post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
+    }
+    // --intervals: refused before anything touches a GPU
+    if (intervals_given) {
+        const std::string expects = "--intervals expects 1 .. 4 distinct levels in [0.01, 0.998] separated by commas, not '" + intervals + "'";
+        for (size_t from = 0; from <= intervals.size();) {
+            const size_t to = std::min(intervals.find(',', from), intervals.size());
+            const std::string word = intervals.substr(from, to - from);
+            char *e = nullptr;
+            const double l = strtod(word.c_str(), &e);
+            if (word.empty() || *e != '\0' || !(l >= 0.01 && l <= 0.998) || J.iv_levels.size() == 4) die(expects);
+            for (double have : J.iv_levels) if (have == l) die(expects);
+            J.iv_levels.push_back(l);
+            from = to + 1;
+        }
+        for (double l : J.iv_levels) { J.iv_tau.push_back((1.0 - l) / 2.0); J.iv_tau.push_back((1.0 + l) / 2.0); }
+        std::sort(J.iv_tau.begin(), J.iv_tau.end());
+        for (double l : J.iv_levels) {
+            J.iv_lo.push_back((int)(std::find(J.iv_tau.begin(), J.iv_tau.end(), (1.0 - l) / 2.0) - J.iv_tau.begin()));
+            J.iv_hi.push_back((int)(std::find(J.iv_tau.begin(), J.iv_tau.end(), (1.0 + l) / 2.0) - J.iv_tau.begin()));
+        }
+        if (tensor_given) die("--intervals does not go together with --tensor (the intervals are those of a matrix model)");
+        if (J.ordinal) die("--intervals does not go together with --ordinal (its predictive is over levels)");
+        if (J.probit) die("--intervals does not go together with --probit (its predictive is a probability, not an interval)");
+        if (J.implicit) die("--intervals does not go together with --implicit (its likelihood runs over every cell of the matrix)");
+        if (J.robust) die("--intervals does not go together with --robust (a mixture of Student-t distributions needs an incomplete beta function on the device: deliberately out of scope)");
+        if (g_given || ngpu >= 1) die("--intervals runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample ring of a sharded side is not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--intervals does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--intervals does not go together with a propagated posterior (-m / -l)");
+        if (model_given && !predict_given) die("--intervals with --model needs --predict FILE (the cells, with their values as the observations)");
+        if (!model_given && probename.empty()) die("--intervals needs a test matrix (-p TEST: its cells get the intervals, its values the calibration)");
+        if (!model_given && (J.nsims - J.burnin < 1 || J.nsims - J.burnin > BPMF_HIP_INTERVAL_MAX_SAMPLES))
+            die("--intervals needs 1 .. " + std::to_string(BPMF_HIP_INTERVAL_MAX_SAMPLES) + " post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
     }
     // --model / --predict / --save-model: refused before anything touches a GPU
     if (predict_given && !model_given) die("--predict needs --model DIR (cells are predicted from a saved model)");
@@ -2597,6 +2744,7 @@ int main(int argc, char *argv[])
     write_similar(J);
     write_diag(J);
     write_score(J, &J.T, &J.M);
+    write_intervals(J);
 
     const RankMetrics rkm = write_ranks(J);
 
@@ -2682,6 +2830,7 @@ int main(int argc, char *argv[])
     os << "Final Avg RMSE: " << J.rmse_avg << std::endl;
     print_diag(os, J, true);
     print_score(os, J);
+    print_intervals(os, J);
     if (J.ordinal && !J.cat_prob.empty()) {
         os << "Final ordinal RMSE: " << J.ord_rmse << std::endl;
         os << "Final accuracy: " << J.ord_accuracy << std::endl;

@@ -5,19 +5,20 @@
 
 using namespace bpmf_capi;
 
-namespace {
-
 // The trace buffer of a batch.  A batch must fill the device on its own (its two kernels run behind those of the batch before): at the
 // ML-1M shape, 100 k cells, K = 32, S = 1000, batches of 8 388 cells (64 MiB) took 18.8 ms, of 32 768 cells 12.6 ms, one batch of all
 // cells (800 MB) 10.2 ms, beside 9.6 ms of k_predict_cells
-constexpr int64_t kTraceBytes = (int64_t)256 << 20;
-std::atomic<int> g_batch_cells{0};                                     // bpmf_hip_diag_batch_cells (0: from kTraceBytes)
-
-int64_t batch_traces(int S)
+int64_t bpmf_capi::trace_batch_cells(int S, int forced)
 {
-    const int forced = g_batch_cells.load();
+    constexpr int64_t kTraceBytes = (int64_t)256 << 20;
     return forced > 0 ? forced : std::max<int64_t>(1, kTraceBytes / ((int64_t)S * (int64_t)sizeof(double)));
 }
+
+namespace {
+
+std::atomic<int> g_batch_cells{0};                                     // bpmf_hip_diag_batch_cells (0: from the trace buffer's size)
+
+int64_t batch_traces(int S) { return trace_batch_cells(S, g_batch_cells.load()); }
 
 int refuse_samples(const std::string &who, int S)
 {

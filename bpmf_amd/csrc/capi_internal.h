@@ -16,6 +16,8 @@
 //                      (bpmf_hip_predict_cells); what the cell lists share: their checks, their sort and their batches (CellsPlan)
 //   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
 //   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells)
+//   capi_interval.hip  predictive intervals: the probability integral transform and quantiles of the posterior predictive mixture of a list of cells
+//                      (bpmf_hip_interval_cells) and of host traces (bpmf_hip_interval_traces)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities
@@ -163,8 +165,8 @@ struct TopnLists {
     int read_back(const char *who, int32_t *idx, double *score, double *mean, double *std) const;   // score NULL: not scored
 };
 
-// A list of (query, candidate) cells over two rings (capi_model.hip): what bpmf_hip_predict_cells, bpmf_hip_diag_cells and
-// bpmf_hip_score_cells share.  cells_check_list refuses, as `who` and on the host alone, what pair_check_sides does (single GPU), then
+// A list of (query, candidate) cells over two rings (capi_model.hip): what bpmf_hip_predict_cells, bpmf_hip_diag_cells,
+// bpmf_hip_score_cells and bpmf_hip_interval_cells share.  cells_check_list refuses, as `who` and on the host alone, what pair_check_sides does (single GPU), then
 // n, mean_rating, a NULL list and a cell out of range; pair_open_rings follows the caller's own checks.  cells_sort groups the list by
 // query (stable counting sort).
 struct CellsSorted { std::vector<int32_t> query, cand, orig; };       // per sorted cell: its query, its candidate, its place in the caller's list
@@ -186,6 +188,28 @@ struct CellsPlan {
     const int32_t *orig() const { return d_orig.get(); }
     void bind(bpmf_launch::PredCellsLaunch &p, size_t b) const;        // nseg, seg_q, seg_beg, seg_cnt of batch b; cand, orig
 };
+
+// cells of a batch whose traces (S doubles per cell) fill the trace buffer of 256 MiB, or `forced` if > 0 (capi_diag.hip): what
+// bpmf_hip_diag_cells / _traces and bpmf_hip_interval_cells / _traces cut their lists by
+int64_t trace_batch_cells(int S, int forced);
+
+// Phi^-1(p), 0 < p < 1: Newton on Phi(x) - p from 0 in the variable that keeps the tail resolved (p <= 1/2 by symmetry), each
+// step limited to 1; the start of the default cutpoints (capi_ordinal.hip) and the z of a quantile's bracket (capi_interval.hip)
+inline double normal_quantile(double p)
+{
+    const bool upper = p > 0.5;
+    const double q = upper ? 1.0 - p : p;                              // q = Phi(x), x <= 0
+    double x = 0.0;
+    for (int it = 0; it < 200; ++it) {
+        const double f = 0.5 * std::erfc(-x * 0.70710678118654752440) - q;
+        const double d = std::exp(-0.5 * x * x) * 0.3989422804014326779;
+        double step = f / d;
+        step = step > 1.0 ? 1.0 : step < -1.0 ? -1.0 : step;
+        x -= step;
+        if (std::fabs(step) <= 1e-16 * (1.0 + std::fabs(x))) break;
+    }
+    return upper ? -x : x;
+}
 
 // side information (capi_link.hip): what bpmf_hip_side_set_features and _set_features_sparse share -- the refusals (reported as `who`),
 // then the arrays both kinds of features need, zeroed, with the ratings as the first residuals.  *out is not attached to `s` yet.

@@ -32,24 +32,6 @@ double logmass(double a, double b)
     return std::log(0.5 * (std::erfc(a * kRsqrt2) - std::erfc(b * kRsqrt2)));
 }
 
-// Phi^-1(p), 0 < p < 1: Newton on Phi(x) - p from 0 in the variable that keeps the tail resolved (p <= 1/2 by symmetry), each
-// step limited to 1; the start of the default cutpoints
-double normal_quantile(double p)
-{
-    const bool upper = p > 0.5;
-    const double q = upper ? 1.0 - p : p;                              // q = Phi(x), x <= 0
-    double x = 0.0;
-    for (int it = 0; it < 200; ++it) {
-        const double f = 0.5 * std::erfc(-x * kRsqrt2) - q;
-        const double d = std::exp(-0.5 * x * x) * 0.3989422804014326779;
-        double step = f / d;
-        step = step > 1.0 ? 1.0 : step < -1.0 ? -1.0 : step;
-        x -= step;
-        if (std::fabs(step) <= 1e-16 * (1.0 + std::fabs(x))) break;
-    }
-    return upper ? -x : x;
-}
-
 int check_cutpoints(const char *who, const double *cut, int nlev)
 {
     for (int i = 0; i + 1 < nlev; ++i) {

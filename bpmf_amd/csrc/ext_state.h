@@ -137,6 +137,7 @@ struct bpmf_ring {
     Timed sim;                               // around the newest bpmf_hip_similar of the side (bpmf_hip_similar_last_ms)
     Timed diag;                              // around the kernels of the newest bpmf_hip_diag_cells with the side as the queries (bpmf_hip_diag_last_ms)
     Timed score;                             // around the kernels of the newest bpmf_hip_score_cells with the side as the queries (bpmf_hip_score_last_ms)
+    Timed interval;                          // around the kernels of the newest bpmf_hip_interval_cells with the side as the queries (bpmf_hip_interval_last_ms)
 };
 
 // rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as

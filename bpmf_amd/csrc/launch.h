@@ -247,6 +247,21 @@ int cell_traces_segment(int Kp);                            // cells of a segmen
 int cell_traces(const PredCellsLaunch &p, double *trace, int64_t tbase, hipStream_t st);          // -1: shape not supported (nothing launched)
 int trace_diag(const double *traces, int64_t ntr, int S, const int32_t *orig, double *rhat, double *ess, hipStream_t st);   // -1 likewise
 
+// predictive intervals (kernels_interval.h, kinterval.hip): the probability integral transform of y (NULL: none) and nq quantiles of the
+// mixture of S normals around ntr traces of S samples (row-major, on the device; what cell_traces stores), to pit[orig[t]] and
+// quant[orig[t] * nq + j] (orig NULL: [t]).  y and w (NULL: 1) are read at the same places; sa: sqrt(alpha_s), S doubles on the device,
+// or NULL: sa0 for every sample; tau increasing, z = Phi^-1(tau).
+struct TraceQuantLaunch {
+    const double *traces; int64_t ntr; int S; const int32_t *orig;
+    double mean_rating;
+    const double *y, *w, *sa; double sa0;
+    int nq; double tau[8], z[8];
+    double *pit, *quant;
+};
+int interval_max_samples();
+int interval_max_quantiles();
+int trace_quantiles(const TraceQuantLaunch &p, hipStream_t st);   // -1: shape not supported (nothing launched)
+
 // model comparison (kernels_score.h, kscore.hip): predict_cells' walk of one batch of sorted cells (`cells`; want_prob, t, sigma and
 // prob are not read), which also turns every cell's S predictions into the log pointwise predictive density and the variance of the
 // log density.  kind: BPMF_HIP_LOGDENS_*; y, w (NULL: 1) and flag (NULL: none; probit: the sign of the label, never NULL) are in the

@@ -392,6 +392,83 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_score_last_ms(query.handle, C.byref(ms)))
         return ms.value
 
+    # -- predictive intervals ------------------------------------------------------
+    INTERVAL_MAX_SAMPLES, INTERVAL_MAX_QUANTILES = 4096, 8
+
+    @staticmethod
+    def _interval_args(who, n, y, w, alpha, tau):
+        """The optional arrays of interval_cells / interval_traces as contiguous float64 (None stays None), alpha and tau as vectors."""
+        def per_item(a, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float64)
+            if a.shape != (n,):
+                raise ValueError("%s: %s must have one value per item" % (who, what))
+            return a
+        alpha = np.ascontiguousarray(np.atleast_1d(alpha), np.float64)
+        if alpha.ndim != 1 or len(alpha) < 1:
+            raise ValueError("%s: alpha must be one number or one per sample" % who)
+        tau = np.ascontiguousarray(np.atleast_1d(tau) if tau is not None else np.zeros(0), np.float64)
+        if tau.ndim != 1:
+            raise ValueError("%s: tau must be a vector" % who)
+        return per_item(y, "y"), per_item(w, "w"), alpha, tau
+
+    def interval_traces(self, D, alpha, tau=(), y=None, w=None, mean_rating=0.0):
+        """(pit [n] or None, quant [n, nq]) of the mixtures (1/S) sum_s N(mean_rating + D[i, s], 1 / (alpha_s w[i])) around the n traces
+        D [n, S] (one trace: [S]), 1 <= S <= 4096: pit[i] = F_i(y[i]) (y None: no pit), quant[i, j] =
+        F_i^-1(tau[j]) for up to 8 strictly increasing tau in [0.001, 0.999].  alpha: one number or S values.  A trace holding a value
+        that is not finite gives NaN."""
+        D = np.ascontiguousarray(D, np.float64)
+        if D.ndim == 1:
+            D = D[None, :]
+        if D.ndim != 2:
+            raise ValueError("interval_traces: D must be [n, S]")
+        n, S = D.shape
+        y, w, alpha, tau = self._interval_args("interval_traces", n, y, w, alpha, tau)
+        nq = len(tau)
+        pit = np.empty(n) if y is not None else None
+        quant = np.empty((n, nq))
+        hold = np.zeros(1)
+
+        def opt(a):
+            return None if a is None else _ptr(a if a.size else hold)
+        _lib.check(self.lib.bpmf_hip_interval_traces(self.ctx, n, S, _ptr(D if D.size else hold), float(mean_rating), opt(y), opt(w), len(alpha),
+                                                     _ptr(alpha), nq, _ptr(tau if nq else hold), opt(pit), _ptr(quant if quant.size else hold)))
+        return pit, quant
+
+    def interval_cells(self, query, cand, mean_rating, q, c, alpha, tau=(), y=None, w=None):
+        """dict(pit, quant, mean, std) of the cells (q[i], c[i]) over the S samples of the two rings: the
+        probability integral transform pit [n] of the observed values y (None without y) and the quantiles quant [n, nq] at tau of the
+        posterior predictive mixture, as interval_traces defines them around p_s = mean_rating + u_s . v_s; mean and std are
+        predict_cells's, bit for bit.  alpha: the noise precision, one number or S values in ring-slot order; w: per-cell weights."""
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32)
+        if q.ndim != 1 or q.shape != c.shape:
+            raise ValueError("interval_cells: q and c must be one-dimensional and of the same length")
+        n = len(q)
+        y, w, alpha, tau = self._interval_args("interval_cells", n, y, w, alpha, tau)
+        nq = len(tau)
+        pit = np.empty(n) if y is not None else None
+        quant = np.empty((n, nq)); mean = np.empty(n); std = np.empty(n)
+        hold = np.zeros(1); holdi = np.zeros(1, np.int32)
+
+        def opt(a):
+            return None if a is None else _ptr(a if a.size else hold)
+        _lib.check(self.lib.bpmf_hip_interval_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else holdi), _ptr(c if n else holdi),
+                                                    opt(y), opt(w), len(alpha), _ptr(alpha), nq, _ptr(tau if nq else hold), opt(pit),
+                                                    _ptr(quant if quant.size else hold), opt(mean), opt(std)))
+        return dict(pit=pit, quant=quant, mean=mean, std=std)
+
+    def interval_batch_cells(self, cells):
+        """Cells per batch of interval_cells and interval_traces (0: automatic, from the size of the trace buffer).  For tests: results do
+        not depend on it."""
+        _lib.check(self.lib.bpmf_hip_interval_batch_cells(int(cells)))
+
+    def interval_last_ms(self, query):
+        """Device time of the kernels of the newest interval_cells with `query` as the queries, between two events (tools/interval_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_interval_last_ms(query.handle, C.byref(ms)))
+        return ms.value
+
     def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
         """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
         (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""

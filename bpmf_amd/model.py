@@ -262,3 +262,82 @@ def score_cells(res, rows, cols, values, weights=None, flags=None):
     d.update(rows=rows, cols=cols, samples=S, kind=kind, elpd=d["lpd"] - d["pwaic"])
     d["summary"] = score_summary(d)
     return d
+
+
+def interval_taus(levels):
+    """(levels, taus, lo_at, hi_at): the 1 .. 4 distinct levels in [0.01, 0.998] as floats, the strictly increasing quantile orders
+    (1 - l) / 2 and (1 + l) / 2 of their central intervals, and per level the places of its two ends among them."""
+    levels = [float(l) for l in np.atleast_1d(np.asarray(levels, np.float64))]
+    if not 1 <= len(levels) <= 4:
+        raise ValueError("intervals: 1 .. 4 levels, not %d" % len(levels))
+    for l in levels:
+        if not (0.01 <= l <= 0.998):
+            raise ValueError("intervals: the level %r is outside [0.01, 0.998]" % (l,))
+    if len(set(levels)) != len(levels):
+        raise ValueError("intervals: the levels must differ")
+    taus = sorted([(1.0 - l) / 2.0 for l in levels] + [(1.0 + l) / 2.0 for l in levels])
+    lo_at = [taus.index((1.0 - l) / 2.0) for l in levels]
+    hi_at = [taus.index((1.0 + l) / 2.0) for l in levels]
+    return levels, np.asarray(taus, np.float64), lo_at, hi_at
+
+
+def calibration_summary(pit, levels, lo=None, hi=None):
+    """How well central predictive intervals cover held-out values, from their probability integral transforms pit [n] alone (a value
+    lies inside the central interval of level l exactly when |pit - 1/2| <= l / 2): dict(n, levels, coverage, se, width, hist, ks) with
+    per level the share of values inside and its binomial standard error sqrt(l (1 - l) / n) under perfect calibration, the mean width
+    hi - lo of the intervals (lo, hi [n, levels]; NaN without them), the ten-bin histogram of the pits (counts; uniform when calibrated:
+    a hump in the middle says the intervals are too wide, a U that they are too narrow) and the Kolmogorov distance
+    sup_u |ecdf(pit)(u) - u|.  Pits that are NaN are left out and counted as n_nan."""
+    pit = np.asarray(pit, np.float64).ravel()
+    ok = ~np.isnan(pit)
+    p = np.sort(pit[ok])
+    n = len(p)
+    levels = [float(l) for l in np.atleast_1d(np.asarray(levels, np.float64))]
+    nan = float("nan")
+    cover = [float(np.mean(np.abs(p - 0.5) <= 0.5 * l)) if n else nan for l in levels]
+    se = [math.sqrt(l * (1.0 - l) / n) if n else nan for l in levels]
+    if lo is not None and hi is not None and n:
+        wd = (np.asarray(hi, np.float64) - np.asarray(lo, np.float64)).reshape(len(pit), len(levels))[ok]
+        width = [float(wd[:, k].mean()) for k in range(len(levels))]
+    else:
+        width = [nan] * len(levels)
+    hist = np.bincount(np.minimum((p * 10.0).astype(np.int64), 9), minlength=10).astype(np.int64) if n else np.zeros(10, np.int64)
+    if n:
+        i = np.arange(n, dtype=np.float64)
+        ks = float(max(((i + 1.0) / n - p).max(), (p - i / n).max()))
+    else:
+        ks = nan
+    return dict(n=int(n), n_nan=int(len(pit) - n), levels=levels, coverage=cover, se=se, width=width, hist=hist, ks=ks)
+
+
+def predict_intervals(res, rows, cols, levels=(0.9,), values=None, weights=None):
+    """Central predictive intervals of the cells (rows[i], cols[i]) -- user, movie, 0-based -- from the kept samples of `res` (gibbs with
+    the rings kept, or load_model; 1 .. 4096 samples): dict(rows, cols, mean, std, levels, lo, hi, pit, samples,
+    summary).  The posterior predictive of a cell is the mixture over the samples of N(p_s, 1 / (alpha_s w)); lo and hi [n, levels] are
+    its quantiles at (1 - l) / 2 and (1 + l) / 2 for each of the 1 .. 4 levels in [0.01, 0.998]; mean and std are predict_cells's.
+    values: observed values of the cells; then pit [n] is their probability integral transform and summary = calibration_summary of
+    it (else both None).  weights: per-cell precision weights (None: 1, what held-out cells have).  alpha is the precision every
+    kept sample ran with (model_info["alpha_samples"], one per sample, else model_info["alpha"]).  Gaussian likelihoods only: probit,
+    ordinal, implicit and Student-t (robust=) runs are refused."""
+    users, movies = res["users"], res["movies"]
+    info = res.get("model_info")
+    if info is None:
+        raise ValueError("predict_intervals: the result carries no model_info (it comes from gibbs or load_model)")
+    if info.get("probit") or not info.get("scored", True):
+        raise ValueError("predict_intervals: probit, ordinal and implicit runs have no Gaussian predictive")
+    if info.get("nu") is not None:
+        raise ValueError("predict_intervals: not after robust= (a mixture of Student-t distributions needs an incomplete beta function on the device: out of scope)")
+    levels, taus, lo_at, hi_at = interval_taus(levels)
+    engine = users.engine
+    S = engine.samples_count(users.side)
+    rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
+    alpha = info.get("alpha_samples")
+    if alpha is None:
+        alpha = float(info.get("alpha", float("nan")))
+    elif len(alpha) != S:
+        raise ValueError("predict_intervals: model_info has %d values of alpha for %d kept samples" % (len(alpha), S))
+    d = engine.interval_cells(users.side, movies.side, movies.mean_rating, rows, cols, alpha, taus, y=values, w=weights)
+    quant = d.pop("quant")
+    d.update(rows=rows, cols=cols, levels=levels, lo=np.ascontiguousarray(quant[:, lo_at]), hi=np.ascontiguousarray(quant[:, hi_at]), samples=S)
+    d["summary"] = calibration_summary(d["pit"], levels, d["lo"], d["hi"]) if values is not None else None
+    return d

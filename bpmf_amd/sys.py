@@ -198,7 +198,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False, intervals=None):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -381,7 +381,32 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     (summary["waic"] = -2 elpd).  The likelihood is the run's: Gaussian with the alpha every kept iteration ran with (noise="adaptive":
     res["alpha"] of that iteration), Student-t with nu degrees of freedom under robust=nu (the marginal density, the weights integrated
     out), probit under probit=True; bias terms are part of the rings.  Refused: ordinal (it has res["logp"]), implicit, a
-    communicator, BPMF_REDUCE, fewer than 2 kept samples.  False (the default): nothing changes."""
+    communicator, BPMF_REDUCE, fewer than 2 kept samples.  False (the default): nothing changes.
+
+    intervals=True | levels: predictive intervals and their calibration.  The sample rings are kept as for
+    score, and after the chain res["intervals"] = dict(test=bpmf_amd.predict_intervals's dict over the cells of T with their values):
+    per test cell the central intervals lo / hi of the posterior predictive mixture at the 1 .. 4 levels (True: 0.9), the probability
+    integral transform pit of its held-out value, and "summary" (bpmf_amd.calibration_summary: coverage per level, mean width, PIT
+    histogram, Kolmogorov distance).  alpha is that of every kept iteration (noise="adaptive": res["alpha"] of that iteration); test
+    cells have weight 1; bias terms are part of the rings.  Needs a test matrix and 1 .. 4096 kept samples.  Refused: probit, ordinal,
+    implicit, robust (a mixture of Student-t distributions is out of scope), a communicator, BPMF_REDUCE.  None (the default):
+    nothing changes."""
+    intervals_on = intervals is not None and intervals is not False
+    if intervals_on:                                 # (refused before the engine is used)
+        from .model import interval_taus as _interval_taus
+        interval_levels = _interval_taus((0.9,) if intervals is True else intervals)[0]
+        for on, what, why in ((bool(probit), "probit", "its predictive is a probability, not an interval"),
+                              (ordinal is not None and ordinal is not False, "ordinal", "its predictive is over levels"),
+                              (implicit is not None, "implicit", "its likelihood runs over every cell of the matrix"),
+                              (robust is not None, "robust", "a mixture of Student-t distributions needs an incomplete beta function on the device: out of scope"),
+                              (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator", "the rings of both sides must be whole on one GPU"),
+                              (_os.environ.get("BPMF_REDUCE", "0") not in ("", "0"), "BPMF_REDUCE", "the rings of both sides must be whole on one GPU")):
+            if on:
+                raise ValueError("intervals does not go together with %s (%s)" % (what, why))
+        if T is None:
+            raise ValueError("intervals needs a test matrix (its cells get the intervals, its values the calibration)")
+        if not (1 <= nsims - burnin <= _engine.HipEngine.INTERVAL_MAX_SAMPLES):
+            raise ValueError("intervals needs 1 .. %d post-burn-in samples (nsims - burnin = %d)" % (_engine.HipEngine.INTERVAL_MAX_SAMPLES, nsims - burnin))
     score_on = bool(score)
     if score_on:                                     # (refused before the engine is used)
         for on, what, why in ((ordinal is not None and ordinal is not False, "ordinal", "its held-out log density is res['logp']"),
@@ -726,8 +751,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -957,6 +982,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         m_cols = np.repeat(np.arange(len(M[0]) - 1, dtype=np.int32), np.diff(np.asarray(M[0], np.int64)))
         res["score"]["train"] = _score_cells(res, M[1], m_cols, M[2], weights=wts[0] if weights is not None else None,
                                              flags=cflags[0] if censored is not None else None)
+    if intervals_on:
+        from .model import predict_intervals as _predict_intervals
+        t_cols = np.repeat(np.arange(len(T[0]) - 1, dtype=np.int32), np.diff(np.asarray(T[0], np.int64)))
+        res["intervals"] = dict(test=_predict_intervals(res, T[1], t_cols, interval_levels, values=T[2]))
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res

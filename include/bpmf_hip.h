@@ -518,6 +518,37 @@ BPMF_API int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, dou
 BPMF_API int bpmf_hip_score_batch_cells(int cells);
 BPMF_API int bpmf_hip_score_last_ms(const bpmf_hip_side *query, float *ms);
 
+/* ---- predictive intervals: probability integral transform and quantiles of the posterior predictive ----
+ *   For the cell i = (q[i], c[i]) with the weight w_i = w[i] (NULL: 1), over the S samples both rings hold,
+ * with p_s = mean_rating + u_s(q[i]) . v_s(c[i]) and alpha_s the noise precision sample s ran with (alpha[0] for nalpha = 1, else
+ * alpha[s] in ring-slot order, nalpha = S: the convention of bpmf_hip_score_cells), the posterior predictive of the cell is the mixture
+ *     F_i(x) = (1/S) sum_s Phi((x - p_s) sqrt(alpha_s w_i)),   Phi(t) = erfc(-t / sqrt 2) / 2
+ *     pit[i] = F_i(y[i])                 the probability integral transform of the observed value y[i] (y NULL: none)
+ *     quant[i * nq + j] = F_i^-1(tau[j])  F_i increases strictly, so the root is unique
+ * A central interval of level l is [F^-1((1 - l) / 2), F^-1((1 + l) / 2)], and y[i] lies inside it exactly when |pit[i] - 1/2| <= l / 2.
+ * 0 <= nq <= BPMF_HIP_INTERVAL_MAX_QUANTILES, tau strictly increasing, every tau in [0.001, 0.999]; 1 <= S <= BPMF_HIP_INTERVAL_MAX_SAMPLES.
+ * The root is found in x - mean_rating by a Newton iteration kept inside the bracket of the component quantiles, with at most 128
+ * evaluations of F (kernels_interval.h); tau > 1/2 is solved on the survival function.  All fp64, also on fp32 contexts; quantiles never
+ * decrease in tau.  mean and std (either may be NULL) are those of bpmf_hip_predict_cells, bit for bit.  The bits of a cell depend on
+ * the cell, S, the alphas, its weight, its y and the taus alone: not on the other cells, its place in the list or the batches
+ * (bpmf_hip_interval_batch_cells sets the cells per batch, 0: automatic, for tests).  A cell whose trace holds a value that is not
+ * finite gets NaN, and no other cell does.  Checked on the host before any launch, BPMF_HIP_EINVAL with a line that names the first
+ * offender: what bpmf_hip_predict_cells refuses, nq outside the range, nothing to do (y NULL and nq = 0), a tau outside the range or
+ * not increasing, nalpha that is neither 1 nor S, an alpha or w that is not finite and > 0, a y that is not finite, S above the
+ * range, pit NULL with y given or quant NULL with nq > 0.  n = 0 launches nothing.  Waits.
+ * bpmf_hip_interval_traces: the same for n traces d_s = p_s - mean_rating of S samples given by the host, row-major (y, w per trace).
+ * bpmf_hip_interval_last_ms: device time of the kernels of the newest bpmf_hip_interval_cells with `query` as the queries. */
+#define BPMF_HIP_INTERVAL_MAX_SAMPLES 4096
+#define BPMF_HIP_INTERVAL_MAX_QUANTILES 8
+BPMF_API int bpmf_hip_interval_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                     const int32_t *c, const double *y, const double *w, int nalpha, const double *alpha, int nq,
+                                     const double *tau, double *pit, double *quant, double *mean, double *std);
+BPMF_API int bpmf_hip_interval_traces(bpmf_hip_ctx *ctx, int64_t n, int S, const double *traces, double mean_rating, const double *y,
+                                      const double *w, int nalpha, const double *alpha, int nq, const double *tau, double *pit,
+                                      double *quant);
+BPMF_API int bpmf_hip_interval_batch_cells(int cells);
+BPMF_API int bpmf_hip_interval_last_ms(const bpmf_hip_side *query, float *ms);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
