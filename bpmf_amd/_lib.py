@@ -81,6 +81,11 @@ _SIGNATURES = {
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_interval_batch_cells": (C.c_int, [C.c_int]),
     "bpmf_hip_interval_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bpmf_hip_loo_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_loo_traces": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_loo_batch_cells": (C.c_int, [C.c_int]),
+    "bpmf_hip_loo_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bpmf_hip_topn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_int64, C.c_int64, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_rank_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

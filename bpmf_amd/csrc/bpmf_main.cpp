@@ -21,6 +21,10 @@
 // its held-out value: two more Final lines (coverage, PIT) and, with -o DIR, DIR/intervals.csv (row,col,value,mean,std,pit,lo<L>,hi<L>,..;
 // 1-based original ids in test-set order).  With --model DIR --predict FILE the same file for FILE's cells, FILE's values being the
 // observations.
+// --loo (2 <= -i - -b <= 4096; one GPU, no -g): PSIS-LOO cross-validation of the training cells.  The run keeps
+// the sample rings of both sides (the blocking loop) and after the chain bpmf_hip_loo_cells gives every training cell its leave-one-out
+// log predictive density by Pareto-smoothed importance sampling and the diagnostic khat: one more Final line and, with -o DIR,
+// DIR/loo-elpd.sdm and DIR/loo-khat.sdm in the training matrix's numbering.  With --model DIR -n TRAIN the same for TRAIN's cells.
 // --topn-score ucb|prob|ei ranks by an acquisition score of the kept samples instead of their mean:
 // mean + kappa std (--topn-kappa), the posterior probability that a rating exceeds --topn-threshold, or the expected excess over
 // it, with sigma = 1 / sqrt(-a) (1 under --probit); topn.csv then has the columns query,rank,candidate,score,mean,std.
@@ -187,6 +191,11 @@ void usage()
               << "              (row,col,value,mean,std,pit,lo<L>,hi<L>,..).  Needs 1 <= -i - -b <= 4096 and -p TEST; one GPU, no -g; not with\n"
               << "              --tensor, --ordinal, --probit, --implicit, --robust, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE:\n"
               << "              the same file for FILE's cells, FILE's values being the observations\n"
+              << "  [--loo]: PSIS-LOO cross-validation: for every training cell the log predictive density a model fitted without it would\n"
+              << "              give it, by Pareto-smoothed importance sampling over the kept samples, and the diagnostic khat (<= 0.7: the\n"
+              << "              estimate can be trusted): one more Final line (looic, elpd, p_loo, se, the share of cells with k > 0.7) and, with\n"
+              << "              -o DIR, DIR/loo-elpd.sdm and DIR/loo-khat.sdm.  Needs 2 <= -i - -b <= 4096; one GPU, no -g; not with --tensor,\n"
+              << "              --ordinal, --implicit, -m / -l or BPMF_REDUCE=1; with --model DIR it needs -n TRAIN (the cells)\n"
               << "  [--topn-by rows|cols]: rank items per user (rows, the default) or users per item (cols)\n"
               << "  [--topn-score mean|ucb|prob|ei]: what --topn ranks by (default mean).  ucb: mean + kappa std; prob: the posterior\n"
               << "              probability that a rating exceeds the threshold; ei: the expected excess over the threshold; the\n"
@@ -481,6 +490,9 @@ struct Job {
     struct ScoreSet { bool have = false; std::vector<int32_t> q, c; std::vector<double> y, lpd, pw, mean, std; } sc_test, sc_train;   // cells (user, movie) in the numbering of the run
     std::vector<double> sc_alpha;                                    // the alpha of every kept sample (one value: the same for all)
     int sc_samples = 0;
+    bool loo = false;                                                // --loo: PSIS-LOO of the training cells
+    std::vector<double> loo_elpd, loo_khat, loo_lpd;                 // per training cell, in the order of M's values
+    int loo_samples = 0;
     std::vector<double> iv_levels;                                   // --intervals L1[,L2..]: the levels, as given; the quantile orders they need, increasing
     std::vector<double> iv_tau;
     std::vector<int> iv_lo, iv_hi;                                   // per level: the places of its two ends in iv_tau
@@ -701,6 +713,19 @@ void print_diag(std::ostream &os, const Job &J, bool traces)
     os << buf << std::endl;
 }
 
+// The cells of `cells` (one column per movie) as the lists a cell query takes -- user, movie and the observed value, in the order of its
+// values; probit: the label as +-1 -- resized to at least one entry: what serve_score and serve_loo hand to the library
+void observed_cells(const Job &J, const Csc &cells, std::vector<int32_t> &q, std::vector<int32_t> &c, std::vector<double> &y)
+{
+    const size_t n1 = std::max<size_t>((size_t)cells.nnz(), 1);
+    q.resize(n1); c.resize(n1); y.resize(n1);
+    for (int64_t col = 0; col < cells.ncols; ++col)
+        for (int64_t at = cells.colptr[(size_t)col]; at < cells.colptr[(size_t)col + 1]; ++at) {
+            q[(size_t)at] = cells.rowidx[(size_t)at]; c[(size_t)at] = (int32_t)col;
+            y[(size_t)at] = J.probit ? (cells.vals[(size_t)at] > J.probit_threshold ? 1.0 : -1.0) : cells.vals[(size_t)at];
+        }
+}
+
 // --score over the sample rings of both sides: after the chain or from a loaded model.  `test` (NULL: none): the
 // held-out cells with their values; `train` (NULL: none): the training cells, with the weights and censoring flags of the run.  The
 // likelihood is the run's: probit, Student-t under --robust, else Gaussian; J.sc_alpha holds the alpha of the kept samples.
@@ -712,12 +737,8 @@ void serve_score(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc 
     auto run = [&](const Csc &cells, Job::ScoreSet &out, const double *w, const int8_t *flag) {
         const size_t n = (size_t)cells.nnz(), n1 = std::max<size_t>(n, 1);
         out.have = true;
-        out.q.resize(n1); out.c.resize(n1); out.y.resize(n1); out.lpd.resize(n1); out.pw.resize(n1); out.mean.resize(n1); out.std.resize(n1);
-        for (int64_t col = 0; col < cells.ncols; ++col)
-            for (int64_t at = cells.colptr[(size_t)col]; at < cells.colptr[(size_t)col + 1]; ++at) {
-                out.q[(size_t)at] = cells.rowidx[(size_t)at]; out.c[(size_t)at] = (int32_t)col;
-                out.y[(size_t)at] = J.probit ? (cells.vals[(size_t)at] > J.probit_threshold ? 1.0 : -1.0) : cells.vals[(size_t)at];
-            }
+        observed_cells(J, cells, out.q, out.c, out.y);
+        out.lpd.resize(n1); out.pw.resize(n1); out.mean.resize(n1); out.std.resize(n1);
         check(bpmf_hip_score_cells(users, movies, J.mean_m, (int64_t)n, out.q.data(), out.c.data(), out.y.data(), n ? w : nullptr, n ? flag : nullptr, kind,
                                    J.robust_nu, (int)J.sc_alpha.size(), J.sc_alpha.data(), out.lpd.data(), out.pw.data(), out.mean.data(), out.std.data()));
         out.q.resize(n); out.c.resize(n); out.y.resize(n); out.lpd.resize(n); out.pw.resize(n); out.mean.resize(n); out.std.resize(n);
@@ -787,6 +808,58 @@ void print_score(std::ostream &os, const Job &J)
                  e.empty() ? NAN : 100.0 * (double)above / (double)e.size());
         os << buf << std::endl;
     }
+}
+
+// --loo over the sample rings of both sides: after the chain or from a loaded model, for the training cells with the
+// weights and censoring flags of the run, under the likelihood serve_score names; J.sc_alpha holds the alpha of the kept samples.
+void serve_loo(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc &train)
+{
+    if (!J.loo) return;                                              // one rank (main refuses -g)
+    const double t0 = tick();
+    const int kind = J.probit ? BPMF_HIP_LOGDENS_PROBIT : J.robust ? BPMF_HIP_LOGDENS_STUDENT : BPMF_HIP_LOGDENS_GAUSSIAN;
+    const size_t n = (size_t)train.nnz(), n1 = std::max<size_t>(n, 1);
+    std::vector<int32_t> q, c;
+    std::vector<double> y;
+    observed_cells(J, train, q, c, y);
+    J.loo_elpd.resize(n1); J.loo_khat.resize(n1); J.loo_lpd.resize(n1);
+    check(bpmf_hip_loo_cells(users, movies, J.mean_m, (int64_t)n, q.data(), c.data(), y.data(), n && J.weighted && !J.implicit ? J.w_m.data() : nullptr,
+                             n && J.censored ? J.cens_m.data() : nullptr, kind, J.robust_nu, (int)J.sc_alpha.size(), J.sc_alpha.data(), J.loo_elpd.data(),
+                             J.loo_khat.data(), J.loo_lpd.data(), nullptr, nullptr));
+    J.loo_elpd.resize(n); J.loo_khat.resize(n); J.loo_lpd.resize(n);
+    J.loo_samples = bpmf_hip_side_samples_count(users);
+    std::cerr << "loo: " << n << " training cells over " << J.loo_samples << " samples, " << (tick() - t0) * 1e3 << " ms" << std::endl;
+}
+
+// DIR/loo-elpd.sdm and DIR/loo-khat.sdm: elpd_loo and khat of every training cell in the training matrix's original numbering (like
+// waic-elpd.sdm); an infinite khat is written as inf
+void write_loo(const Job &J, const Csc &train)
+{
+    if (!J.loo || J.odirname.empty() || J.loo_elpd.empty()) return;
+    try {
+        for (int which = 0; which < 2; ++which) {
+            Csc P = train;
+            P.vals = which ? J.loo_khat : J.loo_elpd;
+            if (!J.perm_m.empty()) P = permute(P, inverse(J.perm_m), J.perm_u);
+            bpmf::io::write_sparse(J.odirname + (which ? "/loo-khat.sdm" : "/loo-elpd.sdm"), P);
+        }
+    } catch (const std::exception &e) { die(e.what()); }
+}
+
+// the Final line of --loo (bpmf_amd.loo_summary computes the same figures)
+void print_loo(std::ostream &os, const Job &J)
+{
+    if (!J.loo) return;
+    const size_t n = J.loo_elpd.size();
+    double s = 0.0, v = 0.0, p = 0.0;
+    size_t above = 0;
+    for (size_t i = 0; i < n; ++i) { s += J.loo_elpd[i]; p += J.loo_lpd[i] - J.loo_elpd[i]; above += J.loo_khat[i] > 0.7; }
+    const double m = n ? s / (double)n : 0.0;
+    for (double e : J.loo_elpd) v += (e - m) * (e - m);
+    const double se = n > 1 ? std::sqrt((double)n * (v / (double)(n - 1))) : 0.0;
+    char buf[512];
+    snprintf(buf, sizeof buf, "Final PSIS-LOO: looic %.4f elpd %.4f p_loo %.4f se %.4f (%lld cells, %d samples, %.2f%% with k > 0.7)", -2.0 * s, s, p, se,
+             (long long)n, J.loo_samples, n ? 100.0 * (double)above / (double)n : NAN);
+    os << buf << std::endl;
 }
 
 // --intervals over the sample rings of both sides: after the chain or from a loaded model, for the cells of `cells`
@@ -1109,7 +1182,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     }
     // a ring of the post-burn-in samples of a side: --topn, or the candidates of the other side's new entities
     const bool saving = !J.save_model.empty();
-    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty(), ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty();
+    const bool ring_m = J.topn > 0 || J.new_u.n > 0 || J.fold_u.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && !J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty() || J.loo, ring_u = J.topn > 0 || J.new_m.n > 0 || J.fold_m.n > 0 || J.rank_eval > 0 || saving || (J.similar > 0 && J.similar_by_rows) || J.diagnose || J.score || !J.iv_levels.empty() || J.loo;
     if (ring_m) check(bpmf_hip_side_samples_reserve(movies, J.nsims - J.burnin));
     if (ring_u) check(bpmf_hip_side_samples_reserve(users, J.nsims - J.burnin));
     // fold-in: the hyper-parameters every kept iteration of the side ran with, beside the other side's ring
@@ -1232,6 +1305,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         for (double l : J.iv_levels) os << " " << level_name(l) << "%";
         os << ", and the calibration of their held-out values" << std::endl;
     }
+    if (J.loo) os << "loo: PSIS-LOO cross-validation of the training cells" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -1293,7 +1367,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     // (--rank-eval keeps the samples in the rings, which the loop below fills)
     // (--bias: the evaluation of an iteration reads the bias vectors the next one overwrites -- the blocking loop)
     // (--diagnose keeps the samples in the rings too)
-    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose && !J.score && J.iv_levels.empty()) {
+    if (J.odirname.empty() && !J.verbose && !linked && !J.implicit && J.rank_eval == 0 && !saving && !J.bias && !J.diagnose && !J.score && J.iv_levels.empty() && !J.loo) {
         // Plain sampling run: the loop of c++/bpmf.cpp:180-198 software-pipelined by one half-iteration.
         // The library only enqueues in bpmf_hip_sys_sample; the line of iteration i-1 (its RMSE sums
         // and norms) is collected after iteration i has been queued, so the device
@@ -1479,12 +1553,13 @@ void rank_main(Job &J, int rank, std::ostream &os)
         for (const std::vector<double> &t : J.dg_trace) tr.insert(tr.end(), t.begin(), t.end());
         check(bpmf_hip_diag_traces(ctx, 3, (int)S, tr.data(), rh.data(), J.dg_trace_ess));
     }
-    if (J.score || !J.iv_levels.empty()) {                           // the alpha every kept iteration ran with
+    if (J.score || !J.iv_levels.empty() || J.loo) {                  // the alpha every kept iteration ran with
         J.sc_alpha.clear();
         if (J.adaptive) for (int it = burnin; it < nsims; ++it) J.sc_alpha.push_back(J.alpha_trace[(size_t)it]);
         else J.sc_alpha.push_back(J.probit ? 1.0 : J.alpha);
         serve_score(J, users, movies, J.T.nnz() > 0 ? &J.T : nullptr, &J.M);     // (no test cell: no test line)
         serve_intervals(J, users, movies, J.T);
+        serve_loo(J, users, movies, J.M);
     }
     // the new entities against every column of the other side, in query ranges: the device holds one range's block at a time
     auto predict_new = [&](bpmf_hip_side *side, bpmf_hip_side *cand, Job::NewRows &N, int64_t nc, bool by_new) {
@@ -1655,6 +1730,9 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
     if (J.score && m.S < 2) die("--score needs at least 2 samples, the model " + dir + " holds " + std::to_string(m.S));
     if (J.score && !m.probit && !(m.alpha > 0.0) && !m.hyper) die("--score needs a model with alpha > 0 (the noise precision of its likelihood)");
+    if (J.loo && (m.S < 2 || m.S > BPMF_HIP_LOO_MAX_SAMPLES))
+        die("--loo needs 2 .. " + std::to_string(BPMF_HIP_LOO_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
+    if (J.loo && !m.probit && !(m.alpha > 0.0) && !m.hyper) die("--loo needs a model with alpha > 0 (the noise precision of its likelihood)");
     if (!J.iv_levels.empty() && m.probit) die("--intervals: " + dir + " is a probit model (its predictive is a probability, not an interval)");
     if (!J.iv_levels.empty() && m.S > BPMF_HIP_INTERVAL_MAX_SAMPLES)
         die("--intervals takes at most " + std::to_string(BPMF_HIP_INTERVAL_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
@@ -1756,13 +1834,14 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     serve_rank(J, users, movies);
     serve_similar(J, users, movies);
     serve_diag(J, users, movies, P);                                 // --predict FILE --diagnose: FILE's cells
-    if (J.score || !J.iv_levels.empty()) {                           // --predict FILE --score / --intervals: FILE's values are the observations; -n TRAIN: its WAIC
+    if (J.score || !J.iv_levels.empty() || J.loo) {                  // --predict FILE --score / --intervals: FILE's values are the observations; -n TRAIN: its WAIC
         J.probit_threshold = m.probit_threshold;
         J.sc_alpha.clear();
         if (m.hyper && !m.probit) for (size_t sm = 0; sm < (size_t)m.S; ++sm) J.sc_alpha.push_back(m.Uh[sm * (1 + (size_t)K + (size_t)K * K)]);
         else J.sc_alpha.push_back(m.probit ? 1.0 : m.alpha);
         serve_score(J, users, movies, predict_file.empty() ? nullptr : &P, fname.empty() ? nullptr : &J.M);
         serve_intervals(J, users, movies, P);
+        serve_loo(J, users, movies, J.M);
     }
     serve_fold(J, users, movies);
     bpmf_hip_side_destroy(movies);
@@ -1777,6 +1856,8 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     print_score(std::cout, J);
     write_intervals(J);
     print_intervals(std::cout, J);
+    write_loo(J, J.M);
+    print_loo(std::cout, J);
     const RankMetrics rkm = write_ranks(J);
     write_new(J, J.fold_u, true, nmovies, "foldin");
     write_new(J, J.fold_m, false, nusers, "foldin");
@@ -1828,6 +1909,7 @@ int main(int argc, char *argv[])
                                               {"bias-prior", required_argument, nullptr, 1092},
                                               {"diagnose", no_argument, nullptr, 1100},
                                               {"score", no_argument, nullptr, 1101}, {"intervals", required_argument, nullptr, 1102},
+                                              {"loo", no_argument, nullptr, 1103},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
     std::string bias_lambda, bias_prior;
@@ -1904,6 +1986,7 @@ int main(int argc, char *argv[])
         case 1100: J.diagnose = true; break;
         case 1101: J.score = true; break;
         case 1102: intervals = optarg; intervals_given = true; break;
+        case 1103: J.loo = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -1971,6 +2054,18 @@ int main(int argc, char *argv[])
         if (model_given && !predict_given && fname.empty()) die("--score with --model needs --predict FILE (held-out cells with their values) or -n TRAIN (the cells of WAIC)");
         if (!model_given && J.nsims - J.burnin < 2) die("--score needs at least 2 post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
     }
+    // --loo: refused before anything touches a GPU
+    if (J.loo) {
+        if (tensor_given) die("--loo does not go together with --tensor (the scored likelihoods are those of a matrix model)");
+        if (J.ordinal) die("--loo does not go together with --ordinal (its likelihood over levels is not among the scored ones)");
+        if (J.implicit) die("--loo does not go together with --implicit (its likelihood runs over every cell of the matrix)");
+        if (g_given || ngpu >= 1) die("--loo runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (the sample ring of a sharded side is not complete)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--loo does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--loo does not go together with a propagated posterior (-m / -l)");
+        if (model_given && fname.empty()) die("--loo with --model needs -n TRAIN (the training cells are what is cross-validated)");
+        if (!model_given && (J.nsims - J.burnin < 2 || J.nsims - J.burnin > BPMF_HIP_LOO_MAX_SAMPLES))
+            die("--loo needs 2 .. " + std::to_string(BPMF_HIP_LOO_MAX_SAMPLES) + " post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
+    }
     // --intervals: refused before anything touches a GPU
     if (intervals_given) {
         const std::string expects = "--intervals expects 1 .. 4 distinct levels in [0.01, 0.998] separated by commas, not '" + intervals + "'";
@@ -2024,7 +2119,7 @@ int main(int argc, char *argv[])
         if (J.topn > 0 && fname.empty()) die("--topn with --model needs -n TRAIN (the rated cells are what the lists exclude)");
         if (rank_eval_given && fname.empty()) die("--rank-eval with --model needs -n TRAIN (the rated cells are what the ranks exclude)");
         if (rank_eval_given && probename.empty()) die("--rank-eval with --model needs -p TEST (the held-out cells)");
-        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty() && !similar_given && !J.score)
+        if (!predict_given && J.topn < 1 && !rank_eval_given && fold_in_rows.empty() && fold_in_cols.empty() && !similar_given && !J.score && !J.loo)
             die("--model: nothing to do (--predict FILE, --topn N, --rank-eval N, --similar N, --fold-in-rows FILE or --fold-in-cols FILE)");
         if (J.odirname.empty()) die("--model needs -o DIR (the results go to files in DIR)");
     }
@@ -2745,6 +2840,7 @@ int main(int argc, char *argv[])
     write_diag(J);
     write_score(J, &J.T, &J.M);
     write_intervals(J);
+    write_loo(J, J.M);
 
     const RankMetrics rkm = write_ranks(J);
 
@@ -2831,6 +2927,7 @@ int main(int argc, char *argv[])
     print_diag(os, J, true);
     print_score(os, J);
     print_intervals(os, J);
+    print_loo(os, J);
     if (J.ordinal && !J.cat_prob.empty()) {
         os << "Final ordinal RMSE: " << J.ord_rmse << std::endl;
         os << "Final accuracy: " << J.ord_accuracy << std::endl;

@@ -15,9 +15,12 @@
 //   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells
 //                      (bpmf_hip_predict_cells); what the cell lists share: their checks, their sort and their batches (CellsPlan)
 //   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
-//   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells)
+//   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells); what it
+//                      shares with capi_loo.hip: the refusals of a likelihood's arguments and its per-sample constants (logdens_check_args, logdens_constants)
 //   capi_interval.hip  predictive intervals: the probability integral transform and quantiles of the posterior predictive mixture of a list of cells
 //                      (bpmf_hip_interval_cells) and of host traces (bpmf_hip_interval_traces)
+//   capi_loo.hip       PSIS-LOO cross-validation: Pareto-smoothed importance sampling of the log densities of a list of observed cells
+//                      (bpmf_hip_loo_cells) and of host traces (bpmf_hip_loo_traces)
 //   capi_noise.hip     training residuals and the draw of the noise precision (adaptive noise)
 //   capi_probit.hip    probit likelihood: latent scores ahead of every sampler launch, predictive probabilities, AUC
 //   capi_ordinal.hip   ordinal probit likelihood: latent scores between the cutpoints of their level, the Metropolis-Hastings step of the cutpoints, level probabilities
@@ -192,6 +195,14 @@ struct CellsPlan {
 // cells of a batch whose traces (S doubles per cell) fill the trace buffer of 256 MiB, or `forced` if > 0 (capi_diag.hip): what
 // bpmf_hip_diag_cells / _traces and bpmf_hip_interval_cells / _traces cut their lists by
 int64_t trace_batch_cells(int S, int forced);
+
+// The likelihood of a list of observed cells (capi_score.hip): what bpmf_hip_score_cells and bpmf_hip_loo_cells share.  logdens_check_args
+// refuses, as `who` and on the host alone, an unknown kind, a NULL alpha, a NULL y or output (null_output) with n > 0, flags or weights
+// beside a kind that is not Gaussian, nu, nalpha < 1, an alpha, y, w or flag out of range.  logdens_constants: c0 | as | sa of
+// kernels_score.h, S doubles each.
+int logdens_check_args(const std::string &who, int64_t n, const int32_t *q, const int32_t *cc, const double *y, const double *w, const int8_t *flag,
+                       int kind, double nu, int nalpha, const double *alpha, bool null_output);
+std::vector<double> logdens_constants(int kind, double nu, int nalpha, const double *alpha, int S);
 
 // Phi^-1(p), 0 < p < 1: Newton on Phi(x) - p from 0 in the variable that keeps the tail resolved (p <= 1/2 by symmetry), each
 // step limited to 1; the start of the default cutpoints (capi_ordinal.hip) and the z of a quantile's bracket (capi_interval.hip)

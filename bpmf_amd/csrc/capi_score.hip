@@ -18,6 +18,44 @@ std::string cell_name(int64_t i, const int32_t *q, const int32_t *cc)
 
 }  // namespace
 
+int bpmf_capi::logdens_check_args(const std::string &who, int64_t n, const int32_t *q, const int32_t *cc, const double *y, const double *w, const int8_t *flag,
+                                  int kind, double nu, int nalpha, const double *alpha, bool null_output)
+{
+    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && kind != BPMF_HIP_LOGDENS_STUDENT && kind != BPMF_HIP_LOGDENS_PROBIT)
+        return fail(BPMF_HIP_EINVAL, who + ": unknown kind " + std::to_string(kind) + " (BPMF_HIP_LOGDENS_GAUSSIAN, _STUDENT, _PROBIT)");
+    if (!alpha) return fail(BPMF_HIP_EINVAL, who + ": NULL alpha");
+    if (n > 0 && (!y || null_output)) return fail(BPMF_HIP_EINVAL, who + ": NULL argument");
+    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && flag) return fail(BPMF_HIP_EINVAL, who + ": censoring flags go with the gaussian kind alone");
+    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && w) return fail(BPMF_HIP_EINVAL, who + ": weights go with the gaussian kind alone");
+    if (kind == BPMF_HIP_LOGDENS_STUDENT && !(std::isfinite(nu) && nu >= 1.0))
+        return fail(BPMF_HIP_EINVAL, who + ": the degrees of freedom nu must be finite and >= 1");
+    if (nalpha < 1) return fail(BPMF_HIP_EINVAL, who + ": nalpha must be 1 or the number of samples");
+    for (int s = 0; s < nalpha; ++s)
+        if (!(std::isfinite(alpha[s]) && alpha[s] > 0.0))
+            return fail(BPMF_HIP_EINVAL, who + ": alpha of sample " + std::to_string(s) + " is not finite and > 0");
+    for (int64_t i = 0; i < n; ++i) {                                          // before the device is used
+        if (!std::isfinite(y[i])) return fail(BPMF_HIP_EINVAL, who + ": the value of " + cell_name(i, q, cc) + " is not finite");
+        if (w && !(std::isfinite(w[i]) && w[i] > 0.0)) return fail(BPMF_HIP_EINVAL, who + ": the weight of " + cell_name(i, q, cc) + " is not finite and > 0");
+        if (flag && (flag[i] < -1 || flag[i] > 1))
+            return fail(BPMF_HIP_EINVAL, who + ": the flag " + std::to_string((int)flag[i]) + " of " + cell_name(i, q, cc) + " is not -1, 0 or +1");
+    }
+    return 0;
+}
+
+std::vector<double> bpmf_capi::logdens_constants(int kind, double nu, int nalpha, const double *alpha, int S)
+{
+    std::vector<double> cst((size_t)3 * (size_t)S);
+    const double kPi = 3.14159265358979323846;
+    const double lg = kind == BPMF_HIP_LOGDENS_STUDENT ? std::lgamma(0.5 * (nu + 1.0)) - std::lgamma(0.5 * nu) : 0.0;
+    for (int s = 0; s < S; ++s) {
+        const double al = alpha[nalpha == 1 ? 0 : s];
+        cst[(size_t)s] = kind == BPMF_HIP_LOGDENS_STUDENT ? lg + 0.5 * std::log(al / (nu * kPi)) : 0.5 * std::log(al / (2.0 * kPi));
+        cst[(size_t)S + s] = kind == BPMF_HIP_LOGDENS_STUDENT ? al / nu : al;
+        cst[(size_t)2 * S + s] = std::sqrt(al);
+    }
+    return cst;
+}
+
 extern "C" int bpmf_hip_score_batch_cells(int cells)
 {
     if (cells < 0) return fail(BPMF_HIP_EINVAL, "score_batch_cells: the cells per batch must be >= 0 (0: automatic)");
@@ -30,24 +68,7 @@ extern "C" int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, d
                                     double *lpd_out, double *pw_out, double *mean_out, double *std_out)
 {
     { const int rc = cells_check_list("score_cells", query, cand, mean_rating, n, q, cc); if (rc) return rc; }
-    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && kind != BPMF_HIP_LOGDENS_STUDENT && kind != BPMF_HIP_LOGDENS_PROBIT)
-        return fail(BPMF_HIP_EINVAL, "score_cells: unknown kind " + std::to_string(kind) + " (BPMF_HIP_LOGDENS_GAUSSIAN, _STUDENT, _PROBIT)");
-    if (!alpha) return fail(BPMF_HIP_EINVAL, "score_cells: NULL alpha");
-    if (n > 0 && (!y || !lpd_out || !pw_out || !mean_out || !std_out)) return fail(BPMF_HIP_EINVAL, "score_cells: NULL argument");
-    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && flag) return fail(BPMF_HIP_EINVAL, "score_cells: censoring flags go with the gaussian kind alone");
-    if (kind != BPMF_HIP_LOGDENS_GAUSSIAN && w) return fail(BPMF_HIP_EINVAL, "score_cells: weights go with the gaussian kind alone");
-    if (kind == BPMF_HIP_LOGDENS_STUDENT && !(std::isfinite(nu) && nu >= 1.0))
-        return fail(BPMF_HIP_EINVAL, "score_cells: the degrees of freedom nu must be finite and >= 1");
-    if (nalpha < 1) return fail(BPMF_HIP_EINVAL, "score_cells: nalpha must be 1 or the number of samples");
-    for (int s = 0; s < nalpha; ++s)
-        if (!(std::isfinite(alpha[s]) && alpha[s] > 0.0))
-            return fail(BPMF_HIP_EINVAL, "score_cells: alpha of sample " + std::to_string(s) + " is not finite and > 0");
-    for (int64_t i = 0; i < n; ++i) {                                          // before the device is used
-        if (!std::isfinite(y[i])) return fail(BPMF_HIP_EINVAL, "score_cells: the value of " + cell_name(i, q, cc) + " is not finite");
-        if (w && !(std::isfinite(w[i]) && w[i] > 0.0)) return fail(BPMF_HIP_EINVAL, "score_cells: the weight of " + cell_name(i, q, cc) + " is not finite and > 0");
-        if (flag && (flag[i] < -1 || flag[i] > 1))
-            return fail(BPMF_HIP_EINVAL, "score_cells: the flag " + std::to_string((int)flag[i]) + " of " + cell_name(i, q, cc) + " is not -1, 0 or +1");
-    }
+    { const int rc = logdens_check_args("score_cells", n, q, cc, y, w, flag, kind, nu, nalpha, alpha, !lpd_out || !pw_out || !mean_out || !std_out); if (rc) return rc; }
     bpmf_launch::ScoreCellsLaunch sl{};
     bpmf_launch::PredCellsLaunch &p = sl.cells;
     int rc;
@@ -59,16 +80,7 @@ extern "C" int bpmf_hip_score_cells(bpmf_hip_side *query, bpmf_hip_side *cand, d
     bpmf_hip_ctx *c = query->ctx;
     Timed &timed = query->ring->score;
 
-    // the per-sample constants (kernels_score.h): c0 | as | sa
-    std::vector<double> cst((size_t)3 * (size_t)S);
-    const double kPi = 3.14159265358979323846;
-    const double lg = kind == BPMF_HIP_LOGDENS_STUDENT ? std::lgamma(0.5 * (nu + 1.0)) - std::lgamma(0.5 * nu) : 0.0;
-    for (int s = 0; s < S; ++s) {
-        const double al = alpha[nalpha == 1 ? 0 : s];
-        cst[(size_t)s] = kind == BPMF_HIP_LOGDENS_STUDENT ? lg + 0.5 * std::log(al / (nu * kPi)) : 0.5 * std::log(al / (2.0 * kPi));
-        cst[(size_t)S + s] = kind == BPMF_HIP_LOGDENS_STUDENT ? al / nu : al;
-        cst[(size_t)2 * S + s] = std::sqrt(al);
-    }
+    const std::vector<double> cst = logdens_constants(kind, nu, nalpha, alpha, S);     // c0 | as | sa
     std::vector<int8_t> sign;                                                  // probit: the label of a cell as the kernel's flag
     if (kind == BPMF_HIP_LOGDENS_PROBIT) {
         sign.resize((size_t)n);

@@ -138,6 +138,7 @@ struct bpmf_ring {
     Timed diag;                              // around the kernels of the newest bpmf_hip_diag_cells with the side as the queries (bpmf_hip_diag_last_ms)
     Timed score;                             // around the kernels of the newest bpmf_hip_score_cells with the side as the queries (bpmf_hip_score_last_ms)
     Timed interval;                          // around the kernels of the newest bpmf_hip_interval_cells with the side as the queries (bpmf_hip_interval_last_ms)
+    Timed loo;                               // around the kernels of the newest bpmf_hip_loo_cells with the side as the queries (bpmf_hip_loo_last_ms)
 };
 
 // rows unseen in training (capi_newrows.hip): the features of n new entities of a side with features, as

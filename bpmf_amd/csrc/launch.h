@@ -262,6 +262,20 @@ int interval_max_samples();
 int interval_max_quantiles();
 int trace_quantiles(const TraceQuantLaunch &p, hipStream_t st);   // -1: shape not supported (nothing launched)
 
+// PSIS-LOO (kernels_loo.h, kloo.hip): Pareto-smoothed importance sampling of ntr traces of S samples (row-major, on the device), to
+// elpd[orig[t]], khat[orig[t]] and lpd[orig[t]] (orig NULL: [t]).  kind -1: the traces hold the log densities l_s.  Else BPMF_HIP_LOGDENS_*:
+// they hold what cell_traces stores, and l_s is formed from it as score_cells forms it -- y, w (NULL: 1) and flag (NULL: none; probit:
+// the sign of the label, never NULL) are read at the same places, c0 / as / sa are the per-sample constants of kernels_score.h.
+struct TracePsisLaunch {
+    const double *traces; int64_t ntr; int S; const int32_t *orig;
+    int kind; double nu, mean_rating;
+    const double *y, *w; const int8_t *flag;
+    const double *c0, *as, *sa;
+    double *elpd, *khat, *lpd;
+};
+int loo_max_samples();
+int trace_psis(const TracePsisLaunch &p, hipStream_t st);   // -1: shape or kind not supported (nothing launched)
+
 // model comparison (kernels_score.h, kscore.hip): predict_cells' walk of one batch of sorted cells (`cells`; want_prob, t, sigma and
 // prob are not read), which also turns every cell's S predictions into the log pointwise predictive density and the variance of the
 // log density.  kind: BPMF_HIP_LOGDENS_*; y, w (NULL: 1) and flag (NULL: none; probit: the sign of the label, never NULL) are in the

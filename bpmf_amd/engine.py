@@ -469,6 +469,71 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_interval_last_ms(query.handle, C.byref(ms)))
         return ms.value
 
+    # -- PSIS-LOO ------------------------------------------------------------------
+    LOO_MAX_SAMPLES = 4096
+
+    def loo_traces(self, L, want_lpd=True):
+        """dict(elpd_loo, khat, lpd), [n] each, of the n traces L [n, S] (one trace: [S]) of log densities l_s, 1 <= S <= 4096, by
+        Pareto-smoothed importance sampling: the leave-one-out log predictive density, the shape khat of the
+        generalised Pareto distribution fitted to the tail of the importance ratios (+inf where nothing is smoothed: S < 25, a
+        constant tail) and lpd = log mean_s exp l_s (None without want_lpd).  A trace holding a value that is not finite gives NaN."""
+        L = np.ascontiguousarray(L, np.float64)
+        if L.ndim == 1:
+            L = L[None, :]
+        if L.ndim != 2:
+            raise ValueError("loo_traces: L must be [n, S]")
+        n, S = L.shape
+        elpd = np.empty(n); khat = np.empty(n); lpd = np.empty(n) if want_lpd else None
+        hold = np.zeros(1)
+        _lib.check(self.lib.bpmf_hip_loo_traces(self.ctx, n, S, _ptr(L if L.size else hold), _ptr(elpd if n else hold), _ptr(khat if n else hold),
+                                                None if lpd is None else _ptr(lpd if n else hold)))
+        return dict(elpd_loo=elpd, khat=khat, lpd=lpd)
+
+    def loo_cells(self, query, cand, mean_rating, q, c, y, alpha, kind="gaussian", nu=0.0, w=None, flag=None, want=("lpd", "mean", "std")):
+        """dict(elpd_loo, khat, lpd, mean, std), [n] each, of the observed cells (q[i], c[i]) with the values y[i] over the S <= 4096
+        samples of the two rings: loo_traces's rule on the log densities score_cells's likelihoods give the
+        cell under every sample (kind, nu, w, flag and alpha as there); lpd is score_cells's up to rounding, mean and std are
+        predict_cells's, bit for bit.  want: which of lpd, mean and std are read back (the others are None)."""
+        if kind not in self.LOGDENS_KINDS:
+            raise ValueError("loo_cells: kind must be one of %s, not %r" % (sorted(self.LOGDENS_KINDS), kind))
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32); y = np.ascontiguousarray(y, np.float64)
+        if q.ndim != 1 or q.shape != c.shape or y.shape != q.shape:
+            raise ValueError("loo_cells: q, c and y must be one-dimensional and of the same length")
+        n = len(q)
+        alpha = np.ascontiguousarray(np.atleast_1d(alpha), np.float64)
+        if alpha.ndim != 1 or len(alpha) < 1:
+            raise ValueError("loo_cells: alpha must be one number or one per sample")
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            if w.shape != q.shape:
+                raise ValueError("loo_cells: w must have one weight per cell")
+        if flag is not None:
+            flag = np.ascontiguousarray(flag, np.int8)
+            if flag.shape != q.shape:
+                raise ValueError("loo_cells: flag must have one flag per cell")
+        out = dict(elpd_loo=np.empty(n), khat=np.empty(n))
+        for name in ("lpd", "mean", "std"):
+            out[name] = np.empty(n) if name in want else None
+        hold = np.zeros(1, np.int32)
+
+        def opt(a):
+            return None if a is None else _ptr(a if n else np.zeros(1, a.dtype))
+        _lib.check(self.lib.bpmf_hip_loo_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
+                                               _ptr(y if n else np.zeros(1)), opt(w), opt(flag), self.LOGDENS_KINDS[kind], float(nu), len(alpha),
+                                               _ptr(alpha), *[opt(out[name]) for name in ("elpd_loo", "khat", "lpd", "mean", "std")]))
+        return out
+
+    def loo_batch_cells(self, cells):
+        """Cells per batch of loo_cells and loo_traces (0: automatic, from the size of the trace buffer).  For tests: results do not
+        depend on it."""
+        _lib.check(self.lib.bpmf_hip_loo_batch_cells(int(cells)))
+
+    def loo_last_ms(self, query):
+        """Device time of the kernels of the newest loo_cells with `query` as the queries, between two events (tools/loo_bench.py)."""
+        ms = C.c_float()
+        _lib.check(self.lib.bpmf_hip_loo_last_ms(query.handle, C.byref(ms)))
+        return ms.value
+
     def topn(self, query, cand, mean_rating, n, q_from=0, q_to=None, exclude_rated=True):
         """The n best columns of `cand` by posterior-mean score for every column q_from .. q_to - 1 of `query`:
         (idx int32[nq, n], mean f64[nq, n], std f64[nq, n]); empty slots have idx -1, mean 0, std 0."""

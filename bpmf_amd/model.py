@@ -212,14 +212,51 @@ def score_summary(d):
 def score_compare(a, b):
     """Two models scored on the same cells, `a` and `b` = dict(lpd, pwaic) in the same order: dict(n, elpd_diff, elpd_se, lpd_diff,
     lpd_se) with the differences a - b of the sums and their paired standard errors sqrt(n var_i(a_i - b_i)).  A positive
-    difference of more than a few standard errors says that `a` predicts these cells better."""
-    la, lb = np.asarray(a["lpd"], np.float64), np.asarray(b["lpd"], np.float64)
-    if la.shape != lb.shape or la.ndim != 1:
+    difference of more than a few standard errors says that `a` predicts these cells better.  PSIS-LOO results compare the same way:
+    `a` and `b` = dict(elpd_loo, lpd) (bpmf_amd.loo_cells), or the two per-cell elpd_loo arrays themselves, which give dict(n,
+    elpd_diff, elpd_se) alone."""
+    def per_cell(d):
+        if not isinstance(d, dict):
+            return np.asarray(d, np.float64), None
+        lpd = np.asarray(d["lpd"], np.float64) if d.get("lpd") is not None else None
+        if "pwaic" in d:
+            return lpd - np.asarray(d["pwaic"], np.float64), lpd
+        return np.asarray(d["elpd_loo"], np.float64), lpd
+    (ea, la), (eb, lb) = per_cell(a), per_cell(b)
+    if ea.shape != eb.shape or ea.ndim != 1 or (la is None) != (lb is None):
         raise ValueError("score_compare: the two results must cover the same cells")
-    ea, eb = la - np.asarray(a["pwaic"], np.float64), lb - np.asarray(b["pwaic"], np.float64)
     elpd_diff, elpd_se = _sum_se(ea - eb)
+    if la is None:
+        return dict(n=int(len(ea)), elpd_diff=elpd_diff, elpd_se=elpd_se)
     lpd_diff, lpd_se = _sum_se(la - lb)
     return dict(n=int(len(la)), elpd_diff=elpd_diff, elpd_se=elpd_se, lpd_diff=lpd_diff, lpd_se=lpd_se)
+
+
+def _likelihood(who, res, values, weights, flags):
+    """(S, y, alpha, kind, nu) of the likelihood `res` ran with, for the observed values: what score_cells and loo_cells hand to the engine."""
+    info = res.get("model_info")
+    if info is None:
+        raise ValueError("%s: the result carries no model_info (it comes from gibbs or load_model)" % who)
+    if not info.get("scored", True):
+        raise ValueError("%s: ordinal and implicit runs are not scored" % who)
+    S = res["users"].engine.samples_count(res["users"].side)
+    y = np.ascontiguousarray(values, np.float64)
+    alpha = info.get("alpha_samples")
+    if alpha is None:
+        alpha = float(info.get("alpha", float("nan")))
+    elif len(alpha) != S:
+        raise ValueError("%s: model_info has %d values of alpha for %d kept samples" % (who, len(alpha), S))
+    nu = info.get("nu")
+    if info.get("probit"):
+        kind, nu, alpha = "probit", 0.0, 1.0
+        y = np.where(y > float(info.get("probit_threshold", 0.0)), 1.0, -1.0)
+    elif nu is not None:
+        kind = "student"
+    else:
+        kind, nu = "gaussian", 0.0
+    if kind != "gaussian" and (weights is not None or flags is not None):
+        raise ValueError("%s: weights and flags go with the Gaussian likelihood alone, this run is %s" % (who, kind))
+    return S, y, alpha, kind, nu
 
 
 def score_cells(res, rows, cols, values, weights=None, flags=None):
@@ -234,33 +271,53 @@ def score_cells(res, rows, cols, values, weights=None, flags=None):
     gibbs gave them to the training cells; flags: int8, +-1 for a censored value (the value is then a bound, as censored= of gibbs);
     both Gaussian only, None for held-out cells."""
     users, movies = res["users"], res["movies"]
-    info = res.get("model_info")
-    if info is None:
-        raise ValueError("score_cells: the result carries no model_info (it comes from gibbs or load_model)")
-    if not info.get("scored", True):
-        raise ValueError("score_cells: ordinal and implicit runs are not scored")
+    S, y, alpha, kind, nu = _likelihood("score_cells", res, values, weights, flags)
     engine = users.engine
-    S = engine.samples_count(users.side)
     rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
-    y = np.ascontiguousarray(values, np.float64)
-    alpha = info.get("alpha_samples")
-    if alpha is None:
-        alpha = float(info.get("alpha", float("nan")))
-    elif len(alpha) != S:
-        raise ValueError("score_cells: model_info has %d values of alpha for %d kept samples" % (len(alpha), S))
-    nu = info.get("nu")
-    if info.get("probit"):
-        kind, nu, alpha = "probit", 0.0, 1.0
-        y = np.where(y > float(info.get("probit_threshold", 0.0)), 1.0, -1.0)
-    elif nu is not None:
-        kind = "student"
-    else:
-        kind, nu = "gaussian", 0.0
-    if kind != "gaussian" and (weights is not None or flags is not None):
-        raise ValueError("score_cells: weights and flags go with the Gaussian likelihood alone, this run is %s" % kind)
     d = engine.score_cells(users.side, movies.side, movies.mean_rating, rows, cols, y, alpha, kind, nu, weights, flags)
     d.update(rows=rows, cols=cols, samples=S, kind=kind, elpd=d["lpd"] - d["pwaic"])
     d["summary"] = score_summary(d)
+    return d
+
+
+def loo_summary(d):
+    """What one line says of the per-cell PSIS-LOO results `d` = dict(elpd_loo, khat, lpd) (engine.loo_cells, bpmf_amd.loo_cells):
+    n (cells), elpd_loo (the sum) and se = sqrt(n var_i elpd_loo_i) (var with n - 1), p_loo = sum (lpd_i - elpd_loo_i) (the effective
+    number of parameters), looic = -2 elpd_loo, samples (d["samples"] if given, else None), khat_counts = the cells with khat <= 0.5,
+    in (0.5, 0.7], in (0.7, 1], > 1 and finite, and infinite (nothing was smoothed: fewer than 25 samples, or a constant tail), as a
+    dict(good, ok, bad, very_bad, inf), khat_threshold = min(1 - 1 / log10 S, 0.7) (Vehtari et al. 2024; NaN without samples) and
+    khat_above = the share of cells whose khat exceeds it (infinite ones included), khat_above_07 the share above 0.7.  Cells whose
+    khat is NaN (a trace that was not finite) are counted as n_nan and fall in no class.  Without a cell the sums are 0 and the
+    shares NaN."""
+    elpd = np.asarray(d["elpd_loo"], np.float64); khat = np.asarray(d["khat"], np.float64); lpd = np.asarray(d["lpd"], np.float64)
+    n = len(elpd)
+    S = d.get("samples")
+    nan = float("nan")
+    s, se = _sum_se(elpd)
+    thr = nan if S is None else (min(1.0 - 1.0 / math.log10(S), 0.7) if S > 1 else -math.inf)
+    fin = np.isfinite(khat)
+    counts = dict(good=int(np.sum(khat <= 0.5)), ok=int(np.sum((khat > 0.5) & (khat <= 0.7))), bad=int(np.sum((khat > 0.7) & (khat <= 1.0))),
+                  very_bad=int(np.sum(fin & (khat > 1.0))), inf=int(np.sum(np.isposinf(khat))))
+    return dict(n=int(n), samples=S, elpd_loo=s, se=se, p_loo=float((lpd - elpd).sum()), looic=-2.0 * s, khat_counts=counts,
+                n_nan=int(np.sum(np.isnan(khat))), khat_threshold=thr, khat_above=float(np.mean(khat > thr)) if n and S is not None else nan,
+                khat_above_07=float(np.mean(khat > 0.7)) if n else nan)
+
+
+def loo_cells(res, rows, cols, values, weights=None, flags=None):
+    """PSIS-LOO of the observed cells (rows[i], cols[i]) -- user, movie, 0-based -- with the values values[i], over the kept samples of
+    `res` (gibbs with the rings kept, or load_model; 1 .. 4096 samples): dict(rows, cols, elpd_loo, khat, lpd,
+    p_loo, mean, std, samples, kind, summary).  Over the training cells elpd_loo_i estimates the log predictive density cell i would get
+    from a model fitted without it, by Pareto-smoothed importance sampling of the per-sample log densities; khat_i is the shape of the
+    generalised Pareto distribution fitted to the tail of its importance ratios and says whether the estimate can be trusted (<= 0.7;
+    +inf where nothing was smoothed); lpd is score_cells's, p_loo_i = lpd_i - elpd_loo_i; mean and std are predict_cells's; summary =
+    loo_summary of it.  The likelihood, weights and flags are those of score_cells."""
+    users, movies = res["users"], res["movies"]
+    S, y, alpha, kind, nu = _likelihood("loo_cells", res, values, weights, flags)
+    engine = users.engine
+    rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
+    d = engine.loo_cells(users.side, movies.side, movies.mean_rating, rows, cols, y, alpha, kind, nu, weights, flags)
+    d.update(rows=rows, cols=cols, samples=S, kind=kind, p_loo=d["lpd"] - d["elpd_loo"])
+    d["summary"] = loo_summary(d)
     return d
 
 

@@ -198,7 +198,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False, intervals=None):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False, intervals=None, loo=False):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -390,7 +390,25 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     histogram, Kolmogorov distance).  alpha is that of every kept iteration (noise="adaptive": res["alpha"] of that iteration); test
     cells have weight 1; bias terms are part of the rings.  Needs a test matrix and 1 .. 4096 kept samples.  Refused: probit, ordinal,
     implicit, robust (a mixture of Student-t distributions is out of scope), a communicator, BPMF_REDUCE.  None (the default):
-    nothing changes."""
+    nothing changes.
+
+    loo=True: PSIS-LOO cross-validation of the training cells.  The sample rings are kept as for score, and
+    after the chain res["loo"] = bpmf_amd.loo_cells's dict over the cells of M with the run's weights and censoring flags: per
+    training cell elpd_loo (the log predictive density a model fitted without the cell would give it, by Pareto-smoothed importance
+    sampling), khat (the diagnostic that says whether that estimate can be trusted: <= 0.7), lpd, p_loo, and "summary"
+    (bpmf_amd.loo_summary: the sum with its standard error, p_loo, looic = -2 elpd_loo, the khat classes).  It replaces WAIC where the
+    variance of the log density is large (score's "var > 0.4").  The likelihood is score's; so are the refusals: ordinal, implicit, a
+    communicator, BPMF_REDUCE, fewer than 2 kept samples; and more than 4096.  False (the default): nothing changes."""
+    loo_on = bool(loo)
+    if loo_on:                                       # (refused before the engine is used)
+        for on, what, why in ((ordinal is not None and ordinal is not False, "ordinal", "its held-out log density is res['logp']"),
+                              (implicit is not None, "implicit", "its likelihood runs over every cell of the matrix"),
+                              (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator", "the rings of both sides must be whole on one GPU"),
+                              (_os.environ.get("BPMF_REDUCE", "0") not in ("", "0"), "BPMF_REDUCE", "the rings of both sides must be whole on one GPU")):
+            if on:
+                raise ValueError("loo does not go together with %s (%s)" % (what, why))
+        if not (2 <= nsims - burnin <= _engine.HipEngine.LOO_MAX_SAMPLES):
+            raise ValueError("loo needs 2 .. %d post-burn-in samples (nsims - burnin = %d)" % (_engine.HipEngine.LOO_MAX_SAMPLES, nsims - burnin))
     intervals_on = intervals is not None and intervals is not False
     if intervals_on:                                 # (refused before the engine is used)
         from .model import interval_taus as _interval_taus
@@ -751,8 +769,8 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
     res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on or loo_on   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on or loo_on
     hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
@@ -986,6 +1004,11 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         from .model import predict_intervals as _predict_intervals
         t_cols = np.repeat(np.arange(len(T[0]) - 1, dtype=np.int32), np.diff(np.asarray(T[0], np.int64)))
         res["intervals"] = dict(test=_predict_intervals(res, T[1], t_cols, interval_levels, values=T[2]))
+    if loo_on:
+        from .model import loo_cells as _loo_cells
+        m_cols = np.repeat(np.arange(len(M[0]) - 1, dtype=np.int32), np.diff(np.asarray(M[0], np.int64)))
+        res["loo"] = _loo_cells(res, M[1], m_cols, M[2], weights=wts[0] if weights is not None else None,
+                                flags=cflags[0] if censored is not None else None)
     if out is not None:
         out.write("Final Avg RMSE: %g\n" % movies.rmse_avg)
     return res

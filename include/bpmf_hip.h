@@ -549,6 +549,41 @@ BPMF_API int bpmf_hip_interval_traces(bpmf_hip_ctx *ctx, int64_t n, int S, const
 BPMF_API int bpmf_hip_interval_batch_cells(int cells);
 BPMF_API int bpmf_hip_interval_last_ms(const bpmf_hip_side *query, float *ms);
 
+/* ---- PSIS-LOO: leave-one-out cross-validation of observed cells by Pareto-smoothed importance sampling ----
+ * (Vehtari, Gelman & Gabry 2017; Vehtari et al. 2024.)  For one cell, l_s is its log density under kept sample s
+ * (the likelihoods of bpmf_hip_score_cells), s = 0 .. S - 1, 1 <= S <= BPMF_HIP_LOO_MAX_SAMPLES.  Everything is fp64, also on fp32 contexts.
+ *  1. r_s = -l_s, shifted so that max_s r_s = 0; r_(0) <= .. <= r_(S-1) are the sorted values.
+ *  2. The tail length is M = min(floor(0.2 S), ceil(3 sqrt S)) (the relative efficiency is taken as 1; M <= 192).  M < 5 (S < 25): no
+ *     smoothing, khat = +infinity.
+ *  3. The cutoff is c = r_(S-M-1); the tail excesses are x_j = exp(r_(S-M-1+j)) - exp(c), j = 1 .. M, ascending.  x_M = x_1 (a constant
+ *     tail), or x at the index floor(M/4 + 1/2) equal to 0: no smoothing, khat = +infinity.
+ *  4. The generalised Pareto fit of Zhang & Stephens 2009: m = 30 + floor(sqrt M), x* = x at the index floor(M/4 + 1/2) (1-based),
+ *     theta_j = 1 / x_M + (1 - sqrt(m / (j - 1/2))) / (3 x*), j = 1 .. m;  k_j = (1/M) sum_i log1p(-theta_j x_i);
+ *     L_j = M (log(-theta_j / k_j) - k_j - 1);  w_j = exp(L_j - max L) / sum_j exp(L_j - max L);  theta^ = sum_j w_j theta_j;
+ *     k = (1/M) sum_i log1p(-theta^ x_i);  sigma = -k / theta^;  khat = (k M + 5) / (M + 10).  An L_j, theta^, k, sigma or khat that is
+ *     not finite: no smoothing, khat = +infinity.
+ *  5. The smoothed tail: p_j = (j - 1/2) / M, t_j = -log1p(-p_j), q_j = sigma expm1(khat t_j) / khat (sigma t_j for |khat| < 1e-30),
+ *     lw_(S-M-1+j) = min(log(q_j + exp(c)), 0); every other lw_s = r_s.
+ *  6. elpd_loo = logsumexp_s(lw_s + l_s) - logsumexp_s(lw_s);  lpd = logsumexp_s(l_s) - log S;  khat as above.
+ * On the host: p_loo = lpd - elpd_loo and looic = -2 sum elpd_loo.  khat <= 0.7 (for small S: min(1 - 1 / log10 S, 0.7)) says that the
+ * estimate of the cell can be trusted.  Every sum runs over the positions of the sorted order -- a lane adds positions lane, lane + 64, ..
+ * in increasing order, then the 64 lanes add by a butterfly (xor 32 .. 1); the M terms of a k_j are added in increasing i -- so the bits
+ * of a cell depend on the cell, S, the kind and its parameters alone: not on the other cells, its place in the list or the batches
+ * (bpmf_hip_loo_batch_cells sets the cells per batch, 0: automatic, for tests).  No atomics.  A trace holding a value that is not finite
+ * gives NaN in its own three outputs and touches no other trace.
+ * bpmf_hip_loo_cells: the arguments, checks and refusals of bpmf_hip_score_cells (y, w, flag, kind, nu, nalpha, alpha), and S above
+ * BPMF_HIP_LOO_MAX_SAMPLES is refused; lpd, mean and std may be NULL; mean and std are those of bpmf_hip_predict_cells, bit for bit.
+ * n = 0 launches nothing.  Waits.
+ * bpmf_hip_loo_traces: the same rule for n traces of l_s given by the host, row-major (n x S); lpd may be NULL.
+ * bpmf_hip_loo_last_ms: device time of the kernels of the newest bpmf_hip_loo_cells with `query` as the queries. */
+#define BPMF_HIP_LOO_MAX_SAMPLES 4096
+BPMF_API int bpmf_hip_loo_cells(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                const int32_t *c, const double *y, const double *w, const int8_t *flag, int kind, double nu, int nalpha,
+                                const double *alpha, double *elpd_loo, double *khat, double *lpd, double *mean, double *std);
+BPMF_API int bpmf_hip_loo_traces(bpmf_hip_ctx *ctx, int64_t n, int S, const double *logdens, double *elpd_loo, double *khat, double *lpd);
+BPMF_API int bpmf_hip_loo_batch_cells(int cells);
+BPMF_API int bpmf_hip_loo_last_ms(const bpmf_hip_side *query, float *ms);
+
 /* ---- adaptive noise precision -------------------------------------------------
  * SSE = sum over the ratings of `side` (row r, column c, value v) of (v - mean_rating - x_c . y_r)^2, x = side's current
  * factors, y = other's (other has one column per row of side's ratings); *n = the number of those ratings.  fp64 throughout
