@@ -13,6 +13,6 @@ from .weights import rating_weights  # noqa: F401
 from .rank import held_out_lists, rank_metrics  # noqa: F401
 from .io import read_tns, write_tns  # noqa: F401
 from .tensor import tensor_gibbs  # noqa: F401
-from .model import save_model, load_model, predict_cells, read_model, write_model, diagnose, diag_summary, score_cells, score_summary, score_compare, predict_intervals, calibration_summary, loo_cells, loo_summary  # noqa: F401
+from .model import pool_models, run_chains, save_model, load_model, predict_cells, read_model, write_model, diagnose, diag_summary, score_cells, score_summary, score_compare, predict_intervals, calibration_summary, loo_cells, loo_summary  # noqa: F401
 
 __all__ = ["load_library", "library_path", "BpmfHipError", "HipEngine", "auc", "hyper_sample", "Sys", "HyperParams", "gibbs", "fold_in", "censor_flags", "rating_weights", "held_out_lists", "rank_metrics", "read_tns", "write_tns", "tensor_gibbs"]

@@ -71,6 +71,11 @@ _SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     "bpmf_hip_diag_batch_cells": (C.c_int, [C.c_int]),
     "bpmf_hip_diag_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "bpmf_hip_side_set_chain": (C.c_int, [C.c_void_p, C.c_int]),
+    "bpmf_hip_side_chain": (C.c_int, [C.c_void_p]),
+    "bpmf_hip_diag_traces_mc": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpmf_hip_diag_cells_mc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_score_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpmf_hip_score_batch_cells": (C.c_int, [C.c_int]),

@@ -179,6 +179,14 @@ void usage()
               << "              post-burn-in traces of RMSE, FU and FM: four more Final lines and, with -o DIR, DIR/diagnostics.csv\n"
               << "              (row,col,mean,std,rhat,ess,mcse; mcse = std / sqrt(ess)).  Needs 8 <= -i - -b <= 4096; one GPU, no -g; not with\n"
               << "              --tensor, -m / -l or BPMF_REDUCE=1; with --model DIR --predict FILE: the same file for FILE's cells\n"
+              << "  [--diagnose-rank]: --diagnose with the rank-normalised estimator over chains (Vehtari et al. 2021): rank-normalised split-Rhat,\n"
+              << "              bulk and tail ESS; the Final lines read `Final ESS: bulk min .. tail min ..`, `Final rank-Rhat`, and the file is\n"
+              << "              row,col,mean,std,rhat,ess_bulk,ess_tail,mcse.  Accepted wherever --diagnose is; --diagnose under --model D0,D1,..\n"
+              << "              takes it by itself\n"
+              << "  [--chain c]: chain c (0 .. 63) of the model: the same run with its random numbers taken at the half-iteration indices\n"
+              << "              c * 1048576, .. (one process per chain and GPU, each with --save-model DIR_c; --model D0,D1,.. pools them: a\n"
+              << "              directory name with a comma is not supported).  One GPU, no -g; -i <= 1048576; not with features, --ordinal,\n"
+              << "              --bias, --implicit, --tensor, -m / -l or BPMF_REDUCE=1\n"
               << "  [--score]: model comparison: the log posterior predictive density of every test cell (a proper score of held-out data) and\n"
               << "              WAIC over the training cells, under the likelihood of the run: two more Final lines and, with -o DIR,\n"
               << "              DIR/score.csv (row,col,value,lpd,mean,std) and DIR/waic-elpd.sdm.  Needs -i - -b >= 2; one GPU, no -g; not with\n"
@@ -484,6 +492,10 @@ struct Job {
     std::vector<int32_t> dg_q, dg_c;                                 // the cells (user, movie), in the numbering of the run
     std::vector<double> dg_mean, dg_std, dg_rhat, dg_ess;            // per cell
     int dg_samples = 0;                                              // the kept samples behind them
+    bool diag_rank = false;                                          // --diagnose-rank, or --diagnose under a pooled model: the estimator of DESIGN.md section 33
+    int dg_chains = 1;                                               // the chains the rings hold one after the other (--model D0,D1,..)
+    std::vector<double> dg_tail;                                     // per cell: the tail ESS (dg_ess is then the bulk ESS, dg_rhat the rank-normalised one)
+    int chain = -1;                                                  // --chain c (-1: not given)
     std::vector<double> dg_trace[3];                                 // the post-burn-in traces of RMSE, FU, FM
     double dg_trace_ess[3] = {NAN, NAN, NAN};
     bool score = false;                                              // --score: log predictive density of the test cells, WAIC of the training cells
@@ -661,6 +673,12 @@ void serve_diag(Job &J, bpmf_hip_side *users, bpmf_hip_side *movies, const Csc &
         }
     J.dg_mean.resize(std::max<size_t>(n, 1)); J.dg_std.resize(std::max<size_t>(n, 1)); J.dg_rhat.resize(std::max<size_t>(n, 1)); J.dg_ess.resize(std::max<size_t>(n, 1));
     static const int32_t none = 0;
+    if (J.diag_rank) {
+        J.dg_tail.resize(std::max<size_t>(n, 1));
+        check(bpmf_hip_diag_cells_mc(users, movies, J.mean_m, (int64_t)n, n ? J.dg_q.data() : &none, n ? J.dg_c.data() : &none, J.dg_chains, J.dg_mean.data(),
+                                     J.dg_std.data(), J.dg_rhat.data(), J.dg_ess.data(), J.dg_tail.data()));
+        J.dg_tail.resize(n);
+    } else
     check(bpmf_hip_diag_cells(users, movies, J.mean_m, (int64_t)n, n ? J.dg_q.data() : &none, n ? J.dg_c.data() : &none, J.dg_mean.data(), J.dg_std.data(),
                               J.dg_rhat.data(), J.dg_ess.data()));
     J.dg_mean.resize(n); J.dg_std.resize(n); J.dg_rhat.resize(n); J.dg_ess.resize(n);
@@ -675,9 +693,15 @@ void write_diag(const Job &J)
     const std::string name = J.odirname + "/diagnostics.csv";
     FILE *f = fopen(name.c_str(), "w");
     if (!f) die("cannot write " + name);
-    fprintf(f, "row,col,mean,std,rhat,ess,mcse\n");
+    fprintf(f, J.diag_rank ? "row,col,mean,std,rhat,ess_bulk,ess_tail,mcse\n" : "row,col,mean,std,rhat,ess,mcse\n");
     for (size_t i = 0; i < J.dg_q.size(); ++i) {
         const int64_t r = J.dg_q[i], c = J.dg_c[i];
+        if (J.diag_rank) {
+            fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
+                    (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.dg_mean[i], J.dg_std[i], J.dg_rhat[i], J.dg_ess[i], J.dg_tail[i],
+                    J.dg_std[i] / std::sqrt(J.dg_ess[i]));
+            continue;
+        }
         fprintf(f, "%lld,%lld,%.17g,%.17g,%.17g,%.17g,%.17g\n", (long long)((J.perm_u.empty() ? r : J.perm_u[(size_t)r]) + 1),
                 (long long)((J.perm_m.empty() ? c : J.perm_m[(size_t)c]) + 1), J.dg_mean[i], J.dg_std[i], J.dg_rhat[i], J.dg_ess[i],
                 J.dg_std[i] / std::sqrt(J.dg_ess[i]));
@@ -689,9 +713,12 @@ void write_diag(const Job &J)
 void print_diag(std::ostream &os, const Job &J, bool traces)
 {
     if (!J.diagnose) return;
-    std::vector<double> rh, es, ms;
+    std::vector<double> rh, es, ms, tl;
     for (size_t i = 0; i < J.dg_rhat.size(); ++i)
-        if (!std::isnan(J.dg_rhat[i]) && !std::isnan(J.dg_ess[i])) { rh.push_back(J.dg_rhat[i]); es.push_back(J.dg_ess[i]); ms.push_back(1.0 / std::sqrt(J.dg_ess[i])); }
+        if (!std::isnan(J.dg_rhat[i]) && !std::isnan(J.dg_ess[i]) && !(J.diag_rank && std::isnan(J.dg_tail[i]))) {
+            rh.push_back(J.dg_rhat[i]); es.push_back(J.dg_ess[i]); ms.push_back(1.0 / std::sqrt(J.dg_ess[i]));
+            if (J.diag_rank) tl.push_back(J.dg_tail[i]);
+        }
     auto median = [](std::vector<double> v) {
         if (v.empty()) return (double)NAN;
         std::sort(v.begin(), v.end());
@@ -700,10 +727,15 @@ void print_diag(std::ostream &os, const Job &J, bool traces)
     size_t above = 0;
     for (double r : rh) above += r > 1.01;
     char buf[512];
+    if (J.diag_rank)
+        snprintf(buf, sizeof buf, "Final ESS: bulk min %.1f median %.1f tail min %.1f median %.1f of %d samples in %d chains (%lld cells)",
+                 es.empty() ? NAN : *std::min_element(es.begin(), es.end()), median(es), tl.empty() ? NAN : *std::min_element(tl.begin(), tl.end()), median(tl),
+                 J.dg_samples, J.dg_chains, (long long)J.dg_rhat.size());
+    else
     snprintf(buf, sizeof buf, "Final ESS: min %.1f median %.1f of %d samples (%lld cells)", es.empty() ? NAN : *std::min_element(es.begin(), es.end()), median(es),
              J.dg_samples, (long long)J.dg_rhat.size());
     os << buf << std::endl;
-    snprintf(buf, sizeof buf, "Final split-Rhat: median %.4f max %.4f above 1.01: %.2f%%", median(rh), rh.empty() ? NAN : *std::max_element(rh.begin(), rh.end()),
+    snprintf(buf, sizeof buf, J.diag_rank ? "Final rank-Rhat: median %.4f max %.4f above 1.01: %.2f%%" : "Final split-Rhat: median %.4f max %.4f above 1.01: %.2f%%", median(rh), rh.empty() ? NAN : *std::max_element(rh.begin(), rh.end()),
              rh.empty() ? NAN : 100.0 * (double)above / (double)rh.size());
     os << buf << std::endl;
     snprintf(buf, sizeof buf, "Final MCSE/std: median %.4f", median(ms));
@@ -1132,6 +1164,10 @@ void rank_main(Job &J, int rank, std::ostream &os)
         const size_t off = (size_t)J.Mt.colptr[(size_t)u0];
         check(bpmf_hip_side_create(ctx, nusers, nmovies, u0, u1, cp.data(), J.Mt.rowidx.data() + off, J.Mt.vals.data() + off, J.mean_u, &users));
     }
+    if (J.chain >= 0) {                                              // --chain c: both sides, before their first half-iteration
+        check(bpmf_hip_side_set_chain(movies, J.chain));
+        check(bpmf_hip_side_set_chain(users, J.chain));
+    }
     if (J.probit) {                                                  // (streams: tag 1 = movies, 2 = users)
         check(bpmf_hip_side_set_probit(movies, J.probit_threshold, 1));
         check(bpmf_hip_side_set_probit(users, J.probit_threshold, 2));
@@ -1298,7 +1334,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
     if (J.fold_u.n > 0) os << "fold-in rows: " << J.fold_u.n << " (--fold-in-rows), " << J.fold_u.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (J.fold_m.n > 0) os << "fold-in columns: " << J.fold_m.n << " (--fold-in-cols), " << J.fold_m.Fr.nnz() << " ratings, folded in against the kept samples" << std::endl;
     if (saving) os << "save-model: " << J.save_model << std::endl;
-    if (J.diagnose) os << "diagnose: split-Rhat and ESS of the test predictions" << std::endl;
+    if (J.diagnose) os << (J.diag_rank ? "diagnose: rank-normalised split-Rhat, bulk and tail ESS of the test predictions" : "diagnose: split-Rhat and ESS of the test predictions") << std::endl;
     if (J.score) os << "score: WAIC of the training cells and log density of the test cells" << std::endl;
     if (!J.iv_levels.empty()) {
         os << "intervals: central predictive intervals of the test cells at";
@@ -1306,6 +1342,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         os << ", and the calibration of their held-out values" << std::endl;
     }
     if (J.loo) os << "loo: PSIS-LOO cross-validation of the training cells" << std::endl;
+    if (J.chain >= 0) os << "chain: " << J.chain << " (random streams of half-iterations " << (long long)J.chain * BPMF_HIP_CHAIN_STRIDE << " ...)" << std::endl;
     os << "update_freq: " << J.update_freq << std::endl;
     if (!J.perm_m.empty()) os << "assignment: greedy (c++/assign.cpp), columns renumbered" << std::endl;
     if (J.sharded) os << "movs domain: [" << m0 << ", " << m1 << ")  users domain: [" << u0 << ", " << u1 << ")" << std::endl;
@@ -1339,7 +1376,7 @@ void rank_main(Job &J, int rank, std::ostream &os)
         J.alpha_trace.push_back(alpha);
         check(bpmf_hip_train_sse(movies, users, &sse, &n));
         J.train_rmse.push_back(std::sqrt(sse / (double)n));
-        if (i + 1 < nsims) check(bpmf_hip_noise_sample(J.a0, J.b0, sse, n, i, J.alpha_max, &alpha));
+        if (i + 1 < nsims) check(bpmf_hip_noise_sample(J.a0, J.b0, sse, n, i + (J.chain > 0 ? J.chain * BPMF_HIP_CHAIN_STRIDE : 0), J.alpha_max, &alpha));
     };
     // --ordinal, after both sides of iteration i: the Metropolis-Hastings step of the cutpoints of iteration i + 1 (one pass over the
     // training ratings on the device, the rest on the host; the pipelined loop waits here once per iteration, as adapt does).  The
@@ -1724,8 +1761,43 @@ static int run_tensor(const std::string &file, const std::string &test_file, con
 static int run_model(Job &J, const std::string &dir, const std::string &fname, const std::string &probename, const std::string &predict_file,
                      bool thr_given, double thr, const std::string &fold_in_rows, const std::string &fold_in_cols, bool d_given, int d)
 {
+    // DIR may be a list D0,D1,.. of chains of one model: pooled along the sample axis in list order (bpmf_amd.pool_models)
     bpmf::io::Model m;
-    try { m = bpmf::io::read_model(dir); } catch (const std::exception &e) { die(e.what()); }
+    int chains = 0;
+    for (size_t from = 0; from <= dir.size();) {
+        const size_t to = std::min(dir.find(',', from), dir.size());
+        const std::string one = dir.substr(from, to - from);
+        from = to + 1;
+        if (one.empty()) die("--model: an empty directory name in the list '" + dir + "'");
+        bpmf::io::Model c;
+        try { c = bpmf::io::read_model(one); } catch (const std::exception &e) { die(e.what()); }
+        if (chains++ == 0) { m = std::move(c); continue; }
+        const int S0 = m.S / (chains - 1);                           // samples of one chain
+        const char *what = c.rows != m.rows || c.cols != m.cols ? "shape" : c.K != m.K ? "num_latent" : c.probit != m.probit || c.probit_threshold != m.probit_threshold ? "likelihood" :
+                           c.mean_rating != m.mean_rating ? "mean rating" : c.f32 != m.f32 ? "dtype" : c.S != S0 ? "samples" : c.hyper != m.hyper ? "the presence of the hyper files" : nullptr;
+        if (what) die("--model: " + one + " differs from " + dir.substr(0, dir.find(',')) + " in " + what + " (chains of one model are pooled)");
+        const size_t sk = (size_t)S0 * (size_t)m.K;                  // doubles of one chain per row / column
+        for (int prev = 0; prev < chains - 1; ++prev) {
+            bool same = true;
+            for (int64_t r = 0; r < m.rows && same; ++r)
+                same = memcmp(&m.U[(size_t)r * (size_t)m.S * (size_t)m.K + (size_t)prev * sk], &c.U[(size_t)r * sk], sizeof(double) * (size_t)m.K) == 0;
+            if (same) die("--model: " + one + " has the first kept sample of chain " + std::to_string(prev) + " of the list, byte for byte: the same chain twice (bpmf --chain c makes them differ)");
+        }
+        auto append = [&](std::vector<double> &all, const std::vector<double> &add, int64_t n) {   // n blocks: (all's block, add's block) interleaved
+            const size_t a = all.size() / (size_t)n, b = add.size() / (size_t)n;
+            std::vector<double> out; out.reserve(all.size() + add.size());
+            for (int64_t i = 0; i < n; ++i) {
+                out.insert(out.end(), all.begin() + (ptrdiff_t)((size_t)i * a), all.begin() + (ptrdiff_t)((size_t)(i + 1) * a));
+                out.insert(out.end(), add.begin() + (ptrdiff_t)((size_t)i * b), add.begin() + (ptrdiff_t)((size_t)(i + 1) * b));
+            }
+            all.swap(out);
+        };
+        append(m.U, c.U, m.rows); append(m.V, c.V, m.cols);
+        if (m.hyper) { m.Uh.insert(m.Uh.end(), c.Uh.begin(), c.Uh.end()); m.Vh.insert(m.Vh.end(), c.Vh.begin(), c.Vh.end()); }
+        m.S += c.S;
+    }
+    J.dg_chains = chains;
+    if (chains > 1) J.diag_rank = J.diagnose;                        // --diagnose under a pooled model is the multi-chain estimator
     const int K = m.K;
     if (d_given && d != K) die("-d " + std::to_string(d) + " differs from the num_latent " + std::to_string(K) + " of the model " + dir);
     if (J.score && m.S < 2) die("--score needs at least 2 samples, the model " + dir + " holds " + std::to_string(m.S));
@@ -1737,8 +1809,10 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     if (!J.iv_levels.empty() && m.S > BPMF_HIP_INTERVAL_MAX_SAMPLES)
         die("--intervals takes at most " + std::to_string(BPMF_HIP_INTERVAL_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
     if (!J.iv_levels.empty() && !(m.alpha > 0.0) && !m.hyper) die("--intervals needs a model with alpha > 0 (the noise precision of its likelihood)");
-    if (J.diagnose && (m.S < 8 || m.S > BPMF_HIP_DIAG_MAX_SAMPLES))
-        die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
+    if (J.diagnose && (m.S / chains < 8 || m.S > BPMF_HIP_DIAG_MAX_SAMPLES))
+        die(chains > 1 ? "--diagnose needs 8 or more samples per chain and " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " at most in all, the models " + dir + " hold " +
+                         std::to_string(chains) + " x " + std::to_string(m.S / chains)
+                       : "--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " samples, the model " + dir + " holds " + std::to_string(m.S));
     for (const std::string *f : {&fold_in_rows, &fold_in_cols}) {
         if (f->empty()) continue;
         const std::string w = f == &fold_in_rows ? "--fold-in-rows" : "--fold-in-cols";
@@ -1787,7 +1861,7 @@ static int run_model(Job &J, const std::string &dir, const std::string &fname, c
     if (!predict_file.empty() && thr_given && !m.probit && !(m.alpha > 0.0)) die("--predict-threshold needs a model with alpha > 0 (sigma = 1 / sqrt(alpha))");
 
     std::cout << "model: " << dir << ", " << nusers << " x " << nmovies << ", num_latent " << K << ", " << m.S << " samples, " << (m.probit ? "probit" : "gaussian")
-              << std::endl;
+              << (chains > 1 ? ", " + std::to_string(chains) + " chains" : std::string()) << std::endl;
     int device = 0;
     if (const char *e = getenv("BPMF_HIP_DEVICES")) device = atoi(e);
     bpmf_hip_ctx *ctx = nullptr;
@@ -1910,6 +1984,7 @@ int main(int argc, char *argv[])
                                               {"diagnose", no_argument, nullptr, 1100},
                                               {"score", no_argument, nullptr, 1101}, {"intervals", required_argument, nullptr, 1102},
                                               {"loo", no_argument, nullptr, 1103},
+                                              {"chain", required_argument, nullptr, 1104}, {"diagnose-rank", no_argument, nullptr, 1105},
                                               {nullptr, 0, nullptr, 0}};
     std::string similar_n, similar_by = "cols", similar_kind = "cosine", similar_kappa, similar_min;
     std::string bias_lambda, bias_prior;
@@ -1928,6 +2003,8 @@ int main(int argc, char *argv[])
     std::string intervals;
     bool intervals_given = false;
     bool save_model_given = false, model_given = false, predict_given = false, predict_threshold_given = false;
+    std::string chain_arg;
+    bool chain_given = false;
     bool nsims_given = false, burnin_given = false, d_given = false, g_given = false;
     std::string training_flag;                                       // the first flag of the likelihood / the chain (refused with --model)
     auto training = [&](const char *flag) { if (training_flag.empty()) training_flag = flag; };
@@ -1987,6 +2064,8 @@ int main(int argc, char *argv[])
         case 1101: J.score = true; break;
         case 1102: intervals = optarg; intervals_given = true; break;
         case 1103: J.loo = true; break;
+        case 1104: training("--chain"); chain_arg = optarg; chain_given = true; break;
+        case 1105: J.diagnose = true; J.diag_rank = true; break;
         case 'i': J.nsims = atoi(optarg); nsims_given = true; break;
         case 'b': J.burnin = atoi(optarg); burnin_given = true; break;
         case 'f': training("-f"); J.update_freq = atoi(optarg); break;
@@ -2042,6 +2121,22 @@ int main(int argc, char *argv[])
         if (model_given && !predict_given) die("--diagnose with --model needs --predict FILE (the cells whose predictions are diagnosed)");
         if (!model_given && (J.nsims - J.burnin < 8 || J.nsims - J.burnin > BPMF_HIP_DIAG_MAX_SAMPLES))
             die("--diagnose needs 8 .. " + std::to_string(BPMF_HIP_DIAG_MAX_SAMPLES) + " post-burn-in samples (-i - -b = " + std::to_string(J.nsims - J.burnin) + ")");
+    }
+    // --chain: refused before anything touches a GPU (the refusals of bpmf_hip_side_set_chain)
+    if (chain_given) {
+        char *end = nullptr;
+        const long c = chain_arg.empty() ? -1 : strtol(chain_arg.c_str(), &end, 10);
+        if (chain_arg.empty() || *end != '\0' || c < 0 || c > BPMF_HIP_CHAIN_MAX) die("--chain expects 0 <= c <= " + std::to_string(BPMF_HIP_CHAIN_MAX) + ", not '" + chain_arg + "'");
+        J.chain = (int)c;
+        if (tensor_given) die("--chain does not go together with --tensor");
+        if (!row_features.empty() || !col_features.empty() || !new_row_features.empty() || !new_col_features.empty()) die("--chain does not go together with features (--row-features / --col-features)");
+        if (J.ordinal) die("--chain does not go together with --ordinal");
+        if (J.bias) die("--chain does not go together with --bias");
+        if (J.implicit) die("--chain does not go together with --implicit");
+        if (g_given || ngpu >= 1) die("--chain runs on one GPU without -g: -g " + std::to_string(ngpu) + " is not supported (run one process per chain and GPU)");
+        if (getenv("BPMF_REDUCE") && atoi(getenv("BPMF_REDUCE")) != 0) die("--chain does not go together with BPMF_REDUCE=1");
+        if (!mname.empty() || !lname.empty()) die("--chain does not go together with a propagated posterior (-m / -l)");
+        if (J.nsims > BPMF_HIP_CHAIN_STRIDE) die("--chain needs -i <= " + std::to_string(BPMF_HIP_CHAIN_STRIDE) + " (the chains' random streams are that many half-iterations apart), not -i " + std::to_string(J.nsims));
     }
     // --score: refused before anything touches a GPU
     if (J.score) {

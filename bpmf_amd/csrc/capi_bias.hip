@@ -70,7 +70,7 @@ extern "C" int bpmf_hip_side_set_bias(bpmf_hip_side *s, double lambda, unsigned 
     if (s->bias) return fail(BPMF_HIP_EINVAL, "side_set_bias: the side has bias terms already");
     if (s->tensor_mode) return fail(BPMF_HIP_EINVAL, "side_set_bias: not on a mode of a tensor (its rows are products of two other modes' rows)");
     if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_bias: not on an implicit side (bpmf_hip_side_set_implicit)");
-    int rc = refuse("side_set_bias", s, {Not::probit, Not::ordinal, Not::censored, Not::robust, Not::weights, Not::features, Not::prop_posterior, Not::reduce});
+    int rc = refuse("side_set_bias", s, {Not::probit, Not::ordinal, Not::censored, Not::robust, Not::weights, Not::features, Not::prop_posterior, Not::reduce, Not::chain});
     if (rc || (rc = require_single_gpu("side_set_bias", c, s))) return rc;
     if (s->ring) return fail(BPMF_HIP_EINVAL, "side_set_bias: not on a side with a sample ring (bpmf_hip_side_samples_reserve)");
     if (s->foldin) return fail(BPMF_HIP_EINVAL, "side_set_bias: not together with fold-in (bpmf_hip_side_hyper_reserve)");

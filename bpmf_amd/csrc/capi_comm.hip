@@ -143,6 +143,7 @@ extern "C" int bpmf_hip_sys_set_reduce(bpmf_hip_side *a, bpmf_hip_side *b, int o
     if ((rc = settle_async(a)) || (rc = settle_async(b))) return rc;
     { const int rs_ = bounded_stream_sync(c, c->stream.get(), __func__); if (rs_) return rs_; }
     if (!on) { a->reduce_on = b->reduce_on = false; return BPMF_HIP_OK; }
+    if ((rc = refuse("sys_set_reduce", a, {Not::chain})) || (rc = refuse("sys_set_reduce", b, {Not::chain}))) return rc;
     if (a->probit || b->probit) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with the probit likelihood (bpmf_hip_side_set_probit)");
     if (a->censor || b->censor) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with censored ratings (bpmf_hip_side_set_censored)");
     if (a->ordinal || b->ordinal) return fail(BPMF_HIP_EINVAL, "sys_set_reduce: not together with the ordinal likelihood (bpmf_hip_side_set_ordinal)");

@@ -20,7 +20,7 @@ extern "C" int bpmf_hip_side_set_implicit(bpmf_hip_side *s, double w0, const dou
     if (!(w0 > 0.0) || !std::isfinite(w0)) return fail(BPMF_HIP_EINVAL, "side_set_implicit: w0 must be finite and > 0");
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on an fp32 context");
     if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_implicit: the side is an implicit side already");
-    int rc = refuse("side_set_implicit", s, {Not::bias, Not::robust});
+    int rc = refuse("side_set_implicit", s, {Not::bias, Not::robust, Not::chain});
     if (rc) return rc;
     if (s->weights) return fail(BPMF_HIP_EINVAL, "side_set_implicit: not on a side with per-rating weights (pass the confidences to this call)");
     if ((rc = refuse("side_set_implicit", s, {Not::probit, Not::censored, Not::ordinal, Not::features, Not::prop_posterior, Not::reduce}))) return rc;

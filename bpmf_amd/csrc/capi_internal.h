@@ -14,7 +14,8 @@
 //   capi_foldin.hip    the per-sample hyper-parameters of a side (hyper ring) and the fold-in of new rows from their ratings (bpmf_hip_foldin*)
 //   capi_model.hip     saved models: read-back and load of a sample ring (bpmf_hip_side_samples_get / _set), predictions for a list of cells
 //                      (bpmf_hip_predict_cells); what the cell lists share: their checks, their sort and their batches (CellsPlan)
-//   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells)
+//   capi_diag.hip      convergence diagnostics: split-Rhat and ESS of host traces (bpmf_hip_diag_traces) and of the predictions of a list of cells (bpmf_hip_diag_cells);
+//                      the rank-normalised multi-chain forms (bpmf_hip_diag_traces_mc, bpmf_hip_diag_cells_mc)
 //   capi_score.hip     model comparison: log pointwise predictive density and WAIC of a list of observed cells (bpmf_hip_score_cells); what it
 //                      shares with capi_loo.hip: the refusals of a likelihood's arguments and its per-sample constants (logdens_check_args, logdens_constants)
 //   capi_interval.hip  predictive intervals: the probability integral transform and quantiles of the posterior predictive mixture of a list of cells
@@ -66,6 +67,8 @@ int build_schedule(bpmf_hip_side *s, const int64_t *colptr);
 void free_schedule(bpmf_hip_side *s);
 void pad_square(int Kt, int K, const double *src, double *dst, double diag);
 void unpad_square(int Kt, int K, const double *src, double *dst);
+// the index that keys the random numbers of the side's half-iteration `iter` (bpmf_hip_side_set_chain; bookkeeping keeps `iter`)
+inline int key_iter(const bpmf_hip_side *s, int iter) { return iter + s->chain * BPMF_HIP_CHAIN_STRIDE; }
 inline bool sharded(const bpmf_hip_side *s) { return s->from != 0 || s->to != s->ncols || !s->bounds.empty(); }
 // refuses with "<who>: needs the side (both sides) whole on one GPU<tail>" when the context has a communicator or a side is a shard
 int require_single_gpu(const char *who, const bpmf_hip_ctx *c, const bpmf_hip_side *a, const bpmf_hip_side *b = nullptr,
@@ -116,7 +119,7 @@ int latent_read_back(const char *func, bpmf_hip_side *s, const double *z, double
 // (bpmf_hip_side_set_probit)" etc. (the table is in capi_side.hip): the first of `order` that holds for `s` is reported as
 // BPMF_HIP_EINVAL, 0 if none does.  The order decides what a side with two of the properties is told (a robust side has weights
 // too); a caller whose wording differs writes that line out at its place between two calls.
-enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce, bias };
+enum class Not { probit, ordinal, censored, robust, weights, features, prop_posterior, reduce, bias, chain };
 int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> order);
 
 // ---- Ring queries: what the entry points that reduce mean + u_s . v_s over two rings share (defined in capi_topn.hip) ----

@@ -142,7 +142,7 @@ int link_attach_common(const char *who, bpmf_hip_side *s, int D, double lambda, 
     if (c->dtype != BPMF_HIP_F64) return fail(BPMF_HIP_EINVAL, w + ": not on an fp32 context");
     int rc = require_single_gpu(who, c, s);
     if (rc) return rc;
-    if ((rc = refuse(who, s, {Not::reduce, Not::bias}))) return rc;
+    if ((rc = refuse(who, s, {Not::reduce, Not::bias, Not::chain}))) return rc;
     if (s->probit) return fail(BPMF_HIP_EINVAL, w + ": not on a probit side");
     if (s->ordinal) return fail(BPMF_HIP_EINVAL, w + ": not on an ordinal side");
     if (s->censor) return fail(BPMF_HIP_EINVAL, w + ": not on a censored side (the residuals would have to be formed from the latent values)");

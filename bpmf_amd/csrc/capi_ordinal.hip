@@ -118,7 +118,7 @@ extern "C" int bpmf_hip_side_set_ordinal(bpmf_hip_side *s, const double *levels,
         if (i > 0 && !(levels[i] > levels[i - 1])) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the levels are not strictly increasing");
     }
     if (s->ordinal) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the side is an ordinal side already");
-    int rc = refuse("side_set_ordinal", s, {Not::bias, Not::probit, Not::censored, Not::robust, Not::weights, Not::features, Not::prop_posterior});
+    int rc = refuse("side_set_ordinal", s, {Not::bias, Not::probit, Not::censored, Not::robust, Not::weights, Not::features, Not::prop_posterior, Not::chain});
     if (rc) return rc;
     if (s->mean_rating != 0.0) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: the side must have been created with mean_rating = 0");
     if (tag == 0) return fail(BPMF_HIP_EINVAL, "side_set_ordinal: tag must be >= 1 (key word 0 belongs to the samplers' streams)");

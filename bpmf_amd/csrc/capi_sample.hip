@@ -464,7 +464,7 @@ void predraw_main(bpmf_hip_side *s)
         auto &sl = P.slot[it % bpmf_hip_side::Predraw::DEPTH];
         lk.unlock();
         sl.au.resize((size_t)K * K); sl.z.resize(K);
-        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)it, sl.au.data(), sl.z.data());
+        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)key_iter(s, it), sl.au.data(), sl.z.data());
         lk.lock();
         sl.iter = rc ? -3 - it : it;                                  // (a failed draw is recomputed inline by the consumer)
         P.cv.notify_all();
@@ -486,7 +486,7 @@ int predraw_get(bpmf_hip_side *s, int iter)
     if (iter < P.consumed + 1 || iter >= P.next + bpmf_hip_side::Predraw::DEPTH) {      // out of order (never in a chain): inline
         lk.unlock();
         s->rd_au.resize((size_t)K * K); s->rd_z.resize(K);
-        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)iter, s->rd_au.data(), s->rd_z.data());
+        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)key_iter(s, iter), s->rd_au.data(), s->rd_z.data());
         if (!rc) s->rd_iter = iter;
         return rc;
     }
@@ -498,7 +498,7 @@ int predraw_get(bpmf_hip_side *s, int iter)
     lk.unlock();
     if (!ok) {
         s->rd_au.resize((size_t)K * K); s->rd_z.resize(K);
-        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)iter, s->rd_au.data(), s->rd_z.data());
+        const int rc = bpmf_hyper_draws(K, s->ncols, (uint32_t)key_iter(s, iter), s->rd_au.data(), s->rd_z.data());
         if (rc) return rc;
     }
     s->rd_iter = iter;
@@ -525,7 +525,10 @@ int draw_and_release(bpmf_hip_side *s, int iter, double *mu, double *LU, double 
     int rc = 0;
     if (s->rd_iter != iter) rc = predraw_get(s, iter);
     if (!rc) rc = bpmf_hyper_finish(K, s->ncols, s->cov.data(), nullptr, s->rd_au.data(), s->rd_z.data(), mu, LU, LF);
-    if (!rc) fill_blob_ctx(c, mu, LF, s->a_h_in.host(), c->K == 64 && c->dtype == BPMF_HIP_F64 && s->lr_n > 0, LU);   // (R0, R0^-1: only the low-rank forms read them)
+    // (R0, R0^-1: only the low-rank forms read them.  Chain 0 takes the factor the draw produced, as it always has; a chain other than 0
+    // factorises LambdaF as the stateless bpmf_hip_sample_side does, so that its half-iteration i is that call at iter = key_iter(i) bit
+    // for bit -- the two factors differ by rounding)
+    if (!rc) fill_blob_ctx(c, mu, LF, s->a_h_in.host(), c->K == 64 && c->dtype == BPMF_HIP_F64 && s->lr_n > 0, s->chain == 0 ? LU : nullptr);
     // the gate is opened even after an error: a sampler may already be queued behind it and must
     // not be left spinning (its results are never looked at: the error is reported first)
     {   // test hook: a host worker that is descheduled for a while (SIGSTOP, debugger, oversubscription)
@@ -697,6 +700,10 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
         return fail(BPMF_HIP_EINVAL, "sys_sample: the side is a shard: give the context a communicator "
                                      "(bpmf_hip_ctx_comm_init) and the side its ranges (bpmf_hip_side_set_ranges), "
                                      "or use bpmf_hip_sample_side and all-reduce the sums yourself");
+    if (self->chain != other->chain)
+        return fail(BPMF_HIP_EINVAL, "sys_sample: the sides belong to different chains (" + std::to_string(self->chain) + " and " + std::to_string(other->chain) +
+                    "; bpmf_hip_side_set_chain)");
+    if (self->chain != 0 && c->comm) return fail(BPMF_HIP_EINVAL, "sys_sample: a chain other than 0 not on a context with a communicator");
     const int K = c->K;
     if (c->comm_dead.load()) return fail(BPMF_HIP_ENODEV, "sys_sample: the communicator of this context was aborted (a collective timed out)");
     HIP_TRY(hipSetDevice(c->device));
@@ -761,7 +768,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     // kernel of a robust side: likewise.
     self->latent_queued = false;
     if (likelihood(self) != Likelihood::gaussian) {
-        if ((rc = latent_enqueue(self, other, iter, alpha, s0))) return rc;
+        if ((rc = latent_enqueue(self, other, key_iter(self, iter), alpha, s0))) return rc;
         self->latent_queued = true;
     }
     if (fused) {
@@ -797,7 +804,7 @@ extern "C" int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, do
     self->cur_fused = fz;
     self->cur_riders = riders;
     self->cur_gate_flag = fused ? self->a_dflag.get() : nullptr; self->cur_gate_want = seq;
-    rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, iter, alpha, self->a_d_in.get(), s0, (ride && timed) ? ev[0] : nullptr,
+    rc = BPMF_DISPATCH_K(K, sample_and_exchange<KK, FF>(self, other, key_iter(self, iter), alpha, self->a_d_in.get(), s0, (ride && timed) ? ev[0] : nullptr,
                                                     ride ? ev[1] : nullptr));
     self->cur_gate_flag = nullptr;
     self->latent_queued = false;

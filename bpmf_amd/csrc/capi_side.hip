@@ -376,13 +376,31 @@ int refuse(const char *who, const bpmf_hip_side *s, std::initializer_list<Not> o
                                             "not together with features (bpmf_hip_side_set_features)",
                                             "not together with propagated priors",
                                             "not together with the BPMF_REDUCE formulation",
-                                            "not on a side with bias terms (bpmf_hip_side_set_bias)"};
+                                            "not on a side with bias terms (bpmf_hip_side_set_bias)",
+                                            "not on a side whose chain is not 0 (bpmf_hip_side_set_chain)"};
     const bool holds[] = {(bool)s->probit, (bool)s->ordinal, (bool)s->censor, (bool)s->robust, (bool)s->weights,
-                          (bool)s->link, (bool)s->d_prop, s->reduce_on, (bool)s->bias};
+                          (bool)s->link, (bool)s->d_prop, s->reduce_on, (bool)s->bias, s->chain != 0};
     for (const Not n : order)
         if (holds[(int)n]) return fail(BPMF_HIP_EINVAL, std::string(who) + ": " + kSentence[(int)n]);
     return 0;
 }
+
+extern "C" int bpmf_hip_side_set_chain(bpmf_hip_side *s, int chain)
+{
+    if (!s) return fail(BPMF_HIP_EINVAL, "side_set_chain: NULL");
+    if (chain < 0 || chain > BPMF_HIP_CHAIN_MAX)
+        return fail(BPMF_HIP_EINVAL, "side_set_chain: chain " + std::to_string(chain) + " given, 0 .. " + std::to_string(BPMF_HIP_CHAIN_MAX) + " allowed");
+    if (s->iter >= 0) return fail(BPMF_HIP_EINVAL, "side_set_chain: the side has taken a half-iteration (set the chain before the first bpmf_hip_sys_sample)");
+    if (s->ctx->comm) return fail(BPMF_HIP_EINVAL, "side_set_chain: not on a context with a communicator");
+    if (sharded(s)) return fail(BPMF_HIP_EINVAL, "side_set_chain: not on a shard of a side");
+    if (s->tensor_mode) return fail(BPMF_HIP_EINVAL, "side_set_chain: not on a mode of a tensor");
+    if (s->implicit) return fail(BPMF_HIP_EINVAL, "side_set_chain: not on a side with implicit feedback (bpmf_hip_side_set_implicit)");
+    { const int rc = refuse("side_set_chain", s, {Not::features, Not::ordinal, Not::bias, Not::prop_posterior, Not::reduce}); if (rc) return rc; }
+    s->chain = chain;
+    return BPMF_HIP_OK;
+}
+
+extern "C" int bpmf_hip_side_chain(const bpmf_hip_side *s) { return s ? s->chain : 0; }
 
 int latent_settle(const char *func, bpmf_hip_side *s)
 {
@@ -427,7 +445,7 @@ extern "C" int bpmf_hip_side_set_prop_posterior(bpmf_hip_side *s, const double *
 {
     if (!s) return fail(BPMF_HIP_EINVAL, "set_prop_posterior: NULL");
     (void)mu;
-    if (Lambda) { const int rf = refuse("set_prop_posterior", s, {Not::bias, Not::robust, Not::weights, Not::ordinal}); if (rf) return rf; }
+    if (Lambda) { const int rf = refuse("set_prop_posterior", s, {Not::bias, Not::robust, Not::weights, Not::ordinal, Not::chain}); if (rf) return rf; }
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rc = settle_async(s); if (rc) return rc; }
     { const int rs_ = bounded_stream_sync(s->ctx, s->ctx->stream.get(), __func__); if (rs_) return rs_; }

@@ -246,6 +246,13 @@ int diag_max_samples();
 int cell_traces_segment(int Kp);                            // cells of a segment at most
 int cell_traces(const PredCellsLaunch &p, double *trace, int64_t tbase, hipStream_t st);          // -1: shape not supported (nothing launched)
 int trace_diag(const double *traces, int64_t ntr, int S, const int32_t *orig, double *rhat, double *ess, hipStream_t st);   // -1 likewise
+// over several chains (kernels_diag_mc.h, kdiagmc.hip): the rank-normalised split-Rhat, bulk and tail ESS of ntr traces of C chains of S
+// samples (chain-major rows of C S doubles, on the device) to rhat / ess_bulk / ess_tail[orig[t]] (orig NULL: [t])
+int diag_mc_max_chains();
+int diag_mc_min_samples();
+int diag_mc_max_values();                                   // C * S at most
+int trace_diag_mc(const double *traces, int64_t ntr, int C, int S, const int32_t *orig, double *rhat, double *ess_bulk, double *ess_tail,
+                  hipStream_t st);                          // -1 likewise
 
 // predictive intervals (kernels_interval.h, kinterval.hip): the probability integral transform of y (NULL: none) and nq quantiles of the
 // mixture of S normals around ntr traces of S samples (row-major, on the device; what cell_traces stores), to pit[orig[t]] and

@@ -292,6 +292,7 @@ struct bpmf_hip_side {
     bpmf::StatRiders cur_riders{};       // fp32 path: statistics riders of the k_sample_wg2 launch being enqueued
     const unsigned *cur_gate_flag = nullptr; unsigned cur_gate_want = 0;   // what the launch being enqueued polls (NULL: ordered by the queue)
     unsigned a_seq = 0;
+    int chain = 0;                       // bpmf_hip_side_set_chain: the random numbers of half-iteration i are those keyed i + chain * BPMF_HIP_CHAIN_STRIDE
     int iter = -1;                       // state of the reference's Sys (c++/bpmf.h:139,221-226) for bpmf_hip_sys_sample
     bool pending = false;
     hipEvent_t last_stop = nullptr;      // stop event of this side's newest sampler (diagnostic: boundary to the next launch)

@@ -206,6 +206,18 @@ class HipEngine:
         assert items.shape == (side.ncols, self.K)
         _lib.check(self.lib.bpmf_hip_side_set_items(side.handle, _ptr(items)))
 
+    # -- independent chains -------------------------------------------------------
+    CHAIN_STRIDE, CHAIN_MAX = 1 << 20, 63
+
+    def side_set_chain(self, side, chain):
+        """Makes `side` chain `chain` (0 .. 63) of its model: sys_sample keys the random numbers of its half-iteration i by
+        i + chain * 2^20 (include/bpmf_hip.h).  Before the side's first half-iteration; both sides of a pair get
+        the same chain.  Chain 0 is the run as it was."""
+        _lib.check(self.lib.bpmf_hip_side_set_chain(side.handle, int(chain)))
+
+    def side_chain(self, side):
+        return int(self.lib.bpmf_hip_side_chain(side.handle))
+
     # -- hot path ---------------------------------------------------------------
     def sample_side_launch(self, side, other, it, alpha, mu, LambdaF):
         mu = np.ascontiguousarray(mu, np.float64)
@@ -335,6 +347,41 @@ class HipEngine:
         _lib.check(self.lib.bpmf_hip_diag_cells(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
                                                 *[_ptr(a if n else np.zeros(1)) for a in out]))
         return dict(mean=out[0], std=out[1], rhat=out[2], ess=out[3])
+
+    DIAG_MAX_CHAINS = 64
+
+    def diag_traces_mc(self, X, chains):
+        """(rhat, ess_bulk, ess_tail), [n] each: the rank-normalised split-Rhat, the bulk and the tail effective sample size
+        (Vehtari et al. 2021) of the n traces X [n, chains * S] (one trace: [chains * S]),
+        chain-major: chain c is X[i, c S : (c + 1) S], chronological inside.  1 <= chains <= 64, S >= 8, chains * S <= 4096.  A
+        trace with a value that is not finite gives NaN for all three; see bpmf_hip.h for the other NaN rules."""
+        X = np.ascontiguousarray(X, np.float64)
+        chains = int(chains)
+        if X.ndim == 1:
+            X = X[None, :]
+        if X.ndim != 2:
+            raise ValueError("diag_traces_mc: X must be [n, chains * S]")
+        n, L = X.shape
+        if chains < 1 or L % chains:
+            raise ValueError("diag_traces_mc: %d values per trace are not %d chains of one length" % (L, chains))
+        out = [np.empty(n) for _ in range(3)]
+        hold = np.zeros(1)
+        _lib.check(self.lib.bpmf_hip_diag_traces_mc(self.ctx, n, chains, L // chains, _ptr(X if n else hold), *[_ptr(a if n else hold) for a in out]))
+        return tuple(out)
+
+    def diag_cells_mc(self, query, cand, mean_rating, q, c, chains):
+        """dict(mean, std, rhat, ess_bulk, ess_tail), [n] each, of the cells (q[i], c[i]) over two rings that hold the samples of
+        `chains` chains of one length one after the other (bpmf_amd.pool_models): mean and std are predict_cells's, bit for bit; the
+        other three are diag_traces_mc's of the cell's predictions."""
+        q = np.ascontiguousarray(q, np.int32); c = np.ascontiguousarray(c, np.int32)
+        if q.ndim != 1 or q.shape != c.shape:
+            raise ValueError("diag_cells_mc: q and c must be one-dimensional and of the same length")
+        n = len(q)
+        out = [np.empty(n) for _ in range(5)]
+        hold = np.zeros(1, np.int32)
+        _lib.check(self.lib.bpmf_hip_diag_cells_mc(query.handle, cand.handle, float(mean_rating), n, _ptr(q if n else hold), _ptr(c if n else hold),
+                                                   int(chains), *[_ptr(a if n else np.zeros(1)) for a in out]))
+        return dict(mean=out[0], std=out[1], rhat=out[2], ess_bulk=out[3], ess_tail=out[4])
 
     def diag_batch_cells(self, cells):
         """Cells per batch of diag_cells (0: automatic, from the size of the trace buffer).  For tests: results do not depend on it."""

@@ -76,33 +76,78 @@ def save_model(res, path):
     """Writes the kept samples of the run `res` = gibbs(...) as a model directory.  The run must have kept the sample rings of both
     sides (save_model=, topn=, foldin= or rank_eval=); the hyper-parameters are stored when both sides kept theirs (save_model= of a
     Gaussian run, foldin=True without features).  The engine of the run must still be open."""
+    write_model(path, _run_model("save_model", res))
+
+
+def _run_model(who, res):
+    """the dict write_model takes, read back from the rings of the run `res`"""
     if not isinstance(res, dict) or "users" not in res or "movies" not in res:
-        raise ValueError("save_model needs the result of gibbs(...)")
+        raise ValueError("%s needs the result of gibbs(...)" % who)
     users, movies = res["users"], res["movies"]
     info = res.get("model_info")
     if info is None:
-        raise ValueError("save_model: the result carries no model_info (it comes from gibbs or load_model)")
+        raise ValueError("%s: the result carries no model_info (it comes from gibbs or load_model)" % who)
     if not info.get("plain", True):
-        raise ValueError("save_model: %s" % info["why"])
+        raise ValueError("%s: %s" % (who, info["why"]))
     engine = users.engine
     S = engine.samples_count(users.side)
     if S < 1 or engine.samples_count(movies.side) != S:
-        raise ValueError("save_model: the run kept no samples of both sides (gibbs(save_model=DIR), or topn / foldin / rank_eval)")
+        raise ValueError("%s: the run kept no samples of both sides (gibbs(save_model=DIR), or topn / foldin / rank_eval)" % who)
     hyper = engine.hyper_count(users.side) == S and engine.hyper_count(movies.side) == S
-    write_model(path, dict(num_latent=engine.K, rows=users.num(), cols=movies.num(), samples=S, mean_rating=movies.mean_rating,
-                           alpha=info["alpha"], probit=info["probit"], probit_threshold=info["probit_threshold"],
-                           dtype=getattr(engine, "dtype", "f64"), U=engine.samples_get(users.side), V=engine.samples_get(movies.side),
-                           U_hyper=engine.hyper_get(users.side) if hyper else None, V_hyper=engine.hyper_get(movies.side) if hyper else None))
+    return dict(num_latent=engine.K, rows=users.num(), cols=movies.num(), samples=S, mean_rating=movies.mean_rating,
+                alpha=info["alpha"], probit=info["probit"], probit_threshold=info["probit_threshold"],
+                dtype=getattr(engine, "dtype", "f64"), U=engine.samples_get(users.side), V=engine.samples_get(movies.side),
+                U_hyper=engine.hyper_get(users.side) if hyper else None, V_hyper=engine.hyper_get(movies.side) if hyper else None)
+
+
+def pool_models(models):
+    """One model from the chains `models`: each the dict of read_model, or a run gibbs(...) that kept its
+    rings.  U, V and the hyper arrays are concatenated along the sample axis in the order given, "samples" counts them all and
+    "chains" says how many chains they are -- everything that reads rings serves the pool as it serves one chain, and
+    bpmf_amd.diagnose takes the multi-chain estimator.  ValueError: chains that differ in shape, num_latent, likelihood, mean rating,
+    dtype, samples or presence of the hyper-parameters; two chains whose first kept sample of U is byte-identical (the same chain
+    twice: gibbs(chain=) or bpmf --chain was forgotten)."""
+    ms = [_run_model("pool_models", m) if not isinstance(m, dict) or "users" in m else m for m in models]   # (a run has "users" and "movies")
+    if not ms:
+        raise ValueError("pool_models: no chain given")
+    first = ms[0]
+    for c, m in enumerate(ms[1:], 1):
+        for key, what in (("rows", "shape"), ("cols", "shape"), ("num_latent", "num_latent"), ("probit", "likelihood"),
+                          ("probit_threshold", "likelihood"), ("mean_rating", "mean rating"), ("dtype", "dtype"), ("samples", "samples")):
+            if m[key] != first[key]:
+                raise ValueError("pool_models: chain %d differs from chain 0 in %s (%s: %r, not %r)" % (c, what, key, m[key], first[key]))
+        if (m["U_hyper"] is None) != (first["U_hyper"] is None) or (m["V_hyper"] is None) != (first["V_hyper"] is None):
+            raise ValueError("pool_models: chain %d differs from chain 0 in the presence of the hyper-parameters" % c)
+    heads = [np.ascontiguousarray(m["U"][:, 0, :], np.float64).tobytes() for m in ms]
+    for c in range(1, len(ms)):
+        if heads[c] in heads[:c]:
+            raise ValueError("pool_models: chain %d has the first kept sample of chain %d, byte for byte: the same chain twice "
+                             "(gibbs(chain=c) / bpmf --chain c makes them differ)" % (c, heads[:c].index(heads[c])))
+    out = dict(first)
+    out["U"] = np.concatenate([np.asarray(m["U"], np.float64) for m in ms], axis=1)
+    out["V"] = np.concatenate([np.asarray(m["V"], np.float64) for m in ms], axis=1)
+    for key in ("U_hyper", "V_hyper"):
+        out[key] = None if first[key] is None else tuple(np.concatenate([np.asarray(m[key][j], np.float64) for m in ms], axis=0) for j in range(3))
+    out["samples"] = first["samples"] * len(ms)
+    out["chains"] = len(ms)
+    return out
 
 
 def load_model(engine, path, M=None):
-    """Loads a model directory into `engine` (its num_latent must be the model's) and returns a dict with "users", "movies" and
+    """Loads a model directory -- or, given a list of directories, the pool of those chains (pool_models, in list order; the dict
+    then has "chains") -- into `engine` (its num_latent must be the model's) and returns a dict with "users", "movies" and
     "foldin" like gibbs's result: bpmf_amd.fold_in, engine.topn, topn_scored, rank_eval, predict_block and bpmf_amd.predict_cells
     work on it unchanged, with res["movies"].mean_rating as the mean rating.  M: the training matrix as gibbs takes it (CSC, one
     column per movie), whose cells the rankings exclude; None: no cell is excluded.  No chain runs."""
+    if isinstance(path, (list, tuple)):
+        return _load(engine, pool_models([read_model(p) for p in path]), M)
+    return _load(engine, read_model(path), M)
+
+
+def _load(engine, m, M=None):
+    """load_model of the dict `m` of read_model / pool_models"""
     from scipy import sparse as sp
     from .sys import Sys
-    m = read_model(path)
     if engine.K != m["num_latent"]:
         raise ValueError("load_model: the engine has num_latent %d, the model %d" % (engine.K, m["num_latent"]))
     rows, cols, S = m["rows"], m["cols"], m["samples"]
@@ -128,7 +173,35 @@ def load_model(engine, path, M=None):
                 engine.hyper_add(sd.side, alpha[s], mu[s], lam[s])
     info = dict(alpha=m["alpha"], probit=m["probit"], probit_threshold=m["probit_threshold"], plain=True, dtype=m["dtype"], samples=S,
                 nu=None, alpha_samples=[float(a) for a in m["U_hyper"][0]] if foldin else None)   # (score_cells: the format stores no nu)
-    return dict(users=users, movies=movies, foldin=foldin, model_info=info)
+    res = dict(users=users, movies=movies, foldin=foldin, model_info=info)
+    if "chains" in m:
+        res["chains"] = int(m["chains"])
+    return res
+
+
+def run_chains(engine, M, Mt, T, nusers, nmovies, chains=4, **gibbs_kwargs):
+    """Runs gibbs(chain=c, keep_rings=True, **gibbs_kwargs) for c = 0 .. chains - 1 one after the other on `engine` and returns the
+    pool (pool_models, loaded as load_model loads it: "users", "movies", "foldin", "model_info", "chains") with "per_chain": per
+    chain dict(chain, rmse, rmse_avg, final_rmse, final_rmse_avg).  What goes with chain= goes here (gibbs's docstring); every chain
+    needs nsims > burnin.  The sides of the single chains are destroyed once their samples are read back."""
+    from .sys import gibbs
+    chains = int(chains)
+    if not 1 <= chains <= 64:
+        raise ValueError("run_chains: chains must be 1 .. 64, not %r" % (chains,))
+    for key in ("chain", "keep_rings"):
+        if key in gibbs_kwargs:
+            raise ValueError("run_chains sets %s itself" % key)
+    models, per_chain = [], []
+    for c in range(chains):
+        r = gibbs(engine, M, Mt, T, nusers, nmovies, chain=c, keep_rings=True, **gibbs_kwargs)
+        models.append(_run_model("run_chains", r))
+        per_chain.append(dict(chain=c, rmse=list(r["rmse"]), rmse_avg=list(r["rmse_avg"]), final_rmse=r.get("final_rmse"),
+                              final_rmse_avg=r.get("final_rmse_avg")))
+        engine.side_destroy(r["users"].side); engine.side_destroy(r["movies"].side)
+    pool = _load(engine, pool_models(models), M)
+    pool["chains"] = chains
+    pool["per_chain"] = per_chain
+    return pool
 
 
 def predict_cells(res, rows, cols, threshold=None):
@@ -159,26 +232,49 @@ def diag_summary(d):
     (cells whose rhat or ess is NaN: a constant trace), samples (d["samples"] if given, else None), ess_min, ess_median,
     rhat_median, rhat_max, rhat_above (the share of cells with rhat > 1.01) and mcse_over_std_median, the median of
     mcse / std = 1 / sqrt(ess) with mcse = std / sqrt(ess) the Monte-Carlo standard error of the mean.  NaNs are left out and
-    counted; without a cell left every figure is NaN."""
-    rhat = np.asarray(d["rhat"], np.float64); ess = np.asarray(d["ess"], np.float64)
+    counted; without a cell left every figure is NaN.
+    The dict of the multi-chain estimator (rhat, ess_bulk, ess_tail: engine.diag_cells_mc, diagnose of a pool or with rank=True;
+    DESIGN.md section 33) gives the same keys with ess = ess_bulk and rhat the rank-normalised one, and adds chains, ess_bulk_min,
+    ess_bulk_median, ess_tail_min, ess_tail_median; a cell with a NaN in any of the three is left out and counted."""
+    mc = "ess_bulk" in d
+    rhat = np.asarray(d["rhat"], np.float64); ess = np.asarray(d["ess_bulk" if mc else "ess"], np.float64)
     ok = ~(np.isnan(rhat) | np.isnan(ess))
+    if mc:
+        tail = np.asarray(d["ess_tail"], np.float64)
+        ok &= ~np.isnan(tail)
     r, e = rhat[ok], ess[ok]
     nan = float("nan")
     have = len(r) > 0
-    return dict(n=int(len(rhat)), n_nan=int(len(rhat) - len(r)), samples=d.get("samples"),
-                ess_min=float(e.min()) if have else nan, ess_median=float(np.median(e)) if have else nan,
-                rhat_median=float(np.median(r)) if have else nan, rhat_max=float(r.max()) if have else nan,
-                rhat_above=float(np.mean(r > 1.01)) if have else nan,
-                mcse_over_std_median=float(np.median(1.0 / np.sqrt(e))) if have else nan)
+    s = dict(n=int(len(rhat)), n_nan=int(len(rhat) - len(r)), samples=d.get("samples"),
+             ess_min=float(e.min()) if have else nan, ess_median=float(np.median(e)) if have else nan,
+             rhat_median=float(np.median(r)) if have else nan, rhat_max=float(r.max()) if have else nan,
+             rhat_above=float(np.mean(r > 1.01)) if have else nan,
+             mcse_over_std_median=float(np.median(1.0 / np.sqrt(e))) if have else nan)
+    if mc:
+        t = tail[ok]
+        s.update(chains=d.get("chains"), ess_bulk_min=s["ess_min"], ess_bulk_median=s["ess_median"],
+                 ess_tail_min=float(t.min()) if have else nan, ess_tail_median=float(np.median(t)) if have else nan)
+    return s
 
 
-def diagnose(res, rows, cols):
+def diagnose(res, rows, cols, rank=None):
     """Convergence diagnostics of the predictions of the cells (rows[i], cols[i]) -- user, movie, 0-based -- over the kept samples of
     `res` (gibbs with the rings kept, or load_model; 8 .. 4096 samples): dict(rows, cols, mean, std, rhat, ess, mcse, samples, summary)
     with mean and std as predict_cells gives them, rhat and ess the split-Rhat and the effective sample size of the cell's trace
-    (DESIGN.md section 29), mcse = std / sqrt(ess) and summary = diag_summary of it."""
+    (DESIGN.md section 29), mcse = std / sqrt(ess) and summary = diag_summary of it.
+    A pool of chains (res["chains"] > 1: run_chains, load_model of a list) or rank=True takes the rank-normalised multi-chain
+    estimator (one chain: C = 1) instead: dict(rows, cols, mean, std, rhat, ess_bulk, ess_tail, mcse, chains,
+    samples, summary) with mcse = std / sqrt(ess_bulk); every chain needs 8 samples or more, all of them 4096 at most."""
     users, movies = res["users"], res["movies"]
     rows = np.ascontiguousarray(rows, np.int32); cols = np.ascontiguousarray(cols, np.int32)
+    chains = int(res.get("chains", 1))
+    if chains > 1 or rank:
+        d = users.engine.diag_cells_mc(users.side, movies.side, movies.mean_rating, rows, cols, chains)
+        d.update(rows=rows, cols=cols, chains=chains, samples=users.engine.samples_count(users.side))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d["mcse"] = d["std"] / np.sqrt(d["ess_bulk"])
+        d["summary"] = diag_summary(d)
+        return d
     d = users.engine.diag_cells(users.side, movies.side, movies.mean_rating, rows, cols)
     d.update(rows=rows, cols=cols, samples=users.engine.samples_count(users.side))
     with np.errstate(invalid="ignore", divide="ignore"):

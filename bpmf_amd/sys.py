@@ -59,6 +59,7 @@ class Sys:
         self.engine = engine
         self.K = engine.K
         self.iter = -1                                    # c++/sample.cpp:113
+        self.key_offset = 0                               # gibbs(chain=c): c * 2^20, added where the host keys random numbers by iter
         self._num = int(num)
         self.nrows = int(nrows)
         self.dom = (0, self._num) if dom is None else (int(dom[0]), int(dom[1]))
@@ -132,9 +133,9 @@ class Sys:
             self._stale = True
             return
         self.iter += 1
-        self.hp.sample(self.num(), self.sum, self.cov, self.iter)          # :349-350
+        self.hp.sample(self.num(), self.sum, self.cov, self.iter + self.key_offset)          # :349-350
         t0 = time.perf_counter()
-        s, prod, norm = self.engine.sample_side(self.side, other.side, self.iter, Sys.alpha, self.hp.mu, self.hp.LambdaF)
+        s, prod, norm = self.engine.sample_side(self.side, other.side, self.iter + self.key_offset, Sys.alpha, self.hp.mu, self.hp.LambdaF)
         if self.comm is not None:
             # exchange the fresh columns (send_item / bcast of the MPI back-ends) and
             # all-reduce sum | prod | norm, then form cov once from the global sums
@@ -193,12 +194,34 @@ class Sys:
             Sys.procid, phase, self.iter, self.rmse, self.rmse_avg, norm_u, norm_m, items_per_sec, ratings_per_sec / 1e6)
 
 
+CHAIN_STRIDE, CHAIN_MAX = 1 << 20, 63
+
+
+def _check_chain(engine, chain, nsims, features, ordinal, bias, bias_prior, implicit):
+    """gibbs(chain=): the chain as an int, or the ValueError of what it does not go together with (before the device is used)"""
+    if isinstance(chain, bool) or not isinstance(chain, (int, np.integer)) or not 0 <= int(chain) <= CHAIN_MAX:
+        raise ValueError("chain must be an integer 0 .. %d, not %r" % (CHAIN_MAX, chain))
+    chain = int(chain)
+    if chain == 0:
+        return 0
+    for on, what in ((features, "features"), (ordinal is not None and ordinal is not False, "ordinal"),
+                     ((bias is not None and bias is not False) or bias_prior is not None, "bias"), (implicit is not None, "implicit"),
+                     (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator"),
+                     (_os.environ.get("BPMF_REDUCE", "0") not in ("", "0"), "BPMF_REDUCE")):
+        if on:
+            raise ValueError("chain=%d does not go together with %s (only chain 0 runs with it)" % (chain, what))
+    if nsims > CHAIN_STRIDE:
+        raise ValueError("chain=%d needs nsims <= %d: the chains' random streams are %d half-iterations apart (nsims = %d)"
+                         % (chain, CHAIN_STRIDE, CHAIN_STRIDE, nsims))
+    return chain
+
+
 def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out=None, keep_samples=False, Tt=None, pipelined=False,
           topn=None, noise="fixed", alpha_prior=(1.0, 1.0), alpha_max=None, probit=False, threshold=0.5,
           row_features=None, col_features=None, lambda_beta=5.0, link_tol=1e-6, link_max_iter=1000, lambda_beta_prior=None, censored=None,
           new_row_features=None, new_col_features=None, topn_score=None, foldin=False, weights=None, robust=None,
           ordinal=None, cutpoints=None, ordinal_step=None, implicit=None, rank_eval=None, rank_by="rows", rank_threshold=None, save_model=None,
-          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False, intervals=None, loo=False):
+          similar=None, similar_by="cols", similar_kind="cosine", similar_kappa=0.0, similar_min_ratings=0, bias=None, bias_prior=None, diagnose=None, score=False, intervals=None, loo=False, chain=0, keep_rings=False):
     """The loop of main() (c++/bpmf.cpp:131-253) in NO_COMM mode.  M / T: CSC
     with one column per movie (rows = users); Mt its transpose.  Returns a dict
     with the per-iteration trace; `out` (a file object) receives the reference's
@@ -398,7 +421,21 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     sampling), khat (the diagnostic that says whether that estimate can be trusted: <= 0.7), lpd, p_loo, and "summary"
     (bpmf_amd.loo_summary: the sum with its standard error, p_loo, looic = -2 elpd_loo, the khat classes).  It replaces WAIC where the
     variance of the log density is large (score's "var > 0.4").  The likelihood is score's; so are the refusals: ordinal, implicit, a
-    communicator, BPMF_REDUCE, fewer than 2 kept samples; and more than 4096.  False (the default): nothing changes."""
+    communicator, BPMF_REDUCE, fewer than 2 kept samples; and more than 4096.  False (the default): nothing changes.
+
+    chain=c (0 .. 63): an independent chain of the same model: the run restarted from the same initial factors
+    with its random numbers taken at the half-iteration indices c * 2^20, c * 2^20 + 1, .. (engine.side_set_chain on both sides; the
+    host-keyed draws, noise="adaptive" among them, get the offset index).  res["chain"] = c.  chain=0 (the default) is the run as it
+    was, bit for bit.  Goes with Gaussian runs at any alpha, noise="adaptive", weights, robust, probit=True and censored, on fp64 and
+    fp32 engines.  Refused before the device is used: features, ordinal, bias, implicit, a communicator, BPMF_REDUCE, nsims > 2^20.
+    bpmf_amd.run_chains runs several and pools them; bpmf_amd.diagnose of the pool is the rank-normalised multi-chain estimator.
+
+    keep_rings=True: the sample rings of both sides and the hyper-parameters are kept as save_model=DIR keeps them, and nothing is
+    written (bpmf_amd.run_chains, bpmf_amd.pool_models read them back).  It is refused where save_model is, under its own name."""
+    keeps_model = save_model is not None or bool(keep_rings)
+    keeps_what = "save_model" if save_model is not None else "keep_rings"
+    chain = _check_chain(engine, chain, nsims, row_features is not None or col_features is not None or new_row_features is not None
+                         or new_col_features is not None, ordinal, bias, bias_prior, implicit)
     loo_on = bool(loo)
     if loo_on:                                       # (refused before the engine is used)
         for on, what, why in ((ordinal is not None and ordinal is not False, "ordinal", "its held-out log density is res['logp']"),
@@ -482,7 +519,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
                               (new_row_features is not None or new_col_features is not None, "new_row_features / new_col_features", "they need features"),
                               (noise == "adaptive", "noise='adaptive'", "the training residuals leave the biases out"),
                               (foldin, "foldin=True", "a folded-in row would need a bias of its own"),
-                              (save_model is not None, "save_model", "the model format stores no biases"),
+                              (keeps_model, "save_model" if save_model is not None else "keep_rings", "the model format stores no biases"),
                               (similar is not None, "similar", "the two bias rows of the sample ring would enter the cosine"),
                               (getattr(engine, "dtype", "f64") == "f32", "an fp32 engine", "the bias kernels are fp64"),
                               (getattr(engine, "comm_nranks", lambda: 1)() > 1, "a communicator", "the bias step needs both sides whole on one GPU")):
@@ -503,13 +540,13 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
             raise ValueError("similar_min_ratings = %r must be an integer >= 0" % (similar_min_ratings,))
         if nsims - burnin < 1:
             raise ValueError("similar needs at least one post-burn-in sample (nsims > burnin)")
-    if save_model is not None:                       # (refused before the engine is used)
+    if keeps_model:                                  # (refused before the engine is used)
         for on, what in ((ordinal is not None and ordinal is not False, "ordinal"), (implicit is not None, "implicit"),
                          (row_features is not None or col_features is not None, "row_features / col_features")):
             if on:
-                raise ValueError("save_model does not go together with %s (serving it would need state that model format 1 does not store)" % what)
+                raise ValueError("%s does not go together with %s (serving it would need state that model format 1 does not store)" % (keeps_what, what))
         if nsims - burnin < 1:
-            raise ValueError("save_model needs at least one post-burn-in sample (nsims > burnin)")
+            raise ValueError("%s needs at least one post-burn-in sample (nsims > burnin)" % keeps_what)
     if implicit is not None:                         # (refused before the engine is used)
         try:
             implicit = float(implicit)
@@ -725,6 +762,9 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
     Sys.nsims, Sys.burnin, Sys.alpha = nsims, burnin, alpha
     movies = Sys("movs", engine, M, nmovies, nusers, T=T, mean_rating=0.0 if probit or ordinal_on or implicit is not None else None)
     users = Sys("users", engine, Mt, nusers, nmovies, T=Tt, mean_rating=0.0 if probit or ordinal_on or implicit is not None else None)
+    if chain:
+        engine.side_set_chain(movies.side, chain); engine.side_set_chain(users.side, chain)
+        movies.key_offset = users.key_offset = chain * CHAIN_STRIDE
     if ordinal_on:
         engine.set_ordinal(movies.side, ord_levels, cutpoints, ORDINAL_TAGS[0])
         engine.set_ordinal(users.side, ord_levels, engine.ordinal_cut_get(movies.side), ORDINAL_TAGS[1])   # (the same bits on both sides)
@@ -768,10 +808,10 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
                     engine.link_lambda_prior(sd.side, lb_a0, lb_b0)
     if Tt is not None:
         movies.set_twin(users)                       # users.predict(movies) rides with movies.predict(users)
-    res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[])
-    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on or loo_on   # a side's sample ring: topn, or the other side's new entities
-    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or save_model is not None or similar is not None or diag_on or score_on or intervals_on or loo_on
-    hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (save_model is not None and not probit)) and F is None]
+    res = dict(rmse=[], rmse_avg=[], norm_u=[], norm_m=[], secs=[], samples=[], chain=chain)
+    ring_movies = topn is not None or new_row_features is not None or foldin or rank_eval is not None or keeps_model or similar is not None or diag_on or score_on or intervals_on or loo_on   # a side's sample ring: topn, or the other side's new entities
+    ring_users = topn is not None or new_col_features is not None or foldin or rank_eval is not None or keeps_model or similar is not None or diag_on or score_on or intervals_on or loo_on
+    hyper_sides = [sd for sd, F in ((users, row_features), (movies, col_features)) if (foldin or (keeps_model and not probit)) and F is None]
     for sd in hyper_sides:
         engine.hyper_reserve(sd.side, nsims - burnin)
     if ring_movies:
@@ -851,7 +891,7 @@ def gibbs(engine, M, Mt, T, nusers, nmovies, nsims=20, burnin=5, alpha=None, out
         sse, n = engine.train_sse(movies.side, users.side)
         res["train_rmse"].append(math.sqrt(sse / n))
         if i + 1 < nsims:
-            Sys.alpha = engine.noise_sample(a0, b0, sse, n, i, alpha_max)
+            Sys.alpha = engine.noise_sample(a0, b0, sse, n, i + chain * CHAIN_STRIDE, alpha_max)
     nnz = movies.local_nnz
 
     def line(it, secs, norm_u, norm_m):

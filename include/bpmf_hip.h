@@ -253,6 +253,20 @@ BPMF_API int bpmf_hip_sample_side_finish(bpmf_hip_side *self, double *sum_out, d
  * call: bpmf_hip_sys_state / the side's next bpmf_hip_sys_sample wait for that collection, and an
  * error of the half-iteration (BPMF_HIP_ECHOL) is reported by whichever of them comes first. */
 BPMF_API int bpmf_hip_sys_sample(bpmf_hip_side *self, bpmf_hip_side *other, double alpha);
+/* Independent chains.  Chain c of a side is the chain restarted from the initial state with its random numbers
+ * taken at the half-iteration indices c * BPMF_HIP_CHAIN_STRIDE, c * BPMF_HIP_CHAIN_STRIDE + 1, ..: wherever bpmf_hip_sys_sample keys
+ * random numbers of the side by the half-iteration index i -- the samplers' streams, the Normal-Wishart draw of the hyper-parameters,
+ * the latent steps of a probit, censored or Student-t side -- it uses i + c * BPMF_HIP_CHAIN_STRIDE.  Everything that counts
+ * half-iterations (bpmf_hip_sys_state, bpmf_hip_sys_norm) keeps the chain's own index 0, 1, ..; the entry points that take `iter`
+ * from the caller (bpmf_hip_sample_side*, bpmf_hip_noise_sample) use what they are given: the caller passes the offset index.
+ * Chain 0, or no call, is the run as it was, bit for bit.  BPMF_HIP_EINVAL with a one-line reason: a chain outside
+ * 0 .. BPMF_HIP_CHAIN_MAX; a side that has taken a half-iteration; a context with a communicator or a shard; a side with features,
+ * ordinal cutpoints, biases, implicit feedback, a tensor mode, propagated priors or BPMF_REDUCE -- whose setters in turn refuse a
+ * side whose chain is not 0.  bpmf_hip_sys_sample refuses two sides of different chains. */
+#define BPMF_HIP_CHAIN_STRIDE (1 << 20)
+#define BPMF_HIP_CHAIN_MAX 63
+BPMF_API int bpmf_hip_side_set_chain(bpmf_hip_side *side, int chain);
+BPMF_API int bpmf_hip_side_chain(const bpmf_hip_side *side);
 /* Sys::iter, Sys::norm, Sys::cov, hp.mu, hp.LambdaF, hp.LambdaU (c++/bpmf.h:86-89,139,222-223);
  * any output pointer may be NULL */
 BPMF_API int bpmf_hip_sys_state(const bpmf_hip_side *side, int *iter, double *norm, double *cov, double *mu,
@@ -489,6 +503,32 @@ BPMF_API int bpmf_hip_diag_cells(bpmf_hip_side *query, bpmf_hip_side *cand, doub
                                  const int32_t *c, double *mean_out, double *std_out, double *rhat_out, double *ess_out);
 BPMF_API int bpmf_hip_diag_batch_cells(int cells);
 BPMF_API int bpmf_hip_diag_last_ms(const bpmf_hip_side *query, float *ms);
+
+/* ---- convergence diagnostics over several chains: rank-normalised split-Rhat, bulk and tail ESS ----
+ * (Vehtari, Gelman, Simpson, Carpenter & Buerkner 2021.)  A trace is C * S doubles, chain-major: chain c is
+ * x[c S, (c + 1) S), chronological inside; 1 <= C <= 64, S >= 8, C S <= BPMF_HIP_DIAG_MAX_SAMPLES.  With n = floor(S / 2) every chain
+ * gives the half-chains x_c[0, n) and x_c[S - n, S): M = 2C half-chains, N = M n kept values.  est(y) is the estimator of the section
+ * above with the two halves generalised to M half-chains: c(t) = (1 / N) sum over the half-chains of sum_i d_i d_{i+t},
+ * W = c(0) n / (n - 1), var+ = c(0) + sum_h (m_h - mbar)^2 / (M - 1), tau = max(-1 + 2 sum_k P_k, 1 / log10 N), ess = N / tau.
+ * z(y) replaces every value by the normal score of its rank among the N (average ranks for values that compare equal):
+ * z = -+ sqrt 2 erfcinv((2a - 0.75) / (N + 0.25)), a = min(r, N + 1 - r).
+ *     rhat     = max(est(z(x)).rhat, est(z(|x - med|)).rhat), med the mean of the two middle order statistics
+ *     ess_bulk = est(z(x)).ess
+ *     ess_tail = min over p in {0.05, 0.95} of est(1[x <= x_(floor((N - 1) p) + 1)]).ess
+ * An est with W not > 0 gives NaN for what depends on it (a constant trace, chains that are each constant, a tail indicator that is
+ * constant in every half-chain); a value that is not finite anywhere in the trace gives NaN for all three, for that trace alone.
+ * All fp64, also on fp32 contexts; the bits of a trace depend on the trace alone.
+ * bpmf_hip_diag_traces_mc: n >= 0 traces, row-major on the host.  BPMF_HIP_EINVAL: C or S outside the ranges, a NULL argument.
+ * bpmf_hip_diag_cells_mc: as bpmf_hip_diag_cells over two rings that hold exactly C S samples in chain-major order (what
+ * bpmf_hip_samples_set of C chains one after the other leaves); its refusals, C and S outside the ranges, and a number of samples
+ * that C does not divide.  mean_out and std_out are those of bpmf_hip_predict_cells, bit for bit.  bpmf_hip_diag_batch_cells and
+ * bpmf_hip_diag_last_ms serve it as they serve bpmf_hip_diag_cells.  Waits. */
+#define BPMF_HIP_DIAG_MAX_CHAINS 64
+BPMF_API int bpmf_hip_diag_traces_mc(bpmf_hip_ctx *ctx, int64_t n, int C, int S, const double *traces, double *rhat, double *ess_bulk,
+                                     double *ess_tail);
+BPMF_API int bpmf_hip_diag_cells_mc(bpmf_hip_side *query, bpmf_hip_side *cand, double mean_rating, int64_t n, const int32_t *q,
+                                    const int32_t *c, int C, double *mean_out, double *std_out, double *rhat_out, double *ess_bulk_out,
+                                    double *ess_tail_out);
 
 /* ---- model comparison: log pointwise predictive density and WAIC ----
  *   For the observed cell i = (q[i], c[i]) with the value y[i], over the S samples both rings hold, with
